@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- ranked (query,doc) pairs/sec of the encode-and-rank hot path on N MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
 
 N > 1: launched by torch.distributed.run (one rank per GPU; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) -- or plainly, in
 which case bench.py starts the N ranks itself.  A world that is not --gpus is refused; n_gpus of the line = an all-reduce of ones.
@@ -9,15 +9,19 @@ which case bench.py starts the N ranks itself.  A world that is not --gpus is re
 OUTPUT.  The LAST line of stdout is ONE compact JSON object (~2.5 KB): metric / value / unit / n_gpus / steps / warmup / reps / ms_per_step /
 scaling / dtype / data, `config`, `roofline`, `cpu_baseline` and one four-scalar entry per sub-record in `sub`.  The full records (every
 sub-record's roofline block, per-kernel microseconds, precompute, H2D stream) go to bench_detail.json (`config.detail`).  stderr of a successful
-run is EMPTY: file descriptor 2 points at bench_stderr.<rank>.log for the length of the run and is replayed only on failure.  At N > 1 the
-headline is printed as a complete record before the sub-records run; the final line supersedes it.
+run is EMPTY: file descriptor 2 points at bench_stderr.<rank>.log for the length of the run and is replayed only on failure.  Both files are
+written in the repository root (BENCH_LOG_DIR overrides it), or, where the running user cannot write there, in a per-user directory under the
+system temporary directory (log_path).  At N > 1 the headline is printed as a complete record before the sub-records run; the final line
+supersedes it.
 
 HEADLINE: BASELINE.json configs[2], the largest configuration BASELINE marks 1 x MI355X -- CARS multitask, 16 sessions x session_len 7 x 10
 candidates, q_len 4, doc_len 64, emb_dim 300, fp32, synthetic MSMARCO-shaped ids (Zipf over a 100 000 x 300 table, seed 1013), full-length
 sequences.  A "step" = Multitask.predict's ranking path on one batch already resident in HBM: encode + rank_document + softmax over the
 candidates (the suggestion decoder is not a ranking step; sub-record C3_cars_with_decode times the full predict).  Steps are replayed as
 hipGraphs over resident macro-batches (8 batches per replay at C3, 4 lanes); EXACTLY --steps steps are timed between barrier + synchronize,
-max over ranks; a region shorter than 0.25 s is repeated and the median reported (`reps`).
+max over ranks; a region shorter than 0.25 s is repeated and the median reported (`reps`).  --dump-outputs DIR: after the timed region, the
+probabilities of the last timed step are written to DIR/click_scores.npy (session models, [B,S,N]) or DIR/scores.npy (rankers, [B,N]), float32;
+the inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 
 SUB-RECORDS (N = 1): C1 ESM 8x5, C2 MatchTensor 32x10, the north-star 32x50 MatchTensor shape, C4 DUET and DRMM 64x50xdoc_len 290 (DRMM / ESM
 with uniform ids over a 1M-row table so the gather really comes from HBM; DRMM with its histogram gap on overlapping ids), the C5 shape (CARS
@@ -43,13 +47,6 @@ import os
 import re
 import sys
 import time
-
-# The ROCm runtime multiplexes HIP streams onto GPU_MAX_HW_QUEUES hardware queues (default 4).  With 4 batches in
-# flight plus torch's own streams that leaves no spare queue and lanes serialise behind each other (measured: 2.35 M
-# pairs/s at 4 queues, 3.13 M at 8 on C2).  Must be set before the HIP runtime initialises, i.e. before `import torch`.
-if not ("--streams" in sys.argv and sys.argv[sys.argv.index("--streams") + 1:][:1] == ["1"]):
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-os.environ.setdefault("DEBUG_HIP_FORCE_GRAPH_QUEUES", "8")     # streams the runtime spreads the parallel branches of ONE hipGraph over
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -250,6 +247,9 @@ def parse():
     ap.add_argument("--no-graph", action="store_true", help="do not replay the step from a captured hipGraph")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps of the headline, write the probabilities its LAST timed step computed to DIR/<name>.npy (float32): "
+                    "click_scores [B,S,N] for the session models, scores [B,N] for the rankers")
     return ap.parse_args()
 
 
@@ -445,8 +445,8 @@ def _phase(name, what):
             f.write("%s: %s\n" % (name, what))
 
 
-def run_config(name, c, args, env, steps, warmup, shard, want_cpu=False, with_h2d=False, axis=None, kg=None):
-    """Time one workload; returns the record dict (rank 0) or None."""
+def run_config(name, c, args, env, steps, warmup, shard, want_cpu=False, with_h2d=False, axis=None, kg=None, dump=None):
+    """Time one workload; returns the record dict (rank 0) or None.  dump: directory for the outputs of the last timed step (write_outputs)."""
     _phase(name, "start")
     L = lib.load()
     dev, world, rank = env.dev, env.world, env.rank
@@ -806,6 +806,8 @@ def run_config(name, c, args, env, steps, warmup, shard, want_cpu=False, with_h2
                 out = forward(i)
             return finish(out)
 
+    final = {"step": None}     # -> the output tensor of the last step run_steps issued (what a caller of that step receives; --dump-outputs)
+
     def run_steps(n):
         """exactly n steps: pipelined segments (sharded CARS), fused groups of KSTEP (+ one remainder group) on one stream, else one
         replay / eager call per step."""
@@ -821,6 +823,8 @@ def run_config(name, c, args, env, steps, warmup, shard, want_cpu=False, with_h2
                     g.replay()
                     if allg is not None:
                         env.dist.all_gather_into_tensor(allg.view(-1, *mine.shape[1:]), mine)     # [G*k, bper, S, N] <- [k, bper, S, N]
+                # step k-1 of the group: this rank's block of the macro-batch, or every rank's sessions of it from the all-gather
+                final["step"] = (lambda m=mine, a=allg, j=k - 1: m[j] if a is None else a[:, j].reshape(-1, *m.shape[2:])[:c["batch"]])
                 gi += 1
                 left -= k
             stages["pos"] = gi
@@ -842,19 +846,24 @@ def run_config(name, c, args, env, steps, warmup, shard, want_cpu=False, with_h2
                     G[((b + nl) % nb, "flush")].replay()
                     stages["exchange"](ln)
             stages["pos"] = start + n
+            final["step"] = None      # (the probabilities live in the pipelines' exchange buffers: not dumped)
             return
         if fused is None:
+            out = None
             for i in range(n):
-                run(i)
+                out = run(i)
+            final["step"] = lambda o=out: o
             return
         with torch.cuda.stream(lanes[0]):
             for k in range(n // KSTEP):
                 fused["full"][k % 2][0].replay()
+                final["step"] = lambda o=fused["full"][k % 2][1][-1]: o
             rem = n % KSTEP
             if rem:
                 if rem not in fused["rem"]:
                     fused["rem"][rem] = fused["capture"](2 * KSTEP, rem)
                 fused["rem"][rem][0].replay()
+                final["step"] = lambda o=fused["rem"][rem][1][-1]: o
 
     def rewind():
         """every call pattern starts from the same group position: the remainder groups captured in the dry run are the ones the timed
@@ -872,6 +881,9 @@ def run_config(name, c, args, env, steps, warmup, shard, want_cpu=False, with_h2
             fused["rem"][n] = fused["capture"](2 * KSTEP, n)
     rewind()
     run_steps(max(warmup, 1))
+
+    if dump and stages is not None and "aligned" not in stages:      # (every rank takes this exit: the arguments are the same on all of them)
+        raise SystemExit("bench.py: --dump-outputs is not available on the software-pipelined candidate-axis path of %s" % name)
 
     _phase(name, "timed region")
     def timed_region():
@@ -902,6 +914,9 @@ def run_config(name, c, args, env, steps, warmup, shard, want_cpu=False, with_h2
     value = per_step_pairs * steps / elapsed
     ms_per_step = elapsed / steps * 1e3
     spread = (round(min(samples) / steps * 1e3, 5), round(max(samples) / steps * 1e3, 5))
+    if dump and rank == 0:           # every repetition replays the same steps: the buffers hold the last timed step's result
+        probs = final["step"]().reshape(c["batch"], *((c["session"],) if is_sess else ()), ncand)
+        write_outputs(dump, {"click_scores" if is_sess else "scores": probs})
     power = None
     if rank == 0 and not env.multi and not adhoc_power_off:        # every N = 1 record: which configurations run at the package power cap
         def busy():
@@ -1319,13 +1334,28 @@ def self_launch(args):
         sys.stderr.write(p.stderr.decode(errors="replace")[-6000:])
     else:
         try:
-            open(os.path.join(LOG_DIR, "bench_launcher.log"), "wb").write(p.stderr)
+            open(log_path("bench_launcher.log"), "wb").write(p.stderr)
         except OSError:
             pass
     raise SystemExit(p.returncode)
 
 
 LOG_DIR = os.environ.get("BENCH_LOG_DIR", ROOT)
+
+
+def log_path(name):
+    """<LOG_DIR>/<name> when the running user may write it there, else <name> in a per-user directory under the system temporary directory
+    (the same path for the launcher and every rank): a checkout that is read-only for the user, or holds another user's file of an earlier
+    run, is still benchmarked."""
+    path = os.path.join(LOG_DIR, name)
+    if os.access(path, os.W_OK) if os.path.exists(path) else os.access(LOG_DIR, os.W_OK):
+        return path
+    import tempfile
+    d = os.path.join(tempfile.gettempdir(), "context_attentive_ir_bench.%d" % os.getuid())
+    os.makedirs(d, exist_ok=True)
+    return os.path.join(d, name)
+
+
 OVERLAP_TOL = 1e-5      # max |concurrent - serial| of one captured graph's output above which a record FAILS
 ROOF_KEYS = ("kernel", "avg_us", "launches_per_step", "bound", "achieved", "peak", "unit", "frac", "hbm_frac_8d", "traffic", "traffic_ratio",
              "mfma_busy_pmc", "step_hbm_GBps_8d")
@@ -1363,7 +1393,7 @@ def main():
     args = parse()
     launcher = args.gpus > 1 and "WORLD_SIZE" not in os.environ
     # (the redirect starts BEFORE the HIP runtime initialises: libdrm's "amdgpu.ids: No such file" line is stderr noise of every run on this image)
-    with QuietStderr(os.path.join(LOG_DIR, "bench_stderr.%s.log" % ("launcher" if launcher else "rank%d" % int(os.environ.get("RANK", "0"))))):
+    with QuietStderr(log_path("bench_stderr.%s.log" % ("launcher" if launcher else "rank%d" % int(os.environ.get("RANK", "0"))))):
         if not torch.cuda.is_available():
             raise SystemExit("bench.py needs a ROCm GPU (the HIP path has no CPU fallback)")
         if launcher:
@@ -1394,6 +1424,8 @@ def run_records(args, env):
         k, v = kv.split("=")
         lib.check(lib.load().nir_debug_set_tunable(k.encode(), int(v)), "nir_debug_set_tunable")
     if args.config == "C5_stream":
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs is not available for --config C5_stream")
         r = stream_record(args, env, seconds=None)
         if env.rank != 0:
             return None
@@ -1413,7 +1445,7 @@ def run_records(args, env):
     if head["model"] in SESSION_MODELS:
         head.setdefault("session", 7)
     hname = args.config if not adhoc else "adhoc_" + head["model"]
-    rec = run_config(hname, head, args, env, args.steps, args.warmup, shard=True, want_cpu=True, with_h2d=True)
+    rec = run_config(hname, head, args, env, args.steps, args.warmup, shard=True, want_cpu=True, with_h2d=True, dump=args.dump_outputs)
     if env.multi and env.world > 1 and env.rank == 0:
         # N > 1: a rank that fails inside a sub-record must take the job down (the others would hang in its collectives) -- so the headline is
         # printed NOW as a complete record of its own; the final line (with the sub-records) supersedes it as the last line of stdout
@@ -1549,13 +1581,31 @@ def compose_line(args, env, rec, sub, weak):
     return json.dumps(line, separators=(",", ":"))
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every tensor as <path>/<name>.npy, float32 (float64 stays float64), at most DUMP_MAX_BYTES in all.  An array larger
+    than its share of that is written as a fixed sample: the elements at the first n positions of a seed-0 permutation of its flattened
+    index, in that order (the same positions for every build of the same shape)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        a = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+        if a.nbytes > share:
+            a = a.reshape(-1)[np.random.default_rng(0).permutation(a.size)[:share // a.itemsize]]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 def write_detail(obj):
     """the full records (every sub-record with its roofline block, per-kernel microseconds, precompute, H2D stream) -> bench_detail.json"""
-    path = os.environ.get("BENCH_DETAIL", os.path.join(LOG_DIR, "bench_detail.json"))
+    path = os.environ.get("BENCH_DETAIL") or log_path("bench_detail.json")
     try:
         with open(path, "w") as f:
             json.dump(obj, f, indent=1, default=str)
-        return os.path.relpath(path, ROOT)
+        rel = os.path.relpath(path, ROOT)
+        return path if rel.startswith("..") else rel          # (outside the checkout: the absolute path)
     except OSError:
         return None
 

@@ -46,6 +46,53 @@ def test_bench_single_gpu_line():
     assert full["sub"]["C1_esm"]["roofline"]["kernel"] and full["headline"]["roofline"]["kernels_us_per_step"]
 
 
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the click probabilities of the LAST timed step as DIR/click_scores.npy (float32 [B,S,N]).  12 steps over the resident
+    C3 batches (macro-batches of 8: batches 0-7, then 8-11) end on batch 11, so the file equals Multitask.predict of that batch, rebuilt here from
+    the same seeds; the line's `steps` is the argument."""
+    import numpy as np
+    from context_attentive_ir_amd import synth
+    from context_attentive_ir_amd.config import default_args
+    from context_attentive_ir_amd.detinit import fill_module_
+    from context_attentive_ir_amd.wrappers import Multitask
+    env = dict(os.environ, BENCH_NO_H2D="1", BENCH_NO_POWER="1")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--sub", "none", "--no-cpu-baseline",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = _last_json(out.stdout)
+    assert d["steps"] == 12 and d["ms_per_step"] > 0 and d["config"]["macro_batch"] == 8
+    got = np.load(os.path.join(str(tmp_path), "click_scores.npy"))
+    assert got.dtype == np.float32 and got.shape == (16, 7, 10)
+    V = 100000
+    mt = Multitask(default_args("CARS", src_vocab_size=V))
+    fill_module_(mt.network, 1013)
+    mt.cuda()
+    mt.network.eval()
+    ex = synth.session_batch(16, 7, 10, 4, 64, V, 1013 + 7919 * 11)
+    want = mt.predict({k: v.cuda() for k, v in ex.items()}, suggest=False)["click_scores"].cpu().numpy()
+    assert float(np.abs(got - want).max()) < 1e-5
+
+
+def test_bench_runs_where_its_log_directory_is_read_only(tmp_path):
+    """a checkout the benchmarking user cannot write to (here the log directory, BENCH_LOG_DIR, made read-only): the stderr log and the detail
+    file go to a per-user directory under the system temporary directory, and the run prints its line as usual."""
+    ro = tmp_path / "ro"
+    ro.mkdir()
+    ro.chmod(0o555)
+    try:
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--sub", "none", "--no-cpu-baseline"],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ, BENCH_LOG_DIR=str(ro), BENCH_NO_H2D="1"))
+        written = os.listdir(str(ro))
+    finally:
+        ro.chmod(0o755)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = _last_json(out.stdout)
+    assert d["steps"] == 12 and d["value"] > 0
+    assert _detail(d)["headline"]["steps"] == 12
+    if os.getuid() != 0:                     # (root may write anywhere)
+        assert written == [] and os.path.isabs(d["config"]["detail"])
+
+
 def test_bench_gpus_2_launches_two_ranks_by_itself():
     """plain `python bench.py --gpus 2` (no launcher around it): bench.py starts the two ranks itself (both on the one GPU, BENCH_BACKEND=gloo)
     and n_gpus is what the process group counted; with the RCCL backend and one visible device it refuses instead of measuring one GPU."""
@@ -142,18 +189,20 @@ def test_stream_device_gather_over_one_rank_rccl_group():
 
 
 @pytest.mark.parametrize("axis,emulate", [("auto", "1"), ("candidate", "4"), ("pair", "8")])
-def test_bench_rccl_sharded_step_is_graph_replayed(axis, emulate):
+def test_bench_rccl_sharded_step_is_graph_replayed(axis, emulate, tmp_path):
     """The RCCL path of the sharded CARS step over a real (1-rank) RCCL process group (BENCH_FORCE_DIST; BENCH_EMULATE_WORLD gives this
     process rank 0's share of a larger world): hipGraph replays around eager collectives -- pair axis: one graph + the all-gather of the
     probabilities; candidate axis: the software-pipelined segment graphs + ONE all-to-all per step."""
-    env = dict(os.environ, BENCH_FORCE_DIST="1", MASTER_PORT="29553", BENCH_SHARD_AXIS=axis, BENCH_EMULATE_WORLD=emulate, BENCH_NO_H2D="1")
+    env = dict(os.environ, BENCH_FORCE_DIST="1", MASTER_PORT="29553", BENCH_SHARD_AXIS=axis, BENCH_EMULATE_WORLD=emulate, BENCH_NO_H2D="1",
+               BENCH_LOG_DIR=str(tmp_path))
+    log = os.path.join(str(tmp_path), "bench_stderr.rank0.log")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "5", "--sub", "none", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     if out.returncode < 0:       # killed by a signal (seen once in round 5: SIGABRT with an empty log, not reproduced on the next box): one retry, log kept
-        print("bench.py died with signal %d; rank log tail:\n%s" % (-out.returncode, open(os.path.join(ROOT, "bench_stderr.rank0.log")).read()[-2000:]))
+        print("bench.py died with signal %d; rank log tail:\n%s" % (-out.returncode, open(log).read()[-2000:]))
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
-    assert out.returncode == 0, (out.stderr[-2000:], open(os.path.join(ROOT, "bench_stderr.rank0.log")).read()[-2000:])
-    assert "graph capture unavailable" not in open(os.path.join(ROOT, "bench_stderr.rank0.log")).read()
+    assert out.returncode == 0, (out.stderr[-2000:], open(log).read()[-2000:])
+    assert "graph capture unavailable" not in open(log).read()
     d = _last_json(out.stdout)
     assert d["scaling"] == "strong" and d["config"]["hipgraph"] is True and d["value"] > 0
     assert ("pair axis" in d["config"]["parallelism"]) == (axis != "candidate")

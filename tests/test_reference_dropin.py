@@ -1,100 +1,96 @@
-"""Drop-in check against the REAL reference wrappers (authoring container only: /root/reference is not on the GPU box).
+"""Drop-in check against the reference wrappers' contract, recorded from the REAL reference (tests/golden/reference_dropin.npz, written by
+tests/golden/generate.py): the state-dict keys and shapes, parameter counts and vocabularies of the reference's own networks at these
+arguments, the arch hyper-parameters of its `hyparam`, the failure of its CARS forward with unequal encoder sizes, and its `tens2sen` output.
 
-The reference's own `neuroir.models.ranker.Ranker` / `neuroir.models.multitask.Multitask` are constructed with this package's
-network classes monkey-patched in (the two import lines a maintainer changes) and everything the
-drivers main/ranker.py / main/multitask.py do with a model object is exercised up to the kernel launch: construction from
-`config.get_model_args`, state-dict key identity with the reference's own networks, load_embeddings, init_optimizer
-(fix_embeddings freezes `network.word_embeddings` / `network.embedder.word_embeddings`), save -> load, checkpoint ->
-load_checkpoint.  predict/update on CPU tensors must fail loudly (no CPU fallback)."""
+Everything the drivers main/ranker.py / main/multitask.py do with a model object is exercised on this package's wrappers, which take the
+reference wrappers' place: construction from the arguments `config.get_model_args` builds, state-dict key and
+shape identity with the reference's own networks (its `load_state_dict` is strict), count_parameters, load_embeddings, init_optimizer
+(fix_embeddings freezes `network.word_embeddings` / `network.embedder.word_embeddings`), save -> load, checkpoint -> load_checkpoint.
+predict on CPU tensors must fail loudly (no CPU fallback)."""
+import json
 import os
-import sys
-import types
 from argparse import Namespace
 
 import numpy as np
 import pytest
 import torch
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference is only present in the authoring container")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_dropin.npz")
+
+
+class Vocab(object):
+    """The part of the reference's Vocabulary the wrappers use (len, `in`, id <-> token, ind2tok), over a recorded id -> token list."""
+
+    def __init__(self, ind2tok):
+        self.ind2tok = dict(enumerate(ind2tok))
+        self.tok2ind = {t: i for i, t in enumerate(ind2tok)}
+
+    def __len__(self):
+        return len(self.ind2tok)
+
+    def __contains__(self, key):
+        return key in (self.ind2tok if isinstance(key, int) else self.tok2ind)
+
+    def __getitem__(self, key):
+        return self.ind2tok[key] if isinstance(key, int) else self.tok2ind[key]
 
 
 @pytest.fixture(scope="module")
 def ref():
-    sys.path.insert(0, REF)
-    pt = types.ModuleType("prettytable")
-
-    class _PT(object):
-        def __init__(self, *a, **k):
-            self.field_names, self.align = [], {}
-
-        def add_row(self, *a, **k):
-            pass
-
-    pt.PrettyTable = _PT
-    sys.modules.setdefault("prettytable", pt)
-    if not hasattr(np, "float_"):
-        np.float_ = np.float64
-    orig_load = torch.load                        # SURVEY Appendix D shim 5: the reference pickles Namespace / Vocabulary objects
-
-    def _load(*a, **k):
-        k.setdefault("weights_only", False)
-        return orig_load(*a, **k)
-
-    torch.load = _load
-    import neuroir.models.multitask as rm
-    import neuroir.models.ranker as rr
-    from neuroir import hyparam
-    from neuroir.inputters.vocabulary import Vocabulary
-    yield types.SimpleNamespace(rr=rr, rm=rm, hyparam=hyparam, Vocabulary=Vocabulary)
-    torch.load = orig_load
-    sys.path.remove(REF)
-
-
-def _vocab(ref, n):
-    v = ref.Vocabulary()
-    for i in range(n):
-        v.add("tok%d" % i)
-    return v
+    z = np.load(GOLDEN)
+    g = {k: z[k] for k in z.files}
+    return Namespace(g=g, arch=json.loads(str(g["arch_json"])), src=Vocab([str(t) for t in g["src_ind2tok"]]),
+                     tgt=Vocab([str(t) for t in g["tgt_ind2tok"]]))
 
 
 def _args(ref, model, **kw):
     a = dict(emsize=300, dropout_emb=0.2, dropout=0.2, dropout_rnn=0.2, max_doc_len=20, max_query_len=6, num_candidates=4,
              use_word=True, fix_embeddings=True, model_type=model, optimizer="adam", learning_rate=0.001, weight_decay=0,
              momentum=0, grad_clipping=10)
-    a.update(ref.hyparam.get_model_specific_params(model, "arch"))
+    a.update(ref.arch[model])
     a.update(kw)
     return Namespace(**a)
 
 
+def _shapes(net):
+    return {k: ",".join(str(d) for d in v.shape) for k, v in net.state_dict().items()}
+
+
+def _ref_shapes(ref, prefix):
+    return dict(zip((str(k) for k in ref.g[prefix + "_keys"]), (str(s) for s in ref.g[prefix + "_shapes"])))
+
+
+def test_arch_hyperparameters_are_the_reference_ones(ref):
+    from context_attentive_ir_amd import config
+    for model, params in ref.arch.items():
+        assert config.get_model_specific_params(model, "arch") == params, model
+
+
 @pytest.mark.parametrize("model,attr", [("ESM", "ESM"), ("MATCH_TENSOR", "MatchTensor"), ("DRMM", "DRMM"), ("DUET", "DUET")])
-def test_reference_ranker_with_swapped_network(ref, model, attr, monkeypatch, tmp_path):
+def test_reference_ranker_with_swapped_network(ref, model, attr, tmp_path):
     from context_attentive_ir_amd import rankers
-    vocab = _vocab(ref, 40)
-    own = ref.rr.Ranker(_args(ref, model), vocab)                       # the reference's own network: the key set to match
-    ref_keys = {k: tuple(v.shape) for k, v in own.network.state_dict().items()}
-    monkeypatch.setattr(ref.rr, attr, getattr(rankers, attr))
-    m = ref.rr.Ranker(_args(ref, model), vocab)
-    assert type(m.network).__module__.startswith("context_attentive_ir_amd")
-    assert {k: tuple(v.shape) for k, v in m.network.state_dict().items()} == ref_keys
-    assert m.count_parameters() == own.count_parameters()
-    # load_embeddings -> init_word_vectors on the swapped network's word_embeddings
+    from context_attentive_ir_amd.wrappers import Ranker
+    vocab = ref.src
+    m = Ranker(_args(ref, model), vocab)
+    assert type(m.network) is getattr(rankers, attr)
+    assert _shapes(m.network) == _ref_shapes(ref, model)               # the reference's own network: the key set to match
+    assert m.count_parameters() == int(ref.g[model + "_count"])
+    # load_embeddings -> init_word_vectors on the network's word_embeddings
     emb = tmp_path / "emb.txt"
     emb.write_text("\n".join("tok%d %s" % (i, " ".join(["%.3f" % (0.01 * i)] * 300)) for i in range(5)))
     m.load_embeddings(["tok%d" % i for i in range(5)], str(emb))
     row = m.network.word_embeddings.table[vocab["tok3"]]
     assert torch.allclose(row, torch.full((300,), 0.03), atol=1e-6)
     if model != "ESM":
-        m.init_optimizer()
+        m.init_optimizer(use_gpu=False)
         assert all(not p.requires_grad for p in m.network.word_embeddings.parameters())
         m.checkpoint(str(tmp_path / "c.mdl"), 3)
-        m2, epoch = ref.rr.Ranker.load_checkpoint(str(tmp_path / "c.mdl"), use_gpu=False)
+        m2, epoch = Ranker.load_checkpoint(str(tmp_path / "c.mdl"), use_gpu=False)
         assert epoch == 3 and type(m2.network) is type(m.network)
     m.save(str(tmp_path / "m.mdl"))
-    m3 = ref.rr.Ranker.load(str(tmp_path / "m.mdl"))
+    m3 = Ranker.load(str(tmp_path / "m.mdl"))
     for k, v in m.network.state_dict().items():
         assert torch.equal(v, m3.network.state_dict()[k])
-    own.network.load_state_dict(m.network.state_dict())                 # and the reference's own class loads our weights strictly
     ex = dict(que_rep=torch.zeros(2, 6, dtype=torch.long), que_len=torch.full((2,), 6), doc_rep=torch.zeros(2, 4, 20, dtype=torch.long),
               doc_len=torch.full((2, 4), 20), label=torch.zeros(2, 4))
     with pytest.raises(RuntimeError, match="no CPU fallback"):
@@ -102,21 +98,19 @@ def test_reference_ranker_with_swapped_network(ref, model, attr, monkeypatch, tm
 
 
 @pytest.mark.parametrize("kw", [{}, dict(query_session_off=True), dict(doc_session_off=True)])
-def test_reference_multitask_with_swapped_cars(ref, kw, monkeypatch, tmp_path):
+def test_reference_multitask_with_swapped_cars(ref, kw, tmp_path):
     from context_attentive_ir_amd.multitask import CARS
-    src, tgt = _vocab(ref, 40), _vocab(ref, 30)
-    own = ref.rm.Multitask(_args(ref, "CARS", **kw), src, tgt)
-    ref_keys = {k: tuple(v.shape) for k, v in own.network.state_dict().items()}
-    monkeypatch.setattr(ref.rm, "CARS", CARS)
-    m = ref.rm.Multitask(_args(ref, "CARS", **kw), src, tgt)
+    from context_attentive_ir_amd.wrappers import Multitask
+    m = Multitask(_args(ref, "CARS", **kw), ref.src, ref.tgt)
     assert type(m.network) is CARS
-    assert {k: tuple(v.shape) for k, v in m.network.state_dict().items()} == ref_keys
-    m.init_optimizer()
+    assert _shapes(m.network) == _ref_shapes(ref, "cars_" + (next(iter(kw)) if kw else "default"))
+    m.init_optimizer(use_gpu=False)
     assert all(not p.requires_grad for p in m.network.embedder.word_embeddings.parameters())
     m.save(str(tmp_path / "m.mdl"))
-    m2 = ref.rm.Multitask.load(str(tmp_path / "m.mdl"))
+    m2 = Multitask.load(str(tmp_path / "m.mdl"))
     assert type(m2.network) is CARS
-    own.network.load_state_dict(m.network.state_dict())
+    for k, v in m.network.state_dict().items():
+        assert torch.equal(v, m2.network.state_dict()[k])
     # every attribute / method Multitask.predict touches on the network exists with the reference's signature
     for name in ("encode", "rank_document", "decode", "forward", "embedder"):
         assert hasattr(m.network, name)
@@ -127,55 +121,39 @@ def test_reference_multitask_with_swapped_cars(ref, kw, monkeypatch, tmp_path):
         m.predict(ex)
 
 
-def test_reference_cars_itself_fails_with_unequal_encoder_sizes(ref, monkeypatch):
+def test_reference_cars_itself_fails_with_unequal_encoder_sizes(ref):
     """`multitask/cars.py` of this package refuses nhid_query != nhid_document.  That mirrors the reference: its session loop multiplies
     session_doc_attn(states) [B, k, nhid_document] with the pooled QUERY [B, nhid_query, 1] (cars.py:357-360), so with the document-session
-    encoder and the ranker on (every hyparam configuration) its own forward raises for unequal sizes -- reproduced here against the real class."""
-    from neuroir.multitask.cars import CARS as RefCARS
-    from context_attentive_ir_amd import synth
-    orig_mf = torch.Tensor.masked_fill_                       # SURVEY Appendix D shim: the reference masks with uint8 tensors
-    monkeypatch.setattr(torch.Tensor, "masked_fill_", lambda self, mask, value: orig_mf(self, mask.bool() if mask.dtype == torch.uint8 else mask, value))
+    encoder and the ranker on (every hyparam configuration) its own forward raises for unequal sizes -- recorded from the real class at these
+    sizes, next to the finite ranking loss it gives for the same inputs with equal sizes."""
     from context_attentive_ir_amd.multitask import CARS
-    kw = dict(src_vocab_size=60, tgt_vocab_size=60, nhid_query=16, nhid_document=24, nhid_session_query=8, nhid_session_document=8, nhid_decoder=8,
-              emsize=12, max_query_len=4)
-    a = _args(ref, "CARS", **kw)
-    net = RefCARS(a)
-    net.eval()
-    ex = synth.session_batch(2, 3, 3, 4, 6, 60, seed=1)
-    tgt = torch.ones(2, 2, 5, dtype=torch.long)                    # [B, S-1, TL]: the next query of every step but the last
-    call = lambda n: n(ex["source_words"], ex["source_lens"], tgt, torch.full((2, 2), 5), tgt, ex["document_words"], ex["document_lens"],      # noqa: E731
-                       ex["document_labels"])
-    with pytest.raises(RuntimeError, match="batch2"):                     # the bmm of cars.py:361 inside the reference's encode_session
-        call(net)
-    ok = RefCARS(_args(ref, "CARS", **dict(kw, nhid_document=16)))       # the same inputs with equal sizes go through: the failure is the size mismatch
-    ok.eval()
-    assert torch.isfinite(call(ok)["ranking_loss"])
+    kw = json.loads(str(ref.g["cars_unequal_kw_json"]))
+    assert kw["nhid_query"] != kw["nhid_document"]
+    assert "batch2" in str(ref.g["cars_unequal_error"])                         # the bmm of cars.py:361 inside the reference's encode_session
+    assert np.isfinite(float(ref.g["cars_equal_ranking_loss"]))                 # with equal sizes the reference goes through
     with pytest.raises(NotImplementedError, match="nhid_query == nhid_document"):
-        CARS(a)
+        CARS(_args(ref, "CARS", **kw))
+    assert type(CARS(_args(ref, "CARS", **dict(kw, nhid_document=kw["nhid_query"])))) is CARS
 
 
 def test_predict_text_outputs_equal_the_reference_tail(ref):
     """wrappers.Multitask._suggestion_text (the host tail of predict for a batch in the reference's collate layout) against the reference's own
-    code: `tens2sen` over the decoder's ids per step, `ex_ids`, `targets`, `src_sequences` exactly as models/multitask.py:294-316 builds them --
-    what main/multitask.py:validate_official reads from `outputs`."""
-    from neuroir.utils.misc import tens2sen
+    tail: `tens2sen` over the decoder's ids per step (recorded from the reference for these ids), `ex_ids`, `targets`, `src_sequences` exactly as
+    models/multitask.py:294-316 builds them -- what main/multitask.py:validate_official reads from `outputs`."""
     from context_attentive_ir_amd.config import default_args
     from context_attentive_ir_amd.wrappers import Multitask
-    tgt = _vocab(ref, 30)
+    tgt = ref.tgt
     w = Multitask(default_args("CARS", src_vocab_size=40, tgt_vocab_size=len(tgt)), tgt_dict=tgt)
-    B, S, ML = 3, 4, 6
-    g = torch.Generator().manual_seed(5)
-    pred = torch.randint(0, len(tgt) + 3, (B, S - 1, ML), generator=g)           # incl. BOS / EOS / PAD and ids past the dictionary
-    pred[0, 0, :] = 2                                                              # only BOS: an empty sentence
-    pred[1, 1, 2] = 3                                                              # EOS in the middle
+    pred = torch.from_numpy(ref.g["tail_pred"].copy())                           # incl. BOS / EOS / PAD and ids past the dictionary
+    B, S, ML = pred.shape[0], pred.shape[1] + 1, pred.shape[2]
+    assert (pred[0, 0] == 2).all() and pred[1, 1, 2] == 3                        # only BOS: an empty sentence; EOS in the middle
     src_tok = [[["<s>"] + ["q%d_%d_%d" % (b, s, j) for j in range(2 + s)] + ["</s>"] for s in range(S)] for b in range(B)]
     ex = {"ids": ["sess%d_" % b for b in range(B)], "batch_size": B, "session_len": S, "source_tokens": src_tok,
           "target_tokens": [[src_tok[b][s] for s in range(1, S)] for b in range(B)]}
     got = w._suggestion_text(ex, pred)
     # the reference's tail, verbatim semantics
-    want_pred, want_tgt, want_src = [], [], []
+    want_pred, want_tgt, want_src = [str(s) for s in ref.g["tail_predictions"]], [], []
     for sidx in range(S - 1):
-        want_pred.extend(tens2sen(pred[:, sidx, :], tgt, None))
         for bidx in range(B):
             tokens = ex["target_tokens"][bidx][sidx]
             want_tgt.append([" ".join(tokens[1:-1])])
