@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- ranked (query,doc) pairs/sec of the encode-and-rank hot path on N MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the timed steps, --dump-outputs, the line.  --full adds
+everything else this file measures: the headline's roofline, power, one-batch latency, precompute, H2D-inclusive, wrapper-default and CPU
+baseline figures, the sub-records (--sub picks among them) and at N > 1 the weak-scaling figure.  Without --full those entries of the line
+are null (`sub` is empty) and `full` is false.
 
 N > 1: launched by torch.distributed.run (one rank per GPU; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment) -- or plainly, in
 which case bench.py starts the N ranks itself.  A world that is not --gpus is refused; n_gpus of the line = an all-reduce of ones.
@@ -11,8 +16,8 @@ scaling / dtype / data, `config`, `roofline`, `cpu_baseline` and one four-scalar
 sub-record's roofline block, per-kernel microseconds, precompute, H2D stream) go to bench_detail.json (`config.detail`).  stderr of a successful
 run is EMPTY: file descriptor 2 points at bench_stderr.<rank>.log for the length of the run and is replayed only on failure.  Both files are
 written in the repository root (BENCH_LOG_DIR overrides it), or, where the running user cannot write there, in a per-user directory under the
-system temporary directory (log_path).  At N > 1 the headline is printed as a complete record before the sub-records run; the final line
-supersedes it.
+system temporary directory (log_path).  At N > 1 with --full the headline is printed as a complete record before the sub-records run; the
+final line supersedes it.
 
 HEADLINE: BASELINE.json configs[2], the largest configuration BASELINE marks 1 x MI355X -- CARS multitask, 16 sessions x session_len 7 x 10
 candidates, q_len 4, doc_len 64, emb_dim 300, fp32, synthetic MSMARCO-shaped ids (Zipf over a 100 000 x 300 table, seed 1013), full-length
@@ -23,20 +28,20 @@ max over ranks; a region shorter than 0.25 s is repeated and the median reported
 probabilities of the last timed step are written to DIR/click_scores.npy (session models, [B,S,N]) or DIR/scores.npy (rankers, [B,N]), float32;
 the inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 
-SUB-RECORDS (N = 1): C1 ESM 8x5, C2 MatchTensor 32x10, the north-star 32x50 MatchTensor shape, C4 DUET and DRMM 64x50xdoc_len 290 (DRMM / ESM
+SUB-RECORDS (--full, N = 1): C1 ESM 8x5, C2 MatchTensor 32x10, the north-star 32x50 MatchTensor shape, C4 DUET and DRMM 64x50xdoc_len 290 (DRMM / ESM
 with uniform ids over a 1M-row table so the gather really comes from HBM; DRMM with its histogram gap on overlapping ids), the C5 shape (CARS
 64x7x50) in bf16, the two other session rankers (M_MATCH_TENSOR, MNSRF) at the configs[2] shape, C3 without folded tables, C3 with decode, the C5 session stream (ids from the host), the CARS / MatchTensor training steps.
 
 N > 1 (strong scaling): every rank holds the SAME global batch.  Rankers: its slice of the candidate axis (ceil(N_cand / N),
 padded), all-gather of the score shards over RCCL.  CARS: the (session, candidate) pair axis in whole sessions per rank when B % N == 0 (no exchange
 of pooled vectors, all-gather of the probabilities), else the candidate axis with an all-to-all.  value = global pairs / max-rank time.
-Sub-records: C4 DUET / DRMM, the C5 shape, the headline on the other CARS axis, the C5 stream in both stream modes, and
+Sub-records (--full): C4 DUET / DRMM, the C5 shape, the headline on the other CARS axis, the C5 stream in both stream modes, and
 `config.weak_scaling_pairs_per_s` (labelled, secondary: every rank scoring its own full batch with no collective).
 
-roofline: the dominant kernel (largest summed duration), timed with HIP events on its launch stream in a profiled pass over the same launches
+roofline (--full): the dominant kernel (largest summed duration), timed with HIP events on its launch stream in a profiled pass over the same launches
 right after the timed region; algorithmic flops / bytes per launch are priced from the launch's own shape.  Peaks: HBM
 8 TB/s; fp32 MFMA 157.3 TFLOP/s; fp16 / bf16 MFMA 2500 TFLOP/s (a two-term fp16 split executes 3 MFMAs per product, a three-term bf16 split 6).
-cpu_baseline: the pinned CPU oracle (oracle/neuroir_cpu.py) on the host cores, bounded sample, rank 0 at N = 1 only.
+cpu_baseline (--full): the pinned CPU oracle (oracle/neuroir_cpu.py) on the host cores, bounded sample, rank 0 at N = 1 only.
 """
 import os
 os.environ.setdefault("NIR_DEBUG_TUNABLES", "1")      # the isolated-kernel profile pass switches the library's internal fork off (nir_debug_set_tunable)
@@ -228,7 +233,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=40)
     ap.add_argument("--config", default=HEADLINE, choices=sorted(CONFIGS) + ["C5_stream"],
                     help="headline workload (default: C3 CARS); C5_stream = the whole 223 876-session bf16 stream, ids from the host (prints its own record)")
-    ap.add_argument("--sub", default=None, help="comma-separated sub-records to measure (default: all; 'none' to skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline's timed steps: its roofline, power, one-batch latency, H2D, wrapper-default "
+                    "and CPU-baseline figures, the sub-records and (N > 1) the weak-scaling figure; off: setup, warm-up, the timed steps, "
+                    "--dump-outputs and the line")
+    ap.add_argument("--sub", default=None, help="--full: comma-separated sub-records to measure (default: all; 'none' to skip)")
     # ad-hoc shapes (tools/, profiling): override fields of --config
     ap.add_argument("--model", default=None, choices=["match_tensor", "esm", "drmm", "duet", "cars", "m_match_tensor", "mnsrf"])
     ap.add_argument("--batch", type=int, default=None)
@@ -245,8 +254,8 @@ def parse():
     ap.add_argument("--in-flight-hint", type=int, default=0, help="library batches-in-flight hint (default: --streams); profiling runs pass the timed run's "
                     "lane count with --streams 1 so that the serial capture launches the SAME kernel instantiations the timed run does")
     ap.add_argument("--no-graph", action="store_true", help="do not replay the step from a captured hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline and no checker legs against the CPU oracle")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: seconds of the CPU baseline's timed sample")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps of the headline, write the probabilities its LAST timed step computed to DIR/<name>.npy (float32): "
                     "click_scores [B,S,N] for the session models, scores [B,N] for the rankers")
@@ -445,8 +454,9 @@ def _phase(name, what):
             f.write("%s: %s\n" % (name, what))
 
 
-def run_config(name, c, args, env, steps, warmup, shard, want_cpu=False, with_h2d=False, axis=None, kg=None, dump=None):
-    """Time one workload; returns the record dict (rank 0) or None.  dump: directory for the outputs of the last timed step (write_outputs)."""
+def run_config(name, c, args, env, steps, warmup, shard, want_cpu=False, with_h2d=False, axis=None, kg=None, dump=None, lean=False):
+    """Time one workload; returns the record dict (rank 0) or None.  dump: directory for the outputs of the last timed step (write_outputs).
+    lean: set-up, warm-up and the timed steps only -- no precompute, power, one-batch / overlap, profile or checker legs (their fields are None)."""
     _phase(name, "start")
     L = lib.load()
     dev, world, rank = env.dev, env.world, env.rank
@@ -461,7 +471,7 @@ def run_config(name, c, args, env, steps, warmup, shard, want_cpu=False, with_h2
         wsh = int(os.environ["BENCH_EMULATE_WORLD"])
     emu = wsh != world
     model = build_model(c, args)
-    pre = precompute_info(model, c) if rank == 0 else None
+    pre = precompute_info(model, c) if rank == 0 and not lean else None
     # batches in flight: --streams lanes (BENCH_SHARD_LANES overrides it for the sharded CARS step)
     nlanes = max(1, args.streams)
     if sharded and c["model"] == "cars" and wsh > 1 and env.backend == "nccl":
@@ -871,13 +881,14 @@ def run_config(name, c, args, env, steps, warmup, shard, want_cpu=False, with_h2
         if stages is not None:
             stages["pos"] = 0
 
+    patterns = (max(warmup, 1), steps) + (() if lean else (max(6, min(steps, 60)),))      # (the last: the one-batch / overlap check's)
     if stages is not None and "aligned" in stages:      # dry run of every call pattern below: remainder groups get captured now
-        for n in (max(warmup, 1), steps, max(6, min(steps, 60))):
+        for n in patterns:
             rewind()
             run_steps(n)
         torch.cuda.synchronize()
     if fused is not None:                    # remainder groups are captured before the timed region
-        for n in {max(warmup, 1) % KSTEP, steps % KSTEP, max(6, min(steps, 60)) % KSTEP} - {0}:
+        for n in {p % KSTEP for p in patterns} - {0}:
             fused["rem"][n] = fused["capture"](2 * KSTEP, n)
     rewind()
     run_steps(max(warmup, 1))
@@ -918,7 +929,7 @@ def run_config(name, c, args, env, steps, warmup, shard, want_cpu=False, with_h2
         probs = final["step"]().reshape(c["batch"], *((c["session"],) if is_sess else ()), ncand)
         write_outputs(dump, {"click_scores" if is_sess else "scores": probs})
     power = None
-    if rank == 0 and not env.multi and not adhoc_power_off:        # every N = 1 record: which configurations run at the package power cap
+    if rank == 0 and not env.multi and not adhoc_power_off and not lean:        # every N = 1 record: which configurations run at the package power cap
         def busy():
             rewind()
             run_steps(steps)
@@ -926,8 +937,8 @@ def run_config(name, c, args, env, steps, warmup, shard, want_cpu=False, with_h2
         power = sample_power(busy, 2.5 if want_cpu else 1.5)
 
     _phase(name, "single / overlap check")
-    single_ms, overlap_diff = ms_per_step, None
-    if len(lanes) > 1:
+    single_ms, overlap_diff = (None if lean else ms_per_step), None
+    if len(lanes) > 1 and not lean:
         if graphs is not None and not sharded:
             # concurrent-vs-serial check of EVERY captured graph.  (Round 4 cloned the outputs the timed region happened to leave behind: with
             # more resident batches than steps + warm-up -- X3_mnsrf: 32 graphs, 30 steps, 8 warm-up replays -- the last graphs had never
@@ -1043,28 +1054,29 @@ def run_config(name, c, args, env, steps, warmup, shard, want_cpu=False, with_h2
         except Exception as e:  # pragma: no cover - secondary figure only
             print("[bench] H2D-inclusive figure unavailable: %s: %s" % (type(e).__name__, e), file=sys.stderr)
 
-    _phase(name, "profile pass")
-    # ---- profiled pass: HIP events around every kernel of the library, same workload, serial -------------------
-    torch.cuda.set_stream(lanes[0])
-    lib.set_batches_in_flight(hint, lanes)
-    nprof = max(4, min(steps, 30))
-    L.nir_debug_set_tunable(b"no_fork", 1)          # time every kernel in isolation (no query/document stream overlap)
-    if rank == 0:
-        L.nir_profile_enable(1)
-    prof_div = nprof
-    if macro_single and stages is not None:        # the launches of the timed region: macro-batches of KG batches
-        KGp = stages["KG"]
-        for i in range(max(2, nprof // KGp)):
-            stages["eager"][(i % stages["ngroups"], KGp)]()
-        prof_div = max(2, nprof // KGp) * KGp
-    else:
-        for i in range(nprof):
-            finish(forward(i))
-    torch.cuda.synchronize()
-    L.nir_profile_enable(0)
-    L.nir_debug_set_tunable(b"no_fork", 0)
     roofline = None
-    if rank == 0:
+    if not lean:
+        _phase(name, "profile pass")
+        # ---- profiled pass: HIP events around every kernel of the library, same workload, serial -------------------
+        torch.cuda.set_stream(lanes[0])
+        lib.set_batches_in_flight(hint, lanes)
+        nprof = max(4, min(steps, 30))
+        L.nir_debug_set_tunable(b"no_fork", 1)          # time every kernel in isolation (no query/document stream overlap)
+        if rank == 0:
+            L.nir_profile_enable(1)
+        prof_div = nprof
+        if macro_single and stages is not None:        # the launches of the timed region: macro-batches of KG batches
+            KGp = stages["KG"]
+            for i in range(max(2, nprof // KGp)):
+                stages["eager"][(i % stages["ngroups"], KGp)]()
+            prof_div = max(2, nprof // KGp) * KGp
+        else:
+            for i in range(nprof):
+                finish(forward(i))
+        torch.cuda.synchronize()
+        L.nir_profile_enable(0)
+        L.nir_debug_set_tunable(b"no_fork", 0)
+    if rank == 0 and not lean:
         buf = ctypes.create_string_buffer(1 << 17)
         L.nir_profile_report(buf, len(buf))
         kern = {}
@@ -1154,7 +1166,7 @@ def run_config(name, c, args, env, steps, warmup, shard, want_cpu=False, with_h2
         cpu = cpu_baseline(c, model, batches, lambda: finish(forward(0)), pairs_global, args)
     _phase(name, "checker legs")
     tier_err = None
-    if (c.get("dtype") == "f32_split2" or c.get("oracle_slice")) and rank == 0 and not env.multi and not args.no_cpu_baseline:
+    if (c.get("dtype") == "f32_split2" or c.get("oracle_slice")) and rank == 0 and not env.multi and not args.no_cpu_baseline and not lean:
         # the record's own error figure (checker leg, the oracle as the checker only): click probabilities of two resident batches against the oracle
         # (oracle_slice = n: the first n sessions of each -- the synthetic labels hold exactly one click per query, so the batch-wide click count
         # of cars.py:285-289 is 1 for the slice as for the batch)
@@ -1210,7 +1222,7 @@ def run_config(name, c, args, env, steps, warmup, shard, want_cpu=False, with_h2
             # machine-readable marker of the lane-count tuning aid (BENCH_EMULATE_WORLD): `pairs_per_s` is then rank 0's 1/W share x W on ONE GPU
             "emulated": bool(emu), "emulated_world": wsh if emu else None,
             "kg": (stages["KG"] if (stages is not None and "aligned" in stages) else 1), "pairs_per_s": round(value, 1), "ms_per_step": round(ms_per_step, 5),
-            "ms_per_step_one_batch_in_flight": round(single_ms, 5), "global_batch_pairs": per_step_pairs, "parallelism": par, "world_size": world,
+            "ms_per_step_one_batch_in_flight": None if single_ms is None else round(single_ms, 5), "global_batch_pairs": per_step_pairs, "parallelism": par, "world_size": world,
             "steps": steps, "reps": reps, "ms_per_step_min_max": spread, "hipgraph": (graphs is not None) or (stages is not None and stages.get("graphed", True)) or (fused is not None),
             "batches_in_flight": len(lanes) * (stages["KG"] if (stages is not None and "aligned" in stages) else 1),
             "macro_batch": (stages["KG"] if (stages is not None and "aligned" in stages) else 1), "lanes": len(lanes), "host_enqueue_ms_per_step": round(host_ms, 5),
@@ -1391,6 +1403,8 @@ def short_sub(n, r):
 
 def main():
     args = parse()
+    if args.sub not in (None, "none") and not args.full:
+        raise SystemExit("bench.py: --sub %s names sub-records: they run with --full only" % args.sub)
     launcher = args.gpus > 1 and "WORLD_SIZE" not in os.environ
     # (the redirect starts BEFORE the HIP runtime initialises: libdrm's "amdgpu.ids: No such file" line is stderr noise of every run on this image)
     with QuietStderr(log_path("bench_stderr.%s.log" % ("launcher" if launcher else "rank%d" % int(os.environ.get("RANK", "0"))))):
@@ -1445,7 +1459,10 @@ def run_records(args, env):
     if head["model"] in SESSION_MODELS:
         head.setdefault("session", 7)
     hname = args.config if not adhoc else "adhoc_" + head["model"]
-    rec = run_config(hname, head, args, env, args.steps, args.warmup, shard=True, want_cpu=True, with_h2d=True, dump=args.dump_outputs)
+    rec = run_config(hname, head, args, env, args.steps, args.warmup, shard=True, want_cpu=args.full, with_h2d=args.full, dump=args.dump_outputs,
+                     lean=not args.full)
+    if not args.full:                   # a plain run: the headline's timed steps and nothing else
+        return compose_line(args, env, rec, {}, None) if env.rank == 0 else None
     if env.multi and env.world > 1 and env.rank == 0:
         # N > 1: a rank that fails inside a sub-record must take the job down (the others would hang in its collectives) -- so the headline is
         # printed NOW as a complete record of its own; the final line (with the sub-records) supersedes it as the last line of stdout
@@ -1571,8 +1588,8 @@ def compose_line(args, env, rec, sub, weak):
     line = {"metric": "ranked (query,doc) pairs/sec", "value": rec["pairs_per_s"], "unit": "pairs/s", "n_gpus": env.seen,
             "steps": args.steps, "warmup": args.warmup, "reps": rec["reps"], "ms_per_step": rec["ms_per_step"], "higher_is_better": True,
             # the global batch is FIXED as N grows (every rank scores its share of the same batch): strong scaling at every N
-            "scaling": "strong", "vs_baseline": None, "dtype": rec["dtype"], "data": "synthetic",
-            "config": cfg, "roofline": small, "power": pw, "cpu_baseline": cpu, "sub": [short_sub(n, r) for n, r in sub.items()]}
+            "scaling": "strong", "vs_baseline": None, "dtype": rec["dtype"], "data": "synthetic", "full": args.full,
+            "config": cfg, "roofline": small if args.full else None, "power": pw, "cpu_baseline": cpu, "sub": [short_sub(n, r) for n, r in sub.items()]}
     if rec.get("emulated"):
         # BENCH_EMULATE_WORLD (tuning aid, never set by the driver): `value` is ONE GPU's 1/W share of the work extrapolated x W, not a measured
         # multi-GPU figure -- flagged at the top level so that a tool reading value / n_gpus cannot take it for one

@@ -23,10 +23,11 @@ def _detail(d):
 
 
 def test_bench_single_gpu_line():
-    """the record as the driver reads it: `python bench.py --steps 20 --warmup 5`, stdout FOLLOWED by stderr -- the last line of that is ONE
-    compact JSON object (< 4 KB) with the contract keys + roofline + cpu_baseline, stderr of a successful run is empty, a short region is
+    """the full record as the driver reads it: `python bench.py --full --steps 20 --warmup 5`, stdout FOLLOWED by stderr -- the last line of that
+    is ONE compact JSON object (< 4 KB) with the contract keys + roofline + cpu_baseline, stderr of a successful run is empty, a short region is
     repeated (`reps`) with `steps` = the argument; the full sub-records are in the detail file the line names."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--sub", "C1_esm,C4_drmm", "--cpu-seconds", "2"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--sub", "C1_esm,C4_drmm",
+                          "--cpu-seconds", "2"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stderr.strip() == "", out.stderr[-2000:]
@@ -44,6 +45,29 @@ def test_bench_single_gpu_line():
     assert {"hist_rows_differ", "pairs_differ", "map_delta_vs_oracle"} <= set(subs["C4_drmm"])       # the DRMM parity gap rides with its record
     full = _detail(d)
     assert full["sub"]["C1_esm"]["roofline"]["kernel"] and full["headline"]["roofline"]["kernels_us_per_step"]
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """a plain `python bench.py --steps 20 --warmup 5`: the same headline figure (C3, `value` and `ms_per_step` of the 1 120-pair step, `reps`,
+    one compact last line, empty stderr) and nothing that --full adds -- no roofline, power, CPU baseline, one-batch latency, H2D or
+    wrapper-default figure, no sub-record, `full` false; the detail file holds the headline record alone."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5"],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert out.stderr.strip() == "", out.stderr[-2000:]
+    d = _last_json(out.stdout)
+    assert KEYS | {"sub", "reps", "full"} <= set(d)
+    assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["reps"] >= 3 and d["value"] > 0 and d["config"]["workload"].startswith("cars")
+    assert d["metric"] == "ranked (query,doc) pairs/sec" and d["unit"] == "pairs/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert abs(d["value"] - 1120 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-3
+    assert d["full"] is False and d["sub"] == [] and d["roofline"] is None and d["power"] is None and d["cpu_baseline"] is None
+    c = d["config"]
+    assert c["macro_batch"] == 8 and c["hipgraph"] is True
+    for k in ("ms_per_step_one_batch_in_flight", "pairs_per_s_with_host_ids_h2d", "default_settings_pairs_per_s", "dropin_loop_pairs_per_s",
+              "resident_sustained_pairs_per_s"):
+        assert c[k] is None, k
+    full = _detail(d)
+    assert full["sub"] == {} and full["headline"]["steps"] == 20 and full["headline"]["precompute"] is None
 
 
 def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
@@ -132,11 +156,11 @@ def test_bench_two_rank_stream_record():
 @pytest.mark.parametrize("axis,needle,port", [("auto", "pair axis in 2 contiguous chunks = 8 whole sessions", "29541"),
                                               ("candidate", "session-sharded tail", "29543")])
 def test_bench_two_ranks_strong_scaling_flow(axis, needle, port):
-    """bench.py --gpus 2 as the driver launches it (two ranks on the one GPU, gloo): the sharded CARS headline in both shard axes, a sharded
-    ranker sub-record, the labelled weak-scaling figure."""
+    """bench.py --full --gpus 2 as the driver launches it (two ranks on the one GPU, gloo): the sharded CARS headline in both shard axes, a
+    sharded ranker sub-record, the labelled weak-scaling figure."""
     env = dict(os.environ, BENCH_BACKEND="gloo", BENCH_SHARD_AXIS=axis)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", port,
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "3", "--sub", "C2_match_tensor" if axis == "auto" else "none"]
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "12", "--warmup", "3", "--sub", "C2_match_tensor" if axis == "auto" else "none"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json(out.stdout)

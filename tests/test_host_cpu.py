@@ -35,6 +35,12 @@ def test_argument_errors_are_reported_without_a_gpu():
     assert L.nir_bilstm_supported(128) == 1 and L.nir_bilstm_supported(129) == 0
 
 
+def test_bench_sub_records_need_full():
+    """bench.py measures sub-records only with --full: naming them in a plain run is refused before any device is touched"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--sub", "C1_esm"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert out.returncode != 0 and "--full" in out.stderr, out.stderr[-2000:]
+
+
 def test_no_cpu_fallback():
     m = build_model("ESM")
     with pytest.raises(RuntimeError, match="no CPU fallback"):

@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 for rep in 1 2 3; do
   for kg in 8 7 10 5; do
-    BENCH_MACRO_BATCH=$kg timeout 200 python bench.py --steps 20 --warmup 5 --sub none --no-cpu-baseline > /tmp/b.log 2>&1
+    BENCH_MACRO_BATCH=$kg timeout 200 python bench.py --full --steps 20 --warmup 5 --sub none --no-cpu-baseline > /tmp/b.log 2>&1
     python - <<PY
 import json
 l=[x for x in open("/tmp/b.log") if x.startswith("{")][-1]

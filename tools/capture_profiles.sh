@@ -1,7 +1,7 @@
 #!/bin/bash
 # rocprofv3 evidence for every bench.py configuration (run on the GPU box through gpurun from the repo root):
 #   gpurun --timeout 2400 -- 'bash tools/capture_profiles.sh r05 [config ...]'
-# First the default `python bench.py` (its compact line + bench_detail.json are kept beside the captures); then per config:
+# First `python bench.py --full` (its compact line + bench_detail.json are kept beside the captures); then per config:
 # (1) --kernel-trace --stats of the serial eager run -- one lane, nothing co-running, every launch attributed -- with the library's batches-in-flight
 #     hint set to the TIMED run's lane count (--in-flight-hint 4), so that the capture launches the same kernel instantiations the timed run does
 #     (round 3 captured lstm16_pt_h2_kernel<3,2,16> for C2 while the line named <3,5,4>);
@@ -13,7 +13,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/${PREFIX}prof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH_DETAIL=$OUT/bench_detail.json python $REPO/bench.py > $OUT/bench_line.json 2> $OUT/bench_line.err
+BENCH_DETAIL=$OUT/bench_detail.json python $REPO/bench.py --full > $OUT/bench_line.json 2> $OUT/bench_line.err
 export BENCH_NO_H2D=1
 CFGS=${@:-C3_cars C1_esm C2_match_tensor NS_match_tensor_50 NS_cars_50 C4_duet C4_drmm C4_esm_hbm C5_cars_bf16 X3_mnsrf X3_m_match_tensor C3_cars_split2}
 for c in $CFGS; do

@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "py
 tail -3 $OUT/pytest.log
 for cfg in "cars --batch 16 --cands 10" "cars --batch 64 --cands 50 --steps 20" "duet --batch 64 --cands 50 --dlen 290 --qlen 8 --steps 20" "drmm --batch 64 --cands 50 --dlen 290 --uniform --vocab 1000000 --steps 100" "esm --batch 64 --cands 50 --dlen 290 --uniform --vocab 1000000 --steps 100" "match_tensor --batch 32 --cands 50"; do
   name=$(echo $cfg | tr ' ' '_' | tr -d '-')
-  timeout 600 python bench.py --model $cfg --no-cpu-baseline 2>$OUT/$name.err | tail -1 > $OUT/$name.json
+  timeout 600 python bench.py --full --model $cfg --no-cpu-baseline 2>$OUT/$name.err | tail -1 > $OUT/$name.json
   python - <<PY
 import json
 try:
