@@ -529,26 +529,16 @@ int launch_lstm_step(const LstmStepArgs& a, int nchains, hipStream_t st) {
         ProfScope ps("lstm_step16_kernel", st);
         // unit groups per workgroup / batch tiles per workgroup: measured at the session shapes (HS = 512, B = 64 / 128): more, smaller workgroups win --
         // the step is a latency chain (one L2 round trip, a few dozen MFMAs, an LDS reduction), not a bandwidth problem: UG 1 / 2 / 4 = 12.5 / 13.8 /
-        // 18.4 us per bench step at B = 128.  Tunables lstm_step_ug / lstm_step_nb override (tools, tests).
-        const int ugsel = tun(g_tun.lstm_step_ug), nbsel = tun(g_tun.lstm_step_nb);
+        // 18.4 us per bench step at B = 128.
         const int NUG = a.H / 4;
-        int NBv = nbsel ? nbsel : (a.B > 32 ? 4 : (a.B > 16 ? 2 : 1));
-        NBv = NBv >= 4 ? 4 : (NBv >= 2 ? 2 : 1);
+        const int NBv = a.B > 32 ? 4 : (a.B > 16 ? 2 : 1);
         // (from 256 rows on -- the greedy decoders' 768 -- the [rows, H] state operand is re-read once per workgroup column: four unit groups per workgroup)
-        const int ugd = ugsel ? ugsel : (a.B >= 256 ? 4 : 1);
-        const int UGv = ugd == 4 ? 4 : (ugd == 2 ? 2 : 1);
+        const int UGv = a.B >= 256 ? 4 : 1;
         const dim3 gridu((unsigned)((NUG + UGv - 1) / UGv), (unsigned)nchains, (unsigned)((a.B + 16 * NBv - 1) / (16 * NBv)));
-        if (NBv == 4) {
-            if (UGv == 4) hipLaunchKernelGGL((lstm_step16_kernel<4, 4, 2>), gridu, dim3(256), 0, st, a);
-            else if (UGv == 2) hipLaunchKernelGGL((lstm_step16_kernel<4, 2, 4>), gridu, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((lstm_step16_kernel<4, 1, 4>), gridu, dim3(256), 0, st, a);
-        } else if (NBv == 2) {
-            if (UGv >= 2) hipLaunchKernelGGL((lstm_step16_kernel<2, 2, 4>), gridu, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((lstm_step16_kernel<2, 1, 8>), gridu, dim3(256), 0, st, a);
-        } else {
-            if (UGv >= 2) hipLaunchKernelGGL((lstm_step16_kernel<1, 2, 4>), gridu, dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((lstm_step16_kernel<1, 1, 8>), gridu, dim3(256), 0, st, a);
-        }
+        if (UGv == 4) hipLaunchKernelGGL((lstm_step16_kernel<4, 4, 2>), gridu, dim3(256), 0, st, a);
+        else if (NBv == 4) hipLaunchKernelGGL((lstm_step16_kernel<4, 1, 4>), gridu, dim3(256), 0, st, a);
+        else if (NBv == 2) hipLaunchKernelGGL((lstm_step16_kernel<2, 1, 8>), gridu, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((lstm_step16_kernel<1, 1, 8>), gridu, dim3(256), 0, st, a);
         NIR_CHECK_LAUNCH("lstm_step16_kernel");
         return 0;
     }

@@ -139,9 +139,8 @@ static int env_int(const char* name, int dflt) {
     return e ? (e[0] ? atoi(e) : 1) : dflt;
 }
 static int env_flag(const char* name) { return getenv(name) ? 1 : 0; }
-Tunables g_tun{{env_flag("NIR_NO_FORK")}, {env_flag("NIR_LSTM_VALU")}, {env_int("NIR_LSTM_MFMA16", -1)}, {env_int("NIR_LSTM_MFMA_S", 0)},
-               {env_int("NIR_LSTM_S", 0)}, {env_int("NIR_LSTM_W16", 0)}, {env_flag("NIR_NO_SKINNY")}, {env_flag("NIR_NO_GEMM16")}, {env_flag("NIR_ESM_WAVE_ROWS")},
-               {env_flag("NIR_DEBUG")}, {env_flag("NIR_EXACT_F32")}};
+Tunables g_tun{{env_flag("NIR_NO_FORK")}, {env_int("NIR_LSTM_MFMA16", -1)}, {env_int("NIR_LSTM_S", 0)}, {env_flag("NIR_DEBUG")},
+               {env_flag("NIR_EXACT_F32")}};
 }  // namespace nir
 extern "C" int nir_set_stream_batches_in_flight(nir_stream_t stream, int n) {
     std::lock_guard<std::mutex> lk(nir::g_bif_mu);
@@ -162,10 +161,10 @@ extern "C" int nir_debug_set_tunable(const char* name, int value) {
         return NIR_ERR_BAD_ARG;
     }
     struct { const char* n; std::atomic<int>* a; } tab[] = {
-        {"no_fork", &g_tun.no_fork}, {"lstm_valu", &g_tun.lstm_valu}, {"lstm_mfma16", &g_tun.lstm_mfma16}, {"lstm_mfma_s", &g_tun.lstm_mfma_s},
-        {"lstm_s", &g_tun.lstm_s}, {"lstm_w16", &g_tun.lstm_w16}, {"no_skinny", &g_tun.no_skinny}, {"no_gemm16", &g_tun.no_gemm16}, {"esm_wave_rows", &g_tun.esm_wave_rows},
-        {"debug", &g_tun.debug}, {"exact_f32", &g_tun.exact_f32}, {"duet_unfused", &g_tun.duet_unfused}, {"attn_unfused", &g_tun.attn_unfused}, {"attn_unfused_pipe", &g_tun.attn_unfused_pipe}, {"duet_rows64", &g_tun.duet_rows64},
-        {"attn_fp32_rows", &g_tun.attn_fp32_rows}, {"attn_io_prio", &g_tun.attn_io_prio}, {"lstm_step_ug", &g_tun.lstm_step_ug}, {"lstm_step_nb", &g_tun.lstm_step_nb}, {"nofold_old", &g_tun.nofold_old}, {"gemm3_ks", &g_tun.gemm3_ks}, {"wgrad_no_lds", &g_tun.wgrad_no_lds}, {"wgrad_lds_tiles", &g_tun.wgrad_lds_tiles}, {"wgrad_min_rows", &g_tun.wgrad_min_rows}, {"lstm_bwd_w8", &g_tun.lstm_bwd_w8}, {"cl_poll_limit", &g_tun.cl_poll_limit}};     // 1: the fp32-accurate recurrence hands fp32 rows (not its term pairs) to the attention pipeline
+        {"no_fork", &g_tun.no_fork}, {"lstm_mfma16", &g_tun.lstm_mfma16}, {"lstm_s", &g_tun.lstm_s}, {"debug", &g_tun.debug},
+        {"exact_f32", &g_tun.exact_f32}, {"duet_unfused", &g_tun.duet_unfused}, {"attn_unfused", &g_tun.attn_unfused},
+        {"attn_unfused_pipe", &g_tun.attn_unfused_pipe}, {"duet_rows64", &g_tun.duet_rows64}, {"attn_fp32_rows", &g_tun.attn_fp32_rows},
+        {"attn_io_prio", &g_tun.attn_io_prio}, {"cl_poll_limit", &g_tun.cl_poll_limit}};
     for (auto& t : tab)
         if (!strcmp(t.n, name)) { t.a->store(value); return 0; }
     set_error("nir_debug_set_tunable: unknown tunable '%s'", name);

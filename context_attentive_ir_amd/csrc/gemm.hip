@@ -1123,8 +1123,8 @@ int launch_linear_ex(const float* a, int64_t lda, const int64_t* ids, const floa
         ProfScope ps(prof_shape_name(bounded ? (ids ? "gemm3h_kernel[gather]" : "gemm3h_kernel") : (ids ? "gemm3_kernel[gather]" : "gemm3_kernel"), M, N, K), st);
         dim3 grid((unsigned)(8 * nb3 * ((mb3 + 7) / 8)));
         // fp16 two-term form: two k-tiles per pipeline stage (one barrier and one prefetch per 32 of K; 66 KB of LDS: still two workgroups per CU):
-        // 8 960 x 512 x 1 024 65.5 -> 57.4 us, the gather-GEMM 573 440 x 1 024 x 300 2.135 -> 2.096 ms (tunable gemm3_ks = 1: one tile per stage)
-        if (bounded && tun(g_tun.gemm3_ks) != 1 && K >= 64) {
+        // 8 960 x 512 x 1 024 65.5 -> 57.4 us, the gather-GEMM 573 440 x 1 024 x 300 2.135 -> 2.096 ms
+        if (bounded && K >= 64) {
             constexpr size_t lds2 = (size_t)2 * 2 * 2 * 2 * G3_PLANE * 2;
             static std::once_flag once;
             std::call_once(once, [] {
@@ -1148,13 +1148,13 @@ int launch_linear_ex(const float* a, int64_t lda, const int64_t* ids, const floa
         NIR_CHECK_LAUNCH("nir_linear_f32[bf16x3]");
         return 0;
     }
-    if (N <= 64 && vec && M >= 4096 && (!ids || K <= E) && sk_lds <= 128 * 1024 && act != ACT_MAXOUT2 && act != ACT_TANH_ROWDOT16 && !tun(g_tun.no_skinny)) {
+    if (N <= 64 && vec && M >= 4096 && (!ids || K <= E) && sk_lds <= 128 * 1024 && act != ACT_MAXOUT2 && act != ACT_TANH_ROWDOT16) {
         ProfScope ps(prof_shape_name(ids ? "gemm_skinny_kernel[gather]" : "gemm_skinny_kernel", M, N, K), st);
         if (skNT == 1) launch_skinny<1>(p, skG, sk_lds, st);
         else if (skNT == 2) launch_skinny<2>(p, skG, sk_lds, st);
         else if (skNT == 3) launch_skinny<3>(p, skG, sk_lds, st);
         else launch_skinny<4>(p, skG, sk_lds, st);
-    } else if (mb * nb < 160 && !tun(g_tun.no_gemm16) && !ids && vec && K % 16 == 0 && ((M + 31) / 32) * ((N + 31) / 32) >= 200) {
+    } else if (mb * nb < 160 && !ids && vec && K % 16 == 0 && ((M + 31) / 32) * ((N + 31) / 32) >= 200) {
         // mid-size: 32x32 output blocks still give >= 200 workgroups
         ProfScope ps(prof_shape_name("gemm32_kernel", M, N, K), st);
         // rows per workgroup (16 RA) chosen for the fewest rounds of workgroups over the CUs times the work per workgroup: 1120 x 512 is
@@ -1181,7 +1181,7 @@ int launch_linear_ex(const float* a, int64_t lda, const int64_t* ids, const floa
             case 5: hipLaunchKernelGGL(gemm32_kernel<5>, grid, dim3(256), 0, st, p); break;
             default: hipLaunchKernelGGL(gemm32_kernel<6>, grid, dim3(256), 0, st, p); break;
         }
-    } else if (mb * nb < 160 && !tun(g_tun.no_gemm16)) {
+    } else if (mb * nb < 160) {
         // too few 64x64 tiles to fill 256 CUs: one 16x16 tile per workgroup, K split over the waves
         ProfScope ps(prof_shape_name(ids ? "gemm16_kernel[gather]" : "gemm16_kernel", M, N, K), st);
         dim3 grid((unsigned)((M + 15) / 16), (unsigned)((N + 15) / 16));

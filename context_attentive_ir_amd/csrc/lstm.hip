@@ -377,13 +377,12 @@ int launch_bilstm(const float* gin, const int64_t* lens, const float* whh, const
     // M = 1120 353 vs 439 us, M = 22400 3.86 vs 7.06 ms).  Below that: the quad/VALU kernel when its workgroup fills the
     // 4 SIMDs evenly (KP/16 waves a multiple of 4: H = 128 439 us vs 520 us for the 4x4x1 layout at M = 1120), the
     // 4x4x1-MFMA recurrence for the unbalanced sizes (H = 70: 5 waves).
-    if (!tun(g_tun.lstm_valu)) {   // many sequences, wide H: 16 sequences per workgroup on 16x16x4 MFMAs
-        int rc = launch_bilstm_mfma16(gin, lens, whh, h0, c0, out, hn, cn, M, T, H, ND, st);
-        if (rc != NIR_ERR_UNSUPPORTED) return rc;
-    }
+    // many sequences, wide H: 16 sequences per workgroup on 16x16x4 MFMAs
+    int rc = launch_bilstm_mfma16(gin, lens, whh, h0, c0, out, hn, cn, M, T, H, ND, st);
+    if (rc != NIR_ERR_UNSUPPORTED) return rc;
     const bool valu_balanced = (((H + 15) / 16) % 4) == 0;
-    if (!valu_balanced && !tun(g_tun.lstm_valu)) {
-        int rc = launch_bilstm_mfma(gin, lens, whh, h0, c0, out, hn, cn, M, T, H, ND, st);
+    if (!valu_balanced) {
+        rc = launch_bilstm_mfma(gin, lens, whh, h0, c0, out, hn, cn, M, T, H, ND, st);
         if (rc != NIR_ERR_UNSUPPORTED) return rc;
     }
     LstmArgs p{gin, nullptr, nullptr, nullptr, nullptr, lens, whh, h0, c0, out, hn, cn, M, T, H, ND, 0};
@@ -401,10 +400,9 @@ int launch_bilstm_fused(const float* x, int I, const float* wih, const float* bi
     NIR_REQUIRE(M >= 0 && T > 0 && (ND == 1 || ND == 2), "bilstm_fused: bad dims");
     NIR_REQUIRE(H >= 1 && H <= 128 && I >= 1 && I <= 64, "bilstm_fused: H=%d (1..128) / I=%d (1..64) unsupported", H, I);
     if (M == 0) return 0;
-    if (!tun(g_tun.lstm_valu)) {   // matrix-core recurrence (lstm_mfma.hip) when the shape has an instantiation
-        int rc = launch_bilstm_fused_mfma(x, I, wih, bih, bhh, lens, whh, h0, c0, out, hn, cn, M, T, H, ND, st);
-        if (rc != NIR_ERR_UNSUPPORTED) return rc;
-    }
+    // matrix-core recurrence (lstm_mfma.hip) when the shape has an instantiation
+    const int rc = launch_bilstm_fused_mfma(x, I, wih, bih, bhh, lens, whh, h0, c0, out, hn, cn, M, T, H, ND, st);
+    if (rc != NIR_ERR_UNSUPPORTED) return rc;
     LstmArgs p{nullptr, x, wih, bih, bhh, lens, whh, h0, c0, out, hn, cn, M, T, H, ND, I};
     int S = pick_s(M * ND, true);
     const int IP = I <= 48 ? 48 : 64;

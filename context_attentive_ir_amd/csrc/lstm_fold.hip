@@ -523,7 +523,7 @@ __global__ __launch_bounds__(1024) void lstm16_pt_bf16_kernel(LstmPtArgs p) {
 __device__ unsigned long long* g_pt_trace_dev;
 #define PT_T(var) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var) :: "memory")
 #endif
-// NW waves per workgroup, NT gate tiles per wave (NW * NT * 4 >= H units).  16 waves x 2 tiles is the latency form (H = 128); for
+// NW waves per workgroup, NT gate tiles per wave (NW * NT * 4 >= H units).  16 waves x 2 tiles is the latency form (H <= 96; 8 x 4 for H = 128); for
 // H <= 80 four waves x 5 tiles leave room for three workgroups per CU, which fill each other's per-step bubbles when several
 // batches are in flight.
 // H1 (round 5, the opt-in "split2" precision tier, <4,4,8,true> only): h enters the recurrent product as ONE fp16 term -- w.h = w1.h1 + 2^-11 w2'.h1:
@@ -1298,7 +1298,7 @@ __global__ __launch_bounds__(64) void lstm_whh_frag_kernel(const float* __restri
 // true when launch_bilstm_folded(.., out_f16 = 2) is served: the dispatch below ends in lstm16_pt_h2_kernel<4,4,8> with every lane `full`
 bool bilstm_folded_split_out_ok(int pt_dtype, int H, int T) {
     (void)T;
-    return pt_dtype == NIR_DTYPE_F32 && H == 128 && !tun(g_tun.exact_f32) && tun(g_tun.lstm_w16) != 1 && (tun(g_tun.lstm_w16) < 3 || tun(g_tun.lstm_w16) == 6);
+    return pt_dtype == NIR_DTYPE_F32 && H == 128 && !tun(g_tun.exact_f32);
 }
 
 int launch_bilstm_folded(const void* pt, int pt_dtype, const int64_t* ids, const int64_t* lens, const float* whh, float* out,
@@ -1317,8 +1317,8 @@ int launch_bilstm_folded(const void* pt, int pt_dtype, const int64_t* ids, const
         const int KB = (H + 31) / 32;
         if (H <= 64) return KB == 1 ? launch_pt_bf16<1, 1>(p, st) : launch_pt_bf16<2, 1>(p, st);
         if (KB == 3) return launch_pt_bf16<3, 2>(p, st);
-        // H in (96, 128]: two 8-wave workgroups per CU (tunable lstm_w16 = 1: the 16-wave form, one workgroup per CU)
-        return tun(g_tun.lstm_w16) == 1 ? launch_pt_bf16<4, 2>(p, st) : launch_pt_bf16w8(p, st);
+        // H in (96, 128]: two 8-wave workgroups per CU
+        return launch_pt_bf16w8(p, st);
     }
     if (!tun(g_tun.exact_f32) && H >= 32) {      // fp32-accurate two-term fp16 split on the fp16 matrix cores
         const int KB = (H + 31) / 32;
@@ -1333,8 +1333,7 @@ int launch_bilstm_folded(const void* pt, int pt_dtype, const int64_t* ids, const
             if (sel == 2 || (sel != 1 && wgs >= 2 * (int64_t)ncu)) return launch_pt_h2<3, 5, 4>(p, st);
         }
         if (KB == 3) return launch_pt_h2<3, 2>(p, st);
-        // H in (96, 128]: 8 waves x 4 tiles with the in-wave pipeline (tunable lstm_w16 = 1: the 16-wave x 2-tile form)
-        if (tun(g_tun.lstm_w16) == 1) return launch_pt_h2<4, 2>(p, st);
+        // H in (96, 128]: 8 waves x 4 tiles with the in-wave pipeline
         // (two sequence groups per workgroup sharing the W registers, skewed wave roles, output stores on one early wave: measured in rounds 3-4,
         // all tied or lost -- DESIGN.md section 10; sources archived under tools/variants/, not built)
         if (p.out_f16 == 3) return launch_pt_h2<4, 4, 8, true>(p, st);      // the opt-in one-term-h tier (H = 128, checked by the caller)

@@ -628,10 +628,7 @@ static int launch_mfma(const LstmMfmaArgs& p, hipStream_t st) {
         if (4 * p.H <= 256) return launch_mfma_s<NG, KQ, 4, 1>(p, st);
     }
     bool three = false;
-    const int force = tun(g_tun.lstm_mfma_s);
-    if (force) {
-        three = force == 3;
-    } else if (batches_in_flight(st) <= 1) {
+    if (batches_in_flight(st) <= 1) {
         // (with several batches in flight the 4-sequence layout wins: all 4 MFMA rows carry work and 160 workgroups of
         //  one batch leave CUs for the next -- measured 3.69 M vs 3.36 M pairs/s at 4 batches in flight)
         const int64_t wg4 = ((p.M + 3) / 4) * p.ND, wg3 = ((p.M + 2) / 3) * p.ND;

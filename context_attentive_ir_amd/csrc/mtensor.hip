@@ -680,7 +680,7 @@ static int matchtensor_impl(const int64_t* q_ids, const int64_t* q_len, const in
     }
     // the channel projection of the documents runs inside the head kernel when the host supplied its fragment planes (fp16 two-term
     // head only; 2Hd a multiple of 4 for the 16-byte row loads); a requested proj_d output keeps the separate GEMM
-    const bool fuse_proj = h2 && w->dproj_frag && (2 * w->Hd) % 4 == 0 && 2 * w->Hd >= 8 && w->C <= 64 && !tun(g_tun.no_skinny);
+    const bool fuse_proj = h2 && w->dproj_frag && (2 * w->Hd) % 4 == 0 && 2 * w->Hd >= 8 && w->C <= 64;
     if (fuse_proj) { hw.hd = hd; hw.dpf = w->dproj_frag; hw.dpb = w->dproj_b; }
     if (!fuse_proj || proj_d)
         NIR_PROPAGATE(launch_linear(hd, 2 * w->Hd, nullptr, nullptr, 0, 0, 0, w->dproj_w, 2 * w->Hd, w->dproj_b, nullptr, pd, w->C, Md, w->C, 2 * w->Hd, NIR_ACT_NONE, st));

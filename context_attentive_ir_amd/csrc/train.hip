@@ -1215,26 +1215,14 @@ __global__ void lstm_cell_seq_fwd_kernel(const float* __restrict__ gx, int64_t l
     h[b * ldh + j] = go * tanhf(cn);
 }
 // dh = dh1 (strided, the consumers of this step's h) + dh2 (contiguous, from the next step's recurrent GEMM), dc likewise; any may be NULL
-// (lens != NULL: the step is position t of padded sequences -- a row with t >= lens[b] takes no part: zero gate gradients, zero dc_prev, its
-//  incoming gradients ignored; c_prev exists where 0 <= tprev < lens[b], tprev = the position of the previous recurrence step)
 __global__ void lstm_cell_seq_bwd_kernel(const float* __restrict__ dh1, int64_t ld1, const float* __restrict__ dh2, const float* __restrict__ dc1,
                                          int64_t ldc1, const float* __restrict__ dc2, const float* __restrict__ act, int64_t ldact,
                                          const float* __restrict__ c, int64_t ldc, const float* __restrict__ cprev, int64_t ldcp, float* __restrict__ dg,
-                                         int64_t lddg, float* __restrict__ dcprev, int64_t B, int H, const int64_t* __restrict__ lens, int t, int tprev) {
+                                         int64_t lddg, float* __restrict__ dcprev, int64_t B, int H) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= B * H) return;
     const int64_t b = i / H;
     const int j = (int)(i % H);
-    if (lens) {
-        const int64_t l = lens[b];
-        if (t >= l) {
-            float* dr = dg + b * lddg;
-            dr[j] = 0.f; dr[H + j] = 0.f; dr[2 * H + j] = 0.f; dr[3 * H + j] = 0.f;
-            dcprev[i] = 0.f;
-            return;
-        }
-        if (tprev < 0 || tprev >= l) cprev = nullptr;
-    }
     const float* ar = act + b * ldact;
     const float gi = ar[j], gf = ar[H + j], gg = ar[2 * H + j], go = ar[3 * H + j];
     const float th = tanhf(c[b * ldc + j]);
@@ -1385,8 +1373,8 @@ static int wgrad_impl(const float* dy, int64_t lddy, const float* x, int64_t ldx
     }
     // LDS-staged workgroup tiles for the big gradients (float4 rows: widths, strides and bases in units of 16 bytes)
     const int64_t xstride = ids ? (int64_t)E : ldx;
-    const bool lds_ok = (M >= 32768 || (M >= 256 && (int64_t)((N + 127) / 128) * ((K + 127) / 128) >= (tun(g_tun.wgrad_lds_tiles) > 0 ? tun(g_tun.wgrad_lds_tiles) : 192))) && N >= 128 && K >= 128 && N % 4 == 0 && K % 4 == 0 && lddy % 4 == 0 && xstride % 4 == 0 &&
-                        ((uintptr_t)dy & 15) == 0 && ((uintptr_t)(ids ? table : x) & 15) == 0 && !tun(g_tun.wgrad_no_lds);
+    const bool lds_ok = (M >= 32768 || (M >= 256 && (int64_t)((N + 127) / 128) * ((K + 127) / 128) >= 192)) && N >= 128 && K >= 128 && N % 4 == 0 && K % 4 == 0 && lddy % 4 == 0 && xstride % 4 == 0 &&
+                        ((uintptr_t)dy & 15) == 0 && ((uintptr_t)(ids ? table : x) & 15) == 0;
     if (lds_ok) {
         int wk = 2;                                                    // K tile of 64 wk columns: least padding, then the widest
         int64_t best = -1;
@@ -1407,10 +1395,7 @@ static int wgrad_impl(const float* dy, int64_t lddy, const float* x, int64_t ldx
             case 2: wgrad_lds_launch<2, 2>(a, tiles * slices, st); break;
             case 3: wgrad_lds_launch<2, 3>(a, tiles * slices, st); break;
             case 4: wgrad_lds_launch<2, 4>(a, tiles * slices, st); break;
-            default:                                                    // 128 x 320: eight waves of 1 x 5 blocks (tunable wgrad_lds_tiles = -5: ten of 2 x 2)
-                if (tun(g_tun.wgrad_lds_tiles) == -5) wgrad_lds_launch<2, 5>(a, tiles * slices, st);
-                else wgrad_lds_launch<4, 2, 1, 5>(a, tiles * slices, st);
-                break;
+            default: wgrad_lds_launch<4, 2, 1, 5>(a, tiles * slices, st); break;     // 128 x 320: eight waves of 1 x 5 blocks
         }
         NIR_CHECK_LAUNCH("wgrad_lds_kernel");
         return 0;
@@ -1420,7 +1405,7 @@ static int wgrad_impl(const float* dy, int64_t lddy, const float* x, int64_t ldx
     const int nb = big ? 2 : 1, kb = big ? 2 : 1;
     const int64_t tiles = (int64_t)((N + 32 * nb - 1) / (32 * nb)) * ((K + 32 * kb - 1) / (32 * kb));
     // slices of >= 256 rows (big M) / >= 64 rows (1 x 1: a slice is then two to eight load -> MFMA round trips), as many as fill the chip
-    const int64_t minrows = (big && M >= 4096) ? 256 : std::max(32, tun(g_tun.wgrad_min_rows) > 0 ? tun(g_tun.wgrad_min_rows) : 64);
+    const int64_t minrows = big ? 256 : 64;
     int64_t slices = std::max<int64_t>(1, std::min<int64_t>((M + minrows - 1) / minrows, (4096 + tiles - 1) / tiles));
     const int64_t mslice = ((M + slices - 1) / slices + 31) / 32 * 32;
     slices = (M + mslice - 1) / mslice;
@@ -1547,10 +1532,10 @@ extern "C" int nir_lstm_train_fwd(const float* gates_in, const int64_t* lengths,
     NIR_REQUIRE(gates_in && w_hh && out && act && cst, "lstm_train_fwd: null pointer");
     NIR_REQUIRE(M >= 0 && T > 0 && (ndir == 1 || ndir == 2) && H >= 1 && H <= 128, "lstm_train_fwd: bad dims (H <= 128)");
     if (M == 0) return 0;
-    if (H >= 33 && !tun(g_tun.lstm_valu)) {
+    if (H >= 33) {
         // the inference recurrence on the f32 matrix cores (csrc/lstm_mfma.hip: 16 sequences per workgroup, W_hh resident in registers, one
         // barrier per step) with the activation / cell-state stores of train mode: 4.9 ms -> 0.4 ms at the C3 document shape against the
-        // one-thread-per-gate-row kernel below (kept for H <= 32 and as the `lstm_valu` cross-check)
+        // one-thread-per-gate-row kernel below (kept for H <= 32 and for the shapes the matrix-core form does not take)
         const int rc = launch_bilstm_mfma16(gates_in, lengths, w_hh, h0, c0, out, hn, cn, M, T, H, ndir, (hipStream_t)stream, act, cst);
         if (rc != NIR_ERR_UNSUPPORTED) return rc;
     }
@@ -1575,26 +1560,22 @@ extern "C" int nir_lstm_train_bwd(const float* dout, const float* dhn, const flo
     NIR_REQUIRE(M >= 0 && T > 0 && (ndir == 1 || ndir == 2) && H >= 1 && H <= 128, "lstm_train_bwd: bad dims (H <= 128)");
     if (M == 0) return 0;
     LstmBwdArgs a{dout, dhn, dcn, dcst, act, cst, c0, lengths, w_hh, dgates, dh0, dc0, M, T, H, ndir};
-    // W_hh resident on the matrix cores for the hidden sizes that fill 4 waves x 2 unit tiles (H <= 128); tunable lstm_valu keeps the VALU form
+    // W_hh resident on the matrix cores for the hidden sizes that fill 4 waves x 2 unit tiles (H <= 128); other shapes take the VALU form
     const int hp = (H + 3) / 4 * 4;
     // (H % 4 != 0 has no 16-byte cell IO: with scalar loads MatchTensor's H = 70 measured 666 against 427 us at 320 sequences, 1430 against
     // 1790 us at 2560; even H uses 8-byte pieces, odd H keeps the scalar form and this kernel only from 1024 sequences on)
-    if (!tun(g_tun.lstm_valu) && H >= 16 && (hp == 32 || hp == 64 || hp == 72 || hp == 96 || hp == 128) && (H % 2 == 0 || M >= 1024)) {
+    if (H >= 16 && (hp == 32 || hp == 64 || hp == 72 || hp == 96 || hp == 128) && (H % 2 == 0 || M >= 1024)) {
         const size_t ldm = (size_t)2 * 16 * 4 * (hp + 4) * 4 + 16 * 4;
         ProfScope ps(prof_shape_name("lstm_train_bwd_mfma_kernel", M, T, H), (hipStream_t)stream);
         const dim3 grid((unsigned)((M + 15) / 16), (unsigned)ndir);
         hipStream_t st = (hipStream_t)stream;
-        // more than four unit tiles: eight waves x one tile (tunable lstm_bwd_w8 = 2: the four-wave form; bit-identical results) -- C3 documents
-        // 566 -> 443 us, MatchTensor's H = 70 418 -> 372 us
-        const bool w8 = tun(g_tun.lstm_bwd_w8) != 2;
-        if (hp == 128 && w8) hipLaunchKernelGGL((lstm_train_bwd_mfma_kernel<128, 1>), grid, dim3(512), ldm, st, a);
-        else if (hp == 96 && w8) hipLaunchKernelGGL((lstm_train_bwd_mfma_kernel<96, 1>), grid, dim3(512), ldm, st, a);
-        else if (hp == 72 && w8) hipLaunchKernelGGL((lstm_train_bwd_mfma_kernel<72, 1>), grid, dim3(512), ldm, st, a);
-        else if (hp == 32) hipLaunchKernelGGL(lstm_train_bwd_mfma_kernel<32>, grid, dim3(256), ldm, st, a);
+        // more than four unit tiles: eight waves x one tile (bit-identical to four waves x two tiles) -- C3 documents 566 -> 443 us, MatchTensor's
+        // H = 70 418 -> 372 us
+        if (hp == 32) hipLaunchKernelGGL(lstm_train_bwd_mfma_kernel<32>, grid, dim3(256), ldm, st, a);
         else if (hp == 64) hipLaunchKernelGGL(lstm_train_bwd_mfma_kernel<64>, grid, dim3(256), ldm, st, a);
-        else if (hp == 72) hipLaunchKernelGGL(lstm_train_bwd_mfma_kernel<72>, grid, dim3(256), ldm, st, a);
-        else if (hp == 96) hipLaunchKernelGGL(lstm_train_bwd_mfma_kernel<96>, grid, dim3(256), ldm, st, a);
-        else hipLaunchKernelGGL(lstm_train_bwd_mfma_kernel<128>, grid, dim3(256), ldm, st, a);
+        else if (hp == 72) hipLaunchKernelGGL((lstm_train_bwd_mfma_kernel<72, 1>), grid, dim3(512), ldm, st, a);
+        else if (hp == 96) hipLaunchKernelGGL((lstm_train_bwd_mfma_kernel<96, 1>), grid, dim3(512), ldm, st, a);
+        else hipLaunchKernelGGL((lstm_train_bwd_mfma_kernel<128, 1>), grid, dim3(512), ldm, st, a);
         NIR_CHECK_LAUNCH("lstm_train_bwd_mfma_kernel");
         return 0;
     }
@@ -1682,18 +1663,7 @@ extern "C" int nir_lstm_cell_seq_bwd(const float* dh_step, int64_t ld_dh, const 
     NIR_REQUIRE(act && c && dgates && dc_prev && B >= 0 && H > 0, "lstm_cell_seq_bwd: bad args");
     if (B == 0) return 0;
     hipLaunchKernelGGL(lstm_cell_seq_bwd_kernel, g1(B * H), dim3(256), 0, (hipStream_t)stream, dh_step, ld_dh, dh_rec, dc_step, ld_dc, dc_rec, act, ldact, c,
-                       ldc, c_prev, ldcp, dgates, lddg, dc_prev, B, H, nullptr, 0, 0);
-    NIR_CHECK_LAUNCH("lstm_cell_seq_bwd_kernel");
-    return 0;
-}
-extern "C" int nir_lstm_cell_seq_bwd_masked(const float* dh_step, int64_t ld_dh, const float* dh_rec, const float* dc_rec, const float* act, int64_t ldact,
-                                            const float* c, int64_t ldc, const float* c_prev, int64_t ldcp, float* dgates, int64_t lddg, float* dc_prev,
-                                            const int64_t* lengths, int t, int t_prev, int64_t B, int H, nir_stream_t stream) {
-    using namespace nir;
-    NIR_REQUIRE(act && c && dgates && dc_prev && lengths && B >= 0 && H > 0, "lstm_cell_seq_bwd_masked: bad args");
-    if (B == 0) return 0;
-    hipLaunchKernelGGL(lstm_cell_seq_bwd_kernel, g1(B * H), dim3(256), 0, (hipStream_t)stream, dh_step, ld_dh, dh_rec, (const float*)nullptr, (int64_t)0, dc_rec,
-                       act, ldact, c, ldc, c_prev, ldcp, dgates, lddg, dc_prev, B, H, lengths, t, t_prev);
+                       ldc, c_prev, ldcp, dgates, lddg, dc_prev, B, H);
     NIR_CHECK_LAUNCH("lstm_cell_seq_bwd_kernel");
     return 0;
 }

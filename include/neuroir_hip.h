@@ -52,8 +52,8 @@ const char* nir_last_error_string(void);
  * mutate): independent callers sharing the library do not steer each other.  Returns 0. */
 int nir_set_stream_batches_in_flight(nir_stream_t stream, int n);
 /* Tuning / debug switches (kernel-family selection, fork on/off, exact f32 MFMA instead of the split-precision GEMM ...).  They
- * are read from the environment ONCE when the library is loaded (NIR_NO_FORK, NIR_LSTM_VALU, NIR_LSTM_MFMA16, NIR_LSTM_MFMA_S,
- * NIR_LSTM_S, NIR_NO_SKINNY, NIR_NO_GEMM16, NIR_ESM_WAVE_ROWS, NIR_DEBUG, NIR_EXACT_F32); this call changes one at run time by
+ * are read from the environment ONCE when the library is loaded (NIR_NO_FORK, NIR_LSTM_MFMA16, NIR_LSTM_S, NIR_DEBUG,
+ * NIR_EXACT_F32); this call changes one at run time by
  * its lower-case name without the prefix ("lstm_mfma16", ...).  Never changes results beyond fp32 rounding.
  * FROZEN in a product process: the call only takes effect when the library was loaded with NIR_DEBUG_TUNABLES set in the environment
  * (tests, profilers, bench.py's isolated-kernel pass); otherwise it returns NIR_ERR_BAD_ARG and changes nothing -- no caller can change
@@ -684,11 +684,6 @@ int nir_lstm_cell_seq_fwd(const float* gx, int64_t ldgx, const float* gh, const 
 int nir_lstm_cell_seq_bwd(const float* dh_step, int64_t ld_dh, const float* dh_rec, const float* dc_step, int64_t ld_dc, const float* dc_rec,
                           const float* act, int64_t ldact, const float* c, int64_t ldc, const float* c_prev, int64_t ldcp, float* dgates,
                           int64_t lddg, float* dc_prev, int64_t B, int H, nir_stream_t stream);
-/* The same step at position t of PADDED sequences (autograd._BiLSTM256): a row with t >= lengths[b] takes no part (zero gate gradients and
- * dc_prev, incoming gradients ignored); c_prev counts where 0 <= t_prev < lengths[b] (t_prev = position of the previous recurrence step). */
-int nir_lstm_cell_seq_bwd_masked(const float* dh_step, int64_t ld_dh, const float* dh_rec, const float* dc_rec, const float* act, int64_t ldact,
-                                 const float* c, int64_t ldc, const float* c_prev, int64_t ldcp, float* dgates, int64_t lddg, float* dc_prev,
-                                 const int64_t* lengths, int t, int t_prev, int64_t B, int H, nir_stream_t stream);
 /* Inverted dropout with a counter-based mask: keep[i] = uniform(splitmix64(seed ^ i*c)) >= p, y = x*keep/(1-p).  The mask is an
  * output so that a parity test can replay it through the oracle. */
 int nir_dropout_f32(const float* x, float* y, unsigned char* keep, int64_t n, float p, uint64_t seed, nir_stream_t stream);

@@ -60,13 +60,12 @@ def test_bilstm_backward(H, I, M, T_, bi):
     xd = x.to(DEV).requires_grad_(True)
     for packed, split in ((False, True), (True, False)):       # (64 < H <= 128: split-fp16 and fp32 recurrence; other H: the flag changes nothing)
         A.PACKED_WGRAD, A.SPLIT_TRAIN_FWD = packed, split
-        A.FUSED_BPTT256 = not packed                           # (H = 256: the one-launch-per-step BPTT and the cell kernel + GEMM per step form)
         try:
             lstm.zero_grad(); xd.grad = None
             out = A.bilstm(xd, lens.to(DEV), lstm)
             out.backward(dout.to(DEV))
         finally:
-            A.PACKED_WGRAD, A.SPLIT_TRAIN_FWD, A.FUSED_BPTT256 = False, True, True
+            A.PACKED_WGRAD, A.SPLIT_TRAIN_FWD = False, True
         _rel(out, ref, 2e-5); _rel(xd.grad, xr.grad)
         for k, p in lstm.named_parameters():
             _rel(p.grad, sd["e.rnns.0." + k].grad)

@@ -28,7 +28,7 @@ def main():
     ap.add_argument("--dtype", default="f32")
     ap.add_argument("--lens", default="full", help="full | ragged (uniform in [1, T])")
     ap.add_argument("--ids", default="uniform", help="uniform | zipf | hot (64 distinct rows: the row gathers hit in L2)")
-    ap.add_argument("--tune", default="", help="name=value,... through nir_debug_set_tunable (lstm_w16=3: two sequence groups per workgroup)")
+    ap.add_argument("--tune", default="", help="name=value,... through nir_debug_set_tunable (lstm_s=2: four waves x five tiles at 64 < H <= 80)")
     a = ap.parse_args()
     name = "libneuroir_hip%s.so" % ("_" + a.lib if a.lib else "")
     L = C.CDLL(os.path.join(ROOT, "context_attentive_ir_amd", name))

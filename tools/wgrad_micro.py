@@ -1,5 +1,5 @@
-"""dW = dY^T X (+ db) of the training step: the LDS-staged workgroup-tile kernel against the register-blocked one (tunable wgrad_no_lds)
-and torch, per shape: max |diff| relative to the fp64 product and microseconds per launch.
+"""dW = dY^T X (+ db) of the training step (nir_linear_wgrad_bias_set_f32, the kernel the shape selects) against torch, per shape: max |diff|
+relative to the fp64 product and microseconds per launch.
 
     python tools/wgrad_micro.py [--shapes 71680x1024x300,71680x512x128]
 """
@@ -8,7 +8,6 @@ import json
 import os
 import sys
 
-os.environ.setdefault("NIR_DEBUG_TUNABLES", "1")
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -35,8 +34,6 @@ def run(L, dy, x, db, set_=True, iters=20):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="71680x1024x300,71680x512x128,8960x1024x300,20000x256x512,4480x768x256")
-    ap.add_argument("--tiles", type=int, default=0, help="tunable wgrad_lds_tiles: LDS kernel for M >= 256 once the dW has this many 128 x 128 tiles")
-    ap.add_argument("--min-rows", type=int, default=0)
     a = ap.parse_args()
     L = lib.load()
     for sh in a.shapes.split(","):
@@ -47,17 +44,12 @@ def main():
         ref = (dy.double().t() @ x.double())
         refb = dy.double().sum(0)
         rec = {"shape": sh, "gflop": 2e-9 * M * N * K}
-        L.nir_debug_set_tunable(b"wgrad_lds_tiles", a.tiles)
-        L.nir_debug_set_tunable(b"wgrad_min_rows", a.min_rows)
-        for name, flag in (("lds", 0), ("regs", 1)):
-            L.nir_debug_set_tunable(b"wgrad_no_lds", flag)
-            db = torch.empty(N, device="cuda")
-            dw, us = run(L, dy, x, db)
-            rec[name + "_us"] = round(us, 1)
-            rec[name + "_tflops"] = round(rec["gflop"] / us * 1e-3, 1)
-            rec[name + "_err"] = float((dw.double() - ref).abs().max() / ref.abs().max())
-            rec[name + "_db_err"] = float((db.double() - refb).abs().max() / refb.abs().max())
-        L.nir_debug_set_tunable(b"wgrad_no_lds", 0)
+        db = torch.empty(N, device="cuda")
+        dw, us = run(L, dy, x, db)
+        rec["hip_us"] = round(us, 1)
+        rec["hip_tflops"] = round(rec["gflop"] / us * 1e-3, 1)
+        rec["hip_err"] = float((dw.double() - ref).abs().max() / ref.abs().max())
+        rec["hip_db_err"] = float((db.double() - refb).abs().max() / refb.abs().max())
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         dy.t() @ x
         t0.record()
