@@ -8,6 +8,9 @@ forward AND backward run on the hand-written HIP kernels of csrc/train.hip / csr
     bilstm      RNNEncoder in train mode: gate GEMM + nir_lstm_train_fwd (saves gate activations / cell states);
                 bwd: BPTT nir_lstm_train_bwd -> dgates, then dW_ih / dW_hh / db / dx as GEMMs
     bce_with_logits   nir_rank_loss_bce / nir_rank_loss_bce_bwd
+    max_pool    max over the middle axis with its arg-max (nir_maxpool_arg_f32; bwd scatter nir_maxpool_arg_bwd_f32)
+    cosine      query-broadcast cosine (nir_cosine_bcast_f32 / nir_cosine_bcast_bwd_f32)
+    softmax_nll list-wise softmax NLL (nir_rank_loss_softmax_nll / nir_rank_loss_softmax_nll_bwd)
 
 What stays in torch in the train-mode model forwards (models call these functions and glue them with tensor reshapes,
 concatenations, element-wise products and max-reductions) is stated in DESIGN.md section 8; every matrix product, recurrence,
@@ -982,3 +985,85 @@ class _BCE(Function):
 def bce_with_logits(scores, labels):
     """mean BCE-with-logits over all entries (models/ranker.py:55-69, multitask/cars.py:603)."""
     return _BCE.apply(scores, labels)
+
+
+class _MaxPool(Function):
+    @staticmethod
+    def forward(ctx, x):
+        lib.require_device(x)
+        xc = _f32c(x)
+        R, T, D = xc.shape
+        y = torch.empty(R, D, device=xc.device, dtype=torch.float32)
+        idx = torch.empty(R, D, device=xc.device, dtype=torch.int32)
+        lib.check(lib.load().nir_maxpool_arg_f32(lib.ptr(xc), R, T, D, lib.ptr(y), lib.ptr(idx), lib.stream()), "nir_maxpool_arg_f32")
+        ctx.save_for_backward(idx)
+        ctx.T = T
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (idx,) = ctx.saved_tensors
+        R, D = idx.shape
+        d = _f32c(dy)
+        dx = torch.empty(R, ctx.T, D, device=d.device, dtype=torch.float32)
+        lib.check(lib.load().nir_maxpool_arg_bwd_f32(lib.ptr(d), lib.ptr(idx), R, ctx.T, D, lib.ptr(dx), lib.stream()), "nir_maxpool_arg_bwd_f32")
+        return dx
+
+
+def max_pool(x):
+    """x [R,T,D] -> x.max(1)[0] (dssm.py:49,55; cdssm.py:63,71): the arg-max is kept for the scatter backward."""
+    return _MaxPool.apply(x)
+
+
+class _Cosine(Function):
+    @staticmethod
+    def forward(ctx, q, d):
+        lib.require_device(q, d)
+        qc, dc = _f32c(q), _f32c(d)
+        B, N, D = dc.shape
+        s = torch.empty(B, N, device=dc.device, dtype=torch.float32)
+        lib.check(lib.load().nir_cosine_bcast_f32(lib.ptr(qc), lib.ptr(dc), B, N, D, lib.ptr(s), lib.stream()), "nir_cosine_bcast_f32")
+        ctx.save_for_backward(qc, dc)
+        return s
+
+    @staticmethod
+    def backward(ctx, g):
+        qc, dc = ctx.saved_tensors
+        B, N, D = dc.shape
+        gc = _f32c(g)
+        dq, dd = torch.empty_like(qc), torch.empty_like(dc)
+        lib.check(lib.load().nir_cosine_bcast_bwd_f32(lib.ptr(qc), lib.ptr(dc), lib.ptr(gc), B, N, D, lib.ptr(dq), lib.ptr(dd), lib.stream()),
+                  "nir_cosine_bcast_bwd_f32")
+        return dq, dd
+
+
+def cosine(q, d):
+    """q [B,D], d [B,N,D] -> [B,N]: F.cosine_similarity(q.unsqueeze(1).expand_as(d), d, dim=2) (dssm.py:61-62, cdssm.py:74-76)."""
+    return _Cosine.apply(q, d)
+
+
+class _SoftmaxNLL(Function):
+    @staticmethod
+    def forward(ctx, scores, labels):
+        s, y = _f32c(scores), _f32c(labels)
+        loss = torch.empty(1, device=s.device)
+        n = s.shape[-1]
+        lib.check(lib.load().nir_rank_loss_softmax_nll(lib.ptr(s), lib.ptr(y), s.numel() // n, n, lib.ptr(loss), lib.stream()),
+                  "nir_rank_loss_softmax_nll")
+        ctx.save_for_backward(s, y)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        s, y = ctx.saved_tensors
+        ds = torch.empty_like(s)
+        n = s.shape[-1]
+        gg = _f32c(g).reshape(1)
+        lib.check(lib.load().nir_rank_loss_softmax_nll_bwd(lib.ptr(s), lib.ptr(y), lib.ptr(gg), s.numel() // n, n, lib.ptr(ds), lib.stream()),
+                  "nir_rank_loss_softmax_nll_bwd")
+        return ds, None
+
+
+def softmax_nll(scores, labels):
+    """-(log_softmax(scores) * labels).sum(1).mean() -- the list-wise criterion of DSSM / CDSSM (models/ranker.py:79-89)."""
+    return _SoftmaxNLL.apply(scores, labels)

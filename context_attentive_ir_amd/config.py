@@ -4,7 +4,7 @@ Mirror of the reference's config API for the five hot-path models (SURVEY.md App
   * add_model_args / get_model_args / update_model_args / override_model_args keep the call
     shapes of /root/reference/neuroir/config.py:33,98,115,123;
   * the per-model fixed hyper-parameters keep the values of /root/reference/neuroir/hyparam.py
-    (ESM :3-8, DUET :34-46, DRMM :78-86, MATCH_TENSOR :88-105, CARS :197-225).
+    (ESM :3-8, DSSM :10-20, CDSSM :22-32, DUET :34-46, DRMM :78-86, MATCH_TENSOR :88-105, CARS :197-225).
 Everything is table-driven here; models outside the hot path are not listed (they keep
 running on the reference's own stock-PyTorch classes).
 """
@@ -17,6 +17,8 @@ _LSTM = dict(rnn_type="LSTM", bidirection=True, nlayers=1, dropout_rnn=0.2)
 
 MODEL_ARCHITECTURE = {
     "ESM": dict(arch={}, data={}),
+    "DSSM": dict(arch=dict(nhid=300, nout=128), data=dict(use_char_ngram=3, src_vocab_size=30000, embedding_file="")),
+    "CDSSM": dict(arch=dict(nhid=300, nout=128), data=dict(use_char_ngram=3, src_vocab_size=30000, embedding_file="")),
     "DUET": dict(arch=dict(nfilters=300, local_filter_size=1, dist_filter_size=3, pool_size=5),
                  data=dict(src_vocab_size=None, force_pad=True, fix_embeddings=True)),
     "DRMM": dict(arch=dict(nbins=5), data=dict(src_vocab_size=None, fix_embeddings=True)),

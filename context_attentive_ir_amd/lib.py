@@ -40,6 +40,8 @@ DuetWeights = _struct(
 DuetWeights = type("nir_duet_weights", (C.Structure,), {"_fields_": list(DuetWeights._fields_) + [
     (f, C.c_void_p) for f in ("table_h1", "table_h2", "convd1_h1", "convd1_h2", "convd2_h1", "convd2_h2")] + [("EP", C.c_int)] + [
     ("fw1", C.c_void_p), ("fw2", C.c_void_p), ("K1P", C.c_int), ("ftable", C.c_void_p), ("fw1c", C.c_void_p), ("EPT", C.c_int)]})
+DssmWeights = _struct("nir_dssm_weights", ["q_w1t", "q_b1", "q_w2t", "q_b2", "d_w1t", "d_b1", "d_w2t", "d_b2"], ["NH", "NO"])
+CdssmWeights = _struct("nir_cdssm_weights", ["q_w5t", "q_b", "q_semt", "q_semb", "d_w5t", "d_b", "d_semt", "d_semb"], ["NH", "NO"])
 CarsEncoderWeights = _struct(
     "nir_cars_encoder_weights",
     ["wih", "whh", "bih", "bhh", "attn0_w", "attn0_b", "attn3_w", "attn3_b"], ["H", "bounded"])
@@ -133,6 +135,15 @@ SIGNATURES = {
     "nir_duet_workspace_bytes": (_z, [_i, _i, _i, _i, _i, C.POINTER(DuetWeights)]),
     "nir_duet_score": (_i, [c_ip, c_ip, _i, _i, _i, _i, c_fp, _l, _i, C.POINTER(DuetWeights), C.c_void_p, _z,
                             c_fp, c_fp, c_fp, c_st]),
+    "nir_dssm_workspace_bytes": (_z, [_i, _i, _i]),
+    "nir_dssm_score": (_i, [c_ip, c_ip, _i, _i, _i, _i, c_fp, _l, _i, _l, C.POINTER(DssmWeights), C.c_void_p, _z, c_fp, c_fp, c_fp, c_st]),
+    "nir_cdssm_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "nir_cdssm_score": (_i, [c_ip, c_ip, _i, _i, _i, _i, c_fp, _l, _i, _l, C.POINTER(CdssmWeights), C.c_void_p, _z, c_fp, c_fp, c_fp, c_st]),
+    "nir_maxpool_arg_f32": (_i, [c_fp, _l, _i, _i, c_fp, C.c_void_p, c_st]),
+    "nir_maxpool_arg_bwd_f32": (_i, [c_fp, C.c_void_p, _l, _i, _i, c_fp, c_st]),
+    "nir_cosine_bcast_f32": (_i, [c_fp, c_fp, _l, _i, _i, c_fp, c_st]),
+    "nir_cosine_bcast_bwd_f32": (_i, [c_fp, c_fp, c_fp, _l, _i, _i, c_fp, c_fp, c_st]),
+    "nir_rank_loss_softmax_nll_bwd": (_i, [c_fp, c_fp, c_fp, _l, _i, c_fp, c_st]),
     "nir_cars_encode_workspace_bytes": (_z, [_l, _i, _i, C.POINTER(CarsEncoderWeights)]),
     "nir_cars_encode": (_i, [c_ip, c_ip, _l, _i, c_fp, _l, _i, C.POINTER(CarsEncoderWeights), C.c_void_p, _z,
                              c_fp, c_fp, c_st]),

@@ -2,5 +2,7 @@ from .esm import ESM
 from .mtensor import MatchTensor
 from .drmm import DRMM
 from .duet import DUET
+from .dssm import DSSM
+from .cdssm import CDSSM
 
-__all__ = ["ESM", "MatchTensor", "DRMM", "DUET"]
+__all__ = ["ESM", "MatchTensor", "DRMM", "DUET", "DSSM", "CDSSM"]

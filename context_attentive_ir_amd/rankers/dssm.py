@@ -1,0 +1,69 @@
+"""DSSM (drop-in for neuroir.rankers.dssm.DSSM, /root/reference/neuroir/rankers/dssm.py:8-63).
+
+rep = tanh(W2 tanh(W1 x + b1) + b2) per tower, x = max over ALL padded positions of the embedded ids; score = cos(rep_q, rep_d).
+Eval: one C-ABI call (nir_dssm_score), two launches -- the tower kernel (query and document rows in one launch: gather + max, both
+layers) and the cosine.  The lengths are ignored like in the reference; the max runs over the padded width, the PAD row included
+wherever a row has padding (read from the table: a loaded state dict may hold a non-zero PAD row).
+Train mode: autograd.embed -> dropout -> max_pool -> linear (x2) -> cosine, all on the HIP operators.
+"""
+import torch
+import torch.nn as nn
+
+from .. import autograd as A
+from .. import lib
+from ..constants import PAD
+from ..modules import Embeddings
+
+
+class DSSM(nn.Module, lib.IdCheck):
+    def __init__(self, args):
+        super().__init__()
+        self.word_embeddings = Embeddings(args.emsize, args.src_vocab_size, PAD)
+        self.emb_drop = nn.Dropout(p=args.dropout_emb)
+        self.query_mlp = nn.Sequential(nn.Linear(args.emsize, args.nhid), nn.Tanh(), nn.Linear(args.nhid, args.nout), nn.Tanh())
+        self.doc_mlp = nn.Sequential(nn.Linear(args.emsize, args.nhid), nn.Tanh(), nn.Linear(args.nhid, args.nout), nn.Tanh())
+        self._pack = lib.PackCache()
+
+    def _weights(self):
+        def build():
+            q, d = self.query_mlp, self.doc_mlp
+            t = dict(q_w1t=q[0].weight.t(), q_b1=q[0].bias, q_w2t=q[2].weight.t(), q_b2=q[2].bias,
+                     d_w1t=d[0].weight.t(), d_b1=d[0].bias, d_w2t=d[2].weight.t(), d_b2=d[2].bias)
+            return lib.Packed(lib.DssmWeights, t, dict(NH=q[0].out_features, NO=q[2].out_features))
+        return self._pack.get(list(self.query_mlp.parameters()) + list(self.doc_mlp.parameters()), build)
+
+    def _forward_train(self, q, d):
+        B, QL = q.shape
+        N, DL = d.shape[1], d.shape[2]
+        table = self.word_embeddings.table
+        eq = A.dropout(A.embed(q, table, PAD), self.emb_drop.p, True)
+        ed = A.dropout(A.embed(d.reshape(B * N, DL), table, PAD), self.emb_drop.p, True)
+
+        def mlp(x, m):
+            return A.linear(A.linear(x, m[0].weight, m[0].bias, act="tanh"), m[2].weight, m[2].bias, act="tanh")
+        rq = mlp(A.max_pool(eq), self.query_mlp)
+        rd = mlp(A.max_pool(ed), self.doc_mlp)
+        return A.cosine(rq, rd.view(B, N, -1))
+
+    def forward(self, batch_queries, query_len, batch_docs, doc_len, return_reps=False):
+        """scores [B,N]; return_reps: also the tower outputs rep_q [B,nout] / rep_d [B,N,nout] (eval only)."""
+        assert batch_queries.shape[0] == batch_docs.shape[0]
+        table = self.word_embeddings.table
+        lib.require_device(batch_queries, batch_docs, table)
+        q, d = self._clean_ids(batch_queries, batch_docs, table.shape[0])
+        B, QL = q.shape
+        N, DL = d.shape[1], d.shape[2]
+        if self.training and not return_reps:
+            return self._forward_train(q, d)
+        L = lib.load()
+        w = self._weights()
+        dev = q.device
+        NO = w.struct.NO
+        scores = torch.empty(B, N, device=dev, dtype=torch.float32)
+        rq = torch.empty(B, NO, device=dev, dtype=torch.float32) if return_reps else None
+        rd = torch.empty(B, N, NO, device=dev, dtype=torch.float32) if return_reps else None
+        if B > 0:
+            ws = lib.workspace(L.nir_dssm_workspace_bytes(B, N, NO), dev)
+            lib.check(L.nir_dssm_score(lib.ptr(q), lib.ptr(d), B, N, QL, DL, lib.ptr(table), table.shape[0], table.shape[1], PAD, w.ref(),
+                                       lib.ptr(ws), ws.numel(), lib.ptr(scores), lib.ptr(rq), lib.ptr(rd), lib.stream()), "nir_dssm_score")
+        return (scores, rq, rd) if return_reps else scores

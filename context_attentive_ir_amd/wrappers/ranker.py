@@ -9,11 +9,12 @@ shard the CANDIDATE axis over the ranks of a torch.distributed group and all-gat
 import torch
 
 from .. import lib, sharding
-from ..rankers import DRMM, DUET, ESM, MatchTensor
+from ..rankers import CDSSM, DRMM, DSSM, DUET, ESM, MatchTensor
 from .common import WrapperBase
 
-NETWORKS = {"ESM": ESM, "DUET": DUET, "DRMM": DRMM, "MATCH_TENSOR": MatchTensor}
+NETWORKS = {"ESM": ESM, "DUET": DUET, "DRMM": DRMM, "MATCH_TENSOR": MatchTensor, "DSSM": DSSM, "CDSSM": CDSSM}
 BCE_MODELS = {"DUET", "DRMM", "MATCH_TENSOR"}
+NLL_MODELS = {"DSSM", "CDSSM"}        # Ranker.compute_loss: list-wise softmax NLL (models/ranker.py:43-48, 79-89)
 
 
 class Ranker(WrapperBase):
@@ -97,14 +98,14 @@ class Ranker(WrapperBase):
 
     @torch.no_grad()
     def loss(self, ex):
-        """forward + criterion of the model (BCEWithLogits, models/ranker.py:55-69); ESM has none."""
-        if self.kind not in BCE_MODELS:
+        """forward + criterion of the model (BCEWithLogits, models/ranker.py:55-69; DSSM / CDSSM: softmax NLL, :79-89); ESM has none."""
+        if self.kind not in BCE_MODELS and self.kind not in NLL_MODELS:
             raise RuntimeError("%s has no training criterion (main/ranker.py:414)" % self.kind)
         s = self.scores(ex).contiguous()
         y = ex["label"].to(s.device).float().contiguous()
         out = torch.empty(1, device=s.device)
-        lib.check(lib.load().nir_rank_loss_bce(lib.ptr(s), lib.ptr(y), s.shape[0], s.shape[1], lib.ptr(out),
-                                               lib.stream()), "nir_rank_loss_bce")
+        fn = "nir_rank_loss_softmax_nll" if self.kind in NLL_MODELS else "nir_rank_loss_bce"
+        lib.check(getattr(lib.load(), fn)(lib.ptr(s), lib.ptr(y), s.shape[0], s.shape[1], lib.ptr(out), lib.stream()), fn)
         return out[0]
 
     def update(self, ex):
@@ -113,7 +114,7 @@ class Ranker(WrapperBase):
         torch.optim, as in the reference."""
         if self.optimizer is None:
             raise RuntimeError("No optimizer set.")
-        if self.kind not in BCE_MODELS:
+        if self.kind not in BCE_MODELS and self.kind not in NLL_MODELS:
             raise RuntimeError("%s has no training criterion (main/ranker.py:414)" % self.kind)
         if not hasattr(self.network, "_forward_train"):
             raise NotImplementedError("%s has no train-mode forward" % self.kind)
@@ -135,7 +136,7 @@ class Ranker(WrapperBase):
             labels = ex["label"].float()
             labels = labels.cuda(non_blocking=True) if self.use_cuda else labels
             scores = self.network(q, ql, d, dl)
-            loss = A.bce_with_logits(scores, labels)
+            loss = (A.softmax_nll if self.kind in NLL_MODELS else A.bce_with_logits)(scores, labels)
             loss.backward()
         except BaseException:
             A.STEP.abort()

@@ -310,6 +310,46 @@ int nir_duet_score(const int64_t* q_ids, const int64_t* d_ids, int B, int N, int
                    size_t workspace_bytes, float* scores, float* local_out, float* dist_out, nir_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * DSSM  (neuroir/rankers/dssm.py:33-63) and CDSSM (neuroir/rankers/cdssm.py:42-77):  score[b,n] = cos(rep(q_b), rep(d_bn))
+ *   DSSM   rep = tanh(W2 tanh(W1 x + b1) + b2),  x = max over ALL padded positions of table[id]
+ *   CDSSM  rep = max over the L-4 windows j of tanh(S tanh(W5 [x_j; ..; x_{j+4}] + b) + s),  W5 = the Conv1d(3E -> NH, k=3) weight
+ *          over the 3-row interleave (cdssm.py:33-41) folded into 5 taps: W5[o][m][e] = sum_{i+k=m} W[o][i E + e][k]
+ * Lengths are not inputs: like the reference the max runs over the padded width.  The kernels evaluate a row up to its last non-PAD
+ * id and fold the all-PAD vector (DSSM: the table's PAD row; CDSSM: the tower on a window of PAD ids) into the max of rows that have
+ * such a tail -- exact.  fp32 arithmetic.  Per call: 2 launches (tower, cosine).  rep_q [B,NO] / rep_d [B*N,NO]: optional outputs.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    const float *q_w1t, *q_b1, *q_w2t, *q_b2;  /* query_mlp.0.weight^T [E][NH], .0.bias, query_mlp.2.weight^T [NH][NO], .2.bias */
+    const float *d_w1t, *d_b1, *d_w2t, *d_b2;  /* doc_mlp, same layouts */
+    int NH, NO;                                /* nhid, nout (NO <= 256) */
+} nir_dssm_weights;
+size_t nir_dssm_workspace_bytes(int B, int N, int NO);
+int nir_dssm_score(const int64_t* q_ids, const int64_t* d_ids, int B, int N, int QL, int DL, const float* table, int64_t V, int E, int64_t pad,
+                   const nir_dssm_weights* w /*host*/, void* workspace, size_t workspace_bytes, float* scores, float* rep_q, float* rep_d,
+                   nir_stream_t stream);
+typedef struct {
+    const float *q_w5t, *q_b, *q_semt, *q_semb;  /* folded query_conv weight [5E][NH] (row m E + e), query_conv.bias, query_sem.weight^T [NH][NO], .bias */
+    const float *d_w5t, *d_b, *d_semt, *d_semb;  /* doc_conv / doc_sem, same layouts */
+    int NH, NO;                                  /* nhid <= 320, nout <= 256 */
+} nir_cdssm_weights;
+/* 0 when QL or DL is below the 5-token window (nir_cdssm_score rejects such widths: the reference raises for them) */
+size_t nir_cdssm_workspace_bytes(int B, int N, int QL, int DL, int NO);
+int nir_cdssm_score(const int64_t* q_ids, const int64_t* d_ids, int B, int N, int QL, int DL, const float* table, int64_t V, int E, int64_t pad,
+                    const nir_cdssm_weights* w /*host*/, void* workspace, size_t workspace_bytes, float* scores, float* rep_q, float* rep_d,
+                    nir_stream_t stream);
+/* Training operators of the two models.  nir_maxpool_arg_f32: y[r][d] = max_t x[r][t][d] with its first arg-max (int32) -- the max-pools of
+ * dssm.py:49,55 and cdssm.py:63,71;  backward: dx[r][t][d] = dy[r][d] at the arg-max, 0 elsewhere (every element written).
+ * nir_cosine_bcast_f32: s[b][n] = ATen cosine_similarity(q[b], d[b][n]) (dssm.py:61-62; D <= 256);  backward (D <= 512): dq[b] sums the
+ * candidates' contributions, dd[b][n] = g[b][n] ds/dd.
+ * nir_rank_loss_softmax_nll_bwd: dscores = grad_out[0] (softmax(s) sum_j y_j - y) / rows  (backward of nir_rank_loss_softmax_nll). */
+int nir_maxpool_arg_f32(const float* x, int64_t R, int T, int D, float* y, int* idx, nir_stream_t stream);
+int nir_maxpool_arg_bwd_f32(const float* dy, const int* idx, int64_t R, int T, int D, float* dx, nir_stream_t stream);
+int nir_cosine_bcast_f32(const float* q, const float* d, int64_t B, int N, int D, float* s, nir_stream_t stream);
+int nir_cosine_bcast_bwd_f32(const float* q, const float* d, const float* g, int64_t B, int N, int D, float* dq, float* dd, nir_stream_t stream);
+int nir_rank_loss_softmax_nll_bwd(const float* scores, const float* labels, const float* grad_out, int64_t rows, int n, float* dscores,
+                                  nir_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * CARS ranking path  (neuroir/multitask/cars.py:193-540, 671-691; neuroir/modules/maxout.py:70-84)
  * ------------------------------------------------------------------------------------------------ */
 typedef struct {
