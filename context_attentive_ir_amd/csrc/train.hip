@@ -1143,6 +1143,17 @@ __global__ void embed_kernel(const int64_t* __restrict__ ids, const float* __res
     if (id < 0 || id >= V) { if (err) atomicOr(err, 1); id = 0; }
     *reinterpret_cast<float4*>(out + m * E + c) = *reinterpret_cast<const float4*>(table + id * E + c);
 }
+// the same lookup for E % 4 != 0 (rows not 16-byte aligned): one element per thread
+__global__ void embed1_kernel(const int64_t* __restrict__ ids, const float* __restrict__ table, int64_t V, int E, int64_t M, float* __restrict__ out,
+                              int* err) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M * E) return;
+    const int64_t m = i / E;
+    const int c = (int)(i % E);
+    int64_t id = ids[m];
+    if (id < 0 || id >= V) { if (err) atomicOr(err, 1); id = 0; }
+    out[i] = table[id * E + c];
+}
 __global__ void embed_bwd_kernel(const int64_t* __restrict__ ids, const float* __restrict__ dout, int64_t V, int E, int64_t M, float* __restrict__ dtable,
                                  int64_t pad_idx) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1691,10 +1702,15 @@ extern "C" int nir_softmax_pool_bwd(const float* weights, const float* dout, con
 }
 extern "C" int nir_embed_f32(const int64_t* ids, const float* table, int64_t V, int E, int64_t M, float* out, int* err_flag, nir_stream_t stream) {
     using namespace nir;
-    NIR_REQUIRE(ids && table && out && V > 0 && E > 0 && E % 4 == 0 && M >= 0, "embed: bad args (E %% 4 == 0)");
+    NIR_REQUIRE(ids && table && out && V > 0 && E > 0 && M >= 0, "embed: bad args");
     if (M == 0) return 0;
-    hipLaunchKernelGGL(embed_kernel, g1(M * (E / 4)), dim3(256), 0, (hipStream_t)stream, ids, table, V, E, M, out, err_flag);
-    NIR_CHECK_LAUNCH("embed_kernel");
+    if (E % 4 == 0) {
+        hipLaunchKernelGGL(embed_kernel, g1(M * (E / 4)), dim3(256), 0, (hipStream_t)stream, ids, table, V, E, M, out, err_flag);
+        NIR_CHECK_LAUNCH("embed_kernel");
+    } else {
+        hipLaunchKernelGGL(embed1_kernel, g1(M * E), dim3(256), 0, (hipStream_t)stream, ids, table, V, E, M, out, err_flag);
+        NIR_CHECK_LAUNCH("embed1_kernel");
+    }
     return 0;
 }
 extern "C" int nir_embed_bwd_f32(const int64_t* ids, const float* dout, int64_t V, int E, int64_t M, float* dtable, int64_t pad_idx, nir_stream_t stream) {

@@ -19,6 +19,22 @@ from ..constants import PAD
 from ..modules import Embeddings
 
 TAPS = 5
+# The eval kernels' envelope (csrc/dssm.hip, nir_cdssm_score), checked at construction so that a model the training operators accept
+# cannot fail later at its first eval forward: cdssm_tile_kernel owns one conv column per thread (320 threads), rank_finish_kernel
+# holds 4 of the representation, and the tile kernel's LDS holds 40 staged floats per embedding column (2 x 20 window rows), within
+# the 159 KiB the launch reserves.
+MAX_NHID, MAX_NOUT, TILE_LDS_BYTES = 320, 256, 160 * 1024 - 1024
+MAX_EMSIZE = TILE_LDS_BYTES // (40 * 4)
+
+
+def check_arch(emsize, nhid, nout):
+    if not (0 < emsize <= MAX_EMSIZE):
+        raise ValueError("CDSSM: emsize %d unsupported (1 <= emsize <= %d: 160 bytes of LDS per column, %d bytes in all)"
+                         % (emsize, MAX_EMSIZE, TILE_LDS_BYTES))
+    if not (0 < nhid <= MAX_NHID):
+        raise ValueError("CDSSM: nhid %d unsupported (1 <= nhid <= %d)" % (nhid, MAX_NHID))
+    if not (0 < nout <= MAX_NOUT):
+        raise ValueError("CDSSM: nout %d unsupported (1 <= nout <= %d)" % (nout, MAX_NOUT))
 
 
 def fold_taps(weight, window=3):
@@ -32,6 +48,7 @@ def fold_taps(weight, window=3):
 class CDSSM(nn.Module, lib.IdCheck):
     def __init__(self, args):
         super().__init__()
+        check_arch(args.emsize, args.nhid, args.nout)
         self.window = 3
         self.word_embeddings = Embeddings(args.emsize, args.src_vocab_size, PAD)
         self.emb_drop = nn.Dropout(p=args.dropout_emb)

@@ -14,10 +14,26 @@ from .. import lib
 from ..constants import PAD
 from ..modules import Embeddings
 
+# The eval kernels' envelope (csrc/dssm.hip, nir_dssm_score), checked at construction so that a model the training operators accept
+# cannot fail later at its first eval forward: a dssm_tower_kernel lane gathers 8 of the 64-column groups of an embedded row,
+# rank_finish_kernel holds 4 of the representation, and the tower kernel keeps 4 E + E + nhid floats in 64 KiB of LDS.
+MAX_EMSIZE, MAX_NOUT, TOWER_LDS_BYTES = 512, 256, 64 * 1024
+
+
+def check_arch(emsize, nhid, nout):
+    if not (0 < emsize <= MAX_EMSIZE):
+        raise ValueError("DSSM: emsize %d unsupported (1 <= emsize <= %d)" % (emsize, MAX_EMSIZE))
+    if not (0 < nout <= MAX_NOUT):
+        raise ValueError("DSSM: nout %d unsupported (1 <= nout <= %d)" % (nout, MAX_NOUT))
+    if nhid <= 0 or (5 * emsize + nhid) * 4 > TOWER_LDS_BYTES:
+        raise ValueError("DSSM: nhid %d unsupported at emsize %d (1 <= nhid, (5 emsize + nhid) floats <= %d bytes of LDS)"
+                         % (nhid, emsize, TOWER_LDS_BYTES))
+
 
 class DSSM(nn.Module, lib.IdCheck):
     def __init__(self, args):
         super().__init__()
+        check_arch(args.emsize, args.nhid, args.nout)
         self.word_embeddings = Embeddings(args.emsize, args.src_vocab_size, PAD)
         self.emb_drop = nn.Dropout(p=args.dropout_emb)
         self.query_mlp = nn.Sequential(nn.Linear(args.emsize, args.nhid), nn.Tanh(), nn.Linear(args.nhid, args.nout), nn.Tanh())

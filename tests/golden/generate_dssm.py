@@ -4,7 +4,10 @@
 Reuses generate.py's compatibility shims, deterministic weights and helpers by import; like there, the fixtures carry ids and
 outputs only -- every consumer regenerates the weights from their state-dict keys (context_attentive_ir_amd.detinit).
 
-    python tests/golden/generate_dssm.py          # rewrites tests/golden/dssm.npz and cdssm.npz
+    python tests/golden/generate_dssm.py          # rewrites tests/golden/dssm.npz, cdssm.npz, dssm_arch.npz and cdssm_arch.npz
+
+dssm_arch.npz / cdssm_arch.npz hold one case each at a non-default emsize / nhid / nout (recorded under "arch"): an emsize off the
+64-column groups with nhid % 8 != 0 and nout > 160 for DSSM, an emsize past the 64 KiB LDS line with the largest nhid and nout for CDSSM.
 """
 import json
 import os
@@ -69,8 +72,28 @@ def gen(name, cls, seed):
     G.save(name, **out)
 
 
+# non-default sizes: (emsize, nhid, nout), widths (QL, DL); the CDSSM documents span two 32-window tiles
+ARCH = {"dssm": (dict(emsize=37, nhid=257, nout=200), (9, 70)), "cdssm": (dict(emsize=416, nhid=320, nout=256), (9, 40))}
+
+
+@torch.no_grad()
+def gen_arch(name, cls, seed):
+    rng = np.random.default_rng(seed)
+    arch, (QL, DL) = ARCH[name]
+    m = G.load_det(cls(G.base_args(name.upper(), dropout_emb=0.2, fix_embeddings=False, **arch)))
+    q, ql, d, dl = batches(rng, 3, 4, QL, DL)
+    s, p = run(m, q, ql, d, dl)
+    emb = m.word_embeddings.word_lut.weight
+    emb[0] = PAD_ROW_SCALE * emb[1]
+    sp, pp = run(m, q, ql, d, dl)
+    G.save(name + "_arch", arch=np.asarray(json.dumps(arch)), que_rep=q, que_len=ql, doc_rep=d, doc_len=dl, scores=s, softmax=p,
+           scores_padrow=sp, softmax_padrow=pp, pad_row_scale=np.asarray(PAD_ROW_SCALE))
+
+
 if __name__ == "__main__":
     torch.manual_seed(G.SEED)
     torch.set_num_threads(4)
     gen("dssm", DSSM, 11)
     gen("cdssm", CDSSM, 12)
+    gen_arch("dssm", DSSM, 13)
+    gen_arch("cdssm", CDSSM, 14)

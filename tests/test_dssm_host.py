@@ -82,3 +82,28 @@ def test_models_need_the_device():
     m = DSSM(default_args("dssm", src_vocab_size=50, emsize=8, nhid=6, nout=4))
     with pytest.raises(RuntimeError, match="ROCm device"):
         m(torch.ones(2, 3, dtype=torch.long), None, torch.ones(2, 3, 4, dtype=torch.long), None)
+
+
+@pytest.mark.parametrize("kind,emsize,nhid,nout,limit", [
+    ("dssm", 513, 300, 128, "emsize 513 unsupported .*<= 512"),
+    ("dssm", 300, 300, 257, "nout 257 unsupported .*<= 256"),
+    ("dssm", 512, 13825, 128, "nhid 13825 unsupported at emsize 512 .*65536 bytes of LDS"),
+    ("cdssm", 1018, 320, 128, "emsize 1018 unsupported .*<= 1017"),
+    ("cdssm", 300, 321, 128, "nhid 321 unsupported .*<= 320"),
+    ("cdssm", 300, 300, 257, "nout 257 unsupported .*<= 256"),
+])
+def test_models_reject_sizes_the_eval_kernels_cannot_run(kind, emsize, nhid, nout, limit):
+    """The training operators accept any size, the eval kernels do not (csrc/dssm.hip): construction refuses what a later predict() would,
+    naming the limit, and the largest admitted sizes still construct."""
+    from context_attentive_ir_amd.rankers import CDSSM, DSSM
+    from context_attentive_ir_amd.wrappers import Ranker
+    cls = DSSM if kind == "dssm" else CDSSM
+    with pytest.raises(ValueError, match=limit):
+        cls(default_args(kind, src_vocab_size=20, emsize=emsize, nhid=nhid, nout=nout))
+    with pytest.raises(ValueError, match=limit):
+        Ranker(default_args(kind, src_vocab_size=20, emsize=emsize, nhid=nhid, nout=nout))
+    for bad in (dict(emsize=0), dict(nhid=0), dict(nout=0)):
+        with pytest.raises(ValueError, match="unsupported"):
+            cls(default_args(kind, src_vocab_size=20, **dict(dict(emsize=8, nhid=6, nout=4), **bad)))
+    biggest = dict(emsize=512, nhid=13824, nout=256) if kind == "dssm" else dict(emsize=1017, nhid=320, nout=256)
+    cls(default_args(kind, src_vocab_size=4, **biggest))
