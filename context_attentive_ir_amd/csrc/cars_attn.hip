@@ -13,13 +13,9 @@
 #include <algorithm>
 #include <mutex>
 #include <type_traits>
-#include "common.hpp"
+#include "split2.hpp"
 
 namespace nir {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int AP_D = 256;                   // 2H
 constexpr int AP_ROWS = 64, AP_RT = 4, AP_CT = 4, AP_S = AP_D / 32;
@@ -27,17 +23,6 @@ constexpr int AP_KG = AP_ROWS * 8 + 32;     // halves per k-group block [row][8]
 constexpr int AP_PLANE_HALVES = 2 * AP_S * 4 * AP_KG;            // [2 terms][8 k-steps][4 k-groups][KG]
 constexpr int AP_RED_FLOATS = 4 * 16 * AP_D;                     // weighted-sum partials [4 waves][<= 16 sequences][256] (overlays the planes)
 constexpr size_t AP_LDS = (size_t)(AP_PLANE_HALVES * 2 > AP_RED_FLOATS * 4 ? AP_PLANE_HALVES * 2 : AP_RED_FLOATS * 4) + (4 * 64 + 64) * 4;
-
-#define AP_MMA(ACC, A, W) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(ACC) : "v"(A), "v"(W))
-#define AP_MMA_DRAIN() asm volatile("s_nop 15\n\ts_nop 15" ::: "memory")
-
-__device__ __forceinline__ void ap_mma_n(int n, f32x4 (&acc)[AP_CT][AP_RT], f32x4 (&acx)[AP_CT][AP_RT], const f16x8 (&af)[AP_RT][2],
-                                         const f16x8 (&w)[AP_CT][2]) {
-    const int j = n / (3 * AP_RT), ph = (n / AP_RT) % 3, i = n % AP_RT;
-    if (ph == 0) AP_MMA(acx[j][i], af[i][1], w[j][0]);
-    else if (ph == 1) AP_MMA(acx[j][i], af[i][0], w[j][1]);
-    else AP_MMA(acc[j][i], af[i][0], w[j][0]);
-}
 
 // max / sum over aligned groups of T lanes (T a power of two, 4..64): DPP inside 16-lane rows, ds_bpermute only across rows
 __device__ __forceinline__ float ap_group_max(float v, int T) {
@@ -104,12 +89,10 @@ __global__ __launch_bounds__(256, 1) void attn_pool_fused_kernel(AttnPoolArgs p)
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const float4 v = hv[j];
-            const fp16x2_t a01 = __builtin_amdgcn_cvt_pkrtz(v.x, v.y), a23 = __builtin_amdgcn_cvt_pkrtz(v.z, v.w);
-            const fp16x2_t b01 = __builtin_amdgcn_cvt_pkrtz((v.x - (float)a01[0]) * 2048.0f, (v.y - (float)a01[1]) * 2048.0f);
-            const fp16x2_t b23 = __builtin_amdgcn_cvt_pkrtz((v.z - (float)a23[0]) * 2048.0f, (v.w - (float)a23[1]) * 2048.0f);
+            const Split2x4 s = split2(v);
             unsigned short* d = Pp + (sk * 4 + kg) * KG + (wave + 4 * j) * 8 + e0;
-            *reinterpret_cast<uint2*>(d) = make_uint2(__builtin_bit_cast(unsigned, a01), __builtin_bit_cast(unsigned, a23));
-            *reinterpret_cast<uint2*>(d + AP_S * 4 * KG) = make_uint2(__builtin_bit_cast(unsigned, b01), __builtin_bit_cast(unsigned, b23));
+            *reinterpret_cast<uint2*>(d) = s.hi;
+            *reinterpret_cast<uint2*>(d + AP_S * 4 * KG) = s.lo;
         }
     }
     f32x4 acc[AP_CT][AP_RT], acx[AP_CT][AP_RT];
@@ -143,7 +126,7 @@ __global__ __launch_bounds__(256, 1) void attn_pool_fused_kernel(AttnPoolArgs p)
         const _Float16* wn_ = wp + (int64_t)sn_ * WSTEP;                                  \
         const unsigned short* pn_ = Pp + sn_ * 4 * KG + foff;                             \
         _Pragma("clang loop unroll(full)") for (int n_ = 0; n_ < 3 * AP_RT * AP_CT; ++n_) { \
-            ap_mma_n(n_, acc, acx, AFC, WC);                                              \
+            mma_n(n_, acc, acx, AFC, WC);                                              \
             if (n_ == 8) { AP_KEEP_HEAD(WN, AFN) }                                        \
             if (n_ % 6 == 2 && n_ / 6 < 2 * AP_CT)                                        \
                 WN[(n_ / 6) >> 1][(n_ / 6) & 1] = *reinterpret_cast<const f16x8*>(wn_ + (n_ / 6) * 512); \
@@ -159,7 +142,7 @@ __global__ __launch_bounds__(256, 1) void attn_pool_fused_kernel(AttnPoolArgs p)
         AP_STEP(s, afa, afb, w, wb)
         AP_STEP(s + 1, afb, afa, wb, w)
     }
-    AP_MMA_DRAIN();
+    MMA_DRAIN();
     // the fp32 rows again for the weighted sum (L2 hits; holding them across the k-loop cost 64 VGPRs and pushed fragments into AGPR
     // spills): issued here, consumed after the softmax
     float4 hv[16];
@@ -186,7 +169,7 @@ __global__ __launch_bounds__(256, 1) void attn_pool_fused_kernel(AttnPoolArgs p)
             for (int i = 0; i < AP_RT; ++i)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float z = fmaf(fmaf(acx[j][i][r], 1.0f / 2048.0f, acc[j][i][r]), C2, bz);
+                    const float z = fmaf(split2_combine(acc[j][i][r], acx[j][i][r]), C2, bz);
                     const float th = fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z)), 1.0f);
                     rs[i][r] = fmaf(w3c, th, rs[i][r]);
                 }
@@ -288,10 +271,10 @@ template <bool ONE, bool ROW1>
 __device__ __forceinline__ void ap2_mma_n(int n, f32x4 (&acc)[AP_CT][AP_RT], f32x4 (&acx)[AP_CT][AP_RT], const f16x8 (&af)[AP_RT][2],
                                           const f16x8 (&w)[AP_CT][2]) {
     const int i = n / (3 * AP_CT), ph = (n / AP_CT) % 3, j = n % AP_CT;      // row tile outermost
-    if (ph == 2) AP_MMA(acc[j][i], af[i][0], w[j][0]);
+    if (ph == 2) MMA_A(acc[j][i], af[i][0], w[j][0]);
     else if (ONE) return;                                                      // leading fp16 term only (bf16 encoders)
-    else if (ph == 0) { if (!ROW1) AP_MMA(acx[j][i], af[i][1], w[j][0]); }
-    else AP_MMA(acx[j][i], af[i][0], w[j][1]);
+    else if (ph == 0) { if (!ROW1) MMA_A(acx[j][i], af[i][1], w[j][0]); }
+    else MMA_A(acx[j][i], af[i][0], w[j][1]);
 }
 
 // ONE: the encoder runs in bf16 (bf16 folded table + bf16 recurrence): h and W0 enter the attention MLP as single fp16 terms (11
@@ -413,7 +396,7 @@ __global__ __launch_bounds__(512, 1) void attn_pool_pipe_kernel(AttnPoolArgs p, 
                 AP2_STEP(AP_S - 2, wa, wb, 0, 0)
                 AP2_STEP(AP_S - 1, wb, wa, 1, 1)
                 if (w4 == 0) { AP_T(1) }
-                AP_MMA_DRAIN();
+                MMA_DRAIN();
                 {   // logits: tanh, times w3, summed over this wave's 64 columns
                     // sum_c w3_c tanh(z_c) = -2 ( sum_c w3_c / (1 + 2^(C2 z_c)) - sum_c w3_c / 2 ): the lane accumulates w3_c / (1 + 2^..) starting from
                     // -1/2 of its four w3 (one FMA per value less than forming tanh first); the factor -2 is applied once per row after the reduction
@@ -436,7 +419,8 @@ __global__ __launch_bounds__(512, 1) void attn_pool_pipe_kernel(AttnPoolArgs p, 
                         for (int i = 0; i < AP_RT; ++i)
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
-                                const float z = fmaf(fmaf(acx[j][i][r], 1.0f / 2048.0f, acc[j][i][r]), C2, bzv[j]);
+                                // split2_combine spelled out: acx is read before acc, the order this kernel was scheduled with
+                                const float z = fmaf(fmaf(acx[j][i][r], SPLIT2_INV, acc[j][i][r]), C2, bzv[j]);
                                 rs[i][r] = fmaf(w3v[j], __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z)), rs[i][r]);
                             }
                     }
@@ -550,7 +534,7 @@ __global__ __launch_bounds__(512, 1) void attn_pool_pipe_kernel(AttnPoolArgs p, 
                         // convert per term plus the FMAs -- the IO wave shares its SIMD's issue slots with an MMA wave
                         (void)a01; (void)a23;
                         ap_fma_mix(a, u1[q8], pr);
-                        if (!ROW1) ap_fma_mix(a, u2[q8], pr * (1.0f / 2048.0f));
+                        if (!ROW1) ap_fma_mix(a, u2[q8], pr * SPLIT2_INV);
 #else
                         if (ROW1) {
                             a.x = fmaf(pr, (float)a01[0], a.x);
@@ -559,10 +543,10 @@ __global__ __launch_bounds__(512, 1) void attn_pool_pipe_kernel(AttnPoolArgs p, 
                             a.w = fmaf(pr, (float)a23[1], a.w);
                         } else {
                             const fp16x2_t b01 = __builtin_bit_cast(fp16x2_t, u2[q8].x), b23 = __builtin_bit_cast(fp16x2_t, u2[q8].y);
-                            a.x = fmaf(pr, fmaf((float)b01[0], 1.0f / 2048.0f, (float)a01[0]), a.x);
-                            a.y = fmaf(pr, fmaf((float)b01[1], 1.0f / 2048.0f, (float)a01[1]), a.y);
-                            a.z = fmaf(pr, fmaf((float)b23[0], 1.0f / 2048.0f, (float)a23[0]), a.z);
-                            a.w = fmaf(pr, fmaf((float)b23[1], 1.0f / 2048.0f, (float)a23[1]), a.w);
+                            a.x = fmaf(pr, split2_combine((float)a01[0], (float)b01[0]), a.x);
+                            a.y = fmaf(pr, split2_combine((float)a01[1], (float)b01[1]), a.y);
+                            a.z = fmaf(pr, split2_combine((float)a23[0], (float)b23[0]), a.z);
+                            a.w = fmaf(pr, split2_combine((float)a23[1], (float)b23[1]), a.w);
                         }
 #endif
                         if (((q + 1) & (per - 1)) == 0) {              // sequence complete: fold the four row subgroups, subgroup 0 stores
@@ -590,12 +574,12 @@ __global__ __launch_bounds__(512, 1) void attn_pool_pipe_kernel(AttnPoolArgs p, 
                         *reinterpret_cast<uint2*>(d + AP_S * 4 * KG) = make_uint2(__float_as_uint(v.z), __float_as_uint(v.w));
                         continue;
                     }
-                    const fp16x2_t a01 = __builtin_amdgcn_cvt_pkrtz(v.x, v.y), a23 = __builtin_amdgcn_cvt_pkrtz(v.z, v.w);
-                    *reinterpret_cast<uint2*>(d) = make_uint2(__builtin_bit_cast(unsigned, a01), __builtin_bit_cast(unsigned, a23));
+                    const fp16x2_t a01 = split2_hi(v.x, v.y), a23 = split2_hi(v.z, v.w);
+                    *reinterpret_cast<uint2*>(d) = split2_words(a01, a23);
                     if (!ONE) {
-                        const fp16x2_t b01 = __builtin_amdgcn_cvt_pkrtz((v.x - (float)a01[0]) * 2048.0f, (v.y - (float)a01[1]) * 2048.0f);
-                        const fp16x2_t b23 = __builtin_amdgcn_cvt_pkrtz((v.z - (float)a23[0]) * 2048.0f, (v.w - (float)a23[1]) * 2048.0f);
-                        *reinterpret_cast<uint2*>(d + AP_S * 4 * KG) = make_uint2(__builtin_bit_cast(unsigned, b01), __builtin_bit_cast(unsigned, b23));
+                        const fp16x2_t b01 = split2_hi(split2_res(v.x, a01[0]), split2_res(v.y, a01[1]));
+                        const fp16x2_t b23 = split2_hi(split2_res(v.z, a23[0]), split2_res(v.w, a23[1]));
+                        *reinterpret_cast<uint2*>(d + AP_S * 4 * KG) = split2_words(b01, b23);
                     }
                 }
                 if (w4 == 0) { AP_T(6) }

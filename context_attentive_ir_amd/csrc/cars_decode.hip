@@ -15,7 +15,7 @@
 // Everything is enqueued on the caller's stream; no host synchronisation.
 #include <algorithm>
 #include <mutex>
-#include "common.hpp"
+#include "split2.hpp"
 
 namespace nir {
 
@@ -114,9 +114,6 @@ __global__ __launch_bounds__(256) void argmax_map_kernel(const float* __restrict
 // ds_bpermute hops, the four waves write one partial per decode row, argmax_finish_kernel reduces the partials of all workgroups and maps
 // the winner to the next input token.  Replaces a 96 x 30 000 x 256 fp32 GEMM that wrote 11.5 MB of logits per step plus an arg-max kernel
 // that read them back.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int PA_K = 256, PA_KS = PA_K / 32, PA_NBT = 6, PA_ROWS = 16 * PA_NBT, PA_LD = PA_K + 8;     // 96 decode rows per pass
 constexpr int PA_TW = 2;                                                                              // vocabulary tiles per wave and pass
 constexpr size_t PA_LDS = (size_t)2 * PA_ROWS * PA_LD * 2;
@@ -157,12 +154,10 @@ __global__ __launch_bounds__(256, 1) void pred_argmax_kernel(const float* __rest
             const int r = e / (PA_K / 4), k4 = (e - r * (PA_K / 4)) * 4;
             float4 v = sv[q];
             if (b0 + r >= Bd) v = make_float4(0.f, 0.f, 0.f, 0.f);
-            const fp16x2_t a01 = __builtin_amdgcn_cvt_pkrtz(v.x, v.y), a23 = __builtin_amdgcn_cvt_pkrtz(v.z, v.w);
-            const fp16x2_t b01 = __builtin_amdgcn_cvt_pkrtz((v.x - (float)a01[0]) * 2048.0f, (v.y - (float)a01[1]) * 2048.0f);
-            const fp16x2_t b23 = __builtin_amdgcn_cvt_pkrtz((v.z - (float)a23[0]) * 2048.0f, (v.w - (float)a23[1]) * 2048.0f);
+            const Split2x4 s = split2(v);
             _Float16* d = pa_sm + r * PA_LD + k4;
-            *reinterpret_cast<uint2*>(d) = make_uint2(__builtin_bit_cast(unsigned, a01), __builtin_bit_cast(unsigned, a23));
-            *reinterpret_cast<uint2*>(d + PA_ROWS * PA_LD) = make_uint2(__builtin_bit_cast(unsigned, b01), __builtin_bit_cast(unsigned, b23));
+            *reinterpret_cast<uint2*>(d) = s.hi;
+            *reinterpret_cast<uint2*>(d + PA_ROWS * PA_LD) = s.lo;
         }
         __syncthreads();
         float best[PA_NBT];
@@ -237,7 +232,7 @@ __global__ __launch_bounds__(256, 1) void pred_argmax_kernel(const float* __rest
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int64_t v = (t0 + u) * 16 + 4 * g4 + r;         // ascending in (u, r): '>' keeps the first index on ties
-                        const float x = fmaf(acx[u][bt][r], 1.0f / 2048.0f, acc[u][bt][r]);
+                        const float x = fmaf(acx[u][bt][r], SPLIT2_INV, acc[u][bt][r]);      // split2_combine spelled out: acx is read first, as scheduled
                         if (v < VT && x > best[bt]) { best[bt] = x; bidx[bt] = (int)v; }
                     }
             }
@@ -353,10 +348,10 @@ __global__ void h16_pack_kernel(const float* __restrict__ h, int64_t n, _Float16
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
     const float v = h[e];
-    const _Float16 a = (_Float16)v;
+    const _Float16 a = split2_hi1_rne(v);
     _Float16* d = out + (e >> 3) * 16 + (e & 7);
     d[0] = a;
-    d[8] = (_Float16)((v - (float)a) * 2048.0f);
+    d[8] = split2_lo1(v, a);
 }
 
 struct DecPlan {

@@ -13,7 +13,7 @@
 //       over the 4 waves, cell update in the same kernel -- no gate tensor, no separate cell kernel, no fill kernels
 //   1 session_attend2 (softmax over the t+1 previous states incl. the zero state, weighted sums, [q; sq; sd] rows)
 //   1 rank projection GEMM (W_q | W_shared + W_priv1 packed once per weight version), 1 feature kernel, 3 maxout GEMMs
-#include "common.hpp"
+#include "split2.hpp"
 #include <algorithm>
 
 namespace nir {
@@ -28,7 +28,6 @@ constexpr int ACT_MAXOUT2 = 16;
 constexpr int ACT_BOUNDED = 0x100;      // (gemm.hip) operands bounded by 2^15: the split-precision GEMM may use its fp16 two-term form
 constexpr int ACT_TANH_ROWDOT16 = 17;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // one wave per (b,s) row, N <= 64: batch-wide m = max_rows count_nonzero(labels) (cars.py:285-289), stable descending
 // rank by label, attend over {rank < count} U {rank >= m} (Appendix E2), logits e_k = sum of the NP epilogue partials + b3
@@ -351,7 +350,6 @@ __global__ __launch_bounds__(256) void lstm_step_kernel(LstmStepArgs p) {
 // the weights -- 23.6 us per step, six steps per tail.  Here a k-block of 32 is three 16-cycle MFMAs, W_hh arrives pre-split in lane
 // order (no conversion), h arrives as the term pairs the previous step wrote, and the input side comes from the hoisted GEMM (gx).
 // ---------------------------------------------------------------------------------------------------------------------
-typedef _Float16 f16x8s __attribute__((ext_vector_type(8)));
 
 // UG unit groups (4 units each) per workgroup: every workgroup reads the WHOLE previous state (B x H term pairs) as its B operand, so with 4
 // units per workgroup (H / 4 workgroups per chain) the state was fetched from L2 128 times per chain and step -- 32 MB per pass at B = 64
@@ -368,7 +366,7 @@ __global__ __launch_bounds__(256) void lstm_step16_kernel(LstmStepArgs p) {
     const float* cprev = p.cprev[ch];
     const float* gxp = p.gx[ch];
     // result view: lane = (batch column i, unit_local g), registers r = gates i,f,g,o
-    const f16x8s* wf = reinterpret_cast<const f16x8s*>(p.whh_frag[ch]) + lane;
+    const f16x8* wf = reinterpret_cast<const f16x8*>(p.whh_frag[ch]) + lane;
     size_t wbase[UG];
     int udv[UG];
 #pragma unroll
@@ -430,7 +428,7 @@ __global__ __launch_bounds__(256) void lstm_step16_kernel(LstmStepArgs p) {
                 hr[t] = hp16 + ((int64_t)(b < p.B ? b : p.B - 1) * H8 + g) * 16;      // rows past the batch: clamped (their columns are never stored)
             }
             for (int q0 = wave; q0 < KB; q0 += 4 * CK) {
-                f16x8s w1[CK][UG], w2[CK][UG], h1[CK][NB], h2[CK][NB];
+                f16x8 w1[CK][UG], w2[CK][UG], h1[CK][NB], h2[CK][NB];
 #pragma unroll
                 for (int c = 0; c < CK; ++c) {
                     const int kb = q0 + 4 * c;
@@ -440,14 +438,14 @@ __global__ __launch_bounds__(256) void lstm_step16_kernel(LstmStepArgs p) {
                         w1[c][u] = wf[wbase[u] + (size_t)(kc * 2) * 64];
                         w2[c][u] = wf[wbase[u] + (size_t)(kc * 2 + 1) * 64];
                         if (kb >= KB) {                          // past the end: zero weights, the MFMAs below run unconditionally (a wave-uniform
-                            w1[c][u] = f16x8s{};                 // `continue` around them cost phi copies of every accumulator: 693 v_accvgpr moves,
-                            w2[c][u] = f16x8s{};                 // 512 registers and 32 bytes of scratch per lane in the <4, 4, 2> instantiation;
+                            w1[c][u] = f16x8{};                 // `continue` around them cost phi copies of every accumulator: 693 v_accvgpr moves,
+                            w2[c][u] = f16x8{};                 // 512 registers and 32 bytes of scratch per lane in the <4, 4, 2> instantiation;
                         }                                        // 391 registers and none now.  Slabs of 96 rows (<6, 4>: 256 workgroups at 768
                     }                                            // rows, one round over the chip) still spill 140-190 bytes: not built)
 #pragma unroll
                     for (int t = 0; t < NB; ++t) {
-                        h1[c][t] = *reinterpret_cast<const f16x8s*>(hr[t] + (int64_t)kc * 64);
-                        h2[c][t] = *reinterpret_cast<const f16x8s*>(hr[t] + (int64_t)kc * 64 + 8);
+                        h1[c][t] = *reinterpret_cast<const f16x8*>(hr[t] + (int64_t)kc * 64);
+                        h2[c][t] = *reinterpret_cast<const f16x8*>(hr[t] + (int64_t)kc * 64 + 8);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -469,7 +467,7 @@ __global__ __launch_bounds__(256) void lstm_step16_kernel(LstmStepArgs p) {
 #pragma unroll
             for (int t = 0; t < NB; ++t)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) red[wave][u][t][r * 64 + lane] = fmaf(acx[u][t][r], 1.0f / 2048.0f, acc[u][t][r]);
+                for (int r = 0; r < 4; ++r) red[wave][u][t][r * 64 + lane] = split2_combine(acc[u][t][r], acx[u][t][r]);
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < EPW; ++k) {
@@ -488,10 +486,10 @@ __global__ __launch_bounds__(256) void lstm_step16_kernel(LstmStepArgs p) {
                 const float hn = fast_sigmoid(g4[3]) * fast_tanh(cn);
                 p.cnext[ch][si] = cn;
                 p.hnext[ch][si] = hn;
-                const _Float16 a = (_Float16)hn;                 // the next step's B operand: the two fp16 terms
+                const _Float16 a = split2_hi1_rne(hn);           // the next step's B operand: the two fp16 terms
                 _Float16* d = p.h16next[ch] + ((int64_t)b * H8 + (ud >> 3)) * 16 + (ud & 7);
                 d[0] = a;
-                d[8] = (_Float16)((hn - (float)a) * 2048.0f);
+                d[8] = split2_lo1(hn, a);
             }
         }
         __syncthreads();
@@ -510,9 +508,9 @@ __global__ __launch_bounds__(64) void lstm_step_whh_frag_kernel(const float* __r
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const float w = wr[j];
-        const _Float16 a = (_Float16)w;
+        const _Float16 a = split2_hi1_rne(w);
         o[j] = a;
-        o[64 * 8 + j] = (_Float16)((w - (float)a) * 2048.0f);
+        o[64 * 8 + j] = split2_lo1(w, a);
         bad |= !(fabsf(w) < 32768.0f);
     }
     if (bad && err) atomicOr(err, 2);
@@ -715,8 +713,6 @@ static SessPlan sess_plan(void* ws, size_t cap, int B, int S, int N, int D, int 
     p.bytes = align_up(a.off, 256);
     return p;
 }
-
-static inline dim3 g1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 }  // namespace nir
 

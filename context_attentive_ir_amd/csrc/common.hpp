@@ -150,6 +150,7 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 }
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+static inline dim3 g1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }      // 1-D grid of 256-thread blocks over n elements
 
 // Bump allocator over the caller-provided workspace.
 struct Workspace {

@@ -13,7 +13,7 @@
 //                       (packed fp32 FMA, two windows per instruction), bias + tanh kept in LDS, Linear(NH -> NO) + tanh, column max over the tile -> partial [rows, tiles, NO];
 //                       tiles past the effective length exit at once; two extra workgroups evaluate the all-PAD window of each tower
 //   rank_finish_kernel  one wave per (query, candidate): max over the tiles (+ the all-PAD vector), ATen cosine -> scores [B, N]
-#include "common.hpp"
+#include "split2.hpp"
 #include <algorithm>
 
 namespace nir {
@@ -23,7 +23,6 @@ constexpr int CD_TAPS = 5;         // Conv1d(k=3) over the 3-row interleave = a 
 constexpr int CD_THREADS = 320;    // one GEMM-1 column per thread at NH <= 320
 constexpr int CD_HALF = CD_TP / 2;  // GEMM 1 pairs window p with window p + CD_HALF
 constexpr int CD_NQ = CD_HALF + CD_TAPS - 1;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int DS_INFLIGHT = 8;     // table rows a dssm_tower_kernel wave has in flight
 
 __device__ __forceinline__ int wave_max_i(int v) {

@@ -8,7 +8,7 @@
 //         conv_d2 (1x1) as GEMM; Hadamard with the query vector, Linear over positions, fc3, fc4.
 // The document branch (conv_d1 -> pool -> conv_d2 -> Hadamard . fc2) runs as ONE kernel per document tile when the pack carries
 // the fragment-ordered weight planes (duet_fused.hip); the GEMM-per-layer chain below it is the general fallback.
-#include "common.hpp"
+#include "split2.hpp"
 
 namespace nir {
 
@@ -157,13 +157,12 @@ __global__ __launch_bounds__(256) void maxpool_t_planes_kernel(const float* __re
                         a.z = fmaxf(a.z, v[k + dt].z); a.w = fmaxf(a.w, v[k + dt].w);
                     }
                 if (!real) a = make_float4(0.f, 0.f, 0.f, 0.f);
-                typedef __fp16 h2_t __attribute__((ext_vector_type(2)));
-                const h2_t p01 = __builtin_amdgcn_cvt_pkrtz(a.x, a.y), p23 = __builtin_amdgcn_cvt_pkrtz(a.z, a.w);
-                const h2_t q01 = __builtin_amdgcn_cvt_pkrtz((a.x - (float)p01[0]) * 2048.f, (a.y - (float)p01[1]) * 2048.f);
-                const h2_t q23 = __builtin_amdgcn_cvt_pkrtz((a.z - (float)p23[0]) * 2048.f, (a.w - (float)p23[1]) * 2048.f);
+                const fp16x2_t p01 = split2_hi(a.x, a.y), p23 = split2_hi(a.z, a.w);
+                const fp16x2_t q01 = split2_hi(split2_res(a.x, p01[0]), split2_res(a.y, p01[1]));
+                const fp16x2_t q23 = split2_hi(split2_res(a.z, p23[0]), split2_res(a.w, p23[1]));
                 const int64_t off = ((m * Tout + t0 + k) * NF4P + f4) * 4;
-                *reinterpret_cast<uint2*>(o1 + off) = make_uint2(__builtin_bit_cast(unsigned, p01), __builtin_bit_cast(unsigned, p23));
-                *reinterpret_cast<uint2*>(o2 + off) = make_uint2(__builtin_bit_cast(unsigned, q01), __builtin_bit_cast(unsigned, q23));
+                *reinterpret_cast<uint2*>(o1 + off) = split2_words(p01, p23);
+                *reinterpret_cast<uint2*>(o2 + off) = split2_words(q01, q23);
             }
         }
     }

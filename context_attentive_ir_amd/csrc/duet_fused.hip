@@ -12,7 +12,7 @@
 //   GEMM 2  D2[rows, NFP] = P[rows, NFP] W2^T P = pooled tile as fp16 term planes in LDS (fragment order), W2 streamed like W1
 //   fc2     partial[tile][slot][f] = sum_rows fc2_w[t] * D2[row][f]   (rows whose pooling window leaves the document get weight 0)
 // A second tiny kernel folds the tiles of a document: m1[pair][f] = tanh(fc2_b + qv[b][f] * sum partial).
-// Arithmetic: two-term fp16 split (x = h1 + 2^-11 h2', three v_mfma_f32_16x16x32_f16 per k-block, two accumulator sets) as in
+// Arithmetic: two-term fp16 split (split2.hpp: x = h1 + 2^-11 h2', three v_mfma_f32_16x16x32_f16 per k-block, two accumulator sets) as in
 // gemm3_kernel<., true> -- needs |table|, |weights| < 2^15 (host-checked `bounded`); activations are tanh outputs.
 // The GEMM phases are bound by the W stream out of L2 (every CU streams all of W1 / W2 per tile: 40 KB per k-step; measured with 64-row
 // tiles: TCC busy 95 %, 13 TB/s of L2 reads), so the tile is as tall as registers and LDS allow, one workgroup (4 waves, one per SIMD)
@@ -27,14 +27,9 @@
 // documents): 92 of 96 rows carry useful pooled rows.
 #include <algorithm>
 #include <mutex>
-#include "common.hpp"
+#include "split2.hpp"
 
 namespace nir {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int DF_NFP = 320;                 // filter columns (4 waves x 5 tiles x 16)
 constexpr int DF_CT = 5;                    // column tiles per wave
@@ -62,13 +57,13 @@ struct DuetDocArgs {
 };
 
 __device__ __forceinline__ void df_split_store(unsigned short* base, int kgs, int row, int kg, int e0, const float4& v) {
-    const fp16x2_t a01 = __builtin_amdgcn_cvt_pkrtz(v.x, v.y), a23 = __builtin_amdgcn_cvt_pkrtz(v.z, v.w);
-    const float r0 = (v.x - (float)a01[0]) * 2048.0f, r1 = (v.y - (float)a01[1]) * 2048.0f;
-    const float r2 = (v.z - (float)a23[0]) * 2048.0f, r3 = (v.w - (float)a23[1]) * 2048.0f;
-    const fp16x2_t b01 = __builtin_amdgcn_cvt_pkrtz(r0, r1), b23 = __builtin_amdgcn_cvt_pkrtz(r2, r3);
+    const fp16x2_t a01 = split2_hi(v.x, v.y), a23 = split2_hi(v.z, v.w);          // all four residuals first, then the packs
+    const float r0 = split2_res(v.x, a01[0]), r1 = split2_res(v.y, a01[1]);
+    const float r2 = split2_res(v.z, a23[0]), r3 = split2_res(v.w, a23[1]);
+    const fp16x2_t b01 = split2_hi(r0, r1), b23 = split2_hi(r2, r3);
     unsigned short* d = base + kg * kgs + row * 8 + e0;
-    *reinterpret_cast<uint2*>(d) = make_uint2(__builtin_bit_cast(unsigned, a01), __builtin_bit_cast(unsigned, a23));
-    *reinterpret_cast<uint2*>(d + 4 * kgs) = make_uint2(__builtin_bit_cast(unsigned, b01), __builtin_bit_cast(unsigned, b23));
+    *reinterpret_cast<uint2*>(d) = split2_words(a01, a23);
+    *reinterpret_cast<uint2*>(d + 4 * kgs) = split2_words(b01, b23);
 }
 
 // tanh(x) for z = 2 log2(e) x already formed:  1 - 2 / (1 + 2^z)   (v_exp_f32, v_rcp_f32; saturates correctly at +-inf)
@@ -84,22 +79,12 @@ __device__ __forceinline__ float df_bperm(float v, int byte_idx) {
     return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(byte_idx, __builtin_bit_cast(int, v)));
 }
 
-// In-place accumulate in AGPRs.  Written as inline assembly: with the builtin, hipcc assigns the result of each accumulator chain to a
-// different register tuple than its loop-carried input and rotates most tuples through VGPRs on every k-step (112 v_accvgpr_* moves per
-// 60 MFMAs).  The operands come straight from ds_read / global_load (s_waitcnt is still compiler-inserted); the accumulators are first
-// read by VALU code after DF_MMA_DRAIN.
-#define DF_MMA(ACC, A, W) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(ACC) : "v"(A), "v"(W))
-#define DF_MMA_V(ACC, A, W) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(ACC) : "v"(A), "v"(W))
-// first product of an accumulator chain: C = 0 (no zero fill of 240 registers between the two GEMMs)
-#define DF_MMA0(ACC, A, W) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=a"(ACC) : "v"(A), "v"(W))
-#define DF_MMA0_V(ACC, A, W) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=v"(ACC) : "v"(A), "v"(W))
 #ifdef DF_TIMING
 __device__ long long df_dbg[16];
 #define DF_T(I) if (blockIdx.x == 3000 && threadIdx.x == 0) df_dbg[I] = __builtin_readcyclecounter();
 #else
 #define DF_T(I)
 #endif
-#define DF_MMA_DRAIN() asm volatile("s_nop 15\n\ts_nop 15" ::: "memory")
 // Accumulator element -> VGPR at the point of use.  Left to the compiler, every accumulator is copied out of its AGPR right behind the
 // last MFMA (240 v_accvgpr_read in a row for the 96-row tile: the epilogue then spills, and so do the GEMM loops around it).
 __device__ __forceinline__ float df_acc(const f32x4& a, int r, bool from_agpr) {      // from_agpr folds to a constant after unrolling
@@ -109,23 +94,12 @@ __device__ __forceinline__ float df_acc(const f32x4& a, int r, bool from_agpr) {
     return x;
 }
 
-// MFMA number n of a k-step (n is a compile-time constant after unrolling): column tile n / (3 RT), term pair (n / RT) % 3, row tile n % RT
-template <int RT>
-__device__ __forceinline__ void df_mma_n(int n, f32x4 (&acc)[DF_CT][RT], f32x4 (&acx)[DF_CT][RT], const f16x8 (&af)[RT][2],
-                                         const f16x8 (&w)[DF_CT][2]) {
-    const int j = n / (3 * RT), ph = (n / RT) % 3, i = n % RT;
-    if (ph == 0) DF_MMA(acx[j][i], af[i][1], w[j][0]);
-    else if (ph == 1) DF_MMA(acx[j][i], af[i][0], w[j][1]);
-    else DF_MMA(acc[j][i], af[i][0], w[j][0]);
-}
-
 // one half (two elements) of a staged float4: split into the two fp16 terms and store 4 bytes into each term plane
 __device__ __forceinline__ void df_split_store_half(unsigned short* base, int kgs, int row, int kg, int e0, float x, float y) {
-    const fp16x2_t a = __builtin_amdgcn_cvt_pkrtz(x, y);
-    const fp16x2_t b = __builtin_amdgcn_cvt_pkrtz((x - (float)a[0]) * 2048.0f, (y - (float)a[1]) * 2048.0f);
+    const Split2x2 s = split2(x, y);
     unsigned short* d = base + kg * kgs + row * 8 + e0;
-    *reinterpret_cast<unsigned*>(d) = __builtin_bit_cast(unsigned, a);
-    *reinterpret_cast<unsigned*>(d + 4 * kgs) = __builtin_bit_cast(unsigned, b);
+    *reinterpret_cast<unsigned*>(d) = split2_word(s.hi);
+    *reinterpret_cast<unsigned*>(d + 4 * kgs) = split2_word(s.lo);
 }
 
 template <int RT>
@@ -264,13 +238,13 @@ __global__ __launch_bounds__(256, 1) void duet_doc_kernel(DuetDocArgs p) {
         _Pragma("clang loop unroll(full)") for (int n_ = 0; n_ < 15 * RT; ++n_) {         \
             const int i_ = n_ / 15, m_ = n_ % 15, j_ = m_ % 5, b_ = i_ & 1;               \
             if (i_ >= RT - VACC) {                                                        \
-                if (m_ < 5) { if (FIRST) DF_MMA0_V(acx[j_][i_], af[b_][1], WC[j_][0]); else DF_MMA_V(acx[j_][i_], af[b_][1], WC[j_][0]); } \
-                else if (m_ < 10) DF_MMA_V(acx[j_][i_], af[b_][0], WC[j_][1]);            \
-                else { if (FIRST) DF_MMA0_V(acc[j_][i_], af[b_][0], WC[j_][0]); else DF_MMA_V(acc[j_][i_], af[b_][0], WC[j_][0]); } \
+                if (m_ < 5) { if (FIRST) MMA0_V(acx[j_][i_], af[b_][1], WC[j_][0]); else MMA_V(acx[j_][i_], af[b_][1], WC[j_][0]); } \
+                else if (m_ < 10) MMA_V(acx[j_][i_], af[b_][0], WC[j_][1]);            \
+                else { if (FIRST) MMA0_V(acc[j_][i_], af[b_][0], WC[j_][0]); else MMA_V(acc[j_][i_], af[b_][0], WC[j_][0]); } \
             } else {                                                                      \
-                if (m_ < 5) { if (FIRST) DF_MMA0(acx[j_][i_], af[b_][1], WC[j_][0]); else DF_MMA(acx[j_][i_], af[b_][1], WC[j_][0]); } \
-                else if (m_ < 10) DF_MMA(acx[j_][i_], af[b_][0], WC[j_][1]);              \
-                else { if (FIRST) DF_MMA0(acc[j_][i_], af[b_][0], WC[j_][0]); else DF_MMA(acc[j_][i_], af[b_][0], WC[j_][0]); } \
+                if (m_ < 5) { if (FIRST) MMA0_A(acx[j_][i_], af[b_][1], WC[j_][0]); else MMA_A(acx[j_][i_], af[b_][1], WC[j_][0]); } \
+                else if (m_ < 10) MMA_A(acx[j_][i_], af[b_][0], WC[j_][1]);              \
+                else { if (FIRST) MMA0_A(acc[j_][i_], af[b_][0], WC[j_][0]); else MMA_A(acc[j_][i_], af[b_][0], WC[j_][0]); } \
             }                                                                             \
             EXTRA                                                                         \
             if (n_ >= 3 && (n_ - 3) % WS_ == 0 && (n_ - 3) / WS_ < 2 * DF_CT) {           \
@@ -327,7 +301,7 @@ __global__ __launch_bounds__(256, 1) void duet_doc_kernel(DuetDocArgs p) {
         const _Float16* wn_ = wp1 + (int64_t)s1_ * WSTEP;                                 \
         unsigned short* an_ = As + (((S) + 1) & 1) * (2 * 4 * KG);                        \
         _Pragma("clang loop unroll(full)") for (int n_ = 0; n_ < 15 * RT; ++n_) {                          \
-            df_mma_n<RT>(n_, acc, acx, AFC, WC);                                          \
+            mma_n(n_, acc, acx, AFC, WC);                                          \
             if (n_ == 8) { DF_KEEP_HEAD(WN, AFN) }                                        \
             if (n_ % 6 == 2 && n_ / 6 < 2 * DF_CT)                                        \
                 WN[(n_ / 6) >> 1][(n_ / 6) & 1] = *reinterpret_cast<const f16x8*>(wn_ + (n_ / 6) * 512); \
@@ -500,7 +474,7 @@ __global__ __launch_bounds__(256, 1) void duet_doc_kernel(DuetDocArgs p) {
         }
     }
     DF_T(2)
-    DF_MMA_DRAIN();
+    MMA_DRAIN();
     if constexpr (PL) lds_barrier();       // the P planes overwrite the token tile: every wave is past its last fragment read
     // ================= tanh, max-pool over rows, split into the P planes =================
     // C layout of the 16x16 tile: column = lane & 15, row = 4 * (lane >> 4) + r.  Pooled row pr needs rows pr .. pr+P-1: the rest of
@@ -515,7 +489,7 @@ __global__ __launch_bounds__(256, 1) void duet_doc_kernel(DuetDocArgs p) {
             const float biasz = (col < p.NF ? p.b1[col] : 0.f) * DF_2LOG2E;
             float v[RT][4], x[RT + 1][4];
             if constexpr (PL) {                                            // packed fp32 math: the same operations, two values per issue slot
-                const f32x2 k1 = {1.0f / 2048.0f, 1.0f / 2048.0f}, k2 = {DF_2LOG2E, DF_2LOG2E}, b2 = {biasz, biasz}, one = {1.f, 1.f}, m2 = {-2.f, -2.f};
+                const f32x2 k1 = {SPLIT2_INV, SPLIT2_INV}, k2 = {DF_2LOG2E, DF_2LOG2E}, b2 = {biasz, biasz}, one = {1.f, 1.f}, m2 = {-2.f, -2.f};
 #pragma unroll
                 for (int i = 0; i < RT; ++i) {
                     const bool ag = i < RT - (RT > 4 ? RT - 4 : 0);
@@ -537,7 +511,7 @@ __global__ __launch_bounds__(256, 1) void duet_doc_kernel(DuetDocArgs p) {
                 for (int i = 0; i < RT; ++i)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        v[i][r] = df_tanh_z(fmaf(fmaf(acx[j][i][r], 1.0f / 2048.0f, acc[j][i][r]), DF_2LOG2E, biasz));
+                        v[i][r] = df_tanh_z(fmaf(split2_combine(acc[j][i][r], acx[j][i][r]), DF_2LOG2E, biasz));
                         x[i][r] = df_bperm(v[i][r], nb_idx);
                     }
             }
@@ -575,9 +549,9 @@ __global__ __launch_bounds__(256, 1) void duet_doc_kernel(DuetDocArgs p) {
                     const float mine = odd ? m[2 * hh + 1] : m[2 * hh], give = odd ? m[2 * hh] : m[2 * hh + 1];
                     const float got = dpp_mov<0xB1>(give);
                     const float lo = odd ? got : mine, hi = odd ? mine : got;
-                    const fp16x2_t h1 = __builtin_amdgcn_cvt_pkrtz(lo, hi);
-                    const f32x2 rs = (f32x2{lo, hi} - f32x2{(float)h1[0], (float)h1[1]}) * f32x2{2048.0f, 2048.0f};      // v_pk_add / v_pk_mul
-                    const fp16x2_t h2 = __builtin_amdgcn_cvt_pkrtz(rs[0], rs[1]);
+                    const fp16x2_t h1 = split2_hi(lo, hi);
+                    const f32x2 rs = (f32x2{lo, hi} - f32x2{(float)h1[0], (float)h1[1]}) * f32x2{SPLIT2_SCALE, SPLIT2_SCALE};      // split2_res, packed: v_pk_add / v_pk_mul
+                    const fp16x2_t h2 = split2_hi(rs[0], rs[1]);
                     const int row = 16 * i + 4 * g + 2 * hh + odd;
                     *reinterpret_cast<unsigned*>(dst + row * 8) = __builtin_bit_cast(unsigned, h1);
                     *reinterpret_cast<unsigned*>(dst + DF_S2 * 4 * KG + row * 8) = __builtin_bit_cast(unsigned, h2);
@@ -617,7 +591,7 @@ __global__ __launch_bounds__(256, 1) void duet_doc_kernel(DuetDocArgs p) {
         const _Float16* wn_ = wp2 + (int64_t)sn_ * WSTEP;                                 \
         const unsigned short* pn_ = Pp + sn_ * 4 * KG + foff;                             \
         _Pragma("clang loop unroll(full)") for (int n_ = 0; n_ < 15 * RT; ++n_) {                          \
-            df_mma_n<RT>(n_, acc, acx, AFC, WC);                                          \
+            mma_n(n_, acc, acx, AFC, WC);                                          \
             if (n_ == 8) { DF_KEEP_HEAD(WN, AFN) }                                        \
             if (n_ % 6 == 2 && n_ / 6 < 2 * DF_CT)                                        \
                 WN[(n_ / 6) >> 1][(n_ / 6) & 1] = *reinterpret_cast<const f16x8*>(wn_ + (n_ / 6) * 512); \
@@ -655,7 +629,7 @@ __global__ __launch_bounds__(256, 1) void duet_doc_kernel(DuetDocArgs p) {
     }
 
     DF_T(4)
-    DF_MMA_DRAIN();
+    MMA_DRAIN();
     // ================= tanh, fc2 over the tile's rows =================
     // Row weight = fc2_w[t] when the row is one of the tile's own pooled rows and its window stays inside the document, else 0.  A
     // flattened tile touches at most two documents: slot 0 = the document of the tile's first row, slot 1 = the next one.
@@ -686,7 +660,7 @@ __global__ __launch_bounds__(256, 1) void duet_doc_kernel(DuetDocArgs p) {
             if constexpr (PL) {
                 // packed fp32 math (v_pk_fma_f32 / v_pk_add_f32: two values per issue slot; one wave per SIMD, the epilogue is issue-bound)
                 f32x2 s2 = {0.f, 0.f};
-                const f32x2 k1 = {1.0f / 2048.0f, 1.0f / 2048.0f}, k2 = {DF_2LOG2E, DF_2LOG2E}, b2 = {biasz, biasz};
+                const f32x2 k1 = {SPLIT2_INV, SPLIT2_INV}, k2 = {DF_2LOG2E, DF_2LOG2E}, b2 = {biasz, biasz};
                 const f32x2 one = {1.f, 1.f}, m2 = {-2.f, -2.f};
 #pragma unroll
                 for (int i = 0; i < RT; ++i) {
@@ -712,7 +686,7 @@ __global__ __launch_bounds__(256, 1) void duet_doc_kernel(DuetDocArgs p) {
                 for (int i = 0; i < RT; ++i)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const float d2 = df_tanh_z(fmaf(fmaf(acx[j][i][r], 1.0f / 2048.0f, acc[j][i][r]), DF_2LOG2E, biasz));
+                        const float d2 = df_tanh_z(fmaf(split2_combine(acc[j][i][r], acx[j][i][r]), DF_2LOG2E, biasz));
                         sum = fmaf(wrow[i][r], d2, sum);
                         sum1 = fmaf(w1row[i][r], d2, sum1);
                     }

@@ -7,14 +7,13 @@
 // a lane's ds_read_b128 then covers 4 consecutive k of its row and the 16-lane read groups hit 16 distinct
 // 16-byte slots (conflict-free).  The 4 floats feed 4 successive MFMAs; the k-order inside an 8-wide group
 // is permuted identically for A and W (lane>>5 selects which half), which leaves the sum unchanged.
-#include "common.hpp"
+#include "split2.hpp"
 #include <algorithm>
 #include <mutex>
 #include <stdlib.h>
 
 namespace nir {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct GemmArgs {
     const float* a;
@@ -228,7 +227,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     }
 }
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Small-M path (session LSTM steps, ranknet, attention MLPs on a handful of rows): the 64x64 tiling would leave
 // most CUs idle and serialise K.  Here one workgroup owns ONE 16x16 output tile, its 4 waves split K, operands are
@@ -579,7 +577,6 @@ __global__ __launch_bounds__(64 * SK_WAVES) void gemm_skinny_kernel(GemmArgs p, 
 // t+1 are in flight during the 24 MFMAs of tile t; the split (VALU) runs in the shadow of the other waves' MFMAs.
 // Operand addressing (dense / embedding gather / conv taps), epilogues and the XCD-aware block order are gemm_kernel's.
 // ---------------------------------------------------------------------------------------------------------------------
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int G3_BM = 128, G3_BN = 128, G3_BK = 16;
 constexpr int G3_HALF = 128 * 8 + 32;                 // one k-half: 128 rows x 8 bf16, + 64 B so the two halves sit 16 banks apart
 constexpr int G3_PLANE = 2 * G3_HALF;                 // bf16 elements per (operand, stage, term): [k-half][row][8]
@@ -605,20 +602,15 @@ __device__ __forceinline__ void g3_split_store(unsigned short* base, int row, in
     *reinterpret_cast<uint2*>(d + 2 * G3_PLANE) = make_uint2(c01, c23);
 }
 
-// Two-term fp16 split (operands bounded by 2^15, e.g. tanh/sigmoid outputs, embeddings, weights): x = h1 + 2^-11 h2' with
-// h1 = fp16_rtz(x) (v_cvt_pkrtz_f16_f32 converts and packs two values per instruction; the residual is exact) and
-// h2' = fp16(2^11 (x - h1)).  Leading products go to one accumulator set, the two cross terms (scaled by 2^11) to a second one:
-// 3 fp16 MFMAs per k-block instead of 6 bf16 ones, ~4 VALU ops per element instead of 5.5, 2 LDS planes instead of 3.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2_t __attribute__((ext_vector_type(2)));
+// Two-term fp16 split (split2.hpp) of four k-consecutive values into the two term planes; all four residuals first, then the packs
 __device__ __forceinline__ void g3_split_store_h2(unsigned short* base, int row, int kq, const float4& v) {
-    const fp16x2_t a01 = __builtin_amdgcn_cvt_pkrtz(v.x, v.y), a23 = __builtin_amdgcn_cvt_pkrtz(v.z, v.w);
-    const float r0 = (v.x - (float)a01[0]) * 2048.0f, r1 = (v.y - (float)a01[1]) * 2048.0f;
-    const float r2 = (v.z - (float)a23[0]) * 2048.0f, r3 = (v.w - (float)a23[1]) * 2048.0f;
-    const fp16x2_t b01 = __builtin_amdgcn_cvt_pkrtz(r0, r1), b23 = __builtin_amdgcn_cvt_pkrtz(r2, r3);
+    const fp16x2_t a01 = split2_hi(v.x, v.y), a23 = split2_hi(v.z, v.w);
+    const float r0 = split2_res(v.x, a01[0]), r1 = split2_res(v.y, a01[1]);
+    const float r2 = split2_res(v.z, a23[0]), r3 = split2_res(v.w, a23[1]);
+    const fp16x2_t b01 = split2_hi(r0, r1), b23 = split2_hi(r2, r3);
     unsigned short* d = base + (kq >> 1) * G3_HALF + row * 8 + (kq & 1) * 4;
-    *reinterpret_cast<uint2*>(d) = make_uint2(__builtin_bit_cast(unsigned, a01), __builtin_bit_cast(unsigned, a23));
-    *reinterpret_cast<uint2*>(d + G3_PLANE) = make_uint2(__builtin_bit_cast(unsigned, b01), __builtin_bit_cast(unsigned, b23));
+    *reinterpret_cast<uint2*>(d) = split2_words(a01, a23);
+    *reinterpret_cast<uint2*>(d + G3_PLANE) = split2_words(b01, b23);
 }
 
 // MODE 0: dense A; 1: embedding gather, one row per A row (K <= E); 2: conv taps (E < K <= 3E, one table row per tap).
@@ -839,7 +831,7 @@ __global__ __launch_bounds__(256, 2) void gemm3_kernel(GemmArgs p) {
             for (int r = 0; r < 16; ++r) {
                 const int64_t m = m0 + wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 float v = acc[a][b][r];
-                if (H2) v = fmaf(acx[a][b][r], 1.0f / 2048.0f, v);
+                if (H2) v = split2_combine(v, acx[a][b][r]);
                 gemm_store(p, m, n, v, bsum);
             }
     }
@@ -1010,7 +1002,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h2p_kernel(GemmPlaneArgs q) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int64_t mm = m0 + wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                gemm_store(p, mm, nn, fmaf(acx[a][b][r], 1.0f / 2048.0f, acc[a][b][r]), bsum);
+                gemm_store(p, mm, nn, split2_combine(acc[a][b][r], acx[a][b][r]), bsum);
             }
     }
 }
@@ -1023,9 +1015,9 @@ __global__ void split_f16x2_kernel(const float* __restrict__ x, int64_t rows, in
     const int64_t r = i / cols_pad;
     const int c = (int)(i % cols_pad);
     const float v = c < cols ? x[r * ld + c] : 0.f;
-    const fp16x2_t a = __builtin_amdgcn_cvt_pkrtz(v, 0.f);
-    p1[i] = (_Float16)a[0];
-    p2[i] = (_Float16)((v - (float)a[0]) * 2048.0f);
+    const _Float16 a = split2_hi1_rtz(v);
+    p1[i] = a;
+    p2[i] = split2_lo1(v, a);
 }
 
 int launch_split_f16x2(const float* x, int64_t rows, int cols, int64_t ld, int cols_pad, void* p1, void* p2, hipStream_t st) {

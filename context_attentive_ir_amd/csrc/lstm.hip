@@ -23,13 +23,12 @@
 //
 // Variable length = masking: a sequence stops updating at step >= len; the reverse direction walks t = len-1-step
 // (packed-sequence semantics) -- no sort, no pack, no host sync (the reference does lengths.tolist(), :73).
-#include "common.hpp"
+#include "split2.hpp"
 #include <stdlib.h>
 #include <string>
 
 namespace nir {
 
-typedef float v2f __attribute__((ext_vector_type(2)));
 
 // matrix-core variants (lstm_mfma.hip); return NIR_ERR_UNSUPPORTED when the shape has no instantiation
 int launch_bilstm_mfma16(const float* gin, const int64_t* lens, const float* whh, const float* h0, const float* c0,
@@ -105,8 +104,8 @@ __global__ __launch_bounds__(4 * KP) void lstm_rec_kernel(LstmArgs p) {
     for (int s = 0; s < S; ++s) tmax = max(tmax, len[s]);
 
     // my quarter of the four gate rows of unit j -> registers (packed pairs for v_pk_fma_f32)
-    v2f w[4][KQ / 2];
-    v2f wi[4][IP > 0 ? IQ / 2 : 1];
+    f32x2 w[4][KQ / 2];
+    f32x2 wi[4][IP > 0 ? IQ / 2 : 1];
     float bias = 0.f;   // lane q carries the bias of gate q (added once per quad)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -184,7 +183,7 @@ __global__ __launch_bounds__(4 * KP) void lstm_rec_kernel(LstmArgs p) {
         float tot[S][4];
 #pragma unroll
         for (int s = 0; s < S; ++s) {
-            v2f acc[4];
+            f32x2 acc[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 acc[g].x = (g == q) ? gin_now[s] : 0.f;
@@ -203,7 +202,7 @@ __global__ __launch_bounds__(4 * KP) void lstm_rec_kernel(LstmArgs p) {
                 for (int k = 0; k < IQ / 4; ++k) xv[k] = *reinterpret_cast<const float4*>(xr + 4 * k);
 #pragma unroll
                 for (int k = 0; k < IQ / 4; ++k) {
-                    const v2f lo = {xv[k].x, xv[k].y}, hi = {xv[k].z, xv[k].w};
+                    const f32x2 lo = {xv[k].x, xv[k].y}, hi = {xv[k].z, xv[k].w};
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
                         acc[g] = __builtin_elementwise_fma(wi[g][2 * k], lo, acc[g]);
@@ -213,7 +212,7 @@ __global__ __launch_bounds__(4 * KP) void lstm_rec_kernel(LstmArgs p) {
             }
 #pragma unroll
             for (int k = 0; k < KQ / 4; ++k) {
-                const v2f lo = {hv[k].x, hv[k].y}, hi = {hv[k].z, hv[k].w};
+                const f32x2 lo = {hv[k].x, hv[k].y}, hi = {hv[k].z, hv[k].w};
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     acc[g] = __builtin_elementwise_fma(w[g][2 * k], lo, acc[g]);

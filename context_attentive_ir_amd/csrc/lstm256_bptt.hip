@@ -20,12 +20,11 @@
 //   against 1.59; four K slices of 64 units x RT = 3 -- half the partials -- 1.585 ms: the template keeps the parameter, the host uses 8).
 //   Also measured and not kept: touching the NEXT step's activations / states / dout during this launch (so that they wait in the Infinity Cache):
 //   26.5 us per step against 24.8 -- every extra request lengthens the launch's one operand burst.
-#include "common.hpp"
+#include "split2.hpp"
 #include <algorithm>
 
 namespace nir {
 
-typedef float f32x4_b __attribute__((ext_vector_type(4)));
 
 struct Bptt256Args {
     const float* dout;       // [M,T,ND*256]   gradient of the memory bank
@@ -152,7 +151,7 @@ __global__ __launch_bounds__(512, 1) void lstm256_bptt_step_kernel(Bptt256Args p
         if (!prod) continue;
         lds_barrier();
         // partial dh_prev[unit, seq] += W_hh[k, unit] dg[seq, k] over the member's 4 KU gate rows, sequence tile rt
-        f32x4_b acc0 = (f32x4_b){0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
+        f32x4 acc0 = (f32x4){0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
         const float* bp = bs + ((16 * rt + sq) * 4 + pq) * RS;
 #ifndef NIR_B256_NOMMA
 #pragma unroll

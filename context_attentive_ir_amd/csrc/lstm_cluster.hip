@@ -20,18 +20,11 @@
 // parity double buffering: h(s+1) goes to buffer (s+1)&1, which a member can only overwrite after every partner has produced h(s+1),
 // i.e. consumed h(s-1).  All four members of a cluster must be resident together: consecutive dispatch slots of one XCD; every poll
 // is bounded (a cluster that cannot make progress raises err bit 2 and leaves instead of hanging the device).
-#include "common.hpp"
+#include "split2.hpp"
 #include <algorithm>
 #include <mutex>
 
 namespace nir {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int CL_H = 256, CL_KB = 8, CL_NT = 2, CL_NW = 8, CL_SEQ = 16, CL_ZLD = CL_H + 8, CL_NC = 4, CL_UW = 64;
 constexpr int CL_GRAN = CL_UW * CL_SEQ;                       // granules one member publishes per group and step (1024)
@@ -60,21 +53,6 @@ struct LstmClArgs {
     int T, ND, tiles, ncld;       // tiles = ceil(M/16), ncld = clusters per direction = ceil(tiles / NG)
     int poll_limit;               // bounded spin of every wait on a partner (CL_POLL_LIMIT; the debug tunable cl_poll_limit lets a test force the time-out)
 };
-
-// the LSTM cell of lstm_fold.hip (lstm_cell_v): gates (i, f, g, o) of one unit in x; 5 v_exp + 3 v_rcp
-__device__ __forceinline__ void cl_cell(const f32x4 x, float& c, float& h) {
-    constexpr float L2E = 1.4426950408889634f;
-    const f32x2 e_if = (f32x2){x[0], x[1]} * (f32x2){-L2E, -L2E};
-    const f32x2 e_go = (f32x2){fabsf(x[2]), x[3]} * (f32x2){-2.f * L2E, -L2E};
-    const float a = __builtin_amdgcn_exp2f(e_if.x), b = __builtin_amdgcn_exp2f(e_if.y);
-    const float d = __builtin_amdgcn_exp2f(e_go.x), q = __builtin_amdgcn_exp2f(e_go.y);
-    const f32x2 p_ab = (f32x2){a, b} + (f32x2){1.f, 1.f};
-    const f32x2 p_dq = (f32x2){d, q} + (f32x2){1.f, 1.f};
-    const float r1 = __builtin_amdgcn_rcpf(p_ab.x * p_dq.x), rf = __builtin_amdgcn_rcpf(p_ab.y);
-    c = fmaf(c, rf, copysignf((1.f - d) * r1, x[2]));
-    const float e = __builtin_amdgcn_exp2f(fabsf(c) * (-2.f * L2E));
-    h = copysignf((1.f - e) * __builtin_amdgcn_rcpf(p_dq.y * (1.f + e)), c);
-}
 
 #ifdef NIR_CL_TRACE   // tools/cluster_micro.py --trace: phase-segment clocks of one wave of workgroup 0, summed over the launch (s_memtime ticks)
 __device__ unsigned long long* g_cl_trace_dev;
@@ -105,7 +83,6 @@ constexpr int CL_AUX_LD = (int)0x80000011;                    // buffer load: sc
 template <int NG, int MODE>
 __global__ __launch_bounds__(512, 1) void lstm_cluster_kernel(LstmClArgs p) {
     constexpr int H = CL_H, KB = CL_KB, NT = CL_NT, NW = CL_NW, SEQ = CL_SEQ, ZLD = CL_ZLD, NC = CL_NC, NTH = 64 * NW, H4 = 4 * H;
-    constexpr float SC = 2048.0f, ISC = 1.0f / 2048.0f;
     constexpr uint32_t OOB = 0x7FFFFFF0u;
     const int TP = p.T + 3;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -433,13 +410,13 @@ __global__ __launch_bounds__(512, 1) void lstm_cluster_kernel(LstmClArgs p) {
             for (int t = 0; t < NT; ++t) hn[t] = (acx[t][0] + acc[t][1]) * 1e-3f + creg[g][t];
 #else
             for (int t = 0; t < NT; ++t) {
-                if constexpr (MODE == 2) {            // the backward needs i, f, g, o themselves, not the merged fractions of cl_cell
-                    const f32x4 x = acx[t] * ISC + acc[t];
+                if constexpr (MODE == 2) {            // the backward needs i, f, g, o themselves, not the merged fractions of lstm_cell_v
+                    const f32x4 x = split2_combine(acc[t], acx[t]);
                     tga[t][0] = fast_sigmoid(x[0]); tga[t][1] = fast_sigmoid(x[1]); tga[t][2] = fast_tanh(x[2]); tga[t][3] = fast_sigmoid(x[3]);
                     creg[g][t] = tga[t][1] * creg[g][t] + tga[t][0] * tga[t][2];
                     hn[t] = tga[t][3] * fast_tanh(creg[g][t]);
                 } else {
-                    cl_cell(acx[t] * ISC + acc[t], creg[g][t], hn[t]);
+                    lstm_cell_v(split2_combine(acc[t], acx[t]), creg[g][t], hn[t]);
                 }
             }
 #endif
@@ -447,8 +424,8 @@ __global__ __launch_bounds__(512, 1) void lstm_cluster_kernel(LstmClArgs p) {
             _Float16 a[NT], r_[NT];
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
-                a[t] = (_Float16)hn[t];
-                r_[t] = (_Float16)((hn[t] - (float)a[t]) * SC);
+                a[t] = split2_hi1_rne(hn[t]);
+                r_[t] = split2_lo1(hn[t], a[t]);
             }
             *reinterpret_cast<f16x2*>(zn + cl_zo(sq, ug)) = (f16x2){a[0], a[1]};
             *reinterpret_cast<f16x2*>(zn + SEQ * ZLD + cl_zo(sq, ug)) = (f16x2){r_[0], r_[1]};
@@ -529,9 +506,9 @@ __global__ __launch_bounds__(64) void lstm256_whh_frag_kernel(const float* __res
             _Float16* o2 = o1 + 64 * 8;
             for (int j = 0; j < 8; ++j) {
                 const float w = wr[32 * kb + 8 * kq + j];
-                const _Float16 hi = (_Float16)w;
+                const _Float16 hi = split2_hi1_rne(w);
                 o1[j] = hi;
-                o2[j] = (_Float16)((w - (float)hi) * 2048.0f);
+                o2[j] = split2_lo1(w, hi);
                 bad |= !(fabsf(w) < 32768.0f);
             }
         }

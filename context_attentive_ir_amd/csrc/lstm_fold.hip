@@ -18,7 +18,7 @@
 //   lstm16_pt_bf16_kernel<KB,NT> bf16: v_mfma_f32_16x16x32_bf16, bf16 W_hh / h_t operands, fp32 accumulate, fp32 cell
 //                                state, bf16 folded table (BASELINE config 5)
 #include <type_traits>
-#include "common.hpp"
+#include "split2.hpp"
 #include <hip/hip_bf16.h>
 #include <string>
 #include <algorithm>
@@ -28,10 +28,6 @@ namespace nir {
 int launch_linear(const float* a, int64_t lda, const int64_t* ids, const float* table, int E, int64_t rows_per_seq,
                   int64_t seq_stride, const float* w, int64_t ldw, const float* bias, const float* bias2, float* c,
                   int64_t ldc, int64_t M, int N, int K, int act, hipStream_t st);
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // wperm[(dir*H + unit)*4 + gate][:] = wih[dir*4H + gate*H + unit][:],  bperm likewise = bih + bhh
 __global__ void fold_permute_kernel(const float* __restrict__ wih, const float* __restrict__ bih, const float* __restrict__ bhh,
@@ -243,74 +239,6 @@ __global__ __launch_bounds__(1024) void lstm16_pt_kernel(LstmPtArgs p) {
             for (int t2 = mylen; t2 < T; ++t2) p.out[(m * T + t2) * OW + (int64_t)dir * H + unit_d[t]] = 0.f;
         }
     }
-}
-
-// LSTM cell on the four pre-activations x = (i, f, g, o) of one unit, merged fractions: sigma(i) tanh(g) = sgn(g) (1 - d) / ((1 + a)(1 + d))
-// with a = e^-i, d = e^-2|g| (d in (0, 1]; a = inf gives 1 / inf = 0, the right limit), likewise o and tanh(c): 5 v_exp_f32 + 3 v_rcp_f32
-// instead of 5 + 5 -- the transcendentals are quarter rate, and the VALU port (gate math of all waves of a SIMD) is as loaded as the
-// matrix pipe in these recurrences.  The plain arithmetic is packed along the gate axis, (i, f) and (g, o) are adjacent accumulator
-// registers: v_pk_{fma,mul,add}_f32 without any register shuffling.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void lstm_cell_v(const f32x4 x, float& c, float& h) {
-    constexpr float L2E = 1.4426950408889634f;
-    const f32x2 e_if = (f32x2){x[0], x[1]} * (f32x2){-L2E, -L2E};
-    const f32x2 e_go = (f32x2){fabsf(x[2]), x[3]} * (f32x2){-2.f * L2E, -L2E};
-    const float a = __builtin_amdgcn_exp2f(e_if.x), b = __builtin_amdgcn_exp2f(e_if.y);
-    const float d = __builtin_amdgcn_exp2f(e_go.x), q = __builtin_amdgcn_exp2f(e_go.y);
-    const f32x2 p_ab = (f32x2){a, b} + (f32x2){1.f, 1.f};
-    const f32x2 p_dq = (f32x2){d, q} + (f32x2){1.f, 1.f};
-    const float r1 = __builtin_amdgcn_rcpf(p_ab.x * p_dq.x), rf = __builtin_amdgcn_rcpf(p_ab.y);
-    c = fmaf(c, rf, copysignf((1.f - d) * r1, x[2]));
-    const float e = __builtin_amdgcn_exp2f(fabsf(c) * (-2.f * L2E));
-    h = copysignf((1.f - e) * __builtin_amdgcn_rcpf(p_dq.y * (1.f + e)), c);
-}
-
-// The same cell for N units at once, written statement by statement ACROSS the units: program order is then N independent dependence chains
-// interleaved (every instruction's operand was produced N instructions earlier), which is what an in-order wave needs when this block is
-// issued between the MFMAs of another sequence group -- unit by unit, each v_exp / v_rcp result was consumed by the very next instruction.
-template <int N>
-__device__ __forceinline__ void lstm_cell_vn(const f32x4 (&x)[N], float (&c)[N], float (&h)[N]) {
-    constexpr float L2E = 1.4426950408889634f;
-    f32x2 e_if[N], e_go[N], p_ab[N], p_dq[N];
-    float a[N], b[N], d[N], q[N], r1[N], rf[N], e[N], t1[N], t2[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) e_if[i] = (f32x2){x[i][0], x[i][1]} * (f32x2){-L2E, -L2E};
-#pragma unroll
-    for (int i = 0; i < N; ++i) e_go[i] = (f32x2){fabsf(x[i][2]), x[i][3]} * (f32x2){-2.f * L2E, -L2E};
-#pragma unroll
-    for (int i = 0; i < N; ++i) a[i] = __builtin_amdgcn_exp2f(e_if[i].x);
-#pragma unroll
-    for (int i = 0; i < N; ++i) b[i] = __builtin_amdgcn_exp2f(e_if[i].y);
-#pragma unroll
-    for (int i = 0; i < N; ++i) d[i] = __builtin_amdgcn_exp2f(e_go[i].x);
-#pragma unroll
-    for (int i = 0; i < N; ++i) q[i] = __builtin_amdgcn_exp2f(e_go[i].y);
-#pragma unroll
-    for (int i = 0; i < N; ++i) p_ab[i] = (f32x2){a[i], b[i]} + (f32x2){1.f, 1.f};
-#pragma unroll
-    for (int i = 0; i < N; ++i) p_dq[i] = (f32x2){d[i], q[i]} + (f32x2){1.f, 1.f};
-#pragma unroll
-    for (int i = 0; i < N; ++i) t1[i] = p_ab[i].x * p_dq[i].x;
-#pragma unroll
-    for (int i = 0; i < N; ++i) r1[i] = __builtin_amdgcn_rcpf(t1[i]);
-#pragma unroll
-    for (int i = 0; i < N; ++i) rf[i] = __builtin_amdgcn_rcpf(p_ab[i].y);
-#pragma unroll
-    for (int i = 0; i < N; ++i) t2[i] = (1.f - d[i]) * r1[i];
-#pragma unroll
-    for (int i = 0; i < N; ++i) c[i] = fmaf(c[i], rf[i], copysignf(t2[i], x[i][2]));
-#pragma unroll
-    for (int i = 0; i < N; ++i) e[i] = __builtin_amdgcn_exp2f(fabsf(c[i]) * (-2.f * L2E));
-#pragma unroll
-    for (int i = 0; i < N; ++i) t1[i] = p_dq[i].y * (1.f + e[i]);
-#pragma unroll
-    for (int i = 0; i < N; ++i) r1[i] = __builtin_amdgcn_rcpf(t1[i]);
-#pragma unroll
-    for (int i = 0; i < N; ++i) h[i] = copysignf((1.f - e[i]) * r1[i], c[i]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -538,7 +466,6 @@ __global__ __launch_bounds__(64 * NW, NW <= 4 ? 2 : 1) void lstm16_pt_h2_kernel(
     constexpr int NTH = 64 * NW;
     constexpr int SEQ = 16, KP = 32 * KB, ZLD = KP + 8;     // fp16 elements per h row
     constexpr uint32_t OOB = 0x7FFFFFF0u;
-    constexpr float SC = 2048.0f, ISC = 1.0f / 2048.0f;
     // LDS layout of an h row (round 6).  The B fragments are read with ds_read_b128, whose lane groups are {0-3,12-15,20-27}, {4-11,16-19,28-31}, ...
     // (MI355X_MICROARCH.md, LDS): a group mixes sequences {0-3,12-15} of k-quarter kq = 2j with sequences {4-11} of kq = 2j + 1.  In the plain
     // [sequence][k] layout (row pitch 17 x 16 B) the two sets land one 16-byte slot apart and overlap in one slot: 2-way in every group, +4 LDS
@@ -693,9 +620,9 @@ __global__ __launch_bounds__(64 * NW, NW <= 4 ? 2 : 1) void lstm16_pt_h2_kernel(
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float w = wv[kb][j];
-                const _Float16 a = (_Float16)w;
+                const _Float16 a = split2_hi1_rne(w);
                 w1[t][kb][j] = a;
-                w2[t][kb][j] = (_Float16)((w - (float)a) * SC);
+                w2[t][kb][j] = split2_lo1(w, a);
                 wbad |= !(fabsf(w) < 32768.0f);             // outside the fp16 split's range (or NaN): flagged, never silently wrong
             }
         creg[t] = 0.f;
@@ -766,14 +693,14 @@ __global__ __launch_bounds__(64 * NW, NW <= 4 ? 2 : 1) void lstm16_pt_h2_kernel(
     float tga[TR ? NT : 1][4];                               // train mode: this step's i, f, g, o of the lane's units
     auto gates = [&](int t) {
         if constexpr (TR) {
-            const f32x4 x = acx[t] * ISC + acc[t];
+            const f32x4 x = split2_combine(acc[t], acx[t]);
             const float gi = fast_sigmoid(x[0]), gf = fast_sigmoid(x[1]), gg = fast_tanh(x[2]), go = fast_sigmoid(x[3]);
             const float cn = gf * creg[t] + gi * gg;
             creg[t] = cn;
             hn[t] = go * fast_tanh(cn);
             tga[t][0] = gi; tga[t][1] = gf; tga[t][2] = gg; tga[t][3] = go;
         } else {
-            lstm_cell_v(acx[t] * ISC + acc[t], creg[t], hn[t]);
+            lstm_cell_v(split2_combine(acc[t], acx[t]), creg[t], hn[t]);
         }
     };
     uint32_t aoff = (uint32_t)(((int64_t)(sq * T + (dir == 0 ? 0 : mylen - 1)) * GW + dir * H4 + u0) * 4);
@@ -903,7 +830,7 @@ __global__ __launch_bounds__(64 * NW, NW <= 4 ? 2 : 1) void lstm16_pt_h2_kernel(
         if (full && (NT == 4 || NT == 2)) {
             _Float16 a[NT], r[NT];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) a[t] = (_Float16)hn[t];
+            for (int t = 0; t < NT; ++t) a[t] = split2_hi1_rne(hn[t]);
             // residual = fp16(2^11 (h - a)) from ONE FMA per value: 2^11 a is exact in fp16 (|a| <= 1: a packed fp16 multiply per pair) and
             // h 2^11 - (2^11 a) is the same exact real number as (h - a) 2^11, rounded once -- bit-identical to convert / subtract / scale /
             // convert, 12 VALU per four values instead of 16 (8 with hand-written v_fma_mix{lo,hi}_f16).  Measured (tools/recur_micro.py,
@@ -912,11 +839,11 @@ __global__ __launch_bounds__(64 * NW, NW <= 4 ? 2 : 1) void lstm16_pt_h2_kernel(
                 _Float16 as_[NT];
 #pragma unroll
                 for (int t = 0; t < NT; t += 2) {
-                    const f16x2 p2 = (f16x2){a[t], a[(t + 1) % NT]} * (f16x2){(_Float16)2048.0f, (_Float16)2048.0f};
+                    const f16x2 p2 = (f16x2){a[t], a[(t + 1) % NT]} * (f16x2){(_Float16)SPLIT2_SCALE, (_Float16)SPLIT2_SCALE};
                     as_[t] = p2[0]; as_[(t + 1) % NT] = p2[1];
                 }
 #pragma unroll
-                for (int t = 0; t < NT; ++t) r[t] = (_Float16)__builtin_fmaf(hn[t], SC, -(float)as_[t]);
+                for (int t = 0; t < NT; ++t) r[t] = (_Float16)__builtin_fmaf(hn[t], SPLIT2_SCALE, -(float)as_[t]);
             }
             if (NT == 4) {
                 const f16x4 av = (f16x4){a[0], a[1 % NT], a[2 % NT], a[3 % NT]}, rv = (f16x4){r[0], r[1 % NT], r[2 % NT], r[3 % NT]};
@@ -938,9 +865,9 @@ __global__ __launch_bounds__(64 * NW, NW <= 4 ? 2 : 1) void lstm16_pt_h2_kernel(
 #pragma unroll
             for (int t = 0; t < NT; ++t)
                 if (u0 + t < H) {
-                    const _Float16 a = (_Float16)hn[t];
+                    const _Float16 a = split2_hi1_rne(hn[t]);
                     zn[zoff(sq, u0 + t)] = a;
-                    zn[SEQ * ZLD + zoff(sq, u0 + t)] = (_Float16)((hn[t] - (float)a) * SC);
+                    zn[SEQ * ZLD + zoff(sq, u0 + t)] = split2_lo1(hn[t], a);
                 }
         }
         if (!split && !H1) {
@@ -1285,9 +1212,9 @@ __global__ __launch_bounds__(64) void lstm_whh_frag_kernel(const float* __restri
             _Float16* o2 = o1 + 64 * 8;
             for (int j = 0; j < 8; ++j) {
                 const float w = wr[32 * kb + 8 * kq + j];
-                const _Float16 hi = (_Float16)w;
+                const _Float16 hi = split2_hi1_rne(w);
                 o1[j] = hi;
-                o2[j] = (_Float16)((w - (float)hi) * 2048.0f);
+                o2[j] = split2_lo1(w, hi);
                 bad |= !(fabsf(w) < 32768.0f);
             }
         }

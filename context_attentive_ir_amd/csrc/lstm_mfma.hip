@@ -13,12 +13,11 @@
 // barrier, (unit, seq) threads add the 4 partials + bias, apply the cell update (c_t in a register), write h_t and
 // x_{t+1} (prefetched from HBM one step ahead) into the other z buffer and h_t to HBM through a branch-free
 // raw-buffer store, barrier.  Masking / reverse-direction semantics as in lstm.hip.
-#include "common.hpp"
+#include "split2.hpp"
 #include <string>
 
 namespace nir {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct LstmMfmaArgs {
     const float* x;         // [M,T,I]

@@ -81,7 +81,6 @@ __global__ void copy_f32_kernel(const float* s, float* d, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) d[i] = s[i];
 }
-static dim3 g1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 size_t lstm_steps_ws_floats(int64_t M, int H) { return 2 * ((size_t)M * H * 2 + (size_t)M * 4 * H); }   // one set per direction
 

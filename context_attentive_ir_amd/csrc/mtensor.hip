@@ -9,7 +9,7 @@
 // by all N candidates, cutting the per-pair conv work 3x (the di sum) -- U is read through the scalar cache as
 // wave-uniform SGPR operands, the document projections sit transposed in LDS (one lane per doc position), and
 // ReLU / 1x1 conv / global max-pool / output Linear are fused in registers + wave shuffles.
-#include "common.hpp"
+#include "split2.hpp"
 #include <stdlib.h>
 #include <algorithm>
 
@@ -24,8 +24,6 @@ int launch_bilstm_fused(const float* x, int I, const float* wih, const float* bi
 
 int launch_bilstm_folded(const void* pt, int pt_dtype, const int64_t* ids, const int64_t* lens, const float* whh, float* out,
                          int* err, int64_t M, int64_t V, int T, int H, int ND, hipStream_t st, int out_f16 = 0, const void* whh_frag = nullptr);
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int CP = 56;     // channels padded 50 -> 56 so an 8-wide K group never straddles a conv tap (dj)
 constexpr int NFC = 6;     // filters per conv (hyparam.py:101)
@@ -59,10 +57,7 @@ constexpr int FOLD_Z = 4;
 // fp16 two-term form (H2) of the same operand, for the v_mfma_f32_16x16x32_f16 interaction GEMM: every conv tap is padded to 64 channels
 // (two 32-wide k-steps) and stored as MFMA A-fragments,
 //   Uh[b][tap 0..14][half 0..1][row tile 0..2MT-1][term 0..1][lane 64][8],   lane = 16 * (c % 32 / 8) + row % 16,
-// x = h1 + 2^-11 h2' with h1 = fp16_rtz(x), h2' = fp16(2^11 (x - h1))  (requires |U| < 2^15: host-checked `bounded`).
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// in the split2 format (split2.hpp; requires |U| < 2^15: host-checked `bounded`).
 constexpr int CH = 64;     // channels per tap in the H2 form
 __host__ __device__ inline int mt_tapoff(int k) { return k == 0 ? 0 : (k == 1 ? 3 : 8); }
 __host__ __device__ inline size_t mt_uh_halves(int MT) { return (size_t)15 * 2 * (2 * MT) * 2 * 64 * 8; }
@@ -112,12 +107,11 @@ __global__ __launch_bounds__(256) void mt_fold_kernel(const float* __restrict__ 
                     }
                 }
             }
-            const fp16x2_t h1 = __builtin_amdgcn_cvt_pkrtz(a0, a1);
-            const fp16x2_t h2 = __builtin_amdgcn_cvt_pkrtz((a0 - (float)h1[0]) * 2048.0f, (a1 - (float)h1[1]) * 2048.0f);
+            const Split2x2 s = split2(a0, a1);
             const int tk = mt_tapoff(k) + dj, half = c >> 5, kg = (c >> 3) & 3, e8 = c & 7, rt = r >> 4, row16 = r & 15;
             _Float16* d = uh + ((((int64_t)(tk * 2 + half) * (2 * MT) + rt) * 2) * 64 + kg * 16 + row16) * 8 + e8;
-            *reinterpret_cast<unsigned*>(d) = __builtin_bit_cast(unsigned, h1);
-            *reinterpret_cast<unsigned*>(d + 64 * 8) = __builtin_bit_cast(unsigned, h2);
+            *reinterpret_cast<unsigned*>(d) = split2_word(s.hi);
+            *reinterpret_cast<unsigned*>(d + 64 * 8) = split2_word(s.lo);
         }
         return;
     }
@@ -245,11 +239,10 @@ __global__ __launch_bounds__(256, 3) void mt_head_kernel(const float* __restrict
         __syncthreads();
         auto put = [&](int e, float x0, float x1) {            // elements 2e, 2e+1 -> the two term planes
             const int j = (2 * e) / C, c = 2 * e - j * C;
-            const fp16x2_t h1 = __builtin_amdgcn_cvt_pkrtz(x0, x1);
-            const fp16x2_t h2 = __builtin_amdgcn_cvt_pkrtz((x0 - (float)h1[0]) * 2048.0f, (x1 - (float)h1[1]) * 2048.0f);
+            const Split2x2 s = split2(x0, x1);
             _Float16* d = pdh + (j + 3) * CPH + c;
-            *reinterpret_cast<unsigned*>(d) = __builtin_bit_cast(unsigned, h1);
-            *reinterpret_cast<unsigned*>(d + DLH * CPH) = __builtin_bit_cast(unsigned, h2);
+            *reinterpret_cast<unsigned*>(d) = split2_word(s.hi);
+            *reinterpret_cast<unsigned*>(d + DLH * CPH) = split2_word(s.lo);
         };
         if (fuse_proj) {
             // Pd = hd Wd^T + b computed here (replaces the [M*DL,140] x [140,50] projection launch and the Pd round trip): wave = 16
@@ -285,12 +278,12 @@ __global__ __launch_bounds__(256, 3) void mt_head_kernel(const float* __restrict
                     }
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        const fp16x2_t a0 = __builtin_amdgcn_cvt_pkrtz(x0[i].x, x0[i].y), a1 = __builtin_amdgcn_cvt_pkrtz(x0[i].z, x0[i].w);
-                        const fp16x2_t a2 = __builtin_amdgcn_cvt_pkrtz(x1[i].x, x1[i].y), a3 = __builtin_amdgcn_cvt_pkrtz(x1[i].z, x1[i].w);
-                        const fp16x2_t b0 = __builtin_amdgcn_cvt_pkrtz((x0[i].x - (float)a0[0]) * 2048.0f, (x0[i].y - (float)a0[1]) * 2048.0f);
-                        const fp16x2_t b1 = __builtin_amdgcn_cvt_pkrtz((x0[i].z - (float)a1[0]) * 2048.0f, (x0[i].w - (float)a1[1]) * 2048.0f);
-                        const fp16x2_t b2 = __builtin_amdgcn_cvt_pkrtz((x1[i].x - (float)a2[0]) * 2048.0f, (x1[i].y - (float)a2[1]) * 2048.0f);
-                        const fp16x2_t b3 = __builtin_amdgcn_cvt_pkrtz((x1[i].z - (float)a3[0]) * 2048.0f, (x1[i].w - (float)a3[1]) * 2048.0f);
+                        const fp16x2_t a0 = split2_hi(x0[i].x, x0[i].y), a1 = split2_hi(x0[i].z, x0[i].w);
+                        const fp16x2_t a2 = split2_hi(x1[i].x, x1[i].y), a3 = split2_hi(x1[i].z, x1[i].w);
+                        const fp16x2_t b0 = split2_hi(split2_res(x0[i].x, a0[0]), split2_res(x0[i].y, a0[1]));
+                        const fp16x2_t b1 = split2_hi(split2_res(x0[i].z, a1[0]), split2_res(x0[i].w, a1[1]));
+                        const fp16x2_t b2 = split2_hi(split2_res(x1[i].x, a2[0]), split2_res(x1[i].y, a2[1]));
+                        const fp16x2_t b3 = split2_hi(split2_res(x1[i].z, a3[0]), split2_res(x1[i].w, a3[1]));
                         const f16x8 h1 = __builtin_bit_cast(f16x8, make_uint4(__builtin_bit_cast(unsigned, a0), __builtin_bit_cast(unsigned, a1),
                                                                                     __builtin_bit_cast(unsigned, a2), __builtin_bit_cast(unsigned, a3)));
                         const f16x8 h2 = __builtin_bit_cast(f16x8, make_uint4(__builtin_bit_cast(unsigned, b0), __builtin_bit_cast(unsigned, b1),
@@ -307,11 +300,11 @@ __global__ __launch_bounds__(256, 3) void mt_head_kernel(const float* __restrict
                         for (int r = 0; r < 4; ++r) {
                             const int j = jt * 64 + 16 * i + 4 * g4 + r;
                             if (j < DL) {
-                                const float v = fmaf(px[i][r], 1.0f / 2048.0f, pa[i][r]) + bias;
-                                const _Float16 a = (_Float16)__builtin_amdgcn_cvt_pkrtz(v, 0.f)[0];
+                                const float v = split2_combine(pa[i][r], px[i][r]) + bias;
+                                const _Float16 a = split2_hi1_rtz(v);
                                 _Float16* d = pdh + (j + 3) * CPH + c;
                                 d[0] = a;
-                                d[DLH * CPH] = (_Float16)((v - (float)a) * 2048.0f);
+                                d[DLH * CPH] = split2_lo1(v, a);
                             }
                         }
                 }
@@ -442,7 +435,7 @@ __global__ __launch_bounds__(256, 3) void mt_head_kernel(const float* __restrict
                     for (int j = 0; j < 2; ++j) {
                         float* yk = Y + ((int64_t)k * rows + mtl * 32 + 16 * i + 4 * g4) * YLD + nt * 32 + 16 * j + c16;
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) yk[r * YLD] = fmaf(acx[i][j][r], 1.0f / 2048.0f, acc[i][j][r]);
+                        for (int r = 0; r < 4; ++r) yk[r * YLD] = split2_combine(acc[i][j][r], acx[i][j][r]);
                     }
                 continue;
             }

@@ -10,7 +10,7 @@
 //   nir_dropout_f32        counter-based Bernoulli mask (splitmix64 of seed ^ index): the mask is an OUTPUT, so a parity
 //                          test can replay exactly the same mask through the oracle
 //   nir_act_bwd_f32, nir_bce_bwd_f32, nir_softmax_nll_bwd_f32   element-wise backward pieces
-#include "common.hpp"
+#include "split2.hpp"
 #include <mutex>
 #include <algorithm>
 
@@ -18,7 +18,6 @@ namespace nir {
 int launch_bilstm_mfma16(const float* gin, const int64_t* lens, const float* whh, const float* h0, const float* c0, float* out, float* hn,
                          float* cn, int64_t M, int T, int H, int ND, hipStream_t st, float* act, float* cst);
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---------------------------------------------------------------------------------------------------------------------
 // dW[n,k] += sum_m dY[m,n] * X[m,k].  One wave owns a 32x32 tile of dW and one slice of M; v_mfma_f32_32x32x2_f32 takes
@@ -686,7 +685,6 @@ __global__ __launch_bounds__(512) void lstm_train_bwd_kernel(LstmBwdArgs p) {
 // LDS [seq][q][k-step] (fp32, 16 B reads feed four k-steps) -> barrier -> NKS MFMAs per tile -> next step.  Two LDS buffers, one barrier
 // per step.
 // ---------------------------------------------------------------------------------------------------------------------
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // NTW = unit tiles per wave: 2 -> 4 waves (one per SIMD, W_hh fragments fill half the register file); 1 -> 8 waves, two per SIMD with 256
 // registers each (round 5: with 256 of 512 registers in fragments the prefetched cell inputs of the 4-wave form aliased the registers the
@@ -1246,8 +1244,6 @@ __global__ void lstm_cell_seq_bwd_kernel(const float* __restrict__ dh1, int64_t 
     dr[3 * H + j] = dhh * th * go * (1.f - go);
     dcprev[i] = dct * gf;
 }
-
-static inline dim3 g1(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 // ---- im2col as ROWS (training forwards of the 2-D convolutions, rankers/mtensor.py:108-121): out[(m, y, x)][(c, dy, dx)] =
 // in[m, c, y + dy - ph, x + dx - pw] (0 outside), stride 1, "same" geometry (2 ph = kh - 1, 2 pw = kw - 1) -- the A operand of the
