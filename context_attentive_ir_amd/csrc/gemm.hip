@@ -1224,6 +1224,14 @@ extern "C" int nir_linear_f32(const float* a, int64_t lda, const int64_t* ids, c
                               act, (hipStream_t)stream);
 }
 
+extern "C" int nir_linear_ex_f32(const float* a, int64_t lda, const int64_t* ids, const float* table, int E,
+                                 int64_t rows_per_seq, int64_t seq_stride, const float* w, int64_t ldw,
+                                 const float* bias, const float* bias2, float* c, int64_t ldc, int64_t M, int N, int K,
+                                 int act, const float* add, int64_t ldadd, nir_stream_t stream) {
+    return nir::launch_linear_ex(a, lda, ids, table, E, rows_per_seq, seq_stride, w, ldw, bias, bias2, c, ldc, M, N, K,
+                                 act, add, ldadd, (hipStream_t)stream);
+}
+
 extern "C" int nir_rowdot_f32(const float* x, int64_t ldx, const float* w, const float* b, float* out, int64_t M,
                               int K, int act, nir_stream_t stream) {
     return nir::launch_rowdot(x, ldx, w, b, out, M, K, act, (hipStream_t)stream);

@@ -28,6 +28,8 @@ typedef __fp16 fp16x2_t __attribute__((ext_vector_type(2)));      // what v_cvt_
 // h2' h1 and h1 h2' (both scaled by 2^11) to a second one (acx); the result is acc + 2^-11 acx (split2_combine).  That is 3 fp16 MFMAs
 // per k-block instead of the 6 bf16 ones of the three-term split (common.hpp: split3), ~4 VALU ops per element instead of 5.5, 2 LDS
 // planes instead of 3, at fp32-class accuracy (the dropped h2' h2' term is 2^-22 relative).
+// Lower range: h2' is an fp16 subnormal (quantum 2^-24) once 2^11 |x - h1| < 2^-14, so x is carried to max(2^-22 |x|, 2^-35) absolute:
+// fp32-class down to |x| ~ 2^-13, then the relative precision falls off (operands of 2^-20: about 3e-5 of a GEMM result).
 // Range: |x| < 2^15, else h1 overflows fp16.  Kernels that pack caller-provided weights test !(|w| < 32768) per element and raise bit 1
 // (value 2) of their error flag; the entry points that split activations on the fly take a host-checked `bounded` promise instead.
 // The helpers return values; where the terms go (LDS plane, fragment order, global) is the call site's business.  hipcc's schedule

@@ -93,6 +93,7 @@ SIGNATURES = {
     "nir_host_rank_metric": (C.c_double, [_i, C.c_void_p, C.c_void_p, _i, _l, _i, _i]),
     "nir_widen_ids_i32": (_i, [C.c_void_p, C.c_void_p, _l, c_st]),
     "nir_linear_f32": (_i, [c_fp, _l, c_ip, c_fp, _i, _l, _l, c_fp, _l, c_fp, c_fp, c_fp, _l, _l, _i, _i, _i, c_st]),
+    "nir_linear_ex_f32": (_i, [c_fp, _l, c_ip, c_fp, _i, _l, _l, c_fp, _l, c_fp, c_fp, c_fp, _l, _l, _i, _i, _i, c_fp, _l, c_st]),
     "nir_rowdot_f32": (_i, [c_fp, _l, c_fp, c_fp, c_fp, _l, _i, _i, c_st]),
     "nir_bilstm_fwd": (_i, [c_fp, c_ip, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, _l, _i, _i, _i, c_st]),
     "nir_bilstm_supported": (_i, [_i]),

@@ -142,11 +142,37 @@ int nir_widen_ids_i32(const int32_t* src, int64_t* dst, int64_t n, nir_stream_t 
  *       i.e. the embedding gather (neuroir/modules/embeddings.py:243-252) fused into the A-operand load; with
  *       K = ksize*E and rows_per_seq = L-ksize+1, seq_stride = L it is Conv1d(E -> N, ksize) over a padded
  *       id sequence (neuroir/rankers/duet.py:172-174).  W for the conv case must be laid out [N][ksize][E].
- * bias / bias2 may be NULL.  fp32 MFMA (v_mfma_f32_32x32x2_f32), exact-fp32 products. */
+ * bias / bias2 may be NULL.  The kernel is chosen by shape and alignment.  Small, skinny and mid-size problems, unaligned operands
+ * and gathers of more than three taps run on the fp32 matrix instructions (v_mfma_f32_32x32x2_f32 / 16x16x4_f32): exact fp32 products,
+ * fp32 accumulation.  Large ones (N >= 96, K >= 32, 16-byte aligned operands, at least 96 tiles of 128 x 128) run on the bf16 matrix
+ * cores: each operand is split into three truncated bf16 terms while its tile is staged and the six leading cross products are
+ * accumulated in fp32 -- fp32-class error (2^-22 of |a|.|w| from the format, plus the accumulation), not bit-exact fp32 products.
+ * The debug tunable "exact_f32" forces the fp32-MFMA kernels everywhere. */
 int nir_linear_f32(const float* a, int64_t lda, const int64_t* ids, const float* table, int E,
                    int64_t rows_per_seq, int64_t seq_stride, const float* w, int64_t ldw, const float* bias,
                    const float* bias2, float* c, int64_t ldc, int64_t M, int N, int K, int act,
                    nir_stream_t stream);
+
+/* nir_linear_f32 with every epilogue of the GEMM: v[m,n] = sum_k A(m,k) W[n,k] + bias[n] + bias2[n], then by `act & 0xff`
+ *   NIR_ACT_NONE / TANH / RELU   C[m,n] = act(v[m,n] + add[m*ldadd + n]);  add [M, ldadd] may be NULL.  C is [M, N].
+ *   NIR_ACT_MAXOUT2 (16)         C[m,j] = max(u[m,2j], u[m,2j+1]) with u = v + add (add [M, ldadd] or NULL).  N must be even; C is [M, N/2].
+ *   NIR_ACT_TANH_ROWDOT16 (17)   C[m,j] = sum_{n = 16j .. 16j+15} tanh(v[m,n]) * add[n]: a Linear(N,1) fused behind Linear+Tanh, the
+ *                                caller sums the N/16 partials of a row.  add is the [N] weight row (required; ldadd unused); N % 16 == 0;
+ *                                C is [M, N/16].
+ * ldc is the row stride of C as stored (>= N, N/2, N/16).  A violated condition is NIR_ERR_BAD_ARG and nothing is enqueued.
+ * NIR_ACT_BOUNDED (0x100) OR-ed into act is the caller's PROMISE that every element of both operands is below 2^15 in magnitude (tanh /
+ * sigmoid outputs, checked embedding tables and weights).  The large-problem path then uses the two-term fp16 split
+ * (x = h1 + 2^-11 h2', three fp16 MFMAs per product block) instead of the bf16 one; every other path ignores the flag.  Elements of
+ * 2^15 and above overflow the leading term: the result is then undefined, nothing checks it.  Lower range: the scaled residual h2' is an
+ * fp16 subnormal below 2^-14, so an operand is carried to max(2^-22 |x|, 2^-35) absolute -- fp32-class down to |x| ~ 2^-13; below that
+ * the relative precision falls off (about 3e-5 of the result for operands of 2^-20). */
+#define NIR_ACT_MAXOUT2 16
+#define NIR_ACT_TANH_ROWDOT16 17
+#define NIR_ACT_BOUNDED 0x100
+int nir_linear_ex_f32(const float* a, int64_t lda, const int64_t* ids, const float* table, int E,
+                      int64_t rows_per_seq, int64_t seq_stride, const float* w, int64_t ldw, const float* bias,
+                      const float* bias2, float* c, int64_t ldc, int64_t M, int N, int K, int act,
+                      const float* add, int64_t ldadd, nir_stream_t stream);
 
 /* out[m] = act( sum_k x[m*ldx+k] * w[k] + b[0] )  -- Linear(K -> 1). */
 int nir_rowdot_f32(const float* x, int64_t ldx, const float* w, const float* b, float* out, int64_t M, int K,
