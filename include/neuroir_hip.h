@@ -180,10 +180,15 @@ int nir_rowdot_f32(const float* x, int64_t ldx, const float* w, const float* b, 
 
 /* Recurrent half of RNNEncoder (neuroir/encoders/rnn_encoder.py:62-141; nn.LSTM, 1 layer, batch_first):
  *   gates_in [M,T,ndir*4H]  = x W_ih^T + b_ih + b_hh, PyTorch gate order (i,f,g,o), forward direction first;
- *   lengths  [M] (>=1, or NULL = all T); w_hh [ndir,4H,H];
+ *   lengths  [M] (the reference feeds >= 1; NULL = all T); w_hh [ndir,4H,H];
  *   h0/c0 [ndir,M,H] or NULL (zeros);  out [M,T,ndir*H], zero at t >= length (pack/unpack semantics);
  *   hn/cn [ndir,M,H] or NULL.  Variable length is handled by masking -- no sort, no host sync.
- * Supported H: 1..128 for ndir*... see nir_bilstm_supported(). */
+ * Every kernel clamps a length to [0, T]: a length above T behaves as T; a length of 0 (or below) leaves the sequence's row of out all
+ * zero and returns its initial state in hn / cn (h0 / c0, zeros where they are NULL).  The reverse direction of a sequence walks
+ * t = length-1 .. 0.  h0 and c0 are independent: either may be given without the other, the missing one is zeros; hn and cn likewise
+ * (either, both or neither is written).  Nothing but out [M,T,ndir*H] (every element, the padded tail included) and hn / cn is written.
+ * Supported H: 1..128 per direction for ndir 1 and 2 (nir_bilstm_supported(H)); T * ndir * H is limited by 32-bit tile offsets
+ * (8 * T * ndir * 4H * 4 bytes < 2^31 - 16, refused beyond); larger H: nir_bilstm_steps_fwd. */
 int nir_bilstm_fwd(const float* gates_in, const int64_t* lengths, const float* w_hh, const float* h0,
                    const float* c0, float* out, float* hn, float* cn, int64_t M, int T, int H, int ndir,
                    nir_stream_t stream);
@@ -607,7 +612,9 @@ int nir_lstm256_bptt(const float* dout, const float* act, const float* cst, cons
 
 /* The same streaming recurrence for either cell of the reference's RNNEncoder (rnn_encoder.py:28-60: getattr(nn, rnn_type), one module per
  * layer): NIR_CELL_LSTM = nir_bilstm_steps_fwd; NIR_CELL_GRU: torch.nn.GRU semantics, gate order (r, z, n), gates_in = x W_ih^T + b_ih
- * [M,T,ndir*3H], w_hh [ndir,3H,H], b_hh [ndir,3H] (inside the reset-gate product), c0 / cn unused.  Workspace: nir_bilstm_steps_workspace_bytes. */
+ * [M,T,ndir*3H], w_hh [ndir,3H,H], b_hh [ndir,3H] (inside the reset-gate product), c0 / cn unused.  Workspace: nir_bilstm_steps_workspace_bytes.
+ * Lengths are clamped to [0, T] as in nir_bilstm_fwd (length 0: out and c_steps rows zero, hn / cn = the initial state); c_steps is zero at
+ * t >= length like out. */
 #define NIR_CELL_LSTM 0
 #define NIR_CELL_GRU 1
 int nir_birnn_steps_fwd(int cell, const float* gates_in, const int64_t* lengths, const float* w_hh, const float* b_hh, const float* h0,

@@ -124,9 +124,11 @@ def test_rnn_encoder(H, I, M, T_):
     (hn_ref, cn_ref), ref = O.rnn_encode(sd, "e", x, lens)
     enc = enc.to(DEV)
     (hn, cn), out = enc(x.to(DEV), lens.to(DEV))
-    _close(out, ref, 2e-5)
+    # 5e-6: the recurrence alone is held to <= 3.6e-6 against float64 at such shapes (tests/test_gpu_rnn_envelope.py), this oracle is an fp32
+    # chain itself (<= 6e-7) and the input GEMM over I = 300 adds ~1e-6 to the gates; measured worst 1.9e-6 (H = 128, I = 300, 1100 sequences)
+    _close(out, ref, 5e-6)
     order = torch.sort(lens, 0, True)[1]                   # reference leaves final states in sorted order
-    _close(hn[:, order], hn_ref, 2e-5); _close(cn[:, order], cn_ref, 2e-5)
+    _close(hn[:, order], hn_ref, 5e-6); _close(cn[:, order], cn_ref, 5e-6)
 
 
 @pytest.mark.parametrize("H,I,M,T_", [(70, 40, 37, 20), (15, 40, 50, 6), (128, 300, 40, 12), (96, 64, 21, 8), (96, 100, 33, 9),
