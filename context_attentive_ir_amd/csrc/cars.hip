@@ -62,6 +62,7 @@ __global__ __launch_bounds__(256) void attn_pool_kernel(const float* __restrict_
             float4 v = *reinterpret_cast<const float4*>(h + (m * T + t) * D + 4 * c);
             acc.x = fmaf(p, v.x, acc.x); acc.y = fmaf(p, v.y, acc.y); acc.z = fmaf(p, v.z, acc.z); acc.w = fmaf(p, v.w, acc.w);
         }
+        if (len == 0) acc = make_float4(NAN, NAN, NAN, NAN);   // like softmax over an all -inf row, and like every other pooling kernel
         *reinterpret_cast<float4*>(pooled + m * D + 4 * c) = acc;
     }
 }
@@ -113,6 +114,40 @@ __global__ __launch_bounds__(256) void attn_pool2_kernel(const float* __restrict
         if (len == 0) acc = make_float4(NAN, NAN, NAN, NAN);
         *reinterpret_cast<float4*>(pooled + m * D + 4 * c) = acc;
     }
+}
+
+// true when the non-plain attn_pool_dispatch runs a fused kernel (the callers choose the recurrence's output format by it)
+static bool attn_pool_fused_selected(const nir_cars_encoder_weights* w, int D, int T) {
+    return w->attn_frag && (w->bounded & 1) && attn_pool_fused_usable(D, T) && !tun(g_tun.attn_unfused) && !tun(g_tun.exact_f32);
+}
+
+// apply_pooling on finished rows: the one place that chooses among the pooling kernels (nir_cars_encode, nir_cars_encode_folded and
+// nir_attn_pool_f32 all end here).  in_fmt: the row format launch_attn_pool_fused takes (0 fp32, 1 fp16 rows, 2 term pairs, 3 fp16 rows with
+// two-term W0); plain: the exact three-launch chain (GEMM + tanh, row-dot, attn_pool_kernel) with a1 [M*T, D] and logit [M*T]; otherwise
+// the fused kernel where it applies, else the ACT_TANH_ROWDOT16 GEMM into a1 [M*T, D/16] plus attn_pool2_kernel.
+static int attn_pool_dispatch(const float* enc, int in_fmt, const nir_cars_encoder_weights* w, const int64_t* lens, int64_t M, int T, int D,
+                              int one_term, bool plain, float* a1, float* logit, float* pooled, hipStream_t st) {
+    if (plain) {
+        NIR_PROPAGATE(launch_linear(enc, D, nullptr, nullptr, 0, 0, 0, w->attn0_w, D, w->attn0_b, nullptr, a1, D, M * T, D, D, NIR_ACT_TANH, st));
+        NIR_PROPAGATE(launch_rowdot(a1, D, w->attn3_w, w->attn3_b, logit, M * T, D, NIR_ACT_NONE, st));
+        {
+            ProfScope ps("attn_pool_kernel", st);
+            hipLaunchKernelGGL(attn_pool_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, enc, logit, lens, M, T, D, pooled);
+        }
+        NIR_CHECK_LAUNCH("attn_pool_kernel");
+        return 0;
+    }
+    if (attn_pool_fused_selected(w, D, T))
+        return launch_attn_pool_fused(enc, w->attn_frag, w->attn0_b, w->attn3_w, w->attn3_b, lens, M, T, pooled, one_term, st, in_fmt);
+    const int NP = D / 16;
+    NIR_PROPAGATE(launch_linear_ex(enc, D, nullptr, nullptr, 0, 0, 0, w->attn0_w, D, w->attn0_b, nullptr, a1, NP, M * T, D, D,
+                                   ACT_TANH_ROWDOT16 | ((w->bounded & 1) ? ACT_BOUNDED : 0), w->attn3_w, 0, st));
+    {
+        ProfScope ps("attn_pool2_kernel", st);
+        hipLaunchKernelGGL(attn_pool2_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), (size_t)4 * T * 4, st, enc, a1, NP, w->attn3_b, lens, M, T, D, pooled);
+    }
+    NIR_CHECK_LAUNCH("attn_pool2_kernel");
+    return 0;
 }
 
 struct EncPlan {
@@ -168,32 +203,15 @@ extern "C" int nir_cars_encode(const int64_t* ids, const int64_t* lens, int64_t 
         // (bit 1 of `bounded`: |table|, |W_ih| < 2^15 host-checked -> the gather-GEMM takes the fp16 two-term split, 3 MFMAs per product instead of 6)
         NIR_PROPAGATE(launch_linear_ex(nullptr, 0, ids, table, E, 1, 1, p.wperm, E, p.bperm, nullptr, p.gates, 8 * H, M * T, 8 * H, E,
                                        NIR_ACT_NONE | ((w->bounded & 2) ? ACT_BOUNDED : 0), nullptr, 0, st));
-        const bool fused_attn = w->attn_frag && (w->bounded & 1) && attn_pool_fused_usable(D, T) && !tun(g_tun.attn_unfused);
+        const bool fused_attn = attn_pool_fused_selected(w, D, T);          // (exact_f32 is off on this branch)
         const bool inside = fused_attn && !encoded && attn_pool_pipe_selected(M, T);
         const int enc16 = inside && bilstm_folded_split_out_ok(NIR_DTYPE_F32, H, T) && !tun(g_tun.attn_fp32_rows) ? 2 : 0;
         NIR_PROPAGATE(launch_bilstm_folded(p.gates, NIR_DTYPE_F32, p.iota, lens, w->whh, enc, nullptr, M, M * T, T, H, 2, st, enc16, w->whh_frag));
-        if (fused_attn)
-            return launch_attn_pool_fused(enc, w->attn_frag, w->attn0_b, w->attn3_w, w->attn3_b, lens, M, T, pooled, 0, st, enc16);
-        const int NP = D / 16;
-        NIR_PROPAGATE(launch_linear_ex(enc, D, nullptr, nullptr, 0, 0, 0, w->attn0_w, D, w->attn0_b, nullptr, p.a1, NP, M * T, D, D,
-                                       ACT_TANH_ROWDOT16 | ((w->bounded & 1) ? ACT_BOUNDED : 0), w->attn3_w, 0, st));
-        {
-            ProfScope ps("attn_pool2_kernel", st);
-            hipLaunchKernelGGL(attn_pool2_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), (size_t)4 * T * 4, st, enc, p.a1, NP, w->attn3_b, lens, M, T, D, pooled);
-        }
-        NIR_CHECK_LAUNCH("attn_pool2_kernel");
-        return 0;
+        return attn_pool_dispatch(enc, enc16, w, lens, M, T, D, 0, false, p.a1, p.logit, pooled, st);
     }
     NIR_PROPAGATE(launch_linear(nullptr, 0, ids, table, E, 1, 1, w->wih, E, w->bih, w->bhh, p.gates, 8 * H, M * T, 8 * H, E, NIR_ACT_NONE, st));
     NIR_PROPAGATE(launch_bilstm(p.gates, lens, w->whh, nullptr, nullptr, enc, nullptr, nullptr, M, T, H, 2, st));
-    NIR_PROPAGATE(launch_linear(enc, D, nullptr, nullptr, 0, 0, 0, w->attn0_w, D, w->attn0_b, nullptr, p.a1, D, M * T, D, D, NIR_ACT_TANH, st));
-    NIR_PROPAGATE(launch_rowdot(p.a1, D, w->attn3_w, w->attn3_b, p.logit, M * T, D, NIR_ACT_NONE, st));
-    {
-        ProfScope ps("attn_pool_kernel", st);
-        hipLaunchKernelGGL(attn_pool_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, enc, p.logit, lens, M, T, D, pooled);
-    }
-    NIR_CHECK_LAUNCH("attn_pool_kernel");
-    return 0;
+    return attn_pool_dispatch(enc, 0, w, lens, M, T, D, 0, true, p.a1, p.logit, pooled, st);
 }
 
 namespace nir {
@@ -229,14 +247,14 @@ extern "C" int nir_cars_encode_folded(const int64_t* ids, const int64_t* lens, i
     // apply (H = 128, T in {4..64}, enough tiles); anywhere else the call is the plain fp32-accurate one
     const bool split2 = dtype == NIR_DTYPE_F32_SPLIT2;
     if (split2) dtype = NIR_DTYPE_F32;
-    const int H = w->H, D = 2 * H, NP = D / 16;
+    const int H = w->H, D = 2 * H;
     EncFoldPlan p = enc_fold_plan(workspace, workspace_bytes, M, T, H);
     if (!workspace || p.bytes > workspace_bytes) {
         set_error("cars_encode_folded: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
         return NIR_ERR_WORKSPACE;
     }
     float* enc = encoded ? encoded : p.enc;
-    const bool fused_attn = w->attn_frag && (w->bounded & 1) && attn_pool_fused_usable(D, T) && !tun(g_tun.attn_unfused) && !tun(g_tun.exact_f32);
+    const bool fused_attn = attn_pool_fused_selected(w, D, T);
     // bf16 encoder whose per-token states stay inside this call and go to the attention pipeline: they travel as fp16 (the pipeline
     // takes single fp16 terms from a bf16 encoder anyway) -- half the bytes written by the recurrence and read by the pooling
     // fp32-accurate encoder in the same situation: the recurrence already forms the two fp16 terms of every h_t for its own next step and
@@ -247,16 +265,39 @@ extern "C" int nir_cars_encode_folded(const int64_t* ids, const int64_t* lens, i
                                      (bilstm_folded_split_out_ok(dtype, H, T) && !tun(g_tun.attn_fp32_rows) ? (split2 ? 3 : 2) : 0));
     NIR_PROPAGATE(launch_bilstm_folded(folded, dtype, ids, lens, w->whh, enc, err_flag, M, V, T, H, 2, st, enc16, dtype == NIR_DTYPE_F32 ? w->whh_frag : nullptr));
     // enc = o * tanh(c) lies in (-1,1); the attention weights are bounded (checked by the host when it packs them)
-    if (fused_attn)
-        return launch_attn_pool_fused(enc, w->attn_frag, w->attn0_b, w->attn3_w, w->attn3_b, lens, M, T, pooled, dtype == NIR_DTYPE_BF16, st, enc16);
-    NIR_PROPAGATE(launch_linear_ex(enc, D, nullptr, nullptr, 0, 0, 0, w->attn0_w, D, w->attn0_b, nullptr, p.lpart, NP, M * T, D, D,
-                                   ACT_TANH_ROWDOT16 | ((w->bounded & 1) ? ACT_BOUNDED : 0), w->attn3_w, 0, st));
-    {
-        ProfScope ps("attn_pool2_kernel", st);
-        hipLaunchKernelGGL(attn_pool2_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), (size_t)4 * T * 4, st, enc, p.lpart, NP,
-                           w->attn3_b, lens, M, T, D, pooled);
-    }
-    NIR_CHECK_LAUNCH("attn_pool2_kernel");
-    return 0;
+    return attn_pool_dispatch(enc, enc16, w, lens, M, T, D, dtype == NIR_DTYPE_BF16, false, p.lpart, nullptr, pooled, st);
 }
 
+// CARS.apply_pooling alone, on rows the caller provides: the dispatch of the two encode entries above (include/neuroir_hip.h)
+extern "C" size_t nir_attn_pool_workspace_bytes(int64_t M, int T, int D) {
+    if (M < 0 || T <= 0 || D <= 0) return 0;
+    return nir::align_up((size_t)M * T * D * sizeof(float), 256) + nir::align_up((size_t)M * T * sizeof(float), 256);
+}
+
+extern "C" int nir_attn_pool_f32(const void* rows, int row_format, const nir_cars_encoder_weights* w, const int64_t* lens, int64_t M, int T,
+                                 int D, int flags, void* workspace, size_t workspace_bytes, float* pooled, nir_stream_t stream) {
+    using namespace nir;
+    hipStream_t st = (hipStream_t)stream;
+    NIR_REQUIRE(rows && w && pooled, "attn_pool: null pointer");
+    NIR_REQUIRE(w->attn0_w && w->attn0_b && w->attn3_w && w->attn3_b, "attn_pool: null attention weight");
+    NIR_REQUIRE(M >= 0 && T > 0 && D > 0 && D % 4 == 0 && D <= 1024, "attn_pool: bad dims (D %% 4 == 0, D <= 1024)");
+    // attn_pool2_kernel reads the D / 16 logit partials of a row as float4: like the encode entries, (2H) % 64 == 0
+    NIR_REQUIRE((flags & NIR_ATTN_POOL_PLAIN) || D % 64 == 0, "attn_pool: D = %d needs D %% 64 == 0 (or NIR_ATTN_POOL_PLAIN)", D);
+    NIR_REQUIRE(row_format >= 0 && row_format <= 3 && (flags & ~3) == 0, "attn_pool: unknown row format %d / flags %d", row_format, flags);
+    if (M == 0) return 0;
+    const bool plain = (flags & NIR_ATTN_POOL_PLAIN) != 0;
+    const bool fused = !plain && attn_pool_fused_selected(w, D, T);
+    NIR_REQUIRE(row_format == 0 || fused, "attn_pool: fp16 rows and term pairs are only taken by the fused pipeline (D = 256, T in 4..64, "
+                "attn_frag, bounded)");
+    float *a1 = nullptr, *logit = nullptr;
+    if (!fused) {
+        const size_t need = nir_attn_pool_workspace_bytes(M, T, D);
+        if (!workspace || need > workspace_bytes) {
+            set_error("attn_pool: workspace too small (%zu < %zu)", workspace_bytes, need);
+            return NIR_ERR_WORKSPACE;
+        }
+        a1 = (float*)workspace;
+        logit = (float*)((char*)workspace + align_up((size_t)M * T * D * sizeof(float), 256));
+    }
+    return attn_pool_dispatch((const float*)rows, row_format, w, lens, M, T, D, flags & NIR_ATTN_POOL_ONE_TERM, plain, a1, logit, pooled, st);
+}

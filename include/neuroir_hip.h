@@ -401,7 +401,8 @@ typedef struct {
 } nir_cars_encoder_weights;
 size_t nir_cars_encode_workspace_bytes(int64_t M, int T, int E, const nir_cars_encoder_weights* w /*host*/);
 /* CARS.encode / CARS.encode_document (cars.py:193-260): ids [M,T], lens [M] -> pooled [M,2H];
- * encoded (optional) [M,T,2H] memory bank. */
+ * encoded (optional) [M,T,2H] memory bank.  Lengths are clamped to [0, T]; a sequence of length 0 gets an all-NaN row of pooled (its
+ * softmax is 0/0, as the reference's masked_fill(-inf) + softmax gives) on every kernel path -- see nir_attn_pool_f32. */
 int nir_cars_encode(const int64_t* ids, const int64_t* lens, int64_t M, int T, const float* table, int64_t V, int E,
                     const nir_cars_encoder_weights* w /*host*/, void* workspace, size_t workspace_bytes,
                     float* pooled, float* encoded, nir_stream_t stream);
@@ -434,11 +435,46 @@ int nir_bilstm_folded_fwd(const void* folded, int dtype, const int64_t* ids, con
                           float* out, int* err_flag, int64_t M, int64_t V, int T, int H, int ndir, nir_stream_t stream);
 /* CARS.encode / encode_document (cars.py:193-260) over a folded table: same outputs as nir_cars_encode.  With a bf16 table,
  * `encoded` == NULL and a launch large enough for the pipelined attention kernel, the per-token states stay inside the call as
- * fp16 rows (the attention MLP then takes single fp16 terms); pass `encoded` to get them as fp32. */
+ * fp16 rows (the attention MLP then takes single fp16 terms); pass `encoded` to get them as fp32.
+ * Lengths are clamped to [0, T]; a sequence of length 0 gets an all-NaN row of pooled, as in nir_cars_encode. */
 size_t nir_cars_encode_folded_workspace_bytes(int64_t M, int T, const nir_cars_encoder_weights* w /*host*/);
 int nir_cars_encode_folded(const int64_t* ids, const int64_t* lens, int64_t M, int T, const void* folded, int dtype, int64_t V,
                            const nir_cars_encoder_weights* w /*host*/, void* workspace, size_t workspace_bytes, float* pooled,
                            float* encoded, int* err_flag, nir_stream_t stream);
+
+/* CARS.apply_pooling (cars.py:671-691) alone, on rows the caller provides -- the tail of nir_cars_encode / nir_cars_encode_folded, which
+ * both end in the same internal dispatch:
+ *     logit[m,t] = attn3_w . tanh(attn0_w rows[m,t] + attn0_b) + attn3_b;   p[m,:] = softmax over t < lens[m];   pooled[m] = sum_t p[m,t] rows[m,t]
+ * w: only attn0_w [D,D], attn0_b [D], attn3_w [D], attn3_b [1], `bounded` (bit 0) and attn_frag are read (all four weights required).
+ * rows [M*T, D] in `row_format`:
+ *   0  fp32.
+ *   1  fp16 rows (2 bytes per element); they and W0 enter the GEMM as single fp16 terms.
+ *   2  term pairs, as the fp32-accurate folded recurrence writes them: per row and group of four columns 16 bytes = the 4 leading fp16
+ *      terms h1, then the 4 residual terms h2' = fp16(2^11 (x - h1)); x = h1 + 2^-11 h2'.  4 bytes per element, like fp32.
+ *   3  fp16 rows as single terms against the two-term W0.
+ * Formats 1-3 are taken only by the pipelined fused kernel: D = 256, T in {4, 8, 16, 32, 64}, attn_frag given, bit 0 of `bounded` set, the
+ * attn_unfused / exact_f32 tunables clear, and M * T large enough for the pipeline (at least 2 * 64 rows per compute unit; or forced by
+ * the tunable attn_unfused_pipe = 2).  Anywhere else they are NIR_ERR_BAD_ARG, as is format 2 with NIR_ATTN_POOL_ONE_TERM.
+ * flags: NIR_ATTN_POOL_ONE_TERM -- fp32 rows and W0 enter the pipelined kernel's GEMM as ONE fp16 term each, rounded toward zero (what a
+ * bf16 encoder asks for; ignored by every other kernel).  NIR_ATTN_POOL_PLAIN -- the exact chain: fp32 GEMM + tanh, row-dot, pooling kernel.
+ * Without PLAIN: a fused kernel under the conditions above (fp32 rows: any M), else the GEMM with the tanh-rowdot epilogue plus a pooling
+ * kernel.  workspace: nir_attn_pool_workspace_bytes(M, T, D), needed by the two unfused chains only (may be NULL for a fused call).
+ * D % 64 == 0 and D <= 1024 (the pooling kernel behind the GEMM reads the D / 16 logit partials of a row four at a time); with
+ * NIR_ATTN_POOL_PLAIN any D % 4 == 0, D <= 1024.  Any other D is NIR_ERR_BAD_ARG.
+ * Bounded operands: with bit 0 of `bounded` set the caller promises |attn0_w| < 2^15 and rows inside (-1, 1) (encoder outputs o * tanh(c));
+ * the split-precision kernels carry both as fp16 terms and nothing checks it.  tanh saturates cleanly: any finite pre-activation gives a
+ * finite result.
+ * lens [M] or NULL (= all T).  Every kernel clamps a length to [0, T].  Length 0: that row of pooled is all NaN (0/0, what softmax over an
+ * all -inf row gives in the reference) -- every kernel form agrees; the other rows are not affected.
+ * Padded rows (t >= length) never reach pooled: their probability is exactly 0 and their own logit is not read, so pooled is bit-identical
+ * whatever finite values they hold.  They must be FINITE: the fused kernels multiply them by that 0 (an Inf or NaN there makes the row of
+ * pooled NaN); the unfused kernels skip them.
+ * Writes pooled [M, D] and the workspace, nothing else.  M == 0 returns 0 and enqueues nothing. */
+#define NIR_ATTN_POOL_ONE_TERM 1
+#define NIR_ATTN_POOL_PLAIN 2
+size_t nir_attn_pool_workspace_bytes(int64_t M, int T, int D);
+int nir_attn_pool_f32(const void* rows, int row_format, const nir_cars_encoder_weights* w /*host*/, const int64_t* lens, int64_t M, int T,
+                      int D, int flags, void* workspace, size_t workspace_bytes, float* pooled, nir_stream_t stream);
 
 typedef struct {
     const float *click0_w, *click0_b, *click3_w, *click3_b; /* click_attn.{0,3} [D,D],[D],[1,D],[1] */

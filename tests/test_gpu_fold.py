@@ -178,11 +178,12 @@ def test_fused_attention_pooling_matches_layer_chain_and_oracle(S, N, QL, DL):
     with lib.tunable("attn_unfused", 1, 0):
         p0, e0, _ = m.encode(exd["source_words"], exd["source_lens"])
         d0 = m.encode_document(exd["document_words"], exd["document_lens"])
-    _close(p1, p0, 5e-6); _close(d1, d0, 5e-6); _close(e1, e0, 0)
+    # (twice the worst deviation measured on the MI355X over the four shapes: 5.96e-8 for the queries, 1.49e-7 for the documents)
+    _close(p1, p0, 1.2e-7); _close(d1, d0, 3e-7); _close(e1, e0, 0)
     sd = cpu_state_dict(m)
     pq, _ = O.cars_encode(sd, ex["source_words"], ex["source_lens"])
-    _close(p1, pq, 1e-5)
-    _close(d1, O.cars_encode_document(sd, ex["document_words"], ex["document_lens"]), 1e-5)
+    _close(p1, pq, 2.4e-7)                               # against the oracle: measured worst 1.19e-7 (queries), 1.49e-7 (documents)
+    _close(d1, O.cars_encode_document(sd, ex["document_words"], ex["document_lens"]), 3e-7)
 
 
 @pytest.mark.parametrize("S,N,QL,DL", [(3, 9, 4, 64), (2, 5, 8, 16), (5, 3, 16, 32), (1, 2, 4, 4)])
@@ -201,14 +202,15 @@ def test_attention_pooling_pipeline_kernel(S, N, QL, DL):
         d1 = m.encode_document(ex["document_words"], ex["document_lens"])       # H = 128: the recurrence hands its term pairs over (mode 2)
         with lib.tunable("attn_fp32_rows", 1, 0):
             d2 = m.encode_document(ex["document_words"], ex["document_lens"])   # fp32 rows, split again by the IO waves (mode 0)
-    _close(p1, p0, 5e-6); _close(d1, d0, 5e-6); _close(d2, d0, 5e-6)
+    # (twice the worst deviation measured on the MI355X over the four shapes: 8.94e-8, 1.19e-7 and 1.49e-7)
+    _close(p1, p0, 1.8e-7); _close(d1, d0, 2.4e-7); _close(d2, d0, 3e-7)
     assert not torch.equal(d1, d2)                       # two different roundings of the residual term (nearest vs toward zero): both ran
 
 
 def test_recurrence_hands_term_pairs_to_attention_pipeline_vs_oracle():
     """A document block large enough for the pipeline to be selected by tile count (608 documents x 64 steps = 608 tiles >= 2 x 256 CUs), ragged
     lengths: lstm16_pt_h2_kernel<4,4,8> writes every h_t as [4 x leading fp16 term | 4 x residual term] per group of 4 units and
-    attn_pool_pipe_kernel<false,2> stages those 16-byte groups straight into its LDS planes.  pooled_docs against the ORACLE at 2e-5
+    attn_pool_pipe_kernel<false,2> stages those 16-byte groups straight into its LDS planes.  pooled_docs against the ORACLE at 3.9e-7
     (|pooled| < 1), and the raw hand-over buffer decodes to the fp32 states of the plain output (2^-22 relative to |h| < 1)."""
     from context_attentive_ir_amd import lib
     V, M, T_ = 3000, 608, 64
@@ -221,10 +223,10 @@ def test_recurrence_hands_term_pairs_to_attention_pipeline_vs_oracle():
     sd = cpu_state_dict(m)
     ref = O.cars_encode_document(sd, ids.view(1, 1, M, T_), lens.view(1, 1, M)).view(M, -1)
     got = m.encode_document(ids.view(1, 1, M, T_).to(DEV), lens.view(1, 1, M).to(DEV)).view(M, -1).cpu()
-    np.testing.assert_allclose(got.numpy(), ref.numpy(), rtol=0, atol=2e-5)
+    np.testing.assert_allclose(got.numpy(), ref.numpy(), rtol=0, atol=3.9e-7)             # measured worst 1.94e-7, both row formats
     with lib.tunable("attn_fp32_rows", 1, 0):
         got0 = m.encode_document(ids.view(1, 1, M, T_).to(DEV), lens.view(1, 1, M).to(DEV)).view(M, -1).cpu()
-    np.testing.assert_allclose(got0.numpy(), ref.numpy(), rtol=0, atol=2e-5)
+    np.testing.assert_allclose(got0.numpy(), ref.numpy(), rtol=0, atol=3.9e-7)
     assert not torch.equal(got, got0)
     # the hand-over format itself, through the C-ABI recurrence entry (plain fp32 output) against the decode of what the pipeline reads
     from context_attentive_ir_amd.encoders.rnn_encoder import lstm_cat_weights
