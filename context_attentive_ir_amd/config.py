@@ -4,7 +4,7 @@ Mirror of the reference's config API for the five hot-path models (SURVEY.md App
   * add_model_args / get_model_args / update_model_args / override_model_args keep the call
     shapes of /root/reference/neuroir/config.py:33,98,115,123;
   * the per-model fixed hyper-parameters keep the values of /root/reference/neuroir/hyparam.py
-    (ESM :3-8, DSSM :10-20, CDSSM :22-32, DUET :34-46, DRMM :78-86, MATCH_TENSOR :88-105, CARS :197-225).
+    (ESM :3-8, DSSM :10-20, CDSSM :22-32, DUET :34-46, ARCI :48-59, DRMM :78-86, MATCH_TENSOR :88-105, CARS :197-225).
 Everything is table-driven here; models outside the hot path are not listed (they keep
 running on the reference's own stock-PyTorch classes).
 """
@@ -20,6 +20,8 @@ MODEL_ARCHITECTURE = {
     "DSSM": dict(arch=dict(nhid=300, nout=128), data=dict(use_char_ngram=3, src_vocab_size=30000, embedding_file="")),
     "CDSSM": dict(arch=dict(nhid=300, nout=128), data=dict(use_char_ngram=3, src_vocab_size=30000, embedding_file="")),
     "DUET": dict(arch=dict(nfilters=300, local_filter_size=1, dist_filter_size=3, pool_size=5),
+                 data=dict(src_vocab_size=None, force_pad=True, fix_embeddings=True)),
+    "ARCI": dict(arch=dict(filters_1d=[256, 128], kernel_size_1d=[3, 3], maxpool_size_1d=[2, 2]),
                  data=dict(src_vocab_size=None, force_pad=True, fix_embeddings=True)),
     "DRMM": dict(arch=dict(nbins=5), data=dict(src_vocab_size=None, fix_embeddings=True)),
     "MATCH_TENSOR": dict(arch=dict(_LSTM, featsize=40, nhid_query=30, nhid_doc=140, nchannels=50,

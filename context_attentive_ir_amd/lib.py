@@ -42,6 +42,18 @@ DuetWeights = type("nir_duet_weights", (C.Structure,), {"_fields_": list(DuetWei
     ("fw1", C.c_void_p), ("fw2", C.c_void_p), ("K1P", C.c_int), ("ftable", C.c_void_p), ("fw1c", C.c_void_p), ("EPT", C.c_int)]})
 DssmWeights = _struct("nir_dssm_weights", ["q_w1t", "q_b1", "q_w2t", "q_b2", "d_w1t", "d_b1", "d_w2t", "d_b2"], ["NH", "NO"])
 CdssmWeights = _struct("nir_cdssm_weights", ["q_w5t", "q_b", "q_semt", "q_semb", "d_w5t", "d_b", "d_semt", "d_semb"], ["NH", "NO"])
+CONV1D_SPLIT, CONV1D_FP32, ARCI_MAX_LAYERS = 0, 1, 8
+
+
+class Conv1dLayer(C.Structure):
+    _fields_ = [("planes", C.c_void_p), ("wt", c_fp), ("bias", c_fp)] + [(f, C.c_int) for f in ("C_in", "F", "k", "p", "path")]
+
+
+class ArciWeights(C.Structure):
+    _fields_ = [("q", Conv1dLayer * ARCI_MAX_LAYERS), ("d", Conv1dLayer * ARCI_MAX_LAYERS), ("head_wq", c_fp), ("head_wd", c_fp), ("head_b", c_fp),
+                ("n_layers", C.c_int), ("q_feats", C.c_int), ("d_feats", C.c_int)]
+
+
 CarsEncoderWeights = _struct(
     "nir_cars_encoder_weights",
     ["wih", "whh", "bih", "bhh", "attn0_w", "attn0_b", "attn3_w", "attn3_b"], ["H", "bounded"])
@@ -142,6 +154,12 @@ SIGNATURES = {
     "nir_dssm_score": (_i, [c_ip, c_ip, _i, _i, _i, _i, c_fp, _l, _i, _l, C.POINTER(DssmWeights), C.c_void_p, _z, c_fp, c_fp, c_fp, c_st]),
     "nir_cdssm_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
     "nir_cdssm_score": (_i, [c_ip, c_ip, _i, _i, _i, _i, c_fp, _l, _i, _l, C.POINTER(CdssmWeights), C.c_void_p, _z, c_fp, c_fp, c_fp, c_st]),
+    "nir_conv1d_planes_bytes": (_z, [_i, _i, _i]),
+    "nir_conv1d_pack": (_i, [c_fp, _i, _i, _i, C.c_void_p, c_fp, C.c_void_p, c_st]),
+    "nir_conv1d_pool_out_floats": (_z, [_l, _i, _i, _i, _i]),
+    "nir_conv1d_pool_f32": (_i, [c_ip, c_fp, _l, _i, C.POINTER(Conv1dLayer), _i, c_fp, c_fp, c_st]),
+    "nir_arci_workspace_bytes": (_z, [_i, _i, _i, _i, C.POINTER(ArciWeights)]),
+    "nir_arci_score": (_i, [c_ip, c_ip, _i, _i, _i, _i, c_fp, _l, _i, C.POINTER(ArciWeights), C.c_void_p, _z, c_fp, c_st]),
     "nir_maxpool_arg_f32": (_i, [c_fp, _l, _i, _i, c_fp, C.c_void_p, c_st]),
     "nir_maxpool_arg_bwd_f32": (_i, [c_fp, C.c_void_p, _l, _i, _i, c_fp, c_st]),
     "nir_cosine_bcast_f32": (_i, [c_fp, c_fp, _l, _i, _i, c_fp, c_st]),

@@ -4,5 +4,6 @@ from .drmm import DRMM
 from .duet import DUET
 from .dssm import DSSM
 from .cdssm import CDSSM
+from .arci import ARCI
 
-__all__ = ["ESM", "MatchTensor", "DRMM", "DUET", "DSSM", "CDSSM"]
+__all__ = ["ESM", "MatchTensor", "DRMM", "DUET", "DSSM", "CDSSM", "ARCI"]

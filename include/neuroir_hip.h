@@ -381,7 +381,56 @@ int nir_rank_loss_softmax_nll_bwd(const float* scores, const float* labels, cons
                                   nir_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
- * CARS ranking path  (neuroir/multitask/cars.py:193-540, 671-691; neuroir/modules/maxout.py:70-84)
+ * ARC-I  (neuroir/rankers/arci.py:26-58 construction, :60-105 forward; eval mode)
+ *   tower   per layer  y = MaxPool1d(p)(ReLU(Conv1d(C_in -> F, k, padding k/2)(x)))   (arci.py:28-44, 79-81, 97-99); the pool has stride p
+ *           and floor mode: the trailing L % p positions are dropped.  Lengths are not inputs: the convolutions run over the padded width,
+ *           a PAD id contributes the table's PAD row, the conv's own padding is zeros at the edges of every layer's input.
+ *   score   mlp([flatten(query features), flatten(document features)]) with flatten index f * feats + t (arci.py:83-104); mlp is two
+ *           Linear layers with nothing in between, so the caller folds it once per weight version into one vector w_eff and one scalar b_eff.
+ *
+ * nir_conv1d_pool_f32: ONE layer (arci.py:31-36) over M sequences of width L.
+ *   A operand: ids != NULL -> row (m, t) is x[ids[m L + t]] (x is the table [V, C_in]; ids must already be inside the table), else x is the
+ *   dense position-major activation [M, L, C_in].  Tap j of output position t reads row t + j - k/2, zeros outside [0, L).
+ *   Epilogue: + bias, act (NIR_ACT_NONE or NIR_ACT_RELU), max over p consecutive positions (floor).
+ *     head_w == NULL: out [M, L/p, F].
+ *     head_w != NULL: head_w is [F][L/p]; out [M L/p][ceil(F/128)][2] holds per pooled position the partial dot products
+ *                     sum_f pooled[f] head_w[f][t] (arci.py:103-104 folded); their sum is the sequence's share of the score.  No atomics.
+ *   layer->path NIR_CONV1D_SPLIT: two-term fp16 split on v_mfma_f32_16x16x32_f16 (every element of x and of the weight must be < 2^15 in
+ *   magnitude: the caller's promise, see nir_conv1d_pack); NIR_CONV1D_FP32: plain fp32 FMA, any finite values, slow.
+ *   Limits (NIR_ERR_BAD_ARG outside): 1 <= C_in <= 1024, 1 <= F <= 1024, k in {1, 3, 5, 7}, 1 <= p <= 64, L >= 1.
+ *   nir_conv1d_pool_out_floats: the size of out.
+ * nir_conv1d_pack: Conv1d weight [F][C_in][k] -> planes (nir_conv1d_planes_bytes; MFMA fragment order, two fp16 terms) and wt (fp32
+ *   [k C_in][F], row j C_in + c) ; ORs 2 into *flag when a weight is >= 2^15 in magnitude or not finite.
+ * nir_arci_score: the whole forward, n_layers + 1 launches (one per layer for both towers, one finish).  A layer runs the split path only
+ *   when both towers ask for it.  QL / DL need not be the widths of construction, but must pool to q_feats / d_feats (the reference fails
+ *   in mlp otherwise, arci.py:104): NIR_ERR_BAD_ARG, nothing enqueued.  Stateless, caller-owned buffers, never synchronises.
+ * ------------------------------------------------------------------------------------------------ */
+#define NIR_CONV1D_SPLIT 0
+#define NIR_CONV1D_FP32 1
+#define NIR_ARCI_MAX_LAYERS 8
+typedef struct {
+    const void* planes;          /* nir_conv1d_pack (NIR_CONV1D_SPLIT) */
+    const float* wt;             /* nir_conv1d_pack (NIR_CONV1D_FP32) */
+    const float* bias;           /* [F] */
+    int C_in, F, k, p, path;
+} nir_conv1d_layer;
+typedef struct {
+    nir_conv1d_layer q[NIR_ARCI_MAX_LAYERS], d[NIR_ARCI_MAX_LAYERS]; /* {query,doc}_conv1d_layers.{i}.0 */
+    const float *head_wq, *head_wd;  /* w_eff = mlp.1.weight mlp.0.weight split at F_last q_feats: [F_last][q_feats], [F_last][d_feats] */
+    const float* head_b;             /* b_eff = mlp.1.weight mlp.0.bias + mlp.1.bias, one float on the device */
+    int n_layers, q_feats, d_feats;
+} nir_arci_weights;
+size_t nir_conv1d_planes_bytes(int C_in, int F, int k);
+int nir_conv1d_pack(const float* w, int C_in, int F, int k, void* planes, float* wt, int* flag, nir_stream_t stream);
+size_t nir_conv1d_pool_out_floats(int64_t M, int L, int F, int p, int head);
+int nir_conv1d_pool_f32(const int64_t* ids, const float* x, int64_t M, int L, const nir_conv1d_layer* layer /*host*/, int act, const float* head_w,
+                        float* out, nir_stream_t stream);
+size_t nir_arci_workspace_bytes(int B, int N, int QL, int DL, const nir_arci_weights* w /*host*/);
+int nir_arci_score(const int64_t* q_ids, const int64_t* d_ids, int B, int N, int QL, int DL, const float* table, int64_t V, int E,
+                   const nir_arci_weights* w /*host*/, void* workspace, size_t workspace_bytes, float* scores, nir_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * CARS ranking path (neuroir/multitask/cars.py:193-540, 671-691; neuroir/modules/maxout.py:70-84)
  * ------------------------------------------------------------------------------------------------ */
 typedef struct {
     const float *wih, *whh, *bih, *bhh;  /* <enc>.encoder.rnns.0 fwd+rev concatenated [2*4H,E],[2,4H,H],[2*4H],[2*4H] */
