@@ -1,10 +1,10 @@
 """Flag / hyper-parameter surface of the hot-path models.
 
-Mirror of the reference's config API for the five hot-path models:
+Mirror of the reference's config API for the hot-path models:
   * add_model_args / get_model_args / update_model_args / override_model_args keep the call
     shapes of /root/reference/neuroir/config.py:33,98,115,123;
   * the per-model fixed hyper-parameters keep the values of /root/reference/neuroir/hyparam.py
-    (ESM :3-8, DSSM :10-20, CDSSM :22-32, DUET :34-46, ARCI :48-59, DRMM :78-86, MATCH_TENSOR :88-105, CARS :197-225).
+    (ESM :3-8, DSSM :10-20, CDSSM :22-32, DUET :34-46, ARCI :48-59, ARCII :61-76, DRMM :78-86, MATCH_TENSOR :88-105, CARS :197-225).
 Everything is table-driven here; models outside the hot path are not listed (they keep
 running on the reference's own stock-PyTorch classes).
 """
@@ -23,6 +23,9 @@ MODEL_ARCHITECTURE = {
                  data=dict(src_vocab_size=None, force_pad=True, fix_embeddings=True)),
     "ARCI": dict(arch=dict(filters_1d=[256, 128], kernel_size_1d=[3, 3], maxpool_size_1d=[2, 2]),
                  data=dict(src_vocab_size=None, force_pad=True, fix_embeddings=True)),
+    "ARCII": dict(arch=dict(filters_1d=128, kernel_size_1d=3, filters_2d=[256, 128], kernel_size_2d=[[3, 3], [3, 3]],
+                            maxpool_size_2d=[[2, 2], [2, 2]]),
+                  data=dict(src_vocab_size=None, force_pad=True, fix_embeddings=True, max_doc_len=100, max_query_len=10)),
     "DRMM": dict(arch=dict(nbins=5), data=dict(src_vocab_size=None, fix_embeddings=True)),
     "MATCH_TENSOR": dict(arch=dict(_LSTM, featsize=40, nhid_query=30, nhid_doc=140, nchannels=50,
                                    nfilters=6, match_filter_size=20),

@@ -16,33 +16,11 @@
 //                              are not known to be below 2^15 (the pack-time bound, rankers/arci.py).  Slow, exact-fp32 class.
 //   arci_finish_kernel         one wave per (query, candidate): the partials of the query and of the document in a fixed order, + b_eff.
 // No float atomics anywhere: two calls give the same bits.
-#include "split2.hpp"
+// The tile constants, the staging helpers and the declarations ARC-II's first stage uses (arcii.hip) are in conv_pool.hpp.
+#include "conv_pool.hpp"
 #include <algorithm>
 
 namespace nir {
-
-constexpr int CV_ROWS = 64;        // conv positions per workgroup (4 MFMA row tiles)
-constexpr int CV_COLS = 128;       // filters per workgroup: 4 waves x 2 column tiles of 16
-constexpr int CV_CT = 2, CV_RT = 4;
-constexpr int CV_EP_LD = CV_COLS + 4;
-constexpr int CV_MAX_C = 1024, CV_MAX_F = 1024, CV_MAX_K = 7, CV_MAX_P = CV_ROWS;
-
-struct ConvSide {
-    const int64_t* ids;       // [M, L] token ids (x is then the table [V, C]) or NULL (x is the dense [M, L, C] activation)
-    const float* x;
-    const uint4* planes;      // conv1d_pack_kernel's fragments
-    const float* wt;          // fp32 [k C][F]
-    const float* bias;
-    const float* head_w;      // NULL: out is [M, L / p, F]; else w_eff [F][L / p] and out is the partial list [M L/p][NCB][2]
-    float* out;
-    int64_t M;
-    int L;
-};
-struct ConvArgs {
-    ConvSide s[2];
-    int64_t nblk0;            // blocks [0, nblk0) belong to s[0], the rest to s[1]
-    int C, F, k, p, act;
-};
 
 // Weight [F][C][k] (Conv1d layout) -> (a) split2 fragments: step ks covers K indices kk = 32 ks .. + 31 of the tap-major order
 // kk = j * roundup(C, 32) + c; fragment (ks, nt, term) is 64 lanes x 8 halfs, lane l holding filter 16 nt + (l & 15), kk = 32 ks + 8 (l >> 4) + e
@@ -77,32 +55,6 @@ __global__ __launch_bounds__(256) void conv1d_pack_kernel(const float* w, int C,
         wt[((int64_t)j * C + c) * F + f] = w[i];
     }
     if (bad) atomicOr(flag, 2);
-}
-
-__device__ __forceinline__ void cv_load8(const float* src, int c, int C, bool vec4, float (&v)[8]) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = 0.f;
-    if (!src) return;
-    if (vec4) {                                  // C % 4 == 0: rows are 16-byte aligned and a float4 is inside the row or outside it
-        if (c + 4 <= C) {
-            const float4 q = *reinterpret_cast<const float4*>(src + c);
-            v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-        }
-        if (c + 8 <= C) {
-            const float4 q = *reinterpret_cast<const float4*>(src + c + 4);
-            v[4] = q.x, v[5] = q.y, v[6] = q.z, v[7] = q.w;
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-            if (c + e < C) v[e] = src[c + e];
-    }
-}
-
-// LDS slot (16 bytes = 8 halfs) of (buffer, term, row, 8-channel chunk).  The chunk is rotated by the row's group of four so that the
-// ds_read_b128 of an A fragment (lane l: row l & 15, chunk l >> 4) meets 16 different bank quads in each of its lane groups.
-__device__ __forceinline__ int cv_slot(int buf, int term, int row, int chunk) {
-    return ((buf * 2 + term) * CV_ROWS + row) * 4 + (chunk ^ ((0 - (row >> 2)) & 3));
 }
 
 __global__ __launch_bounds__(256) void conv1d_pool_split_kernel(ConvArgs a) {
@@ -302,7 +254,7 @@ __global__ __launch_bounds__(256) void arci_finish_kernel(const float* qpart, in
     if (lane == 0) scores[pair] = tot + head_b[0];
 }
 
-static int conv_check(const nir_conv1d_layer* ly, const char* who) {
+int conv_check(const nir_conv1d_layer* ly, const char* who) {
     NIR_REQUIRE(ly, "%s: null layer", who);
     NIR_REQUIRE(ly->C_in >= 1 && ly->C_in <= CV_MAX_C, "%s: C_in %d unsupported (1 <= C_in <= %d)", who, ly->C_in, CV_MAX_C);
     NIR_REQUIRE(ly->F >= 1 && ly->F <= CV_MAX_F, "%s: F %d unsupported (1 <= F <= %d)", who, ly->F, CV_MAX_F);
@@ -313,10 +265,8 @@ static int conv_check(const nir_conv1d_layer* ly, const char* who) {
     return 0;
 }
 
-static size_t conv_ncb(int F) { return (size_t)((F + CV_COLS - 1) / CV_COLS); }
-
 // both sides share (C, F, k, p); a side with M == 0 contributes no block
-static int conv_launch(ConvSide s0, ConvSide s1, int C, int F, int k, int p, int act, int path, hipStream_t st, const char* who) {
+int conv_launch(ConvSide s0, ConvSide s1, int C, int F, int k, int p, int act, int path, hipStream_t st, const char* who) {
     ConvArgs a;
     a.s[0] = s0, a.s[1] = s1;
     a.C = C, a.F = F, a.k = k, a.p = p, a.act = act;
@@ -339,8 +289,15 @@ static int conv_launch(ConvSide s0, ConvSide s1, int C, int F, int k, int p, int
     return 0;
 }
 
-static ConvSide conv_side(const int64_t* ids, const float* x, const nir_conv1d_layer* ly, const float* head_w, float* out, int64_t M, int L) {
+ConvSide conv_side(const int64_t* ids, const float* x, const nir_conv1d_layer* ly, const float* head_w, float* out, int64_t M, int L) {
     return ConvSide{ids, x, (const uint4*)ly->planes, ly->wt, ly->bias, head_w, out, M, L};
+}
+
+int conv_pack_launch(const float* w, int C, int F, int taps, void* planes, float* wt, int* flag, hipStream_t st, const char* who) {
+    const int64_t n = (int64_t)taps * ((C + 31) / 32) * ((F + 15) / 16) * 64;
+    hipLaunchKernelGGL(conv1d_pack_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, st, w, C, F, taps, (uint4*)planes, wt, flag);
+    NIR_CHECK_LAUNCH(who);
+    return 0;
 }
 
 }  // namespace nir
@@ -355,11 +312,7 @@ extern "C" int nir_conv1d_pack(const float* w, int C_in, int F, int k, void* pla
     NIR_REQUIRE(w && planes && wt && flag, "conv1d_pack: null pointer");
     NIR_REQUIRE(C_in >= 1 && C_in <= CV_MAX_C && F >= 1 && F <= CV_MAX_F && k >= 1 && k <= CV_MAX_K && (k & 1),
                 "conv1d_pack: C_in %d / F %d / k %d unsupported (C_in <= %d, F <= %d, k odd <= %d)", C_in, F, k, CV_MAX_C, CV_MAX_F, CV_MAX_K);
-    const int64_t n = (int64_t)k * ((C_in + 31) / 32) * ((F + 15) / 16) * 64;
-    hipLaunchKernelGGL(conv1d_pack_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, C_in, F, k,
-                       (uint4*)planes, wt, flag);
-    NIR_CHECK_LAUNCH("nir_conv1d_pack");
-    return 0;
+    return conv_pack_launch(w, C_in, F, k, planes, wt, flag, (hipStream_t)stream, "nir_conv1d_pack");
 }
 
 extern "C" size_t nir_conv1d_pool_out_floats(int64_t M, int L, int F, int p, int head) {

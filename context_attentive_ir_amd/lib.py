@@ -54,6 +54,18 @@ class ArciWeights(C.Structure):
                 ("n_layers", C.c_int), ("q_feats", C.c_int), ("d_feats", C.c_int)]
 
 
+ARCII_MAX_LAYERS = 8
+
+
+class Conv2dLayer(C.Structure):
+    _fields_ = [("planes", C.c_void_p), ("wt", c_fp), ("bias", c_fp)] + [(f, C.c_int) for f in ("C_in", "F", "kh", "kw", "ph", "pw", "path")]
+
+
+class ArciiWeights(C.Structure):
+    _fields_ = [("q", Conv1dLayer), ("d", Conv1dLayer), ("l", Conv2dLayer * ARCII_MAX_LAYERS), ("head_w", c_fp), ("head_b", c_fp),
+                ("n_layers", C.c_int), ("feats", C.c_int)]
+
+
 CarsEncoderWeights = _struct(
     "nir_cars_encoder_weights",
     ["wih", "whh", "bih", "bhh", "attn0_w", "attn0_b", "attn3_w", "attn3_b"], ["H", "bounded"])
@@ -160,6 +172,12 @@ SIGNATURES = {
     "nir_conv1d_pool_f32": (_i, [c_ip, c_fp, _l, _i, C.POINTER(Conv1dLayer), _i, c_fp, c_fp, c_st]),
     "nir_arci_workspace_bytes": (_z, [_i, _i, _i, _i, C.POINTER(ArciWeights)]),
     "nir_arci_score": (_i, [c_ip, c_ip, _i, _i, _i, _i, c_fp, _l, _i, C.POINTER(ArciWeights), C.c_void_p, _z, c_fp, c_st]),
+    "nir_conv2d_planes_bytes": (_z, [_i, _i, _i, _i]),
+    "nir_conv2d_pack": (_i, [c_fp, _i, _i, _i, _i, C.c_void_p, c_fp, C.c_void_p, c_st]),
+    "nir_conv2d_pool_out_floats": (_z, [_l, _i, _i, _i, _i, _i, _i]),
+    "nir_conv2d_pool_f32": (_i, [c_fp, c_fp, c_fp, _l, _i, _i, _i, C.POINTER(Conv2dLayer), _i, c_fp, c_fp, c_st]),
+    "nir_arcii_workspace_bytes": (_z, [_i, _i, _i, _i, C.POINTER(ArciiWeights)]),
+    "nir_arcii_score": (_i, [c_ip, c_ip, _i, _i, _i, _i, c_fp, _l, _i, C.POINTER(ArciiWeights), C.c_void_p, _z, c_fp, c_st]),
     "nir_maxpool_arg_f32": (_i, [c_fp, _l, _i, _i, c_fp, C.c_void_p, c_st]),
     "nir_maxpool_arg_bwd_f32": (_i, [c_fp, C.c_void_p, _l, _i, _i, c_fp, c_st]),
     "nir_cosine_bcast_f32": (_i, [c_fp, c_fp, _l, _i, _i, c_fp, c_st]),

@@ -5,5 +5,6 @@ from .duet import DUET
 from .dssm import DSSM
 from .cdssm import CDSSM
 from .arci import ARCI
+from .arcii import ARCII
 
-__all__ = ["ESM", "MatchTensor", "DRMM", "DUET", "DSSM", "CDSSM", "ARCI"]
+__all__ = ["ESM", "MatchTensor", "DRMM", "DUET", "DSSM", "CDSSM", "ARCI", "ARCII"]

@@ -9,11 +9,12 @@ shard the CANDIDATE axis over the ranks of a torch.distributed group and all-gat
 import torch
 
 from .. import lib, sharding
-from ..rankers import ARCI, CDSSM, DRMM, DSSM, DUET, ESM, MatchTensor
+from ..rankers import ARCI, ARCII, CDSSM, DRMM, DSSM, DUET, ESM, MatchTensor
 from .common import WrapperBase
 
-NETWORKS = {"ESM": ESM, "DUET": DUET, "DRMM": DRMM, "MATCH_TENSOR": MatchTensor, "DSSM": DSSM, "CDSSM": CDSSM, "ARCI": ARCI}
-BCE_MODELS = {"DUET", "DRMM", "MATCH_TENSOR", "ARCI"}      # BCEWithLogitsLoss (models/ranker.py:54-56)
+NETWORKS = {"ESM": ESM, "DUET": DUET, "DRMM": DRMM, "MATCH_TENSOR": MatchTensor, "DSSM": DSSM, "CDSSM": CDSSM, "ARCI": ARCI,
+            "ARCII": ARCII}
+BCE_MODELS = {"DUET", "DRMM", "MATCH_TENSOR", "ARCI", "ARCII"}      # BCEWithLogitsLoss (models/ranker.py:54-58)
 NLL_MODELS = {"DSSM", "CDSSM"}        # Ranker.compute_loss: list-wise softmax NLL (models/ranker.py:43-48, 79-89)
 
 

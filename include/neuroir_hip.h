@@ -430,6 +430,57 @@ int nir_arci_score(const int64_t* q_ids, const int64_t* d_ids, int B, int N, int
                    const nir_arci_weights* w /*host*/, void* workspace, size_t workspace_bytes, float* scores, nir_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * ARC-II  (neuroir/rankers/arcii.py:11-56 construction, :58-111 forward; eval mode)
+ *   Eq = conv_query(embed(q)) [B, F1, QL], Ed = conv_doc(embed(d)) [B N, F1, DL] (Conv1d(k, padding k/2), NO activation), the grid
+ *   X[m, f, i, j] = Ed[m, f, i] + Eq[m / N, f, j] (document axis first) through MaxPool2d(2, 2), then per layer
+ *   Conv2d(kh x kw, padding (kh/2, kw/2)) -> ReLU -> MaxPool2d(ph x pw) (index 0 along the document axis, stride = pool size, floor),
+ *   flatten(1) (feature f Hd Hq + i Hq + j) and mlp, two Linear layers with nothing in between, folded by the caller into w_eff / b_eff.
+ *   The first pool is separable bit for bit, max_pool2d(Ed + Eq, 2 x 2) == max_pool1d(Ed, 2) + max_pool1d(Eq, 2), so the 1-D stage is
+ *   nir_conv1d_pool_f32's kernel (act none, p 2) and the grid is never formed.
+ *
+ * nir_conv2d_pool_f32: ONE 2-D layer over M grids of H x W positions.
+ *   Input: x != NULL -> the dense position-major [M, H, W, C_in] (pd, pq NULL, N 1); else the OUTER SUM of pd [M, H, C_in] and
+ *   pq [M / N, W, C_in]: position (m, i, j) is pd[m, i] + pq[m / N, j], added in fp32.  Tap (a, b) of output (i, j) reads position
+ *   (i + a - kh/2, j + b - kw/2); outside the grid it reads ZERO in both modes (never a one-sided sum).
+ *   Epilogue: + bias, act (NIR_ACT_NONE or NIR_ACT_RELU), max over ph x pw windows (floor).
+ *     head_w == NULL: out [M, H/ph, W/pw, F].
+ *     head_w != NULL: head_w is [F][H/ph][W/pw]; out [M H/ph W/pw][ceil(F/128)][2] holds per pooled position the partial dot products
+ *                     sum_f pooled[f] head_w[f][i][j]; their sum is the grid's score without b_eff.  No atomics.
+ *   layer->path NIR_CONV1D_SPLIT / NIR_CONV1D_FP32 as for nir_conv1d_pool_f32 (split: every input -- in the outer-sum mode every SUM --
+ *   and every weight below 2^15 in magnitude, the caller's promise).
+ *   Limits (NIR_ERR_BAD_ARG outside): 1 <= C_in, F <= 1024, kh, kw in {1, 3, 5, 7}, 1 <= ph pw <= 64, H, W >= 1.
+ *   nir_conv2d_pool_out_floats: the size of out.
+ * nir_conv2d_pack: Conv2d weight [F][C_in][kh][kw] -> planes (nir_conv2d_planes_bytes; the format of nir_conv1d_pack with kh kw taps in
+ *   row-major tap order) and wt (fp32 [kh kw C_in][F]); ORs 2 into *flag when a weight is >= 2^15 in magnitude or not finite.
+ * nir_arcii_score: the whole forward, 2 + n_layers launches (the 1-D stage of both towers, one per 2-D layer, the finish).  QL / DL
+ *   need not be the widths of construction, but F_last Hd Hq of the final grid must equal feats (the reference fails in mlp otherwise,
+ *   arcii.py:110) and no side may pool to 0: NIR_ERR_BAD_ARG, nothing enqueued.  The head is indexed with the RUNTIME Hd, Hq.
+ *   Stateless, caller-owned buffers, never synchronises.
+ * ------------------------------------------------------------------------------------------------ */
+#define NIR_ARCII_MAX_LAYERS 8
+typedef struct {
+    const void* planes;          /* nir_conv2d_pack (NIR_CONV1D_SPLIT) */
+    const float* wt;             /* nir_conv2d_pack (NIR_CONV1D_FP32) */
+    const float* bias;           /* [F] */
+    int C_in, F, kh, kw, ph, pw, path;
+} nir_conv2d_layer;
+typedef struct {
+    nir_conv1d_layer q, d;                  /* conv_query, conv_doc; p must be 2 */
+    nir_conv2d_layer l[NIR_ARCII_MAX_LAYERS]; /* conv2d_layers.{i}.0 */
+    const float* head_w;                    /* w_eff = mlp.1.weight mlp.0.weight, [feats] */
+    const float* head_b;                    /* b_eff = mlp.1.weight mlp.0.bias + mlp.1.bias, one float on the device */
+    int n_layers, feats;
+} nir_arcii_weights;
+size_t nir_conv2d_planes_bytes(int C_in, int F, int kh, int kw);
+int nir_conv2d_pack(const float* w, int C_in, int F, int kh, int kw, void* planes, float* wt, int* flag, nir_stream_t stream);
+size_t nir_conv2d_pool_out_floats(int64_t M, int H, int W, int F, int ph, int pw, int head);
+int nir_conv2d_pool_f32(const float* x, const float* pd, const float* pq, int64_t M, int N, int H, int W, const nir_conv2d_layer* layer /*host*/,
+                        int act, const float* head_w, float* out, nir_stream_t stream);
+size_t nir_arcii_workspace_bytes(int B, int N, int QL, int DL, const nir_arcii_weights* w /*host*/);
+int nir_arcii_score(const int64_t* q_ids, const int64_t* d_ids, int B, int N, int QL, int DL, const float* table, int64_t V, int E,
+                    const nir_arcii_weights* w /*host*/, void* workspace, size_t workspace_bytes, float* scores, nir_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * CARS ranking path (neuroir/multitask/cars.py:193-540, 671-691; neuroir/modules/maxout.py:70-84)
  * ------------------------------------------------------------------------------------------------ */
 typedef struct {
