@@ -15,7 +15,7 @@
 // Everything is enqueued on the caller's stream; no host synchronisation.
 #include <algorithm>
 #include <mutex>
-#include "split2.hpp"
+#include "decode_common.hpp"
 
 namespace nir {
 
@@ -391,6 +391,38 @@ static DecPlan dec_plan(void* ws, size_t cap, int64_t rows_src, int64_t Bd, int 
     p.bytes = align_up(a.off, 256);
     return p;
 }
+
+// host-side launchers of the kernels above for the other greedy decoders (decode_common.hpp)
+int launch_fill_i64(int64_t* p, int64_t v, int64_t n, hipStream_t st) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(fill_i64_kernel, g1(n), dim3(256), 0, st, p, v, n);
+    NIR_CHECK_LAUNCH("fill_i64_kernel");
+    return 0;
+}
+int launch_h16_pack(const float* h, int64_t n, _Float16* out, hipStream_t st) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(h16_pack_kernel, g1(n), dim3(256), 0, st, h, n, out);
+    NIR_CHECK_LAUNCH("h16_pack_kernel");
+    return 0;
+}
+int launch_argmax_map(const float* logits, int64_t V, const int64_t* lut, int64_t* pred, int64_t pstride, int64_t* tgt, int64_t Vsrc, int64_t Bd,
+                      hipStream_t st) {
+    if (Bd <= 0) return 0;
+    {
+        ProfScope ps("argmax_map_kernel", st);
+        hipLaunchKernelGGL(argmax_map_kernel, dim3((unsigned)Bd), dim3(256), 0, st, logits, V, lut, pred, pstride, tgt, Vsrc);
+    }
+    NIR_CHECK_LAUNCH("argmax_map_kernel");
+    return 0;
+}
+int launch_argmax_finish(const float* pval, const int* pidx, int nparts, int64_t Bd, const int64_t* lut, int64_t* pred, int64_t pstride, int64_t* tgt,
+                         int64_t Vsrc, hipStream_t st) {
+    if (Bd <= 0) return 0;
+    hipLaunchKernelGGL(argmax_finish_kernel, dim3((unsigned)Bd), dim3(64), 0, st, pval, pidx, nparts, Bd, lut, pred, pstride, tgt, Vsrc);
+    NIR_CHECK_LAUNCH("argmax_finish_kernel");
+    return 0;
+}
+int device_cu_count() { return cu_count(); }
 
 }  // namespace nir
 

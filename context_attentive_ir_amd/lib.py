@@ -87,6 +87,16 @@ class CarsDecoderWeights(C.Structure):
                                                                                                            ("rnn_whh_frag", C.c_void_p), ("attn_q_w", C.c_void_p)]
 
 
+S2S_ATTN = {"general": 0, "dot": 1, "mlp": 2}
+
+
+class Seq2seqDecoderWeights(C.Structure):
+    _fields_ = [(f, c_fp) for f in ("rnn_wih", "rnn_whh", "rnn_bih", "rnn_bhh", "attn_in_wt", "attn_ctx_w", "attn_query_w", "attn_query_b", "attn_v",
+                                    "attn_out_w", "attn_out_b", "gen_w", "gen_b")] + [("H", C.c_int), ("attn_type", C.c_int), ("VT", C.c_int64),
+                                                                                     ("rnn_gate_fold", C.c_void_p), ("rnn_whh_frag", C.c_void_p),
+                                                                                     ("gen_frag", C.c_void_p)]
+
+
 CarsSessionOutputs = _struct("nir_cars_session_outputs", ["inner_q", "inner_d", "dec_h", "dec_c"])
 
 MnsrfWeights = _struct(
@@ -251,6 +261,14 @@ SIGNATURES = {
     "nir_cars_click_max": (_i, [c_fp, _i, _i, _i, C.c_void_p, c_st]),
     "nir_lstm_step_whh_frag_bytes": (_z, [_i]),
     "nir_lstm_step_pack_whh_frag": (_i, [c_fp, _i, C.c_void_p, C.c_void_p, c_st]),
+    "nir_seq2seq_gen_frag_bytes": (_z, [_l, _i]),
+    "nir_seq2seq_pack_gen_frag": (_i, [c_fp, _l, _i, C.c_void_p, C.c_void_p, c_st]),
+    "nir_seq2seq_gen_argmax_workspace_bytes": (_z, [_l, _i, _l, _i]),
+    "nir_seq2seq_gen_argmax": (_i, [c_fp, _l, _i, c_fp, c_fp, C.c_void_p, _l, c_ip, _l, C.c_void_p, _z, c_ip, _l, c_ip, c_st]),
+    "nir_seq2seq_attend": (_i, [c_fp, c_fp, c_fp, c_fp, c_fp, c_ip, _l, _i, _i, _i, c_fp, c_fp, _l, c_st]),
+    "nir_seq2seq_decode_workspace_bytes": (_z, [_l, _i, C.POINTER(Seq2seqDecoderWeights)]),
+    "nir_seq2seq_decode_greedy": (_i, [c_fp, c_fp, c_fp, c_ip, _l, _i, c_fp, _l, _i, c_ip, _l, _i, C.POINTER(Seq2seqDecoderWeights), C.c_void_p, _z,
+                                       c_ip, c_fp, c_st]),
 }
 
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_SPLIT2 = 0, 1, 2

@@ -1,0 +1,4 @@
+"""Recommender models on the HIP path (mirror of /root/reference/neuroir/recommender): Seq2seq."""
+from .seq2seq import Seq2seq
+
+__all__ = ["Seq2seq"]

@@ -1,0 +1,225 @@
+"""Seq2seq -- the attention encoder-decoder of the recommender driver (drop-in for neuroir.recommender.seq2seq.Seq2seq,
+/root/reference/neuroir/recommender/seq2seq.py:13-195; ACG is the same network with a copy generator on top).
+
+decode():  RNNEncoder over the source query -> the decoder's initial state (the encoder's final state of source row order[b], see below)
+           -> ONE C-ABI call for the whole greedy decode (nir_seq2seq_decode_greedy, csrc/seq2seq.hip): LSTM step, Luong attention
+           ('general' / 'dot' / 'mlp'), linear_out, generator + arg-max, the token fed back through a device lookup table.
+forward(): the teacher-forced loss on the differentiable HIP operators of autograd.py.
+
+Kept quirks of the reference:
+  * RNNEncoder returns its final state in LENGTH-SORTED order (encoders/rnn_encoder.py:72-74,104-121; only the memory bank is un-sorted), so
+    decoder row b starts from the final state of source row order[b], order = torch.sort(lengths, 0, True)[1].  The encoder of this package
+    returns original order; the pairing is applied here with the same torch.sort call on the same device tensor.  (Equal lengths: the
+    pairing is that call's choice.)
+  * there is no input feed: the decoder LSTM reads the previous token's embedding and its own state, attention follows it.
+  * tanh follows linear_out for 'general' and 'dot' only; 'mlp' has a bias there and no tanh (modules/global_attention.py:74-75,193-195).
+  * nlayers != 1 (hyparam.SEQ2SEQ has 2) constructs, and fails in forward / decode like the reference: the encoder (use_last) hands over one
+    layer's state, the decoder LSTM expects nlayers of them.
+"""
+import torch
+import torch.nn as nn
+
+from .. import autograd as A
+from .. import lib
+from ..constants import BOS, PAD
+from ..multitask import suggest
+from .layers import ATTN_TYPES, Decoder, Embedder, Encoder
+
+
+class Seq2seq(nn.Module, lib.IdCheck):
+    def __init__(self, args):
+        super().__init__()
+        if args.rnn_type != "LSTM":
+            raise NotImplementedError("HIP Seq2seq implements rnn_type 'LSTM' (got %r); GRU decoders are a follow-up of their own" % (args.rnn_type,))
+        if getattr(args, "copy_attn", False):
+            raise NotImplementedError("HIP Seq2seq has no copy generator yet (copy_attn=True is ACG: src_map / collapse_copy_scores are the "
+                                      "ACG follow-up)")
+        if args.attn_type not in ATTN_TYPES:
+            raise NotImplementedError("HIP Seq2seq implements attn_type %s (got %r)" % (", ".join(ATTN_TYPES), args.attn_type))
+        self.embedder = Embedder(args.emsize, args.src_vocab_size, args.dropout_emb)
+        self.encoder = Encoder(args.rnn_type, args.emsize, args.bidirection, args.nlayers, args.nhid, args.dropout_rnn)
+        self.decoder = Decoder(args.emsize, args.nlayers, args.nhid, args.attn_type, args.dropout_rnn)
+        self.dropout = nn.Dropout(args.dropout)
+        self.generator = nn.Linear(args.nhid, args.tgt_vocab_size)
+        self.copy_attn = False
+        self.attn_type, self.nlayers, self.nhid = args.attn_type, int(args.nlayers), int(args.nhid)
+        self.bidirection = bool(args.bidirection)
+        self.dec_dropout_p = float(args.dropout_rnn)        # RNNDecoder.dropout (decoders/decoder.py:87)
+        self.fold_decoder_step = True            # decode: per-token gate rows folded into a [V, 4H] table + fp16-term recurrent product
+        self.fuse_generator_argmax = True        # decode: generator + bias + arg-max in one kernel (no [B, VT] logits)
+        self.fold_budget_bytes = 64 << 30
+        self._pdec = lib.PackCache(retain=1)
+
+    # ---- shared checks -----------------------------------------------------------------------------------------------------------
+    def _check_layers(self, B):
+        if self.nlayers != 1:
+            raise RuntimeError("Expected hidden[0] size (%d, %d, %d), got [1, %d, %d]" % (self.nlayers, B, self.nhid, B, self.nhid))
+
+    def _decoder_weights(self):
+        rnn, att = self.decoder.decoder.rnn, self.decoder.decoder.attn
+        table = self.embedder.word_embeddings.table
+
+        def build():
+            L = lib.load()
+            t = dict(rnn_wih=rnn.weight_ih_l0, rnn_whh=rnn.weight_hh_l0, rnn_bih=rnn.bias_ih_l0, rnn_bhh=rnn.bias_hh_l0,
+                     attn_out_w=att.linear_out.weight, gen_w=self.generator.weight, gen_b=self.generator.bias)
+            if self.attn_type == "general":
+                t["attn_in_wt"] = att.linear_in.weight.t()
+            elif self.attn_type == "mlp":
+                t.update(attn_ctx_w=att.linear_context.weight, attn_query_w=att.linear_query.weight, attn_query_b=att.linear_query.bias,
+                         attn_v=att.v.weight, attn_out_b=att.linear_out.bias)
+            H, VT = int(rnn.hidden_size), int(self.generator.weight.shape[0])
+            pk = lib.Packed(lib.Seq2seqDecoderWeights, t, dict(H=H, attn_type=lib.S2S_ATTN[self.attn_type], VT=VT))
+            dev = pk.keep["gen_w"].device
+            if dev.type != "cuda":
+                return pk
+
+            def in_range(fn):
+                """a packed fragment, or None when a weight lies outside the fp16 range of the split (one blocking flag read per weight version)"""
+                flag = torch.zeros(1, dtype=torch.int32, device=dev)
+                frag = fn(flag)
+                return frag if int(flag.item()) == 0 else None
+
+            nb = L.nir_seq2seq_gen_frag_bytes(VT, H)
+            if self.fuse_generator_argmax and nb:
+                def gen(flag):
+                    frag = torch.empty(nb, dtype=torch.uint8, device=dev)
+                    lib.check(L.nir_seq2seq_pack_gen_frag(lib.ptr(pk.keep["gen_w"]), VT, H, lib.ptr(frag), lib.ptr(flag), lib.stream()),
+                              "nir_seq2seq_pack_gen_frag")
+                    return frag
+                frag = in_range(gen)
+                if frag is not None:
+                    pk.keep["gen_frag"] = frag
+                    pk.struct.gen_frag = frag.data_ptr()
+            nb = L.nir_lstm_step_whh_frag_bytes(H)
+            if (self.fold_decoder_step and nb and table.is_cuda and table.shape[1] == rnn.input_size
+                    and table.shape[0] * 4 * H * 4 <= self.fold_budget_bytes):
+                def whh(flag):
+                    frag = torch.empty(nb, dtype=torch.uint8, device=dev)
+                    lib.check(L.nir_lstm_step_pack_whh_frag(lib.ptr(pk.keep["rnn_whh"]), H, lib.ptr(frag), lib.ptr(flag), lib.stream()),
+                              "nir_lstm_step_pack_whh_frag")
+                    return frag
+                frag = in_range(whh)
+                if frag is not None:
+                    pk.keep["rnn_whh_frag"] = frag
+                    pk.keep["rnn_gate_fold"] = lib.fold_lstm_table(table, pk.keep["rnn_wih"], pk.keep["rnn_bih"], pk.keep["rnn_bhh"], H, 1, "f32")
+                    pk.struct.rnn_whh_frag = frag.data_ptr()
+                    pk.struct.rnn_gate_fold = pk.keep["rnn_gate_fold"].data_ptr()
+            return pk
+        params = list(self.decoder.parameters()) + list(self.generator.parameters())
+        return self._pdec.get(params + [table, self.fold_decoder_step, self.fuse_generator_argmax, self.fold_budget_bytes], build)
+
+    # ---- eval: greedy decode -----------------------------------------------------------------------------------------------------
+    def initial_state(self, final, source_len):
+        """decoders/decoder.py:160-177 on the encoder's final (h_n, c_n) [ND, B, nhid / ND] (ORIGINAL row order) -> (h, c) [B, nhid]: row b is
+        the state of source row order[b] (the reference's length-sorted order), forward and reverse halves along the feature axis."""
+        order = torch.sort(source_len, 0, True)[1]
+        return tuple(torch.cat([s[d][order] for d in range(s.shape[0])], 1).contiguous() for s in final)
+
+    @torch.no_grad()
+    def decode(self, source_rep, source_len, max_len, src_dict, tgt_dict, src_map=None, alignment=None, blank=None, fill=None,
+               source_vocabs=None, tgt2src=None):
+        """seq2seq.py:118-195 (greedy) -> {'predictions': LongTensor [B, max_len] (target-vocabulary ids), 'attentions': [B, max_len, QL]}.
+        The reference maps each predicted token back to a source id on the host (tgt_dict[idx] -> word -> src_dict[word]); here that is one
+        device lookup table (identity without dictionaries).  attentions has the padded width QL of `source_rep` (the reference's has
+        max(source_len)); masked positions are exactly 0."""
+        if self.training:
+            raise NotImplementedError("HIP Seq2seq.decode runs in eval mode")
+        B, QL = source_rep.shape
+        self._check_layers(B)                                                # (before any launch, like the reference's failure)
+        table = self.embedder.word_embeddings.table
+        lib.require_device(source_rep, source_len, table)
+        L = lib.load()
+        src, _ = self._clean_ids(source_rep, None, table.shape[0])
+        lens = lib.ids64(source_len)
+        final, bank = self.encoder.encoder(A.embed(src, table), lens)
+        dec_h, dec_c = self.initial_state(final, lens)
+        bank = bank.float().contiguous()
+        dev = bank.device
+        w = self._decoder_weights()
+        if tgt2src is None:
+            tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, int(w.struct.VT), dev)
+        t = table.detach().float().contiguous()
+        max_len = int(max_len)
+        preds = torch.empty(B, max_len, dtype=torch.int64, device=dev)
+        attns = torch.empty(B, max_len, QL, dtype=torch.float32, device=dev)
+        if B > 0 and max_len > 0:
+            ws = lib.workspace(L.nir_seq2seq_decode_workspace_bytes(B, QL, w.ref()), dev)
+            lib.check(L.nir_seq2seq_decode_greedy(lib.ptr(dec_h), lib.ptr(dec_c), lib.ptr(bank), lib.ptr(lens), B, QL, lib.ptr(t), t.shape[0], t.shape[1],
+                                                  lib.ptr(tgt2src), BOS, max_len, w.ref(), lib.ptr(ws), ws.numel(), lib.ptr(preds), lib.ptr(attns),
+                                                  lib.stream()), "nir_seq2seq_decode_greedy")
+        return {"predictions": preds, "attentions": attns}
+
+    # ---- train: teacher-forced loss ---------------------------------------------------------------------------------------------------
+    def _encode_train(self, x, lens):
+        """x [B,T,E] -> (memory bank [B,T,nhid], h_n [B,nhid], c_n [B,nhid]) in ORIGINAL row order, differentiable: the register-resident
+        training recurrence up to 128 units per direction (it returns the cell states), one lstm_seq pass per direction beyond."""
+        rnn = self.encoder.encoder.rnns[0]
+        nd, params = A._lstm_params(rnn)
+        H = rnn.hidden_size
+        B, T, _ = x.shape
+        dev = x.device
+        rows = torch.arange(B, device=dev)
+        last = (lens - 1).clamp(min=0)
+        if H <= 128:
+            out, cst = A._BiLSTM.apply(x, lens, nd, None, None, *params)
+            hs, cs = [out[rows, last, :H]], [cst[rows, last, 0]]
+            if nd == 2:                                                      # the reverse direction ends at position 0
+                hs.append(out[:, 0, H:])
+                cs.append(cst[:, 0, 1])
+            return out, torch.cat(hs, 1), torch.cat(cs, 1)
+        pos = torch.arange(T, device=dev).view(1, T)
+        valid = (pos < lens.view(B, 1)).unsqueeze(2).float()
+
+        class _Dir(object):                                                  # one direction's parameters under the names lstm_seq reads
+            def __init__(self, sfx):
+                for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
+                    setattr(self, n, getattr(rnn, n + sfx))
+        hf, cf = A.lstm_seq(x, _Dir(""))
+        banks, hs, cs = [hf * valid], [hf[rows, last]], [cf[rows, last]]
+        if nd == 2:
+            ridx = (lens.view(B, 1) - 1 - pos).clamp(min=0)                  # position read at reverse step t
+            xr = torch.gather(x, 1, ridx.unsqueeze(2).expand(B, T, x.shape[2])) * valid
+            hr, cr = A.lstm_seq(xr, _Dir("_reverse"))
+            banks.append(torch.gather(hr * valid, 1, ridx.unsqueeze(2).expand(B, T, H)) * valid)
+            hs.append(hr[rows, last])                                        # after the whole valid part, read backwards
+            cs.append(cr[rows, last])
+        return torch.cat(banks, 2), torch.cat(hs, 1), torch.cat(cs, 1)
+
+    def _align(self, h_all, mem):
+        """global_attention.py:81-119 -> [B, TL, QL] (tiny: tensor glue around the library's linears, as in multitask/cars.py)"""
+        att = self.decoder.decoder.attn
+        if self.attn_type == "mlp":
+            wq = A.linear(h_all, att.linear_query.weight, att.linear_query.bias)
+            uh = A.linear(mem, att.linear_context.weight)
+            return A.linear(torch.tanh(wq.unsqueeze(2) + uh.unsqueeze(1)), att.v.weight).squeeze(-1)
+        q = A.linear(h_all, att.linear_in.weight) if self.attn_type == "general" else h_all
+        return (q.unsqueeze(2) * mem.unsqueeze(1)).sum(3)
+
+    def forward(self, source_rep, source_len, target_rep, target_len, target_seq, source_map=None, alignment=None):
+        """seq2seq.py:48-103 -> scalar loss: logits of steps [:-1] against target_seq[:, 1:], NLL masked at PAD, summed over time, averaged
+        over rows.  Differentiable through the HIP operators of autograd.py; dropout is active in train mode only."""
+        B, QL = source_rep.shape
+        self._check_layers(B)
+        table = self.embedder.word_embeddings.table
+        lib.require_device(source_rep, source_len, target_rep, target_seq, table)
+        tr = self.training
+        src, tgt = self._clean_ids(source_rep, target_rep, table.shape[0])
+        lens = lib.ids64(source_len)
+        pe = self.embedder.dropout.p
+        mem, h_n, c_n = self._encode_train(A.dropout(A.embed(src, table), pe, tr), lens)
+        mem = A.dropout(mem, self.dropout.p, tr)
+        order = torch.sort(lens, 0, True)[1]                                 # the reference's length-sorted final state (see the module docstring)
+        dec_h, dec_c = h_n[order], c_n[order]
+        temb = A.dropout(A.embed(tgt, table), pe, tr)
+        rnn, att = self.decoder.decoder.rnn, self.decoder.decoder.attn
+        h_all, _ = A.lstm_seq(temb, rnn, dec_h, dec_c)                       # [B,TL,nhid]
+        TL = h_all.shape[1]
+        align = self._align(h_all, mem)
+        mask = torch.arange(QL, device=mem.device).unsqueeze(0) < lens.unsqueeze(1)          # [B,QL]: the TL rows of a source share it
+        ctx = A.softmax_pool(align, mask, mem, mask_div=TL).view(B, TL, -1)
+        mlp = self.attn_type == "mlp"
+        dec_out = A.linear(torch.cat((ctx, h_all), 2), att.linear_out.weight, att.linear_out.bias if mlp else None, act=None if mlp else "tanh")
+        dec_out = A.dropout(dec_out, self.dec_dropout_p, tr)[:, :-1]
+        logits = A.linear(dec_out, self.generator.weight, self.generator.bias)
+        return A.suggestion_loss(logits, lib.ids64(target_seq)[:, 1:], PAD, 0.0)

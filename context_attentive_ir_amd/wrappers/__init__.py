@@ -1,5 +1,6 @@
 from .ranker import Ranker
 from .multitask import Multitask
+from .recommender import Recommender
 from .common import GraphedUpdate
 
-__all__ = ["Ranker", "Multitask", "GraphedUpdate"]
+__all__ = ["Ranker", "Multitask", "Recommender", "GraphedUpdate"]

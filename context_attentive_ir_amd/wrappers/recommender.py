@@ -1,0 +1,147 @@
+"""Recommender -- wrapper with the call shapes of neuroir.models.recommender.Recommender
+(/root/reference/neuroir/models/recommender.py:21-420) for Seq2seq: update(ex) is the training step, predict(ex) the greedy decode
+(+ the reference's host-side tail for a batch in its collate layout)."""
+import torch
+
+from ..constants import BOS, EOS, PAD, UNK_WORD
+from ..recommender import Seq2seq
+from .common import WrapperBase
+
+NETWORKS = {"SEQ2SEQ": Seq2seq}
+FOLLOW_UPS = {"ACG": "ACG is Seq2seq with a copy generator (copy_attn, src_map, collapse_copy_scores): its own follow-up",
+              "HREDQS": "HredQS (hierarchical session encoder) is its own follow-up"}
+
+
+class Recommender(WrapperBase):
+    def __init__(self, args, src_dict=None, tgt_dict=None, state_dict=None):
+        self.args = args
+        self.src_dict, self.tgt_dict = src_dict, tgt_dict
+        if src_dict is not None:
+            self.args.src_vocab_size = len(src_dict)
+        if tgt_dict is not None:
+            self.args.tgt_vocab_size = len(tgt_dict)
+        self.type = args.model_type.upper()
+        if self.type in FOLLOW_UPS:
+            raise NotImplementedError("HIP Recommender: model_type %s is not built yet -- %s" % (self.type, FOLLOW_UPS[self.type]))
+        if self.type not in NETWORKS:
+            raise RuntimeError("Unsupported model: %s (recommender models on the HIP path: %s)" % (args.model_type, sorted(NETWORKS)))
+        self.network = NETWORKS[self.type](args)
+        if state_dict:
+            state_dict = dict(state_dict)
+            state_dict.pop("fixed_embedding", None)              # models/recommender.py:50-57: a buffer of the embedding layer, not a parameter
+            self.network.load_state_dict(state_dict)
+        self.updates, self.use_cuda, self.parallel = 0, False, False
+        self.group = None
+
+    def _dev(self, t):
+        return t.cuda(non_blocking=True) if self.use_cuda else t
+
+    # ---- training ---------------------------------------------------------------------------------------------------------------------
+    def update(self, ex):
+        """models/recommender.py:160-227: train-mode forward -> backward -> clip_grad_norm(grad_clipping) -> optimizer step; returns the loss."""
+        if self.optimizer is None:
+            raise RuntimeError("No optimizer set.")
+        self._poll_ids()
+        self.optimizer.zero_grad()
+        loss = self._update_body(ex)
+        self.updates += 1
+        self._maybe_check_ids()
+        return loss
+
+    def _update_body(self, ex):
+        from .. import autograd as A
+        self.network.train()
+        A.STEP.begin()
+        try:
+            src, tgt, seq = (self._dev(self._rows3(ex[k])) for k in ("source_words", "target_words", "target_seq"))
+            sl, tl = (self._dev(self._rows2(ex[k])) for k in ("source_lens", "target_lens"))
+            loss = self.network(source_rep=src, source_len=sl, target_rep=tgt, target_len=tl, target_seq=seq, source_map=None, alignment=None)
+            loss.backward()
+        except BaseException:
+            A.STEP.abort()
+            raise
+        A.STEP.end()
+        self.sync_gradients()
+        torch.nn.utils.clip_grad_norm_(self.network.parameters(), self.args.grad_clipping)
+        self.optimizer.step()
+        return loss
+
+    @staticmethod
+    def _rows3(t):
+        return t.squeeze(1) if t.dim() == 3 else t
+
+    @staticmethod
+    def _rows2(t):
+        return t.squeeze(1) if t.dim() == 2 else t
+
+    # ---- prediction -------------------------------------------------------------------------------------------------------------------
+    _FIELDS = ("source_words", "source_lens")
+
+    def _predict_body(self, ex):
+        self.network.eval()
+        dec = self.network.decode(source_rep=self._dev(self._rows3(ex["source_words"])), source_len=self._dev(self._rows2(ex["source_lens"])),
+                                  max_len=self.args.max_query_len, src_dict=self.src_dict, tgt_dict=self.tgt_dict, src_map=None, alignment=None,
+                                  blank=None, fill=None, source_vocabs=ex.get("src_vocab") if isinstance(ex, dict) else None)
+        self._maybe_check_ids()
+        return {"prediction_ids": dec["predictions"], "attentions": dec["attentions"]}
+
+    @torch.no_grad()
+    def predict(self, ex):
+        """models/recommender.py:233-329: {'prediction_ids': LongTensor [B, max_query_len] (target-vocabulary ids), 'attentions':
+        [B, max_query_len, QL]}; for a batch in the reference's collate layout (`ids`, `source_tokens`, `target_tokens`, `src_vocab`) also the
+        reference's `ex_ids`, `predictions` (strings, <unk> replaced by the most attended source token), `targets`, `src_sequences`.
+        From the `predict_graph_min_calls`-th call of a batch shape on, the call replays a captured hipGraph (WrapperBase._graphed)."""
+        self._poll_ids()
+        out = self._graphed(ex, self._FIELDS, "decode", self._predict_body)
+        if out is None:
+            out = self._predict_body(ex)
+        elif self.id_check == "blocking":
+            self._maybe_check_ids()
+        if all(k in ex for k in ("ids", "source_tokens", "target_tokens", "src_vocab")):
+            out.update(self._text(ex, out["prediction_ids"], out["attentions"]))
+        return out
+
+    def _text(self, ex, pred_ids, attns):
+        """the host-side tail of the reference's predict (models/recommender.py:294-309): tens2sen (utils/misc.py:36-62) + replace_unknown
+        (utils/copy_utils.py:51-60: token i of the sentence takes the arg-max of attention row i).  The one place predict synchronises."""
+        host, att = pred_ids.cpu().tolist(), attns.cpu()
+        self._poll_ids()
+        words, nw = self.tgt_dict, (len(self.tgt_dict) if self.tgt_dict is not None else 0)
+        preds = []
+        for b, row in enumerate(host):
+            sent = []
+            for wd in row:
+                if wd == BOS:
+                    continue
+                if wd == EOS:
+                    break
+                sent.append(words[wd] if (words is not None and wd < nw) else str(wd))
+            if not sent:
+                sent = [str(PAD)]
+            src_raw = ex["source_tokens"][b][0]
+            for i, tok in enumerate(sent):
+                if tok == UNK_WORD:
+                    sent[i] = src_raw[int(att[b, i].argmax())]
+            preds.append(" ".join(sent))
+        return {"ex_ids": ex["ids"], "predictions": preds,
+                "targets": [[" ".join(q[1:-1]) for q in item] for item in ex["target_tokens"]],
+                "src_sequences": [[" ".join(q[1:-1]) for q in session] for session in ex["source_tokens"]]}
+
+    # ---- saving / loading -------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def load(filename, new_args=None):
+        saved = torch.load(filename, map_location="cpu", weights_only=False)
+        args = saved["args"]
+        if new_args is not None:
+            from ..config import override_model_args
+            args = override_model_args(args, new_args)
+        return Recommender(args, saved.get("src_dict"), saved.get("tgt_dict"), saved["state_dict"])
+
+    @staticmethod
+    def load_checkpoint(filename, use_gpu=True):
+        saved = torch.load(filename, map_location="cpu", weights_only=False)
+        model = Recommender(saved["args"], saved.get("src_dict"), saved.get("tgt_dict"), saved["state_dict"])
+        if use_gpu:
+            model.cuda()
+        model.init_optimizer(saved["optimizer"], use_gpu)
+        return model, saved["epoch"]

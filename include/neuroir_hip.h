@@ -947,6 +947,62 @@ int nir_softmax_pool_bwd(const float* weights, const float* dout, const float* v
 int nir_embed_f32(const int64_t* ids, const float* table, int64_t V, int E, int64_t M, float* out, int* err_flag, nir_stream_t stream);
 int nir_embed_bwd_f32(const int64_t* ids, const float* dout, int64_t V, int E, int64_t M, float* dtable, int64_t pad_idx, nir_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Seq2seq.decode: greedy decoding of the attention encoder-decoder (neuroir/recommender/seq2seq.py:118-195; decoders/decoder.py:120-177,
+ * decoders/rnn_decoder.py:19-90; modules/global_attention.py:81-211).  csrc/seq2seq.hip.
+ * ------------------------------------------------------------------------------------------------ */
+#define NIR_S2S_ATTN_GENERAL 0
+#define NIR_S2S_ATTN_DOT 1
+#define NIR_S2S_ATTN_MLP 2
+typedef struct {
+    const float *rnn_wih, *rnn_whh, *rnn_bih, *rnn_bhh; /* decoder.decoder.rnn.{weight_ih,weight_hh,bias_ih,bias_hh}_l0 [4H,E],[4H,H],[4H] */
+    const float *attn_in_wt;                            /* general: decoder.decoder.attn.linear_in.weight TRANSPOSED [H,H] (row k = column k of the
+                                                           weight): the score bank bank W_in is one GEMM per decode (global_attention.py:98-105) */
+    const float *attn_ctx_w;                            /* mlp: attn.linear_context.weight [H,H] */
+    const float *attn_query_w, *attn_query_b;           /* mlp: attn.linear_query.{weight,bias} [H,H],[H] */
+    const float *attn_v;                                /* mlp: attn.v.weight [H] */
+    const float *attn_out_w, *attn_out_b;               /* attn.linear_out.weight [H,2H]; bias [H] for mlp only (general / dot: ignored, tanh follows) */
+    const float *gen_w, *gen_b;                         /* generator.{weight,bias} [VT,H],[VT] */
+    int H, attn_type;                                   /* nhid; NIR_S2S_ATTN_* */
+    int64_t VT;                                         /* tgt_vocab_size */
+    const float* rnn_gate_fold;                         /* optional, both or neither: nir_lstm_fold_table(table, rnn_wih, rnn_bih, rnn_bhh, H, 1, f32) [V,4H] */
+    const void* rnn_whh_frag;                           /* and nir_lstm_step_pack_whh_frag(rnn_whh, H) (H % 32 == 0, |w| < 2^15), as in nir_cars_decoder_weights */
+    const void* gen_frag;                               /* optional (NULL: fp32 GEMM + arg-max kernel): nir_seq2seq_pack_gen_frag(gen_w) -- generator and arg-max
+                                                           then run as ONE kernel and the [B, VT] logits are never written (H % 32 == 0, H <= 1024) */
+} nir_seq2seq_decoder_weights;
+/* generator.weight [VT,K] -> two fp16 term planes (x = x1 + 2^-11 x2') in MFMA A-fragment order [ceil(VT/16)][K/32][2 terms][64 lanes][8], rows past
+ * VT zero.  K a multiple of 32 in [32, 1024] (bytes() returns 0 otherwise).  err_flag (int, may be NULL) gets bit 1 (value 2) when a weight
+ * is outside the split's range (|w| >= 2^15 or not finite): the caller then leaves gen_frag NULL. */
+size_t nir_seq2seq_gen_frag_bytes(int64_t VT, int K);
+int nir_seq2seq_pack_gen_frag(const float* gen_w, int64_t VT, int K, void* frag, int* err_flag, nir_stream_t stream);
+/* One generator + arg-max step (seq2seq.py:174-185): predictions[r * pred_stride] = argmax_v (x[r,:] . gen_w[v,:] + gen_b[v]) (first index on
+ * ties, like torch.max), next_tokens[r] = tgt2src ? tgt2src[pred] : pred, <unk> (1) when outside [0, V).  gen_frag != NULL, K % 32 == 0 and
+ * K <= 1024: fused kernel (three v_mfma_f32_16x16x32_f16 per product block over the fp16 term pairs; bias added in fp32); otherwise, or with
+ * the tunable exact_f32, the fp32 GEMM + arg-max kernels.  gen_b may be NULL. */
+size_t nir_seq2seq_gen_argmax_workspace_bytes(int64_t rows, int K, int64_t VT, int fused);
+int nir_seq2seq_gen_argmax(const float* x, int64_t rows, int K, const float* gen_w, const float* gen_b, const void* gen_frag, int64_t VT,
+                           const int64_t* tgt2src, int64_t V, void* workspace, size_t workspace_bytes, int64_t* predictions,
+                           int64_t pred_stride, int64_t* next_tokens, nir_stream_t stream);
+/* One attention step (global_attention.py:121-211) for B decode rows: align_j = q . score_bank[b,j,:] (general: q = h, score_bank = bank W_in;
+ * dot: q = h, score_bank = bank) or sum_f v_f tanh(q_f + score_bank[b,j,f]) (mlp: q = W_q h + b_q, score_bank = linear_context(bank));
+ * positions j >= clamp(source_len[b], 0, QL) are masked; a = softmax(align); cat[b] = [sum_j a_j memory_bank[b,j,:] ; h[b]] ([B,2H]);
+ * attn row b at attn + b * attn_stride gets a ([QL], masked positions exactly 0.0; a row of length 0 is NaN like the reference's).
+ * H % 4 == 0, QL <= 4096. */
+int nir_seq2seq_attend(const float* q, const float* h, const float* memory_bank, const float* score_bank, const float* v,
+                       const int64_t* source_len, int64_t B, int QL, int H, int attn_type, float* cat, float* attn, int64_t attn_stride,
+                       nir_stream_t stream);
+/* The whole greedy decode.  dec_h / dec_c [B,H]: the decoder's initial state (decoders/decoder.py:160-177); memory_bank [B,QL,H] and source_len
+ * [B]; table [V,E]: source embedding table; tgt2src [VT] (NULL = identity): source id of every target token (seq2seq.py:182-185 maps through two
+ * Python dicts on the host); bos: first input token.  predictions [B,max_len] int64 (target-vocabulary ids), attentions [B,max_len,QL].
+ * Per step: LSTM step (folded gate rows + fp16 term pairs when rnn_gate_fold / rnn_whh_frag are given and H % 32 == 0, else fp32), attention,
+ * linear_out (+ tanh: general, dot; + bias: mlp), generator + arg-max.  Enqueued on `stream`; never synchronises, allocates nothing; the same
+ * inputs give the same bits.  Bad arguments: NIR_ERR_BAD_ARG, nothing enqueued. */
+size_t nir_seq2seq_decode_workspace_bytes(int64_t B, int QL, const nir_seq2seq_decoder_weights* w /*host*/);
+int nir_seq2seq_decode_greedy(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL,
+                              const float* table, int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len,
+                              const nir_seq2seq_decoder_weights* w /*host*/, void* workspace, size_t workspace_bytes, int64_t* predictions,
+                              float* attentions, nir_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
