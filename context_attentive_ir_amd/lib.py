@@ -97,6 +97,13 @@ class Seq2seqDecoderWeights(C.Structure):
                                                                                      ("gen_frag", C.c_void_p)]
 
 
+class HredqsDecoderWeights(C.Structure):
+    _fields_ = [(f, c_fp) for f in ("rnn_wih", "rnn_whh", "rnn_bih", "rnn_bhh", "gen_w", "gen_b")] + [("H", C.c_int), ("VT", C.c_int64),
+                                                                                                     ("rnn_gate_fold", C.c_void_p),
+                                                                                                     ("rnn_whh_frag", C.c_void_p),
+                                                                                                     ("gen_frag", C.c_void_p)]
+
+
 CarsSessionOutputs = _struct("nir_cars_session_outputs", ["inner_q", "inner_d", "dec_h", "dec_c"])
 
 MnsrfWeights = _struct(
@@ -269,6 +276,10 @@ SIGNATURES = {
     "nir_seq2seq_decode_workspace_bytes": (_z, [_l, _i, C.POINTER(Seq2seqDecoderWeights)]),
     "nir_seq2seq_decode_greedy": (_i, [c_fp, c_fp, c_fp, c_ip, _l, _i, c_fp, _l, _i, c_ip, _l, _i, C.POINTER(Seq2seqDecoderWeights), C.c_void_p, _z,
                                        c_ip, c_fp, c_st]),
+    "nir_hredqs_gen_argmax_workspace_bytes": (_z, [_l]),
+    "nir_hredqs_gen_argmax": (_i, [C.c_void_p, _l, _i, c_fp, C.c_void_p, _l, c_ip, _l, C.c_void_p, _z, c_ip, _l, c_ip, c_st]),
+    "nir_hredqs_decode_workspace_bytes": (_z, [_l, _l, _i, C.POINTER(HredqsDecoderWeights)]),
+    "nir_hredqs_decode_greedy": (_i, [c_fp, c_fp, _l, _l, c_fp, _l, _i, c_ip, _l, _i, C.POINTER(HredqsDecoderWeights), C.c_void_p, _z, c_ip, c_st]),
 }
 
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_SPLIT2 = 0, 1, 2

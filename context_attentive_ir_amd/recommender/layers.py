@@ -1,6 +1,8 @@
-"""Parameter containers that give Seq2seq the reference's attribute / state-dict nesting (mirror of
+"""Parameter containers that give Seq2seq and HredQS the reference's attribute / state-dict nesting (mirror of
 /root/reference/neuroir/recommender/layers.py:10-93: `embedder.word_embeddings...`, `encoder.encoder.rnns.0...`,
-`decoder.decoder.rnn...`, `decoder.decoder.attn...`).  nn.LSTM / nn.Linear hold the parameters only; the forward never calls them."""
+`decoder.decoder.rnn...`, `decoder.decoder.attn...`).  nn.LSTM / nn.Linear hold the parameters only; the forward never calls them.
+encode_train is the differentiable encoder both models train through."""
+import torch
 import torch.nn as nn
 
 from ..multitask.layers import Embedder, Encoder      # noqa: F401  (the same nesting as the session models')
@@ -27,13 +29,15 @@ class GlobalAttentionParams(nn.Module):
 
 
 class RNNDecoderParams(nn.Module):
-    """decoders/decoder.py:68-118: `rnn` = nn.LSTM(input_size -> hidden_size, num_layers), `attn` = GlobalAttention(hidden_size)."""
+    """decoders/decoder.py:68-118: `rnn` = nn.LSTM(input_size -> hidden_size, num_layers), `attn` = GlobalAttention(hidden_size); attn_type
+    'none' (layers.py:70: HredQS) has no attention module and no attention parameters."""
 
     def __init__(self, input_size, nlayers, nhid, attn_type, dropout):
         super().__init__()
         self.hidden_size = nhid
         self.rnn = nn.LSTM(input_size, nhid, nlayers, batch_first=True)
-        self.attn = GlobalAttentionParams(nhid, attn_type)
+        if attn_type not in (None, "none"):
+            self.attn = GlobalAttentionParams(nhid, attn_type)
         self.dropout = nn.Dropout(dropout)
 
 
@@ -41,3 +45,40 @@ class Decoder(nn.Module):
     def __init__(self, input_size, nlayers, nhid, attn_type, dropout_rnn):
         super().__init__()
         self.decoder = RNNDecoderParams(input_size, nlayers, nhid, attn_type, dropout_rnn)
+
+
+def encode_train(rnn, x, lens):
+    """x [B,T,E] through the single-layer nn.LSTM container `rnn` -> (memory bank [B,T,nhid], zero beyond each length; h_n [B,nhid];
+    c_n [B,nhid]) in ORIGINAL row order, differentiable: the register-resident training recurrence up to 128 units per direction (it
+    returns the cell states), one lstm_seq pass per direction beyond."""
+    from .. import autograd as A
+    nd, params = A._lstm_params(rnn)
+    H = rnn.hidden_size
+    B, T, _ = x.shape
+    dev = x.device
+    rows = torch.arange(B, device=dev)
+    last = (lens - 1).clamp(min=0)
+    if H <= 128:
+        out, cst = A._BiLSTM.apply(x, lens, nd, None, None, *params)
+        hs, cs = [out[rows, last, :H]], [cst[rows, last, 0]]
+        if nd == 2:                                                      # the reverse direction ends at position 0
+            hs.append(out[:, 0, H:])
+            cs.append(cst[:, 0, 1])
+        return out, torch.cat(hs, 1), torch.cat(cs, 1)
+    pos = torch.arange(T, device=dev).view(1, T)
+    valid = (pos < lens.view(B, 1)).unsqueeze(2).float()
+
+    class _Dir(object):                                                  # one direction's parameters under the names lstm_seq reads
+        def __init__(self, sfx):
+            for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
+                setattr(self, n, getattr(rnn, n + sfx))
+    hf, cf = A.lstm_seq(x, _Dir(""))
+    banks, hs, cs = [hf * valid], [hf[rows, last]], [cf[rows, last]]
+    if nd == 2:
+        ridx = (lens.view(B, 1) - 1 - pos).clamp(min=0)                  # position read at reverse step t
+        xr = torch.gather(x, 1, ridx.unsqueeze(2).expand(B, T, x.shape[2])) * valid
+        hr, cr = A.lstm_seq(xr, _Dir("_reverse"))
+        banks.append(torch.gather(hr * valid, 1, ridx.unsqueeze(2).expand(B, T, H)) * valid)
+        hs.append(hr[rows, last])                                        # after the whole valid part, read backwards
+        cs.append(cr[rows, last])
+    return torch.cat(banks, 2), torch.cat(hs, 1), torch.cat(cs, 1)

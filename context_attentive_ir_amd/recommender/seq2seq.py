@@ -23,7 +23,7 @@ from .. import autograd as A
 from .. import lib
 from ..constants import BOS, PAD
 from ..multitask import suggest
-from .layers import ATTN_TYPES, Decoder, Embedder, Encoder
+from .layers import ATTN_TYPES, Decoder, Embedder, Encoder, encode_train
 
 
 class Seq2seq(nn.Module, lib.IdCheck):
@@ -154,37 +154,7 @@ class Seq2seq(nn.Module, lib.IdCheck):
     def _encode_train(self, x, lens):
         """x [B,T,E] -> (memory bank [B,T,nhid], h_n [B,nhid], c_n [B,nhid]) in ORIGINAL row order, differentiable: the register-resident
         training recurrence up to 128 units per direction (it returns the cell states), one lstm_seq pass per direction beyond."""
-        rnn = self.encoder.encoder.rnns[0]
-        nd, params = A._lstm_params(rnn)
-        H = rnn.hidden_size
-        B, T, _ = x.shape
-        dev = x.device
-        rows = torch.arange(B, device=dev)
-        last = (lens - 1).clamp(min=0)
-        if H <= 128:
-            out, cst = A._BiLSTM.apply(x, lens, nd, None, None, *params)
-            hs, cs = [out[rows, last, :H]], [cst[rows, last, 0]]
-            if nd == 2:                                                      # the reverse direction ends at position 0
-                hs.append(out[:, 0, H:])
-                cs.append(cst[:, 0, 1])
-            return out, torch.cat(hs, 1), torch.cat(cs, 1)
-        pos = torch.arange(T, device=dev).view(1, T)
-        valid = (pos < lens.view(B, 1)).unsqueeze(2).float()
-
-        class _Dir(object):                                                  # one direction's parameters under the names lstm_seq reads
-            def __init__(self, sfx):
-                for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
-                    setattr(self, n, getattr(rnn, n + sfx))
-        hf, cf = A.lstm_seq(x, _Dir(""))
-        banks, hs, cs = [hf * valid], [hf[rows, last]], [cf[rows, last]]
-        if nd == 2:
-            ridx = (lens.view(B, 1) - 1 - pos).clamp(min=0)                  # position read at reverse step t
-            xr = torch.gather(x, 1, ridx.unsqueeze(2).expand(B, T, x.shape[2])) * valid
-            hr, cr = A.lstm_seq(xr, _Dir("_reverse"))
-            banks.append(torch.gather(hr * valid, 1, ridx.unsqueeze(2).expand(B, T, H)) * valid)
-            hs.append(hr[rows, last])                                        # after the whole valid part, read backwards
-            cs.append(cr[rows, last])
-        return torch.cat(banks, 2), torch.cat(hs, 1), torch.cat(cs, 1)
+        return encode_train(self.encoder.encoder.rnns[0], x, lens)
 
     def _align(self, h_all, mem):
         """global_attention.py:81-119 -> [B, TL, QL] (tiny: tensor glue around the library's linears, as in multitask/cars.py)"""

@@ -1,6 +1,6 @@
 from .ranker import Ranker
 from .multitask import Multitask
-from .recommender import Recommender
+from .recommender import Recommender, SessionRecommender
 from .common import GraphedUpdate
 
-__all__ = ["Ranker", "Multitask", "Recommender", "GraphedUpdate"]
+__all__ = ["Ranker", "Multitask", "Recommender", "SessionRecommender", "GraphedUpdate"]

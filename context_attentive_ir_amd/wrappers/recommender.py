@@ -1,15 +1,17 @@
 """Recommender -- wrapper with the call shapes of neuroir.models.recommender.Recommender
 (/root/reference/neuroir/models/recommender.py:21-420) for Seq2seq: update(ex) is the training step, predict(ex) the greedy decode
-(+ the reference's host-side tail for a batch in its collate layout)."""
+(+ the reference's host-side tail for a batch in its collate layout).  SessionRecommender is the same wrapper for HredQS, whose batches keep
+their session axis."""
 import torch
 
 from ..constants import BOS, EOS, PAD, UNK_WORD
-from ..recommender import Seq2seq
+from ..recommender import HredQS, Seq2seq
 from .common import WrapperBase
 
 NETWORKS = {"SEQ2SEQ": Seq2seq}
 FOLLOW_UPS = {"ACG": "ACG is Seq2seq with a copy generator (copy_attn, src_map, collapse_copy_scores): its own follow-up",
-              "HREDQS": "HredQS (hierarchical session encoder) is its own follow-up"}
+              "HREDQS": "HredQS keeps the session axis of its batches: build it with wrappers.SessionRecommender (registering it here is its own "
+                        "follow-up)"}
 
 
 class Recommender(WrapperBase):
@@ -21,17 +23,20 @@ class Recommender(WrapperBase):
         if tgt_dict is not None:
             self.args.tgt_vocab_size = len(tgt_dict)
         self.type = args.model_type.upper()
-        if self.type in FOLLOW_UPS:
-            raise NotImplementedError("HIP Recommender: model_type %s is not built yet -- %s" % (self.type, FOLLOW_UPS[self.type]))
-        if self.type not in NETWORKS:
-            raise RuntimeError("Unsupported model: %s (recommender models on the HIP path: %s)" % (args.model_type, sorted(NETWORKS)))
-        self.network = NETWORKS[self.type](args)
+        self.network = self._network_class()(args)
         if state_dict:
             state_dict = dict(state_dict)
             state_dict.pop("fixed_embedding", None)              # models/recommender.py:50-57: a buffer of the embedding layer, not a parameter
             self.network.load_state_dict(state_dict)
         self.updates, self.use_cuda, self.parallel = 0, False, False
         self.group = None
+
+    def _network_class(self):
+        if self.type in FOLLOW_UPS:
+            raise NotImplementedError("HIP Recommender: model_type %s is not built yet -- %s" % (self.type, FOLLOW_UPS[self.type]))
+        if self.type not in NETWORKS:
+            raise RuntimeError("Unsupported model: %s (recommender models on the HIP path: %s)" % (self.args.model_type, sorted(NETWORKS)))
+        return NETWORKS[self.type]
 
     def _dev(self, t):
         return t.cuda(non_blocking=True) if self.use_cuda else t
@@ -64,6 +69,10 @@ class Recommender(WrapperBase):
         self.sync_gradients()
         torch.nn.utils.clip_grad_norm_(self.network.parameters(), self.args.grad_clipping)
         self.optimizer.step()
+        # a fused optimizer step (init_optimizer builds Adam that way on a GPU) writes the parameters without bumping their version counters, and
+        # every version-keyed cache -- lib.PackCache: the folded gate table, the fragments, the encoders' concatenated weights; the predict graph
+        # cache -- would keep serving the weights of before the step to the next decode.  Bump them here, no kernel involved.
+        torch.autograd.graph.increment_version([p for g in self.optimizer.param_groups for p in g["params"]])
         return loss
 
     @staticmethod
@@ -128,20 +137,84 @@ class Recommender(WrapperBase):
                 "src_sequences": [[" ".join(q[1:-1]) for q in session] for session in ex["source_tokens"]]}
 
     # ---- saving / loading -------------------------------------------------------------------------------------------------------------
-    @staticmethod
-    def load(filename, new_args=None):
+    @classmethod
+    def load(cls, filename, new_args=None):
         saved = torch.load(filename, map_location="cpu", weights_only=False)
         args = saved["args"]
         if new_args is not None:
             from ..config import override_model_args
             args = override_model_args(args, new_args)
-        return Recommender(args, saved.get("src_dict"), saved.get("tgt_dict"), saved["state_dict"])
+        return cls(args, saved.get("src_dict"), saved.get("tgt_dict"), saved["state_dict"])
 
-    @staticmethod
-    def load_checkpoint(filename, use_gpu=True):
+    @classmethod
+    def load_checkpoint(cls, filename, use_gpu=True):
         saved = torch.load(filename, map_location="cpu", weights_only=False)
-        model = Recommender(saved["args"], saved.get("src_dict"), saved.get("tgt_dict"), saved["state_dict"])
+        model = cls(saved["args"], saved.get("src_dict"), saved.get("tgt_dict"), saved["state_dict"])
         if use_gpu:
             model.cuda()
         model.init_optimizer(saved["optimizer"], use_gpu)
         return model, saved["epoch"]
+
+
+class SessionRecommender(Recommender):
+    """The same wrapper for HredQS (models/recommender.py:44-45,181-211,260-327): the batch tensors keep their session axis, [B, S, .], and
+    predict decodes every prefix of every session -- prediction_ids [B, S, max_query_len]."""
+
+    def _network_class(self):
+        if self.type != "HREDQS":
+            raise RuntimeError("Unsupported model: %s (SessionRecommender builds HREDQS; Recommender builds %s)" % (self.args.model_type, sorted(NETWORKS)))
+        return HredQS
+
+    @staticmethod
+    def _rows3(t):
+        return t
+
+    @staticmethod
+    def _rows2(t):
+        return t
+
+    def _predict_body(self, ex):
+        self.network.eval()
+        dec = self.network.decode(source_rep=self._dev(ex["source_words"]), source_len=self._dev(ex["source_lens"]), max_len=self.args.max_query_len,
+                                  src_dict=self.src_dict, tgt_dict=self.tgt_dict, src_map=None, alignment=None, blank=None, fill=None,
+                                  source_vocabs=ex.get("src_vocab") if isinstance(ex, dict) else None)
+        self._maybe_check_ids()
+        return {"prediction_ids": dec["predictions"]}
+
+    @torch.no_grad()
+    def predict(self, ex):
+        """models/recommender.py:233-329: {'prediction_ids': LongTensor [B, S, max_query_len] (target-vocabulary ids)}; for a batch in the
+        reference's collate layout (`ids`, `source_tokens`, `target_tokens`) also the reference's `ex_ids`, `predictions`, `targets` and
+        `src_sequences`, step-major (index s B + b).  There are no attentions, so no <unk> is replaced.  From the
+        `predict_graph_min_calls`-th call of a batch shape on, the call replays a captured hipGraph (WrapperBase._graphed)."""
+        self._poll_ids()
+        out = self._graphed(ex, self._FIELDS, "decode", self._predict_body)
+        if out is None:
+            out = self._predict_body(ex)
+        elif self.id_check == "blocking":
+            self._maybe_check_ids()
+        if all(k in ex for k in ("ids", "source_tokens", "target_tokens")):
+            out.update(self._text(ex, out["prediction_ids"]))
+        return out
+
+    def _text(self, ex, pred_ids, attns=None):
+        """the host-side tail of the reference's predict for HREDQS (models/recommender.py:310-327; tens2sen: utils/misc.py:36-62).  The one
+        place predict synchronises."""
+        host = pred_ids.cpu().tolist()                                     # [B][S][max_len]
+        self._poll_ids()
+        words, nw = self.tgt_dict, (len(self.tgt_dict) if self.tgt_dict is not None else 0)
+        B, S = len(host), (len(host[0]) if host else 0)
+        out = {"ex_ids": [_id + str(i) for i in range(S) for _id in ex["ids"]], "predictions": [], "targets": [], "src_sequences": []}
+        for s in range(S):
+            for b in range(B):
+                sent = []
+                for wd in host[b][s]:
+                    if wd == BOS:
+                        continue
+                    if wd == EOS:
+                        break
+                    sent.append(words[wd] if (words is not None and wd < nw) else str(wd))
+                out["predictions"].append(" ".join(sent) if sent else str(PAD))
+                out["targets"].append([" ".join(ex["target_tokens"][b][s][1:-1])])
+                out["src_sequences"].append(" ".join(" ".join(q[1:-1]) for q in ex["source_tokens"][b][0:s + 1]))
+        return out

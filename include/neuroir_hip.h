@@ -1003,6 +1003,43 @@ int nir_seq2seq_decode_greedy(const float* dec_h, const float* dec_c, const floa
                               const nir_seq2seq_decoder_weights* w /*host*/, void* workspace, size_t workspace_bytes, int64_t* predictions,
                               float* attentions, nir_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * HredQS.decode: greedy decoding of the hierarchical recurrent encoder-decoder for query suggestion (neuroir/recommender/hredqs.py:169-230;
+ * Decoder(attn_type='none'): decoders/decoder.py:120-177).  csrc/hredqs.hip.  A batch of B sessions of S queries decodes R = B S rows: row
+ * r = b S + s of `predictions`.  The session states arrive as the streaming recurrence writes them, [B,S,H]; the reference hands them to
+ * the decoder in STEP-major order (torch.cat over steps, hredqs.py:79-83) next to decode rows in (b, s) order, so decode row r starts from the
+ * state of step r / B of session r % B.  That pairing is applied inside the entry.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    const float *rnn_wih, *rnn_whh, *rnn_bih, *rnn_bhh; /* decoder.decoder.rnn.{weight_ih,weight_hh,bias_ih,bias_hh}_l0 [4H,E],[4H,H],[4H] */
+    const float *gen_w, *gen_b;                         /* generator.{weight,bias} [VT,H],[VT] */
+    int H;                                              /* nhid_session */
+    int64_t VT;                                         /* tgt_vocab_size */
+    const float* rnn_gate_fold;                         /* optional packs, the formats of nir_seq2seq_decoder_weights: nir_lstm_fold_table(table, rnn_wih, */
+    const void* rnn_whh_frag;                           /* rnn_bih, rnn_bhh, H, 1, f32) [V,4H]; nir_lstm_step_pack_whh_frag(rnn_whh, H); */
+    const void* gen_frag;                               /* nir_seq2seq_pack_gen_frag(gen_w, VT, H).  All three, H % 32 == 0 and H <= 1024: the fast form */
+} nir_hredqs_decoder_weights;
+/* One generator + bias + arg-max step on a state that is ALREADY split: h16 [rows][K/8][2 terms][8] fp16, the term pairs the folded LSTM step
+ * writes (h = h1 + 2^-11 h2').  predictions[r * pred_stride] = argmax_v (h[r,:] . gen_w[v,:] + gen_b[v]) (first index on ties, gen_b may be
+ * NULL), next_tokens[r] = tgt2src ? tgt2src[pred] : pred, <unk> (1) when outside [0, V).  gen_frag = nir_seq2seq_pack_gen_frag(gen_w, VT, K);
+ * K a multiple of 32 in [32, 1024], VT < 2^31 - 16.  Three v_mfma_f32_16x16x32_f16 per product block, bias added in fp32; the winner of a row
+ * travels as a 64-bit key through an atomic max (no [rows, VT] tensor, no partials).  workspace: the keys, cleared by the call. */
+size_t nir_hredqs_gen_argmax_workspace_bytes(int64_t rows);
+int nir_hredqs_gen_argmax(const void* h16, int64_t rows, int K, const float* gen_b, const void* gen_frag, int64_t VT, const int64_t* tgt2src,
+                          int64_t V, void* workspace, size_t workspace_bytes, int64_t* predictions, int64_t pred_stride, int64_t* next_tokens,
+                          nir_stream_t stream);
+/* The whole greedy decode.  h_steps / c_steps [B,S,H]: hidden and cell state of every session step; table [V,E]: source embedding table;
+ * tgt2src [VT] (NULL = identity); bos: first input token; predictions [B,S,max_len] int64 (target-vocabulary ids).
+ * Fast form (all three packs, H % 32 == 0, H <= 1024, tunable exact_f32 off): per step the folded LSTM step, which reads the previous step's
+ * arg-max keys itself, and the generator + arg-max kernel above; one launch behind the loop turns the keys into predictions.  Plain form
+ * (everything else): fp32 LSTM step, fp32 generator GEMM, arg-max kernel.  Enqueued on `stream`; never synchronises, allocates nothing; the
+ * same inputs give the same bits.  Bad arguments: NIR_ERR_BAD_ARG, nothing enqueued.  B S == 0 or max_len == 0: nothing enqueued.
+ * E % 4 == 0, H % 4 == 0. */
+size_t nir_hredqs_decode_workspace_bytes(int64_t B, int64_t S, int max_len, const nir_hredqs_decoder_weights* w /*host*/);
+int nir_hredqs_decode_greedy(const float* h_steps, const float* c_steps, int64_t B, int64_t S, const float* table, int64_t V, int E,
+                             const int64_t* tgt2src, int64_t bos, int max_len, const nir_hredqs_decoder_weights* w /*host*/, void* workspace,
+                             size_t workspace_bytes, int64_t* predictions, nir_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
