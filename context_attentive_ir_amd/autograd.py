@@ -428,6 +428,48 @@ def suggestion_loss(logits, target, pad, regularize_coeff=0.0):
     return loss
 
 
+class _CopyLossRows(Function):
+    """logits [R,V], switch logit [R], copy mass [R], target [R], align [R] -> loss [R] of nir_acg_copy_loss_fwd (unmasked, as the
+    reference's criterion returns it); the backward writes dlogits, d switch logit and d mass in one pass."""
+
+    @staticmethod
+    def forward(ctx, logits, switch, mass, target, align, force_copy):
+        lib.require_device(logits, switch, mass)
+        L = lib.load()
+        z, sw, ms = _f32c(logits), _f32c(switch).reshape(-1), _f32c(mass).reshape(-1)
+        R, V = z.shape
+        t, al = lib.ids64(target).reshape(R).contiguous(), lib.ids64(align).reshape(R).contiguous()
+        loss = torch.empty(R, device=z.device)
+        lse = torch.empty(R, device=z.device)
+        lib.check(L.nir_acg_copy_loss_fwd(lib.ptr(z), V, lib.ptr(sw), lib.ptr(ms), lib.ptr(t), lib.ptr(al), int(bool(force_copy)), R, V, lib.ptr(loss),
+                                          lib.ptr(lse), lib.ptr(id_flag(z.device)), lib.stream()), "nir_acg_copy_loss_fwd")
+        ctx.save_for_backward(z, sw, ms, t, al, lse)
+        ctx.force_copy = int(bool(force_copy))
+        ctx.shapes = (switch.shape, mass.shape)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        z, sw, ms, t, al, lse = ctx.saved_tensors
+        R, V = z.shape
+        g = _f32c(gloss)
+        dz, dsw, dms = torch.empty_like(z), torch.empty_like(sw), torch.empty_like(ms)
+        CH = 65535                      # rows per launch (grid.y of the kernel)
+        for r0 in range(0, R, CH):
+            r1 = min(R, r0 + CH)
+            lib.check(lib.load().nir_acg_copy_loss_bwd(lib.ptr(z[r0:r1]), V, lib.ptr(sw[r0:r1]), lib.ptr(ms[r0:r1]), lib.ptr(t[r0:r1]), lib.ptr(al[r0:r1]),
+                                                       ctx.force_copy, lib.ptr(lse[r0:r1]), lib.ptr(g[r0:r1]), r1 - r0, V, lib.ptr(dz[r0:r1]),
+                                                       lib.ptr(dsw[r0:r1]), lib.ptr(dms[r0:r1]), lib.stream()), "nir_acg_copy_loss_bwd")
+        return dz, dsw.view(ctx.shapes[0]), dms.view(ctx.shapes[1]), None, None, None
+
+
+def copy_loss(logits, switch, mass, target, align, force_copy=False):
+    """CopyGeneratorCriterion (modules/copy_generator.py:99-135) on the rows of the copy generator: logits [R,V] (the PAD column is read as
+    -1e-20, copy_generator.py:79, and gets no gradient), switch logit [R], copy mass [R] = the copy attention summed over the source positions
+    whose dictionary slot is align[r] -> -log(out) per row, unmasked."""
+    return _CopyLossRows.apply(logits, switch, mass, target, align, force_copy)
+
+
 class _SoftmaxPool(Function):
     """logits [R,T], mask (bool [MR,T] or None; row of r = (r // mdiv) % MR), values [R/G,T,D] -> out [R,D] = softmax(masked logits) @ values."""
 

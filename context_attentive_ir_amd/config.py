@@ -5,7 +5,7 @@ Mirror of the reference's config API for the hot-path models (SURVEY.md Appendix
     shapes of /root/reference/neuroir/config.py:33,98,115,123;
   * the per-model fixed hyper-parameters keep the values of /root/reference/neuroir/hyparam.py
     (ESM :3-8, DSSM :10-20, CDSSM :22-32, DUET :34-46, ARCI :48-59, ARCII :61-76, DRMM :78-86, MATCH_TENSOR :88-105, SEQ2SEQ :107-120,
-    HREDQS :122-135, CARS :197-225).
+    HREDQS :122-135, ACG :137-153, CARS :197-225).
 Everything is table-driven here; models outside the hot path are not listed (they keep
 running on the reference's own stock-PyTorch classes).
 """
@@ -37,6 +37,9 @@ MODEL_ARCHITECTURE = {
     # (bidirection = True is the reference's table verbatim, hyparam.py:122-135; its own forward fails with it and so does the mirror's)
     "HREDQS": dict(arch=dict(rnn_type="LSTM", bidirection=True, nlayers=1, nhid=512, dropout_rnn=0.2, nhid_session=1024),
                    data=dict(tgt_vocab_size=30000, fix_embeddings=True)),
+    "ACG": dict(arch=dict(rnn_type="LSTM", bidirection=True, nlayers=1, nhid=512, dropout_rnn=0.2, attn_type="general", copy_attn=True,
+                          reuse_copy_attn=True, force_copy=False),
+                data=dict(tgt_vocab_size=10000, fix_embeddings=True)),
     "MNSRF": dict(arch=dict(_LSTM, nhid_query=512, nhid_document=512, nhid_session=1024, regularize_coeff=0.1, alpha=0.5),
                   data=dict(tgt_vocab_size=30000, fix_embeddings=True)),
     "M_MATCH_TENSOR": dict(arch=dict(_LSTM, featsize=40, nhid_query=30, nhid_document=140, nhid_session=300, nchannels=50,

@@ -15,7 +15,7 @@
 // Everything is enqueued on the caller's stream; no host synchronisation, no allocation, no float atomics.
 #include <algorithm>
 #include <mutex>
-#include "decode_common.hpp"
+#include "s2s_gen.hpp"
 
 namespace nir {
 
@@ -73,152 +73,7 @@ __global__ __launch_bounds__(256) void s2s_attend_kernel(const float* __restrict
     }
 }
 
-// ---- generator + bias + arg-max: logits[b, v] = x[b, :] . W[v, :] + bias[v] never leave the chip --------------------------------
-// W [VT, K] (K = 32 .. 1024, a multiple of 32) arrives as two fp16 term planes in MFMA A-fragment order (s2s_gen_frag_kernel):
-//   frag[vt][ks][term][lane][8],  element (lane, j) = W[16 vt + (lane & 15)][32 ks + 8 (lane >> 4) + j],  rows past VT are zero.
-// A workgroup stages 16 NBT decode rows as two fp16 planes in LDS ([2][16 NBT][K + 8] halves: NBT = 4 up to K = 512 -- 133 KB -- and 2
-// beyond -- 132 KB at K = 1024; gfx950 has 160 KB) and walks its range of vocabulary tiles, a wave one tile at a time.  A tile's k-steps
-// go in chunks of S2S_KC: the fragments of the next chunk (or of the next tile's first chunk) are requested before the MFMAs of the
-// current one are issued.  Three v_mfma_f32_16x16x32_f16 per product block (hi hi -> acc; lo hi, hi lo -> acx; result acc + 2^-11 acx),
-// the bias is added in fp32 before the comparison, `>` in ascending index order keeps the first index on ties.  Every wave writes one
-// (value, index) partial per decode row; argmax_finish_kernel reduces them.
-constexpr int S2S_KC = 8;
-
-template <int NBT>
-__global__ __launch_bounds__(256, 1) void s2s_gen_argmax_kernel(const float* __restrict__ x, const _Float16* __restrict__ wfrag,
-                                                                const float* __restrict__ bias, int64_t VT, int64_t ntiles, int64_t Bd, int K,
-                                                                int nvr, float* __restrict__ pval, int* __restrict__ pidx) {
-    extern __shared__ __attribute__((aligned(16))) _Float16 s2s_sm[];          // [2 terms][ROWS][LD]
-    constexpr int ROWS = 16 * NBT;
-    const int LD = K + 8, KS = K / 32, K4 = K / 4;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int c16 = lane & 15, g4 = lane >> 4;
-    const int vr = (int)(blockIdx.x % nvr);
-    const int64_t b0 = (int64_t)(blockIdx.x / nvr) * ROWS;
-    const int64_t per_wg = (ntiles + nvr - 1) / nvr;
-    const int64_t t_lo = (int64_t)vr * per_wg, t_hi = min(ntiles, t_lo + per_wg);
-    {
-        // stage + split this workgroup's decode rows (zero rows past Bd).  The loads of S2S_SB trips are issued before the first is converted
-        // (unconditional, from a clamped element: a branch around a load puts an s_waitcnt vmcnt(0) at its join), as in pred_argmax_kernel:
-        // one load -> convert -> ds_write per trip would be 4 NBT K / 256 dependent L2 round trips.
-        constexpr int S2S_SB = 8;
-        const int total = ROWS * K4;                                              // a multiple of 256
-        for (int e0 = tid; e0 < total; e0 += 256 * S2S_SB) {
-            float4 sv[S2S_SB];
-#pragma unroll
-            for (int q = 0; q < S2S_SB; ++q) {
-                const int e = min(e0 + 256 * q, total - 1);
-                const int r = e / K4, k4 = (e - r * K4) * 4;
-                const int64_t b = b0 + r;
-                sv[q] = *reinterpret_cast<const float4*>(x + (b < Bd ? b : Bd - 1) * K + k4);
-            }
-#pragma unroll
-            for (int q = 0; q < S2S_SB; ++q) {
-                const int e = e0 + 256 * q;
-                if (e < total) {
-                    const int r = e / K4, k4 = (e - r * K4) * 4;
-                    float4 v = sv[q];
-                    if (b0 + r >= Bd) v = make_float4(0.f, 0.f, 0.f, 0.f);
-                    const Split2x4 sp = split2(v);
-                    _Float16* d = s2s_sm + r * LD + k4;
-                    *reinterpret_cast<uint2*>(d) = sp.hi;
-                    *reinterpret_cast<uint2*>(d + ROWS * LD) = sp.lo;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    float best[NBT];
-    int bidx[NBT];
-#pragma unroll
-    for (int bt = 0; bt < NBT; ++bt) { best[bt] = -INFINITY; bidx[bt] = 0x7FFFFFFF; }
-    const int NCH = (KS + S2S_KC - 1) / S2S_KC;
-    const int64_t first = t_lo + wave;
-    const int64_t nt = first < t_hi ? (t_hi - first + 3) / 4 : 0;             // this wave's tiles: first, first + 4, ...
-    const int64_t items = nt * NCH;                                           // (tile, chunk) pairs, in order
-    f32x4 acc[NBT], acx[NBT];
-    auto load_w = [&](int64_t it, f16x8 (&wf)[S2S_KC][2]) {
-        const int64_t t = first + 4 * (it / NCH);
-        const int c = (int)(it % NCH);
-#pragma unroll
-        for (int u = 0; u < S2S_KC; ++u) {
-            const int ks = min(c * S2S_KC + u, KS - 1);                       // clamped: a duplicate k-step is not multiplied below
-            const _Float16* wp = wfrag + ((t * KS + ks) * 2 * 64 + lane) * 8;
-            wf[u][0] = *reinterpret_cast<const f16x8*>(wp);
-            wf[u][1] = *reinterpret_cast<const f16x8*>(wp + 512);
-        }
-    };
-    const _Float16* bp0 = s2s_sm + c16 * LD + 8 * g4;
-    auto compute = [&](int64_t it, const f16x8 (&wf)[S2S_KC][2]) {
-        const int64_t t = first + 4 * (it / NCH);
-        const int c = (int)(it % NCH);
-        if (c == 0) {
-#pragma unroll
-            for (int bt = 0; bt < NBT; ++bt) { acc[bt] = (f32x4){0.f, 0.f, 0.f, 0.f}; acx[bt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-        }
-#pragma unroll
-        for (int u = 0; u < S2S_KC; ++u) {
-            const int ks = c * S2S_KC + u;
-            if (ks < KS) {                                                    // wave-uniform
-                f16x8 b[NBT][2];
-#pragma unroll
-                for (int bt = 0; bt < NBT; ++bt) {
-                    b[bt][0] = *reinterpret_cast<const f16x8*>(bp0 + 32 * ks + bt * 16 * LD);
-                    b[bt][1] = *reinterpret_cast<const f16x8*>(bp0 + 32 * ks + bt * 16 * LD + ROWS * LD);
-                }
-#pragma unroll
-                for (int bt = 0; bt < NBT; ++bt) acx[bt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][1], b[bt][0], acx[bt], 0, 0, 0);
-#pragma unroll
-                for (int bt = 0; bt < NBT; ++bt) acc[bt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][0], b[bt][0], acc[bt], 0, 0, 0);
-#pragma unroll
-                for (int bt = 0; bt < NBT; ++bt) acx[bt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][0], b[bt][1], acx[bt], 0, 0, 0);
-            }
-        }
-        if (c == NCH - 1) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int64_t v = t * 16 + 4 * g4 + r;                        // ascending in r: '>' keeps the first index on ties
-                if (v < VT) {
-                    const float bv = bias ? bias[v] : 0.f;
-#pragma unroll
-                    for (int bt = 0; bt < NBT; ++bt) {
-                        const float y = fmaf(acx[bt][r], SPLIT2_INV, acc[bt][r]) + bv;
-                        if (y > best[bt]) { best[bt] = y; bidx[bt] = (int)v; }
-                    }
-                }
-            }
-        }
-    };
-    {
-        f16x8 wfA[S2S_KC][2], wfB[S2S_KC][2];
-        if (items > 0) load_w(0, wfA);
-        for (int64_t it = 0; it < items; it += 2) {
-            if (it + 1 < items) load_w(it + 1, wfB);
-            compute(it, wfA);
-            if (it + 1 >= items) break;
-            if (it + 2 < items) load_w(it + 2, wfA);
-            compute(it + 1, wfB);
-        }
-    }
-    // lanes l, l + 16, l + 32, l + 48 hold the same decode row: combine (first index wins ties), then one partial per wave and row
-#pragma unroll
-    for (int bt = 0; bt < NBT; ++bt) {
-#pragma unroll
-        for (int sh = 16; sh <= 32; sh <<= 1) {
-            const float ov = __shfl_xor(best[bt], sh);
-            const int oi = __shfl_xor(bidx[bt], sh);
-            if (ov > best[bt] || (ov == best[bt] && oi < bidx[bt])) { best[bt] = ov; bidx[bt] = oi; }
-        }
-        const int64_t b = b0 + bt * 16 + c16;
-        if (g4 == 0 && b < Bd) {
-            const int64_t slot = ((int64_t)vr * 4 + wave) * Bd + b;
-            pval[slot] = best[bt];
-            pidx[slot] = bidx[bt];
-        }
-    }
-}
-
-// generator.weight [VT, K] fp32 -> the fragment order above (h1 rounded to nearest); err_flag bit 1: a weight outside the split's range
+// generator.weight [VT, K] fp32 -> the fragment order of s2s_gen.hpp (h1 rounded to nearest); err_flag bit 1: a weight outside the split's range
 __global__ void s2s_gen_frag_kernel(const float* __restrict__ w, int64_t VT, int K, int64_t n, _Float16* __restrict__ frag, int* __restrict__ err) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       // one (tile, k-step, lane, j)
     if (e >= n) return;
@@ -237,17 +92,6 @@ __global__ void s2s_gen_frag_kernel(const float* __restrict__ w, int64_t VT, int
     d[512] = split2_lo1(v, a);
 }
 
-constexpr int S2S_MAX_WGS = 256;
-static inline int s2s_nbt(int K) { return K <= 512 ? 4 : 2; }
-static inline size_t s2s_lds(int K) { return (size_t)2 * 16 * s2s_nbt(K) * (K + 8) * sizeof(_Float16); }
-static inline bool s2s_fusable(int K, int64_t VT) { return K >= 32 && K <= 1024 && K % 32 == 0 && VT > 0 && VT < 0x7FFFFFF0LL; }
-
-// workgroups per row block: enough for the chip, at least ~2 tiles per wave
-static int s2s_nvr(int64_t Bd, int K, int64_t ntiles) {
-    const int64_t rb = (Bd + 16 * s2s_nbt(K) - 1) / (16 * s2s_nbt(K));
-    return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(S2S_MAX_WGS, (device_cu_count() + rb - 1) / rb), (ntiles + 7) / 8));
-}
-
 static int launch_gen_argmax(const float* x, const void* frag, const float* bias, int64_t VT, int64_t Bd, int K, float* pval, int* pidx,
                              const int64_t* lut, int64_t* pred, int64_t pstride, int64_t* tgt, int64_t Vsrc, hipStream_t st) {
     const int64_t ntiles = (VT + 15) / 16;
@@ -256,17 +100,17 @@ static int launch_gen_argmax(const float* x, const void* frag, const float* bias
     const size_t lds = s2s_lds(K);
     static std::once_flag once;
     std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void*)s2s_gen_argmax_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(512));
-        (void)hipFuncSetAttribute((const void*)s2s_gen_argmax_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(1024));
+        (void)hipFuncSetAttribute((const void*)s2s_gen_argmax_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(512));
+        (void)hipFuncSetAttribute((const void*)s2s_gen_argmax_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(1024));
     });
     {
         ProfScope ps(prof_shape_name("s2s_gen_argmax_kernel", (long long)Bd, (long long)VT, K), st);
         if (nbt == 4)
-            hipLaunchKernelGGL(s2s_gen_argmax_kernel<4>, dim3((unsigned)(nvr * rb)), dim3(256), lds, st, x, (const _Float16*)frag, bias, VT, ntiles, Bd, K,
-                               nvr, pval, pidx);
+            hipLaunchKernelGGL((s2s_gen_argmax_kernel<4, false>), dim3((unsigned)(nvr * rb)), dim3(256), lds, st, x, (const _Float16*)frag, bias, VT, ntiles, Bd, K,
+                               nvr, pval, pidx, (float*)nullptr);
         else
-            hipLaunchKernelGGL(s2s_gen_argmax_kernel<2>, dim3((unsigned)(nvr * rb)), dim3(256), lds, st, x, (const _Float16*)frag, bias, VT, ntiles, Bd, K,
-                               nvr, pval, pidx);
+            hipLaunchKernelGGL((s2s_gen_argmax_kernel<2, false>), dim3((unsigned)(nvr * rb)), dim3(256), lds, st, x, (const _Float16*)frag, bias, VT, ntiles, Bd, K,
+                               nvr, pval, pidx, (float*)nullptr);
     }
     NIR_CHECK_LAUNCH("s2s_gen_argmax_kernel");
     return launch_argmax_finish(pval, pidx, nvr * 4, Bd, lut, pred, pstride, tgt, Vsrc, st);
@@ -287,9 +131,11 @@ struct S2sPlan {
     float *sb, *h[2], *c[2], *h16[2], *qh, *cat, *ah, *logits, *pval;
     int* pidx;
     int64_t* tgt;
+    float *psum, *csb, *cq, *ccat, *cattn;             // ACG only: the sums of the partials; a copy attention of its own
     size_t bytes;
 };
-static S2sPlan s2s_plan(void* ws, size_t cap, int64_t B, int QL, int H, int64_t VT, int attn_type, bool fused) {
+// acg: 0 = Seq2seq, 1 = ACG with reuse_copy_attn, 2 = ACG with a copy attention of its own
+static S2sPlan s2s_plan(void* ws, size_t cap, int64_t B, int QL, int H, int64_t VT, int attn_type, bool fused, int acg = 0) {
     Workspace a(ws, cap);
     S2sPlan p;
     p.sb = a.take<float>(attn_type == NIR_S2S_ATTN_DOT ? 0 : (size_t)B * QL * H);
@@ -302,6 +148,17 @@ static S2sPlan s2s_plan(void* ws, size_t cap, int64_t B, int QL, int H, int64_t 
     p.pval = a.take<float>(fused ? (size_t)S2S_MAX_WGS * 4 * B : 0);
     p.pidx = a.take<int>(fused ? (size_t)S2S_MAX_WGS * 4 * B : 0);
     p.tgt = a.take<int64_t>((size_t)B);
+    p.psum = p.csb = p.cq = p.ccat = p.cattn = nullptr;
+    if (acg) {
+        if (!fused) { p.pval = a.take<float>((size_t)B); p.pidx = a.take<int>((size_t)B); }      // one partial per row behind the GEMM
+        p.psum = a.take<float>(fused ? (size_t)S2S_MAX_WGS * 4 * B : (size_t)B);
+    }
+    if (acg == 2) {
+        p.csb = a.take<float>(attn_type == NIR_S2S_ATTN_DOT ? 0 : (size_t)B * QL * H);
+        p.cq = a.take<float>(attn_type == NIR_S2S_ATTN_MLP ? (size_t)B * H : 0);
+        p.ccat = a.take<float>((size_t)B * 2 * H);
+        p.cattn = a.take<float>((size_t)B * QL);
+    }
     p.bytes = align_up(a.off, 256);
     return p;
 }
@@ -315,6 +172,19 @@ static bool s2s_weights_ok(const nir_seq2seq_decoder_weights* w) {
     if (w->attn_type == NIR_S2S_ATTN_DOT) return true;
     if (w->attn_type == NIR_S2S_ATTN_MLP) return w->attn_ctx_w && w->attn_query_w && w->attn_query_b && w->attn_v && w->attn_out_b;
     return false;
+}
+
+static bool acg_weights_ok(const nir_seq2seq_decoder_weights* w, const AcgDecode* g) {
+    if (!g->cw || !g->cw->copy_w || !g->cw->copy_b) return false;
+    if (g->cw->reuse_copy_attn) return true;
+    if (w->attn_type == NIR_S2S_ATTN_GENERAL) return g->cw->attn_in_wt != nullptr;
+    if (w->attn_type == NIR_S2S_ATTN_MLP) return g->cw->attn_ctx_w && g->cw->attn_query_w && g->cw->attn_query_b && g->cw->attn_v;
+    return true;
+}
+
+size_t s2s_decode_workspace_bytes(int64_t B, int QL, const nir_seq2seq_decoder_weights* w, const AcgDecode* acg) {
+    if (!s2s_weights_ok(w) || B < 0 || QL <= 0 || (acg && !acg_weights_ok(w, acg))) return 0;
+    return s2s_plan(nullptr, 0, B, QL, w->H, w->VT, w->attn_type, s2s_fused(w), acg ? (acg->cw->reuse_copy_attn ? 1 : 2) : 0).bytes;
 }
 
 }  // namespace nir
@@ -378,16 +248,22 @@ extern "C" int nir_seq2seq_attend(const float* q, const float* h, const float* m
 }
 
 extern "C" size_t nir_seq2seq_decode_workspace_bytes(int64_t B, int QL, const nir_seq2seq_decoder_weights* w) {
-    if (!nir::s2s_weights_ok(w) || B < 0 || QL <= 0) return 0;
-    return nir::s2s_plan(nullptr, 0, B, QL, w->H, w->VT, w->attn_type, nir::s2s_fused(w)).bytes;
+    return nir::s2s_decode_workspace_bytes(B, QL, w, nullptr);
 }
 
 extern "C" int nir_seq2seq_decode_greedy(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B,
                                          int QL, const float* table, int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len,
                                          const nir_seq2seq_decoder_weights* w, void* workspace, size_t workspace_bytes, int64_t* predictions,
                                          float* attentions, nir_stream_t stream) {
-    using namespace nir;
-    hipStream_t st = (hipStream_t)stream;
+    return nir::s2s_decode(dec_h, dec_c, memory_bank, source_len, B, QL, table, V, E, tgt2src, bos, max_len, w, workspace, workspace_bytes, predictions,
+                           attentions, nullptr, (hipStream_t)stream);
+}
+
+// The decode of both attention recommenders: acg == NULL is Seq2seq's (generator + arg-max), otherwise ACG's, whose step ends in the copy
+// generator of csrc/acg.hip instead -- and, without reuse_copy_attn, runs a second attention on the attentional output in front of it.
+int nir::s2s_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, const float* table,
+                    int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len, const nir_seq2seq_decoder_weights* w, void* workspace,
+                    size_t workspace_bytes, int64_t* predictions, float* attentions, const AcgDecode* acg, hipStream_t st) {
     NIR_REQUIRE(dec_h && dec_c && memory_bank && source_len && table && w && predictions && attentions, "seq2seq_decode: null pointer");
     NIR_REQUIRE(s2s_weights_ok(w), "seq2seq_decode: decoder weights incomplete for the attention type, or H not a multiple of 4");
     NIR_REQUIRE(B >= 0 && QL > 0 && QL <= 4096 && max_len > 0 && V > 0 && E > 0 && E % 4 == 0, "seq2seq_decode: bad dims");
@@ -396,7 +272,13 @@ extern "C" int nir_seq2seq_decode_greedy(const float* dec_h, const float* dec_c,
     const int H = w->H;
     const bool fused = s2s_fused(w);
     NIR_REQUIRE(fused || w->VT < 0x7FFFFFFFLL, "seq2seq_decode: VT too large for the GEMM path");
-    S2sPlan p = s2s_plan(workspace, workspace_bytes, B, QL, H, w->VT, w->attn_type, fused);
+    const bool own_copy_attn = acg && acg->cw && !acg->cw->reuse_copy_attn;
+    if (acg) {
+        NIR_REQUIRE(acg_weights_ok(w, acg), "acg_decode: copy weights incomplete for the attention type");
+        NIR_REQUIRE(acg->src_map_idx && acg->ext2tgt && acg->ext2src, "acg_decode: null index tensor");
+        NIR_REQUIRE(acg_dims_ok(QL, acg->CV), "acg_decode: CV outside [2, %d]", ACG_MAX_CV);
+    }
+    S2sPlan p = s2s_plan(workspace, workspace_bytes, B, QL, H, w->VT, w->attn_type, fused, acg ? (own_copy_attn ? 2 : 1) : 0);
     if (!workspace || p.bytes > workspace_bytes) {
         set_error("seq2seq_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
         return NIR_ERR_WORKSPACE;
@@ -410,6 +292,12 @@ extern "C" int nir_seq2seq_decode_greedy(const float* dec_h, const float* dec_c,
     } else if (mlp) {                                     // memc = linear_context(bank)  (global_attention.py:112-114)
         NIR_PROPAGATE(launch_linear(memory_bank, H, nullptr, nullptr, 0, 0, 0, w->attn_ctx_w, H, nullptr, nullptr, p.sb, H, B * QL, H, H, NIR_ACT_NONE, st));
         sb = p.sb;
+    }
+    const float* csb = memory_bank;                       // the score bank of ACG's own copy attention, the same forms
+    if (own_copy_attn && w->attn_type != NIR_S2S_ATTN_DOT) {
+        NIR_PROPAGATE(launch_linear(memory_bank, H, nullptr, nullptr, 0, 0, 0, mlp ? acg->cw->attn_ctx_w : acg->cw->attn_in_wt, H, nullptr, nullptr, p.csb, H,
+                                    B * QL, H, H, NIR_ACT_NONE, st));
+        csb = p.csb;
     }
     NIR_PROPAGATE(launch_fill_i64(p.tgt, bos, B, st));
     LstmStepArgs a;
@@ -441,7 +329,21 @@ extern "C" int nir_seq2seq_decode_greedy(const float* dec_h, const float* dec_c,
                                     (int64_t)max_len * QL, st));
         NIR_PROPAGATE(launch_linear(p.cat, 2 * H, nullptr, nullptr, 0, 0, 0, w->attn_out_w, 2 * H, mlp ? w->attn_out_b : nullptr, nullptr, p.ah, H, B, H,
                                     2 * H, mlp ? NIR_ACT_NONE : NIR_ACT_TANH, st));
-        if (fused) {
+        if (acg) {
+            const float* ca = attentions + (int64_t)step * QL;                 // the copy attention: the std one, or the alignment of a second
+            int64_t ca_stride = (int64_t)max_len * QL;                           // attention whose query is the attentional output (its own cat
+            if (own_copy_attn) {                                                 // and linear_out take no part in the value)
+                if (mlp)
+                    NIR_PROPAGATE(launch_linear(p.ah, H, nullptr, nullptr, 0, 0, 0, acg->cw->attn_query_w, H, acg->cw->attn_query_b, nullptr, p.cq, H, B, H,
+                                                H, NIR_ACT_NONE, st));
+                NIR_PROPAGATE(launch_attend(mlp ? p.cq : p.ah, p.ah, memory_bank, csb, acg->cw->attn_v, source_len, B, QL, H, mlp, p.ccat, p.cattn, QL, st));
+                ca = p.cattn;
+                ca_stride = QL;
+            }
+            NIR_PROPAGATE(launch_acg_gen_select(p.ah, B, H, w->gen_w, w->gen_b, fused ? w->gen_frag : nullptr, w->VT, p.logits, p.pval, p.pidx, p.psum,
+                                                acg->cw->copy_w, acg->cw->copy_b, ca, ca_stride, source_len, QL, acg->src_map_idx, acg->ext2tgt,
+                                                acg->ext2src, acg->CV, tgt2src, V, predictions + step, (int64_t)max_len, p.tgt, st));
+        } else if (fused) {
             NIR_PROPAGATE(launch_gen_argmax(p.ah, w->gen_frag, w->gen_b, w->VT, B, H, p.pval, p.pidx, tgt2src, predictions + step, (int64_t)max_len, p.tgt,
                                             V, st));
         } else {

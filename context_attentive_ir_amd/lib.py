@@ -97,6 +97,11 @@ class Seq2seqDecoderWeights(C.Structure):
                                                                                      ("gen_frag", C.c_void_p)]
 
 
+class AcgCopyWeights(C.Structure):
+    _fields_ = [("copy_w", c_fp), ("copy_b", c_fp), ("reuse_copy_attn", C.c_int)] + [(f, c_fp) for f in ("attn_in_wt", "attn_ctx_w", "attn_query_w",
+                                                                                                    "attn_query_b", "attn_v")]
+
+
 class HredqsDecoderWeights(C.Structure):
     _fields_ = [(f, c_fp) for f in ("rnn_wih", "rnn_whh", "rnn_bih", "rnn_bhh", "gen_w", "gen_b")] + [("H", C.c_int), ("VT", C.c_int64),
                                                                                                      ("rnn_gate_fold", C.c_void_p),
@@ -280,6 +285,14 @@ SIGNATURES = {
     "nir_hredqs_gen_argmax": (_i, [C.c_void_p, _l, _i, c_fp, C.c_void_p, _l, c_ip, _l, C.c_void_p, _z, c_ip, _l, c_ip, c_st]),
     "nir_hredqs_decode_workspace_bytes": (_z, [_l, _l, _i, C.POINTER(HredqsDecoderWeights)]),
     "nir_hredqs_decode_greedy": (_i, [c_fp, c_fp, _l, _l, c_fp, _l, _i, c_ip, _l, _i, C.POINTER(HredqsDecoderWeights), C.c_void_p, _z, c_ip, c_st]),
+    "nir_acg_gen_select_workspace_bytes": (_z, [_l, _i, _l, _i]),
+    "nir_acg_gen_select": (_i, [c_fp, _l, _i, c_fp, c_fp, C.c_void_p, _l, c_fp, c_fp, c_fp, _l, c_ip, _i, c_ip, c_ip, c_ip, _i, c_ip, _l, C.c_void_p, _z,
+                                c_ip, _l, c_ip, c_fp, c_fp, c_ip, c_st]),
+    "nir_acg_decode_workspace_bytes": (_z, [_l, _i, _i, C.POINTER(Seq2seqDecoderWeights), C.POINTER(AcgCopyWeights)]),
+    "nir_acg_decode_greedy": (_i, [c_fp, c_fp, c_fp, c_ip, _l, _i, c_fp, _l, _i, c_ip, _l, _i, C.POINTER(Seq2seqDecoderWeights),
+                                   C.POINTER(AcgCopyWeights), c_ip, c_ip, c_ip, _i, C.c_void_p, _z, c_ip, c_fp, c_st]),
+    "nir_acg_copy_loss_fwd": (_i, [c_fp, _l, c_fp, c_fp, c_ip, c_ip, _i, _l, _i, c_fp, c_fp, C.c_void_p, c_st]),
+    "nir_acg_copy_loss_bwd": (_i, [c_fp, _l, c_fp, c_fp, c_ip, c_ip, _i, c_fp, c_fp, _l, _i, c_fp, c_fp, c_fp, c_st]),
 }
 
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_SPLIT2 = 0, 1, 2

@@ -1,0 +1,210 @@
+"""ACG -- Seq2seq with a copy generator (drop-in for neuroir.recommender.seq2seq.Seq2seq built with copy_attn=True,
+/root/reference/neuroir/recommender/seq2seq.py:13-195; modules/copy_generator.py; utils/copy_utils.py).
+
+The network is Seq2seq's; what the copy generator changes is the choice of the next token (decode) and the loss (forward):
+
+decode():  the extended distribution over the VT target words and the CV words of every row's own dynamic dictionary is never written.  ONE
+           C-ABI call (nir_acg_decode_greedy, csrc/acg.hip) runs the Seq2seq step and, in two launches more, the copy generator's arg-max.
+           The reference's dense one-hot `src_map` [B, QL, CV] and its per-row host loop over `blank` / `fill` become three index tensors:
+             src_map_idx [B, QL]   dictionary slot of every source position
+             ext2tgt     [B, CV]   target id of a slot's word, -1 where the slot is not collapsed (slots 0 and 1 never are)
+             ext2src     [B, CV]   source id of a slot's word (the token fed back when the slot wins)
+           decode() takes them directly, or converts the reference's arguments once on the host.  `predictions` are EXTENDED ids in
+           [0, VT + CV), as in the reference.
+forward(): the teacher-forced loss of CopyGeneratorCriterion on the differentiable HIP operators of autograd.py (the [B, TL, QL] gather of
+           the copy mass and the [B, TL] switch logit are tensor glue).
+
+State dict: the reference's keys -- `copy_generator.linear.*` is the generator itself under a second name (one parameter, two keys),
+`copy_generator.linear_copy.*` the switch, `decoder.decoder.copy_attn.*` a second attention when reuse_copy_attn is off (its linear_out is
+loaded and given back but takes no part in any value, as in the reference).
+
+Kept quirks: Seq2seq's (see seq2seq.py), and the PAD logit: the reference overwrites it with -1e-20 behind the generator
+(copy_generator.py:79), so PAD takes part in the softmax as a logit of about zero and no gradient reaches the generator through it.
+"""
+import torch
+import torch.nn as nn
+
+from .. import autograd as A
+from .. import lib
+from ..constants import BOS, PAD, UNK
+from ..multitask import suggest
+from .layers import CopyGeneratorParams
+from .seq2seq import Seq2seq, build_network, check_supported
+
+
+def src_map_index(src_map, QL, device=None):
+    """the reference's `src_map` -> LongTensor [B, QL]: a list of per-row index tensors (the collate layout, what make_src_map reads), the dense
+    one-hot [B, QL', CV] make_src_map builds, or the index tensor itself.  Positions past a row's entries get slot 0 (they lie past its
+    length and are never read)."""
+    if torch.is_tensor(src_map) and not src_map.is_floating_point() and src_map.dim() == 2:
+        idx = src_map.long()
+    elif torch.is_tensor(src_map):
+        if src_map.dim() != 3:
+            raise ValueError("src_map: expected [B, QL, CV] one-hot or [B, QL] indices, got %s" % (tuple(src_map.shape),))
+        idx = src_map.argmax(2)
+    else:
+        idx = torch.zeros(len(src_map), QL, dtype=torch.int64)
+        for b, row in enumerate(src_map):
+            row = torch.as_tensor(row).long().reshape(-1)[:QL]
+            idx[b, :row.numel()] = row
+    if idx.shape[1] < QL:
+        idx = torch.nn.functional.pad(idx, (0, QL - idx.shape[1]))
+    idx = idx[:, :QL].contiguous()
+    return idx.to(device) if device is not None else idx
+
+
+def collapse_index(blank, fill, VT, CV):
+    """collapse_copy_scores' (blank, fill) lists -> ext2tgt LongTensor [B, CV] (CPU): ext2tgt[b, blank - VT] = fill, -1 elsewhere"""
+    e2t = torch.full((len(blank), CV), -1, dtype=torch.int64)
+    for b, (bl, fl) in enumerate(zip(blank, fill)):
+        for x, t in zip(bl, fl):
+            c = int(x) - VT
+            if c < 2 or c >= CV:
+                raise ValueError("blank index %d of row %d is outside the row's dictionary [VT + 2, VT + %d)" % (int(x), b, CV))
+            e2t[b, c] = int(t)
+    return e2t
+
+
+def vocab_index(source_vocabs, src_dict, tgt_dict, CV=None):
+    """the rows' dynamic dictionaries -> (ext2tgt, ext2src) LongTensors [B, CV] (CPU): what collapse_copy_scores (utils/copy_utils.py:5-28) and
+    the reference's `src_dict[source_vocabs[b][pred - VT]]` (seq2seq.py:105-116,182-183) look up, for every slot at once.  CV defaults to the
+    largest dictionary; shorter rows are padded with slots nothing maps to.  tgt_dict None: nothing is collapsed."""
+    n = max(len(v) for v in source_vocabs)
+    CV = n if CV is None else int(CV)
+    if CV < n:
+        raise ValueError("CV = %d is smaller than a row's dictionary (%d)" % (CV, n))
+    e2t = torch.full((len(source_vocabs), CV), -1, dtype=torch.int64)
+    e2s = torch.full((len(source_vocabs), CV), UNK, dtype=torch.int64)
+    for b, vocab in enumerate(source_vocabs):
+        for c in range(len(vocab)):
+            word = vocab[c]
+            e2s[b, c] = int(src_dict[word])
+            if c >= 2 and tgt_dict is not None:
+                t = int(tgt_dict[word])
+                if t != UNK:
+                    e2t[b, c] = t
+    return e2t, e2s
+
+
+class ACG(Seq2seq):
+    def __init__(self, args):
+        nn.Module.__init__(self)
+        if not getattr(args, "copy_attn", False):
+            raise ValueError("recommender.ACG is the copy-generator model (copy_attn=True); without it build recommender.Seq2seq")
+        self.reuse_copy_attn = bool(getattr(args, "reuse_copy_attn", False))
+        if args.attn_type in (None, "none"):                              # the reference's own failures (decoders/decoder.py:107-108;
+            if self.reuse_copy_attn:                                      # modules/global_attention.py:64-65)
+                raise RuntimeError("Attn is turned off, so reuse_copy_attn flag must be false")
+            raise AssertionError("Please select a valid attention type.")
+        check_supported(args, "ACG")
+        build_network(self, args, own_copy_attn=not self.reuse_copy_attn)
+        self.copy_attn = True
+        self.force_copy = bool(getattr(args, "force_copy", False))
+        self.copy_generator = CopyGeneratorParams(args.nhid, self.generator)
+        self._pcopy = lib.PackCache(retain=1)
+
+    # ---- eval: greedy decode -----------------------------------------------------------------------------------------------------
+    def _copy_weights(self):
+        cg = self.copy_generator.linear_copy
+        att = None if self.reuse_copy_attn else self.decoder.decoder.copy_attn
+
+        def build():
+            t = dict(copy_w=cg.weight.reshape(-1), copy_b=cg.bias)
+            if att is not None and self.attn_type == "general":
+                t["attn_in_wt"] = att.linear_in.weight.t()
+            elif att is not None and self.attn_type == "mlp":
+                t.update(attn_ctx_w=att.linear_context.weight, attn_query_w=att.linear_query.weight, attn_query_b=att.linear_query.bias,
+                         attn_v=att.v.weight)
+            return lib.Packed(lib.AcgCopyWeights, t, dict(reuse_copy_attn=int(self.reuse_copy_attn)))
+        return self._pcopy.get(list(cg.parameters()) + (list(att.parameters()) if att is not None else []), build)
+
+    def copy_index(self, QL, src_map=None, blank=None, fill=None, source_vocabs=None, src_dict=None, tgt_dict=None, CV=None):
+        """the reference's decode arguments -> (src_map_idx [B,QL], ext2tgt [B,CV], ext2src [B,CV]) on the CPU, once per batch.  CV: given, else
+        the width of a dense `src_map`, else the largest dictionary.  `blank` / `fill`, when given, decide what is collapsed (they are what the
+        reference's decode reads); otherwise collapse_copy_scores is applied to the dictionaries here."""
+        if src_map is None or source_vocabs is None or src_dict is None:
+            raise NotImplementedError("ACG.decode needs src_map, source_vocabs and src_dict (seq2seq.py:105-116), or the three index tensors")
+        VT = self.generator.weight.shape[0]
+        idx = src_map_index(src_map, QL)
+        if CV is None and torch.is_tensor(src_map) and src_map.dim() == 3:
+            CV = max(int(src_map.shape[2]), max(len(v) for v in source_vocabs))
+        e2t, e2s = vocab_index(source_vocabs, src_dict, tgt_dict if blank is None else None, CV)
+        if blank is not None:
+            e2t = collapse_index(blank, fill, VT, e2t.shape[1])
+        return idx, e2t, e2s
+
+    @torch.no_grad()
+    def decode(self, source_rep, source_len, max_len, src_dict, tgt_dict, src_map=None, alignment=None, blank=None, fill=None,
+               source_vocabs=None, tgt2src=None, src_map_idx=None, ext2tgt=None, ext2src=None):
+        """seq2seq.py:118-195 (greedy) -> {'predictions': LongTensor [B, max_len] (EXTENDED ids: below VT a target word, from VT on slot
+        pred - VT of the row's dynamic dictionary), 'attentions': [B, max_len, QL] (the decoder's own attention)}.  The copy inputs are the
+        reference's (`src_map` as a list of index tensors or the dense one-hot, `blank` / `fill`, `source_vocabs`) or the three index
+        tensors (module docstring); `alignment` is unused, as in the reference's decode."""
+        if self.training:
+            raise NotImplementedError("HIP ACG.decode runs in eval mode")
+        B, QL = source_rep.shape
+        self._check_layers(B)
+        table = self.embedder.word_embeddings.table
+        lib.require_device(source_rep, source_len, table)
+        L = lib.load()
+        if src_map_idx is None or ext2tgt is None or ext2src is None:
+            src_map_idx, ext2tgt, ext2src = self.copy_index(QL, src_map, blank, fill, source_vocabs, src_dict, tgt_dict)
+        dev = table.device
+        idx, e2t, e2s = (lib.ids64(t).to(dev).contiguous() for t in (src_map_idx, ext2tgt, ext2src))
+        CV = int(e2t.shape[1])
+        if tuple(idx.shape) != (B, QL) or tuple(e2t.shape) != (B, CV) or tuple(e2s.shape) != (B, CV):
+            raise ValueError("ACG.decode: src_map_idx %s, ext2tgt %s, ext2src %s do not fit %d rows of width %d"
+                             % (tuple(idx.shape), tuple(e2t.shape), tuple(e2s.shape), B, QL))
+        src, _ = self._clean_ids(source_rep, None, table.shape[0])
+        lens = lib.ids64(source_len)
+        final, bank = self.encoder.encoder(A.embed(src, table), lens)
+        dec_h, dec_c = self.initial_state(final, lens)
+        bank = bank.float().contiguous()
+        w, cw = self._decoder_weights(), self._copy_weights()
+        if tgt2src is None:
+            tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, int(w.struct.VT), dev)
+        t = table.detach().float().contiguous()
+        max_len = int(max_len)
+        preds = torch.empty(B, max_len, dtype=torch.int64, device=dev)
+        attns = torch.empty(B, max_len, QL, dtype=torch.float32, device=dev)
+        if B > 0 and max_len > 0:
+            nb = L.nir_acg_decode_workspace_bytes(B, QL, CV, w.ref(), cw.ref())
+            if nb == 0:
+                raise ValueError("ACG.decode: QL = %d / CV = %d outside the copy generator's range (QL <= 4096, 2 <= CV <= 1024)" % (QL, CV))
+            ws = lib.workspace(nb, dev)
+            lib.check(L.nir_acg_decode_greedy(lib.ptr(dec_h), lib.ptr(dec_c), lib.ptr(bank), lib.ptr(lens), B, QL, lib.ptr(t), t.shape[0], t.shape[1],
+                                              lib.ptr(tgt2src), BOS, max_len, w.ref(), cw.ref(), lib.ptr(idx), lib.ptr(e2t), lib.ptr(e2s), CV,
+                                              lib.ptr(ws), ws.numel(), lib.ptr(preds), lib.ptr(attns), lib.stream()), "nir_acg_decode_greedy")
+        return {"predictions": preds, "attentions": attns}
+
+    # ---- train: teacher-forced loss ---------------------------------------------------------------------------------------------------
+    def forward(self, source_rep, source_len, target_rep, target_len, target_seq, source_map=None, alignment=None):
+        """seq2seq.py:48-103 with copy_attn -> scalar loss: CopyGeneratorCriterion on steps [:-1] against target_seq[:, 1:] and
+        alignment[:, 1:], masked at PAD targets, summed over time, averaged over rows.  source_map: the reference's dense one-hot, a list of
+        per-row index tensors, or the index tensor [B, QL]."""
+        if source_map is None or alignment is None:
+            raise ValueError("ACG.forward needs source_map and alignment (models/recommender.py:170-179)")
+        B, QL = source_rep.shape
+        dec_all, align, mem, mask = self._decoder_outputs(source_rep, source_len, target_rep, target_seq)
+        dev = dec_all.device
+        if self.reuse_copy_attn:
+            scores = align
+        else:                                                             # rnn_decoder.py:82-86: the query is the attentional output behind dropout
+            scores = self._align(dec_all, mem, self.decoder.decoder.copy_attn)
+        a_copy = torch.softmax(scores.masked_fill(~mask.unsqueeze(1), float("-inf")), -1)[:, :-1]        # [B,TL-1,QL], exact 0 past the length
+        dec_out = dec_all[:, :-1]
+        TL1 = dec_out.shape[1]
+        target = lib.ids64(target_seq)[:, 1:]
+        al = lib.ids64(alignment).to(dev)[:, 1:]
+        if al.shape[1] < TL1:
+            al = torch.nn.functional.pad(al, (0, TL1 - al.shape[1]))
+        al = al[:, :TL1]
+        idx = src_map_index(source_map, QL, dev)
+        hit = (idx.unsqueeze(1) == al.unsqueeze(2)).to(a_copy.dtype)                                        # [B,TL-1,QL]
+        mass = (a_copy * hit).sum(2)
+        cg = self.copy_generator.linear_copy
+        switch = (dec_out * cg.weight.view(1, 1, -1)).sum(2) + cg.bias
+        logits = A.linear(dec_out, self.generator.weight, self.generator.bias)
+        V = logits.shape[2]
+        rows = A.copy_loss(logits.reshape(B * TL1, V), switch.reshape(-1), mass.reshape(-1), target.reshape(-1), al.reshape(-1), self.force_copy)
+        return (rows.view(B, TL1) * (target != PAD).to(rows.dtype)).sum(1).mean()

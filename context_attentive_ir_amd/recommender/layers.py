@@ -32,19 +32,30 @@ class RNNDecoderParams(nn.Module):
     """decoders/decoder.py:68-118: `rnn` = nn.LSTM(input_size -> hidden_size, num_layers), `attn` = GlobalAttention(hidden_size); attn_type
     'none' (layers.py:70: HredQS) has no attention module and no attention parameters."""
 
-    def __init__(self, input_size, nlayers, nhid, attn_type, dropout):
+    def __init__(self, input_size, nlayers, nhid, attn_type, dropout, copy_attn=False):
         super().__init__()
         self.hidden_size = nhid
         self.rnn = nn.LSTM(input_size, nhid, nlayers, batch_first=True)
         if attn_type not in (None, "none"):
             self.attn = GlobalAttentionParams(nhid, attn_type)
+        if copy_attn:                                   # decoders/decoder.py:113-116: ACG without reuse_copy_attn, a second attention of the same type
+            self.copy_attn = GlobalAttentionParams(nhid, attn_type)
         self.dropout = nn.Dropout(dropout)
 
 
 class Decoder(nn.Module):
-    def __init__(self, input_size, nlayers, nhid, attn_type, dropout_rnn):
+    def __init__(self, input_size, nlayers, nhid, attn_type, dropout_rnn, copy_attn=False):
         super().__init__()
-        self.decoder = RNNDecoderParams(input_size, nlayers, nhid, attn_type, dropout_rnn)
+        self.decoder = RNNDecoderParams(input_size, nlayers, nhid, attn_type, dropout_rnn, copy_attn)
+
+
+class CopyGeneratorParams(nn.Module):
+    """modules/copy_generator.py:49-55: `linear` IS the model's generator (one parameter under two state-dict keys), `linear_copy` the switch"""
+
+    def __init__(self, nhid, generator):
+        super().__init__()
+        self.linear = generator
+        self.linear_copy = nn.Linear(nhid, 1)
 
 
 def encode_train(rnn, x, lens):

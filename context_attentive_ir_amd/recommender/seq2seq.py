@@ -26,29 +26,39 @@ from ..multitask import suggest
 from .layers import ATTN_TYPES, Decoder, Embedder, Encoder, encode_train
 
 
+def check_supported(args, what):
+    """the configurations both attention recommenders refuse"""
+    if args.rnn_type != "LSTM":
+        raise NotImplementedError("HIP %s implements rnn_type 'LSTM' (got %r); GRU decoders are a follow-up of their own" % (what, args.rnn_type))
+    if args.attn_type not in ATTN_TYPES:
+        raise NotImplementedError("HIP %s implements attn_type %s (got %r)" % (what, ", ".join(ATTN_TYPES), args.attn_type))
+
+
+def build_network(net, args, own_copy_attn=False):
+    """the modules and attributes Seq2seq and ACG share (seq2seq.py:14-39), in the reference's registration order"""
+    net.embedder = Embedder(args.emsize, args.src_vocab_size, args.dropout_emb)
+    net.encoder = Encoder(args.rnn_type, args.emsize, args.bidirection, args.nlayers, args.nhid, args.dropout_rnn)
+    net.decoder = Decoder(args.emsize, args.nlayers, args.nhid, args.attn_type, args.dropout_rnn, own_copy_attn)
+    net.dropout = nn.Dropout(args.dropout)
+    net.generator = nn.Linear(args.nhid, args.tgt_vocab_size)
+    net.attn_type, net.nlayers, net.nhid = args.attn_type, int(args.nlayers), int(args.nhid)
+    net.bidirection = bool(args.bidirection)
+    net.dec_dropout_p = float(args.dropout_rnn)         # RNNDecoder.dropout (decoders/decoder.py:87)
+    net.fold_decoder_step = True             # decode: per-token gate rows folded into a [V, 4H] table + fp16-term recurrent product
+    net.fuse_generator_argmax = True         # decode: generator + bias + arg-max in one kernel (no [B, VT] logits)
+    net.fold_budget_bytes = 64 << 30
+    net._pdec = lib.PackCache(retain=1)
+
+
 class Seq2seq(nn.Module, lib.IdCheck):
     def __init__(self, args):
         super().__init__()
-        if args.rnn_type != "LSTM":
-            raise NotImplementedError("HIP Seq2seq implements rnn_type 'LSTM' (got %r); GRU decoders are a follow-up of their own" % (args.rnn_type,))
         if getattr(args, "copy_attn", False):
-            raise NotImplementedError("HIP Seq2seq has no copy generator yet (copy_attn=True is ACG: src_map / collapse_copy_scores are the "
-                                      "ACG follow-up)")
-        if args.attn_type not in ATTN_TYPES:
-            raise NotImplementedError("HIP Seq2seq implements attn_type %s (got %r)" % (", ".join(ATTN_TYPES), args.attn_type))
-        self.embedder = Embedder(args.emsize, args.src_vocab_size, args.dropout_emb)
-        self.encoder = Encoder(args.rnn_type, args.emsize, args.bidirection, args.nlayers, args.nhid, args.dropout_rnn)
-        self.decoder = Decoder(args.emsize, args.nlayers, args.nhid, args.attn_type, args.dropout_rnn)
-        self.dropout = nn.Dropout(args.dropout)
-        self.generator = nn.Linear(args.nhid, args.tgt_vocab_size)
+            raise NotImplementedError("HIP Seq2seq has no copy generator (copy_attn=True is ACG: build recommender.ACG, or wrappers.CopyRecommender "
+                                      "for the reference's batch layout)")
+        check_supported(args, "Seq2seq")
+        build_network(self, args)
         self.copy_attn = False
-        self.attn_type, self.nlayers, self.nhid = args.attn_type, int(args.nlayers), int(args.nhid)
-        self.bidirection = bool(args.bidirection)
-        self.dec_dropout_p = float(args.dropout_rnn)        # RNNDecoder.dropout (decoders/decoder.py:87)
-        self.fold_decoder_step = True            # decode: per-token gate rows folded into a [V, 4H] table + fp16-term recurrent product
-        self.fuse_generator_argmax = True        # decode: generator + bias + arg-max in one kernel (no [B, VT] logits)
-        self.fold_budget_bytes = 64 << 30
-        self._pdec = lib.PackCache(retain=1)
 
     # ---- shared checks -----------------------------------------------------------------------------------------------------------
     def _check_layers(self, B):
@@ -156,9 +166,9 @@ class Seq2seq(nn.Module, lib.IdCheck):
         training recurrence up to 128 units per direction (it returns the cell states), one lstm_seq pass per direction beyond."""
         return encode_train(self.encoder.encoder.rnns[0], x, lens)
 
-    def _align(self, h_all, mem):
+    def _align(self, h_all, mem, att=None):
         """global_attention.py:81-119 -> [B, TL, QL] (tiny: tensor glue around the library's linears, as in multitask/cars.py)"""
-        att = self.decoder.decoder.attn
+        att = self.decoder.decoder.attn if att is None else att
         if self.attn_type == "mlp":
             wq = A.linear(h_all, att.linear_query.weight, att.linear_query.bias)
             uh = A.linear(mem, att.linear_context.weight)
@@ -169,6 +179,13 @@ class Seq2seq(nn.Module, lib.IdCheck):
     def forward(self, source_rep, source_len, target_rep, target_len, target_seq, source_map=None, alignment=None):
         """seq2seq.py:48-103 -> scalar loss: logits of steps [:-1] against target_seq[:, 1:], NLL masked at PAD, summed over time, averaged
         over rows.  Differentiable through the HIP operators of autograd.py; dropout is active in train mode only."""
+        dec_out = self._decoder_outputs(source_rep, source_len, target_rep, target_seq)[0][:, :-1]
+        logits = A.linear(dec_out, self.generator.weight, self.generator.bias)
+        return A.suggestion_loss(logits, lib.ids64(target_seq)[:, 1:], PAD, 0.0)
+
+    def _decoder_outputs(self, source_rep, source_len, target_rep, target_seq):
+        """seq2seq.py:67-81, teacher-forced -> (attentional outputs of every step [B,TL,nhid] behind the decoder's dropout, the attention's
+        alignment scores [B,TL,QL], the memory bank [B,QL,nhid], the length mask [B,QL])"""
         B, QL = source_rep.shape
         self._check_layers(B)
         table = self.embedder.word_embeddings.table
@@ -190,6 +207,4 @@ class Seq2seq(nn.Module, lib.IdCheck):
         ctx = A.softmax_pool(align, mask, mem, mask_div=TL).view(B, TL, -1)
         mlp = self.attn_type == "mlp"
         dec_out = A.linear(torch.cat((ctx, h_all), 2), att.linear_out.weight, att.linear_out.bias if mlp else None, act=None if mlp else "tanh")
-        dec_out = A.dropout(dec_out, self.dec_dropout_p, tr)[:, :-1]
-        logits = A.linear(dec_out, self.generator.weight, self.generator.bias)
-        return A.suggestion_loss(logits, lib.ids64(target_seq)[:, 1:], PAD, 0.0)
+        return A.dropout(dec_out, self.dec_dropout_p, tr), align, mem, mask

@@ -1,6 +1,6 @@
 from .ranker import Ranker
 from .multitask import Multitask
-from .recommender import Recommender, SessionRecommender
+from .recommender import CopyRecommender, Recommender, SessionRecommender
 from .common import GraphedUpdate
 
-__all__ = ["Ranker", "Multitask", "Recommender", "SessionRecommender", "GraphedUpdate"]
+__all__ = ["Ranker", "Multitask", "Recommender", "SessionRecommender", "CopyRecommender", "GraphedUpdate"]

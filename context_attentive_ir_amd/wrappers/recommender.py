@@ -1,15 +1,16 @@
 """Recommender -- wrapper with the call shapes of neuroir.models.recommender.Recommender
 (/root/reference/neuroir/models/recommender.py:21-420) for Seq2seq: update(ex) is the training step, predict(ex) the greedy decode
 (+ the reference's host-side tail for a batch in its collate layout).  SessionRecommender is the same wrapper for HredQS, whose batches keep
-their session axis."""
+their session axis; CopyRecommender is the same wrapper for ACG, whose batches carry the copy generator's maps."""
 import torch
 
 from ..constants import BOS, EOS, PAD, UNK_WORD
-from ..recommender import HredQS, Seq2seq
+from ..recommender import ACG, HredQS, Seq2seq
 from .common import WrapperBase
 
 NETWORKS = {"SEQ2SEQ": Seq2seq}
-FOLLOW_UPS = {"ACG": "ACG is Seq2seq with a copy generator (copy_attn, src_map, collapse_copy_scores): its own follow-up",
+FOLLOW_UPS = {"ACG": "ACG's batches carry src_map / alignment / src_vocab: build it with wrappers.CopyRecommender (registering it here is its own "
+                     "follow-up)",
               "HREDQS": "HredQS keeps the session axis of its batches: build it with wrappers.SessionRecommender (registering it here is its own "
                         "follow-up)"}
 
@@ -218,3 +219,107 @@ class SessionRecommender(Recommender):
                 out["targets"].append([" ".join(ex["target_tokens"][b][s][1:-1])])
                 out["src_sequences"].append(" ".join(" ".join(q[1:-1]) for q in ex["source_tokens"][b][0:s + 1]))
         return out
+
+
+class CopyRecommender(Recommender):
+    """The same wrapper for ACG (models/recommender.py:168-179,243-258,294-309): update(ex) and predict(ex) take the reference's collate
+    layout with `src_map` and `alignment` (lists of per-row index tensors) and `src_vocab` (the rows' dynamic dictionaries).  The dense one-hot
+    of make_src_map is never built: the lists become index tensors on the host, once per batch.  prediction_ids are EXTENDED ids."""
+
+    def _network_class(self):
+        if self.type != "ACG":
+            raise RuntimeError("Unsupported model: %s (CopyRecommender builds ACG; Recommender builds %s)" % (self.args.model_type, sorted(NETWORKS)))
+        return ACG
+
+    @staticmethod
+    def _rows_of(lists, width):
+        out = torch.zeros(len(lists), width, dtype=torch.int64)
+        for b, row in enumerate(lists):
+            row = torch.as_tensor(row).long().reshape(-1)[:width]
+            out[b, :row.numel()] = row
+        return out
+
+    def _update_body(self, ex):
+        from .. import autograd as A
+        if "src_map" not in ex or "alignment" not in ex:
+            raise AssertionError("ACG.update needs ex['src_map'] and ex['alignment'] (models/recommender.py:171)")
+        self.network.train()
+        A.STEP.begin()
+        try:
+            src, tgt, seq = (self._dev(self._rows3(ex[k])) for k in ("source_words", "target_words", "target_seq"))
+            sl, tl = (self._dev(self._rows2(ex[k])) for k in ("source_lens", "target_lens"))
+            smap = ex["src_map"] if torch.is_tensor(ex["src_map"]) else self._rows_of(ex["src_map"], src.shape[1])
+            al = ex["alignment"] if torch.is_tensor(ex["alignment"]) else self._rows_of(ex["alignment"], seq.shape[1])     # utils/copy_utils.py:42-48
+            loss = self.network(source_rep=src, source_len=sl, target_rep=tgt, target_len=tl, target_seq=seq, source_map=self._dev(smap),
+                                alignment=self._dev(al))
+            loss.backward()
+        except BaseException:
+            A.STEP.abort()
+            raise
+        A.STEP.end()
+        self.sync_gradients()
+        torch.nn.utils.clip_grad_norm_(self.network.parameters(), self.args.grad_clipping)
+        self.optimizer.step()
+        torch.autograd.graph.increment_version([p for g in self.optimizer.param_groups for p in g["params"]])       # (see Recommender._update_body)
+        return loss
+
+    # ---- prediction -------------------------------------------------------------------------------------------------------------------
+    _FIELDS = ("source_words", "source_lens", "copy_src_map_idx", "copy_ext2tgt", "copy_ext2src")
+
+    def _copy_fields(self, ex):
+        """ex + the three index tensors of ACG.decode (CPU): CV is padded to QL + 2 when every row's dictionary fits -- the reference's loader
+        always does: a dictionary holds the four specials and the row's words, <s> and </s> among them -- so that a batch shape has ONE
+        graph shape and the tensors are static inputs of the predict graph: every replay gathers THIS batch's maps."""
+        if all(k in ex for k in self._FIELDS[2:]):
+            return ex
+        if "src_map" not in ex or "src_vocab" not in ex:
+            raise AssertionError("ACG.predict needs ex['src_map'] and ex['src_vocab'] (models/recommender.py:247-258)")
+        QL = self._rows3(ex["source_words"]).shape[1]
+        widest = max(len(v) for v in ex["src_vocab"])
+        idx, e2t, e2s = self.network.copy_index(QL, ex["src_map"], None, None, ex["src_vocab"], self.src_dict, self.tgt_dict,
+                                                CV=max(QL + 2, widest))
+        out = dict(ex)
+        out.update(copy_src_map_idx=idx, copy_ext2tgt=e2t, copy_ext2src=e2s)
+        return out
+
+    def _predict_body(self, ex):
+        self.network.eval()
+        dec = self.network.decode(source_rep=self._dev(self._rows3(ex["source_words"])), source_len=self._dev(self._rows2(ex["source_lens"])),
+                                  max_len=self.args.max_query_len, src_dict=self.src_dict, tgt_dict=self.tgt_dict,
+                                  src_map_idx=self._dev(ex["copy_src_map_idx"]), ext2tgt=self._dev(ex["copy_ext2tgt"]),
+                                  ext2src=self._dev(ex["copy_ext2src"]))
+        self._maybe_check_ids()
+        return {"prediction_ids": dec["predictions"], "attentions": dec["attentions"]}
+
+    @torch.no_grad()
+    def predict(self, ex):
+        """models/recommender.py:233-329: {'prediction_ids': LongTensor [B, max_query_len] (EXTENDED ids: from len(tgt_dict) on, slot
+        id - len(tgt_dict) of the row's `src_vocab`), 'attentions': [B, max_query_len, QL]}; for a full collate batch also `ex_ids`,
+        `predictions` (strings; copied words come from the row's dictionary, a remaining <unk> is replaced by the most attended source token),
+        `targets`, `src_sequences`.  Graph replay as in Recommender.predict; the copy maps are inputs of the graph."""
+        return super().predict(self._copy_fields(ex))
+
+    def _text(self, ex, pred_ids, attns):
+        """tens2sen with the rows' dictionaries (utils/misc.py:36-62) + replace_unknown"""
+        host, att = pred_ids.cpu().tolist(), attns.cpu()
+        self._poll_ids()
+        words, nw = self.tgt_dict, len(self.tgt_dict)
+        preds = []
+        for b, row in enumerate(host):
+            sent = []
+            for wd in row:
+                if wd == BOS:
+                    continue
+                if wd == EOS:
+                    break
+                sent.append(words[wd] if wd < nw else ex["src_vocab"][b][wd - nw])
+            if not sent:
+                sent = [str(PAD)]
+            src_raw = ex["source_tokens"][b][0]
+            for i, tok in enumerate(sent):
+                if tok == UNK_WORD:
+                    sent[i] = src_raw[int(att[b, i].argmax())]
+            preds.append(" ".join(sent))
+        return {"ex_ids": ex["ids"], "predictions": preds,
+                "targets": [[" ".join(q[1:-1]) for q in item] for item in ex["target_tokens"]],
+                "src_sequences": [[" ".join(q[1:-1]) for q in session] for session in ex["source_tokens"]]}

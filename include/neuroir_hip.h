@@ -1040,6 +1040,54 @@ int nir_hredqs_decode_greedy(const float* h_steps, const float* c_steps, int64_t
                              const int64_t* tgt2src, int64_t bos, int max_len, const nir_hredqs_decoder_weights* w /*host*/, void* workspace,
                              size_t workspace_bytes, int64_t* predictions, nir_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * ACG: Seq2seq with a copy generator (neuroir/recommender/seq2seq.py with copy_attn; modules/copy_generator.py; utils/copy_utils.py).
+ * csrc/acg.hip.  Per decode row the extended distribution over VT target words and the CV words of the row's own dynamic dictionary,
+ *   P[v] = (1 - z) softmax(l)[v] (l[PAD] := -1e-20),  P[VT + c] = z sum_{j < len, src_map_idx[j] = c} a[j],  z = sigmoid(copy_w . o + copy_b),
+ * collapsed (slot c >= 2 with ext2tgt[c] = t >= 0: P[t] += P[VT + c], P[VT + c] = 1e-10), is never written: its arg-max comes out of the
+ * softmax statistics of the generator and at most CV candidates.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    const float *copy_w, *copy_b;                       /* copy_generator.linear_copy.{weight [1,H], bias [1]} */
+    int reuse_copy_attn;                                /* != 0: the copy attention is the decoder's own; 0: decoder.decoder.copy_attn, a second attention */
+    const float *attn_in_wt;                            /* of the same type whose query is the attentional output -- the forms of */
+    const float *attn_ctx_w, *attn_query_w, *attn_query_b, *attn_v; /* nir_seq2seq_decoder_weights; its linear_out takes no part in the value */
+} nir_acg_copy_weights;
+/* One copy-generator step for `rows` decode rows.  o [rows,K]: attentional outputs; copy_attn row r at copy_attn + r * attn_stride, [QL], read at
+ * j < clamp(source_len[r], 0, QL); src_map_idx [rows,QL]: dictionary slot of every source position (ignored at j >= len, anything outside
+ * [0, CV) is ignored); ext2tgt [rows,CV]: target id of a slot's word, or -1 (columns 0 and 1 are never collapsed); ext2src [rows,CV]: its
+ * source id.  predictions[r * pred_stride] = argmax of the collapsed P (EXTENDED id, the lower id on ties); next_tokens[r] =
+ * tgt2src[pred] (NULL: pred) below VT, ext2src[r, pred - VT] from VT on, <unk> (1) when outside [0, V).
+ * gen_frag != NULL, K % 32 == 0, K <= 1024 and the tunable exact_f32 off: the statistics come from the fused generator kernel (three
+ * v_mfma_f32_16x16x32_f16 per product block, no logits); otherwise from an fp32 GEMM into the workspace and a row kernel.  Optional outputs
+ * (each may be NULL) stat_max / stat_lse / stat_idx [rows]: max_v l[v], log sum_v exp l[v], the first arg-max of l.
+ * QL <= 4096, 2 <= CV <= 1024, K % 4 == 0. */
+size_t nir_acg_gen_select_workspace_bytes(int64_t rows, int K, int64_t VT, int fused);
+int nir_acg_gen_select(const float* o, int64_t rows, int K, const float* gen_w, const float* gen_b, const void* gen_frag, int64_t VT,
+                       const float* copy_w, const float* copy_b, const float* copy_attn, int64_t attn_stride, const int64_t* source_len, int QL,
+                       const int64_t* src_map_idx, const int64_t* ext2tgt, const int64_t* ext2src, int CV, const int64_t* tgt2src, int64_t V,
+                       void* workspace, size_t workspace_bytes, int64_t* predictions, int64_t pred_stride, int64_t* next_tokens, float* stat_max,
+                       float* stat_lse, int64_t* stat_idx, nir_stream_t stream);
+/* The whole greedy decode: nir_seq2seq_decode_greedy with the step above in the place of the generator + arg-max (and, without
+ * reuse_copy_attn, one more attention per step).  predictions [B,max_len] are EXTENDED ids; attentions [B,max_len,QL] the decoder's own
+ * attention, as in the reference.  Enqueued on `stream`; never synchronises, allocates nothing.  Bad arguments: NIR_ERR_BAD_ARG, nothing enqueued. */
+size_t nir_acg_decode_workspace_bytes(int64_t B, int QL, int CV, const nir_seq2seq_decoder_weights* w /*host*/, const nir_acg_copy_weights* cw /*host*/);
+int nir_acg_decode_greedy(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL,
+                          const float* table, int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len,
+                          const nir_seq2seq_decoder_weights* w /*host*/, const nir_acg_copy_weights* cw /*host*/, const int64_t* src_map_idx,
+                          const int64_t* ext2tgt, const int64_t* ext2src, int CV, void* workspace, size_t workspace_bytes, int64_t* predictions,
+                          float* attentions, nir_stream_t stream);
+/* Rows of the teacher-forced copy loss (CopyGeneratorCriterion, copy_generator.py:99-135).  Row r: logits [V] (row stride ld; the PAD column is
+ * read as -1e-20), switch_logit x, copy_mass c = sum_{j: map[j] = align} a[j], target t, align al (UNK = 1):
+ *   z = sigmoid(x), out = [al != 1] z c + 1e-20 + w (1 - z) softmax(l)[t], w = [t != 1] + [al = 1][t = 1] (force_copy: w = [al = 1]),
+ *   loss[r] = -log(out) (the caller masks PAD targets), lse[r] = logsumexp l.  err_flag bit 0: a target outside [0, V).
+ * Backward (R < 65536): dlogits [R,V] dense with 0 in the PAD column, dswitch [R], dmass [R]. */
+int nir_acg_copy_loss_fwd(const float* logits, int64_t ld, const float* switch_logit, const float* copy_mass, const int64_t* target,
+                          const int64_t* align, int force_copy, int64_t R, int V, float* loss, float* lse, int* err_flag, nir_stream_t stream);
+int nir_acg_copy_loss_bwd(const float* logits, int64_t ld, const float* switch_logit, const float* copy_mass, const int64_t* target,
+                          const int64_t* align, int force_copy, const float* lse, const float* grad_loss, int64_t R, int V, float* dlogits,
+                          float* dswitch, float* dmass, nir_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
