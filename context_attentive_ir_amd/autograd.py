@@ -7,6 +7,9 @@ forward AND backward run on the hand-written HIP kernels of csrc/train.hip / csr
     dropout     counter-based inverted dropout (nir_dropout_f32; the keep mask is kept for the backward and for parity replays)
     bilstm      RNNEncoder in train mode: gate GEMM + nir_lstm_train_fwd (saves gate activations / cell states);
                 bwd: BPTT nir_lstm_train_bwd -> dgates, then dW_ih / dW_hh / db / dx as GEMMs
+    bigru       the same for an nn.GRU container: gate GEMM + nir_gru_train_fwd (saves r, z, n and the reset-gated product); bwd: BPTT
+                nir_gru_train_bwd (W_hh resident on the fp32 matrix cores) -> dgx, dq, then dW_ih / dW_hh / db / dx as GEMMs;
+                gru_seq beyond 128 units per direction; birnn dispatches on the container (RNNEncoder.forward_train)
     bce_with_logits   nir_rank_loss_bce / nir_rank_loss_bce_bwd
     max_pool    max over the middle axis with its arg-max (nir_maxpool_arg_f32; bwd scatter nir_maxpool_arg_bwd_f32)
     cosine      query-broadcast cosine (nir_cosine_bcast_f32 / nir_cosine_bcast_bwd_f32)
@@ -1001,6 +1004,196 @@ def lstm_seq(x, lstm, h0=None, c0=None):
     [M,T,H], c of every step [M,T,H]), any hidden size: the input projection of all steps is one GEMM, each step is the recurrent GEMM and
     the cell kernel working inside the sequence buffers (_LSTMSeq; T is a session or a query: <= ~20)."""
     return lstm_gx(linear(x, lstm.weight_ih_l0, lstm.bias_ih_l0), lstm, h0, c0)
+
+
+GRU_FORM = 0               # _BiGRU.backward: 0 = the library's dispatch, 1 = VALU BPTT, 2 = matrix-core BPTT (NIR_GRU_FORM_*; tests force each)
+
+
+class _BiGRU(Function):
+    """x [M,T,I], lens [M] (or None) and the nn.GRU parameters (per direction: w_ih [3H,I], w_hh [3H,H], b_ih, b_hh; H <= 128) -> memory bank
+    [M,T,ND*H], zero at t >= length.  Forward: ONE input GEMM + nir_gru_train_fwd (saves r, z, n, q of every step).  Backward: nir_gru_train_bwd ->
+    dgx (gradient of the input gates) and dq (gradient of W_hn h + b_hn); dx / dW_ih / db_ih from dgx; dW_hh / db_hh over the saved states shifted
+    by a row -- the r / z rows from dgx, the n rows from dq (the recurrent side's gate gradient differs from dgx in the n slot only)."""
+
+    @staticmethod
+    def forward(ctx, x, lens, nd, *params):
+        lib.require_device(x)
+        L = lib.load()
+        M, T, I = x.shape
+        wih = torch.cat([params[4 * d] for d in range(nd)], 0).float().contiguous()
+        whh = torch.stack([params[4 * d + 1] for d in range(nd)], 0).float().contiguous()
+        bih = torch.cat([params[4 * d + 2] for d in range(nd)], 0).float().contiguous()
+        bhh = torch.stack([params[4 * d + 3] for d in range(nd)], 0).float().contiguous()
+        H = whh.shape[2]
+        if H > 128:
+            raise NotImplementedError("train-mode GRU recurrence (nir_gru_train_fwd / _bwd) supports H <= 128 per direction (got %d); wider GRUs go "
+                                      "through gru_seq" % H)
+        x2 = _f32c(x).reshape(M * T, I)
+        dev = x.device
+        out = torch.empty(M, T, nd * H, device=dev)
+        act = torch.empty(M, T, nd, 4 * H, device=dev)
+        lens64 = lib.ids64(lens) if lens is not None else None
+        gates = _linear_raw(x2, wih, bih, 0)
+        lib.check(L.nir_gru_train_fwd(lib.ptr(gates), lib.ptr(lens64), lib.ptr(whh), lib.ptr(bhh), lib.ptr(out), lib.ptr(act), None, M, T, H, nd,
+                                      lib.stream()), "nir_gru_train_fwd")
+        ctx.nd, ctx.dims, ctx.has_lens = nd, (M, T, I, H), lens64 is not None
+        ctx.save_for_backward(x2, lens64 if lens64 is not None else torch.empty(0), wih, whh, out, act)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, lens64, wih, whh, out, act = ctx.saved_tensors
+        L = lib.load()
+        nd = ctx.nd
+        M, T, I, H = ctx.dims
+        G = nd * 3 * H
+        dev = x2.device
+        st = lib.stream()
+        d = _f32c(dout)
+        dgx = torch.empty(M, T, G, device=dev)
+        dq = torch.empty(M, T, nd * H, device=dev)
+        lib.check(L.nir_gru_train_bwd(lib.ptr(d), None, lib.ptr(act), lib.ptr(out), lib.ptr(lens64) if ctx.has_lens else None, lib.ptr(whh), lib.ptr(dgx),
+                                      lib.ptr(dq), M, T, H, nd, GRU_FORM, st), "nir_gru_train_bwd")
+        dg2, dq2, o2 = dgx.view(M * T, G), dq.view(M * T, nd * H), out.view(M * T, nd * H)
+        dx = _linear_raw(dg2, _transpose(wih), None, 0).view(M, T, I) if ctx.needs_input_grad[0] else None
+        # the reductions as in _BiLSTM.backward: h of the PREVIOUS recurrence step is the row before (forward direction) / after (reverse
+        # direction) the gate row, the first step of a sequence has none (period T, skip 0 / T-1) -- no shifted copy of the states.
+        # PACKED_WGRAD: over a device-built list of the valid positions only
+        rows = cnt = None
+        if PACKED_WGRAD and ctx.has_lens and M * T < 2 ** 31:
+            offs = torch.empty(M + 1, device=dev, dtype=torch.int32)
+            rows = torch.empty(M * T, device=dev, dtype=torch.int32)
+            lib.check(L.nir_seq_rows(lib.ptr(lens64), M, T, 0, lib.ptr(offs), lib.ptr(rows), st), "nir_seq_rows")
+            cnt = offs[M:]
+            dwih = torch.empty(G, I, device=dev)
+            db = torch.empty(G, device=dev)
+            lib.check(L.nir_linear_wgrad_rows_set_f32(lib.ptr(dg2), G, 0, lib.ptr(x2), I, 0, lib.ptr(rows), lib.ptr(cnt), M * T, 0, 0, lib.ptr(dwih), I,
+                                                      lib.ptr(db), G, I, st), "nir_linear_wgrad_rows_set_f32")
+        else:
+            dwih, db = _wgrad_bias(dg2, G, x2, I, M * T, G, I)
+        grads = []
+        for dd in range(nd):
+            dwhh = torch.empty(3 * H, H, device=dev)
+            dbn = torch.empty(H, device=dev)
+            delta, skip = (-1, 0) if dd == 0 else (1, T - 1)
+            xs = _off(o2, dd * H * 4)
+            lib.check(L.nir_linear_wgrad_rows_set_f32(_off(dg2, dd * 3 * H * 4), G, 0, xs, nd * H, delta, lib.ptr(rows), lib.ptr(cnt), M * T, T, skip,
+                                                      lib.ptr(dwhh), H, None, 2 * H, H, st), "nir_linear_wgrad_rows_set_f32")
+            lib.check(L.nir_linear_wgrad_rows_set_f32(_off(dq2, dd * H * 4), nd * H, 0, xs, nd * H, delta, lib.ptr(rows), lib.ptr(cnt), M * T, T, skip,
+                                                      _off(dwhh, 2 * H * H * 4), H, lib.ptr(dbn), H, H, st), "nir_linear_wgrad_rows_set_f32")
+            sl = slice(dd * 3 * H, (dd + 1) * 3 * H)
+            grads += [dwih[sl], dwhh, db[sl], torch.cat((db[dd * 3 * H:dd * 3 * H + 2 * H], dbn))]
+        return (dx, None, None) + tuple(grads)
+
+
+class _GRUSeq(Function):
+    """gx [M,T,3H] (input projection of every step, b_ih included), W_hh [3H,H], b_hh -> h [M,T,H] of full-length sequences from the zero state,
+    any hidden size.  Per step ONE recurrent GEMM (nir_linear_f32) and ONE cell kernel working inside the sequence buffers (nir_gru_cell_seq_fwd /
+    _bwd); the backward keeps the recurrent side's gate gradient dgh [M,T,3H] (the A operand of the per-step dh GEMM) and takes dW_hh / db_hh from
+    it in ONE launch over the saved states shifted by a row."""
+
+    @staticmethod
+    def forward(ctx, gx, whh, bhh):
+        lib.require_device(gx, whh)
+        L = lib.load()
+        g = _f32c(gx)
+        M, T, G = g.shape
+        H = G // 3
+        w, b = _f32c(whh), _f32c(bhh)
+        dev = g.device
+        hs = torch.empty(M, T, H, device=dev)
+        act = torch.empty(M, T, 4 * H, device=dev)
+        gh = torch.empty(M, G, device=dev)
+        st = lib.stream()
+        for t in range(T if M else 0):                       # (an empty batch launches nothing)
+            if t > 0:
+                lib.check(L.nir_linear_f32(_off(hs, (t - 1) * H * 4), T * H, None, None, 0, 0, 0, lib.ptr(w), H, lib.ptr(b), None, lib.ptr(gh), G, M, G, H, 0, st),
+                          "nir_linear_f32")
+            lib.check(L.nir_gru_cell_seq_fwd(_off(g, t * G * 4), T * G, lib.ptr(gh) if t > 0 else None, lib.ptr(b),
+                                             _off(hs, (t - 1) * H * 4) if t > 0 else None, T * H, _off(act, t * 4 * H * 4), T * 4 * H,
+                                             _off(hs, t * H * 4), T * H, M, H, st), "nir_gru_cell_seq_fwd")
+        ctx.save_for_backward(w, hs, act)
+        return hs
+
+    @staticmethod
+    def backward(ctx, dhs):
+        w, hs, act = ctx.saved_tensors
+        L = lib.load()
+        M, T, H = hs.shape
+        G = 3 * H
+        dev = hs.device
+        st = lib.stream()
+        d1 = _f32c(dhs)
+        dgx = torch.empty(M, T, G, device=dev)
+        dgh = torch.empty(M, T, G, device=dev)
+        wt = _transpose(w)                                     # [H, 3H]: dh_{t-1} = z dh + dgh_t W_hh
+        dh_rec = dh_dir = None
+        keep = []                                              # (buffers stay referenced until their launches are enqueued)
+        for t in range(T - 1 if M else -1, -1, -1):
+            nxt = torch.empty(M, H, device=dev)
+            lib.check(L.nir_gru_cell_seq_bwd(_off(d1, t * H * 4), T * H, lib.ptr(dh_rec), lib.ptr(dh_dir), _off(act, t * 4 * H * 4), T * 4 * H,
+                                             _off(hs, (t - 1) * H * 4) if t > 0 else None, T * H, _off(dgx, t * G * 4), T * G, _off(dgh, t * G * 4), T * G,
+                                             lib.ptr(nxt), M, H, st), "nir_gru_cell_seq_bwd")
+            keep.append((dh_rec, dh_dir))
+            dh_dir = nxt
+            if t > 0:
+                dh_rec = torch.empty(M, H, device=dev)
+                lib.check(L.nir_linear_f32(_off(dgh, t * G * 4), T * G, None, None, 0, 0, 0, lib.ptr(wt), G, None, None, lib.ptr(dh_rec), H, M, H, G, 0, st),
+                          "nir_linear_f32")
+        dw = db = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw = torch.empty(G, H, device=dev)
+            db = torch.empty(G, device=dev)
+            if M * T:
+                lib.check(L.nir_linear_wgrad_rows_set_f32(lib.ptr(dgh), G, 0, lib.ptr(hs), H, -1, None, None, M * T, T, 0, lib.ptr(dw), H, lib.ptr(db), G, H, st),
+                          "nir_linear_wgrad_rows_set_f32")
+            else:
+                dw.zero_(); db.zero_()
+        return dgx, dw, db
+
+
+def gru_seq(x, gru):
+    """Unidirectional GRU over full-length sequences x [M,T,I] from the zero state -> h of every step [M,T,H], any hidden size: the input projection
+    of all steps is one GEMM, each step the recurrent GEMM and the cell kernel inside the sequence buffers (_GRUSeq).  `gru` holds weight_ih_l0,
+    weight_hh_l0, bias_ih_l0, bias_hh_l0."""
+    return _GRUSeq.apply(linear(x, gru.weight_ih_l0, gru.bias_ih_l0), gru.weight_hh_l0, gru.bias_hh_l0)
+
+
+def bigru(x, lens, gru):
+    """RNNEncoder body in train mode for an nn.GRU(1 layer, batch_first) parameter container -> memory bank [M,T,ND*H], any hidden size: the
+    register-resident training recurrence (_BiGRU) up to H = 128 per direction; beyond it one gru_seq pass per direction, the reverse direction
+    over each sequence's valid part read backwards (the gather-reversed form of `bilstm`)."""
+    nd, params = _lstm_params(gru)
+    H = gru.hidden_size
+    if H <= 128:
+        return _BiGRU.apply(x, lens, nd, *params)
+    M, T, _ = x.shape
+    dev = x.device
+    ln = lens.to(dev).view(M, 1) if lens is not None else torch.full((M, 1), T, device=dev, dtype=torch.int64)
+    pos = torch.arange(T, device=dev).view(1, T)
+    valid = (pos < ln).unsqueeze(2).float()
+
+    class _Dir(object):                                                          # one direction's parameters under the names gru_seq reads
+        def __init__(self, sfx):
+            for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"):
+                setattr(self, n, getattr(gru, n + sfx))
+    fwd = gru_seq(x, _Dir("")) * valid
+    if nd == 1:
+        return fwd
+    ridx = (ln - 1 - pos).clamp(min=0)                                             # position read at reverse step t
+    xr = torch.gather(x, 1, ridx.unsqueeze(2).expand(M, T, x.shape[2])) * valid
+    rev = gru_seq(xr, _Dir("_reverse")) * valid
+    rev = torch.gather(rev, 1, ridx.unsqueeze(2).expand(M, T, H)) * valid            # back to time order
+    return torch.cat((fwd, rev), 2)
+
+
+def birnn(x, lens, rnn):
+    """train-mode encoder layer for either cell: nn.LSTM -> bilstm, nn.GRU -> bigru (both any hidden size)"""
+    if isinstance(rnn, torch.nn.LSTM):
+        return bilstm(x, lens, rnn)
+    if isinstance(rnn, torch.nn.GRU):
+        return bigru(x, lens, rnn)
+    raise NotImplementedError("birnn: nn.LSTM or nn.GRU parameter container expected (got %s)" % type(rnn).__name__)
 
 
 class _BCE(Function):

@@ -11,7 +11,8 @@ live in nn.LSTM / nn.GRU / nn.Linear modules purely as containers so that state-
 model classes cover that configuration, this class covers the rest of the constructor's envelope.
 Returns (final_state, memory_bank) like the reference; final states are in ORIGINAL batch order (the reference leaves them in
 length-sorted order, an artefact nobody on the hot path consumes, Appendix E4).  Dropout between layers is the eval-mode identity; in
-train mode with dropout > 0 and more than one layer the forward raises (training runs through autograd.py's 1-layer LSTM operators).
+train mode with dropout > 0 and more than one layer `forward` raises.  Training runs through `forward_train`: every layer of either cell
+under autograd (autograd.birnn), dropout in front of every layer but the first; it returns the memory bank and refuses the bridge.
 """
 import torch
 import torch.nn as nn
@@ -122,6 +123,25 @@ class RNNEncoder(nn.Module):
         if isinstance(hidden, tuple):
             return tuple(one(layer, hidden[ix]) for ix, layer in enumerate(self.bridge))
         return one(self.bridge[0], hidden)
+
+    def forward_train(self, emb, lengths=None):
+        """Differentiable pass over all layers of either cell (rnn_encoder.py:62-141 under autograd): every layer is autograd.birnn (HIP
+        recurrence + BPTT); layer i > 0 reads the dropped previous bank (the reference's self.dropout(packed_emb), rnn_encoder.py:95).  Returns
+        the memory bank alone: [M,T,hidden] with use_last, the layers' banks side by side otherwise.  (The final states would cost a gather per
+        layer and no train-mode caller reads them.)"""
+        from .. import autograd as A
+        if self.use_bridge:
+            raise NotImplementedError("HIP RNNEncoder.forward_train: use_bridge is not implemented for training (no train-mode model uses the bridge); "
+                                      "RNNEncoder.forward applies it in eval mode")
+        lib.require_device(emb, lengths)
+        x = emb
+        banks = []
+        for i, rnn in enumerate(self.rnns):
+            if i > 0:
+                x = A.dropout(x, self.dropout.p, self.training)
+            x = A.birnn(x, lengths, rnn)
+            banks.append(x)
+        return banks[-1] if self.use_last or len(banks) == 1 else torch.cat(banks, 2)
 
     def forward(self, emb, lengths=None, init_states=None):
         lib.require_device(emb, lengths)

@@ -148,7 +148,8 @@ class MatchTensor(nn.Module, lib.IdCheck):
         return self._pack.get(params, build)
 
     def _forward_train(self, q, ql, d, dl):
-        """Train-mode forward (mtensor.py:62-131 with dropout active), differentiable: lookups, projections, both BiLSTMs, the
+        """Train-mode forward (mtensor.py:62-131 with dropout active), differentiable: lookups, projections, both encoders (the hyparam
+        1-layer BiLSTMs through A.bilstm; GRU / stacked layers through RNNEncoder.forward_train), the
         three convolutions (im2col rows x filter matrix), the 1x1 convolution and the output layer run on the HIP operators of
         autograd.py, im2col included (patch rows in one launch); the broadcast product, the exact-match comparison and the global max are
         tensor glue."""
@@ -161,8 +162,12 @@ class MatchTensor(nn.Module, lib.IdCheck):
         ed = A.dropout(A.embed(d.reshape(M, DL), table), p, True)
         xq = A.linear(eq, self.linear_projection.weight, self.linear_projection.bias)
         xd = A.linear(ed, self.linear_projection.weight, self.linear_projection.bias)
-        hq = A.bilstm(xq, ql, self.query_encoder.rnns[0])
-        hd = A.bilstm(xd, dl.reshape(-1), self.document_encoder.rnns[0])
+        if self._generic_encoders():          # GRU / stacked layers: every layer under autograd (RNNEncoder.forward_train)
+            hq = self.query_encoder.forward_train(xq, ql)
+            hd = self.document_encoder.forward_train(xd, dl.reshape(-1))
+        else:
+            hq = A.bilstm(xq, ql, self.query_encoder.rnns[0])
+            hd = A.bilstm(xd, dl.reshape(-1), self.document_encoder.rnns[0])
         pq = A.linear(hq, self.query_projection.weight, self.query_projection.bias)            # [B,QL,C]
         pd = A.linear(hd, self.document_projection.weight, self.document_projection.bias)      # [M,DL,C]
         return train_head(self, q, d, pq, pd)
@@ -205,10 +210,7 @@ class MatchTensor(nn.Module, lib.IdCheck):
 
     def forward(self, batch_queries, query_len, batch_docs, doc_len, return_parts=False):
         assert batch_queries.shape[0] == batch_docs.shape[0]
-        if self._generic_encoders():
-            if self.training:
-                raise NotImplementedError("HIP MatchTensor trains the hyparam configuration (1-layer LSTM encoders, autograd.py); "
-                                          "GRU / stacked encoders are eval-only")
+        if self._generic_encoders() and not self.training:
             return self._forward_generic(batch_queries, query_len, batch_docs, doc_len, return_parts)
         if self.training:
             lib.require_device(batch_queries, batch_docs, query_len, doc_len, self.word_embeddings.table)

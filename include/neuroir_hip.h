@@ -893,6 +893,40 @@ int nir_lstm_cell_seq_fwd(const float* gx, int64_t ldgx, const float* gh, const 
 int nir_lstm_cell_seq_bwd(const float* dh_step, int64_t ld_dh, const float* dh_rec, const float* dc_step, int64_t ld_dc, const float* dc_rec,
                           const float* act, int64_t ldact, const float* c, int64_t ldc, const float* c_prev, int64_t ldcp, float* dgates,
                           int64_t lddg, float* dc_prev, int64_t B, int H, nir_stream_t stream);
+/* Train-mode GRU recurrence (neuroir/encoders/rnn_encoder.py:62-141 with rnn_type = 'GRU'; torch.nn.GRU, gate order r, z, n), H <= 128 per
+ * direction, ndir 1 or 2, exact fp32.  gates_in [M,T,ndir*3H] = x W_ih^T + b_ih; w_hh [ndir,3H,H]; b_hh [ndir,3H] (b_hn stays INSIDE the reset
+ * product: n = tanh(gx_n + r (W_hn h + b_hn))).  out [M,T,ndir*H] is zero at t >= length (lengths clamped to [0, T]; NULL: all T); the reverse
+ * direction starts at t = length-1 from the zero state.  act [M,T,ndir,4H] holds (r, z, n, q = W_hn h + b_hn) of every valid step (positions past
+ * a length are not written); hn [ndir,M,H] (optional) the final state.  No initial state: a GRU with initial states is not a working
+ * configuration of the reference (rnn_encoder.py:77).
+ * Enqueued on `stream`; never synchronises, allocates nothing, no float atomics: the same inputs give the same bits.  Bad arguments:
+ * NIR_ERR_BAD_ARG, nothing enqueued.  M == 0: nothing enqueued. */
+int nir_gru_train_fwd(const float* gates_in, const int64_t* lengths, const float* w_hh, const float* b_hh, float* out, float* act, float* hn,
+                      int64_t M, int T, int H, int ndir, nir_stream_t stream);
+/* BPTT of the above (rnn_encoder.py:62-141 under loss.backward(), models/ranker.py:216; torch.nn.GRU): dout [M,T,ndir*H] (+ optional dhn
+ * [ndir,M,H]), the saved act and out (out supplies h_{t-1}: one row back for the forward direction, one row ahead for the reverse one, zero at
+ * a sequence's first step) -> dgx [M,T,ndir*3H] = (da_r, da_z, da_n), the gradient of gates_in, and dq [M,T,ndir*H] = r da_n, the gradient of
+ * q; both zero at t >= length.  The recurrent side's gate gradient is dgh = (da_r, da_z, dq): dW_hh / db_hh reduce its r / z rows from dgx and
+ * its n rows from dq (nir_linear_wgrad_rows_set_f32 over `out` shifted by a row); dW_ih / db_ih / dx follow from dgx.
+ * form: NIR_GRU_FORM_AUTO picks; NIR_GRU_FORM_MFMA forces W_hh resident on v_mfma_f32_16x16x4_f32 (exact fp32; NIR_ERR_BAD_ARG where
+ * nir_gru_train_mfma_supported(H) is 0); NIR_GRU_FORM_VALU forces the plain form (any H <= 128).  Same house rules as the forward (the same
+ * inputs and form give the same bits). */
+#define NIR_GRU_FORM_AUTO 0
+#define NIR_GRU_FORM_VALU 1
+#define NIR_GRU_FORM_MFMA 2
+int nir_gru_train_mfma_supported(int H);
+int nir_gru_train_bwd(const float* dout, const float* dhn, const float* act, const float* out, const int64_t* lengths, const float* w_hh,
+                      float* dgx, float* dq, int64_t M, int T, int H, int ndir, int form, nir_stream_t stream);
+/* The GRU cell inside [B,T,.] sequence buffers, any H (autograd._GRUSeq: rnn_encoder.py:62-141 beyond 128 units per direction; torch.nn.GRU):
+ * gates = gx (row stride ldgx, [3H] per row) and gh ([B,3H] contiguous, h_{t-1} W_hh^T + b_hh from nir_linear_f32; NULL: b_hh alone, the first
+ * step); h_prev with row stride ldhp (NULL: zero); act (row stride ldact, [4H] = r, z, n, q) and h (row stride ldh) go to the step's columns of
+ * the sequence buffers.  Backward: dh = dh_step (strided) + dh_rec ([B,H], dgh_{t+1} W_hh) + dh_dir ([B,H], z dh of step t+1), each may be NULL
+ * -> dgx (row stride lddgx), dgh (row stride lddgh), dh_dir_out [B,H] = z dh.  Element-wise; the house rules of nir_gru_train_fwd. */
+int nir_gru_cell_seq_fwd(const float* gx, int64_t ldgx, const float* gh, const float* b_hh, const float* h_prev, int64_t ldhp, float* act,
+                         int64_t ldact, float* h, int64_t ldh, int64_t B, int H, nir_stream_t stream);
+int nir_gru_cell_seq_bwd(const float* dh_step, int64_t ld_dh, const float* dh_rec, const float* dh_dir, const float* act, int64_t ldact,
+                         const float* h_prev, int64_t ldhp, float* dgx, int64_t lddgx, float* dgh, int64_t lddgh, float* dh_dir_out, int64_t B,
+                         int H, nir_stream_t stream);
 /* Inverted dropout with a counter-based mask: keep[i] = uniform(splitmix64(seed ^ i*c)) >= p, y = x*keep/(1-p).  The mask is an
  * output so that a parity test can replay it through the oracle. */
 int nir_dropout_f32(const float* x, float* y, unsigned char* keep, int64_t n, float p, uint64_t seed, nir_stream_t stream);
