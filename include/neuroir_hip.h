@@ -862,7 +862,9 @@ int nir_transpose_f32(const float* in, int R, int C, float* out, nir_stream_t st
 /* n transposes (HOST arrays of device pointers and dims) in as few launches as possible (up to 48 per launch, descriptors as kernel arguments) */
 int nir_transpose_group_f32(int n, const float* const* in, const int* R, const int* Cc, float* const* out, nir_stream_t stream);
 /* Train-mode recurrence (same contract as nir_bilstm_fwd, H <= 128) that also stores act [M,T,ndir,4H] (i,f,g,o after their
- * non-linearities) and cst [M,T,ndir,H] (c_t) of every valid step. */
+ * non-linearities) and cst [M,T,ndir,H] (c_t) of every valid step.  At t >= length act and cst are UNSPECIFIED (the kernels leave them unwritten)
+ * and nir_lstm_train_bwd does not read them: whatever they hold, NaN included, its results are the same.  hn / cn (optional) are bit for bit the
+ * out / cst entries of a sequence's last valid step (t = length-1 forward, t = 0 reverse), h0 / c0 (zero when NULL) for length 0. */
 int nir_lstm_train_fwd(const float* gates_in, const int64_t* lengths, const float* w_hh, const float* h0, const float* c0, float* out,
                        float* act, float* cst, float* hn, float* cn, int64_t M, int T, int H, int ndir, nir_stream_t stream);
 /* The same forward on the split-fp16 matrix-core recurrence (lstm16_pt_h2_kernel<4,4,8,false,true> / <3,2,16,false,true>; 64 < H <= 128 per direction -- the fp32-accurate
@@ -875,7 +877,12 @@ int nir_lstm_train_fwd_split(const float* gates_perm, const int64_t* row_ids, co
                              float* cst, int* err_flag, int64_t M, int T, int H, int ndir, nir_stream_t stream);
 /* BPTT: dout [M,T,ndir*H] (+ optional dhn/dcn [ndir,M,H] and dcst [M,T,ndir,H], gradients w.r.t. the final state and the stored
  * cell states) -> dgates [M,T,ndir*4H], the gradient w.r.t. gates_in (zero at t >= length), and optionally dh0/dc0.
- * dW_ih / dW_hh / db / dx follow from dgates through the GEMM entry points. */
+ * dW_ih / dW_hh / db / dx follow from dgates through the GEMM entry points.
+ * Final-state gradients: lengths are clamped to [0, T] (negative: 0).  dhn / dcn of a sequence enter at that sequence's OWN last step (t = length-1
+ * forward, t = 0 reverse), not at T-1: a sequence shorter than its neighbours keeps them untouched until its first BPTT step.  A sequence of length
+ * 0 has no step: its dgates are zero and dh0 = dhn, dc0 = dcn bit for bit (zero where dhn / dcn are NULL).  c0 (zero when NULL) is c_{t-1} of the
+ * first step; dout and dcst at t >= length are not read.  act, cst, dout, dgates, dcst and c0 may have any 4-byte alignment (16- and 8-byte aligned
+ * buffers take wider cell IO with the same bits); the same inputs give the same bits. */
 int nir_lstm_train_bwd(const float* dout, const float* dhn, const float* dcn, const float* dcst, const float* act, const float* cst, const float* c0,
                        const int64_t* lengths, const float* w_hh, float* dgates, float* dh0, float* dc0, int64_t M, int T, int H,
                        int ndir, nir_stream_t stream);
@@ -906,7 +913,9 @@ int nir_gru_train_fwd(const float* gates_in, const int64_t* lengths, const float
 /* BPTT of the above (rnn_encoder.py:62-141 under loss.backward(), models/ranker.py:216; torch.nn.GRU): dout [M,T,ndir*H] (+ optional dhn
  * [ndir,M,H]), the saved act and out (out supplies h_{t-1}: one row back for the forward direction, one row ahead for the reverse one, zero at
  * a sequence's first step) -> dgx [M,T,ndir*3H] = (da_r, da_z, da_n), the gradient of gates_in, and dq [M,T,ndir*H] = r da_n, the gradient of
- * q; both zero at t >= length.  The recurrent side's gate gradient is dgh = (da_r, da_z, dq): dW_hh / db_hh reduce its r / z rows from dgx and
+ * q; both zero at t >= length (act at t >= length is unspecified and not read; out is zero there).  dhn of a sequence enters at that sequence's own
+ * last step, as for nir_lstm_train_bwd; a sequence of length 0 has zero gradients and its dhn goes nowhere (there is no initial state).  act, out,
+ * dout, dgx and dq may have any 4-byte alignment (the same bits at any).  The recurrent side's gate gradient is dgh = (da_r, da_z, dq): dW_hh / db_hh reduce its r / z rows from dgx and
  * its n rows from dq (nir_linear_wgrad_rows_set_f32 over `out` shifted by a row); dW_ih / db_ih / dx follow from dgx.
  * form: NIR_GRU_FORM_AUTO picks; NIR_GRU_FORM_MFMA forces W_hh resident on v_mfma_f32_16x16x4_f32 (exact fp32; NIR_ERR_BAD_ARG where
  * nir_gru_train_mfma_supported(H) is 0); NIR_GRU_FORM_VALU forces the plain form (any H <= 128).  Same house rules as the forward (the same
