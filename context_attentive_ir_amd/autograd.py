@@ -1093,7 +1093,7 @@ class _GRUSeq(Function):
     it in ONE launch over the saved states shifted by a row."""
 
     @staticmethod
-    def forward(ctx, gx, whh, bhh):
+    def forward(ctx, gx, whh, bhh, h0=None):
         lib.require_device(gx, whh)
         L = lib.load()
         g = _f32c(gx)
@@ -1105,19 +1105,23 @@ class _GRUSeq(Function):
         act = torch.empty(M, T, 4 * H, device=dev)
         gh = torch.empty(M, G, device=dev)
         st = lib.stream()
+        i0 = _f32c(h0) if h0 is not None else None          # [M,H]: step 0 runs the recurrent GEMM on it and blends it in
         for t in range(T if M else 0):                       # (an empty batch launches nothing)
-            if t > 0:
-                lib.check(L.nir_linear_f32(_off(hs, (t - 1) * H * 4), T * H, None, None, 0, 0, 0, lib.ptr(w), H, lib.ptr(b), None, lib.ptr(gh), G, M, G, H, 0, st),
+            rec = t > 0 or i0 is not None
+            hp, ldhp = (_off(hs, (t - 1) * H * 4), T * H) if t > 0 else ((lib.ptr(i0), H) if i0 is not None else (None, T * H))
+            if rec:
+                lib.check(L.nir_linear_f32(hp, ldhp, None, None, 0, 0, 0, lib.ptr(w), H, lib.ptr(b), None, lib.ptr(gh), G, M, G, H, 0, st),
                           "nir_linear_f32")
-            lib.check(L.nir_gru_cell_seq_fwd(_off(g, t * G * 4), T * G, lib.ptr(gh) if t > 0 else None, lib.ptr(b),
-                                             _off(hs, (t - 1) * H * 4) if t > 0 else None, T * H, _off(act, t * 4 * H * 4), T * 4 * H,
-                                             _off(hs, t * H * 4), T * H, M, H, st), "nir_gru_cell_seq_fwd")
-        ctx.save_for_backward(w, hs, act)
+            lib.check(L.nir_gru_cell_seq_fwd(_off(g, t * G * 4), T * G, lib.ptr(gh) if rec else None, lib.ptr(b), hp, ldhp,
+                                             _off(act, t * 4 * H * 4), T * 4 * H, _off(hs, t * H * 4), T * H, M, H, st), "nir_gru_cell_seq_fwd")
+        ctx.has_h0 = i0 is not None
+        ctx.save_for_backward(*((w, hs, act) + ((i0,) if i0 is not None else ())))
         return hs
 
     @staticmethod
     def backward(ctx, dhs):
-        w, hs, act = ctx.saved_tensors
+        w, hs, act = ctx.saved_tensors[:3]
+        i0 = ctx.saved_tensors[3] if ctx.has_h0 else None
         L = lib.load()
         M, T, H = hs.shape
         G = 3 * H
@@ -1132,8 +1136,8 @@ class _GRUSeq(Function):
         for t in range(T - 1 if M else -1, -1, -1):
             nxt = torch.empty(M, H, device=dev)
             lib.check(L.nir_gru_cell_seq_bwd(_off(d1, t * H * 4), T * H, lib.ptr(dh_rec), lib.ptr(dh_dir), _off(act, t * 4 * H * 4), T * 4 * H,
-                                             _off(hs, (t - 1) * H * 4) if t > 0 else None, T * H, _off(dgx, t * G * 4), T * G, _off(dgh, t * G * 4), T * G,
-                                             lib.ptr(nxt), M, H, st), "nir_gru_cell_seq_bwd")
+                                             _off(hs, (t - 1) * H * 4) if t > 0 else lib.ptr(i0), T * H if t > 0 else H, _off(dgx, t * G * 4), T * G,
+                                             _off(dgh, t * G * 4), T * G, lib.ptr(nxt), M, H, st), "nir_gru_cell_seq_bwd")
             keep.append((dh_rec, dh_dir))
             dh_dir = nxt
             if t > 0:
@@ -1149,14 +1153,26 @@ class _GRUSeq(Function):
                           "nir_linear_wgrad_rows_set_f32")
             else:
                 dw.zero_(); db.zero_()
-        return dgx, dw, db
+        dh0 = None
+        if i0 is not None:                                     # dh0 = z dh + dgh_0 W_hh; step 0's recurrent product joins dW_hh
+            dh0 = torch.zeros(M, H, device=dev)
+            if M * T:
+                lib.check(L.nir_linear_f32(lib.ptr(dgh), T * G, None, None, 0, 0, 0, lib.ptr(wt), G, None, None, lib.ptr(dh0), H, M, H, G, 0, st),
+                          "nir_linear_f32")
+                dh0 = dh0 + dh_dir
+                if dw is not None:
+                    dw = dw + _wgrad(dgh, T * G, i0, H, M, G, H)
+        return dgx, dw, db, dh0
 
 
-def gru_seq(x, gru):
-    """Unidirectional GRU over full-length sequences x [M,T,I] from the zero state -> h of every step [M,T,H], any hidden size: the input projection
-    of all steps is one GEMM, each step the recurrent GEMM and the cell kernel inside the sequence buffers (_GRUSeq).  `gru` holds weight_ih_l0,
-    weight_hh_l0, bias_ih_l0, bias_hh_l0."""
-    return _GRUSeq.apply(linear(x, gru.weight_ih_l0, gru.bias_ih_l0), gru.weight_hh_l0, gru.bias_hh_l0)
+def gru_seq(x, gru, h0=None):
+    """Unidirectional GRU over full-length sequences x [M,T,I] from the zero state, or from h0 [M,H] (the GRU decoders: differentiable) -> h of
+    every step [M,T,H], any hidden size: the input projection of all steps is one GEMM, each step the recurrent GEMM and the cell kernel inside
+    the sequence buffers (_GRUSeq).  `gru` holds weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0."""
+    gx = linear(x, gru.weight_ih_l0, gru.bias_ih_l0)
+    if h0 is None:
+        return _GRUSeq.apply(gx, gru.weight_hh_l0, gru.bias_hh_l0)
+    return _GRUSeq.apply(gx, gru.weight_hh_l0, gru.bias_hh_l0, h0)
 
 
 def bigru(x, lens, gru):

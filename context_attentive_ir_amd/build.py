@@ -30,7 +30,8 @@ def _sources():
 
 def _deps_mtime():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "neuroir_hip.h"))
+    inc = os.path.join(os.path.dirname(HERE), "include")
+    hdrs += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")]
     return max(os.path.getmtime(h) for h in hdrs)
 
 

@@ -334,7 +334,7 @@ extern "C" int nir_acg_gen_select(const float* o, int64_t rows, int K, const flo
 extern "C" size_t nir_acg_decode_workspace_bytes(int64_t B, int QL, int CV, const nir_seq2seq_decoder_weights* w, const nir_acg_copy_weights* cw) {
     if (!cw || !nir::acg_dims_ok(QL, CV)) return 0;
     nir::AcgDecode g{cw, nullptr, nullptr, nullptr, CV};
-    return nir::s2s_decode_workspace_bytes(B, QL, w, &g);
+    return nir::s2s_decode_workspace_bytes(B, QL, w, &g, nir::S2S_CELL_LSTM);
 }
 
 extern "C" int nir_acg_decode_greedy(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL,
@@ -346,7 +346,26 @@ extern "C" int nir_acg_decode_greedy(const float* dec_h, const float* dec_c, con
     NIR_REQUIRE(cw, "acg_decode: null copy weights");
     AcgDecode g{cw, src_map_idx, ext2tgt, ext2src, CV};
     return s2s_decode(dec_h, dec_c, memory_bank, source_len, B, QL, table, V, E, tgt2src, bos, max_len, w, workspace, workspace_bytes, predictions, attentions,
-                      &g, (hipStream_t)stream);
+                      &g, S2S_CELL_LSTM, (hipStream_t)stream);
+}
+
+// The same decode with a GRU decoder (nir_seq2seq_gru_decode_greedy's step in front of the copy generator)
+extern "C" size_t nir_acg_gru_decode_workspace_bytes(int64_t B, int QL, int CV, const nir_seq2seq_decoder_weights* w, const nir_acg_copy_weights* cw) {
+    if (!cw || !nir::acg_dims_ok(QL, CV)) return 0;
+    nir::AcgDecode g{cw, nullptr, nullptr, nullptr, CV};
+    return nir::s2s_decode_workspace_bytes(B, QL, w, &g, nir::S2S_CELL_GRU);
+}
+
+extern "C" int nir_acg_gru_decode_greedy(const float* dec_h, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, const float* table,
+                                         int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len, const nir_seq2seq_decoder_weights* w,
+                                         const nir_acg_copy_weights* cw, const int64_t* src_map_idx, const int64_t* ext2tgt, const int64_t* ext2src,
+                                         int CV, void* workspace, size_t workspace_bytes, int64_t* predictions, float* attentions,
+                                         nir_stream_t stream) {
+    using namespace nir;
+    NIR_REQUIRE(cw, "acg_decode: null copy weights");
+    AcgDecode g{cw, src_map_idx, ext2tgt, ext2src, CV};
+    return s2s_decode(dec_h, nullptr, memory_bank, source_len, B, QL, table, V, E, tgt2src, bos, max_len, w, workspace, workspace_bytes, predictions,
+                      attentions, &g, S2S_CELL_GRU, (hipStream_t)stream);
 }
 
 extern "C" int nir_acg_copy_loss_fwd(const float* logits, int64_t ld, const float* switch_logit, const float* copy_mass, const int64_t* target,

@@ -22,4 +22,28 @@ int launch_argmax_finish(const float* pval, const int* pidx, int nparts, int64_t
 // multiProcessorCount of the current device (256 if unknown)
 int device_cu_count();
 
+// One GRU decoder step (csrc/gru_step.hip).  Fast form (gru_step_fast): whh_frag, h16prev and h16next given, H % 32 == 0, tunable exact_f32 off --
+// one launch when gate_fold is given too, else the gathered input GEMM into `scratch` in front of it.  Plain form otherwise: exact fp32, three
+// launches through `scratch` (gru_step_scratch_floats), h16next filled behind them when given.  hnext must not alias hprev.
+struct GruStepArgs {
+    const int64_t* tok = nullptr;         // [B] token ids, already inside [0, V) (the fast form clamps what it gathers the table by all the same)
+    int64_t V = 0;
+    const float* gate_fold = nullptr;     // [V,3H] = table W_ih^T + b_ih + (b_hr, b_hz, 0), or NULL
+    const float* table = nullptr;         // [V,E] with wih [3H,E], bih [3H]: read when gate_fold is NULL or the plain form runs
+    int E = 0;
+    const float *wih = nullptr, *bih = nullptr;
+    const float *whh = nullptr, *bhh = nullptr;      // [3H,H], [3H]
+    const void* whh_frag = nullptr;       // nir_gru_step_pack_whh_frag(whh, H)
+    const float* hprev = nullptr;         // [B,H]
+    const _Float16* h16prev = nullptr;    // [B][H/8][2 terms][8]
+    float* hnext = nullptr;
+    _Float16* h16next = nullptr;
+    float* scratch = nullptr;
+    int64_t B = 0;
+    int H = 0;
+};
+bool gru_step_fast(const GruStepArgs& a);
+size_t gru_step_scratch_floats(int64_t B, int H);
+int launch_gru_step(const GruStepArgs& a, hipStream_t st);
+
 }  // namespace nir

@@ -213,10 +213,11 @@ int launch_acg_gen_select(const float* o, int64_t B, int K, const float* gen_w, 
                           float* pval, int* pidx, float* psum, const float* copy_w, const float* copy_b, const float* attn, int64_t attn_stride,
                           const int64_t* lens, int QL, const int64_t* src_map_idx, const int64_t* ext2tgt, const int64_t* ext2src, int CV,
                           const int64_t* tgt2src, int64_t V, int64_t* pred, int64_t pstride, int64_t* tgt, hipStream_t st);
-// csrc/seq2seq.hip: the greedy decode of Seq2seq (acg == NULL) and of ACG
-size_t s2s_decode_workspace_bytes(int64_t B, int QL, const nir_seq2seq_decoder_weights* w, const AcgDecode* acg);
+// csrc/seq2seq.hip: the greedy decode of Seq2seq (acg == NULL) and of ACG; cell: the decoder's recurrence
+constexpr int S2S_CELL_LSTM = 0, S2S_CELL_GRU = 1;
+size_t s2s_decode_workspace_bytes(int64_t B, int QL, const nir_seq2seq_decoder_weights* w, const AcgDecode* acg, int cell);
 int s2s_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, const float* table,
                int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len, const nir_seq2seq_decoder_weights* w, void* workspace,
-               size_t workspace_bytes, int64_t* predictions, float* attentions, const AcgDecode* acg, hipStream_t st);
+               size_t workspace_bytes, int64_t* predictions, float* attentions, const AcgDecode* acg, int cell, hipStream_t st);
 
 }  // namespace nir

@@ -132,14 +132,15 @@ struct S2sPlan {
     int* pidx;
     int64_t* tgt;
     float *psum, *csb, *cq, *ccat, *cattn;             // ACG only: the sums of the partials; a copy attention of its own
+    float* gru;                                        // GRU cell only: the gates of the plain step
     size_t bytes;
 };
 // acg: 0 = Seq2seq, 1 = ACG with reuse_copy_attn, 2 = ACG with a copy attention of its own
-static S2sPlan s2s_plan(void* ws, size_t cap, int64_t B, int QL, int H, int64_t VT, int attn_type, bool fused, int acg = 0) {
+static S2sPlan s2s_plan(void* ws, size_t cap, int64_t B, int QL, int H, int64_t VT, int attn_type, bool fused, int acg = 0, int cell = S2S_CELL_LSTM) {
     Workspace a(ws, cap);
     S2sPlan p;
     p.sb = a.take<float>(attn_type == NIR_S2S_ATTN_DOT ? 0 : (size_t)B * QL * H);
-    for (int k = 0; k < 2; ++k) { p.h[k] = a.take<float>((size_t)B * H); p.c[k] = a.take<float>((size_t)B * H); }
+    for (int k = 0; k < 2; ++k) { p.h[k] = a.take<float>((size_t)B * H); p.c[k] = a.take<float>(cell == S2S_CELL_GRU ? 0 : (size_t)B * H); }
     for (int k = 0; k < 2; ++k) p.h16[k] = a.take<float>((size_t)B * H);
     p.qh = a.take<float>(attn_type == NIR_S2S_ATTN_MLP ? (size_t)B * H : 0);
     p.cat = a.take<float>((size_t)B * 2 * H);
@@ -159,6 +160,7 @@ static S2sPlan s2s_plan(void* ws, size_t cap, int64_t B, int QL, int H, int64_t 
         p.ccat = a.take<float>((size_t)B * 2 * H);
         p.cattn = a.take<float>((size_t)B * QL);
     }
+    p.gru = cell == S2S_CELL_GRU ? a.take<float>(gru_step_scratch_floats(B, H)) : nullptr;
     p.bytes = align_up(a.off, 256);
     return p;
 }
@@ -182,9 +184,9 @@ static bool acg_weights_ok(const nir_seq2seq_decoder_weights* w, const AcgDecode
     return true;
 }
 
-size_t s2s_decode_workspace_bytes(int64_t B, int QL, const nir_seq2seq_decoder_weights* w, const AcgDecode* acg) {
+size_t s2s_decode_workspace_bytes(int64_t B, int QL, const nir_seq2seq_decoder_weights* w, const AcgDecode* acg, int cell) {
     if (!s2s_weights_ok(w) || B < 0 || QL <= 0 || (acg && !acg_weights_ok(w, acg))) return 0;
-    return s2s_plan(nullptr, 0, B, QL, w->H, w->VT, w->attn_type, s2s_fused(w), acg ? (acg->cw->reuse_copy_attn ? 1 : 2) : 0).bytes;
+    return s2s_plan(nullptr, 0, B, QL, w->H, w->VT, w->attn_type, s2s_fused(w), acg ? (acg->cw->reuse_copy_attn ? 1 : 2) : 0, cell).bytes;
 }
 
 }  // namespace nir
@@ -248,7 +250,7 @@ extern "C" int nir_seq2seq_attend(const float* q, const float* h, const float* m
 }
 
 extern "C" size_t nir_seq2seq_decode_workspace_bytes(int64_t B, int QL, const nir_seq2seq_decoder_weights* w) {
-    return nir::s2s_decode_workspace_bytes(B, QL, w, nullptr);
+    return nir::s2s_decode_workspace_bytes(B, QL, w, nullptr, nir::S2S_CELL_LSTM);
 }
 
 extern "C" int nir_seq2seq_decode_greedy(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B,
@@ -256,15 +258,31 @@ extern "C" int nir_seq2seq_decode_greedy(const float* dec_h, const float* dec_c,
                                          const nir_seq2seq_decoder_weights* w, void* workspace, size_t workspace_bytes, int64_t* predictions,
                                          float* attentions, nir_stream_t stream) {
     return nir::s2s_decode(dec_h, dec_c, memory_bank, source_len, B, QL, table, V, E, tgt2src, bos, max_len, w, workspace, workspace_bytes, predictions,
-                           attentions, nullptr, (hipStream_t)stream);
+                           attentions, nullptr, nir::S2S_CELL_LSTM, (hipStream_t)stream);
+}
+
+// The same decode with a GRU decoder (decoders/decoder.py:175-177, decoders/rnn_decoder.py:46-47): no cell state; rnn_* are [3H, .], rnn_gate_fold
+// and rnn_whh_frag the GRU forms (csrc/gru_step.hip).
+extern "C" size_t nir_seq2seq_gru_decode_workspace_bytes(int64_t B, int QL, const nir_seq2seq_decoder_weights* w) {
+    return nir::s2s_decode_workspace_bytes(B, QL, w, nullptr, nir::S2S_CELL_GRU);
+}
+
+extern "C" int nir_seq2seq_gru_decode_greedy(const float* dec_h, const float* memory_bank, const int64_t* source_len, int64_t B, int QL,
+                                             const float* table, int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len,
+                                             const nir_seq2seq_decoder_weights* w, void* workspace, size_t workspace_bytes, int64_t* predictions,
+                                             float* attentions, nir_stream_t stream) {
+    return nir::s2s_decode(dec_h, nullptr, memory_bank, source_len, B, QL, table, V, E, tgt2src, bos, max_len, w, workspace, workspace_bytes, predictions,
+                           attentions, nullptr, nir::S2S_CELL_GRU, (hipStream_t)stream);
 }
 
 // The decode of both attention recommenders: acg == NULL is Seq2seq's (generator + arg-max), otherwise ACG's, whose step ends in the copy
 // generator of csrc/acg.hip instead -- and, without reuse_copy_attn, runs a second attention on the attentional output in front of it.
+// cell: the decoder's recurrence, S2S_CELL_LSTM (launch_lstm_step) or S2S_CELL_GRU (launch_gru_step: dec_c unused, no c buffers).
 int nir::s2s_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, const float* table,
                     int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len, const nir_seq2seq_decoder_weights* w, void* workspace,
-                    size_t workspace_bytes, int64_t* predictions, float* attentions, const AcgDecode* acg, hipStream_t st) {
-    NIR_REQUIRE(dec_h && dec_c && memory_bank && source_len && table && w && predictions && attentions, "seq2seq_decode: null pointer");
+                    size_t workspace_bytes, int64_t* predictions, float* attentions, const AcgDecode* acg, int cell, hipStream_t st) {
+    const bool gru = cell == S2S_CELL_GRU;
+    NIR_REQUIRE(dec_h && (dec_c || gru) && memory_bank && source_len && table && w && predictions && attentions, "seq2seq_decode: null pointer");
     NIR_REQUIRE(s2s_weights_ok(w), "seq2seq_decode: decoder weights incomplete for the attention type, or H not a multiple of 4");
     NIR_REQUIRE(B >= 0 && QL > 0 && QL <= 4096 && max_len > 0 && V > 0 && E > 0 && E % 4 == 0, "seq2seq_decode: bad dims");
     NIR_REQUIRE(bos >= 0 && bos < V, "seq2seq_decode: BOS id outside the vocabulary");
@@ -278,7 +296,7 @@ int nir::s2s_decode(const float* dec_h, const float* dec_c, const float* memory_
         NIR_REQUIRE(acg->src_map_idx && acg->ext2tgt && acg->ext2src, "acg_decode: null index tensor");
         NIR_REQUIRE(acg_dims_ok(QL, acg->CV), "acg_decode: CV outside [2, %d]", ACG_MAX_CV);
     }
-    S2sPlan p = s2s_plan(workspace, workspace_bytes, B, QL, H, w->VT, w->attn_type, fused, acg ? (own_copy_attn ? 2 : 1) : 0);
+    S2sPlan p = s2s_plan(workspace, workspace_bytes, B, QL, H, w->VT, w->attn_type, fused, acg ? (own_copy_attn ? 2 : 1) : 0, cell);
     if (!workspace || p.bytes > workspace_bytes) {
         set_error("seq2seq_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
         return NIR_ERR_WORKSPACE;
@@ -307,7 +325,16 @@ int nir::s2s_decode(const float* dec_h, const float* dec_c, const float* memory_
     a.hprev[1] = a.cprev[1] = nullptr; a.hnext[1] = a.cnext[1] = nullptr;
     a.chain0 = 0; a.B = (int)B; a.I = E; a.H = H;
     const bool step16 = w->rnn_gate_fold && w->rnn_whh_frag && H % 32 == 0 && !tun(g_tun.exact_f32);
-    if (step16) {
+    GruStepArgs ga;
+    if (gru) {
+        ga.tok = p.tgt; ga.V = V; ga.table = table; ga.E = E;
+        ga.wih = w->rnn_wih; ga.bih = w->rnn_bih; ga.whh = w->rnn_whh; ga.bhh = w->rnn_bhh;
+        ga.scratch = p.gru; ga.B = B; ga.H = H;
+        if (step16) {
+            ga.gate_fold = w->rnn_gate_fold; ga.whh_frag = w->rnn_whh_frag;
+            NIR_PROPAGATE(launch_h16_pack(dec_h, B * H, reinterpret_cast<_Float16*>(p.h16[1]), st));
+        }
+    } else if (step16) {
         a.gx[0] = w->rnn_gate_fold; a.gxid[0] = p.tgt; a.gxstride = (int64_t)4 * H; a.gx_unit_major = 1;
         a.whh_frag[0] = w->rnn_whh_frag;
         NIR_PROPAGATE(launch_h16_pack(dec_h, B * H, reinterpret_cast<_Float16*>(p.h16[1]), st));
@@ -319,10 +346,15 @@ int nir::s2s_decode(const float* dec_h, const float* dec_c, const float* memory_
         float* cn = p.c[step & 1];
         a.hprev[0] = hp; a.cprev[0] = cp; a.hnext[0] = hn; a.cnext[0] = cn;
         if (step16) {
-            a.h16prev[0] = reinterpret_cast<const _Float16*>(p.h16[(step + 1) & 1]);
-            a.h16next[0] = reinterpret_cast<_Float16*>(p.h16[step & 1]);
+            a.h16prev[0] = ga.h16prev = reinterpret_cast<const _Float16*>(p.h16[(step + 1) & 1]);
+            a.h16next[0] = ga.h16next = reinterpret_cast<_Float16*>(p.h16[step & 1]);
         }
-        NIR_PROPAGATE(launch_lstm_step(a, 1, st));
+        if (gru) {
+            ga.hprev = hp; ga.hnext = hn;
+            NIR_PROPAGATE(launch_gru_step(ga, st));
+        } else {
+            NIR_PROPAGATE(launch_lstm_step(a, 1, st));
+        }
         if (mlp)
             NIR_PROPAGATE(launch_linear(hn, H, nullptr, nullptr, 0, 0, 0, w->attn_query_w, H, w->attn_query_b, nullptr, p.qh, H, B, H, H, NIR_ACT_NONE, st));
         NIR_PROPAGATE(launch_attend(mlp ? p.qh : hn, hn, memory_bank, sb, w->attn_v, source_len, B, QL, H, mlp, p.cat, attentions + (int64_t)step * QL,

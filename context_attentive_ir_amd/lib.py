@@ -300,6 +300,21 @@ SIGNATURES = {
     "nir_acg_copy_loss_bwd": (_i, [c_fp, _l, c_fp, c_fp, c_ip, c_ip, _i, c_fp, c_fp, _l, _i, c_fp, c_fp, c_fp, c_st]),
 }
 
+# The GRU decoders of Seq2seq and ACG, declared in include/neuroir_gru_decode.h (csrc/gru_step.hip, csrc/seq2seq.hip, csrc/acg.hip).  A table of
+# its own: SIGNATURES mirrors the declarations of neuroir_hip.h itself, whose per-family symbol lists are pinned by tests.
+GRU_DECODE_SIGNATURES = {
+    "nir_gru_step_whh_frag_bytes": (_z, [_i]),
+    "nir_gru_step_pack_whh_frag": (_i, [c_fp, _i, C.c_void_p, C.c_void_p, c_st]),
+    "nir_gru_step_workspace_bytes": (_z, [_l, _i]),
+    "nir_gru_step": (_i, [c_ip, _l, c_fp, _l, _i, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_void_p, _i, c_fp, C.c_void_p, c_fp, C.c_void_p, C.c_void_p, _z, c_st]),
+    "nir_seq2seq_gru_decode_workspace_bytes": (_z, [_l, _i, C.POINTER(Seq2seqDecoderWeights)]),
+    "nir_seq2seq_gru_decode_greedy": (_i, [c_fp, c_fp, c_ip, _l, _i, c_fp, _l, _i, c_ip, _l, _i, C.POINTER(Seq2seqDecoderWeights), C.c_void_p, _z,
+                                           c_ip, c_fp, c_st]),
+    "nir_acg_gru_decode_workspace_bytes": (_z, [_l, _i, _i, C.POINTER(Seq2seqDecoderWeights), C.POINTER(AcgCopyWeights)]),
+    "nir_acg_gru_decode_greedy": (_i, [c_fp, c_fp, c_ip, _l, _i, c_fp, _l, _i, c_ip, _l, _i, C.POINTER(Seq2seqDecoderWeights),
+                                       C.POINTER(AcgCopyWeights), c_ip, c_ip, c_ip, _i, C.c_void_p, _z, c_ip, c_fp, c_st]),
+}
+
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_SPLIT2 = 0, 1, 2
 DTYPES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "bf16": DTYPE_BF16, "f32_split2": DTYPE_F32_SPLIT2}
 
@@ -315,7 +330,7 @@ def load():
                 "libneuroir_hip.so not found at %s -- build it with `python -m context_attentive_ir_amd.build` "
                 "(hipcc, gfx950). The HIP path has no CPU fallback." % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(GRU_DECODE_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -29,13 +29,13 @@ class GlobalAttentionParams(nn.Module):
 
 
 class RNNDecoderParams(nn.Module):
-    """decoders/decoder.py:68-118: `rnn` = nn.LSTM(input_size -> hidden_size, num_layers), `attn` = GlobalAttention(hidden_size); attn_type
-    'none' (layers.py:70: HredQS) has no attention module and no attention parameters."""
+    """decoders/decoder.py:68-118: `rnn` = getattr(nn, rnn_type)(input_size -> hidden_size, num_layers), `attn` = GlobalAttention(hidden_size);
+    attn_type 'none' (layers.py:70: HredQS) has no attention module and no attention parameters."""
 
-    def __init__(self, input_size, nlayers, nhid, attn_type, dropout, copy_attn=False):
+    def __init__(self, input_size, nlayers, nhid, attn_type, dropout, copy_attn=False, rnn_type="LSTM"):
         super().__init__()
         self.hidden_size = nhid
-        self.rnn = nn.LSTM(input_size, nhid, nlayers, batch_first=True)
+        self.rnn = (nn.GRU if rnn_type == "GRU" else nn.LSTM)(input_size, nhid, nlayers, batch_first=True)
         if attn_type not in (None, "none"):
             self.attn = GlobalAttentionParams(nhid, attn_type)
         if copy_attn:                                   # decoders/decoder.py:113-116: ACG without reuse_copy_attn, a second attention of the same type
@@ -44,9 +44,9 @@ class RNNDecoderParams(nn.Module):
 
 
 class Decoder(nn.Module):
-    def __init__(self, input_size, nlayers, nhid, attn_type, dropout_rnn, copy_attn=False):
+    def __init__(self, input_size, nlayers, nhid, attn_type, dropout_rnn, copy_attn=False, rnn_type="LSTM"):
         super().__init__()
-        self.decoder = RNNDecoderParams(input_size, nlayers, nhid, attn_type, dropout_rnn, copy_attn)
+        self.decoder = RNNDecoderParams(input_size, nlayers, nhid, attn_type, dropout_rnn, copy_attn, rnn_type)
 
 
 class CopyGeneratorParams(nn.Module):
@@ -93,3 +93,18 @@ def encode_train(rnn, x, lens):
         hs.append(hr[rows, last])                                        # after the whole valid part, read backwards
         cs.append(cr[rows, last])
     return torch.cat(banks, 2), torch.cat(hs, 1), torch.cat(cs, 1)
+
+
+def encode_train_gru(rnn, x, lens):
+    """x [B,T,E] through the single-layer nn.GRU container `rnn` -> (memory bank [B,T,nhid], zero beyond each length; h_n [B,nhid]) in ORIGINAL
+    row order, differentiable (autograd.bigru).  The final state is read from the bank: the forward half at position len - 1, the reverse
+    half at position 0."""
+    from .. import autograd as A
+    H = rnn.hidden_size
+    B = x.shape[0]
+    bank = A.bigru(x, lens, rnn)
+    last = (lens - 1).clamp(min=0)
+    hs = [bank[torch.arange(B, device=x.device), last, :H]]
+    if rnn.bidirectional:
+        hs.append(bank[:, 0, H:])
+    return bank, torch.cat(hs, 1)

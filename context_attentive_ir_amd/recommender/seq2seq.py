@@ -26,10 +26,11 @@ from ..multitask import suggest
 from .layers import ATTN_TYPES, Decoder, Embedder, Encoder, encode_train
 
 
-def check_supported(args, what):
-    """the configurations both attention recommenders refuse"""
-    if args.rnn_type != "LSTM":
-        raise NotImplementedError("HIP %s implements rnn_type 'LSTM' (got %r); GRU decoders are a follow-up of their own" % (what, args.rnn_type))
+def check_supported(args, what, rnn_type="LSTM"):
+    """the configurations both attention recommenders refuse (`rnn_type`: the cell the class is built for)"""
+    if args.rnn_type != rnn_type:
+        raise NotImplementedError("HIP %s implements rnn_type %r (got %r); the GRU decoders are recommender.Seq2seqGRU / recommender.ACGGRU "
+                                  "(wrappers.Recommender / CopyRecommender pick them by args.rnn_type)" % (what, rnn_type, args.rnn_type))
     if args.attn_type not in ATTN_TYPES:
         raise NotImplementedError("HIP %s implements attn_type %s (got %r)" % (what, ", ".join(ATTN_TYPES), args.attn_type))
 
@@ -38,7 +39,7 @@ def build_network(net, args, own_copy_attn=False):
     """the modules and attributes Seq2seq and ACG share (seq2seq.py:14-39), in the reference's registration order"""
     net.embedder = Embedder(args.emsize, args.src_vocab_size, args.dropout_emb)
     net.encoder = Encoder(args.rnn_type, args.emsize, args.bidirection, args.nlayers, args.nhid, args.dropout_rnn)
-    net.decoder = Decoder(args.emsize, args.nlayers, args.nhid, args.attn_type, args.dropout_rnn, own_copy_attn)
+    net.decoder = Decoder(args.emsize, args.nlayers, args.nhid, args.attn_type, args.dropout_rnn, own_copy_attn, args.rnn_type)
     net.dropout = nn.Dropout(args.dropout)
     net.generator = nn.Linear(args.nhid, args.tgt_vocab_size)
     net.attn_type, net.nlayers, net.nhid = args.attn_type, int(args.nlayers), int(args.nhid)

@@ -5,10 +5,12 @@ their session axis; CopyRecommender is the same wrapper for ACG, whose batches c
 import torch
 
 from ..constants import BOS, EOS, PAD, UNK_WORD
-from ..recommender import ACG, HredQS, Seq2seq
+from ..recommender import ACG, ACGGRU, HredQS, Seq2seq, Seq2seqGRU
 from .common import WrapperBase
 
 NETWORKS = {"SEQ2SEQ": Seq2seq}
+# args.rnn_type 'GRU' (config.py:53) builds the GRU-decoder class of the model; any other value goes to the LSTM class, which refuses what it is not
+GRU_NETWORKS = {"SEQ2SEQ": Seq2seqGRU, "ACG": ACGGRU}
 FOLLOW_UPS = {"ACG": "ACG's batches carry src_map / alignment / src_vocab: build it with wrappers.CopyRecommender (registering it here is its own "
                      "follow-up)",
               "HREDQS": "HredQS keeps the session axis of its batches: build it with wrappers.SessionRecommender (registering it here is its own "
@@ -37,7 +39,7 @@ class Recommender(WrapperBase):
             raise NotImplementedError("HIP Recommender: model_type %s is not built yet -- %s" % (self.type, FOLLOW_UPS[self.type]))
         if self.type not in NETWORKS:
             raise RuntimeError("Unsupported model: %s (recommender models on the HIP path: %s)" % (self.args.model_type, sorted(NETWORKS)))
-        return NETWORKS[self.type]
+        return GRU_NETWORKS[self.type] if getattr(self.args, "rnn_type", "LSTM") == "GRU" else NETWORKS[self.type]
 
     def _dev(self, t):
         return t.cuda(non_blocking=True) if self.use_cuda else t
@@ -229,7 +231,7 @@ class CopyRecommender(Recommender):
     def _network_class(self):
         if self.type != "ACG":
             raise RuntimeError("Unsupported model: %s (CopyRecommender builds ACG; Recommender builds %s)" % (self.args.model_type, sorted(NETWORKS)))
-        return ACG
+        return GRU_NETWORKS["ACG"] if getattr(self.args, "rnn_type", "LSTM") == "GRU" else ACG
 
     @staticmethod
     def _rows_of(lists, width):

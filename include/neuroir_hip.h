@@ -1131,6 +1131,10 @@ int nir_acg_copy_loss_bwd(const float* logits, int64_t ld, const float* switch_l
                           const int64_t* align, int force_copy, const float* lse, const float* grad_loss, int64_t R, int V, float* dlogits,
                           float* dswitch, float* dmass, nir_stream_t stream);
 
+/* The GRU decoders of Seq2seq and ACG (one step, and the two greedy decodes with it) are declared in a header of their own, part of this
+ * ABI (ctypes: lib.GRU_DECODE_SIGNATURES): this file's per-family symbol lists are pinned by tests that predate them. */
+#include "neuroir_gru_decode.h"
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,9 @@ the reference's loader guarantees); words of the first tgt_vocab_size source ids
 Prints one JSON line: ms per batch (median of --iters, CUDA events, after --warmup; the calls replay the captured predict graph) per round of
 --rounds alternating rounds and the medians over the rounds, whether the fused and plain tokens agree, and the share of copied words.
 
-    python tools/acg_bench.py [--B 64] [--iters 20] [--warmup 5] [--rounds 3] [--json out.json]
+--rnn_type GRU builds ACGGRU / Seq2seqGRU (csrc/gru_step.hip) instead.
+
+    python tools/acg_bench.py [--rnn_type LSTM|GRU] [--B 64] [--iters 20] [--warmup 5] [--rounds 3] [--json out.json]
 """
 import argparse
 import json
@@ -33,6 +35,7 @@ def main():
     ap.add_argument("--emsize", type=int, default=300)
     ap.add_argument("--nhid", type=int, default=512)
     ap.add_argument("--max_len", type=int, default=20)
+    ap.add_argument("--rnn_type", default="LSTM", choices=["LSTM", "GRU"])
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3, help="alternating repeats of the timings; the spread of their medians is reported")
@@ -43,7 +46,7 @@ def main():
     from context_attentive_ir_amd.wrappers import CopyRecommender, Recommender
     rng = np.random.default_rng(1)
     src_dict = [int(x) for x in rng.integers(4, a.V, size=a.V)]             # src_dict[tgt_dict[i]]: tgt_dict = identity
-    kw = dict(emsize=a.emsize, nhid=a.nhid, nlayers=1, max_query_len=a.max_len, tgt_vocab_size=a.VT)
+    kw = dict(emsize=a.emsize, nhid=a.nhid, nlayers=1, max_query_len=a.max_len, tgt_vocab_size=a.VT, rnn_type=a.rnn_type)
     acg = CopyRecommender(default_args("ACG", **kw), src_dict, list(range(a.VT)))
     s2s = Recommender(default_args("SEQ2SEQ", **kw), src_dict, list(range(a.VT)))
     for r in (acg, s2s):
@@ -87,7 +90,7 @@ def main():
             p_plain = copy().clone()
             s2s_r.append(timed(plain_s2s, a.iters, a.warmup))
     fused, plain, base = (float(np.median(v)) for v in (fused_r, plain_r, s2s_r))
-    out = dict(model="acg", B=a.B, QL=a.ql, CV=CV, emsize=a.emsize, nhid=a.nhid, V=a.V, VT=a.VT, max_len=a.max_len,
+    out = dict(model="acg", rnn_type=a.rnn_type, B=a.B, QL=a.ql, CV=CV, emsize=a.emsize, nhid=a.nhid, V=a.V, VT=a.VT, max_len=a.max_len,
                ms_per_batch=round(fused, 4), plain_ms_per_batch=round(plain, 4), seq2seq_ms_per_batch=round(base, 4),
                ms_rounds=[round(v, 4) for v in fused_r], plain_ms_rounds=[round(v, 4) for v in plain_r], seq2seq_ms_rounds=[round(v, 4) for v in s2s_r],
                copy_step_ms=round(fused - base, 4), tokens_equal_fused_plain=float((p_fused == p_plain).float().mean()),

@@ -8,10 +8,11 @@ with two things in its favour: the source lengths are handed over as a host list
 the token map is a device lookup table (the reference loops over `.item()` and two Python dicts on the host every step).
 
 Prints one JSON line: ms per batch (median of --iters, CUDA events, after --warmup) of predict() with the fused generator + arg-max kernel,
-of predict() with the unfused generator (fp32 GEMM + arg-max kernel) and of the torch composition, each per round of --rounds alternating
-rounds, the medians over the rounds, the speed-up, and whether the tokens of the three paths agree.
+of predict() with the unfused generator (fp32 GEMM + arg-max kernel), of predict() with the plain decoder step (fold_decoder_step off) and
+of the torch composition, each per round of --rounds alternating rounds, the medians over the rounds, the speed-up, and whether the tokens
+of the paths agree.  --rnn_type GRU times Seq2seqGRU (csrc/gru_step.hip) against nn.GRU the same way.
 
-    python tools/seq2seq_bench.py [--iters 20] [--warmup 5] [--rounds 3] [--json out.json]
+    python tools/seq2seq_bench.py [--rnn_type LSTM|GRU] [--iters 20] [--warmup 5] [--rounds 3] [--json out.json]
 """
 import argparse
 import json
@@ -33,9 +34,10 @@ def torch_decode(net, src, lens, lens_host, lut, max_len):
     att = net.decoder.decoder.attn
     order = torch.sort(lens, 0, True)[1]
     packed = pack_padded_sequence(torch.nn.functional.embedding(src, table)[order], sorted(lens_host, reverse=True), batch_first=True)
-    out, (hn, cn) = net.encoder.encoder.rnns[0](packed)
+    out, final = net.encoder.encoder.rnns[0](packed)
     bank = pad_packed_sequence(out, batch_first=True)[0][torch.sort(order, 0)[1]]           # un-sorted; the states stay sorted (rnn_encoder.py:104-113)
-    state = tuple(torch.cat([s[0:s.size(0):2], s[1:s.size(0):2]], 2) for s in (hn, cn))
+    halves = lambda s: torch.cat([s[0:s.size(0):2], s[1:s.size(0):2]], 2)                    # noqa: E731  (decoders/decoder.py:163-177)
+    state = tuple(halves(s) for s in final) if isinstance(final, tuple) else halves(final)
     mask = torch.arange(bank.shape[1], device=src.device).unsqueeze(0) < lens.unsqueeze(1)
     tok = torch.full((src.shape[0], 1), 2, dtype=torch.long, device=src.device)
     preds = []
@@ -60,6 +62,7 @@ def main():
     ap.add_argument("--emsize", type=int, default=300)
     ap.add_argument("--nhid", type=int, default=512)
     ap.add_argument("--max_len", type=int, default=20)
+    ap.add_argument("--rnn_type", default="LSTM", choices=["LSTM", "GRU"])
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3, help="alternating repeats of the timings; the spread of their medians is reported")
@@ -71,7 +74,7 @@ def main():
     rng = np.random.default_rng(1)
     # src_dict[tgt_dict[i]]: tgt_dict = identity, src_dict = a random map into the source vocabulary (its first VT entries are the ones looked up)
     src_dict = [int(x) for x in rng.integers(4, a.V, size=a.V)]
-    r = Recommender(default_args("SEQ2SEQ", emsize=a.emsize, nhid=a.nhid, nlayers=1, max_query_len=a.max_len), src_dict, list(range(a.VT)))
+    r = Recommender(default_args("SEQ2SEQ", emsize=a.emsize, nhid=a.nhid, nlayers=1, max_query_len=a.max_len, rnn_type=a.rnn_type), src_dict, list(range(a.VT)))
     fill_module_(r.network, 1013)
     r.cuda()
     r.predict_graph_min_calls = 2          # the timed calls replay the captured graph (the default captures at the eighth sighting of a shape)
@@ -87,11 +90,11 @@ def main():
     def ours():
         return r.predict(ex)["prediction_ids"]
 
-    def flavour(fuse):
-        net.fuse_generator_argmax = fuse             # (part of the graph cache's key: the next call captures the other path)
+    def flavour(fuse, fold=True):
+        net.fuse_generator_argmax, net.fold_decoder_step = fuse, fold             # (part of the pack's key: the next call captures the other path)
 
     with torch.no_grad():
-        fused_r, plain_r, ref_r = [], [], []
+        fused_r, plain_r, step_r, ref_r = [], [], [], []
         for _ in range(max(1, a.rounds)):                    # the paths alternate, so that drift of the machine meets all of them
             flavour(True)
             fused_r.append(timed(ours, a.iters, a.warmup))
@@ -99,11 +102,16 @@ def main():
             flavour(False)
             plain_r.append(timed(ours, a.iters, a.warmup))
             p_plain = ours().clone()
+            flavour(True, False)
+            step_r.append(timed(ours, a.iters, a.warmup))
+            p_step = ours().clone()
             ref_r.append(timed(lambda: torch_decode(net, srcd, lensd, lens_host, lut, a.max_len), a.iters, a.warmup))
         p_ref = torch_decode(net, srcd, lensd, lens_host, lut, a.max_len)
-    fused, plain, ref = (float(np.median(v)) for v in (fused_r, plain_r, ref_r))
-    out = dict(model="seq2seq", B=a.B, QL=a.ql, emsize=a.emsize, nhid=a.nhid, V=a.V, VT=a.VT, max_len=a.max_len,
+    fused, plain, step, ref = (float(np.median(v)) for v in (fused_r, plain_r, step_r, ref_r))
+    out = dict(model="seq2seq", rnn_type=a.rnn_type, B=a.B, QL=a.ql, emsize=a.emsize, nhid=a.nhid, V=a.V, VT=a.VT, max_len=a.max_len,
                ms_per_batch=round(fused, 4), unfused_ms_per_batch=round(plain, 4), torch_ms_per_batch=round(ref, 4),
+               plain_step_ms_per_batch=round(step, 4), plain_step_ms_rounds=[round(v, 4) for v in step_r],
+               tokens_equal_plain_step=float((p_fused == p_step).float().mean()),
                ms_rounds=[round(v, 4) for v in fused_r], unfused_ms_rounds=[round(v, 4) for v in plain_r], torch_ms_rounds=[round(v, 4) for v in ref_r],
                speedup=round(ref / fused, 2), unfused_speedup=round(ref / plain, 2),
                tokens_equal_fused_unfused=float((p_fused == p_plain).float().mean()), tokens_equal_torch=float((p_fused == p_ref).float().mean()))
