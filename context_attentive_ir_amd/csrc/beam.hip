@@ -1,0 +1,703 @@
+// Beam search for the Seq2seq recommenders (include/neuroir_beam.h).  The reference has the state helpers of a beam
+// (decoders/state.py:16-31 beam_update, :65-69 repeat_beam_size_times) and no search; they fix the row layout row = k B + b and the shuffle
+// new[k] = old[backptr[b, k]].  Per step, for all R = B W decode rows at once:
+//   (h,c) = cell(emb(tok), (h,c)); attention over source row `row % B` (the banks are not repeated); o = linear_out([ctx ; h])    as csrc/seq2seq.hip
+//   per row: lse and the W largest of y = W_g o + b_g         beam_gen_topk_kernel (the logits never leave the chip), or GEMM + beam_row_topk_kernel
+//   per source row: the W best of the <= W W live candidates cum + (y - lse) and the frozen ones (finished beams)            beam_select_kernel
+//   state rows gathered by the back-pointers                                                                                beam_reorder_kernel
+// and once behind the loop beam_backtrack_kernel walks the stored back-pointers.  The global top-W over (k, v) lies inside the per-row top-W of
+// the raw logits, since lse is constant within a row.  Everything is enqueued on the caller's stream; no host synchronisation, no allocation,
+// no float atomics, every reduction in a fixed order.
+#include <mutex>
+#include "s2s_gen.hpp"
+
+namespace nir {
+
+constexpr int BEAM_NONE = 0x7FFFFFFF;                 // the index of an empty list slot
+
+// ---- sorted top-W lists on registers ---------------------------------------------------------------------------------------------------
+// (a, ai) in front of (b, bi): the larger value, the smaller index among equals
+__device__ __forceinline__ bool beam_before(float a, int ai, float b, int bi) { return a > b || (a == b && ai < bi); }
+
+// Insert (y, v) into the descending list tv / ti.  Fully unrolled compare-exchange on constant indices: the lists stay in registers.
+// TOTAL = false: values arrive in ascending index order, a plain `>` keeps the first index in front.  TOTAL = true: any arrival order.
+template <int WM, bool TOTAL>
+__device__ __forceinline__ void beam_insert(float (&tv)[WM], int (&ti)[WM], float y, int v) {
+#pragma unroll
+    for (int j = WM - 1; j >= 0; --j) {
+        const bool here = TOTAL ? beam_before(y, v, tv[j], ti[j]) : y > tv[j];
+        bool above = false;
+        if (j > 0) above = TOTAL ? beam_before(y, v, tv[j - 1], ti[j - 1]) : y > tv[j - 1];
+        const float pv = j > 0 ? tv[j - 1] : 0.f;
+        const int pi = j > 0 ? ti[j - 1] : 0;
+        tv[j] = above ? pv : (here ? y : tv[j]);
+        ti[j] = above ? pi : (here ? v : ti[j]);
+    }
+}
+template <int WM>
+__device__ __forceinline__ void beam_pop(float (&tv)[WM], int (&ti)[WM], bool pop) {
+#pragma unroll
+    for (int j = 0; j < WM; ++j) {
+        const float nv = j + 1 < WM ? tv[j + 1 < WM ? j + 1 : j] : -INFINITY;
+        const int ni = j + 1 < WM ? ti[j + 1 < WM ? j + 1 : j] : BEAM_NONE;
+        tv[j] = pop ? nv : tv[j];
+        ti[j] = pop ? ni : ti[j];
+    }
+}
+
+template <int CTRL>
+__device__ __forceinline__ int dpp_mov_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
+__device__ __forceinline__ int wave_min_i(int v) {
+    v = min(v, dpp_mov_i<0xB1>(v));
+    v = min(v, dpp_mov_i<0x4E>(v));
+    v = min(v, dpp_mov_i<0x141>(v));
+    v = min(v, dpp_mov_i<0x140>(v));
+    return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)), min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
+}
+
+// ---- generator + bias + (lse, top-W): logits[b, v] = x[b, :] . W[v, :] + bias[v] never leave the chip --------------------------------------
+// The staging, tiling, fragment format and chunked prefetch of s2s_gen_argmax_kernel (s2s_gen.hpp), restated here: moving them into shared
+// inline helpers changes the register allocation and schedule of the greedy kernel, whose code is to stay as it is -- a change to the
+// staging, the chunk clamp or the walk has to be made in both.  In the place of its (best, index) every
+// lane keeps, per batch tile, the online-softmax pair (max, sum) and a sorted list of its WM largest biased logits with their indices: one
+// threshold test per value, an insertion only when it passes.  The four lanes of a decode row are merged in the wave (WM rounds: the best of
+// the four heads wins, its owner pops); every wave writes one partial per decode row -- pval / pidx [part][Bd][W], pm / ps [part][Bd] -- and
+// beam_merge_row reduces the partials of all waves and workgroups.
+template <int NBT, int WM>
+__global__ __launch_bounds__(256, 1) void beam_gen_topk_kernel(const float* __restrict__ x, const _Float16* __restrict__ wfrag,
+                                                               const float* __restrict__ bias, int64_t VT, int64_t ntiles, int64_t Bd, int K, int nvr,
+                                                               int W, float* __restrict__ pval, int* __restrict__ pidx, float* __restrict__ pm,
+                                                               float* __restrict__ ps) {
+    extern __shared__ __attribute__((aligned(16))) _Float16 beam_sm[];         // [2 terms][ROWS][LD]
+    constexpr int ROWS = 16 * NBT;
+    const int LD = K + 8, KS = K / 32, K4 = K / 4;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c16 = lane & 15, g4 = lane >> 4;
+    const int vr = (int)(blockIdx.x % nvr);
+    const int64_t b0 = (int64_t)(blockIdx.x / nvr) * ROWS;
+    const int64_t per_wg = (ntiles + nvr - 1) / nvr;
+    const int64_t t_lo = (int64_t)vr * per_wg, t_hi = min(ntiles, t_lo + per_wg);
+    {
+        constexpr int SB = 8;                                                     // loads in flight before the first is converted
+        const int total = ROWS * K4;                                              // a multiple of 256
+        for (int e0 = tid; e0 < total; e0 += 256 * SB) {
+            float4 sv[SB];
+#pragma unroll
+            for (int q = 0; q < SB; ++q) {
+                const int e = min(e0 + 256 * q, total - 1);
+                const int r = e / K4, k4 = (e - r * K4) * 4;
+                const int64_t b = b0 + r;
+                sv[q] = *reinterpret_cast<const float4*>(x + (b < Bd ? b : Bd - 1) * K + k4);
+            }
+#pragma unroll
+            for (int q = 0; q < SB; ++q) {
+                const int e = e0 + 256 * q;
+                if (e < total) {
+                    const int r = e / K4, k4 = (e - r * K4) * 4;
+                    float4 v = sv[q];
+                    if (b0 + r >= Bd) v = make_float4(0.f, 0.f, 0.f, 0.f);
+                    const Split2x4 sp = split2(v);
+                    _Float16* d = beam_sm + r * LD + k4;
+                    *reinterpret_cast<uint2*>(d) = sp.hi;
+                    *reinterpret_cast<uint2*>(d + ROWS * LD) = sp.lo;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    float tv[NBT][WM], rm[NBT], rs[NBT];
+    int ti[NBT][WM];
+#pragma unroll
+    for (int bt = 0; bt < NBT; ++bt) {
+        rm[bt] = -INFINITY;
+        rs[bt] = 0.f;
+#pragma unroll
+        for (int j = 0; j < WM; ++j) { tv[bt][j] = -INFINITY; ti[bt][j] = BEAM_NONE; }
+    }
+    const int NCH = (KS + S2S_KC - 1) / S2S_KC;
+    const int64_t first = t_lo + wave;
+    const int64_t nt = first < t_hi ? (t_hi - first + 3) / 4 : 0;             // this wave's tiles: first, first + 4, ...
+    const int64_t items = nt * NCH;                                           // (tile, chunk) pairs, in order
+    f32x4 acc[NBT], acx[NBT];
+    auto load_w = [&](int64_t it, f16x8 (&wf)[S2S_KC][2]) {
+        const int64_t t = first + 4 * (it / NCH);
+        const int c = (int)(it % NCH);
+#pragma unroll
+        for (int u = 0; u < S2S_KC; ++u) {
+            const int ks = min(c * S2S_KC + u, KS - 1);                       // clamped: a duplicate k-step is not multiplied below
+            const _Float16* wp = wfrag + ((t * KS + ks) * 2 * 64 + lane) * 8;
+            wf[u][0] = *reinterpret_cast<const f16x8*>(wp);
+            wf[u][1] = *reinterpret_cast<const f16x8*>(wp + 512);
+        }
+    };
+    const _Float16* bp0 = beam_sm + c16 * LD + 8 * g4;
+    auto compute = [&](int64_t it, const f16x8 (&wf)[S2S_KC][2]) {
+        const int64_t t = first + 4 * (it / NCH);
+        const int c = (int)(it % NCH);
+        if (c == 0) {
+#pragma unroll
+            for (int bt = 0; bt < NBT; ++bt) { acc[bt] = (f32x4){0.f, 0.f, 0.f, 0.f}; acx[bt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+        }
+#pragma unroll
+        for (int u = 0; u < S2S_KC; ++u) {
+            const int ks = c * S2S_KC + u;
+            if (ks < KS) {                                                    // wave-uniform
+                f16x8 b[NBT][2];
+#pragma unroll
+                for (int bt = 0; bt < NBT; ++bt) {
+                    b[bt][0] = *reinterpret_cast<const f16x8*>(bp0 + 32 * ks + bt * 16 * LD);
+                    b[bt][1] = *reinterpret_cast<const f16x8*>(bp0 + 32 * ks + bt * 16 * LD + ROWS * LD);
+                }
+#pragma unroll
+                for (int bt = 0; bt < NBT; ++bt) acx[bt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][1], b[bt][0], acx[bt], 0, 0, 0);
+#pragma unroll
+                for (int bt = 0; bt < NBT; ++bt) acc[bt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][0], b[bt][0], acc[bt], 0, 0, 0);
+#pragma unroll
+                for (int bt = 0; bt < NBT; ++bt) acx[bt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][0], b[bt][1], acx[bt], 0, 0, 0);
+            }
+        }
+        if (c == NCH - 1) {
+            const int64_t v0 = t * 16 + 4 * g4;
+            float bv[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) bv[r] = (bias && v0 + r < VT) ? bias[v0 + r] : 0.f;
+#pragma unroll
+            for (int bt = 0; bt < NBT; ++bt) {
+                float y[4];
+                float m = rm[bt];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    y[r] = fmaf(acx[bt][r], SPLIT2_INV, acc[bt][r]) + bv[r];  // the greedy kernel's expression: W = 1 picks its token
+                    if (v0 + r >= VT) y[r] = -INFINITY;                       // padded tile rows: never kept, add exp(-inf) = 0
+                    m = fmaxf(m, y[r]);
+                }
+                if (m > -INFINITY) {
+                    rs[bt] = rs[bt] * __expf(rm[bt] - m) + ((__expf(y[0] - m) + __expf(y[1] - m)) + (__expf(y[2] - m) + __expf(y[3] - m)));
+                    rm[bt] = m;
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r)                                   // ascending in r: '>' keeps the first index in front
+                    if (y[r] > tv[bt][WM - 1]) beam_insert<WM, false>(tv[bt], ti[bt], y[r], (int)(v0 + r));
+            }
+        }
+    };
+    {
+        f16x8 wfA[S2S_KC][2], wfB[S2S_KC][2];
+        if (items > 0) load_w(0, wfA);
+        for (int64_t it = 0; it < items; it += 2) {
+            if (it + 1 < items) load_w(it + 1, wfB);
+            compute(it, wfA);
+            if (it + 1 >= items) break;
+            if (it + 2 < items) load_w(it + 2, wfA);
+            compute(it + 1, wfB);
+        }
+    }
+    // lanes l, l + 16, l + 32, l + 48 hold the same decode row: the sums combine (under fp contraction the two lanes of a pair may differ in the
+    // last bit; only the g4 == 0 lane's value is written), the lists merge head by head by comparisons alone
+#pragma unroll
+    for (int bt = 0; bt < NBT; ++bt) {
+#pragma unroll
+        for (int sh = 16; sh <= 32; sh <<= 1) {
+            const float om = __shfl_xor(rm[bt], sh), os = __shfl_xor(rs[bt], sh);
+            const float m = fmaxf(om, rm[bt]);
+            rs[bt] = m > -INFINITY ? rs[bt] * __expf(rm[bt] - m) + os * __expf(om - m) : 0.f;
+            rm[bt] = m;
+        }
+        const int64_t b = b0 + bt * 16 + c16;
+        const int64_t slot = ((int64_t)vr * 4 + wave) * Bd + b;
+        const bool writer = g4 == 0 && b < Bd;
+        if (writer) { pm[slot] = rm[bt]; ps[slot] = rs[bt]; }
+#pragma unroll
+        for (int j = 0; j < WM; ++j) {
+            const float hv = tv[bt][0];
+            const int hi = ti[bt][0];
+            float wv = hv;
+            int wi = hi;
+#pragma unroll
+            for (int sh = 16; sh <= 32; sh <<= 1) {
+                const float ov = __shfl_xor(wv, sh);
+                const int oi = __shfl_xor(wi, sh);
+                if (beam_before(ov, oi, wv, wi)) { wv = ov; wi = oi; }
+            }
+            beam_pop<WM>(tv[bt], ti[bt], hv == wv && hi == wi);
+            if (writer && j < W) { pval[slot * W + j] = wv; pidx[slot * W + j] = wi; }
+        }
+    }
+}
+
+// ---- partial lists of one row -> (lse, top-W), one wave ------------------------------------------------------------------------------------
+// pval / pidx [part][rows][stride] (the first W of a list are read), pm / ps [part][rows] (ps NULL: every sum is 1, so a single part with
+// pm = lse passes through bit for bit).  Lane l takes parts l, l + 64, ... in order; the wave's maxima and sums combine through wave_max /
+// wave_sum (a fixed tree) and the lists through W rounds of (largest head, smallest index among equals, its owner pops).
+// Lane 0 writes out_val / out_idx [W] and *out_lse.
+__device__ __forceinline__ void beam_merge_row(const float* pval, const int* pidx, const float* pm, const float* ps, int nparts, int64_t rows,
+                                               int64_t row, int stride, int W, int lane, float* out_val, int* out_idx, float* out_lse) {
+    constexpr int WM = NIR_BEAM_MAX_W;
+    float tv[WM];
+    int ti[WM];
+#pragma unroll
+    for (int j = 0; j < WM; ++j) { tv[j] = -INFINITY; ti[j] = BEAM_NONE; }
+    float m = -INFINITY, s = 0.f;
+    for (int p = lane; p < nparts; p += 64) {
+        const int64_t slot = (int64_t)p * rows + row;
+        const float om = pm[slot], os = ps ? ps[slot] : 1.f;
+        const float nm = fmaxf(m, om);
+        if (nm > -INFINITY) s = s * expf(m - nm) + os * expf(om - nm);
+        m = nm;
+        for (int j = 0; j < W; ++j) {
+            const float y = pval[slot * stride + j];
+            const int v = pidx[slot * stride + j];
+            if (beam_before(y, v, tv[WM - 1], ti[WM - 1])) beam_insert<WM, true>(tv, ti, y, v);
+        }
+    }
+    const float M = wave_max(m);
+    const float S = wave_sum(m > -INFINITY ? s * expf(m - M) : 0.f);
+    if (lane == 0) *out_lse = M + logf(S);
+    for (int j = 0; j < W; ++j) {
+        const float hv = tv[0];
+        const int hi = ti[0];
+        const float mx = wave_max(hv);
+        const int mi = wave_min_i(hv == mx ? hi : BEAM_NONE);
+        beam_pop<WM>(tv, ti, hv == mx && hi == mi);
+        if (lane == 0) { out_val[j] = mx; out_idx[j] = mi; }
+    }
+}
+
+__global__ __launch_bounds__(64) void beam_topk_finish_kernel(const float* __restrict__ pval, const int* __restrict__ pidx, const float* __restrict__ pm,
+                                                              const float* __restrict__ ps, int nparts, int64_t rows, int W,
+                                                              float* __restrict__ top_val, int* __restrict__ top_idx, float* __restrict__ lse) {
+    const int64_t row = blockIdx.x;
+    beam_merge_row(pval, pidx, pm, ps, nparts, rows, row, W, W, threadIdx.x, top_val + row * W, top_idx + row * W, lse + row);
+}
+
+// ---- plain form: one workgroup per row of [rows, VT] logits -> (lse, top-W), the same tie rule ---------------------------------------------
+__global__ __launch_bounds__(256) void beam_row_topk_kernel(const float* __restrict__ logits, int64_t VT, int W, float* __restrict__ top_val,
+                                                            int* __restrict__ top_idx, float* __restrict__ lse) {
+    constexpr int WM = NIR_BEAM_MAX_W;
+    __shared__ float lv[256 * WM];
+    __shared__ int li[256 * WM];
+    __shared__ float lm[256], ls[256];
+    const int64_t row = blockIdx.x;
+    const int tid = threadIdx.x;
+    const float* y = logits + row * VT;
+    float tv[WM];
+    int ti[WM];
+#pragma unroll
+    for (int j = 0; j < WM; ++j) { tv[j] = -INFINITY; ti[j] = BEAM_NONE; }
+    float m = -INFINITY, s = 0.f;
+    for (int64_t v = tid; v < VT; v += 256) {                                 // ascending: '>' keeps the first index in front
+        const float a = y[v];
+        const float nm = fmaxf(m, a);
+        if (nm > -INFINITY) s = s * expf(m - nm) + expf(a - nm);
+        m = nm;
+        if (a > tv[WM - 1]) beam_insert<WM, false>(tv, ti, a, (int)v);
+    }
+#pragma unroll
+    for (int j = 0; j < WM; ++j) { lv[tid * WM + j] = tv[j]; li[tid * WM + j] = ti[j]; }
+    lm[tid] = m;
+    ls[tid] = s;
+    __syncthreads();
+    if (tid < 64) beam_merge_row(lv, li, lm, ls, 256, 1, 0, WM, W, tid, top_val + row * W, top_idx + row * W, lse + row);
+}
+
+// ---- selection: one wave per source row ----------------------------------------------------------------------------------------------------
+// Per beam k of source row b (decode row k B + b): the partials merge to lse and the top-W logits; lane k W + j then holds candidate j of
+// beam k -- live: cum[b, k] + (y - lse), token v; finished: j = 0 alone, (cum[b, k], EOS).  W rounds pick (score descending, k ascending, v
+// ascending: the flat index k VT + v).  cum and finished are read before anything is written, so they update in place.
+__global__ __launch_bounds__(64) void beam_select_kernel(const float* __restrict__ pval, const int* __restrict__ pidx, const float* __restrict__ pm,
+                                                         const float* __restrict__ ps, int nparts, int64_t B, int W, int64_t VT,
+                                                         const int64_t* __restrict__ lut, int64_t Vsrc, float* __restrict__ cum,
+                                                         int* __restrict__ finished, int* __restrict__ backptr, int* __restrict__ token,
+                                                         int64_t* __restrict__ next_ids) {
+    constexpr int WM = NIR_BEAM_MAX_W;
+    __shared__ float cval[WM * WM], clse[WM];
+    __shared__ int cidx[WM * WM];
+    const int64_t b = blockIdx.x;
+    const int lane = threadIdx.x;
+    for (int k = 0; k < W; ++k) {
+        if (finished[b * W + k]) continue;                                    // wave-uniform: a finished beam's logits are not read
+        beam_merge_row(pval, pidx, pm, ps, nparts, B * W, (int64_t)k * B + b, W, W, lane, cval + k * W, cidx + k * W, clse + k);
+    }
+    __syncthreads();
+    const int k = lane / W, j = lane - k * W;
+    bool open = false;                                                        // a candidate not yet taken
+    float score = -INFINITY;
+    int v = BEAM_NONE;
+    if (k < W) {
+        const float ck = cum[b * W + k];
+        if (finished[b * W + k]) {
+            open = j == 0;
+            score = ck;
+            v = NIR_BEAM_EOS;
+        } else {
+            open = true;
+            score = ck + (cval[k * W + j] - clse[k]);
+            v = cidx[k * W + j];
+        }
+        if (!(score == score)) score = -INFINITY;                             // a NaN never wins and never stalls the rounds
+    }
+    for (int o = 0; o < W; ++o) {
+        const float sc = open ? score : -INFINITY;
+        const float mx = wave_max(sc);
+        const bool c1 = open && sc == mx;
+        const int mk = wave_min_i(c1 ? k : BEAM_NONE);
+        const bool c2 = c1 && k == mk;
+        const int mv = wave_min_i(c2 ? v : BEAM_NONE);
+        if (c2 && v == mv) {
+            open = false;
+            const int64_t tokv = (v >= 0 && (int64_t)v < VT) ? v : 0;
+            const int64_t slot = b * W + o;
+            cum[slot] = score;
+            finished[slot] = tokv == NIR_BEAM_EOS;                             // (a frozen candidate's token is EOS too)
+            backptr[slot] = k;
+            token[slot] = (int)tokv;
+            const int64_t nxt = lut ? lut[tokv] : tokv;
+            next_ids[(int64_t)o * B + b] = (nxt >= 0 && nxt < Vsrc) ? nxt : 1;
+        }
+    }
+}
+
+__global__ void beam_init_kernel(float* __restrict__ cum, int* __restrict__ finished, int64_t n, int W) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    cum[e] = e % W == 0 ? 0.f : -INFINITY;
+    finished[e] = 0;
+}
+
+// ---- the state shuffle: out row k B + b = in row backptr[b, k] B + b, for up to three states of H floats (4 H bytes) per row ------------------
+__global__ __launch_bounds__(256) void beam_reorder_kernel(const int* __restrict__ backptr, int64_t B, int W, int H4, const float4* __restrict__ i0,
+                                                           float4* __restrict__ o0, const float4* __restrict__ i1, float4* __restrict__ o1,
+                                                           const float4* __restrict__ i2, float4* __restrict__ o2) {
+    const int64_t r = blockIdx.x;                                             // k B + b
+    const int64_t k = r / B, b = r - k * B;
+    int src = backptr[b * W + k];
+    src = src < 0 ? 0 : (src >= W ? W - 1 : src);
+    const int64_t s = (int64_t)src * B + b;
+    for (int f = threadIdx.x; f < H4; f += 256) {
+        o0[r * H4 + f] = i0[s * H4 + f];
+        if (i1) o1[r * H4 + f] = i1[s * H4 + f];
+        if (i2) o2[r * H4 + f] = i2[s * H4 + f];
+    }
+}
+
+// ---- backtrack: output beam j of source row b, walked from the last step through the back-pointers ---------------------------------------------
+// tok / bp [max_len][B][W]; attn_ws [max_len][R][QL], the rows as the attention launch of each step wrote them (a step's row belongs to the
+// beam the candidate extended: backptr).
+__global__ __launch_bounds__(64) void beam_backtrack_kernel(const int* __restrict__ tok, const int* __restrict__ bp, const float* __restrict__ attn_ws,
+                                                            const float* __restrict__ cum, int64_t B, int W, int max_len, int QL,
+                                                            int64_t* __restrict__ pred, float* __restrict__ scores, int64_t* __restrict__ lengths,
+                                                            float* __restrict__ attn) {
+    const int64_t o = blockIdx.x;                                             // b W + j
+    const int64_t b = o / W;
+    const int lane = threadIdx.x;
+    int k = (int)(o - b * W);
+    int len = max_len;
+    for (int t = max_len - 1; t >= 0; --t) {
+        const int64_t slot = ((int64_t)t * B + b) * W + k;
+        const int tk = tok[slot];
+        int src = bp[slot];
+        src = src < 0 ? 0 : (src >= W ? W - 1 : src);
+        if (tk == NIR_BEAM_EOS) len = t + 1;
+        if (lane == 0) pred[o * max_len + t] = tk;
+        const float* ar = attn_ws + (((int64_t)t * W + src) * B + b) * QL;
+        float* ao = attn + (o * max_len + t) * QL;
+        for (int q = lane; q < QL; q += 64) ao[q] = ar[q];
+        k = src;
+    }
+    if (lane == 0) { scores[o] = cum[o]; lengths[o] = len; }
+}
+
+// ---- launchers -----------------------------------------------------------------------------------------------------------------------------
+// partials per decode row of the fused generator (one per wave of every vocabulary range); no rows: no row block to size a range by
+static int beam_nparts(int64_t rows, int K, int64_t VT) { return rows > 0 ? 4 * s2s_nvr(rows, K, (VT + 15) / 16) : 0; }
+
+template <int NBT, int WM>
+static void beam_gen_launch(int grid, size_t lds, hipStream_t st, const float* x, const void* frag, const float* bias, int64_t VT, int64_t ntiles,
+                            int64_t rows, int K, int nvr, int W, float* pval, int* pidx, float* pm, float* ps) {
+    hipLaunchKernelGGL((beam_gen_topk_kernel<NBT, WM>), dim3((unsigned)grid), dim3(256), lds, st, x, (const _Float16*)frag, bias, VT, ntiles, rows, K, nvr, W,
+                       pval, pidx, pm, ps);
+}
+// the fused generator: partials pval / pidx [nparts][rows][W], pm / ps [nparts][rows]; returns nparts through *nparts
+static int launch_beam_gen_topk(const float* x, const void* frag, const float* bias, int64_t VT, int64_t rows, int K, int W, float* pval, int* pidx,
+                                float* pm, float* ps, hipStream_t st) {
+    const int64_t ntiles = (VT + 15) / 16;
+    const int nbt = s2s_nbt(K), nvr = s2s_nvr(rows, K, ntiles);
+    const int64_t rb = (rows + 16 * nbt - 1) / (16 * nbt);
+    const size_t lds = s2s_lds(K);
+    static std::once_flag once;
+    std::call_once(once, [] {
+        (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(512));
+        (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(512));
+        (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(1024));
+        (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(1024));
+    });
+    {
+        ProfScope ps_(prof_shape_name("beam_gen_topk_kernel", (long long)rows, (long long)VT, K), st);
+        const int grid = (int)(nvr * rb);
+        if (nbt == 4 && W <= 4) beam_gen_launch<4, 4>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
+        else if (nbt == 4) beam_gen_launch<4, 8>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
+        else if (W <= 4) beam_gen_launch<2, 4>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
+        else beam_gen_launch<2, 8>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
+    }
+    NIR_CHECK_LAUNCH("beam_gen_topk_kernel");
+    return 0;
+}
+static int launch_beam_row_topk(const float* logits, int64_t VT, int64_t rows, int W, float* top_val, int* top_idx, float* lse, hipStream_t st) {
+    {
+        ProfScope ps_("beam_row_topk_kernel", st);
+        hipLaunchKernelGGL(beam_row_topk_kernel, dim3((unsigned)rows), dim3(256), 0, st, logits, VT, W, top_val, top_idx, lse);
+    }
+    NIR_CHECK_LAUNCH("beam_row_topk_kernel");
+    return 0;
+}
+static int launch_beam_select(const float* pval, const int* pidx, const float* pm, const float* ps, int nparts, int64_t B, int W, int64_t VT,
+                              const int64_t* lut, int64_t V, float* cum, int* finished, int* backptr, int* token, int64_t* next_ids, hipStream_t st) {
+    {
+        ProfScope ps_("beam_select_kernel", st);
+        hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)B), dim3(64), 0, st, pval, pidx, pm, ps, nparts, B, W, VT, lut, V, cum, finished, backptr, token,
+                           next_ids);
+    }
+    NIR_CHECK_LAUNCH("beam_select_kernel");
+    return 0;
+}
+static int launch_beam_reorder(const int* backptr, int64_t B, int W, int H, const float* h_in, float* h_out, const float* c_in, float* c_out,
+                               const void* h16_in, void* h16_out, hipStream_t st) {
+    {
+        ProfScope ps_("beam_reorder_kernel", st);
+        hipLaunchKernelGGL(beam_reorder_kernel, dim3((unsigned)(B * W)), dim3(256), 0, st, backptr, B, W, H / 4, (const float4*)h_in, (float4*)h_out,
+                           (const float4*)c_in, (float4*)c_out, (const float4*)h16_in, (float4*)h16_out);
+    }
+    NIR_CHECK_LAUNCH("beam_reorder_kernel");
+    return 0;
+}
+static bool beam_dims_ok(int W, int64_t VT) { return W >= 1 && W <= NIR_BEAM_MAX_W && VT >= W; }
+
+struct BeamPlan {
+    float *sb, *h[2], *c[2], *h16[2], *qh, *cat, *ah, *logits, *pval, *pm, *ps, *cum, *attn, *gru;
+    int *pidx, *fin, *bp, *tok;
+    int64_t* tgt;
+    int nparts;
+    size_t bytes;
+};
+static BeamPlan beam_plan(void* ws, size_t cap, int64_t B, int QL, int W, int max_len, int H, int64_t VT, int attn_type, bool fused, int cell,
+                          bool step16, bool own_bp) {
+    Workspace a(ws, cap);
+    BeamPlan p;
+    const int64_t R = B * W;
+    p.nparts = fused ? beam_nparts(R, H, VT) : 1;
+    p.sb = a.take<float>(attn_type == NIR_S2S_ATTN_DOT ? 0 : (size_t)B * QL * H);
+    for (int k = 0; k < 2; ++k) { p.h[k] = a.take<float>((size_t)R * H); p.c[k] = a.take<float>(cell == S2S_CELL_GRU ? 0 : (size_t)R * H); }
+    for (int k = 0; k < 2; ++k) p.h16[k] = a.take<float>(step16 ? (size_t)R * H : 0);      // the fp16 term pairs, with the fp16-term step only
+    p.qh = a.take<float>(attn_type == NIR_S2S_ATTN_MLP ? (size_t)R * H : 0);
+    p.cat = a.take<float>((size_t)R * 2 * H);
+    p.ah = a.take<float>((size_t)R * H);
+    p.logits = a.take<float>(fused ? 0 : (size_t)R * VT);
+    p.pval = a.take<float>((size_t)p.nparts * R * W);
+    p.pidx = a.take<int>((size_t)p.nparts * R * W);
+    p.pm = a.take<float>((size_t)p.nparts * R);
+    p.ps = a.take<float>(fused ? (size_t)p.nparts * R : 0);
+    p.tgt = a.take<int64_t>((size_t)R);
+    p.cum = a.take<float>((size_t)R);
+    p.fin = a.take<int>((size_t)R);
+    p.bp = a.take<int>(own_bp ? (size_t)max_len * R : 0);                                  // (the caller's `backptr` serves when given)
+    p.tok = a.take<int>((size_t)max_len * R);
+    p.attn = a.take<float>((size_t)max_len * R * QL);
+    p.gru = cell == S2S_CELL_GRU ? a.take<float>(gru_step_scratch_floats(R, H)) : nullptr;
+    p.bytes = align_up(a.off, 256);
+    return p;
+}
+// the fp16-term step runs (both packs given, H a multiple of 32, tunable exact_f32 off)
+static bool beam_step16(const nir_seq2seq_decoder_weights* w) {
+    return w->rnn_gate_fold && w->rnn_whh_frag && w->H % 32 == 0 && !tun(g_tun.exact_f32);
+}
+static size_t beam_decode_workspace_bytes(int64_t B, int QL, int W, int max_len, const nir_seq2seq_decoder_weights* w, int cell) {
+    if (!s2s_weights_ok(w) || B < 0 || QL <= 0 || max_len <= 0 || !beam_dims_ok(W, w->VT)) return 0;
+    return beam_plan(nullptr, 0, B, QL, W, max_len, w->H, w->VT, w->attn_type, s2s_fused(w), cell, beam_step16(w), true).bytes;
+}
+
+// nir::s2s_decode with W decode rows per source row and the four beam launches in the place of the arg-max
+static int s2s_beam_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, int W,
+                           const float* table, int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len, const nir_seq2seq_decoder_weights* w,
+                           void* workspace, size_t workspace_bytes, int64_t* predictions, float* scores, int64_t* lengths, float* attentions,
+                           int32_t* backptr, int cell, hipStream_t st) {
+    const bool gru = cell == S2S_CELL_GRU;
+    NIR_REQUIRE(dec_h && (dec_c || gru) && memory_bank && source_len && table && w && predictions && scores && lengths && attentions,
+                "beam_seq2seq_decode: null pointer");
+    NIR_REQUIRE(s2s_weights_ok(w), "beam_seq2seq_decode: decoder weights incomplete for the attention type, or H not a multiple of 4");
+    NIR_REQUIRE(B >= 0 && QL > 0 && QL <= 4096 && max_len > 0 && V > 0 && E > 0 && E % 4 == 0, "beam_seq2seq_decode: bad dims");
+    NIR_REQUIRE(beam_dims_ok(W, w->VT), "beam_seq2seq_decode: beam width outside [1, %d] or above the target vocabulary", NIR_BEAM_MAX_W);
+    NIR_REQUIRE(B * W < 0x7FFFFFFFLL, "beam_seq2seq_decode: too many decode rows");
+    NIR_REQUIRE(bos >= 0 && bos < V, "beam_seq2seq_decode: BOS id outside the vocabulary");
+    NIR_REQUIRE((w->rnn_gate_fold == nullptr) == (w->rnn_whh_frag == nullptr), "beam_seq2seq_decode: rnn_gate_fold and rnn_whh_frag come together");
+    const int H = w->H;
+    const int64_t R = B * W;
+    const bool fused = s2s_fused(w);
+    NIR_REQUIRE(fused || w->VT < 0x7FFFFFFFLL, "beam_seq2seq_decode: VT too large for the GEMM path");
+    const bool step16 = beam_step16(w);
+    BeamPlan p = beam_plan(workspace, workspace_bytes, B, QL, W, max_len, H, w->VT, w->attn_type, fused, cell, step16, backptr == nullptr);
+    if (!workspace || p.bytes > workspace_bytes) {
+        set_error("beam_seq2seq_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
+        return NIR_ERR_WORKSPACE;
+    }
+    if (B == 0) return 0;
+    const bool mlp = w->attn_type == NIR_S2S_ATTN_MLP;
+    const float* sb = memory_bank;                        // the score bank, over the B source rows only
+    if (w->attn_type == NIR_S2S_ATTN_GENERAL) {
+        NIR_PROPAGATE(launch_linear(memory_bank, H, nullptr, nullptr, 0, 0, 0, w->attn_in_wt, H, nullptr, nullptr, p.sb, H, B * QL, H, H, NIR_ACT_NONE, st));
+        sb = p.sb;
+    } else if (mlp) {
+        NIR_PROPAGATE(launch_linear(memory_bank, H, nullptr, nullptr, 0, 0, 0, w->attn_ctx_w, H, nullptr, nullptr, p.sb, H, B * QL, H, H, NIR_ACT_NONE, st));
+        sb = p.sb;
+    }
+    NIR_PROPAGATE(launch_fill_i64(p.tgt, bos, R, st));
+    hipLaunchKernelGGL(beam_init_kernel, g1(R), dim3(256), 0, st, p.cum, p.fin, R, W);
+    NIR_CHECK_LAUNCH("beam_init_kernel");
+    int* bp = backptr ? backptr : p.bp;
+    LstmStepArgs a;
+    a.x[0] = table; a.xid[0] = p.tgt; a.xstride[0] = E;
+    a.wih[0] = w->rnn_wih; a.whh[0] = w->rnn_whh; a.bih[0] = w->rnn_bih; a.bhh[0] = w->rnn_bhh;
+    a.x[1] = nullptr; a.xid[1] = nullptr; a.xstride[1] = 0; a.wih[1] = a.whh[1] = a.bih[1] = a.bhh[1] = nullptr;
+    a.hprev[1] = a.cprev[1] = nullptr; a.hnext[1] = a.cnext[1] = nullptr;
+    a.chain0 = 0; a.B = (int)R; a.I = E; a.H = H;
+    GruStepArgs ga;
+    // buffers [0]: the state a step reads (the reordered one); [1]: what it writes
+    _Float16* h16cur = reinterpret_cast<_Float16*>(p.h16[0]);
+    _Float16* h16new = reinterpret_cast<_Float16*>(p.h16[1]);
+    if (gru) {
+        ga.tok = p.tgt; ga.V = V; ga.table = table; ga.E = E;
+        ga.wih = w->rnn_wih; ga.bih = w->rnn_bih; ga.whh = w->rnn_whh; ga.bhh = w->rnn_bhh;
+        ga.scratch = p.gru; ga.B = R; ga.H = H;
+        if (step16) { ga.gate_fold = w->rnn_gate_fold; ga.whh_frag = w->rnn_whh_frag; }
+    } else if (step16) {
+        a.gx[0] = w->rnn_gate_fold; a.gxid[0] = p.tgt; a.gxstride = (int64_t)4 * H; a.gx_unit_major = 1;
+        a.whh_frag[0] = w->rnn_whh_frag;
+    }
+    if (step16) NIR_PROPAGATE(launch_h16_pack(dec_h, R * H, h16cur, st));
+    const float* hp = dec_h;
+    const float* cp = dec_c;
+    for (int step = 0; step < max_len; ++step) {
+        float* hn = p.h[1];
+        float* cn = p.c[1];
+        a.hprev[0] = hp; a.cprev[0] = cp; a.hnext[0] = hn; a.cnext[0] = cn;
+        if (step16) {
+            a.h16prev[0] = ga.h16prev = h16cur;
+            a.h16next[0] = ga.h16next = h16new;
+        }
+        if (gru) {
+            ga.hprev = hp; ga.hnext = hn;
+            NIR_PROPAGATE(launch_gru_step(ga, st));
+        } else {
+            NIR_PROPAGATE(launch_lstm_step(a, 1, st));
+        }
+        if (mlp)
+            NIR_PROPAGATE(launch_linear(hn, H, nullptr, nullptr, 0, 0, 0, w->attn_query_w, H, w->attn_query_b, nullptr, p.qh, H, R, H, H, NIR_ACT_NONE, st));
+        NIR_PROPAGATE(launch_attend(mlp ? p.qh : hn, hn, memory_bank, sb, w->attn_v, source_len, R, QL, H, mlp, p.cat, p.attn + (int64_t)step * R * QL, QL, st,
+                                    B));
+        NIR_PROPAGATE(launch_linear(p.cat, 2 * H, nullptr, nullptr, 0, 0, 0, w->attn_out_w, 2 * H, mlp ? w->attn_out_b : nullptr, nullptr, p.ah, H, R, H,
+                                    2 * H, mlp ? NIR_ACT_NONE : NIR_ACT_TANH, st));
+        if (fused) {
+            NIR_PROPAGATE(launch_beam_gen_topk(p.ah, w->gen_frag, w->gen_b, w->VT, R, H, W, p.pval, p.pidx, p.pm, p.ps, st));
+        } else {
+            NIR_PROPAGATE(launch_linear(p.ah, H, nullptr, nullptr, 0, 0, 0, w->gen_w, H, w->gen_b, nullptr, p.logits, w->VT, R, (int)w->VT, H, NIR_ACT_NONE, st));
+            NIR_PROPAGATE(launch_beam_row_topk(p.logits, w->VT, R, W, p.pval, p.pidx, p.pm, st));
+        }
+        NIR_PROPAGATE(launch_beam_select(p.pval, p.pidx, p.pm, fused ? p.ps : nullptr, p.nparts, B, W, w->VT, tgt2src, V, p.cum, p.fin,
+                                         bp + (int64_t)step * R, p.tok + (int64_t)step * R, p.tgt, st));
+        if (step + 1 < max_len)
+            NIR_PROPAGATE(launch_beam_reorder(bp + (int64_t)step * R, B, W, H, hn, p.h[0], gru ? nullptr : cn, gru ? nullptr : p.c[0], step16 ? h16new : nullptr,
+                                              step16 ? h16cur : nullptr, st));
+        hp = p.h[0];
+        cp = p.c[0];
+    }
+    {
+        ProfScope ps_("beam_backtrack_kernel", st);
+        hipLaunchKernelGGL(beam_backtrack_kernel, dim3((unsigned)R), dim3(64), 0, st, p.tok, bp, p.attn, p.cum, B, W, max_len, QL, predictions, scores, lengths,
+                           attentions);
+    }
+    NIR_CHECK_LAUNCH("beam_backtrack_kernel");
+    return 0;
+}
+
+}  // namespace nir
+
+extern "C" size_t nir_beam_gen_topk_workspace_bytes(int64_t rows, int K, int64_t VT, int W, int fused) {
+    using namespace nir;
+    if (rows <= 0 || K <= 0 || !beam_dims_ok(W, VT)) return 0;
+    if (!fused) return (size_t)rows * VT * sizeof(float) + 256;
+    if (!s2s_fusable(K, VT)) return 0;
+    return (size_t)beam_nparts(rows, K, VT) * rows * ((size_t)W * 8 + 8) + 4 * 256;
+}
+
+extern "C" int nir_beam_gen_topk(const float* x, int64_t rows, int K, const float* gen_w, const float* gen_b, const void* gen_frag, int64_t VT, int W,
+                                 void* workspace, size_t workspace_bytes, float* top_val, int32_t* top_idx, float* lse, nir_stream_t stream) {
+    using namespace nir;
+    hipStream_t st = (hipStream_t)stream;
+    NIR_REQUIRE(x && gen_w && workspace && top_val && top_idx && lse, "beam_gen_topk: null pointer");
+    NIR_REQUIRE(rows >= 0 && rows < 0x7FFFFFFFLL && K > 0 && K % 4 == 0 && VT > 0, "beam_gen_topk: bad dims");
+    NIR_REQUIRE(beam_dims_ok(W, VT), "beam_gen_topk: beam width outside [1, %d] or above VT", NIR_BEAM_MAX_W);
+    const bool fused = gen_frag != nullptr && s2s_fusable(K, VT) && !tun(g_tun.exact_f32);
+    NIR_REQUIRE(fused || VT < 0x7FFFFFFFLL, "beam_gen_topk: VT too large for the GEMM path");
+    if (rows == 0) return 0;
+    if (workspace_bytes < nir_beam_gen_topk_workspace_bytes(rows, K, VT, W, fused)) {
+        set_error("beam_gen_topk: workspace too small");
+        return NIR_ERR_WORKSPACE;
+    }
+    Workspace a(workspace, workspace_bytes);
+    if (fused) {
+        const int nparts = beam_nparts(rows, K, VT);
+        float* pval = a.take<float>((size_t)nparts * rows * W);
+        int* pidx = a.take<int>((size_t)nparts * rows * W);
+        float* pm = a.take<float>((size_t)nparts * rows);
+        float* ps = a.take<float>((size_t)nparts * rows);
+        NIR_PROPAGATE(launch_beam_gen_topk(x, gen_frag, gen_b, VT, rows, K, W, pval, pidx, pm, ps, st));
+        hipLaunchKernelGGL(beam_topk_finish_kernel, dim3((unsigned)rows), dim3(64), 0, st, pval, pidx, pm, ps, nparts, rows, W, top_val, top_idx, lse);
+        NIR_CHECK_LAUNCH("beam_topk_finish_kernel");
+        return 0;
+    }
+    float* logits = a.take<float>((size_t)rows * VT);
+    NIR_PROPAGATE(launch_linear(x, K, nullptr, nullptr, 0, 0, 0, gen_w, K, gen_b, nullptr, logits, VT, rows, (int)VT, K, NIR_ACT_NONE, st));
+    return launch_beam_row_topk(logits, VT, rows, W, top_val, top_idx, lse, st);
+}
+
+extern "C" int nir_beam_select(const float* top_val, const int32_t* top_idx, const float* lse, int64_t B, int W, int64_t VT, const int64_t* tgt2src,
+                               int64_t V, float* cum, int32_t* finished, int32_t* backptr, int32_t* token, int64_t* next_ids, nir_stream_t stream) {
+    using namespace nir;
+    NIR_REQUIRE(top_val && top_idx && lse && cum && finished && backptr && token && next_ids, "beam_select: null pointer");
+    NIR_REQUIRE(B >= 0 && B * NIR_BEAM_MAX_W < 0x7FFFFFFFLL && V > 0, "beam_select: bad dims");
+    NIR_REQUIRE(beam_dims_ok(W, VT), "beam_select: beam width outside [1, %d] or above VT", NIR_BEAM_MAX_W);
+    if (B == 0) return 0;
+    return launch_beam_select(top_val, top_idx, lse, nullptr, 1, B, W, VT, tgt2src, V, cum, finished, backptr, token, next_ids, (hipStream_t)stream);
+}
+
+extern "C" int nir_beam_reorder(const int32_t* backptr, int64_t B, int W, int H, const float* h_in, float* h_out, const float* c_in, float* c_out,
+                                const void* h16_in, void* h16_out, nir_stream_t stream) {
+    using namespace nir;
+    NIR_REQUIRE(backptr && h_in && h_out, "beam_reorder: null pointer");
+    NIR_REQUIRE((c_in == nullptr) == (c_out == nullptr) && (h16_in == nullptr) == (h16_out == nullptr), "beam_reorder: a state needs its input and its output");
+    NIR_REQUIRE(B >= 0 && B * NIR_BEAM_MAX_W < 0x7FFFFFFFLL && H > 0 && H % 4 == 0 && (!h16_in || H % 8 == 0), "beam_reorder: bad dims");
+    NIR_REQUIRE(W >= 1 && W <= NIR_BEAM_MAX_W, "beam_reorder: beam width outside [1, %d]", NIR_BEAM_MAX_W);
+    NIR_REQUIRE(h_in != h_out && (!c_in || c_in != c_out) && (!h16_in || h16_in != h16_out), "beam_reorder: an output aliases its input");
+    if (B == 0) return 0;
+    return launch_beam_reorder(backptr, B, W, H, h_in, h_out, c_in, c_out, h16_in, h16_out, (hipStream_t)stream);
+}
+
+extern "C" size_t nir_beam_seq2seq_decode_workspace_bytes(int64_t B, int QL, int W, int max_len, const nir_seq2seq_decoder_weights* w) {
+    return nir::beam_decode_workspace_bytes(B, QL, W, max_len, w, nir::S2S_CELL_LSTM);
+}
+extern "C" int nir_beam_seq2seq_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, int W,
+                                       const float* table, int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len,
+                                       const nir_seq2seq_decoder_weights* w, void* workspace, size_t workspace_bytes, int64_t* predictions, float* scores,
+                                       int64_t* lengths, float* attentions, int32_t* backptr, nir_stream_t stream) {
+    return nir::s2s_beam_decode(dec_h, dec_c, memory_bank, source_len, B, QL, W, table, V, E, tgt2src, bos, max_len, w, workspace, workspace_bytes,
+                                predictions, scores, lengths, attentions, backptr, nir::S2S_CELL_LSTM, (hipStream_t)stream);
+}
+extern "C" size_t nir_beam_seq2seq_gru_decode_workspace_bytes(int64_t B, int QL, int W, int max_len, const nir_seq2seq_decoder_weights* w) {
+    return nir::beam_decode_workspace_bytes(B, QL, W, max_len, w, nir::S2S_CELL_GRU);
+}
+extern "C" int nir_beam_seq2seq_gru_decode(const float* dec_h, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, int W,
+                                           const float* table, int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len,
+                                           const nir_seq2seq_decoder_weights* w, void* workspace, size_t workspace_bytes, int64_t* predictions,
+                                           float* scores, int64_t* lengths, float* attentions, int32_t* backptr, nir_stream_t stream) {
+    return nir::s2s_beam_decode(dec_h, nullptr, memory_bank, source_len, B, QL, W, table, V, E, tgt2src, bos, max_len, w, workspace, workspace_bytes,
+                                predictions, scores, lengths, attentions, backptr, nir::S2S_CELL_GRU, (hipStream_t)stream);
+}

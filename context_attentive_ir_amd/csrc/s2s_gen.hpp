@@ -213,6 +213,12 @@ int launch_acg_gen_select(const float* o, int64_t B, int K, const float* gen_w, 
                           float* pval, int* pidx, float* psum, const float* copy_w, const float* copy_b, const float* attn, int64_t attn_stride,
                           const int64_t* lens, int QL, const int64_t* src_map_idx, const int64_t* ext2tgt, const int64_t* ext2src, int CV,
                           const int64_t* tgt2src, int64_t V, int64_t* pred, int64_t pstride, int64_t* tgt, hipStream_t st);
+// csrc/seq2seq.hip, shared with the beam search of csrc/beam.hip: the weight checks, the fused-generator decision and the attention launch
+// (nsrc: decode row i attends over source row i % nsrc; 0 = one source row per decode row)
+bool s2s_weights_ok(const nir_seq2seq_decoder_weights* w);
+bool s2s_fused(const nir_seq2seq_decoder_weights* w);
+int launch_attend(const float* q, const float* h, const float* mem, const float* sb, const float* v, const int64_t* lens, int64_t B, int QL, int H,
+                  int mlp, float* cat, float* attn, int64_t attn_stride, hipStream_t st, int64_t nsrc = 0);
 // csrc/seq2seq.hip: the greedy decode of Seq2seq (acg == NULL) and of ACG; cell: the decoder's recurrence
 constexpr int S2S_CELL_LSTM = 0, S2S_CELL_GRU = 1;
 size_t s2s_decode_workspace_bytes(int64_t B, int QL, const nir_seq2seq_decoder_weights* w, const AcgDecode* acg, int cell);

@@ -24,19 +24,22 @@ namespace nir {
 // sb [B, QL, H]: the score bank (memq / bank / memc);  mem [B, QL, H]: the memory bank the context is taken from.
 // cat [B, 2H] = [ctx ; h];  attn row b at attn + b * attn_stride, [QL]: masked positions get an exact 0.0 (a row of length 0 is NaN
 // throughout, like the reference's softmax over an all -inf row).
+// nsrc: decode row i reads the banks and the length of source row i % nsrc (the greedy decoders pass nsrc = B; the beam of csrc/beam.hip
+// has W decode rows per source row, row = k nsrc + b, and does not replicate the banks).
 __global__ __launch_bounds__(256) void s2s_attend_kernel(const float* __restrict__ q, const float* __restrict__ h, const float* __restrict__ mem,
                                                          const float* __restrict__ sb, const float* __restrict__ v,
                                                          const int64_t* __restrict__ lens, int B, int QL, int H, int mlp, float* __restrict__ cat,
-                                                         float* __restrict__ attn, int64_t attn_stride) {
+                                                         float* __restrict__ attn, int64_t attn_stride, int nsrc) {
     extern __shared__ float s2s_pr[];                 // [4][QL]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = blockIdx.x * 4 + wave;
     if (i >= B) return;
     float* pw = s2s_pr + wave * QL;
-    int len = (int)lens[i];
+    const int si = i % nsrc;
+    int len = (int)lens[si];
     len = len < 0 ? 0 : (len > QL ? QL : len);
-    const float* mb = mem + (int64_t)i * QL * H;
-    const float* sq = sb + (int64_t)i * QL * H;
+    const float* mb = mem + (int64_t)si * QL * H;
+    const float* sq = sb + (int64_t)si * QL * H;
     const float* qi = q + (int64_t)i * H;
     float mx = -INFINITY;
     for (int j = 0; j < len; ++j) {
@@ -116,12 +119,12 @@ static int launch_gen_argmax(const float* x, const void* frag, const float* bias
     return launch_argmax_finish(pval, pidx, nvr * 4, Bd, lut, pred, pstride, tgt, Vsrc, st);
 }
 
-static int launch_attend(const float* q, const float* h, const float* mem, const float* sb, const float* v, const int64_t* lens, int64_t B, int QL,
-                         int H, int mlp, float* cat, float* attn, int64_t attn_stride, hipStream_t st) {
+int launch_attend(const float* q, const float* h, const float* mem, const float* sb, const float* v, const int64_t* lens, int64_t B, int QL, int H,
+                  int mlp, float* cat, float* attn, int64_t attn_stride, hipStream_t st, int64_t nsrc) {
     {
         ProfScope ps("s2s_attend_kernel", st);
         hipLaunchKernelGGL(s2s_attend_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), (size_t)4 * QL * sizeof(float), st, q, h, mem, sb, v, lens, (int)B,
-                           QL, H, mlp, cat, attn, attn_stride);
+                           QL, H, mlp, cat, attn, attn_stride, (int)(nsrc > 0 ? nsrc : B));
     }
     NIR_CHECK_LAUNCH("s2s_attend_kernel");
     return 0;
@@ -164,10 +167,10 @@ static S2sPlan s2s_plan(void* ws, size_t cap, int64_t B, int QL, int H, int64_t 
     p.bytes = align_up(a.off, 256);
     return p;
 }
-static bool s2s_fused(const nir_seq2seq_decoder_weights* w) {
+bool s2s_fused(const nir_seq2seq_decoder_weights* w) {
     return w->gen_frag != nullptr && s2s_fusable(w->H, w->VT) && !tun(g_tun.exact_f32);
 }
-static bool s2s_weights_ok(const nir_seq2seq_decoder_weights* w) {
+bool s2s_weights_ok(const nir_seq2seq_decoder_weights* w) {
     if (!w || w->H <= 0 || w->H % 4 || w->VT <= 0) return false;
     if (!(w->rnn_wih && w->rnn_whh && w->rnn_bih && w->rnn_bhh && w->attn_out_w && w->gen_w && w->gen_b)) return false;
     if (w->attn_type == NIR_S2S_ATTN_GENERAL) return w->attn_in_wt != nullptr;

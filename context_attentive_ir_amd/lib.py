@@ -315,6 +315,23 @@ GRU_DECODE_SIGNATURES = {
                                        C.POINTER(AcgCopyWeights), c_ip, c_ip, c_ip, _i, C.c_void_p, _z, c_ip, c_fp, c_st]),
 }
 
+# Beam search for Seq2seq, declared in include/neuroir_beam.h (csrc/beam.hip): every symbol starts with nir_beam_.  A table of its own for the
+# same reason.
+BEAM_MAX_W, BEAM_EOS = 8, 3
+_W = C.POINTER(Seq2seqDecoderWeights)
+BEAM_SIGNATURES = {
+    "nir_beam_gen_topk_workspace_bytes": (_z, [_l, _i, _l, _i, _i]),
+    "nir_beam_gen_topk": (_i, [c_fp, _l, _i, c_fp, c_fp, C.c_void_p, _l, _i, C.c_void_p, _z, c_fp, C.c_void_p, c_fp, c_st]),
+    "nir_beam_select": (_i, [c_fp, C.c_void_p, c_fp, _l, _i, _l, c_ip, _l, c_fp, C.c_void_p, C.c_void_p, C.c_void_p, c_ip, c_st]),
+    "nir_beam_reorder": (_i, [C.c_void_p, _l, _i, _i, c_fp, c_fp, c_fp, c_fp, C.c_void_p, C.c_void_p, c_st]),
+    "nir_beam_seq2seq_decode_workspace_bytes": (_z, [_l, _i, _i, _i, _W]),
+    "nir_beam_seq2seq_decode": (_i, [c_fp, c_fp, c_fp, c_ip, _l, _i, _i, c_fp, _l, _i, c_ip, _l, _i, _W, C.c_void_p, _z, c_ip, c_fp, c_ip, c_fp,
+                                     C.c_void_p, c_st]),
+    "nir_beam_seq2seq_gru_decode_workspace_bytes": (_z, [_l, _i, _i, _i, _W]),
+    "nir_beam_seq2seq_gru_decode": (_i, [c_fp, c_fp, c_ip, _l, _i, _i, c_fp, _l, _i, c_ip, _l, _i, _W, C.c_void_p, _z, c_ip, c_fp, c_ip, c_fp,
+                                         C.c_void_p, c_st]),
+}
+
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_SPLIT2 = 0, 1, 2
 DTYPES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "bf16": DTYPE_BF16, "f32_split2": DTYPE_F32_SPLIT2}
 
@@ -330,7 +347,7 @@ def load():
                 "libneuroir_hip.so not found at %s -- build it with `python -m context_attentive_ir_amd.build` "
                 "(hipcc, gfx950). The HIP path has no CPU fallback." % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(GRU_DECODE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(GRU_DECODE_SIGNATURES.items()) + list(BEAM_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

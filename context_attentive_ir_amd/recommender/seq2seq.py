@@ -47,6 +47,7 @@ def build_network(net, args, own_copy_attn=False):
     net.dec_dropout_p = float(args.dropout_rnn)         # RNNDecoder.dropout (decoders/decoder.py:87)
     net.fold_decoder_step = True             # decode: per-token gate rows folded into a [V, 4H] table + fp16-term recurrent product
     net.fuse_generator_argmax = True         # decode: generator + bias + arg-max in one kernel (no [B, VT] logits)
+    net.fuse_generator_topk = True           # decode_beam: generator + bias + (lse, top-W) in one kernel (no [B W, VT] logits)
     net.fold_budget_bytes = 64 << 30
     net._pdec = lib.PackCache(retain=1)
 
@@ -160,6 +161,62 @@ class Seq2seq(nn.Module, lib.IdCheck):
                                                   lib.ptr(tgt2src), BOS, max_len, w.ref(), lib.ptr(ws), ws.numel(), lib.ptr(preds), lib.ptr(attns),
                                                   lib.stream()), "nir_seq2seq_decode_greedy")
         return {"predictions": preds, "attentions": attns}
+
+    # ---- eval: beam search ---------------------------------------------------------------------------------------------------------
+    _BEAM_ENTRY = "nir_beam_seq2seq_decode"
+
+    def _beam_state(self, src, lens):
+        """encoder -> (the decoder's initial state tensors, each [B, nhid], in the sorted-order pairing of initial_state; the memory bank)"""
+        table = self.embedder.word_embeddings.table
+        final, bank = self.encoder.encoder(A.embed(src, table), lens)
+        return self.initial_state(final, lens), bank.float().contiguous()
+
+    @torch.no_grad()
+    def decode_beam(self, source_rep, source_len, max_len, beam_size, src_dict=None, tgt_dict=None, tgt2src=None, return_backptr=False):
+        """Beam search of width `beam_size` (1 .. lib.BEAM_MAX_W) over max_len steps, no early stop (include/neuroir_beam.h)
+        -> {'predictions': LongTensor [B, W, max_len] (best beam first, EOS repeated behind the first EOS), 'scores': [B, W] (sum of the
+        tokens' log-probabilities, frozen at EOS), 'lengths': LongTensor [B, W], 'attentions': [B, W, max_len, QL]} (+ 'backptr': IntTensor
+        [max_len, B, W] on request).  The stages of decode(): encoder, the sorted-order pairing, the state repeated W times in the reference's
+        beam layout (row k B + b: decoders/state.py:65-69), ONE C call.  The memory bank is not repeated."""
+        if self.training:
+            raise NotImplementedError("HIP %s.decode_beam runs in eval mode" % type(self).__name__)
+        if self.copy_attn:
+            raise NotImplementedError("HIP beam search covers Seq2seq and Seq2seqGRU; the copy generator of ACG has no beam (DESIGN.md section 21)")
+        W = int(beam_size)
+        B, QL = source_rep.shape
+        self._check_layers(B)
+        table = self.embedder.word_embeddings.table
+        lib.require_device(source_rep, source_len, table)
+        L = lib.load()
+        w = self._decoder_weights()
+        VT = int(w.struct.VT)
+        if not 1 <= W <= lib.BEAM_MAX_W or W > VT:
+            raise ValueError("decode_beam: beam_size %d outside [1, %d] or above the target vocabulary (%d)" % (W, lib.BEAM_MAX_W, VT))
+        src, _ = self._clean_ids(source_rep, None, table.shape[0])
+        lens = lib.ids64(source_len)
+        state, bank = self._beam_state(src, lens)
+        state = [s.repeat(W, 1).contiguous() for s in (state if isinstance(state, tuple) else (state,))]        # row k B + b
+        dev = bank.device
+        ws_ref = w.ref()
+        if not self.fuse_generator_topk and w.struct.gen_frag:
+            plain = lib.Seq2seqDecoderWeights.from_buffer_copy(w.struct)      # the same pack without the fragment: the plain generator form
+            plain.gen_frag = None
+            ws_ref = lib.C.byref(plain)
+        if tgt2src is None:
+            tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, VT, dev)
+        t = table.detach().float().contiguous()
+        max_len = int(max_len)
+        out = {"predictions": torch.empty(B, W, max_len, dtype=torch.int64, device=dev), "scores": torch.empty(B, W, dtype=torch.float32, device=dev),
+               "lengths": torch.empty(B, W, dtype=torch.int64, device=dev), "attentions": torch.empty(B, W, max_len, QL, dtype=torch.float32, device=dev)}
+        if return_backptr:
+            out["backptr"] = torch.empty(max_len, B, W, dtype=torch.int32, device=dev)
+        if B > 0 and max_len > 0:
+            ws = lib.workspace(getattr(L, self._BEAM_ENTRY + "_workspace_bytes")(B, QL, W, max_len, ws_ref), dev)
+            args = [lib.ptr(s) for s in state] + [lib.ptr(bank), lib.ptr(lens), B, QL, W, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(tgt2src), BOS,
+                                                  max_len, ws_ref, lib.ptr(ws), ws.numel(), lib.ptr(out["predictions"]), lib.ptr(out["scores"]),
+                                                  lib.ptr(out["lengths"]), lib.ptr(out["attentions"]), lib.ptr(out.get("backptr")), lib.stream()]
+            lib.check(getattr(L, self._BEAM_ENTRY)(*args), self._BEAM_ENTRY)
+        return out
 
     # ---- train: teacher-forced loss ---------------------------------------------------------------------------------------------------
     def _encode_train(self, x, lens):

@@ -90,6 +90,11 @@ class _GRUDecoderMixin(object):
         params = list(self.decoder.parameters()) + list(self.generator.parameters())
         return self._pdec.get(params + [table, self.fold_decoder_step, self.fuse_generator_argmax, self.fold_budget_bytes], build)
 
+    _BEAM_ENTRY = "nir_beam_seq2seq_gru_decode"
+
+    def _beam_state(self, src, lens):
+        return self._encode_state(src, lens)
+
     def _encode_state(self, src, lens):
         """eval: embedding -> GRU encoder -> (initial decoder state [B, nhid], memory bank [B, QL, nhid])"""
         table = self.embedder.word_embeddings.table

@@ -113,6 +113,36 @@ class Recommender(WrapperBase):
             out.update(self._text(ex, out["prediction_ids"], out["attentions"]))
         return out
 
+    # ---- beam search ------------------------------------------------------------------------------------------------------------------
+    def _predict_beam_body(self, ex, beam_size):
+        self.network.eval()
+        dec = self.network.decode_beam(source_rep=self._dev(self._rows3(ex["source_words"])), source_len=self._dev(self._rows2(ex["source_lens"])),
+                                       max_len=self.args.max_query_len, beam_size=beam_size, src_dict=self.src_dict, tgt_dict=self.tgt_dict)
+        self._maybe_check_ids()
+        return {"prediction_ids": dec["predictions"], "scores": dec["scores"], "lengths": dec["lengths"], "attentions": dec["attentions"]}
+
+    @torch.no_grad()
+    def predict_beam(self, ex, beam_size):
+        """n-best suggestions by beam search (Seq2seq.decode_beam; the reference has no counterpart): {'prediction_ids': LongTensor
+        [B, W, max_query_len], 'scores': [B, W], 'lengths': LongTensor [B, W], 'attentions': [B, W, max_query_len, QL]}, best beam first; for
+        a batch in the reference's collate layout also `ex_ids`, `targets`, `src_sequences` and `predictions`: per row the list of its W
+        strings, each formed like predict()'s.  `beam_size` is an argument of the call, not a field of args.  Graph replay as in predict()."""
+        W = int(beam_size)
+        if self.network.copy_attn:
+            raise NotImplementedError("HIP beam search covers Seq2seq and Seq2seqGRU; ACG's copy generator has no beam (DESIGN.md section 21)")
+        self._poll_ids()
+        body = lambda e: self._predict_beam_body(e, W)                        # noqa: E731
+        out = self._graphed(ex, Recommender._FIELDS, "decode_beam%d" % W, body)
+        if out is None:
+            out = body(ex)
+        elif self.id_check == "blocking":
+            self._maybe_check_ids()
+        if all(k in ex for k in ("ids", "source_tokens", "target_tokens", "src_vocab")):
+            per_beam = [Recommender._text(self, ex, out["prediction_ids"][:, k], out["attentions"][:, k]) for k in range(W)]
+            out.update(per_beam[0])
+            out["predictions"] = [[per_beam[k]["predictions"][b] for k in range(W)] for b in range(len(per_beam[0]["predictions"]))]
+        return out
+
     def _text(self, ex, pred_ids, attns):
         """the host-side tail of the reference's predict (models/recommender.py:294-309): tens2sen (utils/misc.py:36-62) + replace_unknown
         (utils/copy_utils.py:51-60: token i of the sentence takes the arg-max of attention row i).  The one place predict synchronises."""
@@ -175,6 +205,9 @@ class SessionRecommender(Recommender):
     @staticmethod
     def _rows2(t):
         return t
+
+    def predict_beam(self, ex, beam_size):
+        raise NotImplementedError("HIP beam search covers Seq2seq and Seq2seqGRU; HredQS keeps its greedy decode (DESIGN.md section 21)")
 
     def _predict_body(self, ex):
         self.network.eval()

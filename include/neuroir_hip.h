@@ -1134,6 +1134,8 @@ int nir_acg_copy_loss_bwd(const float* logits, int64_t ld, const float* switch_l
 /* The GRU decoders of Seq2seq and ACG (one step, and the two greedy decodes with it) are declared in a header of their own, part of this
  * ABI (ctypes: lib.GRU_DECODE_SIGNATURES): this file's per-family symbol lists are pinned by tests that predate them. */
 #include "neuroir_gru_decode.h"
+/* Beam search for Seq2seq (both decoders' cells), likewise in a header of its own (ctypes: lib.BEAM_SIGNATURES). */
+#include "neuroir_beam.h"
 
 #ifdef __cplusplus
 }

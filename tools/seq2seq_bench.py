@@ -12,7 +12,10 @@ of predict() with the unfused generator (fp32 GEMM + arg-max kernel), of predict
 of the torch composition, each per round of --rounds alternating rounds, the medians over the rounds, the speed-up, and whether the tokens
 of the paths agree.  --rnn_type GRU times Seq2seqGRU (csrc/gru_step.hip) against nn.GRU the same way.
 
-    python tools/seq2seq_bench.py [--rnn_type LSTM|GRU] [--iters 20] [--warmup 5] [--rounds 3] [--json out.json]
+--beam_size W times `Recommender.predict_beam` (csrc/beam.hip) instead: the fused generator + top-k kernel against the plain form (fp32 GEMM into
+[B W, VT] logits + one workgroup per row), graph replay, the same protocol; the greedy predict() of the same batch is timed next to them.
+
+    python tools/seq2seq_bench.py [--rnn_type LSTM|GRU] [--beam_size W] [--iters 20] [--warmup 5] [--rounds 3] [--json out.json]
 """
 import argparse
 import json
@@ -63,6 +66,7 @@ def main():
     ap.add_argument("--nhid", type=int, default=512)
     ap.add_argument("--max_len", type=int, default=20)
     ap.add_argument("--rnn_type", default="LSTM", choices=["LSTM", "GRU"])
+    ap.add_argument("--beam_size", type=int, default=0, help="> 0: time predict_beam of this width (fused against plain generator top-k)")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3, help="alternating repeats of the timings; the spread of their medians is reported")
@@ -92,6 +96,32 @@ def main():
 
     def flavour(fuse, fold=True):
         net.fuse_generator_argmax, net.fold_decoder_step = fuse, fold             # (part of the pack's key: the next call captures the other path)
+
+    if a.beam_size > 0:
+        def beam():
+            return r.predict_beam(ex, a.beam_size)["prediction_ids"]
+        fused_r, plain_r, greedy_r = [], [], []
+        with torch.no_grad():
+            for _ in range(max(1, a.rounds)):
+                net.fuse_generator_topk = True
+                fused_r.append(timed(beam, a.iters, a.warmup))
+                p_fused = beam().clone()
+                net.fuse_generator_topk = False
+                plain_r.append(timed(beam, a.iters, a.warmup))
+                p_plain = beam().clone()
+                greedy_r.append(timed(ours, a.iters, a.warmup))
+            net.fuse_generator_topk = True
+        fused, plain, greedy = (float(np.median(v)) for v in (fused_r, plain_r, greedy_r))
+        out = dict(model="seq2seq_beam", rnn_type=a.rnn_type, beam_size=a.beam_size, B=a.B, QL=a.ql, emsize=a.emsize, nhid=a.nhid, V=a.V, VT=a.VT,
+                   max_len=a.max_len, ms_per_decode=round(fused, 4), plain_topk_ms_per_decode=round(plain, 4), greedy_ms_per_decode=round(greedy, 4),
+                   ms_rounds=[round(v, 4) for v in fused_r], plain_topk_ms_rounds=[round(v, 4) for v in plain_r],
+                   greedy_ms_rounds=[round(v, 4) for v in greedy_r], fused_wins_outside_spread=bool(max(fused_r) < min(plain_r)),
+                   tokens_equal_fused_plain=float((p_fused == p_plain).float().mean()))
+        print(json.dumps(out))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(out, f, indent=1)
+        return
 
     with torch.no_grad():
         fused_r, plain_r, step_r, ref_r = [], [], [], []
