@@ -314,7 +314,7 @@ extern "C" int nir_acg_gen_select(const float* o, int64_t rows, int K, const flo
                 "acg_gen_select: null pointer");
     NIR_REQUIRE(rows >= 0 && K > 0 && K % 4 == 0 && VT > 0 && VT < 0x7FFFFFF0LL && V > 0 && pred_stride >= 1 && attn_stride >= QL, "acg_gen_select: bad dims");
     NIR_REQUIRE(acg_dims_ok(QL, CV), "acg_gen_select: QL outside [1, 4096] or CV outside [2, %d]", ACG_MAX_CV);
-    const bool fused = gen_frag != nullptr && s2s_fusable(K, VT) && !tun(g_tun.exact_f32);
+    const bool fused = s2s_gen_fused(gen_frag, K, VT);
     if (workspace_bytes < acg_gen_select_bytes(rows, VT, fused)) {
         set_error("acg_gen_select: workspace too small");
         return NIR_ERR_WORKSPACE;

@@ -1,7 +1,8 @@
 // Beam search for the Seq2seq recommenders (include/neuroir_beam.h).  The reference has the state helpers of a beam
 // (decoders/state.py:16-31 beam_update, :65-69 repeat_beam_size_times) and no search; they fix the row layout row = k B + b and the shuffle
-// new[k] = old[backptr[b, k]].  Per step, for all R = B W decode rows at once:
-//   (h,c) = cell(emb(tok), (h,c)); attention over source row `row % B` (the banks are not repeated); o = linear_out([ctx ; h])    as csrc/seq2seq.hip
+// new[k] = old[backptr[b, k]].  The decode is the S2sStepper of csrc/seq2seq.hip (s2s_gen.hpp) over R = B W decode rows and B source rows, with
+// the beam's tail behind it.  Per step, for all R rows at once:
+//   (h,c) = cell(emb(tok), (h,c)); attention over source row `row % B` (the banks are not repeated); o = linear_out([ctx ; h])    S2sStepper::step
 //   per row: lse and the W largest of y = W_g o + b_g         beam_gen_topk_kernel (the logits never leave the chip), or GEMM + beam_row_topk_kernel
 //   per source row: the W best of the <= W W live candidates cum + (y - lse) and the frozen ones (finished beams)            beam_select_kernel
 //   state rows gathered by the back-pointers                                                                                beam_reorder_kernel
@@ -473,9 +474,9 @@ static int launch_beam_reorder(const int* backptr, int64_t B, int W, int H, cons
 static bool beam_dims_ok(int W, int64_t VT) { return W >= 1 && W <= NIR_BEAM_MAX_W && VT >= W; }
 
 struct BeamPlan {
-    float *sb, *h[2], *c[2], *h16[2], *qh, *cat, *ah, *logits, *pval, *pm, *ps, *cum, *attn, *gru;
+    S2sStepBufs s;                                    // the stepper's buffers, over R = B W decode rows
+    float *pval, *pm, *ps, *cum, *attn;
     int *pidx, *fin, *bp, *tok;
-    int64_t* tgt;
     int nparts;
     size_t bytes;
 };
@@ -485,129 +486,70 @@ static BeamPlan beam_plan(void* ws, size_t cap, int64_t B, int QL, int W, int ma
     BeamPlan p;
     const int64_t R = B * W;
     p.nparts = fused ? beam_nparts(R, H, VT) : 1;
-    p.sb = a.take<float>(attn_type == NIR_S2S_ATTN_DOT ? 0 : (size_t)B * QL * H);
-    for (int k = 0; k < 2; ++k) { p.h[k] = a.take<float>((size_t)R * H); p.c[k] = a.take<float>(cell == S2S_CELL_GRU ? 0 : (size_t)R * H); }
-    for (int k = 0; k < 2; ++k) p.h16[k] = a.take<float>(step16 ? (size_t)R * H : 0);      // the fp16 term pairs, with the fp16-term step only
-    p.qh = a.take<float>(attn_type == NIR_S2S_ATTN_MLP ? (size_t)R * H : 0);
-    p.cat = a.take<float>((size_t)R * 2 * H);
-    p.ah = a.take<float>((size_t)R * H);
-    p.logits = a.take<float>(fused ? 0 : (size_t)R * VT);
+    p.s = s2s_step_bufs(a, R, B, QL, H, VT, attn_type, fused, cell, step16);               // (the fp16 term pairs with the fp16-term step only)
     p.pval = a.take<float>((size_t)p.nparts * R * W);
     p.pidx = a.take<int>((size_t)p.nparts * R * W);
     p.pm = a.take<float>((size_t)p.nparts * R);
     p.ps = a.take<float>(fused ? (size_t)p.nparts * R : 0);
-    p.tgt = a.take<int64_t>((size_t)R);
+    p.s.tgt = a.take<int64_t>((size_t)R);
     p.cum = a.take<float>((size_t)R);
     p.fin = a.take<int>((size_t)R);
     p.bp = a.take<int>(own_bp ? (size_t)max_len * R : 0);                                  // (the caller's `backptr` serves when given)
     p.tok = a.take<int>((size_t)max_len * R);
     p.attn = a.take<float>((size_t)max_len * R * QL);
-    p.gru = cell == S2S_CELL_GRU ? a.take<float>(gru_step_scratch_floats(R, H)) : nullptr;
+    if (cell == S2S_CELL_GRU) p.s.gru = a.take<float>(gru_step_scratch_floats(R, H));
     p.bytes = align_up(a.off, 256);
     return p;
 }
-// the fp16-term step runs (both packs given, H a multiple of 32, tunable exact_f32 off)
-static bool beam_step16(const nir_seq2seq_decoder_weights* w) {
-    return w->rnn_gate_fold && w->rnn_whh_frag && w->H % 32 == 0 && !tun(g_tun.exact_f32);
-}
 static size_t beam_decode_workspace_bytes(int64_t B, int QL, int W, int max_len, const nir_seq2seq_decoder_weights* w, int cell) {
     if (!s2s_weights_ok(w) || B < 0 || QL <= 0 || max_len <= 0 || !beam_dims_ok(W, w->VT)) return 0;
-    return beam_plan(nullptr, 0, B, QL, W, max_len, w->H, w->VT, w->attn_type, s2s_fused(w), cell, beam_step16(w), true).bytes;
+    return beam_plan(nullptr, 0, B, QL, W, max_len, w->H, w->VT, w->attn_type, s2s_fused(w), cell, s2s_step16(w), true).bytes;
 }
 
-// nir::s2s_decode with W decode rows per source row and the four beam launches in the place of the arg-max
+// The stepper of s2s_gen.hpp over W decode rows per source row, with the beam's tail behind the attentional output: top-k, select, reorder.  A
+// step always reads state slot 0 (the reordered one) and writes slot 1; the attention rows of every step are kept for the backtrack.
 static int s2s_beam_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, int W,
                            const float* table, int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len, const nir_seq2seq_decoder_weights* w,
                            void* workspace, size_t workspace_bytes, int64_t* predictions, float* scores, int64_t* lengths, float* attentions,
                            int32_t* backptr, int cell, hipStream_t st) {
-    const bool gru = cell == S2S_CELL_GRU;
-    NIR_REQUIRE(dec_h && (dec_c || gru) && memory_bank && source_len && table && w && predictions && scores && lengths && attentions,
-                "beam_seq2seq_decode: null pointer");
-    NIR_REQUIRE(s2s_weights_ok(w), "beam_seq2seq_decode: decoder weights incomplete for the attention type, or H not a multiple of 4");
-    NIR_REQUIRE(B >= 0 && QL > 0 && QL <= 4096 && max_len > 0 && V > 0 && E > 0 && E % 4 == 0, "beam_seq2seq_decode: bad dims");
-    NIR_REQUIRE(beam_dims_ok(W, w->VT), "beam_seq2seq_decode: beam width outside [1, %d] or above the target vocabulary", NIR_BEAM_MAX_W);
-    NIR_REQUIRE(B * W < 0x7FFFFFFFLL, "beam_seq2seq_decode: too many decode rows");
-    NIR_REQUIRE(bos >= 0 && bos < V, "beam_seq2seq_decode: BOS id outside the vocabulary");
-    NIR_REQUIRE((w->rnn_gate_fold == nullptr) == (w->rnn_whh_frag == nullptr), "beam_seq2seq_decode: rnn_gate_fold and rnn_whh_frag come together");
-    const int H = w->H;
     const int64_t R = B * W;
-    const bool fused = s2s_fused(w);
-    NIR_REQUIRE(fused || w->VT < 0x7FFFFFFFLL, "beam_seq2seq_decode: VT too large for the GEMM path");
-    const bool step16 = beam_step16(w);
+    S2sStepper s{"beam_seq2seq_decode", w, cell, table, memory_bank, source_len, V, R, B, E, QL, st};
+    NIR_PROPAGATE(s.check(dec_h, dec_c, predictions && scores && lengths && attentions, bos, max_len));
+    NIR_REQUIRE(beam_dims_ok(W, w->VT), "beam_seq2seq_decode: beam width outside [1, %d] or above the target vocabulary", NIR_BEAM_MAX_W);
+    NIR_REQUIRE(R < 0x7FFFFFFFLL, "beam_seq2seq_decode: too many decode rows");
+    const int H = w->H;
+    const bool fused = s.fused, step16 = s.step16, gru = cell == S2S_CELL_GRU;
     BeamPlan p = beam_plan(workspace, workspace_bytes, B, QL, W, max_len, H, w->VT, w->attn_type, fused, cell, step16, backptr == nullptr);
     if (!workspace || p.bytes > workspace_bytes) {
         set_error("beam_seq2seq_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
         return NIR_ERR_WORKSPACE;
     }
     if (B == 0) return 0;
-    const bool mlp = w->attn_type == NIR_S2S_ATTN_MLP;
-    const float* sb = memory_bank;                        // the score bank, over the B source rows only
-    if (w->attn_type == NIR_S2S_ATTN_GENERAL) {
-        NIR_PROPAGATE(launch_linear(memory_bank, H, nullptr, nullptr, 0, 0, 0, w->attn_in_wt, H, nullptr, nullptr, p.sb, H, B * QL, H, H, NIR_ACT_NONE, st));
-        sb = p.sb;
-    } else if (mlp) {
-        NIR_PROPAGATE(launch_linear(memory_bank, H, nullptr, nullptr, 0, 0, 0, w->attn_ctx_w, H, nullptr, nullptr, p.sb, H, B * QL, H, H, NIR_ACT_NONE, st));
-        sb = p.sb;
-    }
-    NIR_PROPAGATE(launch_fill_i64(p.tgt, bos, R, st));
+    s.b = p.s;
+    NIR_PROPAGATE(s.prepare(dec_h, bos, p.s.h16[0]));
     hipLaunchKernelGGL(beam_init_kernel, g1(R), dim3(256), 0, st, p.cum, p.fin, R, W);
     NIR_CHECK_LAUNCH("beam_init_kernel");
     int* bp = backptr ? backptr : p.bp;
-    LstmStepArgs a;
-    a.x[0] = table; a.xid[0] = p.tgt; a.xstride[0] = E;
-    a.wih[0] = w->rnn_wih; a.whh[0] = w->rnn_whh; a.bih[0] = w->rnn_bih; a.bhh[0] = w->rnn_bhh;
-    a.x[1] = nullptr; a.xid[1] = nullptr; a.xstride[1] = 0; a.wih[1] = a.whh[1] = a.bih[1] = a.bhh[1] = nullptr;
-    a.hprev[1] = a.cprev[1] = nullptr; a.hnext[1] = a.cnext[1] = nullptr;
-    a.chain0 = 0; a.B = (int)R; a.I = E; a.H = H;
-    GruStepArgs ga;
-    // buffers [0]: the state a step reads (the reordered one); [1]: what it writes
-    _Float16* h16cur = reinterpret_cast<_Float16*>(p.h16[0]);
-    _Float16* h16new = reinterpret_cast<_Float16*>(p.h16[1]);
-    if (gru) {
-        ga.tok = p.tgt; ga.V = V; ga.table = table; ga.E = E;
-        ga.wih = w->rnn_wih; ga.bih = w->rnn_bih; ga.whh = w->rnn_whh; ga.bhh = w->rnn_bhh;
-        ga.scratch = p.gru; ga.B = R; ga.H = H;
-        if (step16) { ga.gate_fold = w->rnn_gate_fold; ga.whh_frag = w->rnn_whh_frag; }
-    } else if (step16) {
-        a.gx[0] = w->rnn_gate_fold; a.gxid[0] = p.tgt; a.gxstride = (int64_t)4 * H; a.gx_unit_major = 1;
-        a.whh_frag[0] = w->rnn_whh_frag;
-    }
-    if (step16) NIR_PROPAGATE(launch_h16_pack(dec_h, R * H, h16cur, st));
     const float* hp = dec_h;
     const float* cp = dec_c;
     for (int step = 0; step < max_len; ++step) {
-        float* hn = p.h[1];
-        float* cn = p.c[1];
-        a.hprev[0] = hp; a.cprev[0] = cp; a.hnext[0] = hn; a.cnext[0] = cn;
-        if (step16) {
-            a.h16prev[0] = ga.h16prev = h16cur;
-            a.h16next[0] = ga.h16next = h16new;
-        }
-        if (gru) {
-            ga.hprev = hp; ga.hnext = hn;
-            NIR_PROPAGATE(launch_gru_step(ga, st));
-        } else {
-            NIR_PROPAGATE(launch_lstm_step(a, 1, st));
-        }
-        if (mlp)
-            NIR_PROPAGATE(launch_linear(hn, H, nullptr, nullptr, 0, 0, 0, w->attn_query_w, H, w->attn_query_b, nullptr, p.qh, H, R, H, H, NIR_ACT_NONE, st));
-        NIR_PROPAGATE(launch_attend(mlp ? p.qh : hn, hn, memory_bank, sb, w->attn_v, source_len, R, QL, H, mlp, p.cat, p.attn + (int64_t)step * R * QL, QL, st,
-                                    B));
-        NIR_PROPAGATE(launch_linear(p.cat, 2 * H, nullptr, nullptr, 0, 0, 0, w->attn_out_w, 2 * H, mlp ? w->attn_out_b : nullptr, nullptr, p.ah, H, R, H,
-                                    2 * H, mlp ? NIR_ACT_NONE : NIR_ACT_TANH, st));
+        float* hn = p.s.h[1];
+        float* cn = p.s.c[1];
+        NIR_PROPAGATE(s.step(hp, cp, hn, cn, p.s.h16[0], p.s.h16[1], p.attn + (int64_t)step * R * QL, QL));
         if (fused) {
-            NIR_PROPAGATE(launch_beam_gen_topk(p.ah, w->gen_frag, w->gen_b, w->VT, R, H, W, p.pval, p.pidx, p.pm, p.ps, st));
+            NIR_PROPAGATE(launch_beam_gen_topk(p.s.ah, w->gen_frag, w->gen_b, w->VT, R, H, W, p.pval, p.pidx, p.pm, p.ps, st));
         } else {
-            NIR_PROPAGATE(launch_linear(p.ah, H, nullptr, nullptr, 0, 0, 0, w->gen_w, H, w->gen_b, nullptr, p.logits, w->VT, R, (int)w->VT, H, NIR_ACT_NONE, st));
-            NIR_PROPAGATE(launch_beam_row_topk(p.logits, w->VT, R, W, p.pval, p.pidx, p.pm, st));
+            NIR_PROPAGATE(launch_linear(p.s.ah, H, nullptr, nullptr, 0, 0, 0, w->gen_w, H, w->gen_b, nullptr, p.s.logits, w->VT, R, (int)w->VT, H, NIR_ACT_NONE,
+                                        st));
+            NIR_PROPAGATE(launch_beam_row_topk(p.s.logits, w->VT, R, W, p.pval, p.pidx, p.pm, st));
         }
         NIR_PROPAGATE(launch_beam_select(p.pval, p.pidx, p.pm, fused ? p.ps : nullptr, p.nparts, B, W, w->VT, tgt2src, V, p.cum, p.fin,
-                                         bp + (int64_t)step * R, p.tok + (int64_t)step * R, p.tgt, st));
+                                         bp + (int64_t)step * R, p.tok + (int64_t)step * R, p.s.tgt, st));
         if (step + 1 < max_len)
-            NIR_PROPAGATE(launch_beam_reorder(bp + (int64_t)step * R, B, W, H, hn, p.h[0], gru ? nullptr : cn, gru ? nullptr : p.c[0], step16 ? h16new : nullptr,
-                                              step16 ? h16cur : nullptr, st));
-        hp = p.h[0];
-        cp = p.c[0];
+            NIR_PROPAGATE(launch_beam_reorder(bp + (int64_t)step * R, B, W, H, hn, p.s.h[0], gru ? nullptr : cn, gru ? nullptr : p.s.c[0],
+                                              step16 ? p.s.h16[1] : nullptr, step16 ? p.s.h16[0] : nullptr, st));
+        hp = p.s.h[0];
+        cp = p.s.c[0];
     }
     {
         ProfScope ps_("beam_backtrack_kernel", st);
@@ -635,7 +577,7 @@ extern "C" int nir_beam_gen_topk(const float* x, int64_t rows, int K, const floa
     NIR_REQUIRE(x && gen_w && workspace && top_val && top_idx && lse, "beam_gen_topk: null pointer");
     NIR_REQUIRE(rows >= 0 && rows < 0x7FFFFFFFLL && K > 0 && K % 4 == 0 && VT > 0, "beam_gen_topk: bad dims");
     NIR_REQUIRE(beam_dims_ok(W, VT), "beam_gen_topk: beam width outside [1, %d] or above VT", NIR_BEAM_MAX_W);
-    const bool fused = gen_frag != nullptr && s2s_fusable(K, VT) && !tun(g_tun.exact_f32);
+    const bool fused = s2s_gen_fused(gen_frag, K, VT);
     NIR_REQUIRE(fused || VT < 0x7FFFFFFFLL, "beam_gen_topk: VT too large for the GEMM path");
     if (rows == 0) return 0;
     if (workspace_bytes < nir_beam_gen_topk_workspace_bytes(rows, K, VT, W, fused)) {

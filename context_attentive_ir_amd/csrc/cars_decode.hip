@@ -483,18 +483,12 @@ extern "C" int nir_cars_decode_greedy(const float* dec_h, const float* dec_c, co
                                     NIR_ACT_NONE, st));
     hipLaunchKernelGGL(fill_i64_kernel, dim3((unsigned)((Bd + 255) / 256)), dim3(256), 0, st, p.tgt, bos, Bd);
     NIR_CHECK_LAUNCH("fill_i64_kernel");
-    LstmStepArgs a;
-    a.x[0] = table; a.xid[0] = p.tgt; a.xstride[0] = E;
-    a.wih[0] = w->rnn_wih; a.whh[0] = w->rnn_whh; a.bih[0] = w->rnn_bih; a.bhh[0] = w->rnn_bhh;
-    a.x[1] = nullptr; a.xid[1] = nullptr; a.xstride[1] = 0; a.wih[1] = a.whh[1] = a.bih[1] = a.bhh[1] = nullptr;
-    a.hprev[1] = a.cprev[1] = nullptr; a.hnext[1] = a.cnext[1] = nullptr;
-    a.chain0 = 0; a.B = (int)Bd; a.I = E; a.H = HD;
+    LstmStepArgs a = LstmStepArgs::token_fed(table, p.tgt, E, w->rnn_wih, w->rnn_whh, w->rnn_bih, w->rnn_bhh, Bd, HD);
     // fp16-term decoder step: emb(token) W_ih^T + b_ih + b_hh is a per-token row of the folded gate table (gathered by the previous step's ids),
     // the recurrent product runs on pre-split W_hh fragments and the state travels as term pairs next to its fp32 copy
     const bool step16 = w->rnn_gate_fold && w->rnn_whh_frag && HD % 32 == 0 && !tun(g_tun.exact_f32);
     if (step16) {
-        a.gx[0] = w->rnn_gate_fold; a.gxid[0] = p.tgt; a.gxstride = (int64_t)4 * HD; a.gx_unit_major = 1;
-        a.whh_frag[0] = w->rnn_whh_frag;
+        a.fold_token_fed(w->rnn_gate_fold, w->rnn_whh_frag);
         const int64_t n = Bd * HD;
         hipLaunchKernelGGL(h16_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dec_h, n, reinterpret_cast<_Float16*>(p.h16[1]));
         NIR_CHECK_LAUNCH("h16_pack_kernel");
@@ -603,15 +597,9 @@ extern "C" int nir_decode_greedy_plain_folded(const float* dec_h, const float* d
     // the decoder's input is the previous token's embedding alone: with a folded gate table + W_hh fragments (both or neither) the step gathers
     // its gate rows by token id and runs the recurrent product as fp16 term pairs, like nir_cars_decode_greedy
     const bool step16 = gate_fold && whh_frag && H % 32 == 0 && !tun(g_tun.exact_f32);
-    LstmStepArgs s;
-    s.x[0] = table; s.xid[0] = tgt; s.xstride[0] = E;
-    s.wih[0] = w_ih; s.whh[0] = w_hh; s.bih[0] = b_ih; s.bhh[0] = b_hh;
-    s.x[1] = nullptr; s.xid[1] = nullptr; s.xstride[1] = 0; s.wih[1] = s.whh[1] = s.bih[1] = s.bhh[1] = nullptr;
-    s.hprev[1] = s.cprev[1] = nullptr; s.hnext[1] = s.cnext[1] = nullptr;
-    s.chain0 = 0; s.B = (int)Bd; s.I = E; s.H = H;
+    LstmStepArgs s = LstmStepArgs::token_fed(table, tgt, E, w_ih, w_hh, b_ih, b_hh, Bd, H);
     if (step16) {
-        s.gx[0] = gate_fold; s.gxid[0] = tgt; s.gxstride = (int64_t)4 * H; s.gx_unit_major = 1;
-        s.whh_frag[0] = whh_frag;
+        s.fold_token_fed(gate_fold, whh_frag);
         const int64_t n = Bd * H;
         hipLaunchKernelGGL(h16_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dec_h, n, reinterpret_cast<_Float16*>(h16b[1]));
         NIR_CHECK_LAUNCH("h16_pack_kernel");

@@ -214,6 +214,25 @@ struct LstmStepArgs {
     const void* whh_frag[2] = {nullptr, nullptr};
     const _Float16* h16prev[2] = {nullptr, nullptr};
     _Float16* h16next[2] = {nullptr, nullptr};
+
+    // Host side, the greedy decoders: ONE chain (the second nulled) whose input row b is the embedding table[ids[b]] of the previous step's
+    // token.  The state pointers of chain 0 are the caller's to set at every step.
+    static LstmStepArgs token_fed(const float* table, const int64_t* ids, int E, const float* wih, const float* whh, const float* bih, const float* bhh,
+                                  int64_t B, int H) {
+        LstmStepArgs a;
+        a.x[0] = table; a.xid[0] = ids; a.xstride[0] = E;
+        a.wih[0] = wih; a.whh[0] = whh; a.bih[0] = bih; a.bhh[0] = bhh;
+        a.x[1] = nullptr; a.xid[1] = nullptr; a.xstride[1] = 0; a.wih[1] = a.whh[1] = a.bih[1] = a.bhh[1] = nullptr;
+        a.hprev[1] = a.cprev[1] = nullptr; a.hnext[1] = a.cnext[1] = nullptr;
+        a.chain0 = 0; a.B = (int)B; a.I = E; a.H = H;
+        return a;
+    }
+    // ... in its folded form (the fp16-term step): the gate rows come from the folded per-token table [V, 4H] (unit-major), gathered by the same
+    // ids, and the recurrent product runs on the pre-split W_hh fragments
+    void fold_token_fed(const float* gate_fold, const void* whh_fragments) {
+        gx[0] = gate_fold; gxid[0] = xid[0]; gxstride = (int64_t)4 * H; gx_unit_major = 1;
+        whh_frag[0] = whh_fragments;
+    }
 };
 int launch_lstm_step(const LstmStepArgs& a, int nchains, hipStream_t st);
 

@@ -345,15 +345,9 @@ extern "C" int nir_hredqs_decode_greedy(const float* h_steps, const float* c_ste
                        fast ? reinterpret_cast<_Float16*>(p.h16[1]) : nullptr);
     NIR_CHECK_LAUNCH("hq_pair_kernel");
     NIR_PROPAGATE(launch_fill_i64(p.tgt, bos, R, st));
-    LstmStepArgs a;
-    a.x[0] = table; a.xid[0] = p.tgt; a.xstride[0] = E;
-    a.wih[0] = w->rnn_wih; a.whh[0] = w->rnn_whh; a.bih[0] = w->rnn_bih; a.bhh[0] = w->rnn_bhh;
-    a.x[1] = nullptr; a.xid[1] = nullptr; a.xstride[1] = 0; a.wih[1] = a.whh[1] = a.bih[1] = a.bhh[1] = nullptr;
-    a.hprev[1] = a.cprev[1] = nullptr; a.hnext[1] = a.cnext[1] = nullptr;
-    a.chain0 = 0; a.B = (int)R; a.I = E; a.H = H;
+    LstmStepArgs a = LstmStepArgs::token_fed(table, p.tgt, E, w->rnn_wih, w->rnn_whh, w->rnn_bih, w->rnn_bhh, R, H);
     if (fast) {
-        a.gx[0] = w->rnn_gate_fold; a.gxid[0] = p.tgt; a.gxstride = (int64_t)4 * H; a.gx_unit_major = 1;
-        a.whh_frag[0] = w->rnn_whh_frag;
+        a.fold_token_fed(w->rnn_gate_fold, w->rnn_whh_frag);
         NIR_PROPAGATE((int)hipMemsetAsync(p.keys, 0, (size_t)max_len * R * ARGMAX_KEY_BUCKETS * sizeof(unsigned long long), st));
     }
     for (int step = 0; step < max_len; ++step) {

@@ -193,6 +193,8 @@ constexpr int S2S_MAX_WGS = 256;
 static inline int s2s_nbt(int K) { return K <= 512 ? 4 : 2; }
 static inline size_t s2s_lds(int K) { return (size_t)2 * 16 * s2s_nbt(K) * (K + 8) * sizeof(_Float16); }
 static inline bool s2s_fusable(int K, int64_t VT) { return K >= 32 && K <= 1024 && K % 32 == 0 && VT > 0 && VT < 0x7FFFFFF0LL; }
+// the fused generator runs (arg-max, statistics or top-k alike): the fragments are given, the shape has a fused form, tunable exact_f32 is off
+static inline bool s2s_gen_fused(const void* gen_frag, int K, int64_t VT) { return gen_frag != nullptr && s2s_fusable(K, VT) && !tun(g_tun.exact_f32); }
 
 // workgroups per row block: enough for the chip, at least ~2 tiles per wave
 static inline int s2s_nvr(int64_t Bd, int K, int64_t ntiles) {
@@ -213,14 +215,51 @@ int launch_acg_gen_select(const float* o, int64_t B, int K, const float* gen_w, 
                           float* pval, int* pidx, float* psum, const float* copy_w, const float* copy_b, const float* attn, int64_t attn_stride,
                           const int64_t* lens, int QL, const int64_t* src_map_idx, const int64_t* ext2tgt, const int64_t* ext2src, int CV,
                           const int64_t* tgt2src, int64_t V, int64_t* pred, int64_t pstride, int64_t* tgt, hipStream_t st);
-// csrc/seq2seq.hip, shared with the beam search of csrc/beam.hip: the weight checks, the fused-generator decision and the attention launch
-// (nsrc: decode row i attends over source row i % nsrc; 0 = one source row per decode row)
+// csrc/seq2seq.hip, shared with the beam search of csrc/beam.hip: the weight checks, the two decisions every decode makes once -- the fused
+// generator (s2s_gen_fused above, on the pack's fields) and the fp16-term cell step (both packs given, H a multiple of 32, tunable exact_f32
+// off) -- and the attention launch (nsrc: decode row i attends over source row i % nsrc; 0 = one source row per decode row)
 bool s2s_weights_ok(const nir_seq2seq_decoder_weights* w);
 bool s2s_fused(const nir_seq2seq_decoder_weights* w);
+bool s2s_step16(const nir_seq2seq_decoder_weights* w);
 int launch_attend(const float* q, const float* h, const float* mem, const float* sb, const float* v, const int64_t* lens, int64_t B, int QL, int H,
                   int mlp, float* cat, float* attn, int64_t attn_stride, hipStream_t st, int64_t nsrc = 0);
-// csrc/seq2seq.hip: the greedy decode of Seq2seq (acg == NULL) and of ACG; cell: the decoder's recurrence
+
+// ---- the attention-decoder step, once: cell -> (mlp: query GEMM) -> attention -> linear_out -----------------------------------------------------
+// The greedy decodes of Seq2seq and ACG (s2s_decode) and the beam search (csrc/beam.hip) are this stepper with a tail each behind linear_out:
+// arg-max, the copy generator's select, or top-k + select + reorder.  `rows` decode rows over `nsrc` source rows (greedy: B and B; beam: B W and B,
+// decode row i reads the banks of source row i % nsrc).  cell: the decoder's recurrence, S2S_CELL_LSTM (launch_lstm_step) or S2S_CELL_GRU
+// (launch_gru_step: no cell state, dec_c and the c buffers unused).
 constexpr int S2S_CELL_LSTM = 0, S2S_CELL_GRU = 1;
+struct S2sStepBufs {                                  // the stepper's part of a decode's workspace plan
+    float *sb, *h[2], *c[2], *h16[2], *qh, *cat, *ah, *logits, *gru;       // (logits: the plain generator of the tails; gru: the plain GRU step's gates)
+    int64_t* tgt;                                     // [rows] the token ids the next step reads
+};
+// takes sb .. logits, in this order; h16: with the fp16 term pairs of the state (the greedy plan always, the beam plan with the fp16-term step
+// only).  tgt and gru are taken by the caller's plan where they always lay among its own buffers, so every workspace keeps its layout.
+S2sStepBufs s2s_step_bufs(Workspace& a, int64_t rows, int64_t nsrc, int QL, int H, int64_t VT, int attn_type, bool fused, int cell, bool h16);
+struct S2sStepper {
+    const char* name;                                 // the entry's name: the prefix of every message
+    const nir_seq2seq_decoder_weights* w;
+    int cell;
+    const float *table, *memory_bank;
+    const int64_t* source_len;
+    int64_t V, rows, nsrc;
+    int E, QL;
+    hipStream_t st;
+    bool fused = false, step16 = false;               // set by check()
+    S2sStepBufs b{};                                  // set by the caller from its plan, in front of prepare()
+    const float* sb = nullptr;                        // the bank the scores are taken against (prepare())
+    LstmStepArgs a;
+    GruStepArgs ga;
+    // the argument checks of a decode entry, in its name; outputs: the entry's own output pointers are all given
+    int check(const float* dec_h, const float* dec_c, bool outputs, int64_t bos, int max_len);
+    // the score-bank GEMM, the BOS fill, the cell's arguments and, with the fp16-term step, dec_h as term pairs into h16first
+    int prepare(const float* dec_h, int64_t bos, float* h16first);
+    // one step from (hp, cp, h16prev) into (hn, cn, h16next); attention row i at attn_out + i * attn_stride.  Behind it b.ah [rows, H] is the
+    // attentional output and b.tgt still the ids the step read: the tail writes the next ones
+    int step(const float* hp, const float* cp, float* hn, float* cn, const float* h16prev, float* h16next, float* attn_out, int64_t attn_stride);
+};
+// csrc/seq2seq.hip: the greedy decode of Seq2seq (acg == NULL) and of ACG
 size_t s2s_decode_workspace_bytes(int64_t B, int QL, const nir_seq2seq_decoder_weights* w, const AcgDecode* acg, int cell);
 int s2s_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, const float* table,
                int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len, const nir_seq2seq_decoder_weights* w, void* workspace,

@@ -1,15 +1,22 @@
 // Seq2seq.decode -- greedy decoding of the attention encoder-decoder (neuroir/recommender/seq2seq.py:118-195; RNNDecoder:
 // decoders/decoder.py:120-177, decoders/rnn_decoder.py:19-90; GlobalAttention 'general' / 'dot' / 'mlp': modules/global_attention.py:81-211).
 //
-// Once per decode: the bank the scores are taken against
+// The step is written once, as the host-side S2sStepper (declared in s2s_gen.hpp, defined here): the argument checks, the two decisions (fused
+// generator, fp16-term cell step), the shared part of the workspace plan, prepare() and step().  Three decodes are that stepper with a tail each:
+// Seq2seq's greedy decode (arg-max) and ACG's (the copy generator of csrc/acg.hip) in s2s_decode below, the beam search in csrc/beam.hip.
+//
+// prepare(), once per decode: the bank the scores are taken against
 //   general: memq = bank W_in     (score_j = (W_in h) . m_j = h . (W_in^T m_j): one GEMM instead of one per step)
 //   dot:     memq = bank
 //   mlp:     memc = bank W_c^T
-// Per step, for all B rows at once (there is no input feed: the LSTM reads the previous token's embedding and its own state):
-//   (h,c) = LSTM(emb(tok), (h,c))                     lstm_step_kernel (folded gate rows + fp16 term pairs, or the fp32 step)
+// the BOS fill, the cell's arguments, and the initial state as fp16 term pairs when the fp16-term step runs.
+// step(), for all decode rows at once (there is no input feed: the cell reads the previous token's embedding and its own state):
+//   (h,c) = LSTM(emb(tok), (h,c))                     lstm_step_kernel (folded gate rows + fp16 term pairs, or the fp32 step);
+//   h = GRU(emb(tok), h)                              the kernels of csrc/gru_step.hip
 //   mlp only: qh = W_q h + b_q                        GEMM
-//   a = softmax_j(mask(score_j)); ctx = sum_j a_j m_j; cat = [ctx ; h]; attentions[b, step, :] = a          s2s_attend_kernel
+//   a = softmax_j(mask(score_j)); ctx = sum_j a_j m_j; cat = [ctx ; h]; the attention row a                s2s_attend_kernel
 //   o = linear_out(cat)  (+ tanh for general / dot; + bias, no tanh for mlp)                            GEMM + epilogue
+// The greedy tail of Seq2seq:
 //   tok' = argmax_v (W_g o + b_g)_v; tok = lut[tok']                                                    s2s_gen_argmax_kernel + argmax_finish_kernel
 //                                                                                                    (or GEMM + argmax_map_kernel)
 // Everything is enqueued on the caller's stream; no host synchronisation, no allocation, no float atomics.
@@ -130,28 +137,35 @@ int launch_attend(const float* q, const float* h, const float* mem, const float*
     return 0;
 }
 
+S2sStepBufs s2s_step_bufs(Workspace& a, int64_t rows, int64_t nsrc, int QL, int H, int64_t VT, int attn_type, bool fused, int cell, bool h16) {
+    S2sStepBufs b;
+    b.sb = a.take<float>(attn_type == NIR_S2S_ATTN_DOT ? 0 : (size_t)nsrc * QL * H);
+    for (int k = 0; k < 2; ++k) { b.h[k] = a.take<float>((size_t)rows * H); b.c[k] = a.take<float>(cell == S2S_CELL_GRU ? 0 : (size_t)rows * H); }
+    for (int k = 0; k < 2; ++k) b.h16[k] = a.take<float>(h16 ? (size_t)rows * H : 0);
+    b.qh = a.take<float>(attn_type == NIR_S2S_ATTN_MLP ? (size_t)rows * H : 0);
+    b.cat = a.take<float>((size_t)rows * 2 * H);
+    b.ah = a.take<float>((size_t)rows * H);
+    b.logits = a.take<float>(fused ? 0 : (size_t)rows * VT);
+    b.tgt = nullptr;
+    b.gru = nullptr;
+    return b;
+}
+
 struct S2sPlan {
-    float *sb, *h[2], *c[2], *h16[2], *qh, *cat, *ah, *logits, *pval;
+    S2sStepBufs s;
+    float* pval;
     int* pidx;
-    int64_t* tgt;
     float *psum, *csb, *cq, *ccat, *cattn;             // ACG only: the sums of the partials; a copy attention of its own
-    float* gru;                                        // GRU cell only: the gates of the plain step
     size_t bytes;
 };
 // acg: 0 = Seq2seq, 1 = ACG with reuse_copy_attn, 2 = ACG with a copy attention of its own
 static S2sPlan s2s_plan(void* ws, size_t cap, int64_t B, int QL, int H, int64_t VT, int attn_type, bool fused, int acg = 0, int cell = S2S_CELL_LSTM) {
     Workspace a(ws, cap);
     S2sPlan p;
-    p.sb = a.take<float>(attn_type == NIR_S2S_ATTN_DOT ? 0 : (size_t)B * QL * H);
-    for (int k = 0; k < 2; ++k) { p.h[k] = a.take<float>((size_t)B * H); p.c[k] = a.take<float>(cell == S2S_CELL_GRU ? 0 : (size_t)B * H); }
-    for (int k = 0; k < 2; ++k) p.h16[k] = a.take<float>((size_t)B * H);
-    p.qh = a.take<float>(attn_type == NIR_S2S_ATTN_MLP ? (size_t)B * H : 0);
-    p.cat = a.take<float>((size_t)B * 2 * H);
-    p.ah = a.take<float>((size_t)B * H);
-    p.logits = a.take<float>(fused ? 0 : (size_t)B * VT);
+    p.s = s2s_step_bufs(a, B, B, QL, H, VT, attn_type, fused, cell, true);
     p.pval = a.take<float>(fused ? (size_t)S2S_MAX_WGS * 4 * B : 0);
     p.pidx = a.take<int>(fused ? (size_t)S2S_MAX_WGS * 4 * B : 0);
-    p.tgt = a.take<int64_t>((size_t)B);
+    p.s.tgt = a.take<int64_t>((size_t)B);
     p.psum = p.csb = p.cq = p.ccat = p.cattn = nullptr;
     if (acg) {
         if (!fused) { p.pval = a.take<float>((size_t)B); p.pidx = a.take<int>((size_t)B); }      // one partial per row behind the GEMM
@@ -163,13 +177,12 @@ static S2sPlan s2s_plan(void* ws, size_t cap, int64_t B, int QL, int H, int64_t 
         p.ccat = a.take<float>((size_t)B * 2 * H);
         p.cattn = a.take<float>((size_t)B * QL);
     }
-    p.gru = cell == S2S_CELL_GRU ? a.take<float>(gru_step_scratch_floats(B, H)) : nullptr;
+    if (cell == S2S_CELL_GRU) p.s.gru = a.take<float>(gru_step_scratch_floats(B, H));
     p.bytes = align_up(a.off, 256);
     return p;
 }
-bool s2s_fused(const nir_seq2seq_decoder_weights* w) {
-    return w->gen_frag != nullptr && s2s_fusable(w->H, w->VT) && !tun(g_tun.exact_f32);
-}
+bool s2s_fused(const nir_seq2seq_decoder_weights* w) { return s2s_gen_fused(w->gen_frag, w->H, w->VT); }
+bool s2s_step16(const nir_seq2seq_decoder_weights* w) { return w->rnn_gate_fold && w->rnn_whh_frag && w->H % 32 == 0 && !tun(g_tun.exact_f32); }
 bool s2s_weights_ok(const nir_seq2seq_decoder_weights* w) {
     if (!w || w->H <= 0 || w->H % 4 || w->VT <= 0) return false;
     if (!(w->rnn_wih && w->rnn_whh && w->rnn_bih && w->rnn_bhh && w->attn_out_w && w->gen_w && w->gen_b)) return false;
@@ -177,6 +190,61 @@ bool s2s_weights_ok(const nir_seq2seq_decoder_weights* w) {
     if (w->attn_type == NIR_S2S_ATTN_DOT) return true;
     if (w->attn_type == NIR_S2S_ATTN_MLP) return w->attn_ctx_w && w->attn_query_w && w->attn_query_b && w->attn_v && w->attn_out_b;
     return false;
+}
+
+int S2sStepper::check(const float* dec_h, const float* dec_c, bool outputs, int64_t bos, int max_len) {
+    NIR_REQUIRE(dec_h && (dec_c || cell == S2S_CELL_GRU) && memory_bank && source_len && table && w && outputs, "%s: null pointer", name);
+    NIR_REQUIRE(s2s_weights_ok(w), "%s: decoder weights incomplete for the attention type, or H not a multiple of 4", name);
+    NIR_REQUIRE(nsrc >= 0 && QL > 0 && QL <= 4096 && max_len > 0 && V > 0 && E > 0 && E % 4 == 0, "%s: bad dims", name);
+    NIR_REQUIRE(bos >= 0 && bos < V, "%s: BOS id outside the vocabulary", name);
+    NIR_REQUIRE((w->rnn_gate_fold == nullptr) == (w->rnn_whh_frag == nullptr), "%s: rnn_gate_fold and rnn_whh_frag come together", name);
+    fused = s2s_fused(w);
+    NIR_REQUIRE(fused || w->VT < 0x7FFFFFFFLL, "%s: VT too large for the GEMM path", name);
+    step16 = s2s_step16(w);
+    return 0;
+}
+
+int S2sStepper::prepare(const float* dec_h, int64_t bos, float* h16first) {
+    const int H = w->H;
+    sb = memory_bank;
+    if (w->attn_type != NIR_S2S_ATTN_DOT) {              // general: memq = bank W_in (global_attention.py:98-105); mlp: memc = linear_context(bank) (:112-114)
+        NIR_PROPAGATE(launch_linear(memory_bank, H, nullptr, nullptr, 0, 0, 0, w->attn_type == NIR_S2S_ATTN_MLP ? w->attn_ctx_w : w->attn_in_wt, H, nullptr,
+                                    nullptr, b.sb, H, nsrc * QL, H, H, NIR_ACT_NONE, st));
+        sb = b.sb;
+    }
+    NIR_PROPAGATE(launch_fill_i64(b.tgt, bos, rows, st));
+    if (cell == S2S_CELL_GRU) {
+        ga.tok = b.tgt; ga.V = V; ga.table = table; ga.E = E;
+        ga.wih = w->rnn_wih; ga.bih = w->rnn_bih; ga.whh = w->rnn_whh; ga.bhh = w->rnn_bhh;
+        ga.scratch = b.gru; ga.B = rows; ga.H = H;
+        if (step16) { ga.gate_fold = w->rnn_gate_fold; ga.whh_frag = w->rnn_whh_frag; }
+    } else {
+        a = LstmStepArgs::token_fed(table, b.tgt, E, w->rnn_wih, w->rnn_whh, w->rnn_bih, w->rnn_bhh, rows, H);
+        if (step16) a.fold_token_fed(w->rnn_gate_fold, w->rnn_whh_frag);
+    }
+    if (step16) NIR_PROPAGATE(launch_h16_pack(dec_h, rows * H, reinterpret_cast<_Float16*>(h16first), st));
+    return 0;
+}
+
+int S2sStepper::step(const float* hp, const float* cp, float* hn, float* cn, const float* h16prev, float* h16next, float* attn_out, int64_t attn_stride) {
+    const int H = w->H;
+    const bool mlp = w->attn_type == NIR_S2S_ATTN_MLP;
+    if (step16) {
+        a.h16prev[0] = ga.h16prev = reinterpret_cast<const _Float16*>(h16prev);
+        a.h16next[0] = ga.h16next = reinterpret_cast<_Float16*>(h16next);
+    }
+    if (cell == S2S_CELL_GRU) {
+        ga.hprev = hp; ga.hnext = hn;
+        NIR_PROPAGATE(launch_gru_step(ga, st));
+    } else {
+        a.hprev[0] = hp; a.cprev[0] = cp; a.hnext[0] = hn; a.cnext[0] = cn;
+        NIR_PROPAGATE(launch_lstm_step(a, 1, st));
+    }
+    if (mlp)
+        NIR_PROPAGATE(launch_linear(hn, H, nullptr, nullptr, 0, 0, 0, w->attn_query_w, H, w->attn_query_b, nullptr, b.qh, H, rows, H, H, NIR_ACT_NONE, st));
+    NIR_PROPAGATE(launch_attend(mlp ? b.qh : hn, hn, memory_bank, sb, w->attn_v, source_len, rows, QL, H, mlp, b.cat, attn_out, attn_stride, st, nsrc));
+    return launch_linear(b.cat, 2 * H, nullptr, nullptr, 0, 0, 0, w->attn_out_w, 2 * H, mlp ? w->attn_out_b : nullptr, nullptr, b.ah, H, rows, H, 2 * H,
+                         mlp ? NIR_ACT_NONE : NIR_ACT_TANH, st);
 }
 
 static bool acg_weights_ok(const nir_seq2seq_decoder_weights* w, const AcgDecode* g) {
@@ -221,7 +289,7 @@ extern "C" int nir_seq2seq_gen_argmax(const float* x, int64_t rows, int K, const
     hipStream_t st = (hipStream_t)stream;
     NIR_REQUIRE(x && gen_w && predictions && next_tokens && workspace, "seq2seq_gen_argmax: null pointer");
     NIR_REQUIRE(rows >= 0 && K > 0 && K % 4 == 0 && VT > 0 && V > 0 && pred_stride >= 1, "seq2seq_gen_argmax: bad dims");
-    const bool fused = gen_frag != nullptr && s2s_fusable(K, VT) && !tun(g_tun.exact_f32);
+    const bool fused = s2s_gen_fused(gen_frag, K, VT);
     NIR_REQUIRE(fused || VT < 0x7FFFFFFFLL, "seq2seq_gen_argmax: VT too large for the GEMM path");
     if (workspace_bytes < nir_seq2seq_gen_argmax_workspace_bytes(rows, K, VT, fused)) {
         set_error("seq2seq_gen_argmax: workspace too small");
@@ -278,21 +346,16 @@ extern "C" int nir_seq2seq_gru_decode_greedy(const float* dec_h, const float* me
                            attentions, nullptr, nir::S2S_CELL_GRU, (hipStream_t)stream);
 }
 
-// The decode of both attention recommenders: acg == NULL is Seq2seq's (generator + arg-max), otherwise ACG's, whose step ends in the copy
-// generator of csrc/acg.hip instead -- and, without reuse_copy_attn, runs a second attention on the attentional output in front of it.
-// cell: the decoder's recurrence, S2S_CELL_LSTM (launch_lstm_step) or S2S_CELL_GRU (launch_gru_step: dec_c unused, no c buffers).
+// The greedy decode of both attention recommenders: the stepper (s2s_gen.hpp) with one of two tails behind the attentional output.  acg == NULL is
+// Seq2seq's (generator + arg-max); otherwise ACG's, the copy generator of csrc/acg.hip -- and, without reuse_copy_attn, a second attention on the
+// attentional output in front of it.  The state ping-pongs: step s writes slot s & 1 and reads the other.
 int nir::s2s_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, const float* table,
                     int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len, const nir_seq2seq_decoder_weights* w, void* workspace,
                     size_t workspace_bytes, int64_t* predictions, float* attentions, const AcgDecode* acg, int cell, hipStream_t st) {
-    const bool gru = cell == S2S_CELL_GRU;
-    NIR_REQUIRE(dec_h && (dec_c || gru) && memory_bank && source_len && table && w && predictions && attentions, "seq2seq_decode: null pointer");
-    NIR_REQUIRE(s2s_weights_ok(w), "seq2seq_decode: decoder weights incomplete for the attention type, or H not a multiple of 4");
-    NIR_REQUIRE(B >= 0 && QL > 0 && QL <= 4096 && max_len > 0 && V > 0 && E > 0 && E % 4 == 0, "seq2seq_decode: bad dims");
-    NIR_REQUIRE(bos >= 0 && bos < V, "seq2seq_decode: BOS id outside the vocabulary");
-    NIR_REQUIRE((w->rnn_gate_fold == nullptr) == (w->rnn_whh_frag == nullptr), "seq2seq_decode: rnn_gate_fold and rnn_whh_frag come together");
+    S2sStepper s{"seq2seq_decode", w, cell, table, memory_bank, source_len, V, B, B, E, QL, st};
+    NIR_PROPAGATE(s.check(dec_h, dec_c, predictions && attentions, bos, max_len));
     const int H = w->H;
-    const bool fused = s2s_fused(w);
-    NIR_REQUIRE(fused || w->VT < 0x7FFFFFFFLL, "seq2seq_decode: VT too large for the GEMM path");
+    const bool fused = s.fused;
     const bool own_copy_attn = acg && acg->cw && !acg->cw->reuse_copy_attn;
     if (acg) {
         NIR_REQUIRE(acg_weights_ok(w, acg), "acg_decode: copy weights incomplete for the attention type");
@@ -305,85 +368,42 @@ int nir::s2s_decode(const float* dec_h, const float* dec_c, const float* memory_
         return NIR_ERR_WORKSPACE;
     }
     if (B == 0) return 0;
+    s.b = p.s;
+    NIR_PROPAGATE(s.prepare(dec_h, bos, p.s.h16[1]));
     const bool mlp = w->attn_type == NIR_S2S_ATTN_MLP;
-    const float* sb = memory_bank;
-    if (w->attn_type == NIR_S2S_ATTN_GENERAL) {          // memq = bank W_in  (global_attention.py:98-105)
-        NIR_PROPAGATE(launch_linear(memory_bank, H, nullptr, nullptr, 0, 0, 0, w->attn_in_wt, H, nullptr, nullptr, p.sb, H, B * QL, H, H, NIR_ACT_NONE, st));
-        sb = p.sb;
-    } else if (mlp) {                                     // memc = linear_context(bank)  (global_attention.py:112-114)
-        NIR_PROPAGATE(launch_linear(memory_bank, H, nullptr, nullptr, 0, 0, 0, w->attn_ctx_w, H, nullptr, nullptr, p.sb, H, B * QL, H, H, NIR_ACT_NONE, st));
-        sb = p.sb;
-    }
-    const float* csb = memory_bank;                       // the score bank of ACG's own copy attention, the same forms
+    const float* csb = memory_bank;                       // the score bank of ACG's own copy attention, the forms of the stepper's
     if (own_copy_attn && w->attn_type != NIR_S2S_ATTN_DOT) {
         NIR_PROPAGATE(launch_linear(memory_bank, H, nullptr, nullptr, 0, 0, 0, mlp ? acg->cw->attn_ctx_w : acg->cw->attn_in_wt, H, nullptr, nullptr, p.csb, H,
                                     B * QL, H, H, NIR_ACT_NONE, st));
         csb = p.csb;
     }
-    NIR_PROPAGATE(launch_fill_i64(p.tgt, bos, B, st));
-    LstmStepArgs a;
-    a.x[0] = table; a.xid[0] = p.tgt; a.xstride[0] = E;
-    a.wih[0] = w->rnn_wih; a.whh[0] = w->rnn_whh; a.bih[0] = w->rnn_bih; a.bhh[0] = w->rnn_bhh;
-    a.x[1] = nullptr; a.xid[1] = nullptr; a.xstride[1] = 0; a.wih[1] = a.whh[1] = a.bih[1] = a.bhh[1] = nullptr;
-    a.hprev[1] = a.cprev[1] = nullptr; a.hnext[1] = a.cnext[1] = nullptr;
-    a.chain0 = 0; a.B = (int)B; a.I = E; a.H = H;
-    const bool step16 = w->rnn_gate_fold && w->rnn_whh_frag && H % 32 == 0 && !tun(g_tun.exact_f32);
-    GruStepArgs ga;
-    if (gru) {
-        ga.tok = p.tgt; ga.V = V; ga.table = table; ga.E = E;
-        ga.wih = w->rnn_wih; ga.bih = w->rnn_bih; ga.whh = w->rnn_whh; ga.bhh = w->rnn_bhh;
-        ga.scratch = p.gru; ga.B = B; ga.H = H;
-        if (step16) {
-            ga.gate_fold = w->rnn_gate_fold; ga.whh_frag = w->rnn_whh_frag;
-            NIR_PROPAGATE(launch_h16_pack(dec_h, B * H, reinterpret_cast<_Float16*>(p.h16[1]), st));
-        }
-    } else if (step16) {
-        a.gx[0] = w->rnn_gate_fold; a.gxid[0] = p.tgt; a.gxstride = (int64_t)4 * H; a.gx_unit_major = 1;
-        a.whh_frag[0] = w->rnn_whh_frag;
-        NIR_PROPAGATE(launch_h16_pack(dec_h, B * H, reinterpret_cast<_Float16*>(p.h16[1]), st));
-    }
     const float* hp = dec_h;
     const float* cp = dec_c;
     for (int step = 0; step < max_len; ++step) {
-        float* hn = p.h[step & 1];
-        float* cn = p.c[step & 1];
-        a.hprev[0] = hp; a.cprev[0] = cp; a.hnext[0] = hn; a.cnext[0] = cn;
-        if (step16) {
-            a.h16prev[0] = ga.h16prev = reinterpret_cast<const _Float16*>(p.h16[(step + 1) & 1]);
-            a.h16next[0] = ga.h16next = reinterpret_cast<_Float16*>(p.h16[step & 1]);
-        }
-        if (gru) {
-            ga.hprev = hp; ga.hnext = hn;
-            NIR_PROPAGATE(launch_gru_step(ga, st));
-        } else {
-            NIR_PROPAGATE(launch_lstm_step(a, 1, st));
-        }
-        if (mlp)
-            NIR_PROPAGATE(launch_linear(hn, H, nullptr, nullptr, 0, 0, 0, w->attn_query_w, H, w->attn_query_b, nullptr, p.qh, H, B, H, H, NIR_ACT_NONE, st));
-        NIR_PROPAGATE(launch_attend(mlp ? p.qh : hn, hn, memory_bank, sb, w->attn_v, source_len, B, QL, H, mlp, p.cat, attentions + (int64_t)step * QL,
-                                    (int64_t)max_len * QL, st));
-        NIR_PROPAGATE(launch_linear(p.cat, 2 * H, nullptr, nullptr, 0, 0, 0, w->attn_out_w, 2 * H, mlp ? w->attn_out_b : nullptr, nullptr, p.ah, H, B, H,
-                                    2 * H, mlp ? NIR_ACT_NONE : NIR_ACT_TANH, st));
+        float* hn = p.s.h[step & 1];
+        float* cn = p.s.c[step & 1];
+        NIR_PROPAGATE(s.step(hp, cp, hn, cn, p.s.h16[(step + 1) & 1], p.s.h16[step & 1], attentions + (int64_t)step * QL, (int64_t)max_len * QL));
+        const float* ah = p.s.ah;
         if (acg) {
             const float* ca = attentions + (int64_t)step * QL;                 // the copy attention: the std one, or the alignment of a second
             int64_t ca_stride = (int64_t)max_len * QL;                           // attention whose query is the attentional output (its own cat
             if (own_copy_attn) {                                                 // and linear_out take no part in the value)
                 if (mlp)
-                    NIR_PROPAGATE(launch_linear(p.ah, H, nullptr, nullptr, 0, 0, 0, acg->cw->attn_query_w, H, acg->cw->attn_query_b, nullptr, p.cq, H, B, H,
-                                                H, NIR_ACT_NONE, st));
-                NIR_PROPAGATE(launch_attend(mlp ? p.cq : p.ah, p.ah, memory_bank, csb, acg->cw->attn_v, source_len, B, QL, H, mlp, p.ccat, p.cattn, QL, st));
+                    NIR_PROPAGATE(launch_linear(ah, H, nullptr, nullptr, 0, 0, 0, acg->cw->attn_query_w, H, acg->cw->attn_query_b, nullptr, p.cq, H, B, H, H,
+                                                NIR_ACT_NONE, st));
+                NIR_PROPAGATE(launch_attend(mlp ? p.cq : ah, ah, memory_bank, csb, acg->cw->attn_v, source_len, B, QL, H, mlp, p.ccat, p.cattn, QL, st));
                 ca = p.cattn;
                 ca_stride = QL;
             }
-            NIR_PROPAGATE(launch_acg_gen_select(p.ah, B, H, w->gen_w, w->gen_b, fused ? w->gen_frag : nullptr, w->VT, p.logits, p.pval, p.pidx, p.psum,
+            NIR_PROPAGATE(launch_acg_gen_select(ah, B, H, w->gen_w, w->gen_b, fused ? w->gen_frag : nullptr, w->VT, p.s.logits, p.pval, p.pidx, p.psum,
                                                 acg->cw->copy_w, acg->cw->copy_b, ca, ca_stride, source_len, QL, acg->src_map_idx, acg->ext2tgt,
-                                                acg->ext2src, acg->CV, tgt2src, V, predictions + step, (int64_t)max_len, p.tgt, st));
+                                                acg->ext2src, acg->CV, tgt2src, V, predictions + step, (int64_t)max_len, p.s.tgt, st));
         } else if (fused) {
-            NIR_PROPAGATE(launch_gen_argmax(p.ah, w->gen_frag, w->gen_b, w->VT, B, H, p.pval, p.pidx, tgt2src, predictions + step, (int64_t)max_len, p.tgt,
-                                            V, st));
+            NIR_PROPAGATE(launch_gen_argmax(ah, w->gen_frag, w->gen_b, w->VT, B, H, p.pval, p.pidx, tgt2src, predictions + step, (int64_t)max_len, p.s.tgt, V,
+                                            st));
         } else {
-            NIR_PROPAGATE(launch_linear(p.ah, H, nullptr, nullptr, 0, 0, 0, w->gen_w, H, w->gen_b, nullptr, p.logits, w->VT, B, (int)w->VT, H, NIR_ACT_NONE, st));
-            NIR_PROPAGATE(launch_argmax_map(p.logits, w->VT, tgt2src, predictions + step, (int64_t)max_len, p.tgt, V, B, st));
+            NIR_PROPAGATE(launch_linear(ah, H, nullptr, nullptr, 0, 0, 0, w->gen_w, H, w->gen_b, nullptr, p.s.logits, w->VT, B, (int)w->VT, H, NIR_ACT_NONE, st));
+            NIR_PROPAGATE(launch_argmax_map(p.s.logits, w->VT, tgt2src, predictions + step, (int64_t)max_len, p.s.tgt, V, B, st));
         }
         hp = hn;
         cp = cn;

@@ -512,6 +512,18 @@ def fold_lstm_table(table, wih, bih, bhh, H, ndir, dtype):
     return out
 
 
+def fold_gru_table(table, wih, bih, bhh, H):
+    """the GRU decoders' folded gate table [V, 3H] (fp32) = table W_ih^T + b_ih + (b_hr, b_hz, 0): b_hn stays outside, it belongs inside the
+    reset product (csrc/gru_step.hip) -- weight packing, run once per parameter version (PackCache)."""
+    t = table.detach().float().contiguous()
+    bias = bih.clone()
+    bias[:2 * H] += bhh[:2 * H]
+    out = torch.empty(t.shape[0], 3 * H, device=t.device, dtype=torch.float32)
+    check(load().nir_linear_f32(ptr(t), t.shape[1], None, None, 0, 0, 0, ptr(wih), t.shape[1], ptr(bias), None, ptr(out), 3 * H, t.shape[0], 3 * H,
+                                t.shape[1], 0, stream()), "nir_linear_f32")
+    return out
+
+
 # bumped by anything that changes which kernels an entry point launches without touching a weight (debug tunables): part of the key of
 # graph_runner.PredictGraphCache, so a graph captured before the change is not replayed after it
 GRAPH_EPOCH = [0]

@@ -26,8 +26,7 @@ import torch.nn as nn
 
 from .. import autograd as A
 from .. import lib
-from ..constants import BOS, PAD, UNK
-from ..multitask import suggest
+from ..constants import PAD, UNK
 from .layers import CopyGeneratorParams
 from .seq2seq import Seq2seq, build_network, check_supported
 
@@ -87,16 +86,20 @@ def vocab_index(source_vocabs, src_dict, tgt_dict, CV=None):
 
 
 class ACG(Seq2seq):
+    _GREEDY_ENTRY = "nir_acg%s_decode"                   # + "_greedy" / "_workspace_bytes": nir_acg_decode_greedy, nir_acg_gru_decode_greedy
+
     def __init__(self, args):
         nn.Module.__init__(self)
+        name = type(self).__name__
         if not getattr(args, "copy_attn", False):
-            raise ValueError("recommender.ACG is the copy-generator model (copy_attn=True); without it build recommender.Seq2seq")
+            raise ValueError("recommender.%s is the copy-generator model (copy_attn=True); without it build recommender.%s"
+                             % (name, name.replace("ACG", "Seq2seq")))
         self.reuse_copy_attn = bool(getattr(args, "reuse_copy_attn", False))
         if args.attn_type in (None, "none"):                              # the reference's own failures (decoders/decoder.py:107-108;
             if self.reuse_copy_attn:                                      # modules/global_attention.py:64-65)
                 raise RuntimeError("Attn is turned off, so reuse_copy_attn flag must be false")
             raise AssertionError("Please select a valid attention type.")
-        check_supported(args, "ACG")
+        check_supported(args, name, self._CELL)
         build_network(self, args, own_copy_attn=not self.reuse_copy_attn)
         self.copy_attn = True
         self.force_copy = bool(getattr(args, "force_copy", False))
@@ -140,42 +143,24 @@ class ACG(Seq2seq):
         pred - VT of the row's dynamic dictionary), 'attentions': [B, max_len, QL] (the decoder's own attention)}.  The copy inputs are the
         reference's (`src_map` as a list of index tensors or the dense one-hot, `blank` / `fill`, `source_vocabs`) or the three index
         tensors (module docstring); `alignment` is unused, as in the reference's decode."""
-        if self.training:
-            raise NotImplementedError("HIP ACG.decode runs in eval mode")
-        B, QL = source_rep.shape
-        self._check_layers(B)
-        table = self.embedder.word_embeddings.table
-        lib.require_device(source_rep, source_len, table)
-        L = lib.load()
+        name = type(self).__name__
+        B, QL, table = self._decode_ready("decode", source_rep, source_len)
         if src_map_idx is None or ext2tgt is None or ext2src is None:
             src_map_idx, ext2tgt, ext2src = self.copy_index(QL, src_map, blank, fill, source_vocabs, src_dict, tgt_dict)
-        dev = table.device
-        idx, e2t, e2s = (lib.ids64(t).to(dev).contiguous() for t in (src_map_idx, ext2tgt, ext2src))
+        idx, e2t, e2s = (lib.ids64(t).to(table.device).contiguous() for t in (src_map_idx, ext2tgt, ext2src))
         CV = int(e2t.shape[1])
         if tuple(idx.shape) != (B, QL) or tuple(e2t.shape) != (B, CV) or tuple(e2s.shape) != (B, CV):
-            raise ValueError("ACG.decode: src_map_idx %s, ext2tgt %s, ext2src %s do not fit %d rows of width %d"
-                             % (tuple(idx.shape), tuple(e2t.shape), tuple(e2s.shape), B, QL))
-        src, _ = self._clean_ids(source_rep, None, table.shape[0])
-        lens = lib.ids64(source_len)
-        final, bank = self.encoder.encoder(A.embed(src, table), lens)
-        dec_h, dec_c = self.initial_state(final, lens)
-        bank = bank.float().contiguous()
-        w, cw = self._decoder_weights(), self._copy_weights()
-        if tgt2src is None:
-            tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, int(w.struct.VT), dev)
-        t = table.detach().float().contiguous()
-        max_len = int(max_len)
-        preds = torch.empty(B, max_len, dtype=torch.int64, device=dev)
-        attns = torch.empty(B, max_len, QL, dtype=torch.float32, device=dev)
-        if B > 0 and max_len > 0:
-            nb = L.nir_acg_decode_workspace_bytes(B, QL, CV, w.ref(), cw.ref())
+            raise ValueError("%s.decode: src_map_idx %s, ext2tgt %s, ext2src %s do not fit %d rows of width %d"
+                             % (name, tuple(idx.shape), tuple(e2t.shape), tuple(e2s.shape), B, QL))
+        cw = self._copy_weights()
+
+        def ws_bytes(size, B, QL, w):
+            nb = size(B, QL, CV, w.ref(), cw.ref())
             if nb == 0:
-                raise ValueError("ACG.decode: QL = %d / CV = %d outside the copy generator's range (QL <= 4096, 2 <= CV <= 1024)" % (QL, CV))
-            ws = lib.workspace(nb, dev)
-            lib.check(L.nir_acg_decode_greedy(lib.ptr(dec_h), lib.ptr(dec_c), lib.ptr(bank), lib.ptr(lens), B, QL, lib.ptr(t), t.shape[0], t.shape[1],
-                                              lib.ptr(tgt2src), BOS, max_len, w.ref(), cw.ref(), lib.ptr(idx), lib.ptr(e2t), lib.ptr(e2s), CV,
-                                              lib.ptr(ws), ws.numel(), lib.ptr(preds), lib.ptr(attns), lib.stream()), "nir_acg_decode_greedy")
-        return {"predictions": preds, "attentions": attns}
+                raise ValueError("%s.decode: QL = %d / CV = %d outside the copy generator's range (QL <= 4096, 2 <= CV <= 1024)" % (name, QL, CV))
+            return nb
+        return self._greedy(source_rep, source_len, max_len, src_dict, tgt_dict, tgt2src,
+                            extra=(cw.ref(), lib.ptr(idx), lib.ptr(e2t), lib.ptr(e2s), CV), ws_bytes=ws_bytes)
 
     # ---- train: teacher-forced loss ---------------------------------------------------------------------------------------------------
     def forward(self, source_rep, source_len, target_rep, target_len, target_seq, source_map=None, alignment=None):

@@ -53,19 +53,54 @@ def build_network(net, args, own_copy_attn=False):
 
 
 class Seq2seq(nn.Module, lib.IdCheck):
+    # ---- the decoder's cell, as data: everything else in this class, and in ACG, is written once over it (the GRU forms: seq2seq_gru.py) ----
+    _CELL = "LSTM"                                       # args.rnn_type this class is built for (check_supported)
+    _GATES = 4                                           # rows of W_ih / W_hh per hidden unit; the folded gate table is [V, _GATES H]
+    _WHH_PACK = "nir_lstm_step"                          # + "_whh_frag_bytes" / "_pack_whh_frag": W_hh as fp16 term fragments
+    _LAYER_CHECK = "Expected hidden[0] size (%d, %d, %d), got [1, %d, %d]"        # torch.nn.LSTM's text for a state of the wrong depth
+    _ENTRY_CELL = ""                                     # the cell's part of a C entry's name
+    _GREEDY_ENTRY = "nir_seq2seq%s_decode"               # + "_greedy" / "_workspace_bytes": nir_seq2seq_decode_greedy, nir_seq2seq_gru_decode_greedy
+    _BEAM_ENTRY = "nir_beam_seq2seq%s_decode"            # (+ "_workspace_bytes"): nir_beam_seq2seq_decode, nir_beam_seq2seq_gru_decode
+
+    @staticmethod
+    def _fold_table(table, wih, bih, bhh, H):
+        """the per-token gate rows of the folded step, [V, _GATES H]"""
+        return lib.fold_lstm_table(table, wih, bih, bhh, H, 1, "f32")
+
+    def _encode_train(self, x, lens):
+        """x [B,T,E] -> (memory bank [B,T,nhid], the final state tensors, each [B,nhid]) in ORIGINAL row order, differentiable: the register-resident
+        training recurrence up to 128 units per direction (it returns the cell states), one lstm_seq pass per direction beyond."""
+        mem, h_n, c_n = encode_train(self.encoder.encoder.rnns[0], x, lens)
+        return mem, (h_n, c_n)
+
+    def _cell_train(self, temb, state):
+        """the teacher-forced pass of the decoder's cell from `state` (already in the decoder's row order) -> every step's h [B,TL,nhid]"""
+        return A.lstm_seq(temb, self.decoder.decoder.rnn, *state)[0]
+
     def __init__(self, args):
         super().__init__()
+        name = type(self).__name__
         if getattr(args, "copy_attn", False):
-            raise NotImplementedError("HIP Seq2seq has no copy generator (copy_attn=True is ACG: build recommender.ACG, or wrappers.CopyRecommender "
-                                      "for the reference's batch layout)")
-        check_supported(args, "Seq2seq")
+            raise NotImplementedError("HIP %s has no copy generator (copy_attn=True is ACG: build recommender.%s, or wrappers.CopyRecommender "
+                                      "for the reference's batch layout)" % (name, name.replace("Seq2seq", "ACG")))
+        check_supported(args, name, self._CELL)
         build_network(self, args)
         self.copy_attn = False
 
     # ---- shared checks -----------------------------------------------------------------------------------------------------------
     def _check_layers(self, B):
         if self.nlayers != 1:
-            raise RuntimeError("Expected hidden[0] size (%d, %d, %d), got [1, %d, %d]" % (self.nlayers, B, self.nhid, B, self.nhid))
+            raise RuntimeError(self._LAYER_CHECK % (self.nlayers, B, self.nhid, B, self.nhid))
+
+    def _decode_ready(self, what, source_rep, source_len):
+        """what every decode checks before any launch (the layer check like the reference's failure) -> (B, QL, the embedding table)"""
+        if self.training:
+            raise NotImplementedError("HIP %s.%s runs in eval mode" % (type(self).__name__, what))
+        B, QL = source_rep.shape
+        self._check_layers(B)
+        table = self.embedder.word_embeddings.table
+        lib.require_device(source_rep, source_len, table)
+        return B, QL, table
 
     def _decoder_weights(self):
         rnn, att = self.decoder.decoder.rnn, self.decoder.decoder.attn
@@ -85,38 +120,28 @@ class Seq2seq(nn.Module, lib.IdCheck):
             dev = pk.keep["gen_w"].device
             if dev.type != "cuda":
                 return pk
-
-            def in_range(fn):
-                """a packed fragment, or None when a weight lies outside the fp16 range of the split (one blocking flag read per weight version)"""
-                flag = torch.zeros(1, dtype=torch.int32, device=dev)
-                frag = fn(flag)
-                return frag if int(flag.item()) == 0 else None
-
-            nb = L.nir_seq2seq_gen_frag_bytes(VT, H)
-            if self.fuse_generator_argmax and nb:
-                def gen(flag):
-                    frag = torch.empty(nb, dtype=torch.uint8, device=dev)
-                    lib.check(L.nir_seq2seq_pack_gen_frag(lib.ptr(pk.keep["gen_w"]), VT, H, lib.ptr(frag), lib.ptr(flag), lib.stream()),
-                              "nir_seq2seq_pack_gen_frag")
-                    return frag
-                frag = in_range(gen)
-                if frag is not None:
-                    pk.keep["gen_frag"] = frag
-                    pk.struct.gen_frag = frag.data_ptr()
-            nb = L.nir_lstm_step_whh_frag_bytes(H)
-            if (self.fold_decoder_step and nb and table.is_cuda and table.shape[1] == rnn.input_size
-                    and table.shape[0] * 4 * H * 4 <= self.fold_budget_bytes):
-                def whh(flag):
-                    frag = torch.empty(nb, dtype=torch.uint8, device=dev)
-                    lib.check(L.nir_lstm_step_pack_whh_frag(lib.ptr(pk.keep["rnn_whh"]), H, lib.ptr(frag), lib.ptr(flag), lib.stream()),
-                              "nir_lstm_step_pack_whh_frag")
-                    return frag
-                frag = in_range(whh)
-                if frag is not None:
-                    pk.keep["rnn_whh_frag"] = frag
-                    pk.keep["rnn_gate_fold"] = lib.fold_lstm_table(table, pk.keep["rnn_wih"], pk.keep["rnn_bih"], pk.keep["rnn_bhh"], H, 1, "f32")
-                    pk.struct.rnn_whh_frag = frag.data_ptr()
-                    pk.struct.rnn_gate_fold = pk.keep["rnn_gate_fold"].data_ptr()
+            # both packs behind ONE blocking flag read per weight version; a weight outside the fp16 range of the split leaves its plain form
+            flag = torch.zeros(2, dtype=torch.int32, device=dev)
+            gfrag = wfrag = None
+            nbg, nbw = L.nir_seq2seq_gen_frag_bytes(VT, H), getattr(L, self._WHH_PACK + "_whh_frag_bytes")(H)
+            if self.fuse_generator_argmax and nbg:
+                gfrag = torch.empty(nbg, dtype=torch.uint8, device=dev)
+                lib.check(L.nir_seq2seq_pack_gen_frag(lib.ptr(pk.keep["gen_w"]), VT, H, lib.ptr(gfrag), lib.ptr(flag), lib.stream()),
+                          "nir_seq2seq_pack_gen_frag")
+            if (self.fold_decoder_step and nbw and table.is_cuda and table.shape[1] == rnn.input_size
+                    and table.shape[0] * self._GATES * H * 4 <= self.fold_budget_bytes):
+                wfrag = torch.empty(nbw, dtype=torch.uint8, device=dev)
+                lib.check(getattr(L, self._WHH_PACK + "_pack_whh_frag")(lib.ptr(pk.keep["rnn_whh"]), H, lib.ptr(wfrag), lib.ptr(flag[1:]), lib.stream()),
+                          self._WHH_PACK + "_pack_whh_frag")
+            bad = flag.tolist() if (gfrag is not None or wfrag is not None) else [0, 0]
+            if gfrag is not None and bad[0] == 0:
+                pk.keep["gen_frag"] = gfrag
+                pk.struct.gen_frag = gfrag.data_ptr()
+            if wfrag is not None and bad[1] == 0:
+                pk.keep["rnn_whh_frag"] = wfrag
+                pk.keep["rnn_gate_fold"] = self._fold_table(table, pk.keep["rnn_wih"], pk.keep["rnn_bih"], pk.keep["rnn_bhh"], H)
+                pk.struct.rnn_whh_frag = wfrag.data_ptr()
+                pk.struct.rnn_gate_fold = pk.keep["rnn_gate_fold"].data_ptr()
             return pk
         params = list(self.decoder.parameters()) + list(self.generator.parameters())
         return self._pdec.get(params + [table, self.fold_decoder_step, self.fuse_generator_argmax, self.fold_budget_bytes], build)
@@ -128,25 +153,20 @@ class Seq2seq(nn.Module, lib.IdCheck):
         order = torch.sort(source_len, 0, True)[1]
         return tuple(torch.cat([s[d][order] for d in range(s.shape[0])], 1).contiguous() for s in final)
 
-    @torch.no_grad()
-    def decode(self, source_rep, source_len, max_len, src_dict, tgt_dict, src_map=None, alignment=None, blank=None, fill=None,
-               source_vocabs=None, tgt2src=None):
-        """seq2seq.py:118-195 (greedy) -> {'predictions': LongTensor [B, max_len] (target-vocabulary ids), 'attentions': [B, max_len, QL]}.
-        The reference maps each predicted token back to a source id on the host (tgt_dict[idx] -> word -> src_dict[word]); here that is one
-        device lookup table (identity without dictionaries).  attentions has the padded width QL of `source_rep` (the reference's has
-        max(source_len)); masked positions are exactly 0."""
-        if self.training:
-            raise NotImplementedError("HIP Seq2seq.decode runs in eval mode")
-        B, QL = source_rep.shape
-        self._check_layers(B)                                                # (before any launch, like the reference's failure)
-        table = self.embedder.word_embeddings.table
-        lib.require_device(source_rep, source_len, table)
+    def _encode_state(self, src, lens):
+        """eval: embedding -> encoder -> (the decoder's initial state tensors, each [B, nhid], paired as in initial_state; the bank [B, QL, nhid])"""
+        final, bank = self.encoder.encoder(A.embed(src, self.embedder.word_embeddings.table), lens)
+        state = self.initial_state(final, lens)
+        return (state if isinstance(state, tuple) else (state,)), bank.float().contiguous()
+
+    def _greedy(self, source_rep, source_len, max_len, src_dict, tgt_dict, tgt2src, extra=(), ws_bytes=None):
+        """the greedy decode of Seq2seq and ACG, either cell: encoder, the sorted-order pairing, ONE C call.  extra: the C arguments an entry takes
+        behind the decoder weights (ACG's copy inputs); ws_bytes(size entry, B, QL, weights): the workspace size where the entry's takes more."""
+        B, QL, table = self._decode_ready("decode", source_rep, source_len)
         L = lib.load()
         src, _ = self._clean_ids(source_rep, None, table.shape[0])
         lens = lib.ids64(source_len)
-        final, bank = self.encoder.encoder(A.embed(src, table), lens)
-        dec_h, dec_c = self.initial_state(final, lens)
-        bank = bank.float().contiguous()
+        state, bank = self._encode_state(src, lens)
         dev = bank.device
         w = self._decoder_weights()
         if tgt2src is None:
@@ -156,21 +176,24 @@ class Seq2seq(nn.Module, lib.IdCheck):
         preds = torch.empty(B, max_len, dtype=torch.int64, device=dev)
         attns = torch.empty(B, max_len, QL, dtype=torch.float32, device=dev)
         if B > 0 and max_len > 0:
-            ws = lib.workspace(L.nir_seq2seq_decode_workspace_bytes(B, QL, w.ref()), dev)
-            lib.check(L.nir_seq2seq_decode_greedy(lib.ptr(dec_h), lib.ptr(dec_c), lib.ptr(bank), lib.ptr(lens), B, QL, lib.ptr(t), t.shape[0], t.shape[1],
-                                                  lib.ptr(tgt2src), BOS, max_len, w.ref(), lib.ptr(ws), ws.numel(), lib.ptr(preds), lib.ptr(attns),
-                                                  lib.stream()), "nir_seq2seq_decode_greedy")
+            entry = self._GREEDY_ENTRY % self._ENTRY_CELL
+            size = getattr(L, entry + "_workspace_bytes")
+            ws = lib.workspace(size(B, QL, w.ref()) if ws_bytes is None else ws_bytes(size, B, QL, w), dev)
+            args = [lib.ptr(s) for s in state] + [lib.ptr(bank), lib.ptr(lens), B, QL, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(tgt2src), BOS, max_len,
+                                                  w.ref(), *extra, lib.ptr(ws), ws.numel(), lib.ptr(preds), lib.ptr(attns), lib.stream()]
+            lib.check(getattr(L, entry + "_greedy")(*args), entry + "_greedy")
         return {"predictions": preds, "attentions": attns}
 
+    @torch.no_grad()
+    def decode(self, source_rep, source_len, max_len, src_dict, tgt_dict, src_map=None, alignment=None, blank=None, fill=None,
+               source_vocabs=None, tgt2src=None):
+        """seq2seq.py:118-195 (greedy) -> {'predictions': LongTensor [B, max_len] (target-vocabulary ids), 'attentions': [B, max_len, QL]}.
+        The reference maps each predicted token back to a source id on the host (tgt_dict[idx] -> word -> src_dict[word]); here that is one
+        device lookup table (identity without dictionaries).  attentions has the padded width QL of `source_rep` (the reference's has
+        max(source_len)); masked positions are exactly 0."""
+        return self._greedy(source_rep, source_len, max_len, src_dict, tgt_dict, tgt2src)
+
     # ---- eval: beam search ---------------------------------------------------------------------------------------------------------
-    _BEAM_ENTRY = "nir_beam_seq2seq_decode"
-
-    def _beam_state(self, src, lens):
-        """encoder -> (the decoder's initial state tensors, each [B, nhid], in the sorted-order pairing of initial_state; the memory bank)"""
-        table = self.embedder.word_embeddings.table
-        final, bank = self.encoder.encoder(A.embed(src, table), lens)
-        return self.initial_state(final, lens), bank.float().contiguous()
-
     @torch.no_grad()
     def decode_beam(self, source_rep, source_len, max_len, beam_size, src_dict=None, tgt_dict=None, tgt2src=None, return_backptr=False):
         """Beam search of width `beam_size` (1 .. lib.BEAM_MAX_W) over max_len steps, no early stop (include/neuroir_beam.h)
@@ -183,10 +206,7 @@ class Seq2seq(nn.Module, lib.IdCheck):
         if self.copy_attn:
             raise NotImplementedError("HIP beam search covers Seq2seq and Seq2seqGRU; the copy generator of ACG has no beam (DESIGN.md section 21)")
         W = int(beam_size)
-        B, QL = source_rep.shape
-        self._check_layers(B)
-        table = self.embedder.word_embeddings.table
-        lib.require_device(source_rep, source_len, table)
+        B, QL, table = self._decode_ready("decode_beam", source_rep, source_len)
         L = lib.load()
         w = self._decoder_weights()
         VT = int(w.struct.VT)
@@ -194,8 +214,8 @@ class Seq2seq(nn.Module, lib.IdCheck):
             raise ValueError("decode_beam: beam_size %d outside [1, %d] or above the target vocabulary (%d)" % (W, lib.BEAM_MAX_W, VT))
         src, _ = self._clean_ids(source_rep, None, table.shape[0])
         lens = lib.ids64(source_len)
-        state, bank = self._beam_state(src, lens)
-        state = [s.repeat(W, 1).contiguous() for s in (state if isinstance(state, tuple) else (state,))]        # row k B + b
+        state, bank = self._encode_state(src, lens)
+        state = [s.repeat(W, 1).contiguous() for s in state]                  # row k B + b
         dev = bank.device
         ws_ref = w.ref()
         if not self.fuse_generator_topk and w.struct.gen_frag:
@@ -211,19 +231,15 @@ class Seq2seq(nn.Module, lib.IdCheck):
         if return_backptr:
             out["backptr"] = torch.empty(max_len, B, W, dtype=torch.int32, device=dev)
         if B > 0 and max_len > 0:
-            ws = lib.workspace(getattr(L, self._BEAM_ENTRY + "_workspace_bytes")(B, QL, W, max_len, ws_ref), dev)
+            entry = self._BEAM_ENTRY % self._ENTRY_CELL
+            ws = lib.workspace(getattr(L, entry + "_workspace_bytes")(B, QL, W, max_len, ws_ref), dev)
             args = [lib.ptr(s) for s in state] + [lib.ptr(bank), lib.ptr(lens), B, QL, W, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(tgt2src), BOS,
                                                   max_len, ws_ref, lib.ptr(ws), ws.numel(), lib.ptr(out["predictions"]), lib.ptr(out["scores"]),
                                                   lib.ptr(out["lengths"]), lib.ptr(out["attentions"]), lib.ptr(out.get("backptr")), lib.stream()]
-            lib.check(getattr(L, self._BEAM_ENTRY)(*args), self._BEAM_ENTRY)
+            lib.check(getattr(L, entry)(*args), entry)
         return out
 
     # ---- train: teacher-forced loss ---------------------------------------------------------------------------------------------------
-    def _encode_train(self, x, lens):
-        """x [B,T,E] -> (memory bank [B,T,nhid], h_n [B,nhid], c_n [B,nhid]) in ORIGINAL row order, differentiable: the register-resident
-        training recurrence up to 128 units per direction (it returns the cell states), one lstm_seq pass per direction beyond."""
-        return encode_train(self.encoder.encoder.rnns[0], x, lens)
-
     def _align(self, h_all, mem, att=None):
         """global_attention.py:81-119 -> [B, TL, QL] (tiny: tensor glue around the library's linears, as in multitask/cars.py)"""
         att = self.decoder.decoder.attn if att is None else att
@@ -252,13 +268,12 @@ class Seq2seq(nn.Module, lib.IdCheck):
         src, tgt = self._clean_ids(source_rep, target_rep, table.shape[0])
         lens = lib.ids64(source_len)
         pe = self.embedder.dropout.p
-        mem, h_n, c_n = self._encode_train(A.dropout(A.embed(src, table), pe, tr), lens)
+        mem, final = self._encode_train(A.dropout(A.embed(src, table), pe, tr), lens)
         mem = A.dropout(mem, self.dropout.p, tr)
         order = torch.sort(lens, 0, True)[1]                                 # the reference's length-sorted final state (see the module docstring)
-        dec_h, dec_c = h_n[order], c_n[order]
         temb = A.dropout(A.embed(tgt, table), pe, tr)
-        rnn, att = self.decoder.decoder.rnn, self.decoder.decoder.attn
-        h_all, _ = A.lstm_seq(temb, rnn, dec_h, dec_c)                       # [B,TL,nhid]
+        att = self.decoder.decoder.attn
+        h_all = self._cell_train(temb, [s[order].contiguous() for s in final])          # [B,TL,nhid]
         TL = h_all.shape[1]
         align = self._align(h_all, mem)
         mask = torch.arange(QL, device=mem.device).unsqueeze(0) < lens.unsqueeze(1)          # [B,QL]: the TL rows of a source share it
