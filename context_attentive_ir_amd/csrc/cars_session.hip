@@ -15,6 +15,7 @@
 //   1 rank projection GEMM (W_q | W_shared + W_priv1 packed once per weight version), 1 feature kernel, 3 maxout GEMMs
 #include "split2.hpp"
 #include <algorithm>
+#include <mutex>
 
 namespace nir {
 
@@ -85,7 +86,10 @@ __global__ __launch_bounds__(256) void click_pool2_kernel(const float* __restric
     const float ex = keep ? expf(lg - mx) : 0.f;
     const float p = ex / wave_sum(ex);   // all masked -> NaN, exactly like softmax of all -inf in the reference
     const int nch = D >> 2;
-    for (int c = lane; c < nch; c += 64) {
+    // The whole wave walks the loop (lanes past D / 4 on a clamped column, their store masked): a readlane of p executed by SOME lanes only
+    // returns an undefined value for a lane that is not among them -- with D = 64 (16 lanes) and N = 63 every weight from k = 16 on was garbage.
+    for (int c0 = 0; c0 < nch; c0 += 64) {
+        const int c = c0 + lane < nch ? c0 + lane : 0;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll 8
         for (int k = 0; k < N; ++k) {                     // 8 independent 1 KB row reads in flight
@@ -93,7 +97,7 @@ __global__ __launch_bounds__(256) void click_pool2_kernel(const float* __restric
             const float4 v = *reinterpret_cast<const float4*>(docs + ((int64_t)r * N + k) * D + 4 * c);
             acc.x = fmaf(pk, v.x, acc.x); acc.y = fmaf(pk, v.y, acc.y); acc.z = fmaf(pk, v.z, acc.z); acc.w = fmaf(pk, v.w, acc.w);
         }
-        *reinterpret_cast<float4*>(clicks + (int64_t)r * D + 4 * c) = acc;
+        if (c0 + lane < nch) *reinterpret_cast<float4*>(clicks + (int64_t)r * D + 4 * c) = acc;
     }
 }
 
@@ -829,6 +833,8 @@ extern "C" int nir_cars_rank_session_pre(const float* pooled_q, const float* poo
     NIR_REQUIRE(!rank_docs || (NR > 0 && NR <= N), "cars_rank_session: the ranked candidate slice must hold 1..N candidates (got %d)", NR);
     NIR_REQUIRE(S <= 4096, "cars_rank_session: session length %d > 4096 unsupported", S);
     NIR_REQUIRE(!m_groups || (sessions_per_group > 0 && !labels_all), "cars_rank_session: m_groups needs sessions_per_group > 0 and excludes labels_all");
+    NIR_REQUIRE(!m_groups || B % sessions_per_group == 0, "cars_rank_session: B = %d is not a whole number of blocks of %d sessions", B, sessions_per_group);
+    NIR_REQUIRE(!extra || nch > 0, "cars_rank_session: decoder states need at least one session encoder");
     NIR_REQUIRE(w->D % 64 == 0 && w->HS % 16 == 0 && w->D % 16 == 0, "cars_rank_session: D %% 64 / HS %% 16 required");
     if (B == 0) return 0;
     const int D = w->D, HS = w->HS, NP = D / 16;
@@ -866,9 +872,13 @@ extern "C" int nir_cars_rank_session_pre(const float* pooled_q, const float* poo
             if (N <= 64)
                 hipLaunchKernelGGL(click_pool2_kernel, dim3((unsigned)((BS + 3) / 4)), dim3(256), 0, st, pooled_docs, p.epart, NP, w->click3_b, labels,
                                    lall, rall, m_groups, sessions_per_group * S, (int)BS, N, D, clicks);
-            else
+            else {
+                // 4 waves x 2 x N floats: exactly 64 KiB at the N = 2048 limit, on top of the kernel's 16 static bytes
+                static std::once_flag once;
+                std::call_once(once, [] { (void)hipFuncSetAttribute((const void*)click_pool_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 2048 * (int)sizeof(float)); });
                 hipLaunchKernelGGL(click_pool_big_kernel, dim3((unsigned)((BS + 3) / 4)), dim3(256), (size_t)4 * 2 * N * sizeof(float), st, pooled_docs,
                                    p.epart, NP, w->click3_b, labels, lall, rall, m_groups, sessions_per_group * S, (int)BS, N, D, clicks);
+            }
         }
         NIR_CHECK_LAUNCH("click_pool2_kernel");
     }
@@ -941,7 +951,6 @@ extern "C" int nir_cars_rank_session_pre(const float* pooled_q, const float* poo
     }
     if (want_states) {
         // ---- suggestion-side outputs (cars.py:382-456): inner attention pools and the decoder initial states
-        NIR_REQUIRE(nch > 0, "cars_rank_session: decoder states need at least one session encoder");
         const float* st_a = q_on ? p.Qs : p.Ds;
         const float* st_b = (q_on && d_on) ? p.Ds : nullptr;
         const float* c_a = q_on ? p.Cq : p.Cd;

@@ -643,7 +643,16 @@ int nir_cars_rank_session_shard(const float* pooled_q, const float* pooled_docs,
  * iterates the session axis with batch-parallel ops only), so the scores of a block equal the rows of the unsharded call.
  * m_groups != NULL (excludes labels_all): the B sessions are `B / sessions_per_group` consecutive blocks that come from DIFFERENT batches
  * (several batches' blocks merged into one call so that the session LSTM weights are streamed once for all of them); block g uses
- * m_groups[g] (device ints from nir_cars_click_max over each batch's full label matrix). */
+ * m_groups[g] (device ints from nir_cars_click_max over each batch's full label matrix).  B % sessions_per_group must be 0 (checked:
+ * m_groups holds exactly B / sessions_per_group entries, a ragged last block would read past it).
+ * Limits, all checked on the host before anything is enqueued (NIR_ERR_BAD_ARG, nothing written): 1 <= N <= 2048, 1 <= S <= 4096,
+ * D % 64 == 0, HS % 16 == 0, rank_docs given: 1 <= NR <= N, labels_all given: B*S <= rows_all < 2^30, the document session on: labels given,
+ * the ranker on: wrank (and attn_ut with a session encoder on) packed, `extra` given: at least one session encoder on.  A workspace below
+ * nir_cars_session_workspace_bytes(B, S, N, w) is NIR_ERR_WORKSPACE.  B == 0 returns 0 and enqueues nothing.
+ * A (session, step) row without a click while m == N has every candidate masked: that row of clicks_out is NaN (softmax over all -inf in the
+ * reference) and so is everything of that session computed from it -- the document chain from that step on, hence its scores at later steps,
+ * its dec_h / dec_c rows and inner_d; other sessions are not affected.
+ * S == 1: dec_h / dec_c have no rows and are not written.  rank_on == 0: click_scores is not written (may be NULL). */
 int nir_cars_rank_session_rows(const float* pooled_q, const float* pooled_docs, const float* labels, int B, int S, int N,
                                const nir_cars_session_weights* w /*host*/, void* workspace, size_t workspace_bytes,
                                float* click_scores, float* clicks_out, const nir_cars_session_outputs* extra /*host*/,
