@@ -560,7 +560,269 @@ static int s2s_beam_decode(const float* dec_h, const float* dec_c, const float* 
     return 0;
 }
 
+
+// =================================================================================================================================================
+// The session models' beams (include/neuroir_session_beam.h): the CARS decoder (csrc/cars_decode.hip's step over R = Bd W
+// rows) and the decoders without attention of M_MATCH_TENSOR / MNSRF, with the tail above behind them.  "Source row" = decode row of the greedy
+// decode: beam row r = k Bd + i reads what decode row i reads (memory bank rowmap[i], session term i).  Nothing is repeated by the caller.
+// =================================================================================================================================================
+
+// out row r = in row r % Bd for the two states (H4 float4 per row), and map_out[r] = map_in[r % Bd] (map_in NULL: no map)
+__global__ __launch_bounds__(256) void beam_repeat_kernel(const float4* __restrict__ h_in, const float4* __restrict__ c_in, int64_t Bd, int H4,
+                                                          float4* __restrict__ h_out, float4* __restrict__ c_out, const int64_t* __restrict__ map_in,
+                                                          int64_t* __restrict__ map_out) {
+    const int64_t r = blockIdx.x, i = r % Bd;
+    for (int f = threadIdx.x; f < H4; f += 256) {
+        h_out[r * H4 + f] = h_in[i * H4 + f];
+        c_out[r * H4 + f] = c_in[i * H4 + f];
+    }
+    if (map_in && threadIdx.x == 0) map_out[r] = map_in[i];
+}
+
+// The backtrack without attention rows: one thread per output (source row b, output beam j).
+__global__ __launch_bounds__(256) void beam_backtrack_tokens_kernel(const int* __restrict__ tok, const int* __restrict__ bp, const float* __restrict__ cum,
+                                                                    int64_t B, int W, int max_len, int64_t* __restrict__ pred, float* __restrict__ scores,
+                                                                    int64_t* __restrict__ lengths) {
+    const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;        // b W + j
+    if (o >= B * W) return;
+    const int64_t b = o / W;
+    int k = (int)(o - b * W);
+    int len = max_len;
+    for (int t = max_len - 1; t >= 0; --t) {
+        const int64_t slot = ((int64_t)t * B + b) * W + k;
+        const int tk = tok[slot];
+        int src = bp[slot];
+        src = src < 0 ? 0 : (src >= W ? W - 1 : src);
+        if (tk == NIR_BEAM_EOS) len = t + 1;
+        pred[o * max_len + t] = tk;
+        k = src;
+    }
+    scores[o] = cum[o];
+    lengths[o] = len;
+}
+
+// The beam's own buffers behind a decoder's step buffers (the tail of BeamPlan without the attention rows).
+struct SessBeamBufs {
+    float *pval, *pm, *ps, *cum, *logits;
+    int *pidx, *fin, *bp, *tok;
+    int64_t* tgt;
+    int nparts;
+};
+static SessBeamBufs sess_beam_bufs(Workspace& a, int64_t R, int W, int max_len, int K, int64_t VT, bool fused, bool own_bp) {
+    SessBeamBufs p;
+    p.nparts = fused ? beam_nparts(R, K, VT) : 1;
+    p.logits = a.take<float>(fused ? 0 : (size_t)R * VT);
+    p.pval = a.take<float>((size_t)p.nparts * R * W);
+    p.pidx = a.take<int>((size_t)p.nparts * R * W);
+    p.pm = a.take<float>((size_t)p.nparts * R);
+    p.ps = a.take<float>(fused ? (size_t)p.nparts * R : 0);
+    p.tgt = a.take<int64_t>((size_t)R);
+    p.cum = a.take<float>((size_t)R);
+    p.fin = a.take<int>((size_t)R);
+    p.bp = a.take<int>(own_bp ? (size_t)max_len * R : 0);
+    p.tok = a.take<int>((size_t)max_len * R);
+    return p;
+}
+// (lse, top-W) partials of the generator over x [R, K]: the fused kernel, or the fp32 GEMM into logits + one workgroup per row
+static int sess_beam_gen(const SessBeamBufs& p, bool fused, const float* x, int64_t R, int K, const float* gen_w, const float* gen_b, const void* gen_frag,
+                         int64_t VT, int W, hipStream_t st) {
+    if (fused) return launch_beam_gen_topk(x, gen_frag, gen_b, VT, R, K, W, p.pval, p.pidx, p.pm, p.ps, st);
+    NIR_PROPAGATE(launch_linear(x, K, nullptr, nullptr, 0, 0, 0, gen_w, K, gen_b, nullptr, p.logits, VT, R, (int)VT, K, NIR_ACT_NONE, st));
+    return launch_beam_row_topk(p.logits, VT, R, W, p.pval, p.pidx, p.pm, st);
+}
+// select + (all steps but the last) the state shuffle from slot 1 into slot 0
+static int sess_beam_tail(const SessBeamBufs& p, bool fused, int step, int max_len, int64_t Bd, int W, int H, int64_t VT, const int64_t* tgt2src, int64_t V,
+                          int* bp, float* const* h, float* const* c, float* const* h16, bool step16, hipStream_t st) {
+    const int64_t R = Bd * W;
+    NIR_PROPAGATE(launch_beam_select(p.pval, p.pidx, p.pm, fused ? p.ps : nullptr, p.nparts, Bd, W, VT, tgt2src, V, p.cum, p.fin, bp + (int64_t)step * R,
+                                     p.tok + (int64_t)step * R, p.tgt, st));
+    if (step + 1 < max_len)
+        NIR_PROPAGATE(launch_beam_reorder(bp + (int64_t)step * R, Bd, W, H, h[1], h[0], c[1], c[0], step16 ? h16[1] : nullptr, step16 ? h16[0] : nullptr, st));
+    return 0;
+}
+static int sess_beam_begin(const SessBeamBufs& p, const float* dec_h, const float* dec_c, int64_t Bd, int W, int H, float* h0, float* c0, float* h16first,
+                           bool step16, const int64_t* map_in, int64_t* map_out, int64_t bos, hipStream_t st) {
+    const int64_t R = Bd * W;
+    hipLaunchKernelGGL(beam_repeat_kernel, dim3((unsigned)R), dim3(256), 0, st, (const float4*)dec_h, (const float4*)dec_c, Bd, H / 4, (float4*)h0, (float4*)c0,
+                       map_in, map_out);
+    NIR_CHECK_LAUNCH("beam_repeat_kernel");
+    if (step16) NIR_PROPAGATE(launch_h16_pack(h0, R * H, reinterpret_cast<_Float16*>(h16first), st));
+    NIR_PROPAGATE(launch_fill_i64(p.tgt, bos, R, st));
+    hipLaunchKernelGGL(beam_init_kernel, g1(R), dim3(256), 0, st, p.cum, p.fin, R, W);
+    NIR_CHECK_LAUNCH("beam_init_kernel");
+    return 0;
+}
+static int sess_beam_end(const SessBeamBufs& p, const int* bp, int64_t Bd, int W, int max_len, int64_t* predictions, float* scores, int64_t* lengths,
+                         hipStream_t st) {
+    {
+        ProfScope ps_("beam_backtrack_tokens_kernel", st);
+        hipLaunchKernelGGL(beam_backtrack_tokens_kernel, g1(Bd * W), dim3(256), 0, st, p.tok, bp, p.cum, Bd, W, max_len, predictions, scores, lengths);
+    }
+    NIR_CHECK_LAUNCH("beam_backtrack_tokens_kernel");
+    return 0;
+}
+
+// ---- CARS ----------------------------------------------------------------------------------------------------------------------------------
+// The step of nir_cars_decode_greedy restated over R rows (its keyed arg-max path ties the greedy loop's launches to its own tail; the greedy
+// entry stays as it is): prepare once -- the banks mem / memq over the source rows, the session projection over the R rows through the
+// repeated rowmap -- then per step lstm step, (linear_in,) dec_attend, linear_out + tanh, pred1 + session term.
+struct CarsBeamPlan {
+    float *mem, *memq, *sess, *h[2], *c[2], *h16[2], *qv, *cat, *ah, *p1;
+    int64_t* rowmap;
+    SessBeamBufs b;
+    size_t bytes;
+};
+static bool cars_beam_step16(const nir_cars_decoder_weights* w) { return w->rnn_gate_fold && w->rnn_whh_frag && w->HD % 32 == 0 && !tun(g_tun.exact_f32); }
+static CarsBeamPlan cars_beam_plan(void* ws, size_t cap, int64_t rows_src, int64_t Bd, int QL, int W, int max_len, const nir_cars_decoder_weights* w,
+                                   bool fused, bool own_bp) {
+    Workspace a(ws, cap);
+    CarsBeamPlan p;
+    const int64_t R = Bd * W;
+    const int HD = w->HD, P = w->P;
+    const bool foldq = w->attn_q_w != nullptr, step16 = cars_beam_step16(w);
+    p.mem = a.take<float>((size_t)rows_src * QL * HD);
+    p.memq = a.take<float>(foldq ? (size_t)rows_src * QL * HD : 0);
+    p.sess = a.take<float>(w->KS > 0 ? (size_t)R * P : 0);
+    for (int k = 0; k < 2; ++k) { p.h[k] = a.take<float>((size_t)R * HD); p.c[k] = a.take<float>((size_t)R * HD); }
+    for (int k = 0; k < 2; ++k) p.h16[k] = a.take<float>(step16 ? (size_t)R * HD : 0);
+    p.qv = a.take<float>(foldq ? 0 : (size_t)R * HD);
+    p.cat = a.take<float>((size_t)R * 2 * HD);
+    p.ah = a.take<float>((size_t)R * HD);
+    p.p1 = a.take<float>((size_t)R * P);
+    p.rowmap = a.take<int64_t>((size_t)R);
+    p.b = sess_beam_bufs(a, R, W, max_len, P, w->VT, fused, own_bp);
+    p.bytes = align_up(a.off, 256);
+    return p;
+}
+static bool cars_beam_weights_ok(const nir_cars_decoder_weights* w) {
+    return w && w->rnn_wih && w->rnn_whh && w->rnn_bih && w->rnn_bhh && w->attn_out_w && w->dec_attn_w && w->pred1_w && w->pred2_w &&
+           (w->attn_in_w || w->attn_q_w) && w->HD > 0 && w->DQ > 0 && w->P > 0 && w->KS >= 0 && w->VT > 0 && w->HD % 4 == 0 && w->DQ % 4 == 0 && w->P % 4 == 0;
+}
+
 }  // namespace nir
+
+extern "C" size_t nir_beam_cars_decode_workspace_bytes(int64_t rows_src, int64_t Bd, int QL, int W, int max_len, const nir_cars_decoder_weights* w, int fused) {
+    using namespace nir;
+    if (!cars_beam_weights_ok(w) || rows_src < 0 || Bd < 0 || QL <= 0 || max_len <= 0 || !beam_dims_ok(W, w->VT)) return 0;
+    return cars_beam_plan(nullptr, 0, rows_src, Bd, QL, W, max_len, w, fused && s2s_fusable(w->P, w->VT) && !tun(g_tun.exact_f32), true).bytes;
+}
+
+extern "C" int nir_beam_cars_decode(const float* dec_h, const float* dec_c, const float* encoded_source, const int64_t* source_len, int64_t rows_src, int QL,
+                                    const int64_t* rowmap, int64_t Bd, const float* session_cat, const float* table, int64_t V, int E,
+                                    const int64_t* tgt2src, int64_t bos, int max_len, const nir_cars_decoder_weights* w, const void* gen_frag, int W,
+                                    void* workspace, size_t workspace_bytes, int64_t* predictions, float* scores, int64_t* lengths, int32_t* backptr,
+                                    nir_stream_t stream) {
+    using namespace nir;
+    hipStream_t st = (hipStream_t)stream;
+    NIR_REQUIRE(dec_h && dec_c && encoded_source && source_len && rowmap && table && w && predictions && scores && lengths, "beam_cars_decode: null pointer");
+    NIR_REQUIRE(cars_beam_weights_ok(w), "beam_cars_decode: null weight pointer or bad dims (HD, DQ, P multiples of 4)");
+    NIR_REQUIRE(rows_src > 0 && Bd >= 0 && QL > 0 && max_len > 0 && V > 0 && E > 0 && E % 4 == 0, "beam_cars_decode: bad dims");
+    NIR_REQUIRE(w->KS == 0 || (session_cat && w->sess_w), "beam_cars_decode: session representation / packed projector missing");
+    NIR_REQUIRE(bos >= 0 && bos < V, "beam_cars_decode: BOS id outside the vocabulary");
+    NIR_REQUIRE(beam_dims_ok(W, w->VT), "beam_cars_decode: beam width outside [1, %d] or above the target vocabulary", NIR_BEAM_MAX_W);
+    NIR_REQUIRE(Bd * NIR_BEAM_MAX_W < 0x7FFFFFFFLL && w->VT < 0x7FFFFFF0LL, "beam_cars_decode: too many decode rows or target tokens");
+    const int HD = w->HD, P = w->P;
+    const int64_t R = Bd * W, VT = w->VT;
+    const bool fused = s2s_gen_fused(gen_frag, P, VT), foldq = w->attn_q_w != nullptr, step16 = cars_beam_step16(w);
+    CarsBeamPlan p = cars_beam_plan(workspace, workspace_bytes, rows_src, Bd, QL, W, max_len, w, fused, backptr == nullptr);
+    if (!workspace || p.bytes > workspace_bytes) {
+        set_error("beam_cars_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
+        return NIR_ERR_WORKSPACE;
+    }
+    if (Bd == 0) return 0;
+    // once per decode, as the greedy entry: the banks over every source row, the session projection (gathered through the repeated rowmap)
+    NIR_PROPAGATE(launch_linear(encoded_source, w->DQ, nullptr, nullptr, 0, 0, 0, w->dec_attn_w, w->DQ, nullptr, nullptr, p.mem, HD, rows_src * QL, HD, w->DQ,
+                                NIR_ACT_NONE, st));
+    if (foldq)
+        NIR_PROPAGATE(launch_linear(encoded_source, w->DQ, nullptr, nullptr, 0, 0, 0, w->attn_q_w, w->DQ, nullptr, nullptr, p.memq, HD, rows_src * QL, HD, w->DQ,
+                                    NIR_ACT_NONE, st));
+    NIR_PROPAGATE(sess_beam_begin(p.b, dec_h, dec_c, Bd, W, HD, p.h[0], p.c[0], p.h16[0], step16, rowmap, p.rowmap, bos, st));
+    if (w->KS > 0)
+        NIR_PROPAGATE(launch_linear(nullptr, 0, p.rowmap, session_cat, w->KS, 1, 1, w->sess_w, w->KS, nullptr, nullptr, p.sess, P, R, P, w->KS, NIR_ACT_NONE, st));
+    LstmStepArgs a = LstmStepArgs::token_fed(table, p.b.tgt, E, w->rnn_wih, w->rnn_whh, w->rnn_bih, w->rnn_bhh, R, HD);
+    if (step16) a.fold_token_fed(w->rnn_gate_fold, w->rnn_whh_frag);
+    int* bp = backptr ? backptr : p.b.bp;
+    for (int step = 0; step < max_len; ++step) {
+        // a step reads state slot 0 (the reordered one) and writes slot 1
+        float* hn = p.h[1];
+        a.hprev[0] = p.h[0]; a.cprev[0] = p.c[0]; a.hnext[0] = hn; a.cnext[0] = p.c[1];
+        if (step16) {
+            a.h16prev[0] = reinterpret_cast<const _Float16*>(p.h16[0]);
+            a.h16next[0] = reinterpret_cast<_Float16*>(p.h16[1]);
+        }
+        NIR_PROPAGATE(launch_lstm_step(a, 1, st));
+        if (!foldq) NIR_PROPAGATE(launch_linear(hn, HD, nullptr, nullptr, 0, 0, 0, w->attn_in_w, HD, nullptr, nullptr, p.qv, HD, R, HD, HD, NIR_ACT_NONE, st));
+        NIR_PROPAGATE(launch_dec_attend(foldq ? hn : p.qv, hn, p.mem, foldq ? p.memq : p.mem, p.rowmap, source_len, R, QL, HD, p.cat, st));
+        NIR_PROPAGATE(launch_linear(p.cat, 2 * HD, nullptr, nullptr, 0, 0, 0, w->attn_out_w, 2 * HD, nullptr, nullptr, p.ah, HD, R, HD, 2 * HD, NIR_ACT_TANH, st));
+        NIR_PROPAGATE(launch_linear_ex(p.ah, HD, nullptr, nullptr, 0, 0, 0, w->pred1_w, HD, nullptr, nullptr, p.p1, P, R, P, HD, NIR_ACT_NONE,
+                                       w->KS > 0 ? p.sess : nullptr, P, st));
+        NIR_PROPAGATE(sess_beam_gen(p.b, fused, p.p1, R, P, w->pred2_w, nullptr, gen_frag, VT, W, st));
+        NIR_PROPAGATE(sess_beam_tail(p.b, fused, step, max_len, Bd, W, HD, VT, tgt2src, V, bp, p.h, p.c, p.h16, step16, st));
+    }
+    return sess_beam_end(p.b, bp, Bd, W, max_len, predictions, scores, lengths, st);
+}
+
+// ---- the decoders without attention (M_MATCH_TENSOR, MNSRF): nir_decode_greedy_plain_folded's step over R rows ------------------------------------
+namespace nir {
+struct PlainBeamPlan {
+    float *h[2], *c[2], *h16[2];
+    SessBeamBufs b;
+    size_t bytes;
+};
+static PlainBeamPlan plain_beam_plan(void* ws, size_t cap, int64_t Bd, int H, int64_t VT, int W, int max_len, bool step16, bool fused, bool own_bp) {
+    Workspace a(ws, cap);
+    PlainBeamPlan p;
+    const int64_t R = Bd * W;
+    for (int k = 0; k < 2; ++k) { p.h[k] = a.take<float>((size_t)R * H); p.c[k] = a.take<float>((size_t)R * H); }
+    for (int k = 0; k < 2; ++k) p.h16[k] = a.take<float>(step16 ? (size_t)R * H : 0);
+    p.b = sess_beam_bufs(a, R, W, max_len, H, VT, fused, own_bp);
+    p.bytes = align_up(a.off, 256);
+    return p;
+}
+}  // namespace nir
+
+extern "C" size_t nir_beam_plain_decode_workspace_bytes(int64_t Bd, int H, int64_t VT, int W, int max_len, int folded, int fused) {
+    using namespace nir;
+    if (Bd < 0 || H <= 0 || H % 4 || VT <= 0 || max_len <= 0 || !beam_dims_ok(W, VT)) return 0;
+    return plain_beam_plan(nullptr, 0, Bd, H, VT, W, max_len, folded && H % 32 == 0 && !tun(g_tun.exact_f32), fused && s2s_fusable(H, VT) && !tun(g_tun.exact_f32), true).bytes;
+}
+
+extern "C" int nir_beam_plain_decode(const float* dec_h, const float* dec_c, int64_t Bd, int H, const float* table, int64_t V, int E, const float* w_ih,
+                                     const float* w_hh, const float* b_ih, const float* b_hh, const float* gen_w, const float* gen_b, int64_t VT,
+                                     const int64_t* tgt2src, int64_t bos, int max_len, const float* gate_fold, const void* whh_frag, const void* gen_frag,
+                                     int W, void* workspace, size_t workspace_bytes, int64_t* predictions, float* scores, int64_t* lengths, int32_t* backptr,
+                                     nir_stream_t stream) {
+    using namespace nir;
+    hipStream_t st = (hipStream_t)stream;
+    NIR_REQUIRE(dec_h && dec_c && table && w_ih && w_hh && b_ih && b_hh && gen_w && predictions && scores && lengths, "beam_plain_decode: null pointer");
+    NIR_REQUIRE(Bd >= 0 && H > 0 && E > 0 && V > 0 && VT > 0 && max_len > 0 && E % 4 == 0 && H % 4 == 0, "beam_plain_decode: bad dims");
+    NIR_REQUIRE(bos >= 0 && bos < V, "beam_plain_decode: BOS id outside the vocabulary");
+    NIR_REQUIRE(beam_dims_ok(W, VT), "beam_plain_decode: beam width outside [1, %d] or above the target vocabulary", NIR_BEAM_MAX_W);
+    NIR_REQUIRE(Bd * NIR_BEAM_MAX_W < 0x7FFFFFFFLL && VT < 0x7FFFFFF0LL, "beam_plain_decode: too many decode rows or target tokens");
+    const int64_t R = Bd * W;
+    const bool step16 = gate_fold && whh_frag && H % 32 == 0 && !tun(g_tun.exact_f32), fused = s2s_gen_fused(gen_frag, H, VT);
+    PlainBeamPlan p = plain_beam_plan(workspace, workspace_bytes, Bd, H, VT, W, max_len, step16, fused, backptr == nullptr);
+    if (!workspace || p.bytes > workspace_bytes) {
+        set_error("beam_plain_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
+        return NIR_ERR_WORKSPACE;
+    }
+    if (Bd == 0) return 0;
+    NIR_PROPAGATE(sess_beam_begin(p.b, dec_h, dec_c, Bd, W, H, p.h[0], p.c[0], p.h16[0], step16, nullptr, nullptr, bos, st));
+    LstmStepArgs s = LstmStepArgs::token_fed(table, p.b.tgt, E, w_ih, w_hh, b_ih, b_hh, R, H);
+    if (step16) s.fold_token_fed(gate_fold, whh_frag);
+    int* bp = backptr ? backptr : p.b.bp;
+    for (int step = 0; step < max_len; ++step) {
+        s.hprev[0] = p.h[0]; s.cprev[0] = p.c[0]; s.hnext[0] = p.h[1]; s.cnext[0] = p.c[1];
+        if (step16) {
+            s.h16prev[0] = reinterpret_cast<const _Float16*>(p.h16[0]);
+            s.h16next[0] = reinterpret_cast<_Float16*>(p.h16[1]);
+        }
+        NIR_PROPAGATE(launch_lstm_step(s, 1, st));
+        NIR_PROPAGATE(sess_beam_gen(p.b, fused, p.h[1], R, H, gen_w, gen_b, gen_frag, VT, W, st));
+        NIR_PROPAGATE(sess_beam_tail(p.b, fused, step, max_len, Bd, W, H, VT, tgt2src, V, bp, p.h, p.c, p.h16, step16, st));
+    }
+    return sess_beam_end(p.b, bp, Bd, W, max_len, predictions, scores, lengths, st);
+}
 
 extern "C" size_t nir_beam_gen_topk_workspace_bytes(int64_t rows, int K, int64_t VT, int W, int fused) {
     using namespace nir;

@@ -423,6 +423,18 @@ int launch_argmax_finish(const float* pval, const int* pidx, int nparts, int64_t
     return 0;
 }
 int device_cu_count() { return cu_count(); }
+// dec_attend_kernel over `rows` decode rows whose source rows are rowmap[i] (the beam of csrc/beam.hip passes a map repeated per beam)
+int launch_dec_attend(const float* qv, const float* h, const float* mem, const float* memq, const int64_t* rowmap, const int64_t* lens, int64_t rows, int QL,
+                      int HD, float* cat, hipStream_t st) {
+    if (rows <= 0) return 0;
+    {
+        ProfScope ps("dec_attend_kernel", st);
+        hipLaunchKernelGGL(dec_attend_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), (size_t)4 * QL * 4, st, qv, h, mem, memq, rowmap, lens, (int)rows, QL, HD,
+                           cat);
+    }
+    NIR_CHECK_LAUNCH("dec_attend_kernel");
+    return 0;
+}
 
 }  // namespace nir
 

@@ -9,6 +9,13 @@ int launch_linear(const float* a, int64_t lda, const int64_t* ids, const float* 
                   int64_t seq_stride, const float* w, int64_t ldw, const float* bias, const float* bias2, float* c,
                   int64_t ldc, int64_t M, int N, int K, int act, hipStream_t st);
 
+int launch_linear_ex(const float* a, int64_t lda, const int64_t* ids, const float* table, int E, int64_t rows_per_seq,
+                     int64_t seq_stride, const float* w, int64_t ldw, const float* bias, const float* bias2, float* c,
+                     int64_t ldc, int64_t M, int N, int K, int act, const float* add, int64_t ldadd, hipStream_t st);
+// The CARS decoder's attention (csrc/cars_decode.hip: dec_attend_kernel) over `rows` decode rows: row i scores qv[i] against memq[rowmap[i]], pools
+// mem[rowmap[i]] over the first lens[rowmap[i]] positions and writes cat[i] = [ctx ; h[i]]
+int launch_dec_attend(const float* qv, const float* h, const float* mem, const float* memq, const int64_t* rowmap, const int64_t* lens, int64_t rows, int QL,
+                      int HD, float* cat, hipStream_t st);
 // p[i] = v, i < n
 int launch_fill_i64(int64_t* p, int64_t v, int64_t n, hipStream_t st);
 // h [n = rows * H] fp32 -> the fp16 term pairs of the fp16-term LSTM step: [row][H/8][2 terms][8]  (H % 8 == 0)

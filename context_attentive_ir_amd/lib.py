@@ -332,6 +332,18 @@ BEAM_SIGNATURES = {
                                          C.c_void_p, c_st]),
 }
 
+# Beam search for the session models (CARS, M_MATCH_TENSOR, MNSRF), declared in include/neuroir_session_beam.h (csrc/beam.hip).  BEAM_SIGNATURES
+# mirrors neuroir_beam.h exactly (pinned by a test), so these have a table of their own too.
+_CW = C.POINTER(CarsDecoderWeights)
+SESSION_BEAM_SIGNATURES = {
+    "nir_beam_cars_decode_workspace_bytes": (_z, [_l, _l, _i, _i, _i, _CW, _i]),
+    "nir_beam_cars_decode": (_i, [c_fp, c_fp, c_fp, c_ip, _l, _i, c_ip, _l, c_fp, c_fp, _l, _i, c_ip, _l, _i, _CW, C.c_void_p, _i, C.c_void_p, _z, c_ip,
+                                  c_fp, c_ip, C.c_void_p, c_st]),
+    "nir_beam_plain_decode_workspace_bytes": (_z, [_l, _i, _l, _i, _i, _i, _i]),
+    "nir_beam_plain_decode": (_i, [c_fp, c_fp, _l, _i, c_fp, _l, _i, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, _l, c_ip, _l, _i, c_fp, C.c_void_p, C.c_void_p, _i,
+                                   C.c_void_p, _z, c_ip, c_fp, c_ip, C.c_void_p, c_st]),
+}
+
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_SPLIT2 = 0, 1, 2
 DTYPES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "bf16": DTYPE_BF16, "f32_split2": DTYPE_F32_SPLIT2}
 
@@ -347,7 +359,7 @@ def load():
                 "libneuroir_hip.so not found at %s -- build it with `python -m context_attentive_ir_amd.build` "
                 "(hipcc, gfx950). The HIP path has no CPU fallback." % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(GRU_DECODE_SIGNATURES.items()) + list(BEAM_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(GRU_DECODE_SIGNATURES.items()) + list(BEAM_SIGNATURES.items()) + list(SESSION_BEAM_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

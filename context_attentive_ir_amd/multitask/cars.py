@@ -27,6 +27,7 @@ from .. import lib
 from ..constants import BOS, PAD
 from ..encoders.rnn_encoder import lstm_cat_weights
 from ..modules import Maxout
+from . import suggest
 from .layers import Embedder, Encoder
 
 
@@ -132,6 +133,7 @@ class CARS(nn.Module, lib.IdCheck):
         # bf16 folded table + bf16 MFMA recurrence (BASELINE config 5), "f32" is the parity path.
         self.fold_embeddings = getattr(args, "fold_embeddings", True)
         self.fuse_attention_pooling = True   # attention MLP + masked softmax + weighted sum as one kernel (csrc/cars_attn.hip)
+        self.fuse_generator_topk = True      # decode_beam: token_prob_predictor2 + (lse, top-W) as one kernel, no [Bd W, V_tgt] logits
         self.fuse_decoder_argmax = True      # decode: 256 -> V_tgt projection + arg-max as one kernel, no [Bd, V_tgt] logits
         self.fold_decoder_step = True        # decode: per-token gate rows of the decoder LSTM folded into a [V, 4HD] table + fp16-term recurrent product
         self.fold_decoder_query = True       # decode: attn.linear_in folded into a second memory bank (one GEMM per decode instead of one per step)
@@ -698,6 +700,52 @@ class CARS(nn.Module, lib.IdCheck):
                                            int(max_len), w.ref(), lib.ptr(ws), ws.numel(), lib.ptr(preds), lib.stream()),
                   "nir_cars_decode_greedy")
         return {"predictions": preds.view(B, SD, int(max_len))}
+
+    def decode_beam(self, states, max_len, beam_size, src_dict, tgt_dict, batch_size, session_len, encoded_source, source_len, session_attns,
+                    tgt2src=None, return_backptr=False):
+        """Beam search of width `beam_size` (1 .. lib.BEAM_MAX_W) over max_len steps, no early stop (include/neuroir_session_beam.h, DESIGN.md
+        section 23) -> {'predictions': LongTensor [batch_size, session_len, W, max_len] (best beam first, EOS repeated behind the first EOS),
+        'scores': [batch_size, session_len, W] (sum of the tokens' log-probabilities, frozen at EOS), 'lengths': LongTensor [batch_size,
+        session_len, W]} (+ 'backptr': IntTensor [max_len, Bd, W] on request).  The inputs of decode(); nothing is repeated here: ONE C call."""
+        self._check_eval()
+        if self.no_recommender:
+            raise RuntimeError("decode needs the recommender (turn_recommender_off=False)")
+        assert all(s is not None for s in states)
+        lib.require_device(*states)
+        L = lib.load()
+        dec_h, dec_c = (s.reshape(-1, s.shape[-1]).float().contiguous() for s in states)
+        B, SD, W, max_len = int(batch_size), int(session_len), int(beam_size), int(max_len)
+        Bd = B * SD
+        if dec_h.shape[0] != Bd:
+            raise RuntimeError("decode: %d initial states for %d x %d decode rows" % (dec_h.shape[0], B, SD))
+        dev = dec_h.device
+        enc = encoded_source.float().contiguous()
+        rows_src, QL = enc.shape[0], enc.shape[1]
+        lens = lib.ids64(source_len.reshape(-1))
+        if rows_src != B * (SD + 1) or lens.numel() != rows_src:
+            raise RuntimeError("decode: encoded_source must hold batch_size*(session_len+1) query rows")
+        suggest.check_beam_size(W, self.token_prob_predictor2.weight.shape[0])
+        i = torch.arange(Bd, device=dev)
+        rowmap = ((i // SD) * (SD + 1) + i % SD).contiguous()                       # the reference's [:, :-1] selection
+        cat = [a for a in session_attns if a is not None]
+        session_cat = torch.cat(cat, 2).reshape(rows_src, -1).float().contiguous() if cat else None
+        if tgt2src is None:
+            tgt2src = self._tgt2src(src_dict, tgt_dict, dev)
+        w = self._decoder_weights()
+        # the beam's generator reads nir_seq2seq_pack_gen_frag's fragments of token_prob_predictor2 (any P % 32 == 0), a pack of its own next to
+        # the greedy arg-max's pred2_frag
+        frag = suggest.gen_frag_pack(self, self.token_prob_predictor2.weight, Bd * W)
+        table = self.embedder.word_embeddings.table
+        out = suggest.beam_outputs(Bd, W, max_len, dev, return_backptr)
+        if Bd > 0 and max_len > 0:
+            ws = lib.workspace(L.nir_beam_cars_decode_workspace_bytes(rows_src, Bd, QL, W, max_len, w.ref(), int(frag is not None)), dev)
+            lib.check(L.nir_beam_cars_decode(lib.ptr(dec_h), lib.ptr(dec_c), lib.ptr(enc), lib.ptr(lens), rows_src, QL, lib.ptr(rowmap), Bd,
+                                             lib.ptr(session_cat), lib.ptr(table), table.shape[0], table.shape[1], lib.ptr(tgt2src), BOS, max_len,
+                                             w.ref(), lib.ptr(frag), W, lib.ptr(ws), ws.numel(), lib.ptr(out["predictions"]), lib.ptr(out["scores"]),
+                                             lib.ptr(out["lengths"]), lib.ptr(out.get("backptr")), lib.stream()), "nir_beam_cars_decode")
+        out["predictions"], out["scores"], out["lengths"] = (out["predictions"].view(B, SD, W, max_len), out["scores"].view(B, SD, W),
+                                                             out["lengths"].view(B, SD, W))
+        return out
 
     def _tgt2src(self, src_dict, tgt_dict, dev):
         if src_dict is None or tgt_dict is None:

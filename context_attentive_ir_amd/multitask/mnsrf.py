@@ -227,3 +227,14 @@ class MNSRF(nn.Module, lib.IdCheck):
         self._check_eval()
         return suggest.greedy_decode(self, states, max_len, src_dict, tgt_dict, batch_size, session_len, self.embedder.word_embeddings.table,
                                      self.decoder.decoder.rnn, self.generator, tgt2src)
+
+    fuse_generator_topk = True               # decode_beam: generator + bias + (lse, top-W) in one kernel (no [Bd W, VT] logits)
+
+    def decode_beam(self, states, max_len, beam_size, src_dict, tgt_dict, batch_size, session_len, use_cuda=True, tgt2src=None, return_backptr=False,
+                    **kwargs):
+        """Beam search of width `beam_size` with the arguments of decode() (include/neuroir_session_beam.h) ->
+        {'predictions': LongTensor [batch_size, session_len, W, max_len], 'scores': [batch_size, session_len, W], 'lengths': LongTensor
+        [batch_size, session_len, W]}, best beam first."""
+        self._check_eval()
+        return suggest.beam_decode(self, states, max_len, beam_size, src_dict, tgt_dict, batch_size, session_len, self.embedder.word_embeddings.table,
+                                   self.decoder.decoder.rnn, self.generator, tgt2src, return_backptr)

@@ -49,6 +49,28 @@ def tgt2src_lut(owner, src_dict, tgt_dict, n, dev):
     return owner._lut
 
 
+def plain_fold(owner, table, dec_rnn, t, p, H, dev):
+    """(folded gate table, W_hh fragments) of a decoder without attention, or None -- shared by greedy_decode and beam_decode, cached on `owner`.
+    The decoder LSTM's input is the previous token's embedding alone: gate rows folded per token + W_hh as fp16 term fragments, once per weight
+    version (a weight outside the split's range, H % 32 != 0 or `fold_decoder_step = False` on the model keep the fp32 step)."""
+    L = lib.load()
+
+    def build():
+        nb = L.nir_lstm_step_whh_frag_bytes(H)
+        if not (getattr(owner, "fold_decoder_step", True) and nb and t.is_cuda and t.shape[0] * 4 * H * 4 <= getattr(owner, "fold_budget_bytes", 64 << 30)):
+            return None
+        frag, flag = torch.empty(nb, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+        lib.check(L.nir_lstm_step_pack_whh_frag(lib.ptr(p[1]), H, lib.ptr(frag), lib.ptr(flag), lib.stream()), "nir_lstm_step_pack_whh_frag")
+        if int(flag.item()) != 0:
+            return None
+        return lib.fold_lstm_table(t, p[0], p[2], p[3], H, 1, "f32"), frag
+    cache = getattr(owner, "_pdec_plain", None)
+    if cache is None:
+        cache = owner._pdec_plain = lib.PackCache(retain=1)
+    return cache.get([table] + [getattr(dec_rnn, n) for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")]
+                     + [getattr(owner, "fold_decoder_step", True)], build)
+
+
 def greedy_decode(owner, states, max_len, src_dict, tgt_dict, batch_size, session_len, table, dec_rnn, generator, tgt2src=None):
     """-> {'predictions': LongTensor [batch_size, session_len, max_len]} in target-vocabulary ids; `session_len` = decoded queries per
     session (the caller passes S-1, models/multitask.py:286)."""
@@ -64,22 +86,7 @@ def greedy_decode(owner, states, max_len, src_dict, tgt_dict, batch_size, sessio
         tgt2src = tgt2src_lut(owner, src_dict, tgt_dict, VT, dev)
     t = table.detach().float().contiguous()
     p = [getattr(dec_rnn, n).detach().float().contiguous() for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")]
-    # the decoder LSTM's input is the previous token's embedding alone: gate rows folded per token + W_hh as fp16 term fragments, once per weight
-    # version (a weight outside the split's range, H % 32 != 0 or `fold_decoder_step = False` on the model keep the fp32 step)
-    def build():
-        nb = L.nir_lstm_step_whh_frag_bytes(H)
-        if not (getattr(owner, "fold_decoder_step", True) and nb and t.is_cuda and t.shape[0] * 4 * H * 4 <= getattr(owner, "fold_budget_bytes", 64 << 30)):
-            return None
-        frag, flag = torch.empty(nb, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
-        lib.check(L.nir_lstm_step_pack_whh_frag(lib.ptr(p[1]), H, lib.ptr(frag), lib.ptr(flag), lib.stream()), "nir_lstm_step_pack_whh_frag")
-        if int(flag.item()) != 0:
-            return None
-        return lib.fold_lstm_table(t, p[0], p[2], p[3], H, 1, "f32"), frag
-    cache = getattr(owner, "_pdec_plain", None)
-    if cache is None:
-        cache = owner._pdec_plain = lib.PackCache(retain=1)
-    fold = cache.get([table] + [getattr(dec_rnn, n) for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")]
-                     + [getattr(owner, "fold_decoder_step", True)], build)
+    fold = plain_fold(owner, table, dec_rnn, t, p, H, dev)
     ws = lib.workspace(L.nir_decode_greedy_plain_workspace_bytes(Bd, H, VT), dev)
     preds = torch.empty(Bd, int(max_len), dtype=torch.int64, device=dev)
     lib.check(L.nir_decode_greedy_plain_folded(lib.ptr(dec_h), lib.ptr(dec_c), Bd, H, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(p[0]), lib.ptr(p[1]),
@@ -87,6 +94,85 @@ def greedy_decode(owner, states, max_len, src_dict, tgt_dict, batch_size, sessio
                                                lib.ptr(fold[0]) if fold else None, lib.ptr(fold[1]) if fold else None, lib.ptr(ws),
                                                ws.numel(), lib.ptr(preds), lib.stream()), "nir_decode_greedy_plain_folded")
     return {"predictions": preds.view(int(batch_size), int(session_len), int(max_len))}
+
+
+FUSE_TOPK_MAX_ROWS = 384     # beam rows up to which the fused generator + top-k is the default (it wins at 384, loses at 768)
+
+
+def gen_frag_pack(owner, weight, rows, attr="_pgen_beam"):
+    """nir_seq2seq_pack_gen_frag of a generator weight [VT, K] (the fused generator + top-W kernel of the beam reads it), once per weight version,
+    cached on `owner`; None when K has no fragment form, the weight lies outside the split's range, the model says `fuse_generator_topk = False`
+    or the decode has more than `fuse_topk_max_rows` (default FUSE_TOPK_MAX_ROWS) beam rows: the fused kernel re-reads the fragments once per
+    64-row block, and from there on the fp32 GEMM + row top-k was measured faster."""
+    if not getattr(owner, "fuse_generator_topk", True) or rows > getattr(owner, "fuse_topk_max_rows", FUSE_TOPK_MAX_ROWS):
+        return None
+    L = lib.load()
+
+    def build():
+        w = weight.detach().float().contiguous()
+        VT, K = w.shape
+        nb = L.nir_seq2seq_gen_frag_bytes(VT, K)
+        if not (nb and w.is_cuda):
+            return None
+        frag, flag = torch.empty(nb, dtype=torch.uint8, device=w.device), torch.zeros(1, dtype=torch.int32, device=w.device)
+        lib.check(L.nir_seq2seq_pack_gen_frag(lib.ptr(w), VT, K, lib.ptr(frag), lib.ptr(flag), lib.stream()), "nir_seq2seq_pack_gen_frag")
+        return frag if int(flag.item()) == 0 else None
+    cache = getattr(owner, attr, None)
+    if cache is None:
+        cache = lib.PackCache(retain=1)
+        setattr(owner, attr, cache)
+    return cache.get([weight], build)
+
+
+def beam_outputs(Bd, W, max_len, dev, return_backptr):
+    out = {"predictions": torch.empty(Bd, W, max_len, dtype=torch.int64, device=dev), "scores": torch.empty(Bd, W, dtype=torch.float32, device=dev),
+           "lengths": torch.empty(Bd, W, dtype=torch.int64, device=dev)}
+    if return_backptr:
+        out["backptr"] = torch.empty(max_len, Bd, W, dtype=torch.int32, device=dev)
+    return out
+
+
+def check_beam_size(W, VT):
+    if not 1 <= W <= lib.BEAM_MAX_W or W > VT:
+        raise ValueError("decode_beam: beam_size %d outside [1, %d] or above the target vocabulary (%d)" % (W, lib.BEAM_MAX_W, VT))
+
+
+def beam_decode(owner, states, max_len, beam_size, src_dict, tgt_dict, batch_size, session_len, table, dec_rnn, generator, tgt2src=None,
+                return_backptr=False):
+    """Beam search next to greedy_decode (include/neuroir_session_beam.h) -> {'predictions': LongTensor [batch_size,
+    session_len, W, max_len] (best beam first, EOS repeated behind the first EOS), 'scores': [batch_size, session_len, W], 'lengths': LongTensor
+    [batch_size, session_len, W]} (+ 'backptr': IntTensor [max_len, Bd, W] on request).  The same fold cache as greedy_decode plus a cached
+    generator fragment pack; the initial states are not repeated here -- nir_beam_plain_decode does that."""
+    if owner.training:
+        raise NotImplementedError("HIP %s.decode_beam runs in eval mode" % type(owner).__name__)
+    lib.require_device(*states)
+    L = lib.load()
+    dec_h, dec_c = (s.reshape(-1, s.shape[-1]).float().contiguous() for s in states)
+    Bd, H = dec_h.shape
+    if Bd != int(batch_size) * int(session_len):
+        raise RuntimeError("decode: %d initial states for %d x %d decode rows" % (Bd, batch_size, session_len))
+    dev = dec_h.device
+    W, max_len = int(beam_size), int(max_len)
+    gw, gb = generator.weight.detach().float().contiguous(), generator.bias.detach().float().contiguous()
+    VT = gw.shape[0]
+    check_beam_size(W, VT)
+    if tgt2src is None:
+        tgt2src = tgt2src_lut(owner, src_dict, tgt_dict, VT, dev)
+    t = table.detach().float().contiguous()
+    p = [getattr(dec_rnn, n).detach().float().contiguous() for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")]
+    fold = plain_fold(owner, table, dec_rnn, t, p, H, dev)
+    frag = gen_frag_pack(owner, generator.weight, Bd * W)
+    out = beam_outputs(Bd, W, max_len, dev, return_backptr)
+    if Bd > 0 and max_len > 0:
+        ws = lib.workspace(L.nir_beam_plain_decode_workspace_bytes(Bd, H, VT, W, max_len, int(fold is not None), int(frag is not None)), dev)
+        lib.check(L.nir_beam_plain_decode(lib.ptr(dec_h), lib.ptr(dec_c), Bd, H, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(p[0]), lib.ptr(p[1]),
+                                          lib.ptr(p[2]), lib.ptr(p[3]), lib.ptr(gw), lib.ptr(gb), VT, lib.ptr(tgt2src), BOS, max_len,
+                                          lib.ptr(fold[0]) if fold else None, lib.ptr(fold[1]) if fold else None, lib.ptr(frag), W, lib.ptr(ws), ws.numel(),
+                                          lib.ptr(out["predictions"]), lib.ptr(out["scores"]), lib.ptr(out["lengths"]), lib.ptr(out.get("backptr")),
+                                          lib.stream()), "nir_beam_plain_decode")
+    B, SD = int(batch_size), int(session_len)
+    out["predictions"], out["scores"], out["lengths"] = out["predictions"].view(B, SD, W, max_len), out["scores"].view(B, SD, W), out["lengths"].view(B, SD, W)
+    return out
 
 
 def bilstm_train(x, lens, lstm):

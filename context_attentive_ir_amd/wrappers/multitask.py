@@ -296,6 +296,58 @@ class Multitask(WrapperBase):
         return {"prediction_ids": pred_ids, "predictions": preds, "targets": targets, "src_sequences": srcs,
                 "ex_ids": [_id + str(i) for i in range(S) for _id in ex["ids"]]}
 
+    # ---- beam search ------------------------------------------------------------------------------------------------------------------
+    def _predict_beam_body(self, ex, beam_size):
+        """_predict_body with the beam decode in the place of the greedy one: the same kernels in the same order in front of it"""
+        s, states, attns, enc = self._rank(ex, True)
+        out = {"click_scores": None, "prediction_ids": None, "scores": None, "lengths": None}
+        if torch.is_tensor(s):
+            s = s.contiguous()
+            probs = torch.empty_like(s)
+            lib.check(lib.load().nir_softmax_rows(lib.ptr(s), lib.ptr(probs), s.shape[0] * s.shape[1], s.shape[2], lib.stream()), "nir_softmax_rows")
+            out["click_scores"] = probs
+        B, S = ex["source_words"].shape[0], ex["source_words"].shape[1]
+        dec = self.network.decode_beam(states=states, max_len=self.args.max_query_len, beam_size=beam_size, src_dict=self.src_dict, tgt_dict=self.tgt_dict,
+                                       batch_size=B, session_len=S - 1, encoded_source=enc[0], source_len=enc[1], session_attns=attns)
+        out.update(prediction_ids=dec["predictions"], scores=dec["scores"], lengths=dec["lengths"])
+        self._maybe_check_ids(False)
+        return out
+
+    @torch.no_grad()
+    def predict_beam(self, ex, beam_size):
+        """n-best query suggestions by beam search (decode_beam of the three session models; the reference has no counterpart):
+        {'click_scores': exactly predict()'s, 'prediction_ids': LongTensor [B, S-1, W, max_query_len], 'scores': [B, S-1, W], 'lengths': LongTensor
+        [B, S-1, W]}, best beam first.  For a batch in the reference's collate layout also `ex_ids`, `targets`, `src_sequences` as predict() forms
+        them, and `predictions` = one list of W strings per decoded query (step-major, each string formed like predict()'s).  `beam_size` is an
+        argument of the call, not a field of args.  Graph replay as in predict(), the width in the key.  CARS with the recommender off returns
+        prediction_ids = None, like predict()."""
+        W = int(beam_size)
+        if not 1 <= W <= lib.BEAM_MAX_W:
+            raise ValueError("predict_beam: beam_size %d outside [1, %d]" % (W, lib.BEAM_MAX_W))
+        if self.type == "CARS" and self.network.no_recommender:
+            out = self.predict(ex, suggest=False)
+            out.pop("predictions", None)
+            out.update(prediction_ids=None, scores=None, lengths=None)
+            return out
+        self._poll_ids()
+        fields = self._FIELDS if self.type == "CARS" else self._FIELDS[:4]
+        body = lambda e: self._predict_beam_body(e, W)                        # noqa: E731
+        out = self._graphed(ex, fields, "decode_beam%d" % W, body)
+        if out is not None and self.id_check == "blocking":
+            self._maybe_check_ids()
+        if out is None:
+            out = body(ex)
+        out = dict(out)
+        if out["click_scores"] is not None:
+            out["click_scores"] = self._checked(out["click_scores"])
+        if "ids" in ex and ex.get("source_tokens") is not None:
+            per_beam = [self._suggestion_text(ex, out["prediction_ids"][:, :, k]) for k in range(W)]
+            text = dict(per_beam[0])
+            text["prediction_ids"] = out["prediction_ids"]
+            text["predictions"] = [[per_beam[k]["predictions"][j] for k in range(W)] for j in range(len(per_beam[0]["predictions"]))]
+            out.update(text)
+        return out
+
     def _finish_scores(self, s):
         probs, published = self._softmax_rows(s)
         self._maybe_check_ids(published)

@@ -1145,6 +1145,8 @@ int nir_acg_copy_loss_bwd(const float* logits, int64_t ld, const float* switch_l
 #include "neuroir_gru_decode.h"
 /* Beam search for Seq2seq (both decoders' cells), likewise in a header of its own (ctypes: lib.BEAM_SIGNATURES). */
 #include "neuroir_beam.h"
+/* ... and for the session models (CARS, M_MATCH_TENSOR, MNSRF), in a third one (ctypes: lib.SESSION_BEAM_SIGNATURES). */
+#include "neuroir_session_beam.h"
 
 #ifdef __cplusplus
 }
