@@ -18,8 +18,6 @@
 
 namespace nir {
 
-constexpr float ACG_PAD_LOGIT = -1e-20f;      // copy_generator.py:79: logits[:, :, PAD] = -eps
-
 __device__ __forceinline__ float acg_block_reduce(float v, float* red, bool is_max) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     v = is_max ? wave_max(v) : wave_sum(v);

@@ -9,6 +9,8 @@
 // and once behind the loop beam_backtrack_kernel walks the stored back-pointers.  The global top-W over (k, v) lies inside the per-row top-W of
 // the raw logits, since lse is constant within a row.  Everything is enqueued on the caller's stream; no host synchronisation, no allocation,
 // no float atomics, every reduction in a fixed order.
+// ACG's search (include/neuroir_acg_beam.h) is the same loop with another tail: the PAD-substituting forms of the two top-k
+// kernels, acg_beam_row_kernel (the W best of a row's collapsed extended distribution) and acg_beam_select_kernel.
 #include <mutex>
 #include "s2s_gen.hpp"
 
@@ -64,7 +66,9 @@ __device__ __forceinline__ int wave_min_i(int v) {
 // threshold test per value, an insertion only when it passes.  The four lanes of a decode row are merged in the wave (WM rounds: the best of
 // the four heads wins, its owner pops); every wave writes one partial per decode row -- pval / pidx [part][Bd][W], pm / ps [part][Bd] -- and
 // beam_merge_row reduces the partials of all waves and workgroups.
-template <int NBT, int WM>
+// PAD (the copy generator's beam): the logit of v == 0 is replaced by ACG_PAD_LOGIT before the online-softmax pair and the
+// list insert, as STATS does in s2s_gen_argmax_kernel.  PAD = false compiles to the kernel without the test.
+template <int NBT, int WM, bool PAD = false>
 __global__ __launch_bounds__(256, 1) void beam_gen_topk_kernel(const float* __restrict__ x, const _Float16* __restrict__ wfrag,
                                                                const float* __restrict__ bias, int64_t VT, int64_t ntiles, int64_t Bd, int K, int nvr,
                                                                int W, float* __restrict__ pval, int* __restrict__ pidx, float* __restrict__ pm,
@@ -169,6 +173,9 @@ __global__ __launch_bounds__(256, 1) void beam_gen_topk_kernel(const float* __re
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     y[r] = fmaf(acx[bt][r], SPLIT2_INV, acc[bt][r]) + bv[r];  // the greedy kernel's expression: W = 1 picks its token
+                    if constexpr (PAD) {
+                        if (v0 + r == 0) y[r] = ACG_PAD_LOGIT;                // the reference assigns this constant behind the linear
+                    }
                     if (v0 + r >= VT) y[r] = -INFINITY;                       // padded tile rows: never kept, add exp(-inf) = 0
                     m = fmaxf(m, y[r]);
                 }
@@ -231,8 +238,9 @@ __global__ __launch_bounds__(256, 1) void beam_gen_topk_kernel(const float* __re
 // pm = lse passes through bit for bit).  Lane l takes parts l, l + 64, ... in order; the wave's maxima and sums combine through wave_max /
 // wave_sum (a fixed tree) and the lists through W rounds of (largest head, smallest index among equals, its owner pops).
 // Lane 0 writes out_val / out_idx [W] and *out_lse.
-__device__ __forceinline__ void beam_merge_row(const float* pval, const int* pidx, const float* pm, const float* ps, int nparts, int64_t rows,
-                                               int64_t row, int stride, int W, int lane, float* out_val, int* out_idx, float* out_lse) {
+// beam_merge_row_ms leaves the pair (max, sum) to the caller, in every lane, in the place of lse = max + log(sum).
+__device__ __forceinline__ void beam_merge_row_ms(const float* pval, const int* pidx, const float* pm, const float* ps, int nparts, int64_t rows,
+                                                  int64_t row, int stride, int W, int lane, float* out_val, int* out_idx, float& M, float& S) {
     constexpr int WM = NIR_BEAM_MAX_W;
     float tv[WM];
     int ti[WM];
@@ -251,9 +259,8 @@ __device__ __forceinline__ void beam_merge_row(const float* pval, const int* pid
             if (beam_before(y, v, tv[WM - 1], ti[WM - 1])) beam_insert<WM, true>(tv, ti, y, v);
         }
     }
-    const float M = wave_max(m);
-    const float S = wave_sum(m > -INFINITY ? s * expf(m - M) : 0.f);
-    if (lane == 0) *out_lse = M + logf(S);
+    M = wave_max(m);
+    S = wave_sum(m > -INFINITY ? s * expf(m - M) : 0.f);
     for (int j = 0; j < W; ++j) {
         const float hv = tv[0];
         const int hi = ti[0];
@@ -262,6 +269,12 @@ __device__ __forceinline__ void beam_merge_row(const float* pval, const int* pid
         beam_pop<WM>(tv, ti, hv == mx && hi == mi);
         if (lane == 0) { out_val[j] = mx; out_idx[j] = mi; }
     }
+}
+__device__ __forceinline__ void beam_merge_row(const float* pval, const int* pidx, const float* pm, const float* ps, int nparts, int64_t rows,
+                                               int64_t row, int stride, int W, int lane, float* out_val, int* out_idx, float* out_lse) {
+    float M, S;
+    beam_merge_row_ms(pval, pidx, pm, ps, nparts, rows, row, stride, W, lane, out_val, out_idx, M, S);
+    if (lane == 0) *out_lse = M + logf(S);
 }
 
 __global__ __launch_bounds__(64) void beam_topk_finish_kernel(const float* __restrict__ pval, const int* __restrict__ pidx, const float* __restrict__ pm,
@@ -272,8 +285,11 @@ __global__ __launch_bounds__(64) void beam_topk_finish_kernel(const float* __res
 }
 
 // ---- plain form: one workgroup per row of [rows, VT] logits -> (lse, top-W), the same tie rule ---------------------------------------------
+// PAD (the copy generator's beam): logits[row, 0] is read as ACG_PAD_LOGIT, and the row's pair comes out apart -- max in `lse`, sum in `psum` --
+// the partial format acg_beam_row_kernel merges (one part per row).  PAD = false never touches psum.
+template <bool PAD = false>
 __global__ __launch_bounds__(256) void beam_row_topk_kernel(const float* __restrict__ logits, int64_t VT, int W, float* __restrict__ top_val,
-                                                            int* __restrict__ top_idx, float* __restrict__ lse) {
+                                                            int* __restrict__ top_idx, float* __restrict__ lse, float* __restrict__ psum) {
     constexpr int WM = NIR_BEAM_MAX_W;
     __shared__ float lv[256 * WM];
     __shared__ int li[256 * WM];
@@ -287,7 +303,10 @@ __global__ __launch_bounds__(256) void beam_row_topk_kernel(const float* __restr
     for (int j = 0; j < WM; ++j) { tv[j] = -INFINITY; ti[j] = BEAM_NONE; }
     float m = -INFINITY, s = 0.f;
     for (int64_t v = tid; v < VT; v += 256) {                                 // ascending: '>' keeps the first index in front
-        const float a = y[v];
+        float a = y[v];
+        if constexpr (PAD) {
+            if (v == 0) a = ACG_PAD_LOGIT;
+        }
         const float nm = fmaxf(m, a);
         if (nm > -INFINITY) s = s * expf(m - nm) + expf(a - nm);
         m = nm;
@@ -298,7 +317,15 @@ __global__ __launch_bounds__(256) void beam_row_topk_kernel(const float* __restr
     lm[tid] = m;
     ls[tid] = s;
     __syncthreads();
-    if (tid < 64) beam_merge_row(lv, li, lm, ls, 256, 1, 0, WM, W, tid, top_val + row * W, top_idx + row * W, lse + row);
+    if constexpr (PAD) {
+        if (tid < 64) {
+            float M, S;
+            beam_merge_row_ms(lv, li, lm, ls, 256, 1, 0, WM, W, tid, top_val + row * W, top_idx + row * W, M, S);
+            if (tid == 0) { lse[row] = M; psum[row] = S; }
+        }
+    } else {
+        if (tid < 64) beam_merge_row(lv, li, lm, ls, 256, 1, 0, WM, W, tid, top_val + row * W, top_idx + row * W, lse + row);
+    }
 }
 
 // ---- selection: one wave per source row ----------------------------------------------------------------------------------------------------
@@ -358,6 +385,162 @@ __global__ __launch_bounds__(64) void beam_select_kernel(const float* __restrict
     }
 }
 
+// ---- the copy generator's beam (include/neuroir_acg_beam.h) -------------------------------------------------------------
+// One wave per beam row r = k nsrc + b: the W best (log P, extended id) of the row's COLLAPSED extended distribution, which is never written.
+// Steps 1-3 are those of acg_select_kernel (csrc/acg.hip), in its fp32 expressions: the partials merge to (m, Z) and the raw top-W list (PAD
+// already substituted by the producer), z = sigmoid(x) and 1 - z = sigmoid(-x), the copy mass of every slot (j ascending) and the slots' targets
+// in LDS.  The maps, ext2tgt and the length are those of source row b; o and the copy attention are the beam row's own.  Candidates:
+//   a slot that is not collapsed                     mass[c]                                             id VT + c
+//   a raw top-W entry that no slot collapses onto    (1 - z) exp(l[v] - m) / Z                           id v
+//   a target t of one or more slots                  (1 - z) exp(l[t] - m) / Z + the slots' mass, once   id t   (l[t]: the fp32 row dot)
+// A collapsed slot is no candidate, and a raw entry that is a target is dropped for the third form.  Every lane keeps a sorted list of its
+// offers (any arrival order: beam_insert<TOTAL>); W rounds of (largest head, smallest id among equals) merge them.  log 0 = -inf is a
+// candidate like any other: it loses to every finite one and is ordered by id among its kind.  `finished` [nsrc, W] (optional): the rows of
+// finished beams are skipped, their outputs left as they are -- the selection does not read them.
+__global__ __launch_bounds__(64) void acg_beam_row_kernel(const float* __restrict__ o, int K, const float* __restrict__ gen_w, const float* __restrict__ gen_b,
+                                                          int64_t VT, const float* __restrict__ pval, const int* __restrict__ pidx,
+                                                          const float* __restrict__ pm, const float* __restrict__ ps, int nparts, int64_t R, int64_t nsrc,
+                                                          int W, const float* __restrict__ copy_w, const float* __restrict__ copy_b,
+                                                          const float* __restrict__ attn, int64_t attn_stride, const int64_t* __restrict__ lens, int QL,
+                                                          const int64_t* __restrict__ map, const int64_t* __restrict__ e2t, int CV,
+                                                          const int* __restrict__ finished, float* __restrict__ top_val, int* __restrict__ top_idx) {
+    constexpr int WM = NIR_BEAM_MAX_W;
+    extern __shared__ float acgb_sm[];                         // mass [CV] floats, tl [CV] ints
+    __shared__ float rv[WM];
+    __shared__ int ri[WM];
+    const int lane = threadIdx.x;
+    const int64_t r = blockIdx.x, b = r % nsrc;
+    if (finished && finished[b * W + r / nsrc]) return;        // uniform over the workgroup (one wave)
+    float* mass = acgb_sm;
+    int* tl = reinterpret_cast<int*>(acgb_sm + CV);
+    // 1. the generator's statistics and the raw top-W
+    float m, Z;
+    beam_merge_row_ms(pval, pidx, pm, ps, nparts, R, r, W, W, lane, rv, ri, m, Z);
+    // 2. the copy switch
+    const float* ob = o + r * K;
+    float x = 0.f;
+    for (int k = 4 * lane; k < K; k += 256) {
+        const float4 a = *reinterpret_cast<const float4*>(ob + k), w = *reinterpret_cast<const float4*>(copy_w + k);
+        x += (a.x * w.x + a.y * w.y) + (a.z * w.z + a.w * w.w);
+    }
+    x = wave_sum(x) + copy_b[0];
+    const float z = 1.0f / (1.0f + expf(-x)), omz = 1.0f / (1.0f + expf(x));
+    // 3. the copy mass and the target of every slot of source row b
+    int len = (int)lens[b];
+    len = len < 0 ? 0 : (len > QL ? QL : len);
+    const int64_t* mb = map + b * QL;
+    const float* ab = attn + r * attn_stride;
+    for (int c = lane; c < CV; c += 64) {
+        float acc = 0.f;
+        for (int j = 0; j < len; ++j)
+            if (mb[j] == c) acc += z * ab[j];
+        mass[c] = acc;
+        const int64_t t = e2t[b * CV + c];
+        tl[c] = (c >= 2 && t >= 0 && t < VT) ? (int)t : -1;
+    }
+    __syncthreads();                                           // (one wave: the LDS writes above, rv / ri among them, are visible below)
+    // 4. the candidates
+    float tv[WM];
+    int ti[WM];
+#pragma unroll
+    for (int j = 0; j < WM; ++j) { tv[j] = -INFINITY; ti[j] = BEAM_NONE; }
+    auto offer = [&](float P, int e) {
+        const float lp = logf(P);
+        if (beam_before(lp, e, tv[WM - 1], ti[WM - 1])) beam_insert<WM, true>(tv, ti, lp, e);
+    };
+    for (int c = lane; c < CV; c += 64)
+        if (tl[c] < 0) offer(mass[c], (int)(VT + c));
+    for (int j = 0; j < W; ++j) {                              // wave-uniform
+        const int v = ri[j];
+        if (v < 0 || v >= VT) continue;
+        int hit = 0;
+        for (int c = lane; c < CV; c += 64) hit |= tl[c] == v;
+        if (__any(hit)) continue;
+        if (lane == 0) offer(omz * expf(rv[j] - m) / Z, v);
+    }
+    for (int c = 2; c < CV; ++c) {                             // wave-uniform: every slot that is the FIRST of its target id
+        const int t = tl[c];
+        if (t < 0) continue;
+        int dup = 0;
+        float cp = 0.f;
+        for (int c2 = lane; c2 < CV; c2 += 64)
+            if (tl[c2] == t) {
+                if (c2 < c) dup = 1;
+                else cp += mass[c2];
+            }
+        if (__any(dup)) continue;
+        cp = wave_sum(cp);
+        float lt = ACG_PAD_LOGIT;
+        if (t != 0) {
+            const float* wr = gen_w + (int64_t)t * K;
+            float d = 0.f;
+            for (int k = 4 * lane; k < K; k += 256) {
+                const float4 a = *reinterpret_cast<const float4*>(ob + k), w = *reinterpret_cast<const float4*>(wr + k);
+                d += (a.x * w.x + a.y * w.y) + (a.z * w.z + a.w * w.w);
+            }
+            lt = wave_sum(d) + (gen_b ? gen_b[t] : 0.f);
+        }
+        if (lane == 0) offer(omz * expf(lt - m) / Z + cp, t);
+    }
+    for (int j = 0; j < W; ++j) {
+        const float hv = tv[0];
+        const int hi = ti[0];
+        const float mx = wave_max(hv);
+        const int mi = wave_min_i(hv == mx ? hi : BEAM_NONE);
+        beam_pop<WM>(tv, ti, hv == mx && hi == mi);
+        if (lane == 0) { top_val[r * W + j] = mx; top_idx[r * W + j] = mi; }
+    }
+}
+
+// The selection of beam_select_kernel over finished per-row lists (top_val = log P, lse NULL = 0) of EXTENDED ids in [0, VT + CV): the flat index
+// is k (VT + CV) + e, finished means e == EOS, and the token fed back is lut[e] below VT and e2s[b, e - VT] from VT on (<unk> outside [0, Vsrc)).
+// A sibling, so that beam_select_kernel and its callers stay as they are.
+__global__ __launch_bounds__(64) void acg_beam_select_kernel(const float* __restrict__ top_val, const int* __restrict__ top_idx, const float* __restrict__ lse,
+                                                             int64_t B, int W, int64_t VT, int CV, const int64_t* __restrict__ lut,
+                                                             const int64_t* __restrict__ e2s, int64_t Vsrc, float* __restrict__ cum,
+                                                             int* __restrict__ finished, int* __restrict__ backptr, int* __restrict__ token,
+                                                             int64_t* __restrict__ next_ids) {
+    const int64_t b = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int k = lane / W, j = lane - k * W;
+    bool open = false;
+    float score = -INFINITY;
+    int v = BEAM_NONE;
+    if (k < W) {
+        const float ck = cum[b * W + k];
+        if (finished[b * W + k]) {
+            open = j == 0;
+            score = ck;
+            v = NIR_BEAM_EOS;
+        } else {
+            const int64_t row = (int64_t)k * B + b;
+            open = true;
+            score = ck + (top_val[row * W + j] - (lse ? lse[row] : 0.f));
+            v = top_idx[row * W + j];
+        }
+        if (!(score == score)) score = -INFINITY;
+    }
+    for (int o = 0; o < W; ++o) {
+        const float sc = open ? score : -INFINITY;
+        const float mx = wave_max(sc);
+        const bool c1 = open && sc == mx;
+        const int mk = wave_min_i(c1 ? k : BEAM_NONE);
+        const bool c2 = c1 && k == mk;
+        const int mv = wave_min_i(c2 ? v : BEAM_NONE);
+        if (c2 && v == mv) {
+            open = false;
+            const int64_t tokv = (v >= 0 && (int64_t)v < VT + CV) ? v : 0;
+            const int64_t slot = b * W + o;
+            cum[slot] = score;
+            finished[slot] = tokv == NIR_BEAM_EOS;
+            backptr[slot] = k;
+            token[slot] = (int)tokv;
+            const int64_t nxt = tokv < VT ? (lut ? lut[tokv] : tokv) : e2s[b * CV + (tokv - VT)];
+            next_ids[(int64_t)o * B + b] = (nxt >= 0 && nxt < Vsrc) ? nxt : 1;
+        }
+    }
+}
+
 __global__ void beam_init_kernel(float* __restrict__ cum, int* __restrict__ finished, int64_t n, int W) {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
@@ -412,15 +595,16 @@ __global__ __launch_bounds__(64) void beam_backtrack_kernel(const int* __restric
 // partials per decode row of the fused generator (one per wave of every vocabulary range); no rows: no row block to size a range by
 static int beam_nparts(int64_t rows, int K, int64_t VT) { return rows > 0 ? 4 * s2s_nvr(rows, K, (VT + 15) / 16) : 0; }
 
-template <int NBT, int WM>
+template <int NBT, int WM, bool PAD>
 static void beam_gen_launch(int grid, size_t lds, hipStream_t st, const float* x, const void* frag, const float* bias, int64_t VT, int64_t ntiles,
                             int64_t rows, int K, int nvr, int W, float* pval, int* pidx, float* pm, float* ps) {
-    hipLaunchKernelGGL((beam_gen_topk_kernel<NBT, WM>), dim3((unsigned)grid), dim3(256), lds, st, x, (const _Float16*)frag, bias, VT, ntiles, rows, K, nvr, W,
+    hipLaunchKernelGGL((beam_gen_topk_kernel<NBT, WM, PAD>), dim3((unsigned)grid), dim3(256), lds, st, x, (const _Float16*)frag, bias, VT, ntiles, rows, K, nvr, W,
                        pval, pidx, pm, ps);
 }
 // the fused generator: partials pval / pidx [nparts][rows][W], pm / ps [nparts][rows]; returns nparts through *nparts
+// (pad: the PAD-substituting instantiations of the copy generator's beam)
 static int launch_beam_gen_topk(const float* x, const void* frag, const float* bias, int64_t VT, int64_t rows, int K, int W, float* pval, int* pidx,
-                                float* pm, float* ps, hipStream_t st) {
+                                float* pm, float* ps, hipStream_t st, bool pad = false) {
     const int64_t ntiles = (VT + 15) / 16;
     const int nbt = s2s_nbt(K), nvr = s2s_nvr(rows, K, ntiles);
     const int64_t rb = (rows + 16 * nbt - 1) / (16 * nbt);
@@ -431,22 +615,34 @@ static int launch_beam_gen_topk(const float* x, const void* frag, const float* b
         (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(512));
         (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(1024));
         (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(1024));
+        (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<4, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(512));
+        (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<4, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(512));
+        (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<2, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(1024));
+        (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<2, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(1024));
     });
     {
         ProfScope ps_(prof_shape_name("beam_gen_topk_kernel", (long long)rows, (long long)VT, K), st);
         const int grid = (int)(nvr * rb);
-        if (nbt == 4 && W <= 4) beam_gen_launch<4, 4>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
-        else if (nbt == 4) beam_gen_launch<4, 8>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
-        else if (W <= 4) beam_gen_launch<2, 4>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
-        else beam_gen_launch<2, 8>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
+        if (pad) {
+            if (nbt == 4 && W <= 4) beam_gen_launch<4, 4, true>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
+            else if (nbt == 4) beam_gen_launch<4, 8, true>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
+            else if (W <= 4) beam_gen_launch<2, 4, true>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
+            else beam_gen_launch<2, 8, true>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
+        } else if (nbt == 4 && W <= 4) beam_gen_launch<4, 4, false>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
+        else if (nbt == 4) beam_gen_launch<4, 8, false>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
+        else if (W <= 4) beam_gen_launch<2, 4, false>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
+        else beam_gen_launch<2, 8, false>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
     }
     NIR_CHECK_LAUNCH("beam_gen_topk_kernel");
     return 0;
 }
-static int launch_beam_row_topk(const float* logits, int64_t VT, int64_t rows, int W, float* top_val, int* top_idx, float* lse, hipStream_t st) {
+// psum given: the PAD form, (max, sum) apart in lse / psum
+static int launch_beam_row_topk(const float* logits, int64_t VT, int64_t rows, int W, float* top_val, int* top_idx, float* lse, hipStream_t st,
+                                float* psum = nullptr) {
     {
         ProfScope ps_("beam_row_topk_kernel", st);
-        hipLaunchKernelGGL(beam_row_topk_kernel, dim3((unsigned)rows), dim3(256), 0, st, logits, VT, W, top_val, top_idx, lse);
+        if (psum) hipLaunchKernelGGL(beam_row_topk_kernel<true>, dim3((unsigned)rows), dim3(256), 0, st, logits, VT, W, top_val, top_idx, lse, psum);
+        else hipLaunchKernelGGL(beam_row_topk_kernel<false>, dim3((unsigned)rows), dim3(256), 0, st, logits, VT, W, top_val, top_idx, lse, psum);
     }
     NIR_CHECK_LAUNCH("beam_row_topk_kernel");
     return 0;
@@ -473,15 +669,53 @@ static int launch_beam_reorder(const int* backptr, int64_t B, int W, int H, cons
 }
 static bool beam_dims_ok(int W, int64_t VT) { return W >= 1 && W <= NIR_BEAM_MAX_W && VT >= W; }
 
+// ---- the copy generator's beam: the two per-row launches, and the selection ---------------------------------------------------------------------
+// partials of the PAD-substituting generator top-k (fused: gen_frag given; plain: GEMM into `logits` + the row kernel, one part per row, its sum
+// in ps) -> acg_beam_row_kernel.  ps is needed in both forms.
+static int launch_acg_beam_gen_select(const float* o, int64_t R, int64_t nsrc, int K, const float* gen_w, const float* gen_b, const void* gen_frag,
+                                      int64_t VT, int W, float* logits, float* pval, int* pidx, float* pm, float* ps, const float* copy_w,
+                                      const float* copy_b, const float* attn, int64_t attn_stride, const int64_t* lens, int QL, const int64_t* map,
+                                      const int64_t* e2t, int CV, const int* finished, float* top_val, int* top_idx, hipStream_t st) {
+    int nparts = 1;
+    if (gen_frag) {
+        nparts = beam_nparts(R, K, VT);
+        NIR_PROPAGATE(launch_beam_gen_topk(o, gen_frag, gen_b, VT, R, K, W, pval, pidx, pm, ps, st, true));
+    } else {
+        NIR_PROPAGATE(launch_linear(o, K, nullptr, nullptr, 0, 0, 0, gen_w, K, gen_b, nullptr, logits, VT, R, (int)VT, K, NIR_ACT_NONE, st));
+        NIR_PROPAGATE(launch_beam_row_topk(logits, VT, R, W, pval, pidx, pm, st, ps));
+    }
+    {
+        ProfScope ps_("acg_beam_row_kernel", st);
+        hipLaunchKernelGGL(acg_beam_row_kernel, dim3((unsigned)R), dim3(64), (size_t)2 * CV * sizeof(float), st, o, K, gen_w, gen_b, VT, pval, pidx, pm, ps,
+                           nparts, R, nsrc, W, copy_w, copy_b, attn, attn_stride, lens, QL, map, e2t, CV, finished, top_val, top_idx);
+    }
+    NIR_CHECK_LAUNCH("acg_beam_row_kernel");
+    return 0;
+}
+static int launch_acg_beam_select(const float* top_val, const int* top_idx, const float* lse, int64_t B, int W, int64_t VT, int CV, const int64_t* lut,
+                                  const int64_t* e2s, int64_t V, float* cum, int* finished, int* backptr, int* token, int64_t* next_ids, hipStream_t st) {
+    {
+        ProfScope ps_("acg_beam_select_kernel", st);
+        hipLaunchKernelGGL(acg_beam_select_kernel, dim3((unsigned)B), dim3(64), 0, st, top_val, top_idx, lse, B, W, VT, CV, lut, e2s, V, cum, finished, backptr,
+                           token, next_ids);
+    }
+    NIR_CHECK_LAUNCH("acg_beam_select_kernel");
+    return 0;
+}
+static bool acg_beam_dims_ok(int QL, int CV, int64_t VT) { return acg_dims_ok(QL, CV) && VT + CV < 0x7FFFFFFFLL; }
+
 struct BeamPlan {
     S2sStepBufs s;                                    // the stepper's buffers, over R = B W decode rows
     float *pval, *pm, *ps, *cum, *attn;
     int *pidx, *fin, *bp, *tok;
+    float *tval, *csb, *cq, *ccat, *cattn;            // ACG only: the rows' lists; a copy attention of its own
+    int* tidx;
     int nparts;
     size_t bytes;
 };
+// acg: 0 = Seq2seq, 1 = ACG with reuse_copy_attn, 2 = ACG with a copy attention of its own (its buffers lie behind everything Seq2seq's plan holds)
 static BeamPlan beam_plan(void* ws, size_t cap, int64_t B, int QL, int W, int max_len, int H, int64_t VT, int attn_type, bool fused, int cell,
-                          bool step16, bool own_bp) {
+                          bool step16, bool own_bp, int acg = 0) {
     Workspace a(ws, cap);
     BeamPlan p;
     const int64_t R = B * W;
@@ -498,12 +732,28 @@ static BeamPlan beam_plan(void* ws, size_t cap, int64_t B, int QL, int W, int ma
     p.tok = a.take<int>((size_t)max_len * R);
     p.attn = a.take<float>((size_t)max_len * R * QL);
     if (cell == S2S_CELL_GRU) p.s.gru = a.take<float>(gru_step_scratch_floats(R, H));
+    p.tval = p.csb = p.cq = p.ccat = p.cattn = nullptr;
+    p.tidx = nullptr;
+    if (acg) {
+        if (!fused) p.ps = a.take<float>((size_t)R);                                       // the plain row kernel's sums
+        p.tval = a.take<float>((size_t)R * W);
+        p.tidx = a.take<int>((size_t)R * W);
+    }
+    if (acg == 2) {
+        p.csb = a.take<float>(attn_type == NIR_S2S_ATTN_DOT ? 0 : (size_t)B * QL * H);
+        p.cq = a.take<float>(attn_type == NIR_S2S_ATTN_MLP ? (size_t)R * H : 0);
+        p.ccat = a.take<float>((size_t)R * 2 * H);
+        p.cattn = a.take<float>((size_t)R * QL);
+    }
     p.bytes = align_up(a.off, 256);
     return p;
 }
-static size_t beam_decode_workspace_bytes(int64_t B, int QL, int W, int max_len, const nir_seq2seq_decoder_weights* w, int cell) {
+static size_t beam_decode_workspace_bytes(int64_t B, int QL, int W, int max_len, const nir_seq2seq_decoder_weights* w, int cell,
+                                          const AcgDecode* acg = nullptr) {
     if (!s2s_weights_ok(w) || B < 0 || QL <= 0 || max_len <= 0 || !beam_dims_ok(W, w->VT)) return 0;
-    return beam_plan(nullptr, 0, B, QL, W, max_len, w->H, w->VT, w->attn_type, s2s_fused(w), cell, s2s_step16(w), true).bytes;
+    if (acg && (!acg_weights_ok(w, acg) || !acg_beam_dims_ok(QL, acg->CV, w->VT))) return 0;
+    return beam_plan(nullptr, 0, B, QL, W, max_len, w->H, w->VT, w->attn_type, s2s_fused(w), cell, s2s_step16(w), true,
+                     acg ? (acg->cw->reuse_copy_attn ? 1 : 2) : 0).bytes;
 }
 
 // The stepper of s2s_gen.hpp over W decode rows per source row, with the beam's tail behind the attentional output: top-k, select, reorder.  A
@@ -511,15 +761,22 @@ static size_t beam_decode_workspace_bytes(int64_t B, int QL, int W, int max_len,
 static int s2s_beam_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, int W,
                            const float* table, int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len, const nir_seq2seq_decoder_weights* w,
                            void* workspace, size_t workspace_bytes, int64_t* predictions, float* scores, int64_t* lengths, float* attentions,
-                           int32_t* backptr, int cell, hipStream_t st) {
+                           int32_t* backptr, int cell, hipStream_t st, const AcgDecode* acg = nullptr) {
     const int64_t R = B * W;
-    S2sStepper s{"beam_seq2seq_decode", w, cell, table, memory_bank, source_len, V, R, B, E, QL, st};
+    S2sStepper s{acg ? "acg_beam_decode" : "beam_seq2seq_decode", w, cell, table, memory_bank, source_len, V, R, B, E, QL, st};
     NIR_PROPAGATE(s.check(dec_h, dec_c, predictions && scores && lengths && attentions, bos, max_len));
     NIR_REQUIRE(beam_dims_ok(W, w->VT), "beam_seq2seq_decode: beam width outside [1, %d] or above the target vocabulary", NIR_BEAM_MAX_W);
     NIR_REQUIRE(R < 0x7FFFFFFFLL, "beam_seq2seq_decode: too many decode rows");
+    const bool own_copy_attn = acg && acg->cw && !acg->cw->reuse_copy_attn;
+    if (acg) {
+        NIR_REQUIRE(acg_weights_ok(w, acg), "acg_beam_decode: copy weights incomplete for the attention type");
+        NIR_REQUIRE(acg->src_map_idx && acg->ext2tgt && acg->ext2src, "acg_beam_decode: null index tensor");
+        NIR_REQUIRE(acg_beam_dims_ok(QL, acg->CV, w->VT), "acg_beam_decode: CV outside [2, %d], or VT + CV too large", ACG_MAX_CV);
+    }
     const int H = w->H;
     const bool fused = s.fused, step16 = s.step16, gru = cell == S2S_CELL_GRU;
-    BeamPlan p = beam_plan(workspace, workspace_bytes, B, QL, W, max_len, H, w->VT, w->attn_type, fused, cell, step16, backptr == nullptr);
+    BeamPlan p = beam_plan(workspace, workspace_bytes, B, QL, W, max_len, H, w->VT, w->attn_type, fused, cell, step16, backptr == nullptr,
+                           acg ? (own_copy_attn ? 2 : 1) : 0);
     if (!workspace || p.bytes > workspace_bytes) {
         set_error("beam_seq2seq_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
         return NIR_ERR_WORKSPACE;
@@ -532,19 +789,43 @@ static int s2s_beam_decode(const float* dec_h, const float* dec_c, const float* 
     int* bp = backptr ? backptr : p.bp;
     const float* hp = dec_h;
     const float* cp = dec_c;
+    const bool mlp = w->attn_type == NIR_S2S_ATTN_MLP;
+    const float* csb = memory_bank;                       // the score bank of ACG's own copy attention, over the B source rows (s2s_decode)
+    if (own_copy_attn && w->attn_type != NIR_S2S_ATTN_DOT) {
+        NIR_PROPAGATE(launch_linear(memory_bank, H, nullptr, nullptr, 0, 0, 0, mlp ? acg->cw->attn_ctx_w : acg->cw->attn_in_wt, H, nullptr, nullptr, p.csb, H,
+                                    B * QL, H, H, NIR_ACT_NONE, st));
+        csb = p.csb;
+    }
     for (int step = 0; step < max_len; ++step) {
         float* hn = p.s.h[1];
         float* cn = p.s.c[1];
         NIR_PROPAGATE(s.step(hp, cp, hn, cn, p.s.h16[0], p.s.h16[1], p.attn + (int64_t)step * R * QL, QL));
-        if (fused) {
+        if (acg) {
+            // ACG's tail: (a second attention whose query is the attentional output,) the W best of every row's collapsed extended distribution,
+            // the selection over the source row's W W candidates
+            const float* ca = p.attn + (int64_t)step * R * QL;
+            if (own_copy_attn) {
+                if (mlp)
+                    NIR_PROPAGATE(launch_linear(p.s.ah, H, nullptr, nullptr, 0, 0, 0, acg->cw->attn_query_w, H, acg->cw->attn_query_b, nullptr, p.cq, H, R, H, H,
+                                                NIR_ACT_NONE, st));
+                NIR_PROPAGATE(launch_attend(mlp ? p.cq : p.s.ah, p.s.ah, memory_bank, csb, acg->cw->attn_v, source_len, R, QL, H, mlp, p.ccat, p.cattn, QL, st, B));
+                ca = p.cattn;
+            }
+            NIR_PROPAGATE(launch_acg_beam_gen_select(p.s.ah, R, B, H, w->gen_w, w->gen_b, fused ? w->gen_frag : nullptr, w->VT, W, p.s.logits, p.pval, p.pidx,
+                                                     p.pm, p.ps, acg->cw->copy_w, acg->cw->copy_b, ca, QL, source_len, QL, acg->src_map_idx, acg->ext2tgt,
+                                                     acg->CV, p.fin, p.tval, p.tidx, st));
+            NIR_PROPAGATE(launch_acg_beam_select(p.tval, p.tidx, nullptr, B, W, w->VT, acg->CV, tgt2src, acg->ext2src, V, p.cum, p.fin, bp + (int64_t)step * R,
+                                                 p.tok + (int64_t)step * R, p.s.tgt, st));
+        } else if (fused) {
             NIR_PROPAGATE(launch_beam_gen_topk(p.s.ah, w->gen_frag, w->gen_b, w->VT, R, H, W, p.pval, p.pidx, p.pm, p.ps, st));
         } else {
             NIR_PROPAGATE(launch_linear(p.s.ah, H, nullptr, nullptr, 0, 0, 0, w->gen_w, H, w->gen_b, nullptr, p.s.logits, w->VT, R, (int)w->VT, H, NIR_ACT_NONE,
                                         st));
             NIR_PROPAGATE(launch_beam_row_topk(p.s.logits, w->VT, R, W, p.pval, p.pidx, p.pm, st));
         }
-        NIR_PROPAGATE(launch_beam_select(p.pval, p.pidx, p.pm, fused ? p.ps : nullptr, p.nparts, B, W, w->VT, tgt2src, V, p.cum, p.fin,
-                                         bp + (int64_t)step * R, p.tok + (int64_t)step * R, p.s.tgt, st));
+        if (!acg)
+            NIR_PROPAGATE(launch_beam_select(p.pval, p.pidx, p.pm, fused ? p.ps : nullptr, p.nparts, B, W, w->VT, tgt2src, V, p.cum, p.fin,
+                                             bp + (int64_t)step * R, p.tok + (int64_t)step * R, p.s.tgt, st));
         if (step + 1 < max_len)
             NIR_PROPAGATE(launch_beam_reorder(bp + (int64_t)step * R, B, W, H, hn, p.s.h[0], gru ? nullptr : cn, gru ? nullptr : p.s.c[0],
                                               step16 ? p.s.h16[1] : nullptr, step16 ? p.s.h16[0] : nullptr, st));
@@ -904,4 +1185,89 @@ extern "C" int nir_beam_seq2seq_gru_decode(const float* dec_h, const float* memo
                                            float* scores, int64_t* lengths, float* attentions, int32_t* backptr, nir_stream_t stream) {
     return nir::s2s_beam_decode(dec_h, nullptr, memory_bank, source_len, B, QL, W, table, V, E, tgt2src, bos, max_len, w, workspace, workspace_bytes,
                                 predictions, scores, lengths, attentions, backptr, nir::S2S_CELL_GRU, (hipStream_t)stream);
+}
+
+// ---- the copy generator's beam (include/neuroir_acg_beam.h) ---------------------------------------------------------------------------------------
+extern "C" size_t nir_acg_beam_gen_select_workspace_bytes(int64_t rows, int K, int64_t VT, int W, int fused) {
+    using namespace nir;
+    if (rows <= 0 || K <= 0 || !beam_dims_ok(W, VT)) return 0;
+    if (fused && !s2s_fusable(K, VT)) return 0;
+    const size_t parts = fused ? (size_t)beam_nparts(rows, K, VT) : 1;
+    return (fused ? 0 : align_up((size_t)rows * VT * sizeof(float), 256)) + parts * rows * ((size_t)W * 8 + 8) + 5 * 256;
+}
+
+extern "C" int nir_acg_beam_gen_select(const float* o, int64_t rows, int64_t nsrc, int K, const float* gen_w, const float* gen_b, const void* gen_frag,
+                                       int64_t VT, int W, const float* copy_w, const float* copy_b, const float* copy_attn, int64_t attn_stride,
+                                       const int64_t* source_len, int QL, const int64_t* src_map_idx, const int64_t* ext2tgt, const int64_t* ext2src, int CV,
+                                       void* workspace, size_t workspace_bytes, float* top_val, int32_t* top_idx, nir_stream_t stream) {
+    using namespace nir;
+    NIR_REQUIRE(o && gen_w && copy_w && copy_b && copy_attn && source_len && src_map_idx && ext2tgt && ext2src && workspace && top_val && top_idx,
+                "acg_beam_gen_select: null pointer");
+    NIR_REQUIRE(rows >= 0 && rows < 0x7FFFFFFFLL && nsrc >= 0 && (rows == 0 || (nsrc > 0 && nsrc <= rows)) && K > 0 && K % 4 == 0 && VT > 0 &&
+                    attn_stride >= QL,
+                "acg_beam_gen_select: bad dims");
+    NIR_REQUIRE(beam_dims_ok(W, VT), "acg_beam_gen_select: beam width outside [1, %d] or above VT", NIR_BEAM_MAX_W);
+    NIR_REQUIRE(acg_beam_dims_ok(QL, CV, VT), "acg_beam_gen_select: QL outside [1, 4096], CV outside [2, %d], or VT + CV too large", ACG_MAX_CV);
+    const bool fused = s2s_gen_fused(gen_frag, K, VT);
+    if (rows == 0) return 0;
+    if (workspace_bytes < nir_acg_beam_gen_select_workspace_bytes(rows, K, VT, W, fused)) {
+        set_error("acg_beam_gen_select: workspace too small");
+        return NIR_ERR_WORKSPACE;
+    }
+    Workspace a(workspace, workspace_bytes);
+    const size_t parts = fused ? (size_t)beam_nparts(rows, K, VT) : 1;
+    float* logits = a.take<float>(fused ? 0 : (size_t)rows * VT);
+    float* pval = a.take<float>(parts * rows * W);
+    int* pidx = a.take<int>(parts * rows * W);
+    float* pm = a.take<float>(parts * rows);
+    float* ps = a.take<float>(parts * rows);
+    return launch_acg_beam_gen_select(o, rows, nsrc, K, gen_w, gen_b, fused ? gen_frag : nullptr, VT, W, logits, pval, pidx, pm, ps, copy_w, copy_b, copy_attn,
+                                      attn_stride, source_len, QL, src_map_idx, ext2tgt, CV, nullptr, top_val, top_idx, (hipStream_t)stream);
+}
+
+extern "C" int nir_acg_beam_select(const float* top_val, const int32_t* top_idx, const float* lse, int64_t B, int W, int64_t VT, int CV,
+                                   const int64_t* tgt2src, const int64_t* ext2src, int64_t V, float* cum, int32_t* finished, int32_t* backptr,
+                                   int32_t* token, int64_t* next_ids, nir_stream_t stream) {
+    using namespace nir;
+    NIR_REQUIRE(top_val && top_idx && ext2src && cum && finished && backptr && token && next_ids, "acg_beam_select: null pointer");
+    NIR_REQUIRE(B >= 0 && B * NIR_BEAM_MAX_W < 0x7FFFFFFFLL && V > 0, "acg_beam_select: bad dims");
+    NIR_REQUIRE(beam_dims_ok(W, VT), "acg_beam_select: beam width outside [1, %d] or above VT", NIR_BEAM_MAX_W);
+    NIR_REQUIRE(acg_beam_dims_ok(1, CV, VT), "acg_beam_select: CV outside [2, %d], or VT + CV too large", ACG_MAX_CV);
+    if (B == 0) return 0;
+    return launch_acg_beam_select(top_val, top_idx, lse, B, W, VT, CV, tgt2src, ext2src, V, cum, finished, backptr, token, next_ids, (hipStream_t)stream);
+}
+
+extern "C" size_t nir_acg_beam_decode_workspace_bytes(int64_t B, int QL, int CV, int W, int max_len, const nir_seq2seq_decoder_weights* w,
+                                                      const nir_acg_copy_weights* cw) {
+    if (!cw) return 0;
+    nir::AcgDecode g{cw, nullptr, nullptr, nullptr, CV};
+    return nir::beam_decode_workspace_bytes(B, QL, W, max_len, w, nir::S2S_CELL_LSTM, &g);
+}
+extern "C" int nir_acg_beam_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL,
+                                   const float* table, int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len,
+                                   const nir_seq2seq_decoder_weights* w, const nir_acg_copy_weights* cw, const int64_t* src_map_idx, const int64_t* ext2tgt,
+                                   const int64_t* ext2src, int CV, int W, void* workspace, size_t workspace_bytes, int64_t* predictions, float* scores,
+                                   int64_t* lengths, float* attentions, int32_t* backptr, nir_stream_t stream) {
+    using namespace nir;
+    NIR_REQUIRE(cw, "acg_beam_decode: null copy weights");
+    AcgDecode g{cw, src_map_idx, ext2tgt, ext2src, CV};
+    return s2s_beam_decode(dec_h, dec_c, memory_bank, source_len, B, QL, W, table, V, E, tgt2src, bos, max_len, w, workspace, workspace_bytes, predictions,
+                           scores, lengths, attentions, backptr, S2S_CELL_LSTM, (hipStream_t)stream, &g);
+}
+extern "C" size_t nir_acg_beam_gru_decode_workspace_bytes(int64_t B, int QL, int CV, int W, int max_len, const nir_seq2seq_decoder_weights* w,
+                                                          const nir_acg_copy_weights* cw) {
+    if (!cw) return 0;
+    nir::AcgDecode g{cw, nullptr, nullptr, nullptr, CV};
+    return nir::beam_decode_workspace_bytes(B, QL, W, max_len, w, nir::S2S_CELL_GRU, &g);
+}
+extern "C" int nir_acg_beam_gru_decode(const float* dec_h, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, const float* table,
+                                       int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len, const nir_seq2seq_decoder_weights* w,
+                                       const nir_acg_copy_weights* cw, const int64_t* src_map_idx, const int64_t* ext2tgt, const int64_t* ext2src, int CV,
+                                       int W, void* workspace, size_t workspace_bytes, int64_t* predictions, float* scores, int64_t* lengths,
+                                       float* attentions, int32_t* backptr, nir_stream_t stream) {
+    using namespace nir;
+    NIR_REQUIRE(cw, "acg_beam_decode: null copy weights");
+    AcgDecode g{cw, src_map_idx, ext2tgt, ext2src, CV};
+    return s2s_beam_decode(dec_h, nullptr, memory_bank, source_len, B, QL, W, table, V, E, tgt2src, bos, max_len, w, workspace, workspace_bytes, predictions,
+                           scores, lengths, attentions, backptr, S2S_CELL_GRU, (hipStream_t)stream, &g);
 }

@@ -203,6 +203,7 @@ static inline int s2s_nvr(int64_t Bd, int K, int64_t ntiles) {
 }
 
 // ---- ACG: the copy generator behind the Seq2seq step (csrc/acg.hip) ----------------------------------------------------------------------
+constexpr float ACG_PAD_LOGIT = -1e-20f;              // copy_generator.py:79: logits[:, :, PAD] = -eps
 constexpr int ACG_MAX_CV = 1024;                      // dictionary slots of a row kept in LDS by acg_select_kernel (4 rows x 3 arrays x 4 KB)
 static inline bool acg_dims_ok(int QL, int CV) { return QL > 0 && QL <= 4096 && CV >= 2 && CV <= ACG_MAX_CV; }
 struct AcgDecode {
@@ -210,6 +211,7 @@ struct AcgDecode {
     const int64_t *src_map_idx, *ext2tgt, *ext2src;  // [B,QL], [B,CV], [B,CV]
     int CV;
 };
+bool acg_weights_ok(const nir_seq2seq_decoder_weights* w, const AcgDecode* g);   // csrc/seq2seq.hip: the copy weights the attention type needs
 // generator statistics (fused: gen_frag != NULL, the STATS kernel above; plain: GEMM into `logits` + acg_row_stats_kernel) + acg_select_kernel
 int launch_acg_gen_select(const float* o, int64_t B, int K, const float* gen_w, const float* gen_b, const void* gen_frag, int64_t VT, float* logits,
                           float* pval, int* pidx, float* psum, const float* copy_w, const float* copy_b, const float* attn, int64_t attn_stride,

@@ -247,7 +247,7 @@ int S2sStepper::step(const float* hp, const float* cp, float* hn, float* cn, con
                          mlp ? NIR_ACT_NONE : NIR_ACT_TANH, st);
 }
 
-static bool acg_weights_ok(const nir_seq2seq_decoder_weights* w, const AcgDecode* g) {
+bool acg_weights_ok(const nir_seq2seq_decoder_weights* w, const AcgDecode* g) {
     if (!g->cw || !g->cw->copy_w || !g->cw->copy_b) return false;
     if (g->cw->reuse_copy_attn) return true;
     if (w->attn_type == NIR_S2S_ATTN_GENERAL) return g->cw->attn_in_wt != nullptr;

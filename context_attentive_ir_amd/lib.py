@@ -344,6 +344,22 @@ SESSION_BEAM_SIGNATURES = {
                                    C.c_void_p, _z, c_ip, c_fp, c_ip, C.c_void_p, c_st]),
 }
 
+# Beam search for ACG (the copy generator's collapsed extended distribution), declared in include/neuroir_acg_beam.h (csrc/beam.hip).  The
+# tables above mirror their headers exactly (pinned by tests), so these have one of their own as well.
+_AW = C.POINTER(AcgCopyWeights)
+ACG_BEAM_SIGNATURES = {
+    "nir_acg_beam_gen_select_workspace_bytes": (_z, [_l, _i, _l, _i, _i]),
+    "nir_acg_beam_gen_select": (_i, [c_fp, _l, _l, _i, c_fp, c_fp, C.c_void_p, _l, _i, c_fp, c_fp, c_fp, _l, c_ip, _i, c_ip, c_ip, c_ip, _i, C.c_void_p, _z,
+                                     c_fp, C.c_void_p, c_st]),
+    "nir_acg_beam_select": (_i, [c_fp, C.c_void_p, c_fp, _l, _i, _l, _i, c_ip, c_ip, _l, c_fp, C.c_void_p, C.c_void_p, C.c_void_p, c_ip, c_st]),
+    "nir_acg_beam_decode_workspace_bytes": (_z, [_l, _i, _i, _i, _i, _W, _AW]),
+    "nir_acg_beam_decode": (_i, [c_fp, c_fp, c_fp, c_ip, _l, _i, c_fp, _l, _i, c_ip, _l, _i, _W, _AW, c_ip, c_ip, c_ip, _i, _i, C.c_void_p, _z, c_ip, c_fp,
+                                 c_ip, c_fp, C.c_void_p, c_st]),
+    "nir_acg_beam_gru_decode_workspace_bytes": (_z, [_l, _i, _i, _i, _i, _W, _AW]),
+    "nir_acg_beam_gru_decode": (_i, [c_fp, c_fp, c_ip, _l, _i, c_fp, _l, _i, c_ip, _l, _i, _W, _AW, c_ip, c_ip, c_ip, _i, _i, C.c_void_p, _z, c_ip, c_fp,
+                                     c_ip, c_fp, C.c_void_p, c_st]),
+}
+
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_SPLIT2 = 0, 1, 2
 DTYPES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "bf16": DTYPE_BF16, "f32_split2": DTYPE_F32_SPLIT2}
 
@@ -359,7 +375,8 @@ def load():
                 "libneuroir_hip.so not found at %s -- build it with `python -m context_attentive_ir_amd.build` "
                 "(hipcc, gfx950). The HIP path has no CPU fallback." % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(GRU_DECODE_SIGNATURES.items()) + list(BEAM_SIGNATURES.items()) + list(SESSION_BEAM_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(GRU_DECODE_SIGNATURES.items()) + list(BEAM_SIGNATURES.items()) + list(SESSION_BEAM_SIGNATURES.items())
+                                  + list(ACG_BEAM_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

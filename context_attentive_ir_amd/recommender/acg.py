@@ -11,6 +11,9 @@ decode():  the extended distribution over the VT target words and the CV words o
              ext2src     [B, CV]   source id of a slot's word (the token fed back when the slot wins)
            decode() takes them directly, or converts the reference's arguments once on the host.  `predictions` are EXTENDED ids in
            [0, VT + CV), as in the reference.
+decode_beam(): beam search over the COLLAPSED extended distribution (include/neuroir_acg_beam.h): per beam row the W
+           best entries come out of the generator's top-W, its softmax pair and at most CV further candidates (csrc/beam.hip); a slot that
+           collapses onto a target word is no candidate of its own.  The same index tensors, not repeated over the beams.
 forward(): the teacher-forced loss of CopyGeneratorCriterion on the differentiable HIP operators of autograd.py (the [B, TL, QL] gather of
            the copy mass and the [B, TL] switch logit are tensor glue).
 
@@ -87,6 +90,7 @@ def vocab_index(source_vocabs, src_dict, tgt_dict, CV=None):
 
 class ACG(Seq2seq):
     _GREEDY_ENTRY = "nir_acg%s_decode"                   # + "_greedy" / "_workspace_bytes": nir_acg_decode_greedy, nir_acg_gru_decode_greedy
+    _ACG_BEAM_ENTRY = "nir_acg_beam%s_decode"            # (+ "_workspace_bytes"): nir_acg_beam_decode, nir_acg_beam_gru_decode
 
     def __init__(self, args):
         nn.Module.__init__(self)
@@ -161,6 +165,38 @@ class ACG(Seq2seq):
             return nb
         return self._greedy(source_rep, source_len, max_len, src_dict, tgt_dict, tgt2src,
                             extra=(cw.ref(), lib.ptr(idx), lib.ptr(e2t), lib.ptr(e2s), CV), ws_bytes=ws_bytes)
+
+    # ---- eval: beam search ---------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def decode_beam(self, source_rep, source_len, max_len, beam_size, src_dict=None, tgt_dict=None, src_map=None, blank=None, fill=None,
+                    source_vocabs=None, tgt2src=None, src_map_idx=None, ext2tgt=None, ext2src=None, return_backptr=False):
+        """Beam search of width `beam_size` (1 .. lib.BEAM_MAX_W) over the COLLAPSED extended distribution (include/neuroir_acg_beam.h, DESIGN.md
+        section 24) -> Seq2seq.decode_beam's dict with EXTENDED ids in 'predictions' [B, W, max_len]: below VT a target word, from VT on slot
+        id - VT of the row's dynamic dictionary.  A word is offered once per beam: a slot that collapses onto a target word is no candidate of
+        its own, its mass is part of the word's.  The copy inputs are decode()'s; neither they nor the memory bank are repeated."""
+        name = type(self).__name__
+        if self.training:
+            raise NotImplementedError("HIP %s.decode_beam runs in eval mode" % name)
+        lib.require_device(source_rep, source_len, self.embedder.word_embeddings.table)
+        keep = []
+
+        def extra(B, QL):
+            maps = (src_map_idx, ext2tgt, ext2src)
+            if any(t is None for t in maps):
+                maps = self.copy_index(QL, src_map, blank, fill, source_vocabs, src_dict, tgt_dict)
+            dev = self.embedder.word_embeddings.table.device
+            idx, e2t, e2s = (lib.ids64(t).to(dev).contiguous() for t in maps)
+            CV = int(e2t.shape[1])
+            if tuple(idx.shape) != (B, QL) or tuple(e2t.shape) != (B, CV) or tuple(e2s.shape) != (B, CV):
+                raise ValueError("%s.decode_beam: src_map_idx %s, ext2tgt %s, ext2src %s do not fit %d rows of width %d"
+                                 % (name, tuple(idx.shape), tuple(e2t.shape), tuple(e2s.shape), B, QL))
+            if not (1 <= QL <= 4096 and 2 <= CV <= 1024):
+                raise ValueError("%s.decode_beam: QL = %d / CV = %d outside the copy generator's range (QL <= 4096, 2 <= CV <= 1024)" % (name, QL, CV))
+            cw = self._copy_weights()
+            keep.extend((idx, e2t, e2s, cw))                               # alive until the call is enqueued
+            return (CV,), (cw.ref(), lib.ptr(idx), lib.ptr(e2t), lib.ptr(e2s), CV)
+        return self._beam(source_rep, source_len, max_len, beam_size, src_dict, tgt_dict, tgt2src, return_backptr, entry=self._ACG_BEAM_ENTRY,
+                          extra=extra)
 
     # ---- train: teacher-forced loss ---------------------------------------------------------------------------------------------------
     def forward(self, source_rep, source_len, target_rep, target_len, target_seq, source_map=None, alignment=None):

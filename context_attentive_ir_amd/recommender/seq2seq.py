@@ -203,8 +203,12 @@ class Seq2seq(nn.Module, lib.IdCheck):
         beam layout (row k B + b: decoders/state.py:65-69), ONE C call.  The memory bank is not repeated."""
         if self.training:
             raise NotImplementedError("HIP %s.decode_beam runs in eval mode" % type(self).__name__)
-        if self.copy_attn:
-            raise NotImplementedError("HIP beam search covers Seq2seq and Seq2seqGRU; the copy generator of ACG has no beam (DESIGN.md section 21)")
+        return self._beam(source_rep, source_len, max_len, beam_size, src_dict, tgt_dict, tgt2src, return_backptr)
+
+    def _beam(self, source_rep, source_len, max_len, beam_size, src_dict, tgt_dict, tgt2src, return_backptr, entry=None, extra=None):
+        """the beam search of Seq2seq and ACG, either cell.  entry: the C entry (default: _BEAM_ENTRY, which takes W behind QL); extra(B, QL) ->
+        (what the size entry takes between QL and W, the C arguments the entry takes behind the decoder weights, W following them): ACG's copy
+        inputs, checked once the shapes are known."""
         W = int(beam_size)
         B, QL, table = self._decode_ready("decode_beam", source_rep, source_len)
         L = lib.load()
@@ -212,6 +216,7 @@ class Seq2seq(nn.Module, lib.IdCheck):
         VT = int(w.struct.VT)
         if not 1 <= W <= lib.BEAM_MAX_W or W > VT:
             raise ValueError("decode_beam: beam_size %d outside [1, %d] or above the target vocabulary (%d)" % (W, lib.BEAM_MAX_W, VT))
+        ws_extra, tail = (None, None) if extra is None else extra(B, QL)
         src, _ = self._clean_ids(source_rep, None, table.shape[0])
         lens = lib.ids64(source_len)
         state, bank = self._encode_state(src, lens)
@@ -231,11 +236,20 @@ class Seq2seq(nn.Module, lib.IdCheck):
         if return_backptr:
             out["backptr"] = torch.empty(max_len, B, W, dtype=torch.int32, device=dev)
         if B > 0 and max_len > 0:
-            entry = self._BEAM_ENTRY % self._ENTRY_CELL
-            ws = lib.workspace(getattr(L, entry + "_workspace_bytes")(B, QL, W, max_len, ws_ref), dev)
-            args = [lib.ptr(s) for s in state] + [lib.ptr(bank), lib.ptr(lens), B, QL, W, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(tgt2src), BOS,
-                                                  max_len, ws_ref, lib.ptr(ws), ws.numel(), lib.ptr(out["predictions"]), lib.ptr(out["scores"]),
-                                                  lib.ptr(out["lengths"]), lib.ptr(out["attentions"]), lib.ptr(out.get("backptr")), lib.stream()]
+            entry = (self._BEAM_ENTRY if entry is None else entry) % self._ENTRY_CELL
+            outs = [lib.ptr(out["predictions"]), lib.ptr(out["scores"]), lib.ptr(out["lengths"]), lib.ptr(out["attentions"]), lib.ptr(out.get("backptr")),
+                    lib.stream()]
+            front = [lib.ptr(s) for s in state] + [lib.ptr(bank), lib.ptr(lens), B, QL]
+            mid = [lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(tgt2src), BOS, max_len, ws_ref]
+            if tail is None:
+                ws = lib.workspace(getattr(L, entry + "_workspace_bytes")(B, QL, W, max_len, ws_ref), dev)
+                args = front + [W] + mid + [lib.ptr(ws), ws.numel()] + outs
+            else:
+                nb = getattr(L, entry + "_workspace_bytes")(B, QL, *ws_extra, W, max_len, ws_ref, tail[0])
+                if nb == 0:
+                    raise ValueError("%s.decode_beam: the shapes are outside the entry's range (%s)" % (type(self).__name__, entry))
+                ws = lib.workspace(nb, dev)
+                args = front + mid + list(tail) + [W, lib.ptr(ws), ws.numel()] + outs
             lib.check(getattr(L, entry)(*args), entry)
         return out
 

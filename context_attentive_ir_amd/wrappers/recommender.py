@@ -128,8 +128,6 @@ class Recommender(WrapperBase):
         a batch in the reference's collate layout also `ex_ids`, `targets`, `src_sequences` and `predictions`: per row the list of its W
         strings, each formed like predict()'s.  `beam_size` is an argument of the call, not a field of args.  Graph replay as in predict()."""
         W = int(beam_size)
-        if self.network.copy_attn:
-            raise NotImplementedError("HIP beam search covers Seq2seq and Seq2seqGRU; ACG's copy generator has no beam (DESIGN.md section 21)")
         self._poll_ids()
         body = lambda e: self._predict_beam_body(e, W)                        # noqa: E731
         out = self._graphed(ex, Recommender._FIELDS, "decode_beam%d" % W, body)
@@ -142,6 +140,11 @@ class Recommender(WrapperBase):
             out.update(per_beam[0])
             out["predictions"] = [[per_beam[k]["predictions"][b] for k in range(W)] for b in range(len(per_beam[0]["predictions"]))]
         return out
+
+    def predict_nbest(self, ex, beam_size):
+        """n-best suggestions, the one name every wrapper has: predict_beam here; CopyRecommender's is ACG's search over the copy generator's
+        distribution; SessionRecommender (HredQS) has none."""
+        return self.predict_beam(ex, beam_size)
 
     def _text(self, ex, pred_ids, attns):
         """the host-side tail of the reference's predict (models/recommender.py:294-309): tens2sen (utils/misc.py:36-62) + replace_unknown
@@ -208,6 +211,9 @@ class SessionRecommender(Recommender):
 
     def predict_beam(self, ex, beam_size):
         raise NotImplementedError("HIP beam search covers Seq2seq and Seq2seqGRU; HredQS keeps its greedy decode (DESIGN.md section 21)")
+
+    def predict_nbest(self, ex, beam_size):
+        raise NotImplementedError("HIP beam search covers Seq2seq, Seq2seqGRU, ACG and ACGGRU; HredQS keeps its greedy decode (DESIGN.md sections 21, 24)")
 
     def _predict_body(self, ex):
         self.network.eval()
@@ -333,6 +339,41 @@ class CopyRecommender(Recommender):
         `predictions` (strings; copied words come from the row's dictionary, a remaining <unk> is replaced by the most attended source token),
         `targets`, `src_sequences`.  Graph replay as in Recommender.predict; the copy maps are inputs of the graph."""
         return super().predict(self._copy_fields(ex))
+
+    def predict_beam(self, ex, beam_size):
+        raise NotImplementedError("CopyRecommender.predict_beam: ACG's beam search is predict_nbest(ex, beam_size) -- its ids are EXTENDED ids and its "
+                                  "batches carry the copy maps (DESIGN.md section 24)")
+
+    def _predict_nbest_body(self, ex, beam_size):
+        self.network.eval()
+        dec = self.network.decode_beam(source_rep=self._dev(self._rows3(ex["source_words"])), source_len=self._dev(self._rows2(ex["source_lens"])),
+                                       max_len=self.args.max_query_len, beam_size=beam_size, src_dict=self.src_dict, tgt_dict=self.tgt_dict,
+                                       src_map_idx=self._dev(ex["copy_src_map_idx"]), ext2tgt=self._dev(ex["copy_ext2tgt"]),
+                                       ext2src=self._dev(ex["copy_ext2src"]))
+        self._maybe_check_ids()
+        return {"prediction_ids": dec["predictions"], "scores": dec["scores"], "lengths": dec["lengths"], "attentions": dec["attentions"]}
+
+    @torch.no_grad()
+    def predict_nbest(self, ex, beam_size):
+        """n-best suggestions by beam search over the collapsed extended distribution (ACG.decode_beam; the reference has no counterpart):
+        {'prediction_ids': LongTensor [B, W, max_query_len] (EXTENDED ids), 'scores': [B, W], 'lengths': LongTensor [B, W], 'attentions':
+        [B, W, max_query_len, QL]}, best beam first; for a full collate batch also `ex_ids`, `targets`, `src_sequences` and `predictions`: per
+        row the list of its W strings, each formed like predict()'s (copied words come from the row's dictionary).  Graph replay as in
+        predict(): the width is part of the graph's key, the three copy maps are inputs of the graph."""
+        W = int(beam_size)
+        ex = self._copy_fields(ex)
+        self._poll_ids()
+        body = lambda e: self._predict_nbest_body(e, W)                       # noqa: E731
+        out = self._graphed(ex, self._FIELDS, "decode_nbest%d" % W, body)
+        if out is None:
+            out = body(ex)
+        elif self.id_check == "blocking":
+            self._maybe_check_ids()
+        if all(k in ex for k in ("ids", "source_tokens", "target_tokens", "src_vocab")):
+            per_beam = [self._text(ex, out["prediction_ids"][:, k], out["attentions"][:, k]) for k in range(W)]
+            out.update(per_beam[0])
+            out["predictions"] = [[per_beam[k]["predictions"][b] for k in range(W)] for b in range(len(per_beam[0]["predictions"]))]
+        return out
 
     def _text(self, ex, pred_ids, attns):
         """tens2sen with the rows' dictionaries (utils/misc.py:36-62) + replace_unknown"""

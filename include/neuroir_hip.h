@@ -1147,6 +1147,8 @@ int nir_acg_copy_loss_bwd(const float* logits, int64_t ld, const float* switch_l
 #include "neuroir_beam.h"
 /* ... and for the session models (CARS, M_MATCH_TENSOR, MNSRF), in a third one (ctypes: lib.SESSION_BEAM_SIGNATURES). */
 #include "neuroir_session_beam.h"
+/* ... and for ACG, over the copy generator's collapsed extended distribution, in a fourth (ctypes: lib.ACG_BEAM_SIGNATURES). */
+#include "neuroir_acg_beam.h"
 
 #ifdef __cplusplus
 }

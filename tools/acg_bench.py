@@ -10,7 +10,10 @@ Prints one JSON line: ms per batch (median of --iters, CUDA events, after --warm
 
 --rnn_type GRU builds ACGGRU / Seq2seqGRU (csrc/gru_step.hip) instead.
 
-    python tools/acg_bench.py [--rnn_type LSTM|GRU] [--B 64] [--iters 20] [--warmup 5] [--rounds 3] [--json out.json]
+--beam_size W times `CopyRecommender.predict_nbest(ex, W)` (csrc/beam.hip) instead: the fused generator top-k against
+the plain form (fp32 GEMM + row top-k) and against the greedy `predict` of the same model, in the same alternating rounds.
+
+    python tools/acg_bench.py [--rnn_type LSTM|GRU] [--beam_size W] [--B 64] [--iters 20] [--warmup 5] [--rounds 3] [--json out.json]
 """
 import argparse
 import json
@@ -36,6 +39,7 @@ def main():
     ap.add_argument("--nhid", type=int, default=512)
     ap.add_argument("--max_len", type=int, default=20)
     ap.add_argument("--rnn_type", default="LSTM", choices=["LSTM", "GRU"])
+    ap.add_argument("--beam_size", type=int, default=0, help="> 0: time predict_nbest at this width (fused / plain top-k, greedy next to them)")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3, help="alternating repeats of the timings; the spread of their medians is reported")
@@ -79,6 +83,8 @@ def main():
     def plain_s2s():
         return s2s.predict(ex)["prediction_ids"]
 
+    if a.beam_size > 0:
+        return beam(a, acg, exc, copy, CV)
     with torch.no_grad():
         fused_r, plain_r, s2s_r = [], [], []
         for _ in range(max(1, a.rounds)):                    # the paths alternate, so that drift of the machine meets all of them
@@ -95,6 +101,34 @@ def main():
                ms_rounds=[round(v, 4) for v in fused_r], plain_ms_rounds=[round(v, 4) for v in plain_r], seq2seq_ms_rounds=[round(v, 4) for v in s2s_r],
                copy_step_ms=round(fused - base, 4), tokens_equal_fused_plain=float((p_fused == p_plain).float().mean()),
                copied_share=float((p_fused >= a.VT).float().mean()))
+    print(json.dumps(out))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+def beam(a, acg, exc, greedy, CV):
+    W = a.beam_size
+
+    def nbest():
+        return acg.predict_nbest(exc, W)["prediction_ids"]
+
+    with torch.no_grad():
+        fused_r, plain_r, greedy_r = [], [], []
+        for _ in range(max(1, a.rounds)):                    # the paths alternate, so that drift of the machine meets all of them
+            acg.network.fuse_generator_topk = True           # (part of the graph cache's key: the next call captures the other path)
+            fused_r.append(timed(nbest, a.iters, a.warmup))
+            p_fused = nbest().clone()
+            acg.network.fuse_generator_topk = False
+            plain_r.append(timed(nbest, a.iters, a.warmup))
+            p_plain = nbest().clone()
+            acg.network.fuse_generator_topk = True
+            greedy_r.append(timed(greedy, a.iters, a.warmup))
+    fused, plain, base = (float(np.median(v)) for v in (fused_r, plain_r, greedy_r))
+    out = dict(model="acg_beam", rnn_type=a.rnn_type, beam_size=W, B=a.B, QL=a.ql, CV=CV, emsize=a.emsize, nhid=a.nhid, V=a.V, VT=a.VT, max_len=a.max_len,
+               ms_per_batch=round(fused, 4), plain_ms_per_batch=round(plain, 4), greedy_ms_per_batch=round(base, 4),
+               ms_rounds=[round(v, 4) for v in fused_r], plain_ms_rounds=[round(v, 4) for v in plain_r], greedy_ms_rounds=[round(v, 4) for v in greedy_r],
+               tokens_equal_fused_plain=float((p_fused == p_plain).float().mean()), copied_share=float((p_fused >= a.VT).float().mean()))
     print(json.dumps(out))
     if a.json:
         with open(a.json, "w") as f:
