@@ -11,6 +11,8 @@
 // no float atomics, every reduction in a fixed order.
 // ACG's search (include/neuroir_acg_beam.h) is the same loop with another tail: the PAD-substituting forms of the two top-k
 // kernels, acg_beam_row_kernel (the W best of a row's collapsed extended distribution) and acg_beam_select_kernel.
+// HredQS's search (include/neuroir_hredqs_beam.h) is the plain decoder's loop of section 23 with hq_beam_begin_kernel in
+// front (pairing, repeat, split) and, in its fast form, hq_beam_gen_topk_kernel: the top-W on the split state the folded step leaves.
 #include <mutex>
 #include "s2s_gen.hpp"
 
@@ -282,6 +284,207 @@ __global__ __launch_bounds__(64) void beam_topk_finish_kernel(const float* __res
                                                               float* __restrict__ top_val, int* __restrict__ top_idx, float* __restrict__ lse) {
     const int64_t row = blockIdx.x;
     beam_merge_row(pval, pidx, pm, ps, nparts, rows, row, W, W, threadIdx.x, top_val + row * W, top_idx + row * W, lse + row);
+}
+
+// ---- generator + bias + (lse, top-W) on the SPLIT state: HredQS (include/neuroir_hredqs_beam.h) -------------------------------
+// beam_gen_topk_kernel fed as hq_gen_argmax_kernel (csrc/hredqs.hip) is: the beam rows arrive already split, as the folded LSTM step writes them
+// (h16 [row][K/8][2 terms][8]), so staging is one 16-byte copy per (row, k-group, term) into the two LDS planes [2][16 NBT][K + 8] -- no fp32
+// load, no conversion -- and the grid is that kernel's nrb row blocks x nvr vocabulary ranges with its blockIdx mapping: the row blocks of a
+// range run together on one XCD and share its L2 (nvr a multiple of 8), else they are adjacent in dispatch order.  A beam has W times the rows
+// of the greedy decode, so a range is read by W times the row blocks.  The walk, the chunked fragment prefetch and the three-MFMA product are
+// those of both kernels, restated for the reason given at beam_gen_topk_kernel; the logit is the greedy kernel's expression (W = 1 picks its
+// token) and the epilogue is beam_gen_topk_kernel's, so the partials -- pval / pidx [4 nvr][R][W], pm / ps [4 nvr][R] -- are read by
+// beam_select_kernel and beam_topk_finish_kernel unchanged.  The mapping is a speed choice: any placement gives the same partials up to the
+// order of the parts, which the merge's tie rule does not depend on.
+template <int NBT, int WM>
+__global__ __launch_bounds__(256, 1) void hq_beam_gen_topk_kernel(const _Float16* __restrict__ h16, const _Float16* __restrict__ wfrag,
+                                                                  const float* __restrict__ bias, int64_t VT, int64_t ntiles, int64_t R, int K, int nvr,
+                                                                  int nrb, int W, float* __restrict__ pval, int* __restrict__ pidx,
+                                                                  float* __restrict__ pm, float* __restrict__ ps) {
+    extern __shared__ __attribute__((aligned(16))) _Float16 hqb_sm[];          // [2 terms][ROWS][LD]
+    constexpr int ROWS = 16 * NBT;
+    const int LD = K + 8, KS = K / 32, Q = K / 4;                              // Q: 16-byte chunks of a row (k-group, term)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c16 = lane & 15, g4 = lane >> 4;
+    int vr, rb;
+    if (nvr % 8 == 0) {
+        const int j = (int)(blockIdx.x >> 3);
+        rb = j % nrb;
+        vr = (j / nrb) * 8 + (int)(blockIdx.x & 7);
+    } else {
+        rb = (int)(blockIdx.x % nrb);
+        vr = (int)(blockIdx.x / nrb);
+    }
+    const int64_t b0 = (int64_t)rb * ROWS;
+    const int64_t per_wg = (ntiles + nvr - 1) / nvr;
+    const int64_t t_lo = (int64_t)vr * per_wg, t_hi = min(ntiles, t_lo + per_wg);
+    {
+        // stage this workgroup's beam rows (zero rows past R): the loads of SB trips are issued before the first is written (unconditional, from
+        // a clamped row)
+        constexpr int SB = 8;
+        const int total = ROWS * Q;                                            // a multiple of 256
+        for (int e0 = tid; e0 < total; e0 += 256 * SB) {
+            uint4 sv[SB];
+#pragma unroll
+            for (int q = 0; q < SB; ++q) {
+                const int e = min(e0 + 256 * q, total - 1);
+                const int r = e / Q, c = e - r * Q;
+                const int64_t b = b0 + r;
+                sv[q] = *reinterpret_cast<const uint4*>(h16 + ((b < R ? b : R - 1) * Q + c) * 8);
+            }
+#pragma unroll
+            for (int q = 0; q < SB; ++q) {
+                const int e = e0 + 256 * q;
+                if (e < total) {
+                    const int r = e / Q, c = e - r * Q;
+                    uint4 v = sv[q];
+                    if (b0 + r >= R) v = make_uint4(0u, 0u, 0u, 0u);
+                    *reinterpret_cast<uint4*>(hqb_sm + (c & 1) * ROWS * LD + r * LD + (c >> 1) * 8) = v;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    float tv[NBT][WM], rm[NBT], rs[NBT];
+    int ti[NBT][WM];
+#pragma unroll
+    for (int bt = 0; bt < NBT; ++bt) {
+        rm[bt] = -INFINITY;
+        rs[bt] = 0.f;
+#pragma unroll
+        for (int j = 0; j < WM; ++j) { tv[bt][j] = -INFINITY; ti[bt][j] = BEAM_NONE; }
+    }
+    const int NCH = (KS + HQ_KC - 1) / HQ_KC;
+    const int64_t first = t_lo + wave;
+    const int64_t nt = first < t_hi ? (t_hi - first + 3) / 4 : 0;             // this wave's tiles: first, first + 4, ...
+    const int64_t items = nt * NCH;                                           // (tile, chunk) pairs, in order
+    f32x4 acc[NBT], acx[NBT];
+    auto load_w = [&](int64_t it, f16x8 (&wf)[HQ_KC][2]) {
+        const int64_t t = first + 4 * (it / NCH);
+        const int c = (int)(it % NCH);
+#pragma unroll
+        for (int u = 0; u < HQ_KC; ++u) {
+            const int ks = min(c * HQ_KC + u, KS - 1);                        // clamped: a duplicate k-step is not multiplied below
+            const _Float16* wp = wfrag + ((t * KS + ks) * 2 * 64 + lane) * 8;
+            wf[u][0] = *reinterpret_cast<const f16x8*>(wp);
+            wf[u][1] = *reinterpret_cast<const f16x8*>(wp + 512);
+        }
+    };
+    const _Float16* bp0 = hqb_sm + c16 * LD + 8 * g4;
+    auto compute = [&](int64_t it, const f16x8 (&wf)[HQ_KC][2]) {
+        const int64_t t = first + 4 * (it / NCH);
+        const int c = (int)(it % NCH);
+        if (c == 0) {
+#pragma unroll
+            for (int bt = 0; bt < NBT; ++bt) { acc[bt] = (f32x4){0.f, 0.f, 0.f, 0.f}; acx[bt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+        }
+#pragma unroll
+        for (int u = 0; u < HQ_KC; ++u) {
+            const int ks = c * HQ_KC + u;
+            if (ks < KS) {                                                    // wave-uniform
+                f16x8 b[NBT][2];
+#pragma unroll
+                for (int bt = 0; bt < NBT; ++bt) {
+                    b[bt][0] = *reinterpret_cast<const f16x8*>(bp0 + 32 * ks + bt * 16 * LD);
+                    b[bt][1] = *reinterpret_cast<const f16x8*>(bp0 + 32 * ks + bt * 16 * LD + ROWS * LD);
+                }
+#pragma unroll
+                for (int bt = 0; bt < NBT; ++bt) acx[bt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][1], b[bt][0], acx[bt], 0, 0, 0);
+#pragma unroll
+                for (int bt = 0; bt < NBT; ++bt) acc[bt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][0], b[bt][0], acc[bt], 0, 0, 0);
+#pragma unroll
+                for (int bt = 0; bt < NBT; ++bt) acx[bt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][0], b[bt][1], acx[bt], 0, 0, 0);
+            }
+        }
+        if (c == NCH - 1) {
+            const int64_t v0 = t * 16 + 4 * g4;
+            float bv[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) bv[r] = (bias && v0 + r < VT) ? bias[v0 + r] : 0.f;
+#pragma unroll
+            for (int bt = 0; bt < NBT; ++bt) {
+                float y[4];
+                float m = rm[bt];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    y[r] = fmaf(acx[bt][r], SPLIT2_INV, acc[bt][r]) + bv[r];  // the greedy kernel's expression: W = 1 picks its token
+                    if (v0 + r >= VT) y[r] = -INFINITY;                       // padded tile rows: never kept, add exp(-inf) = 0
+                    m = fmaxf(m, y[r]);
+                }
+                if (m > -INFINITY) {
+                    rs[bt] = rs[bt] * __expf(rm[bt] - m) + ((__expf(y[0] - m) + __expf(y[1] - m)) + (__expf(y[2] - m) + __expf(y[3] - m)));
+                    rm[bt] = m;
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r)                                   // ascending in r: '>' keeps the first index in front
+                    if (y[r] > tv[bt][WM - 1]) beam_insert<WM, false>(tv[bt], ti[bt], y[r], (int)(v0 + r));
+            }
+        }
+    };
+    {
+        f16x8 wfA[HQ_KC][2], wfB[HQ_KC][2];
+        if (items > 0) load_w(0, wfA);
+        for (int64_t it = 0; it < items; it += 2) {
+            if (it + 1 < items) load_w(it + 1, wfB);
+            compute(it, wfA);
+            if (it + 1 >= items) break;
+            if (it + 2 < items) load_w(it + 2, wfA);
+            compute(it + 1, wfB);
+        }
+    }
+    // lanes l, l + 16, l + 32, l + 48 hold the same beam row: the sums combine (only the g4 == 0 lane's value is written), the lists merge head
+    // by head by comparisons alone
+#pragma unroll
+    for (int bt = 0; bt < NBT; ++bt) {
+#pragma unroll
+        for (int sh = 16; sh <= 32; sh <<= 1) {
+            const float om = __shfl_xor(rm[bt], sh), os = __shfl_xor(rs[bt], sh);
+            const float m = fmaxf(om, rm[bt]);
+            rs[bt] = m > -INFINITY ? rs[bt] * __expf(rm[bt] - m) + os * __expf(om - m) : 0.f;
+            rm[bt] = m;
+        }
+        const int64_t b = b0 + bt * 16 + c16;
+        const int64_t slot = ((int64_t)vr * 4 + wave) * R + b;
+        const bool writer = g4 == 0 && b < R;
+        if (writer) { pm[slot] = rm[bt]; ps[slot] = rs[bt]; }
+#pragma unroll
+        for (int j = 0; j < WM; ++j) {
+            const float hv = tv[bt][0];
+            const int hi = ti[bt][0];
+            float wv = hv;
+            int wi = hi;
+#pragma unroll
+            for (int sh = 16; sh <= 32; sh <<= 1) {
+                const float ov = __shfl_xor(wv, sh);
+                const int oi = __shfl_xor(wi, sh);
+                if (beam_before(ov, oi, wv, wi)) { wv = ov; wi = oi; }
+            }
+            beam_pop<WM>(tv[bt], ti[bt], hv == wv && hi == wi);
+            if (writer && j < W) { pval[slot * W + j] = wv; pidx[slot * W + j] = wi; }
+        }
+    }
+}
+
+// ---- the HredQS beam's first state, one launch: pairing, repeat and split --------------------------------------------------------------------------
+// hs / cs [B, S, H] (session b, step s at row b S + s) -> h0 / c0 [R = Bd W, H]: beam row k Bd + i takes the state of step i / B of session
+// i % B (hq_pair_kernel's pairing, on SOURCE rows); h16 (optional): h0 as the fp16 term pairs of the folded step, [row][H/8][2][8], in
+// hq_pair_kernel's expressions.
+__global__ void hq_beam_begin_kernel(const float* __restrict__ hs, const float* __restrict__ cs, int64_t B, int64_t S, int H, int64_t n,
+                                     float* __restrict__ h0, float* __restrict__ c0, _Float16* __restrict__ h16) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;                                                       // n = R H
+    const int64_t r = e / H, i = r % (B * S);
+    const int k = (int)(e - r * H);
+    const int64_t src = ((i % B) * S + i / B) * H + k;
+    const float v = hs[src];
+    h0[e] = v;
+    c0[e] = cs[src];
+    if (h16) {
+        const _Float16 a = split2_hi1_rne(v);
+        _Float16* d = h16 + (e >> 3) * 16 + (e & 7);
+        d[0] = a;
+        d[8] = split2_lo1(v, a);
+    }
 }
 
 // ---- plain form: one workgroup per row of [rows, VT] logits -> (lse, top-W), the same tie rule ---------------------------------------------
@@ -636,6 +839,42 @@ static int launch_beam_gen_topk(const float* x, const void* frag, const float* b
     NIR_CHECK_LAUNCH("beam_gen_topk_kernel");
     return 0;
 }
+// partials per beam row of the split-state generator: one per wave of every vocabulary range of hq_nvr's grid
+static int hq_beam_nparts(int64_t rows, int K, int64_t VT) {
+    return rows > 0 ? 4 * hq_nvr((rows + 16 * hq_nbt(K) - 1) / (16 * hq_nbt(K)), (VT + 15) / 16) : 0;
+}
+template <int NBT, int WM>
+static void hq_beam_gen_launch(int grid, size_t lds, hipStream_t st, const _Float16* h16, const void* frag, const float* bias, int64_t VT, int64_t ntiles,
+                               int64_t rows, int K, int nvr, int nrb, int W, float* pval, int* pidx, float* pm, float* ps) {
+    hipLaunchKernelGGL((hq_beam_gen_topk_kernel<NBT, WM>), dim3((unsigned)grid), dim3(256), lds, st, h16, (const _Float16*)frag, bias, VT, ntiles, rows, K, nvr,
+                       nrb, W, pval, pidx, pm, ps);
+}
+// the fused generator on the split state: partials pval / pidx [nparts][rows][W], pm / ps [nparts][rows], nparts = hq_beam_nparts
+static int launch_hq_beam_gen_topk(const _Float16* h16, const void* frag, const float* bias, int64_t VT, int64_t rows, int K, int W, float* pval, int* pidx,
+                                   float* pm, float* ps, hipStream_t st) {
+    const int64_t ntiles = (VT + 15) / 16;
+    const int nbt = hq_nbt(K);
+    const int64_t nrb = (rows + 16 * nbt - 1) / (16 * nbt);
+    const int nvr = hq_nvr(nrb, ntiles);
+    const size_t lds = hq_lds(K);
+    static std::once_flag once;
+    std::call_once(once, [] {
+        (void)hipFuncSetAttribute((const void*)hq_beam_gen_topk_kernel<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hq_lds(512));
+        (void)hipFuncSetAttribute((const void*)hq_beam_gen_topk_kernel<4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hq_lds(512));
+        (void)hipFuncSetAttribute((const void*)hq_beam_gen_topk_kernel<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hq_lds(1024));
+        (void)hipFuncSetAttribute((const void*)hq_beam_gen_topk_kernel<2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hq_lds(1024));
+    });
+    {
+        ProfScope ps_(prof_shape_name("hq_beam_gen_topk_kernel", (long long)rows, (long long)VT, K), st);
+        const int grid = (int)(nvr * nrb);
+        if (nbt == 4 && W <= 4) hq_beam_gen_launch<4, 4>(grid, lds, st, h16, frag, bias, VT, ntiles, rows, K, nvr, (int)nrb, W, pval, pidx, pm, ps);
+        else if (nbt == 4) hq_beam_gen_launch<4, 8>(grid, lds, st, h16, frag, bias, VT, ntiles, rows, K, nvr, (int)nrb, W, pval, pidx, pm, ps);
+        else if (W <= 4) hq_beam_gen_launch<2, 4>(grid, lds, st, h16, frag, bias, VT, ntiles, rows, K, nvr, (int)nrb, W, pval, pidx, pm, ps);
+        else hq_beam_gen_launch<2, 8>(grid, lds, st, h16, frag, bias, VT, ntiles, rows, K, nvr, (int)nrb, W, pval, pidx, pm, ps);
+    }
+    NIR_CHECK_LAUNCH("hq_beam_gen_topk_kernel");
+    return 0;
+}
 // psum given: the PAD form, (max, sum) apart in lse / psum
 static int launch_beam_row_topk(const float* logits, int64_t VT, int64_t rows, int W, float* top_val, int* top_idx, float* lse, hipStream_t st,
                                 float* psum = nullptr) {
@@ -889,9 +1128,10 @@ struct SessBeamBufs {
     int64_t* tgt;
     int nparts;
 };
-static SessBeamBufs sess_beam_bufs(Workspace& a, int64_t R, int W, int max_len, int K, int64_t VT, bool fused, bool own_bp) {
+// (nparts >= 0: the partial count of another fused producer -- hq_beam_gen_topk_kernel's grid)
+static SessBeamBufs sess_beam_bufs(Workspace& a, int64_t R, int W, int max_len, int K, int64_t VT, bool fused, bool own_bp, int nparts = -1) {
     SessBeamBufs p;
-    p.nparts = fused ? beam_nparts(R, K, VT) : 1;
+    p.nparts = fused ? (nparts >= 0 ? nparts : beam_nparts(R, K, VT)) : 1;
     p.logits = a.take<float>(fused ? 0 : (size_t)R * VT);
     p.pval = a.take<float>((size_t)p.nparts * R * W);
     p.pidx = a.take<int>((size_t)p.nparts * R * W);
@@ -1050,13 +1290,14 @@ struct PlainBeamPlan {
     SessBeamBufs b;
     size_t bytes;
 };
-static PlainBeamPlan plain_beam_plan(void* ws, size_t cap, int64_t Bd, int H, int64_t VT, int W, int max_len, bool step16, bool fused, bool own_bp) {
+static PlainBeamPlan plain_beam_plan(void* ws, size_t cap, int64_t Bd, int H, int64_t VT, int W, int max_len, bool step16, bool fused, bool own_bp,
+                                     int nparts = -1) {
     Workspace a(ws, cap);
     PlainBeamPlan p;
     const int64_t R = Bd * W;
     for (int k = 0; k < 2; ++k) { p.h[k] = a.take<float>((size_t)R * H); p.c[k] = a.take<float>((size_t)R * H); }
     for (int k = 0; k < 2; ++k) p.h16[k] = a.take<float>(step16 ? (size_t)R * H : 0);
-    p.b = sess_beam_bufs(a, R, W, max_len, H, VT, fused, own_bp);
+    p.b = sess_beam_bufs(a, R, W, max_len, H, VT, fused, own_bp, nparts);
     p.bytes = align_up(a.off, 256);
     return p;
 }
@@ -1101,6 +1342,95 @@ extern "C" int nir_beam_plain_decode(const float* dec_h, const float* dec_c, int
         NIR_PROPAGATE(launch_lstm_step(s, 1, st));
         NIR_PROPAGATE(sess_beam_gen(p.b, fused, p.h[1], R, H, gen_w, gen_b, gen_frag, VT, W, st));
         NIR_PROPAGATE(sess_beam_tail(p.b, fused, step, max_len, Bd, W, H, VT, tgt2src, V, bp, p.h, p.c, p.h16, step16, st));
+    }
+    return sess_beam_end(p.b, bp, Bd, W, max_len, predictions, scores, lengths, st);
+}
+
+// ---- HredQS (include/neuroir_hredqs_beam.h): the plain decoder's beam over Bd = B S source rows in the reference's pairing,
+// the fast form's top-W on the split state the folded step leaves ---------------------------------------------------------------------------
+extern "C" size_t nir_beam_hredqs_gen_topk_workspace_bytes(int64_t rows, int K, int64_t VT, int W) {
+    using namespace nir;
+    if (rows <= 0 || !hq_fusable(K, VT) || !beam_dims_ok(W, VT)) return 0;
+    return (size_t)hq_beam_nparts(rows, K, VT) * rows * ((size_t)W * 8 + 8) + 4 * 256;
+}
+
+extern "C" int nir_beam_hredqs_gen_topk(const void* h16, int64_t rows, int K, const float* gen_b, const void* gen_frag, int64_t VT, int W, void* workspace,
+                                        size_t workspace_bytes, float* top_val, int32_t* top_idx, float* lse, nir_stream_t stream) {
+    using namespace nir;
+    hipStream_t st = (hipStream_t)stream;
+    NIR_REQUIRE(h16 && gen_frag && workspace && top_val && top_idx && lse, "beam_hredqs_gen_topk: null pointer");
+    NIR_REQUIRE(rows >= 0 && rows < 0x7FFFFFFFLL, "beam_hredqs_gen_topk: bad dims");
+    NIR_REQUIRE(hq_fusable(K, VT), "beam_hredqs_gen_topk: K must be a multiple of 32 in [32, 1024] and 0 < VT < 2^31 - 16");
+    NIR_REQUIRE(beam_dims_ok(W, VT), "beam_hredqs_gen_topk: beam width outside [1, %d] or above VT", NIR_BEAM_MAX_W);
+    if (rows == 0) return 0;
+    if (workspace_bytes < nir_beam_hredqs_gen_topk_workspace_bytes(rows, K, VT, W)) {
+        set_error("beam_hredqs_gen_topk: workspace too small");
+        return NIR_ERR_WORKSPACE;
+    }
+    Workspace a(workspace, workspace_bytes);
+    const int nparts = hq_beam_nparts(rows, K, VT);
+    float* pval = a.take<float>((size_t)nparts * rows * W);
+    int* pidx = a.take<int>((size_t)nparts * rows * W);
+    float* pm = a.take<float>((size_t)nparts * rows);
+    float* ps = a.take<float>((size_t)nparts * rows);
+    NIR_PROPAGATE(launch_hq_beam_gen_topk((const _Float16*)h16, gen_frag, gen_b, VT, rows, K, W, pval, pidx, pm, ps, st));
+    hipLaunchKernelGGL(beam_topk_finish_kernel, dim3((unsigned)rows), dim3(64), 0, st, pval, pidx, pm, ps, nparts, rows, W, top_val, top_idx, lse);
+    NIR_CHECK_LAUNCH("beam_topk_finish_kernel");
+    return 0;
+}
+
+extern "C" size_t nir_beam_hredqs_decode_workspace_bytes(int64_t B, int64_t S, int W, int max_len, const nir_hredqs_decoder_weights* w) {
+    using namespace nir;
+    if (!hq_weights_ok(w) || B < 0 || S < 0 || max_len <= 0 || !beam_dims_ok(W, w->VT)) return 0;
+    const bool fast = hq_fast(w);
+    return plain_beam_plan(nullptr, 0, B * S, w->H, w->VT, W, max_len, fast, fast, true, hq_beam_nparts(B * S * W, w->H, w->VT)).bytes;
+}
+
+extern "C" int nir_beam_hredqs_decode(const float* h_steps, const float* c_steps, int64_t B, int64_t S, const float* table, int64_t V, int E,
+                                      const int64_t* tgt2src, int64_t bos, int max_len, const nir_hredqs_decoder_weights* w, int W, void* workspace,
+                                      size_t workspace_bytes, int64_t* predictions, float* scores, int64_t* lengths, int32_t* backptr,
+                                      nir_stream_t stream) {
+    using namespace nir;
+    hipStream_t st = (hipStream_t)stream;
+    NIR_REQUIRE(h_steps && c_steps && table && w && predictions && scores && lengths, "beam_hredqs_decode: null pointer");
+    NIR_REQUIRE(hq_weights_ok(w), "beam_hredqs_decode: decoder weights incomplete, H not a multiple of 4 or VT outside (0, 2^31 - 16)");
+    NIR_REQUIRE(B >= 0 && S >= 0 && max_len > 0 && V > 0 && E > 0 && E % 4 == 0, "beam_hredqs_decode: bad dims");
+    NIR_REQUIRE(bos >= 0 && bos < V, "beam_hredqs_decode: BOS id outside the vocabulary");
+    NIR_REQUIRE((w->rnn_gate_fold == nullptr) == (w->rnn_whh_frag == nullptr), "beam_hredqs_decode: rnn_gate_fold and rnn_whh_frag come together");
+    NIR_REQUIRE(beam_dims_ok(W, w->VT), "beam_hredqs_decode: beam width outside [1, %d] or above the target vocabulary", NIR_BEAM_MAX_W);
+    NIR_REQUIRE(B < 0x7FFFFFFFLL && S < 0x7FFFFFFFLL && B * S * NIR_BEAM_MAX_W < 0x7FFFFFFFLL, "beam_hredqs_decode: too many decode rows");
+    const int H = w->H;
+    const int64_t Bd = B * S, R = Bd * W, VT = w->VT;
+    const bool fast = hq_fast(w);
+    PlainBeamPlan p = plain_beam_plan(workspace, workspace_bytes, Bd, H, VT, W, max_len, fast, fast, backptr == nullptr, hq_beam_nparts(R, H, VT));
+    if (!workspace || p.bytes > workspace_bytes) {
+        set_error("beam_hredqs_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
+        return NIR_ERR_WORKSPACE;
+    }
+    if (Bd == 0) return 0;
+    // pairing, repeat and split in one launch: every beam of source row i starts from step i / B of session i % B, in state slot 0
+    hipLaunchKernelGGL(hq_beam_begin_kernel, g1(R * H), dim3(256), 0, st, h_steps, c_steps, B, S, H, R * H, p.h[0], p.c[0],
+                       fast ? reinterpret_cast<_Float16*>(p.h16[0]) : nullptr);
+    NIR_CHECK_LAUNCH("hq_beam_begin_kernel");
+    NIR_PROPAGATE(launch_fill_i64(p.b.tgt, bos, R, st));
+    hipLaunchKernelGGL(beam_init_kernel, g1(R), dim3(256), 0, st, p.b.cum, p.b.fin, R, W);
+    NIR_CHECK_LAUNCH("beam_init_kernel");
+    LstmStepArgs s = LstmStepArgs::token_fed(table, p.b.tgt, E, w->rnn_wih, w->rnn_whh, w->rnn_bih, w->rnn_bhh, R, H);
+    if (fast) s.fold_token_fed(w->rnn_gate_fold, w->rnn_whh_frag);
+    int* bp = backptr ? backptr : p.b.bp;
+    for (int step = 0; step < max_len; ++step) {
+        // a step reads state slot 0 (the reordered one) and writes slot 1
+        s.hprev[0] = p.h[0]; s.cprev[0] = p.c[0]; s.hnext[0] = p.h[1]; s.cnext[0] = p.c[1];
+        if (fast) {
+            s.h16prev[0] = reinterpret_cast<const _Float16*>(p.h16[0]);
+            s.h16next[0] = reinterpret_cast<_Float16*>(p.h16[1]);
+        }
+        NIR_PROPAGATE(launch_lstm_step(s, 1, st));
+        if (fast)
+            NIR_PROPAGATE(launch_hq_beam_gen_topk(s.h16next[0], w->gen_frag, w->gen_b, VT, R, H, W, p.b.pval, p.b.pidx, p.b.pm, p.b.ps, st));
+        else
+            NIR_PROPAGATE(sess_beam_gen(p.b, false, p.h[1], R, H, w->gen_w, w->gen_b, nullptr, VT, W, st));
+        NIR_PROPAGATE(sess_beam_tail(p.b, fast, step, max_len, Bd, W, H, VT, tgt2src, V, bp, p.h, p.c, p.h16, fast, st));
     }
     return sess_beam_end(p.b, bp, Bd, W, max_len, predictions, scores, lengths, st);
 }

@@ -1,6 +1,7 @@
-// Shared by the greedy decoders (csrc/cars_decode.hip, csrc/seq2seq.hip): the GEMM launchers of gemm.hip and the small launches every
-// decoder makes between its steps.  The kernels live in cars_decode.hip; these are their host-side launchers.
+// Shared by the decoders (csrc/cars_decode.hip, csrc/seq2seq.hip, csrc/hredqs.hip, csrc/beam.hip): the GEMM launchers of gemm.hip and the small
+// launches every decoder makes between its steps.  The kernels live in cars_decode.hip; these are their host-side launchers.
 #pragma once
+#include <algorithm>
 #include "split2.hpp"
 
 namespace nir {
@@ -28,6 +29,30 @@ int launch_argmax_finish(const float* pval, const int* pidx, int nparts, int64_t
                          int64_t Vsrc, hipStream_t st);
 // multiProcessorCount of the current device (256 if unknown)
 int device_cu_count();
+
+// ---- the launch geometry of the HredQS generator kernels on the split state (csrc/hredqs.hip: hq_gen_argmax_kernel; csrc/beam.hip:
+// hq_beam_gen_topk_kernel) and the form test of the HredQS decode entries -----------------------------------------------------------------------
+constexpr int HQ_KC = 8;
+
+static inline int hq_nbt(int K) { return K <= 512 ? 4 : 2; }
+static inline size_t hq_lds(int K) { return (size_t)2 * 16 * hq_nbt(K) * (K + 8) * sizeof(_Float16); }
+static inline bool hq_fusable(int K, int64_t VT) { return K >= 32 && K <= 1024 && K % 32 == 0 && VT > 0 && VT < 0x7FFFFFF0LL; }
+
+// vocabulary ranges: one workgroup per CU (the staged rows fill its LDS) in a single round, at least ~2 tiles per wave; a multiple of 8 from
+// 8 on, so that the row blocks of a range can share an XCD (see hq_gen_argmax_kernel)
+static inline int hq_nvr(int64_t nrb, int64_t ntiles) {
+    int64_t n = std::max<int64_t>(1, std::min<int64_t>(device_cu_count() / nrb, (ntiles + 7) / 8));
+    if (n >= 8) n -= n % 8;
+    return (int)n;
+}
+
+static inline bool hq_weights_ok(const nir_hredqs_decoder_weights* w) {
+    return w && w->H > 0 && w->H % 4 == 0 && w->VT > 0 && w->VT < 0x7FFFFFF0LL && w->rnn_wih && w->rnn_whh && w->rnn_bih && w->rnn_bhh && w->gen_w &&
+           w->gen_b;
+}
+static inline bool hq_fast(const nir_hredqs_decoder_weights* w) {
+    return w->rnn_gate_fold && w->rnn_whh_frag && w->gen_frag && hq_fusable(w->H, w->VT) && !tun(g_tun.exact_f32);
+}
 
 // One GRU decoder step (csrc/gru_step.hip).  Fast form (gru_step_fast): whh_frag, h16prev and h16next given, H % 32 == 0, tunable exact_f32 off --
 // one launch when gate_fold is given too, else the gathered input GEMM into `scratch` in front of it.  Plain form otherwise: exact fp32, three

@@ -52,9 +52,7 @@ __global__ void hq_pair_kernel(const float* __restrict__ hs, const float* __rest
 // ascending order there, so with j = blockIdx / 8 the row block is j % nrb and the range (j / nrb) * 8 + blockIdx % 8 (nvr a multiple of 8).
 // A range's fragments then come from HBM once and from that XCD's L2 for the other row blocks.  With nvr no multiple of 8 the row block is
 // blockIdx % nrb: still adjacent in dispatch order, sharing through the Infinity Cache only.  The mapping is a speed choice: any placement
-// gives the same keys.
-constexpr int HQ_KC = 8;
-
+// gives the same keys.  (HQ_KC and the grid helpers hq_nbt / hq_lds / hq_nvr live in decode_common.hpp: the beam's top-W kernel shares them.)
 template <int NBT>
 __global__ __launch_bounds__(256, 1) void hq_gen_argmax_kernel(const _Float16* __restrict__ h16, const _Float16* __restrict__ wfrag,
                                                                const float* __restrict__ bias, int64_t VT, int64_t ntiles, int64_t R, int K, int nvr,
@@ -221,18 +219,6 @@ __global__ void hq_keys_decode_kernel(const unsigned long long* __restrict__ key
     }
 }
 
-static inline int hq_nbt(int K) { return K <= 512 ? 4 : 2; }
-static inline size_t hq_lds(int K) { return (size_t)2 * 16 * hq_nbt(K) * (K + 8) * sizeof(_Float16); }
-static inline bool hq_fusable(int K, int64_t VT) { return K >= 32 && K <= 1024 && K % 32 == 0 && VT > 0 && VT < 0x7FFFFFF0LL; }
-
-// vocabulary ranges: one workgroup per CU (the staged rows fill its LDS) in a single round, at least ~2 tiles per wave; a multiple of 8 from
-// 8 on, so that the row blocks of a range can share an XCD (see the kernel)
-static int hq_nvr(int64_t nrb, int64_t ntiles) {
-    int64_t n = std::max<int64_t>(1, std::min<int64_t>(device_cu_count() / nrb, (ntiles + 7) / 8));
-    if (n >= 8) n -= n % 8;
-    return (int)n;
-}
-
 static int launch_hq_gen_argmax(const _Float16* h16, const void* frag, const float* bias, int64_t VT, int64_t R, int K, unsigned long long* keys,
                                 hipStream_t st) {
     const int64_t ntiles = (VT + 15) / 16;
@@ -281,14 +267,6 @@ static HqPlan hq_plan(void* ws, size_t cap, int64_t R, int H, int64_t VT, int ma
     p.bytes = align_up(a.off, 256);
     return p;
 }
-static bool hq_weights_ok(const nir_hredqs_decoder_weights* w) {
-    return w && w->H > 0 && w->H % 4 == 0 && w->VT > 0 && w->VT < 0x7FFFFFF0LL && w->rnn_wih && w->rnn_whh && w->rnn_bih && w->rnn_bhh && w->gen_w &&
-           w->gen_b;
-}
-static bool hq_fast(const nir_hredqs_decoder_weights* w) {
-    return w->rnn_gate_fold && w->rnn_whh_frag && w->gen_frag && hq_fusable(w->H, w->VT) && !tun(g_tun.exact_f32);
-}
-
 }  // namespace nir
 
 extern "C" size_t nir_hredqs_gen_argmax_workspace_bytes(int64_t rows) {

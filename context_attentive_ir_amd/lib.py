@@ -360,6 +360,16 @@ ACG_BEAM_SIGNATURES = {
                                      c_ip, c_fp, C.c_void_p, c_st]),
 }
 
+# Beam search for HredQS, declared in include/neuroir_hredqs_beam.h (csrc/beam.hip): top-W on the split state of the folded step.  A table of
+# its own, like the ones above.
+_HW = C.POINTER(HredqsDecoderWeights)
+HREDQS_BEAM_SIGNATURES = {
+    "nir_beam_hredqs_gen_topk_workspace_bytes": (_z, [_l, _i, _l, _i]),
+    "nir_beam_hredqs_gen_topk": (_i, [C.c_void_p, _l, _i, c_fp, C.c_void_p, _l, _i, C.c_void_p, _z, c_fp, C.c_void_p, c_fp, c_st]),
+    "nir_beam_hredqs_decode_workspace_bytes": (_z, [_l, _l, _i, _i, _HW]),
+    "nir_beam_hredqs_decode": (_i, [c_fp, c_fp, _l, _l, c_fp, _l, _i, c_ip, _l, _i, _HW, _i, C.c_void_p, _z, c_ip, c_fp, c_ip, C.c_void_p, c_st]),
+}
+
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_SPLIT2 = 0, 1, 2
 DTYPES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "bf16": DTYPE_BF16, "f32_split2": DTYPE_F32_SPLIT2}
 
@@ -376,7 +386,7 @@ def load():
                 "(hipcc, gfx950). The HIP path has no CPU fallback." % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(GRU_DECODE_SIGNATURES.items()) + list(BEAM_SIGNATURES.items()) + list(SESSION_BEAM_SIGNATURES.items())
-                                  + list(ACG_BEAM_SIGNATURES.items())):
+                                  + list(ACG_BEAM_SIGNATURES.items()) + list(HREDQS_BEAM_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

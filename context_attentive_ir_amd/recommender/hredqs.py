@@ -5,6 +5,7 @@ encode():  RNNEncoder over every query -> max over ALL QL positions of the zero-
            per query, the (h, c) of EVERY step -> [1, S B, nhid_session] in step-major order.
 decode():  ONE C-ABI call for the whole greedy decode of all B S session prefixes (nir_hredqs_decode_greedy, csrc/hredqs.hip): the folded LSTM
            step and the generator + bias + arg-max kernel, two launches per step; the winner travels as an arg-max key.
+decode_beam(): ONE C-ABI call for the beam search over the same prefixes (nir_beam_hredqs_decode, csrc/beam.hip): n-best suggestions with scores.
 forward(): the teacher-forced loss on the differentiable HIP operators of autograd.py.
 
 Kept quirks of the reference:
@@ -162,6 +163,41 @@ class HredQS(nn.Module, lib.IdCheck):
         lib.check(L.nir_hredqs_decode_greedy(lib.ptr(hs), lib.ptr(cs), B, S, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(tgt2src), BOS, max_len,
                                              w.ref(), lib.ptr(ws), ws.numel(), lib.ptr(preds), lib.stream()), "nir_hredqs_decode_greedy")
         return {"predictions": preds}
+
+    @torch.no_grad()
+    def decode_beam(self, source_rep, source_len, max_len, beam_size, src_dict=None, tgt_dict=None, tgt2src=None, return_backptr=False):
+        """Beam search next to decode() (include/neuroir_hredqs_beam.h; the reference has no counterpart) ->
+        {'predictions': LongTensor [B, S, W, max_len] (best beam first, EOS repeated behind the first EOS), 'scores': [B, S, W], 'lengths':
+        LongTensor [B, S, W]} (+ 'backptr': IntTensor [max_len, B S, W] on request); there are no attentions.  One C-ABI call
+        (nir_beam_hredqs_decode) over the same session states, pack cache and target -> source table as decode(); the entry pairs and repeats
+        the states itself.  `fast_decode = False` forces its plain form."""
+        if self.training:
+            raise NotImplementedError("HIP HredQS.decode_beam runs in eval mode")
+        self._check_config()
+        max_len, W = int(max_len), int(beam_size)
+        suggest.check_beam_size(W, int(self.generator.weight.shape[0]))
+        if max_len < 1:
+            raise ValueError("decode_beam: max_len must be positive")
+        B, S, QL = source_rep.shape
+        table = self.embedder.word_embeddings.table
+        lib.require_device(source_rep, source_len, table)
+        L = lib.load()
+        dev = table.device
+        out = suggest.beam_outputs(B * S, W, max_len, dev, return_backptr)
+        if B * S > 0:
+            src, _ = self._clean_ids(source_rep.reshape(B * S, QL), None, table.shape[0])
+            hs, cs = self._session_steps(src, lib.ids64(source_len.reshape(-1)), B, S)
+            w = self._decoder_weights()
+            if tgt2src is None:
+                tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, int(w.struct.VT), dev)
+            t = table.detach().float().contiguous()
+            ws = lib.workspace(L.nir_beam_hredqs_decode_workspace_bytes(B, S, W, max_len, w.ref()), dev)
+            lib.check(L.nir_beam_hredqs_decode(lib.ptr(hs), lib.ptr(cs), B, S, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(tgt2src), BOS, max_len,
+                                               w.ref(), W, lib.ptr(ws), ws.numel(), lib.ptr(out["predictions"]), lib.ptr(out["scores"]),
+                                               lib.ptr(out["lengths"]), lib.ptr(out.get("backptr")), lib.stream()), "nir_beam_hredqs_decode")
+        out["predictions"] = out["predictions"].view(B, S, W, max_len)
+        out["scores"], out["lengths"] = out["scores"].view(B, S, W), out["lengths"].view(B, S, W)
+        return out
 
     # ---- train: teacher-forced loss ---------------------------------------------------------------------------------------------------
     def forward(self, source_rep, source_len, target_rep, target_len, target_seq, source_map=None, alignment=None):

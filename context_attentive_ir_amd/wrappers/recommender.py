@@ -4,6 +4,7 @@
 their session axis; CopyRecommender is the same wrapper for ACG, whose batches carry the copy generator's maps."""
 import torch
 
+from .. import lib
 from ..constants import BOS, EOS, PAD, UNK_WORD
 from ..recommender import ACG, ACGGRU, HredQS, Seq2seq, Seq2seqGRU
 from .common import WrapperBase
@@ -143,7 +144,7 @@ class Recommender(WrapperBase):
 
     def predict_nbest(self, ex, beam_size):
         """n-best suggestions, the one name every wrapper has: predict_beam here; CopyRecommender's is ACG's search over the copy generator's
-        distribution; SessionRecommender (HredQS) has none."""
+        distribution; SessionRecommender (HredQS) keeps the session axis: predict_session_nbest."""
         return self.predict_beam(ex, beam_size)
 
     def _text(self, ex, pred_ids, attns):
@@ -210,10 +211,42 @@ class SessionRecommender(Recommender):
         return t
 
     def predict_beam(self, ex, beam_size):
-        raise NotImplementedError("HIP beam search covers Seq2seq and Seq2seqGRU; HredQS keeps its greedy decode (DESIGN.md section 21)")
+        raise NotImplementedError("SessionRecommender.predict_beam: HredQS's beam search is predict_session_nbest(ex, beam_size) -- its outputs keep "
+                                  "the session axis and there are no attentions (DESIGN.md section 25)")
 
     def predict_nbest(self, ex, beam_size):
-        raise NotImplementedError("HIP beam search covers Seq2seq, Seq2seqGRU, ACG and ACGGRU; HredQS keeps its greedy decode (DESIGN.md sections 21, 24)")
+        raise NotImplementedError("SessionRecommender.predict_nbest: the n-best suggestions of HredQS are predict_session_nbest(ex, beam_size) -- one "
+                                  "list per session prefix, [B, S, W, max_query_len] (DESIGN.md section 25)")
+
+    def _predict_session_nbest_body(self, ex, beam_size):
+        self.network.eval()
+        dec = self.network.decode_beam(source_rep=self._dev(ex["source_words"]), source_len=self._dev(ex["source_lens"]), max_len=self.args.max_query_len,
+                                       beam_size=beam_size, src_dict=self.src_dict, tgt_dict=self.tgt_dict)
+        self._maybe_check_ids()
+        return {"prediction_ids": dec["predictions"], "scores": dec["scores"], "lengths": dec["lengths"]}
+
+    @torch.no_grad()
+    def predict_session_nbest(self, ex, beam_size):
+        """n-best suggestions per session prefix by beam search (HredQS.decode_beam; the reference has no counterpart): {'prediction_ids':
+        LongTensor [B, S, W, max_query_len], 'scores': [B, S, W], 'lengths': LongTensor [B, S, W]}, best beam first; for a batch in the
+        reference's collate layout also predict()'s step-major `ex_ids`, `targets`, `src_sequences` and `predictions`: per prefix the list of
+        its W strings.  There are no attentions, so no <unk> is replaced.  `beam_size` is an argument of the call, not a field of args.  Graph
+        replay as in predict(): the width is part of the graph's key."""
+        W = int(beam_size)
+        if not 1 <= W <= lib.BEAM_MAX_W:
+            raise ValueError("predict_session_nbest: beam_size %d outside [1, %d]" % (W, lib.BEAM_MAX_W))
+        self._poll_ids()
+        body = lambda e: self._predict_session_nbest_body(e, W)               # noqa: E731
+        out = self._graphed(ex, self._FIELDS, "decode_session_nbest%d" % W, body)
+        if out is None:
+            out = body(ex)
+        elif self.id_check == "blocking":
+            self._maybe_check_ids()
+        if all(k in ex for k in ("ids", "source_tokens", "target_tokens")):
+            per_beam = [self._text(ex, out["prediction_ids"][:, :, k]) for k in range(W)]
+            out.update(per_beam[0])
+            out["predictions"] = [[per_beam[k]["predictions"][i] for k in range(W)] for i in range(len(per_beam[0]["predictions"]))]
+        return out
 
     def _predict_body(self, ex):
         self.network.eval()

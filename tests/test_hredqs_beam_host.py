@@ -1,0 +1,227 @@
+"""Host-side (no GPU) checks of the HredQS beam search: the restatement at W = 1 against the recorded greedy decodes of the unmodified goldens,
+the conditions of the beam fixtures (tests/golden/hredqs_beam_seeds.json), the teeth of the acceptance criterion (beam_ref's four
+model-independent faults and the pairing only HredQS can get wrong), the registration of the new symbols, their argument checks over fake
+pointers, and the Python surface."""
+import os
+import re
+
+import pytest
+import torch
+
+import beam_ref as BR
+import gemm_ref
+import hredqs_beam_ref as R
+
+CASE_W = R.case_w()
+
+
+@pytest.fixture(scope="module")
+def decodes():
+    """per (case, W): (case, perturbed state dict, fp64 decode, free fp32 decode, fp32 decode forced along the fp64 choices, max_len) -- once"""
+    out = {}
+    for tag, W in CASE_W:
+        cs, sd, ml = R.load_case(tag), R.perturbed(tag, W), R.fixture_max_len(tag, W)
+        ref = R.decode(cs, sd, W, max_len=ml)
+        free = R.decode(cs, sd, W, torch.float32, max_len=ml)
+        chain = R.decode(cs, sd, W, torch.float32, force=(ref["backptr"], ref["tokens"]), max_len=ml)
+        out[tag, W] = (cs, sd, ref, free, chain, ml)
+    return out
+
+
+# ---- W = 1 ties the restatement to the reference ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tag", R.CASES)
+def test_width_one_reproduces_the_recorded_greedy_decode(tag):
+    cs = R.load_case(tag)
+    out = R.decode(cs, cs["sd"], 1)
+    pred, want = out["predictions"][:, 0], cs["greedy"].reshape(cs["B"] * cs["S"], -1)
+    assert pred.shape == want.shape
+    for i in range(want.shape[0]):                                              # up to each row's first EOS
+        n = int(out["lengths"][i, 0])
+        assert torch.equal(pred[i, :n], want[i, :n]), (tag, i)
+    assert int(out["lengths"].min()) >= 1
+
+
+# ---- the beam fixtures ------------------------------------------------------------------------------------------------------------------------
+def test_the_fixture_widths_are_the_ones_the_kernel_forms_need():
+    want = {(t, W) for t in R.CASES for W in R.widths(t)}
+    missing = want - set(CASE_W)
+    assert missing <= {("h64", 8)}, missing                                     # the one pair the seed search may come back from empty-handed
+    assert ("h1024", 8) in CASE_W                                               # 48 beam rows: two 32-row blocks of hq_beam_gen_topk_kernel<2, 8>
+    cs = R.load_case("h1024")
+    assert cs["B"] * cs["S"] * 8 == 48 and cs["cfg"]["nhid_session"] == 1024
+    assert R.seeds()["h1024"]["8"][2] == cs["max_len"]
+
+
+@pytest.mark.parametrize("tag,W", CASE_W)
+def test_fixture_conditions_hold_at_every_step(decodes, tag, W):
+    cs, sd, ref, free, chain, ml = decodes[tag, W]
+    cond = BR.conditions(ref, free, W)
+    print("hredqs beam fixture %s W=%d max_len=%d: %s" % (tag, W, ml, cond))
+    assert ref["gaps"].shape == (ml, cs["B"] * cs["S"], W)                      # no step and no source row is left out
+    assert cond["gap"] and cond["f32"], cond
+    if W > 1:
+        assert cond["eos"] and cond["mixed"] and cond["moved"], cond
+        assert abs(cond["min_gap"] - R.seeds()[tag][str(W)][1]) <= 1e-9         # the recorded smallest gap
+    assert R.conditions_ok(cond, W), cond
+    assert torch.equal(chain["predictions"], ref["predictions"])
+    ok, fig = R.accept_decode(dict(chain), ref, chain, 0)
+    assert ok, fig
+
+
+@pytest.mark.parametrize("tag", R.CASES)
+@pytest.mark.parametrize("fault", ["no_reorder", "raw_logit", "eos_grows", "all_live_step0", "natural_pairing"])
+def test_the_criterion_rejects_every_fault_at_the_margins_cap(decodes, tag, fault):
+    cs, sd, ref, free, chain, ml = decodes[tag, 4]
+    bad = R.decode(cs, sd, 4, fault=fault, max_len=ml)
+    ok, fig = R.accept_decode(bad, ref, chain, R.n_split(cs["QL"], cs["S"], True, ml), margin=gemm_ref.MARGIN_CAP)
+    assert not ok, (tag, fault, fig)
+
+
+def test_natural_pairing_moves_source_rows_not_beam_rows():
+    cs = R.load_case("h64")
+    a, _ = R.model_step(cs, cs["sd"], torch.float64)
+    b, _ = R.model_step(cs, cs["sd"], torch.float64, fault="natural_pairing")
+    B, S = cs["B"], cs["S"]
+    moved = [i for i in range(B * S) if not torch.equal(a[0][i], b[0][i])]
+    assert len(moved) == 10                                                     # B = 3, S = 4: ten of twelve rows
+    for i in range(B * S):                                                      # source row i: step i // B of session i % B
+        assert torch.equal(a[0][i], b[0][(i % B) * S + i // B])
+
+
+# ---- symbols and arguments ----------------------------------------------------------------------------------------------------------------------
+NAMES = {"nir_beam_hredqs_gen_topk_workspace_bytes", "nir_beam_hredqs_gen_topk", "nir_beam_hredqs_decode_workspace_bytes", "nir_beam_hredqs_decode"}
+
+
+def _weights(H=8, VT=10, packs=False):
+    from context_attentive_ir_amd import lib
+    w = lib.HredqsDecoderWeights()
+    for f in ("rnn_wih", "rnn_whh", "rnn_bih", "rnn_bhh", "gen_w", "gen_b") + (("rnn_gate_fold", "rnn_whh_frag", "gen_frag") if packs else ()):
+        setattr(w, f, 16)
+    w.H, w.VT = H, VT
+    return w
+
+
+def test_new_symbols_exist_with_their_prototypes():
+    from conftest import ROOT
+    from context_attentive_ir_amd import lib
+    main = open(os.path.join(ROOT, "include", "neuroir_hip.h")).read()
+    assert '#include "neuroir_hredqs_beam.h"' in main
+    assert not re.findall(r"\bnir_beam_hredqs\w*\s*\(", re.sub(r"/\*.*?\*/", "", main, flags=re.S))       # no prototypes of its own
+    hdr = open(os.path.join(ROOT, "include", "neuroir_hredqs_beam.h")).read()
+    declared = set(re.findall(r"\b(nir_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)))
+    assert NAMES == declared == set(lib.HREDQS_BEAM_SIGNATURES)
+    others = set(lib.SIGNATURES) | set(lib.GRU_DECODE_SIGNATURES) | set(lib.BEAM_SIGNATURES) | set(lib.SESSION_BEAM_SIGNATURES) | set(lib.ACG_BEAM_SIGNATURES)
+    assert not NAMES & others
+    L = lib.load()
+    for n in NAMES:
+        assert hasattr(L, n), n
+        m = re.search(r"\b%s\s*\(([^;]*?)\)\s*;" % n, hdr, re.S)
+        nargs = len([a for a in re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(",") if a.strip()])
+        assert nargs == len(lib.HREDQS_BEAM_SIGNATURES[n][1]), n
+        assert getattr(L, n).argtypes == lib.HREDQS_BEAM_SIGNATURES[n][1]      # registered by lib.load
+
+
+def test_decode_entry_refuses_bad_arguments_before_any_launch():
+    """over fake pointers: nothing may be enqueued (no device needed)"""
+    from context_attentive_ir_amd import lib
+    C = lib.C
+    L = lib.load()
+    err = lambda: L.nir_last_error_string()                                  # noqa: E731
+    p, big = C.c_void_p(16), 1 << 30
+    w = _weights()
+
+    def dec(B=2, S=3, W=3, ws=big, pred=p, wt=w, E=4, bos=2, max_len=6, wsp=p):
+        return L.nir_beam_hredqs_decode(p, p, B, S, p, 20, E, None, bos, max_len, C.byref(wt) if wt is not None else None, W, wsp, ws, pred, p, p, None,
+                                        None)
+    for W, VT in ((0, 10), (9, 10), (4, 3)):                                    # width outside 1..8, VT < W
+        assert dec(W=W, wt=_weights(VT=VT)) == -1 and b"beam width" in err()
+        assert L.nir_beam_hredqs_decode_workspace_bytes(2, 3, W, 6, C.byref(_weights(VT=VT))) == 0
+    assert dec(pred=None) == -1 and b"null" in err()
+    assert dec(wt=None) == -1 and b"null" in err()
+    assert dec(wt=_weights(H=6)) == -1 and b"weights" in err()                  # H no multiple of 4
+    bad = _weights()
+    bad.gen_b = None
+    assert dec(wt=bad) == -1 and b"weights" in err()
+    assert dec(E=6) == -1 and b"bad dims" in err()
+    assert dec(max_len=0) == -1 and b"bad dims" in err()
+    assert dec(B=-1) == -1 and b"bad dims" in err()
+    assert dec(bos=20) == -1 and b"BOS" in err()
+    half = _weights()
+    half.rnn_gate_fold = 16
+    assert dec(wt=half) == -1 and b"come together" in err()
+    assert dec(B=1 << 20, S=1 << 20) == -1 and b"too many" in err()
+    assert dec(ws=16) == -3 and b"workspace" in err()
+    assert dec(wsp=None) == -3 and b"workspace" in err()
+    # B S == 0 enqueues nothing, in both forms
+    for wt in (w, _weights(H=32, VT=100, packs=True)):
+        assert dec(B=0, wt=wt) == 0 and dec(S=0, wt=wt) == 0
+    nb = lambda B, S, W, wt: L.nir_beam_hredqs_decode_workspace_bytes(B, S, W, 6, C.byref(wt))        # noqa: E731
+    assert nb(2, 3, 3, w) > nb(0, 3, 3, w) and nb(2, 3, 8, w) > nb(2, 3, 3, w)
+    assert L.nir_beam_hredqs_decode_workspace_bytes(2, 3, 3, 0, C.byref(w)) == 0
+    # the plain form holds [R, VT] logits, the fast form the split state and the partials instead
+    plain, fast = _weights(H=32, VT=5000), _weights(H=32, VT=5000, packs=True)
+    assert nb(4, 4, 8, plain) > 128 * 5000 * 4 > nb(4, 4, 8, fast) > 0
+
+
+def test_gen_topk_entry_refuses_bad_arguments_before_any_launch():
+    from context_attentive_ir_amd import lib
+    C = lib.C
+    L = lib.load()
+    err = lambda: L.nir_last_error_string()                                  # noqa: E731
+    p, big = C.c_void_p(16), 1 << 30
+
+    def top(rows=5, K=64, VT=40, W=3, ws=big, h16=p, frag=p, out=p):
+        return L.nir_beam_hredqs_gen_topk(h16, rows, K, p, frag, VT, W, p, ws, out, p, p, None)
+    for W, VT in ((0, 40), (9, 40), (4, 3)):
+        assert top(W=W, VT=VT) == -1 and b"beam width" in err()
+        assert L.nir_beam_hredqs_gen_topk_workspace_bytes(5, 64, VT, W) == 0
+    for K in (0, 16, 48, 1056):                                                 # the envelope: K a multiple of 32 in [32, 1024]
+        assert top(K=K) == -1 and b"multiple of 32" in err()
+        assert L.nir_beam_hredqs_gen_topk_workspace_bytes(5, K, 40, 3) == 0
+    assert top(VT=0) == -1 and top(VT=(1 << 31) - 16) == -1
+    assert top(h16=None) == -1 and b"null" in err()
+    assert top(frag=None) == -1 and b"null" in err()
+    assert top(out=None) == -1 and b"null" in err()
+    assert top(rows=-1) == -1 and b"bad dims" in err()
+    assert top(ws=64) == -3 and b"workspace" in err()
+    assert top(rows=0) == 0 and L.nir_beam_hredqs_gen_topk_workspace_bytes(0, 64, 40, 3) == 0
+    assert L.nir_beam_hredqs_gen_topk_workspace_bytes(65, 64, 40, 8) > L.nir_beam_hredqs_gen_topk_workspace_bytes(5, 64, 40, 3) > 0
+
+
+# ---- the Python surface ---------------------------------------------------------------------------------------------------------------------------
+def test_decode_beam_and_the_wrapper_on_the_cpu():
+    import context_attentive_ir_amd.wrappers as Wr
+    from context_attentive_ir_amd.config import default_args
+    from context_attentive_ir_amd.recommender import HredQS
+    cs = R.load_case("h64")
+    import hredqs_ref as H
+    net = H.case("h64")[0]
+    assert callable(getattr(HredQS, "decode_beam"))
+    with pytest.raises(RuntimeError, match="ROCm device only"):                # no CPU fallback
+        net.decode_beam(cs["src"], cs["lens"], 6, 4)
+    for W in (0, 9, cs["VT"] + 1):
+        with pytest.raises(ValueError, match="beam_size"):
+            net.decode_beam(cs["src"], cs["lens"], 6, W)
+    net.train()
+    with pytest.raises(NotImplementedError, match="eval mode"):
+        net.decode_beam(cs["src"], cs["lens"], 6, 4)
+    net.eval()
+    # the same refusals as decode()
+    kw = dict(src_vocab_size=50, tgt_vocab_size=50, nhid=32, nhid_session=32)
+    with pytest.raises(IndexError, match="tuple index out of range"):
+        HredQS(default_args("HREDQS", bidirection=False, nlayers=2, **kw)).eval().decode_beam(cs["src"], cs["lens"], 6, 4)
+    with pytest.raises(RuntimeError, match="Sizes of tensors must match"):
+        HredQS(default_args("HREDQS", bidirection=True, nlayers=1, **kw)).eval().decode_beam(cs["src"], cs["lens"], 6, 4)
+    s = Wr.SessionRecommender(default_args("HREDQS", bidirection=False, nlayers=1, **kw))
+    assert not hasattr(s.args, "beam_size")
+    with pytest.raises(NotImplementedError, match="beam") as e:
+        s.predict_beam({}, 4)
+    assert "predict_session_nbest" in str(e.value)
+    with pytest.raises(NotImplementedError, match="HredQS") as e:
+        s.predict_nbest({}, 4)
+    assert "predict_session_nbest" in str(e.value)
+    assert callable(getattr(Wr.SessionRecommender, "predict_session_nbest")) and not hasattr(Wr.Recommender, "predict_session_nbest")
+    with pytest.raises(ValueError, match="beam_size"):
+        s.predict_session_nbest({}, 9)
+    with pytest.raises(NotImplementedError, match="SessionRecommender"):       # the plain Recommender still refuses HREDQS
+        Wr.Recommender(default_args("HREDQS", bidirection=False, nlayers=1, **kw))
