@@ -9,11 +9,18 @@
 // and once behind the loop beam_backtrack_kernel walks the stored back-pointers.  The global top-W over (k, v) lies inside the per-row top-W of
 // the raw logits, since lse is constant within a row.  Everything is enqueued on the caller's stream; no host synchronisation, no allocation,
 // no float atomics, every reduction in a fixed order.
-// ACG's search (include/neuroir_acg_beam.h) is the same loop with another tail: the PAD-substituting forms of the two top-k
-// kernels, acg_beam_row_kernel (the W best of a row's collapsed extended distribution) and acg_beam_select_kernel.
-// HredQS's search (include/neuroir_hredqs_beam.h) is the plain decoder's loop of section 23 with hq_beam_begin_kernel in
-// front (pairing, repeat, split) and, in its fast form, hq_beam_gen_topk_kernel: the top-W on the split state the folded step leaves.
-#include <mutex>
+// Every search in this file is that loop, and each part of it exists once: one generator top-k kernel (its rows fp32 or already split:
+// BeamRowsF32 / BeamRowsSplit), one wave drain (beam_wave_pop_best), one selection (beam_select_rounds), one backtrack walk
+// (beam_backtrack_walk), one carve of the partials (BeamPartials) and one tail on the host (BeamTail: begin, gen, select, reorder, end).
+// ACG's search (include/neuroir_acg_beam.h) has another tail: the PAD-substituting forms of the two top-k kernels,
+// acg_beam_row_kernel (the W best of a row's collapsed extended distribution) and the selection over extended ids (acg_beam_select_kernel).
+// The session models' searches (include/neuroir_session_beam.h) put the tail behind the CARS step and behind the decoders
+// without attention.  HredQS's search (include/neuroir_hredqs_beam.h) is the latter's loop (plain_beam_decode) with
+// hq_beam_begin_kernel in front (pairing, repeat, split) and, in its fast form, the generator top-k on the split state the folded step leaves.
+// The generator top-k kernel restates the staging, the chunk clamp and the fragment walk of the two greedy kernels, s2s_gen_argmax_kernel
+// (s2s_gen.hpp) and hq_gen_argmax_kernel (csrc/hredqs.hip), whose code and register allocation stay as they are: a change to one of those has
+// to be made in the greedy kernels too.
+#include <type_traits>
 #include "s2s_gen.hpp"
 
 namespace nir {
@@ -59,54 +66,116 @@ __device__ __forceinline__ int wave_min_i(int v) {
     v = min(v, dpp_mov_i<0x140>(v));
     return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)), min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
 }
+// One round of the drain that merges the sorted lists of a wave's 64 lanes: (mx, mi) is the largest head, the smallest index among equals, in
+// every lane; its owner pops.  W rounds give the wave's W best in order.  (The loop stays with the caller: inside the helper it compiles to
+// another schedule of the row kernels.)
+template <int WM>
+__device__ __forceinline__ void beam_wave_pop_best(float (&tv)[WM], int (&ti)[WM], float& mx, int& mi) {
+    const float hv = tv[0];
+    const int hi = ti[0];
+    mx = wave_max(hv);
+    mi = wave_min_i(hv == mx ? hi : BEAM_NONE);
+    beam_pop<WM>(tv, ti, hv == mx && hi == mi);
+}
 
 // ---- generator + bias + (lse, top-W): logits[b, v] = x[b, :] . W[v, :] + bias[v] never leave the chip --------------------------------------
-// The staging, tiling, fragment format and chunked prefetch of s2s_gen_argmax_kernel (s2s_gen.hpp), restated here: moving them into shared
-// inline helpers changes the register allocation and schedule of the greedy kernel, whose code is to stay as it is -- a change to the
-// staging, the chunk clamp or the walk has to be made in both.  In the place of its (best, index) every
-// lane keeps, per batch tile, the online-softmax pair (max, sum) and a sorted list of its WM largest biased logits with their indices: one
-// threshold test per value, an insertion only when it passes.  The four lanes of a decode row are merged in the wave (WM rounds: the best of
-// the four heads wins, its owner pops); every wave writes one partial per decode row -- pval / pidx [part][Bd][W], pm / ps [part][Bd] -- and
-// beam_merge_row reduces the partials of all waves and workgroups.
+// The staging, tiling, fragment format and chunked prefetch of the greedy kernels (see the head of the file).  In the place of their (best,
+// index) every lane keeps, per batch tile, the online-softmax pair (max, sum) and a sorted list of its WM largest biased logits with their
+// indices: one threshold test per value, an insertion only when it passes.  The four lanes of a decode row are merged in the wave (WM rounds:
+// the best of the four heads wins, its owner pops); every wave writes one partial per decode row -- pval / pidx [part][Bd][W], pm / ps
+// [part][Bd] -- and beam_merge_row reduces the partials of all waves and workgroups.  The logit is the greedy kernels' expression: W = 1 picks
+// their token.
 // PAD (the copy generator's beam): the logit of v == 0 is replaced by ACG_PAD_LOGIT before the online-softmax pair and the
 // list insert, as STATS does in s2s_gen_argmax_kernel.  PAD = false compiles to the kernel without the test.
-template <int NBT, int WM, bool PAD = false>
-__global__ __launch_bounds__(256, 1) void beam_gen_topk_kernel(const float* __restrict__ x, const _Float16* __restrict__ wfrag,
+// ROWSRC: where the decode rows come from and how the grid maps to (row block, vocabulary range) -- the only two things the forms differ in.
+// The kernel stages its NR = 16 NBT rows from b0 on into the LDS planes [2 terms][NR][K + 8] in K/4 chunks a row (zero rows past Bd; the loads
+// of SB trips are issued, unconditionally and from a clamped row, before the first is written): load() reads chunk c of a row, store() puts it
+// into the planes.  map() reads blockIdx of a grid of nvr ranges x ceil(Bd / NR) row blocks.  The mapping is a speed choice: any placement
+// gives the same partials up to the order of the parts, which the merge's tie rule does not depend on.
+struct BeamRowsF32 {                                  // fp32 rows x [Bd, K], split into the two fp16 terms on load; a row block's ranges are adjacent
+    using elem = float;
+    template <int NR>
+    static __device__ __forceinline__ void map(int nvr, int64_t, int& vr, int64_t& b0) {
+        vr = (int)(blockIdx.x % nvr);
+        b0 = (int64_t)(blockIdx.x / nvr) * NR;
+    }
+    using chunk = float4;                             // four fp32 of a row -> four fp16 in either plane
+    static __device__ __forceinline__ float4 load(const float* __restrict__ x, int64_t row, int c, int K) {
+        return *reinterpret_cast<const float4*>(x + row * K + c * 4);
+    }
+    template <int NR>
+    static __device__ __forceinline__ void store(_Float16* sm, int r, int c, int LD, float4 v) {
+        const Split2x4 sp = split2(v);
+        _Float16* d = sm + r * LD + c * 4;
+        *reinterpret_cast<uint2*>(d) = sp.hi;
+        *reinterpret_cast<uint2*>(d + NR * LD) = sp.lo;
+    }
+};
+// The rows as the folded LSTM step writes them, h16 [row][K/8][2 terms][8] (HredQS): one 16-byte copy per (row, k-group,
+// term), no fp32 load, no conversion.  The grid is hq_gen_argmax_kernel's nrb row blocks x nvr ranges with its blockIdx mapping: the row blocks
+// of a range run together on one XCD and share its L2 (nvr a multiple of 8), else they are adjacent in dispatch order.  A beam has W times the
+// rows of the greedy decode, so a range is read by W times the row blocks.
+struct BeamRowsSplit {
+    using elem = _Float16;
+    template <int NR>
+    static __device__ __forceinline__ void map(int nvr, int64_t R, int& vr, int64_t& b0) {
+        const int nrb = (int)((uint64_t)(R + NR - 1) / NR);                       // the launcher's row-block count
+        int rb;
+        if (nvr % 8 == 0) {
+            const int j = (int)(blockIdx.x >> 3);
+            rb = j % nrb;
+            vr = (j / nrb) * 8 + (int)(blockIdx.x & 7);
+        } else {
+            rb = (int)(blockIdx.x % nrb);
+            vr = (int)(blockIdx.x / nrb);
+        }
+        b0 = (int64_t)rb * NR;
+    }
+    using chunk = uint4;                              // the eight fp16 of one (k-group, term): 16 bytes, copied
+    static __device__ __forceinline__ uint4 load(const _Float16* __restrict__ h16, int64_t row, int c, int K) {
+        return *reinterpret_cast<const uint4*>(h16 + (row * (K / 4) + c) * 8);
+    }
+    template <int NR>
+    static __device__ __forceinline__ void store(_Float16* sm, int r, int c, int LD, uint4 v) {
+        *reinterpret_cast<uint4*>(sm + (c & 1) * NR * LD + r * LD + (c >> 1) * 8) = v;
+    }
+};
+
+template <class ROWSRC, int NBT, int WM, bool PAD>
+__global__ __launch_bounds__(256, 1) void beam_gen_topk_kernel(const typename ROWSRC::elem* __restrict__ x, const _Float16* __restrict__ wfrag,
                                                                const float* __restrict__ bias, int64_t VT, int64_t ntiles, int64_t Bd, int K, int nvr,
                                                                int W, float* __restrict__ pval, int* __restrict__ pidx, float* __restrict__ pm,
                                                                float* __restrict__ ps) {
     extern __shared__ __attribute__((aligned(16))) _Float16 beam_sm[];         // [2 terms][ROWS][LD]
     constexpr int ROWS = 16 * NBT;
-    const int LD = K + 8, KS = K / 32, K4 = K / 4;
+    const int LD = K + 8, KS = K / 32;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c16 = lane & 15, g4 = lane >> 4;
-    const int vr = (int)(blockIdx.x % nvr);
-    const int64_t b0 = (int64_t)(blockIdx.x / nvr) * ROWS;
+    int vr;
+    int64_t b0;
+    ROWSRC::template map<ROWS>(nvr, Bd, vr, b0);
     const int64_t per_wg = (ntiles + nvr - 1) / nvr;
     const int64_t t_lo = (int64_t)vr * per_wg, t_hi = min(ntiles, t_lo + per_wg);
     {
-        constexpr int SB = 8;                                                     // loads in flight before the first is converted
-        const int total = ROWS * K4;                                              // a multiple of 256
+        constexpr int SB = 8;                                                     // loads in flight before the first is written
+        const int K4 = K / 4, total = ROWS * K4;                                  // K/4 chunks a row in either form; total a multiple of 256
         for (int e0 = tid; e0 < total; e0 += 256 * SB) {
-            float4 sv[SB];
+            typename ROWSRC::chunk sv[SB];
 #pragma unroll
             for (int q = 0; q < SB; ++q) {
                 const int e = min(e0 + 256 * q, total - 1);
-                const int r = e / K4, k4 = (e - r * K4) * 4;
+                const int r = e / K4, c = e - r * K4;
                 const int64_t b = b0 + r;
-                sv[q] = *reinterpret_cast<const float4*>(x + (b < Bd ? b : Bd - 1) * K + k4);
+                sv[q] = ROWSRC::load(x, b < Bd ? b : Bd - 1, c, K);
             }
 #pragma unroll
             for (int q = 0; q < SB; ++q) {
                 const int e = e0 + 256 * q;
                 if (e < total) {
-                    const int r = e / K4, k4 = (e - r * K4) * 4;
-                    float4 v = sv[q];
-                    if (b0 + r >= Bd) v = make_float4(0.f, 0.f, 0.f, 0.f);
-                    const Split2x4 sp = split2(v);
-                    _Float16* d = beam_sm + r * LD + k4;
-                    *reinterpret_cast<uint2*>(d) = sp.hi;
-                    *reinterpret_cast<uint2*>(d + ROWS * LD) = sp.lo;
+                    const int r = e / K4, c = e - r * K4;
+                    typename ROWSRC::chunk v = sv[q];
+                    if (b0 + r >= Bd) v = {};
+                    ROWSRC::template store<ROWS>(beam_sm, r, c, LD, v);
                 }
             }
         }
@@ -238,8 +307,7 @@ __global__ __launch_bounds__(256, 1) void beam_gen_topk_kernel(const float* __re
 // ---- partial lists of one row -> (lse, top-W), one wave ------------------------------------------------------------------------------------
 // pval / pidx [part][rows][stride] (the first W of a list are read), pm / ps [part][rows] (ps NULL: every sum is 1, so a single part with
 // pm = lse passes through bit for bit).  Lane l takes parts l, l + 64, ... in order; the wave's maxima and sums combine through wave_max /
-// wave_sum (a fixed tree) and the lists through W rounds of (largest head, smallest index among equals, its owner pops).
-// Lane 0 writes out_val / out_idx [W] and *out_lse.
+// wave_sum (a fixed tree) and the lists through W rounds of beam_wave_pop_best.  Lane 0 writes out_val / out_idx [W] and *out_lse.
 // beam_merge_row_ms leaves the pair (max, sum) to the caller, in every lane, in the place of lse = max + log(sum).
 __device__ __forceinline__ void beam_merge_row_ms(const float* pval, const int* pidx, const float* pm, const float* ps, int nparts, int64_t rows,
                                                   int64_t row, int stride, int W, int lane, float* out_val, int* out_idx, float& M, float& S) {
@@ -264,11 +332,9 @@ __device__ __forceinline__ void beam_merge_row_ms(const float* pval, const int* 
     M = wave_max(m);
     S = wave_sum(m > -INFINITY ? s * expf(m - M) : 0.f);
     for (int j = 0; j < W; ++j) {
-        const float hv = tv[0];
-        const int hi = ti[0];
-        const float mx = wave_max(hv);
-        const int mi = wave_min_i(hv == mx ? hi : BEAM_NONE);
-        beam_pop<WM>(tv, ti, hv == mx && hi == mi);
+        float mx;
+        int mi;
+        beam_wave_pop_best<WM>(tv, ti, mx, mi);
         if (lane == 0) { out_val[j] = mx; out_idx[j] = mi; }
     }
 }
@@ -284,185 +350,6 @@ __global__ __launch_bounds__(64) void beam_topk_finish_kernel(const float* __res
                                                               float* __restrict__ top_val, int* __restrict__ top_idx, float* __restrict__ lse) {
     const int64_t row = blockIdx.x;
     beam_merge_row(pval, pidx, pm, ps, nparts, rows, row, W, W, threadIdx.x, top_val + row * W, top_idx + row * W, lse + row);
-}
-
-// ---- generator + bias + (lse, top-W) on the SPLIT state: HredQS (include/neuroir_hredqs_beam.h) -------------------------------
-// beam_gen_topk_kernel fed as hq_gen_argmax_kernel (csrc/hredqs.hip) is: the beam rows arrive already split, as the folded LSTM step writes them
-// (h16 [row][K/8][2 terms][8]), so staging is one 16-byte copy per (row, k-group, term) into the two LDS planes [2][16 NBT][K + 8] -- no fp32
-// load, no conversion -- and the grid is that kernel's nrb row blocks x nvr vocabulary ranges with its blockIdx mapping: the row blocks of a
-// range run together on one XCD and share its L2 (nvr a multiple of 8), else they are adjacent in dispatch order.  A beam has W times the rows
-// of the greedy decode, so a range is read by W times the row blocks.  The walk, the chunked fragment prefetch and the three-MFMA product are
-// those of both kernels, restated for the reason given at beam_gen_topk_kernel; the logit is the greedy kernel's expression (W = 1 picks its
-// token) and the epilogue is beam_gen_topk_kernel's, so the partials -- pval / pidx [4 nvr][R][W], pm / ps [4 nvr][R] -- are read by
-// beam_select_kernel and beam_topk_finish_kernel unchanged.  The mapping is a speed choice: any placement gives the same partials up to the
-// order of the parts, which the merge's tie rule does not depend on.
-template <int NBT, int WM>
-__global__ __launch_bounds__(256, 1) void hq_beam_gen_topk_kernel(const _Float16* __restrict__ h16, const _Float16* __restrict__ wfrag,
-                                                                  const float* __restrict__ bias, int64_t VT, int64_t ntiles, int64_t R, int K, int nvr,
-                                                                  int nrb, int W, float* __restrict__ pval, int* __restrict__ pidx,
-                                                                  float* __restrict__ pm, float* __restrict__ ps) {
-    extern __shared__ __attribute__((aligned(16))) _Float16 hqb_sm[];          // [2 terms][ROWS][LD]
-    constexpr int ROWS = 16 * NBT;
-    const int LD = K + 8, KS = K / 32, Q = K / 4;                              // Q: 16-byte chunks of a row (k-group, term)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int c16 = lane & 15, g4 = lane >> 4;
-    int vr, rb;
-    if (nvr % 8 == 0) {
-        const int j = (int)(blockIdx.x >> 3);
-        rb = j % nrb;
-        vr = (j / nrb) * 8 + (int)(blockIdx.x & 7);
-    } else {
-        rb = (int)(blockIdx.x % nrb);
-        vr = (int)(blockIdx.x / nrb);
-    }
-    const int64_t b0 = (int64_t)rb * ROWS;
-    const int64_t per_wg = (ntiles + nvr - 1) / nvr;
-    const int64_t t_lo = (int64_t)vr * per_wg, t_hi = min(ntiles, t_lo + per_wg);
-    {
-        // stage this workgroup's beam rows (zero rows past R): the loads of SB trips are issued before the first is written (unconditional, from
-        // a clamped row)
-        constexpr int SB = 8;
-        const int total = ROWS * Q;                                            // a multiple of 256
-        for (int e0 = tid; e0 < total; e0 += 256 * SB) {
-            uint4 sv[SB];
-#pragma unroll
-            for (int q = 0; q < SB; ++q) {
-                const int e = min(e0 + 256 * q, total - 1);
-                const int r = e / Q, c = e - r * Q;
-                const int64_t b = b0 + r;
-                sv[q] = *reinterpret_cast<const uint4*>(h16 + ((b < R ? b : R - 1) * Q + c) * 8);
-            }
-#pragma unroll
-            for (int q = 0; q < SB; ++q) {
-                const int e = e0 + 256 * q;
-                if (e < total) {
-                    const int r = e / Q, c = e - r * Q;
-                    uint4 v = sv[q];
-                    if (b0 + r >= R) v = make_uint4(0u, 0u, 0u, 0u);
-                    *reinterpret_cast<uint4*>(hqb_sm + (c & 1) * ROWS * LD + r * LD + (c >> 1) * 8) = v;
-                }
-            }
-        }
-    }
-    __syncthreads();
-    float tv[NBT][WM], rm[NBT], rs[NBT];
-    int ti[NBT][WM];
-#pragma unroll
-    for (int bt = 0; bt < NBT; ++bt) {
-        rm[bt] = -INFINITY;
-        rs[bt] = 0.f;
-#pragma unroll
-        for (int j = 0; j < WM; ++j) { tv[bt][j] = -INFINITY; ti[bt][j] = BEAM_NONE; }
-    }
-    const int NCH = (KS + HQ_KC - 1) / HQ_KC;
-    const int64_t first = t_lo + wave;
-    const int64_t nt = first < t_hi ? (t_hi - first + 3) / 4 : 0;             // this wave's tiles: first, first + 4, ...
-    const int64_t items = nt * NCH;                                           // (tile, chunk) pairs, in order
-    f32x4 acc[NBT], acx[NBT];
-    auto load_w = [&](int64_t it, f16x8 (&wf)[HQ_KC][2]) {
-        const int64_t t = first + 4 * (it / NCH);
-        const int c = (int)(it % NCH);
-#pragma unroll
-        for (int u = 0; u < HQ_KC; ++u) {
-            const int ks = min(c * HQ_KC + u, KS - 1);                        // clamped: a duplicate k-step is not multiplied below
-            const _Float16* wp = wfrag + ((t * KS + ks) * 2 * 64 + lane) * 8;
-            wf[u][0] = *reinterpret_cast<const f16x8*>(wp);
-            wf[u][1] = *reinterpret_cast<const f16x8*>(wp + 512);
-        }
-    };
-    const _Float16* bp0 = hqb_sm + c16 * LD + 8 * g4;
-    auto compute = [&](int64_t it, const f16x8 (&wf)[HQ_KC][2]) {
-        const int64_t t = first + 4 * (it / NCH);
-        const int c = (int)(it % NCH);
-        if (c == 0) {
-#pragma unroll
-            for (int bt = 0; bt < NBT; ++bt) { acc[bt] = (f32x4){0.f, 0.f, 0.f, 0.f}; acx[bt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
-        }
-#pragma unroll
-        for (int u = 0; u < HQ_KC; ++u) {
-            const int ks = c * HQ_KC + u;
-            if (ks < KS) {                                                    // wave-uniform
-                f16x8 b[NBT][2];
-#pragma unroll
-                for (int bt = 0; bt < NBT; ++bt) {
-                    b[bt][0] = *reinterpret_cast<const f16x8*>(bp0 + 32 * ks + bt * 16 * LD);
-                    b[bt][1] = *reinterpret_cast<const f16x8*>(bp0 + 32 * ks + bt * 16 * LD + ROWS * LD);
-                }
-#pragma unroll
-                for (int bt = 0; bt < NBT; ++bt) acx[bt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][1], b[bt][0], acx[bt], 0, 0, 0);
-#pragma unroll
-                for (int bt = 0; bt < NBT; ++bt) acc[bt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][0], b[bt][0], acc[bt], 0, 0, 0);
-#pragma unroll
-                for (int bt = 0; bt < NBT; ++bt) acx[bt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][0], b[bt][1], acx[bt], 0, 0, 0);
-            }
-        }
-        if (c == NCH - 1) {
-            const int64_t v0 = t * 16 + 4 * g4;
-            float bv[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) bv[r] = (bias && v0 + r < VT) ? bias[v0 + r] : 0.f;
-#pragma unroll
-            for (int bt = 0; bt < NBT; ++bt) {
-                float y[4];
-                float m = rm[bt];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    y[r] = fmaf(acx[bt][r], SPLIT2_INV, acc[bt][r]) + bv[r];  // the greedy kernel's expression: W = 1 picks its token
-                    if (v0 + r >= VT) y[r] = -INFINITY;                       // padded tile rows: never kept, add exp(-inf) = 0
-                    m = fmaxf(m, y[r]);
-                }
-                if (m > -INFINITY) {
-                    rs[bt] = rs[bt] * __expf(rm[bt] - m) + ((__expf(y[0] - m) + __expf(y[1] - m)) + (__expf(y[2] - m) + __expf(y[3] - m)));
-                    rm[bt] = m;
-                }
-#pragma unroll
-                for (int r = 0; r < 4; ++r)                                   // ascending in r: '>' keeps the first index in front
-                    if (y[r] > tv[bt][WM - 1]) beam_insert<WM, false>(tv[bt], ti[bt], y[r], (int)(v0 + r));
-            }
-        }
-    };
-    {
-        f16x8 wfA[HQ_KC][2], wfB[HQ_KC][2];
-        if (items > 0) load_w(0, wfA);
-        for (int64_t it = 0; it < items; it += 2) {
-            if (it + 1 < items) load_w(it + 1, wfB);
-            compute(it, wfA);
-            if (it + 1 >= items) break;
-            if (it + 2 < items) load_w(it + 2, wfA);
-            compute(it + 1, wfB);
-        }
-    }
-    // lanes l, l + 16, l + 32, l + 48 hold the same beam row: the sums combine (only the g4 == 0 lane's value is written), the lists merge head
-    // by head by comparisons alone
-#pragma unroll
-    for (int bt = 0; bt < NBT; ++bt) {
-#pragma unroll
-        for (int sh = 16; sh <= 32; sh <<= 1) {
-            const float om = __shfl_xor(rm[bt], sh), os = __shfl_xor(rs[bt], sh);
-            const float m = fmaxf(om, rm[bt]);
-            rs[bt] = m > -INFINITY ? rs[bt] * __expf(rm[bt] - m) + os * __expf(om - m) : 0.f;
-            rm[bt] = m;
-        }
-        const int64_t b = b0 + bt * 16 + c16;
-        const int64_t slot = ((int64_t)vr * 4 + wave) * R + b;
-        const bool writer = g4 == 0 && b < R;
-        if (writer) { pm[slot] = rm[bt]; ps[slot] = rs[bt]; }
-#pragma unroll
-        for (int j = 0; j < WM; ++j) {
-            const float hv = tv[bt][0];
-            const int hi = ti[bt][0];
-            float wv = hv;
-            int wi = hi;
-#pragma unroll
-            for (int sh = 16; sh <= 32; sh <<= 1) {
-                const float ov = __shfl_xor(wv, sh);
-                const int oi = __shfl_xor(wi, sh);
-                if (beam_before(ov, oi, wv, wi)) { wv = ov; wi = oi; }
-            }
-            beam_pop<WM>(tv[bt], ti[bt], hv == wv && hi == wi);
-            if (writer && j < W) { pval[slot * W + j] = wv; pidx[slot * W + j] = wi; }
-        }
-    }
 }
 
 // ---- the HredQS beam's first state, one launch: pairing, repeat and split --------------------------------------------------------------------------
@@ -535,6 +422,51 @@ __global__ __launch_bounds__(256) void beam_row_topk_kernel(const float* __restr
 // Per beam k of source row b (decode row k B + b): the partials merge to lse and the top-W logits; lane k W + j then holds candidate j of
 // beam k -- live: cum[b, k] + (y - lse), token v; finished: j = 0 alone, (cum[b, k], EOS).  W rounds pick (score descending, k ascending, v
 // ascending: the flat index k VT + v).  cum and finished are read before anything is written, so they update in place.
+// beam_select_rounds is the selection of source row b by one wave, behind whatever produced the lists.  cand(k, j, y, v): the log-probability
+// and the id of candidate j of the live beam k; ids outside [0, nid) read as 0; fed(tokv): the source-side id the next step reads for token
+// tokv (<unk> outside [0, Vsrc)).
+template <class Cand, class Fed>
+__device__ __forceinline__ void beam_select_rounds(int64_t b, int64_t B, int W, int lane, int64_t nid, int64_t Vsrc, Cand cand, Fed fed,
+                                                   float* __restrict__ cum, int* __restrict__ finished, int* __restrict__ backptr,
+                                                   int* __restrict__ token, int64_t* __restrict__ next_ids) {
+    const int k = lane / W, j = lane - k * W;
+    bool open = false;                                                        // a candidate not yet taken
+    float score = -INFINITY;
+    int v = BEAM_NONE;
+    if (k < W) {
+        const float ck = cum[b * W + k];
+        if (finished[b * W + k]) {
+            open = j == 0;
+            score = ck;
+            v = NIR_BEAM_EOS;
+        } else {
+            float y;
+            cand(k, j, y, v);
+            open = true;
+            score = ck + y;
+        }
+        if (!(score == score)) score = -INFINITY;                             // a NaN never wins and never stalls the rounds
+    }
+    for (int o = 0; o < W; ++o) {
+        const float sc = open ? score : -INFINITY;
+        const float mx = wave_max(sc);
+        const bool c1 = open && sc == mx;
+        const int mk = wave_min_i(c1 ? k : BEAM_NONE);
+        const bool c2 = c1 && k == mk;
+        const int mv = wave_min_i(c2 ? v : BEAM_NONE);
+        if (c2 && v == mv) {
+            open = false;
+            const int64_t tokv = (v >= 0 && (int64_t)v < nid) ? v : 0;
+            const int64_t slot = b * W + o;
+            cum[slot] = score;
+            finished[slot] = tokv == NIR_BEAM_EOS;                             // (a frozen candidate's token is EOS too)
+            backptr[slot] = k;
+            token[slot] = (int)tokv;
+            const int64_t nxt = fed(tokv);
+            next_ids[(int64_t)o * B + b] = (nxt >= 0 && nxt < Vsrc) ? nxt : 1;
+        }
+    }
+}
 __global__ __launch_bounds__(64) void beam_select_kernel(const float* __restrict__ pval, const int* __restrict__ pidx, const float* __restrict__ pm,
                                                          const float* __restrict__ ps, int nparts, int64_t B, int W, int64_t VT,
                                                          const int64_t* __restrict__ lut, int64_t Vsrc, float* __restrict__ cum,
@@ -550,42 +482,13 @@ __global__ __launch_bounds__(64) void beam_select_kernel(const float* __restrict
         beam_merge_row(pval, pidx, pm, ps, nparts, B * W, (int64_t)k * B + b, W, W, lane, cval + k * W, cidx + k * W, clse + k);
     }
     __syncthreads();
-    const int k = lane / W, j = lane - k * W;
-    bool open = false;                                                        // a candidate not yet taken
-    float score = -INFINITY;
-    int v = BEAM_NONE;
-    if (k < W) {
-        const float ck = cum[b * W + k];
-        if (finished[b * W + k]) {
-            open = j == 0;
-            score = ck;
-            v = NIR_BEAM_EOS;
-        } else {
-            open = true;
-            score = ck + (cval[k * W + j] - clse[k]);
+    beam_select_rounds(
+        b, B, W, lane, VT, Vsrc,
+        [&](int k, int j, float& y, int& v) {
+            y = cval[k * W + j] - clse[k];
             v = cidx[k * W + j];
-        }
-        if (!(score == score)) score = -INFINITY;                             // a NaN never wins and never stalls the rounds
-    }
-    for (int o = 0; o < W; ++o) {
-        const float sc = open ? score : -INFINITY;
-        const float mx = wave_max(sc);
-        const bool c1 = open && sc == mx;
-        const int mk = wave_min_i(c1 ? k : BEAM_NONE);
-        const bool c2 = c1 && k == mk;
-        const int mv = wave_min_i(c2 ? v : BEAM_NONE);
-        if (c2 && v == mv) {
-            open = false;
-            const int64_t tokv = (v >= 0 && (int64_t)v < VT) ? v : 0;
-            const int64_t slot = b * W + o;
-            cum[slot] = score;
-            finished[slot] = tokv == NIR_BEAM_EOS;                             // (a frozen candidate's token is EOS too)
-            backptr[slot] = k;
-            token[slot] = (int)tokv;
-            const int64_t nxt = lut ? lut[tokv] : tokv;
-            next_ids[(int64_t)o * B + b] = (nxt >= 0 && nxt < Vsrc) ? nxt : 1;
-        }
-    }
+        },
+        [&](int64_t tokv) { return lut ? lut[tokv] : tokv; }, cum, finished, backptr, token, next_ids);
 }
 
 // ---- the copy generator's beam (include/neuroir_acg_beam.h) -------------------------------------------------------------
@@ -686,62 +589,29 @@ __global__ __launch_bounds__(64) void acg_beam_row_kernel(const float* __restric
         if (lane == 0) offer(omz * expf(lt - m) / Z + cp, t);
     }
     for (int j = 0; j < W; ++j) {
-        const float hv = tv[0];
-        const int hi = ti[0];
-        const float mx = wave_max(hv);
-        const int mi = wave_min_i(hv == mx ? hi : BEAM_NONE);
-        beam_pop<WM>(tv, ti, hv == mx && hi == mi);
+        float mx;
+        int mi;
+        beam_wave_pop_best<WM>(tv, ti, mx, mi);
         if (lane == 0) { top_val[r * W + j] = mx; top_idx[r * W + j] = mi; }
     }
 }
 
-// The selection of beam_select_kernel over finished per-row lists (top_val = log P, lse NULL = 0) of EXTENDED ids in [0, VT + CV): the flat index
-// is k (VT + CV) + e, finished means e == EOS, and the token fed back is lut[e] below VT and e2s[b, e - VT] from VT on (<unk> outside [0, Vsrc)).
-// A sibling, so that beam_select_kernel and its callers stay as they are.
+// beam_select_rounds over finished per-row lists (top_val = log P, lse NULL = 0) of EXTENDED ids in [0, VT + CV): the flat index is
+// k (VT + CV) + e, finished means e == EOS, and the token fed back is lut[e] below VT and e2s[b, e - VT] from VT on.
 __global__ __launch_bounds__(64) void acg_beam_select_kernel(const float* __restrict__ top_val, const int* __restrict__ top_idx, const float* __restrict__ lse,
                                                              int64_t B, int W, int64_t VT, int CV, const int64_t* __restrict__ lut,
                                                              const int64_t* __restrict__ e2s, int64_t Vsrc, float* __restrict__ cum,
                                                              int* __restrict__ finished, int* __restrict__ backptr, int* __restrict__ token,
                                                              int64_t* __restrict__ next_ids) {
     const int64_t b = blockIdx.x;
-    const int lane = threadIdx.x;
-    const int k = lane / W, j = lane - k * W;
-    bool open = false;
-    float score = -INFINITY;
-    int v = BEAM_NONE;
-    if (k < W) {
-        const float ck = cum[b * W + k];
-        if (finished[b * W + k]) {
-            open = j == 0;
-            score = ck;
-            v = NIR_BEAM_EOS;
-        } else {
+    beam_select_rounds(
+        b, B, W, threadIdx.x, VT + CV, Vsrc,
+        [&](int k, int j, float& y, int& v) {
             const int64_t row = (int64_t)k * B + b;
-            open = true;
-            score = ck + (top_val[row * W + j] - (lse ? lse[row] : 0.f));
+            y = top_val[row * W + j] - (lse ? lse[row] : 0.f);
             v = top_idx[row * W + j];
-        }
-        if (!(score == score)) score = -INFINITY;
-    }
-    for (int o = 0; o < W; ++o) {
-        const float sc = open ? score : -INFINITY;
-        const float mx = wave_max(sc);
-        const bool c1 = open && sc == mx;
-        const int mk = wave_min_i(c1 ? k : BEAM_NONE);
-        const bool c2 = c1 && k == mk;
-        const int mv = wave_min_i(c2 ? v : BEAM_NONE);
-        if (c2 && v == mv) {
-            open = false;
-            const int64_t tokv = (v >= 0 && (int64_t)v < VT + CV) ? v : 0;
-            const int64_t slot = b * W + o;
-            cum[slot] = score;
-            finished[slot] = tokv == NIR_BEAM_EOS;
-            backptr[slot] = k;
-            token[slot] = (int)tokv;
-            const int64_t nxt = tokv < VT ? (lut ? lut[tokv] : tokv) : e2s[b * CV + (tokv - VT)];
-            next_ids[(int64_t)o * B + b] = (nxt >= 0 && nxt < Vsrc) ? nxt : 1;
-        }
-    }
+        },
+        [&](int64_t tokv) { return tokv < VT ? (lut ? lut[tokv] : tokv) : e2s[b * CV + (tokv - VT)]; }, cum, finished, backptr, token, next_ids);
 }
 
 __global__ void beam_init_kernel(float* __restrict__ cum, int* __restrict__ finished, int64_t n, int W) {
@@ -770,13 +640,13 @@ __global__ __launch_bounds__(256) void beam_reorder_kernel(const int* __restrict
 // ---- backtrack: output beam j of source row b, walked from the last step through the back-pointers ---------------------------------------------
 // tok / bp [max_len][B][W]; attn_ws [max_len][R][QL], the rows as the attention launch of each step wrote them (a step's row belongs to the
 // beam the candidate extended: backptr).
-__global__ __launch_bounds__(64) void beam_backtrack_kernel(const int* __restrict__ tok, const int* __restrict__ bp, const float* __restrict__ attn_ws,
-                                                            const float* __restrict__ cum, int64_t B, int W, int max_len, int QL,
-                                                            int64_t* __restrict__ pred, float* __restrict__ scores, int64_t* __restrict__ lengths,
-                                                            float* __restrict__ attn) {
-    const int64_t o = blockIdx.x;                                             // b W + j
+// The walk of output o = b W + j: the token of every step into pred, the length up to the first EOS, the score; `writer`: this thread writes
+// them.  step(t, b, src): called per step with the (clamped) beam the candidate extended.
+template <class Step>
+__device__ __forceinline__ void beam_backtrack_walk(const int* __restrict__ tok, const int* __restrict__ bp, const float* __restrict__ cum, int64_t B,
+                                                    int W, int max_len, int64_t o, bool writer, int64_t* __restrict__ pred,
+                                                    float* __restrict__ scores, int64_t* __restrict__ lengths, Step step) {
     const int64_t b = o / W;
-    const int lane = threadIdx.x;
     int k = (int)(o - b * W);
     int len = max_len;
     for (int t = max_len - 1; t >= 0; --t) {
@@ -785,95 +655,110 @@ __global__ __launch_bounds__(64) void beam_backtrack_kernel(const int* __restric
         int src = bp[slot];
         src = src < 0 ? 0 : (src >= W ? W - 1 : src);
         if (tk == NIR_BEAM_EOS) len = t + 1;
-        if (lane == 0) pred[o * max_len + t] = tk;
+        if (writer) pred[o * max_len + t] = tk;
+        step(t, b, src);
+        k = src;
+    }
+    if (writer) { scores[o] = cum[o]; lengths[o] = len; }
+}
+// one wave per output: the lanes copy the attention rows
+__global__ __launch_bounds__(64) void beam_backtrack_kernel(const int* __restrict__ tok, const int* __restrict__ bp, const float* __restrict__ attn_ws,
+                                                            const float* __restrict__ cum, int64_t B, int W, int max_len, int QL,
+                                                            int64_t* __restrict__ pred, float* __restrict__ scores, int64_t* __restrict__ lengths,
+                                                            float* __restrict__ attn) {
+    const int64_t o = blockIdx.x;
+    const int lane = threadIdx.x;
+    beam_backtrack_walk(tok, bp, cum, B, W, max_len, o, lane == 0, pred, scores, lengths, [&](int t, int64_t b, int src) {
         const float* ar = attn_ws + (((int64_t)t * W + src) * B + b) * QL;
         float* ao = attn + (o * max_len + t) * QL;
         for (int q = lane; q < QL; q += 64) ao[q] = ar[q];
-        k = src;
+    });
+}
+// without attention rows: one thread per output
+__global__ __launch_bounds__(256) void beam_backtrack_tokens_kernel(const int* __restrict__ tok, const int* __restrict__ bp, const float* __restrict__ cum,
+                                                                    int64_t B, int W, int max_len, int64_t* __restrict__ pred, float* __restrict__ scores,
+                                                                    int64_t* __restrict__ lengths) {
+    const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= B * W) return;
+    beam_backtrack_walk(tok, bp, cum, B, W, max_len, o, true, pred, scores, lengths, [](int, int64_t, int) {});
+}
+
+// out row r = in row r % Bd for the two states (H4 float4 per row), and map_out[r] = map_in[r % Bd] (map_in NULL: no map): the first state of
+// the session models' beams, whose callers repeat nothing
+__global__ __launch_bounds__(256) void beam_repeat_kernel(const float4* __restrict__ h_in, const float4* __restrict__ c_in, int64_t Bd, int H4,
+                                                          float4* __restrict__ h_out, float4* __restrict__ c_out, const int64_t* __restrict__ map_in,
+                                                          int64_t* __restrict__ map_out) {
+    const int64_t r = blockIdx.x, i = r % Bd;
+    for (int f = threadIdx.x; f < H4; f += 256) {
+        h_out[r * H4 + f] = h_in[i * H4 + f];
+        c_out[r * H4 + f] = c_in[i * H4 + f];
     }
-    if (lane == 0) { scores[o] = cum[o]; lengths[o] = len; }
+    if (map_in && threadIdx.x == 0) map_out[r] = map_in[i];
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------------------------------
+// The partials of a top-k producer in a workspace: pval / pidx [parts][rows][W], pm / ps [parts][rows] (sums = false: a producer that writes no
+// sums -- the row kernel's single part with pm = lse -- and ps NULL).  beam_partials_bytes: what these four takes and `takes` - 4 further ones
+// around them need at most.
+struct BeamPartials {
+    float *pval, *pm, *ps;
+    int* pidx;
+    void take(Workspace& a, size_t parts, int64_t rows, int W, bool sums) {
+        pval = a.take<float>(parts * rows * W);
+        pidx = a.take<int>(parts * rows * W);
+        pm = a.take<float>(parts * rows);
+        ps = sums ? a.take<float>(parts * rows) : nullptr;
+    }
+};
+static size_t beam_partials_bytes(size_t parts, int64_t rows, int W, int takes) { return parts * rows * ((size_t)W * 8 + 8) + (size_t)takes * 256; }
+
+// The dispatch over (NBT, WM) of one form of the fused generator: nbt row tiles a workgroup (s2s_nbt), lists of 4 or NIR_BEAM_MAX_W entries.
+// An instantiation's LDS limit is raised once, in front of its first launch.  name: the label of the profile and of the launch check.
+template <class ROWSRC, bool PAD>
+static int beam_gen_launch(const char* name, int nvr, int nbt, int64_t grid, const typename ROWSRC::elem* x, const void* frag, const float* bias, int64_t VT,
+                           int64_t rows, int K, int W, const BeamPartials& p, hipStream_t st) {
+    auto go = [&](auto nbt_c, auto wm_c) {
+        constexpr int NBT = decltype(nbt_c)::value, WM = decltype(wm_c)::value;
+        static const hipError_t raised = hipFuncSetAttribute((const void*)beam_gen_topk_kernel<ROWSRC, NBT, WM, PAD>,
+                                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(NBT == 4 ? 512 : 1024));
+        (void)raised;
+        hipLaunchKernelGGL((beam_gen_topk_kernel<ROWSRC, NBT, WM, PAD>), dim3((unsigned)grid), dim3(256), s2s_lds(K), st, x, (const _Float16*)frag, bias, VT,
+                           (VT + 15) / 16, rows, K, nvr, W, p.pval, p.pidx, p.pm, p.ps);
+    };
+    {
+        ProfScope ps_(prof_shape_name(name, (long long)rows, (long long)VT, K), st);
+        const std::integral_constant<int, 2> i2;
+        const std::integral_constant<int, 4> i4;
+        const std::integral_constant<int, 8> i8;
+        if (nbt == 4 && W <= 4) go(i4, i4);
+        else if (nbt == 4) go(i4, i8);
+        else if (W <= 4) go(i2, i4);
+        else go(i2, i8);
+    }
+    NIR_CHECK_LAUNCH(name);
+    return 0;
+}
 // partials per decode row of the fused generator (one per wave of every vocabulary range); no rows: no row block to size a range by
 static int beam_nparts(int64_t rows, int K, int64_t VT) { return rows > 0 ? 4 * s2s_nvr(rows, K, (VT + 15) / 16) : 0; }
-
-template <int NBT, int WM, bool PAD>
-static void beam_gen_launch(int grid, size_t lds, hipStream_t st, const float* x, const void* frag, const float* bias, int64_t VT, int64_t ntiles,
-                            int64_t rows, int K, int nvr, int W, float* pval, int* pidx, float* pm, float* ps) {
-    hipLaunchKernelGGL((beam_gen_topk_kernel<NBT, WM, PAD>), dim3((unsigned)grid), dim3(256), lds, st, x, (const _Float16*)frag, bias, VT, ntiles, rows, K, nvr, W,
-                       pval, pidx, pm, ps);
-}
-// the fused generator: partials pval / pidx [nparts][rows][W], pm / ps [nparts][rows]; returns nparts through *nparts
-// (pad: the PAD-substituting instantiations of the copy generator's beam)
-static int launch_beam_gen_topk(const float* x, const void* frag, const float* bias, int64_t VT, int64_t rows, int K, int W, float* pval, int* pidx,
-                                float* pm, float* ps, hipStream_t st, bool pad = false) {
-    const int64_t ntiles = (VT + 15) / 16;
-    const int nbt = s2s_nbt(K), nvr = s2s_nvr(rows, K, ntiles);
+// the fused generator on fp32 rows: beam_nparts partials a row (pad: the PAD-substituting instantiations of the copy generator's beam)
+static int launch_beam_gen_topk(const float* x, const void* frag, const float* bias, int64_t VT, int64_t rows, int K, int W, const BeamPartials& p,
+                                hipStream_t st, bool pad = false) {
+    const int nbt = s2s_nbt(K), nvr = s2s_nvr(rows, K, (VT + 15) / 16);
     const int64_t rb = (rows + 16 * nbt - 1) / (16 * nbt);
-    const size_t lds = s2s_lds(K);
-    static std::once_flag once;
-    std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(512));
-        (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(512));
-        (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(1024));
-        (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(1024));
-        (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<4, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(512));
-        (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<4, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(512));
-        (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<2, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(1024));
-        (void)hipFuncSetAttribute((const void*)beam_gen_topk_kernel<2, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(1024));
-    });
-    {
-        ProfScope ps_(prof_shape_name("beam_gen_topk_kernel", (long long)rows, (long long)VT, K), st);
-        const int grid = (int)(nvr * rb);
-        if (pad) {
-            if (nbt == 4 && W <= 4) beam_gen_launch<4, 4, true>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
-            else if (nbt == 4) beam_gen_launch<4, 8, true>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
-            else if (W <= 4) beam_gen_launch<2, 4, true>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
-            else beam_gen_launch<2, 8, true>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
-        } else if (nbt == 4 && W <= 4) beam_gen_launch<4, 4, false>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
-        else if (nbt == 4) beam_gen_launch<4, 8, false>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
-        else if (W <= 4) beam_gen_launch<2, 4, false>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
-        else beam_gen_launch<2, 8, false>(grid, lds, st, x, frag, bias, VT, ntiles, rows, K, nvr, W, pval, pidx, pm, ps);
-    }
-    NIR_CHECK_LAUNCH("beam_gen_topk_kernel");
-    return 0;
+    if (pad) return beam_gen_launch<BeamRowsF32, true>("beam_gen_topk_kernel", nvr, nbt, nvr * rb, x, frag, bias, VT, rows, K, W, p, st);
+    return beam_gen_launch<BeamRowsF32, false>("beam_gen_topk_kernel", nvr, nbt, nvr * rb, x, frag, bias, VT, rows, K, W, p, st);
 }
 // partials per beam row of the split-state generator: one per wave of every vocabulary range of hq_nvr's grid
 static int hq_beam_nparts(int64_t rows, int K, int64_t VT) {
     return rows > 0 ? 4 * hq_nvr((rows + 16 * hq_nbt(K) - 1) / (16 * hq_nbt(K)), (VT + 15) / 16) : 0;
 }
-template <int NBT, int WM>
-static void hq_beam_gen_launch(int grid, size_t lds, hipStream_t st, const _Float16* h16, const void* frag, const float* bias, int64_t VT, int64_t ntiles,
-                               int64_t rows, int K, int nvr, int nrb, int W, float* pval, int* pidx, float* pm, float* ps) {
-    hipLaunchKernelGGL((hq_beam_gen_topk_kernel<NBT, WM>), dim3((unsigned)grid), dim3(256), lds, st, h16, (const _Float16*)frag, bias, VT, ntiles, rows, K, nvr,
-                       nrb, W, pval, pidx, pm, ps);
-}
-// the fused generator on the split state: partials pval / pidx [nparts][rows][W], pm / ps [nparts][rows], nparts = hq_beam_nparts
-static int launch_hq_beam_gen_topk(const _Float16* h16, const void* frag, const float* bias, int64_t VT, int64_t rows, int K, int W, float* pval, int* pidx,
-                                   float* pm, float* ps, hipStream_t st) {
-    const int64_t ntiles = (VT + 15) / 16;
+// the fused generator on the split state: hq_beam_nparts partials a row
+static int launch_hq_beam_gen_topk(const _Float16* h16, const void* frag, const float* bias, int64_t VT, int64_t rows, int K, int W, const BeamPartials& p,
+                                   hipStream_t st) {
     const int nbt = hq_nbt(K);
     const int64_t nrb = (rows + 16 * nbt - 1) / (16 * nbt);
-    const int nvr = hq_nvr(nrb, ntiles);
-    const size_t lds = hq_lds(K);
-    static std::once_flag once;
-    std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void*)hq_beam_gen_topk_kernel<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hq_lds(512));
-        (void)hipFuncSetAttribute((const void*)hq_beam_gen_topk_kernel<4, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hq_lds(512));
-        (void)hipFuncSetAttribute((const void*)hq_beam_gen_topk_kernel<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hq_lds(1024));
-        (void)hipFuncSetAttribute((const void*)hq_beam_gen_topk_kernel<2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hq_lds(1024));
-    });
-    {
-        ProfScope ps_(prof_shape_name("hq_beam_gen_topk_kernel", (long long)rows, (long long)VT, K), st);
-        const int grid = (int)(nvr * nrb);
-        if (nbt == 4 && W <= 4) hq_beam_gen_launch<4, 4>(grid, lds, st, h16, frag, bias, VT, ntiles, rows, K, nvr, (int)nrb, W, pval, pidx, pm, ps);
-        else if (nbt == 4) hq_beam_gen_launch<4, 8>(grid, lds, st, h16, frag, bias, VT, ntiles, rows, K, nvr, (int)nrb, W, pval, pidx, pm, ps);
-        else if (W <= 4) hq_beam_gen_launch<2, 4>(grid, lds, st, h16, frag, bias, VT, ntiles, rows, K, nvr, (int)nrb, W, pval, pidx, pm, ps);
-        else hq_beam_gen_launch<2, 8>(grid, lds, st, h16, frag, bias, VT, ntiles, rows, K, nvr, (int)nrb, W, pval, pidx, pm, ps);
-    }
-    NIR_CHECK_LAUNCH("hq_beam_gen_topk_kernel");
-    return 0;
+    const int nvr = hq_nvr(nrb, (VT + 15) / 16);
+    return beam_gen_launch<BeamRowsSplit, false>("hq_beam_gen_topk_kernel", nvr, nbt, nvr * nrb, h16, frag, bias, VT, rows, K, W, p, st);
 }
 // psum given: the PAD form, (max, sum) apart in lse / psum
 static int launch_beam_row_topk(const float* logits, int64_t VT, int64_t rows, int W, float* top_val, int* top_idx, float* lse, hipStream_t st,
@@ -912,21 +797,21 @@ static bool beam_dims_ok(int W, int64_t VT) { return W >= 1 && W <= NIR_BEAM_MAX
 // partials of the PAD-substituting generator top-k (fused: gen_frag given; plain: GEMM into `logits` + the row kernel, one part per row, its sum
 // in ps) -> acg_beam_row_kernel.  ps is needed in both forms.
 static int launch_acg_beam_gen_select(const float* o, int64_t R, int64_t nsrc, int K, const float* gen_w, const float* gen_b, const void* gen_frag,
-                                      int64_t VT, int W, float* logits, float* pval, int* pidx, float* pm, float* ps, const float* copy_w,
-                                      const float* copy_b, const float* attn, int64_t attn_stride, const int64_t* lens, int QL, const int64_t* map,
-                                      const int64_t* e2t, int CV, const int* finished, float* top_val, int* top_idx, hipStream_t st) {
+                                      int64_t VT, int W, float* logits, const BeamPartials& p, const float* copy_w, const float* copy_b,
+                                      const float* attn, int64_t attn_stride, const int64_t* lens, int QL, const int64_t* map, const int64_t* e2t, int CV,
+                                      const int* finished, float* top_val, int* top_idx, hipStream_t st) {
     int nparts = 1;
     if (gen_frag) {
         nparts = beam_nparts(R, K, VT);
-        NIR_PROPAGATE(launch_beam_gen_topk(o, gen_frag, gen_b, VT, R, K, W, pval, pidx, pm, ps, st, true));
+        NIR_PROPAGATE(launch_beam_gen_topk(o, gen_frag, gen_b, VT, R, K, W, p, st, true));
     } else {
         NIR_PROPAGATE(launch_linear(o, K, nullptr, nullptr, 0, 0, 0, gen_w, K, gen_b, nullptr, logits, VT, R, (int)VT, K, NIR_ACT_NONE, st));
-        NIR_PROPAGATE(launch_beam_row_topk(logits, VT, R, W, pval, pidx, pm, st, ps));
+        NIR_PROPAGATE(launch_beam_row_topk(logits, VT, R, W, p.pval, p.pidx, p.pm, st, p.ps));
     }
     {
         ProfScope ps_("acg_beam_row_kernel", st);
-        hipLaunchKernelGGL(acg_beam_row_kernel, dim3((unsigned)R), dim3(64), (size_t)2 * CV * sizeof(float), st, o, K, gen_w, gen_b, VT, pval, pidx, pm, ps,
-                           nparts, R, nsrc, W, copy_w, copy_b, attn, attn_stride, lens, QL, map, e2t, CV, finished, top_val, top_idx);
+        hipLaunchKernelGGL(acg_beam_row_kernel, dim3((unsigned)R), dim3(64), (size_t)2 * CV * sizeof(float), st, o, K, gen_w, gen_b, VT, p.pval, p.pidx, p.pm,
+                           p.ps, nparts, R, nsrc, W, copy_w, copy_b, attn, attn_stride, lens, QL, map, e2t, CV, finished, top_val, top_idx);
     }
     NIR_CHECK_LAUNCH("acg_beam_row_kernel");
     return 0;
@@ -943,38 +828,89 @@ static int launch_acg_beam_select(const float* top_val, const int* top_idx, cons
 }
 static bool acg_beam_dims_ok(int QL, int CV, int64_t VT) { return acg_dims_ok(QL, CV) && VT + CV < 0x7FFFFFFFLL; }
 
+// ---- the tail of every search, on the host ---------------------------------------------------------------------------------------------------
+// The beam's own buffers, behind a decoder's step buffers in its workspace, and the launches on them.  B source rows with W beams each are the
+// R = B W decode rows (row k B + b); a step reads state slot 0 (the reordered one) and writes slot 1.
+struct BeamTail {
+    int64_t B, R;
+    int W, max_len, nparts;                           // nparts: partials a row of the top-k producer (1: the row kernel, which writes no sums)
+    BeamPartials part;
+    int64_t* tgt;                                     // [R] the source-side ids the next step reads
+    float* cum;                                       // [B, W]
+    int *fin, *bp, *tok;                              // [B, W]; [max_len][B][W] each -- bp is the caller's `backptr` where given
+
+    // takes the partials, tgt, cum, fin, (bp,) tok, in this order; sums: the producer writes ps
+    void carve(Workspace& a, int64_t B_, int W_, int max_len_, int nparts_, bool sums, int32_t* backptr) {
+        B = B_, W = W_, max_len = max_len_, nparts = nparts_, R = B_ * W_;
+        part.take(a, (size_t)nparts, R, W, sums);
+        tgt = a.take<int64_t>((size_t)R);
+        cum = a.take<float>((size_t)R);
+        fin = a.take<int>((size_t)R);
+        bp = backptr ? backptr : a.take<int>((size_t)max_len * R);
+        tok = a.take<int>((size_t)max_len * R);
+    }
+    // of every source row the first beam alone is alive (tgt is the caller's to fill: a stepper does it with its own launch)
+    int begin(hipStream_t st) const {
+        hipLaunchKernelGGL(beam_init_kernel, g1(R), dim3(256), 0, st, cum, fin, R, W);
+        NIR_CHECK_LAUNCH("beam_init_kernel");
+        return 0;
+    }
+    // the partials of the generator over x [R, K]: the fused kernel, or the fp32 GEMM into logits + one workgroup per row
+    int gen(bool fused, const float* x, int K, const float* gen_w, const float* gen_b, const void* gen_frag, int64_t VT, float* logits, hipStream_t st) const {
+        if (fused) return launch_beam_gen_topk(x, gen_frag, gen_b, VT, R, K, W, part, st);
+        NIR_PROPAGATE(launch_linear(x, K, nullptr, nullptr, 0, 0, 0, gen_w, K, gen_b, nullptr, logits, VT, R, (int)VT, K, NIR_ACT_NONE, st));
+        return launch_beam_row_topk(logits, VT, R, W, part.pval, part.pidx, part.pm, st);
+    }
+    int select(int step, int64_t VT, const int64_t* tgt2src, int64_t V, hipStream_t st) const {
+        return launch_beam_select(part.pval, part.pidx, part.pm, part.ps, nparts, B, W, VT, tgt2src, V, cum, fin, bp + (int64_t)step * R,
+                                  tok + (int64_t)step * R, tgt, st);
+    }
+    // behind all steps but the last: the state shuffle from slot 1 into slot 0 (c / h16 NULL: no such state)
+    int reorder(int step, int H, float* const* h, float* const* c, float* const* h16, hipStream_t st) const {
+        if (step + 1 >= max_len) return 0;
+        return launch_beam_reorder(bp + (int64_t)step * R, B, W, H, h[1], h[0], c ? c[1] : nullptr, c ? c[0] : nullptr, h16 ? h16[1] : nullptr,
+                                   h16 ? h16[0] : nullptr, st);
+    }
+    // the backtrack; attn_ws [max_len][R][QL] given: with the attention rows of every step, one wave per output
+    int end(int64_t* predictions, float* scores, int64_t* lengths, hipStream_t st, const float* attn_ws = nullptr, int QL = 0,
+            float* attentions = nullptr) const {
+        const char* name = attn_ws ? "beam_backtrack_kernel" : "beam_backtrack_tokens_kernel";
+        {
+            ProfScope ps_(name, st);
+            if (attn_ws)
+                hipLaunchKernelGGL(beam_backtrack_kernel, dim3((unsigned)R), dim3(64), 0, st, tok, bp, attn_ws, cum, B, W, max_len, QL, predictions, scores,
+                                   lengths, attentions);
+            else
+                hipLaunchKernelGGL(beam_backtrack_tokens_kernel, g1(R), dim3(256), 0, st, tok, bp, cum, B, W, max_len, predictions, scores, lengths);
+        }
+        NIR_CHECK_LAUNCH(name);
+        return 0;
+    }
+};
+
 struct BeamPlan {
     S2sStepBufs s;                                    // the stepper's buffers, over R = B W decode rows
-    float *pval, *pm, *ps, *cum, *attn;
-    int *pidx, *fin, *bp, *tok;
+    BeamTail t;
+    float* attn;                                      // [max_len][R][QL] the attention rows of every step
     float *tval, *csb, *cq, *ccat, *cattn;            // ACG only: the rows' lists; a copy attention of its own
     int* tidx;
-    int nparts;
     size_t bytes;
 };
 // acg: 0 = Seq2seq, 1 = ACG with reuse_copy_attn, 2 = ACG with a copy attention of its own (its buffers lie behind everything Seq2seq's plan holds)
 static BeamPlan beam_plan(void* ws, size_t cap, int64_t B, int QL, int W, int max_len, int H, int64_t VT, int attn_type, bool fused, int cell,
-                          bool step16, bool own_bp, int acg = 0) {
+                          bool step16, int32_t* backptr, int acg = 0) {
     Workspace a(ws, cap);
     BeamPlan p;
     const int64_t R = B * W;
-    p.nparts = fused ? beam_nparts(R, H, VT) : 1;
     p.s = s2s_step_bufs(a, R, B, QL, H, VT, attn_type, fused, cell, step16);               // (the fp16 term pairs with the fp16-term step only)
-    p.pval = a.take<float>((size_t)p.nparts * R * W);
-    p.pidx = a.take<int>((size_t)p.nparts * R * W);
-    p.pm = a.take<float>((size_t)p.nparts * R);
-    p.ps = a.take<float>(fused ? (size_t)p.nparts * R : 0);
-    p.s.tgt = a.take<int64_t>((size_t)R);
-    p.cum = a.take<float>((size_t)R);
-    p.fin = a.take<int>((size_t)R);
-    p.bp = a.take<int>(own_bp ? (size_t)max_len * R : 0);                                  // (the caller's `backptr` serves when given)
-    p.tok = a.take<int>((size_t)max_len * R);
+    p.t.carve(a, B, W, max_len, fused ? beam_nparts(R, H, VT) : 1, fused, backptr);
+    p.s.tgt = p.t.tgt;
     p.attn = a.take<float>((size_t)max_len * R * QL);
     if (cell == S2S_CELL_GRU) p.s.gru = a.take<float>(gru_step_scratch_floats(R, H));
     p.tval = p.csb = p.cq = p.ccat = p.cattn = nullptr;
     p.tidx = nullptr;
     if (acg) {
-        if (!fused) p.ps = a.take<float>((size_t)R);                                       // the plain row kernel's sums
+        if (!fused) p.t.part.ps = a.take<float>((size_t)R);                                // the plain row kernel's sums
         p.tval = a.take<float>((size_t)R * W);
         p.tidx = a.take<int>((size_t)R * W);
     }
@@ -991,7 +927,7 @@ static size_t beam_decode_workspace_bytes(int64_t B, int QL, int W, int max_len,
                                           const AcgDecode* acg = nullptr) {
     if (!s2s_weights_ok(w) || B < 0 || QL <= 0 || max_len <= 0 || !beam_dims_ok(W, w->VT)) return 0;
     if (acg && (!acg_weights_ok(w, acg) || !acg_beam_dims_ok(QL, acg->CV, w->VT))) return 0;
-    return beam_plan(nullptr, 0, B, QL, W, max_len, w->H, w->VT, w->attn_type, s2s_fused(w), cell, s2s_step16(w), true,
+    return beam_plan(nullptr, 0, B, QL, W, max_len, w->H, w->VT, w->attn_type, s2s_fused(w), cell, s2s_step16(w), nullptr,
                      acg ? (acg->cw->reuse_copy_attn ? 1 : 2) : 0).bytes;
 }
 
@@ -1014,18 +950,17 @@ static int s2s_beam_decode(const float* dec_h, const float* dec_c, const float* 
     }
     const int H = w->H;
     const bool fused = s.fused, step16 = s.step16, gru = cell == S2S_CELL_GRU;
-    BeamPlan p = beam_plan(workspace, workspace_bytes, B, QL, W, max_len, H, w->VT, w->attn_type, fused, cell, step16, backptr == nullptr,
-                           acg ? (own_copy_attn ? 2 : 1) : 0);
+    const BeamPlan p = beam_plan(workspace, workspace_bytes, B, QL, W, max_len, H, w->VT, w->attn_type, fused, cell, step16, backptr,
+                                 acg ? (own_copy_attn ? 2 : 1) : 0);
     if (!workspace || p.bytes > workspace_bytes) {
         set_error("beam_seq2seq_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
         return NIR_ERR_WORKSPACE;
     }
     if (B == 0) return 0;
+    const BeamTail& t = p.t;
     s.b = p.s;
     NIR_PROPAGATE(s.prepare(dec_h, bos, p.s.h16[0]));
-    hipLaunchKernelGGL(beam_init_kernel, g1(R), dim3(256), 0, st, p.cum, p.fin, R, W);
-    NIR_CHECK_LAUNCH("beam_init_kernel");
-    int* bp = backptr ? backptr : p.bp;
+    NIR_PROPAGATE(t.begin(st));
     const float* hp = dec_h;
     const float* cp = dec_c;
     const bool mlp = w->attn_type == NIR_S2S_ATTN_MLP;
@@ -1036,9 +971,7 @@ static int s2s_beam_decode(const float* dec_h, const float* dec_c, const float* 
         csb = p.csb;
     }
     for (int step = 0; step < max_len; ++step) {
-        float* hn = p.s.h[1];
-        float* cn = p.s.c[1];
-        NIR_PROPAGATE(s.step(hp, cp, hn, cn, p.s.h16[0], p.s.h16[1], p.attn + (int64_t)step * R * QL, QL));
+        NIR_PROPAGATE(s.step(hp, cp, p.s.h[1], p.s.c[1], p.s.h16[0], p.s.h16[1], p.attn + (int64_t)step * R * QL, QL));
         if (acg) {
             // ACG's tail: (a second attention whose query is the attentional output,) the W best of every row's collapsed extended distribution,
             // the selection over the source row's W W candidates
@@ -1050,34 +983,20 @@ static int s2s_beam_decode(const float* dec_h, const float* dec_c, const float* 
                 NIR_PROPAGATE(launch_attend(mlp ? p.cq : p.s.ah, p.s.ah, memory_bank, csb, acg->cw->attn_v, source_len, R, QL, H, mlp, p.ccat, p.cattn, QL, st, B));
                 ca = p.cattn;
             }
-            NIR_PROPAGATE(launch_acg_beam_gen_select(p.s.ah, R, B, H, w->gen_w, w->gen_b, fused ? w->gen_frag : nullptr, w->VT, W, p.s.logits, p.pval, p.pidx,
-                                                     p.pm, p.ps, acg->cw->copy_w, acg->cw->copy_b, ca, QL, source_len, QL, acg->src_map_idx, acg->ext2tgt,
-                                                     acg->CV, p.fin, p.tval, p.tidx, st));
-            NIR_PROPAGATE(launch_acg_beam_select(p.tval, p.tidx, nullptr, B, W, w->VT, acg->CV, tgt2src, acg->ext2src, V, p.cum, p.fin, bp + (int64_t)step * R,
-                                                 p.tok + (int64_t)step * R, p.s.tgt, st));
-        } else if (fused) {
-            NIR_PROPAGATE(launch_beam_gen_topk(p.s.ah, w->gen_frag, w->gen_b, w->VT, R, H, W, p.pval, p.pidx, p.pm, p.ps, st));
+            NIR_PROPAGATE(launch_acg_beam_gen_select(p.s.ah, R, B, H, w->gen_w, w->gen_b, fused ? w->gen_frag : nullptr, w->VT, W, p.s.logits, t.part,
+                                                     acg->cw->copy_w, acg->cw->copy_b, ca, QL, source_len, QL, acg->src_map_idx, acg->ext2tgt, acg->CV, t.fin,
+                                                     p.tval, p.tidx, st));
+            NIR_PROPAGATE(launch_acg_beam_select(p.tval, p.tidx, nullptr, B, W, w->VT, acg->CV, tgt2src, acg->ext2src, V, t.cum, t.fin, t.bp + (int64_t)step * R,
+                                                 t.tok + (int64_t)step * R, t.tgt, st));
         } else {
-            NIR_PROPAGATE(launch_linear(p.s.ah, H, nullptr, nullptr, 0, 0, 0, w->gen_w, H, w->gen_b, nullptr, p.s.logits, w->VT, R, (int)w->VT, H, NIR_ACT_NONE,
-                                        st));
-            NIR_PROPAGATE(launch_beam_row_topk(p.s.logits, w->VT, R, W, p.pval, p.pidx, p.pm, st));
+            NIR_PROPAGATE(t.gen(fused, p.s.ah, H, w->gen_w, w->gen_b, w->gen_frag, w->VT, p.s.logits, st));
+            NIR_PROPAGATE(t.select(step, w->VT, tgt2src, V, st));
         }
-        if (!acg)
-            NIR_PROPAGATE(launch_beam_select(p.pval, p.pidx, p.pm, fused ? p.ps : nullptr, p.nparts, B, W, w->VT, tgt2src, V, p.cum, p.fin,
-                                             bp + (int64_t)step * R, p.tok + (int64_t)step * R, p.s.tgt, st));
-        if (step + 1 < max_len)
-            NIR_PROPAGATE(launch_beam_reorder(bp + (int64_t)step * R, B, W, H, hn, p.s.h[0], gru ? nullptr : cn, gru ? nullptr : p.s.c[0],
-                                              step16 ? p.s.h16[1] : nullptr, step16 ? p.s.h16[0] : nullptr, st));
+        NIR_PROPAGATE(t.reorder(step, H, p.s.h, gru ? nullptr : p.s.c, step16 ? p.s.h16 : nullptr, st));
         hp = p.s.h[0];
         cp = p.s.c[0];
     }
-    {
-        ProfScope ps_("beam_backtrack_kernel", st);
-        hipLaunchKernelGGL(beam_backtrack_kernel, dim3((unsigned)R), dim3(64), 0, st, p.tok, bp, p.attn, p.cum, B, W, max_len, QL, predictions, scores, lengths,
-                           attentions);
-    }
-    NIR_CHECK_LAUNCH("beam_backtrack_kernel");
-    return 0;
+    return t.end(predictions, scores, lengths, st, p.attn, QL, attentions);
 }
 
 
@@ -1087,100 +1006,28 @@ static int s2s_beam_decode(const float* dec_h, const float* dec_c, const float* 
 // decode: beam row r = k Bd + i reads what decode row i reads (memory bank rowmap[i], session term i).  Nothing is repeated by the caller.
 // =================================================================================================================================================
 
-// out row r = in row r % Bd for the two states (H4 float4 per row), and map_out[r] = map_in[r % Bd] (map_in NULL: no map)
-__global__ __launch_bounds__(256) void beam_repeat_kernel(const float4* __restrict__ h_in, const float4* __restrict__ c_in, int64_t Bd, int H4,
-                                                          float4* __restrict__ h_out, float4* __restrict__ c_out, const int64_t* __restrict__ map_in,
-                                                          int64_t* __restrict__ map_out) {
-    const int64_t r = blockIdx.x, i = r % Bd;
-    for (int f = threadIdx.x; f < H4; f += 256) {
-        h_out[r * H4 + f] = h_in[i * H4 + f];
-        c_out[r * H4 + f] = c_in[i * H4 + f];
-    }
-    if (map_in && threadIdx.x == 0) map_out[r] = map_in[i];
-}
-
-// The backtrack without attention rows: one thread per output (source row b, output beam j).
-__global__ __launch_bounds__(256) void beam_backtrack_tokens_kernel(const int* __restrict__ tok, const int* __restrict__ bp, const float* __restrict__ cum,
-                                                                    int64_t B, int W, int max_len, int64_t* __restrict__ pred, float* __restrict__ scores,
-                                                                    int64_t* __restrict__ lengths) {
-    const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;        // b W + j
-    if (o >= B * W) return;
-    const int64_t b = o / W;
-    int k = (int)(o - b * W);
-    int len = max_len;
-    for (int t = max_len - 1; t >= 0; --t) {
-        const int64_t slot = ((int64_t)t * B + b) * W + k;
-        const int tk = tok[slot];
-        int src = bp[slot];
-        src = src < 0 ? 0 : (src >= W ? W - 1 : src);
-        if (tk == NIR_BEAM_EOS) len = t + 1;
-        pred[o * max_len + t] = tk;
-        k = src;
-    }
-    scores[o] = cum[o];
-    lengths[o] = len;
-}
-
-// The beam's own buffers behind a decoder's step buffers (the tail of BeamPlan without the attention rows).
-struct SessBeamBufs {
-    float *pval, *pm, *ps, *cum, *logits;
-    int *pidx, *fin, *bp, *tok;
-    int64_t* tgt;
-    int nparts;
-};
-// (nparts >= 0: the partial count of another fused producer -- hq_beam_gen_topk_kernel's grid)
-static SessBeamBufs sess_beam_bufs(Workspace& a, int64_t R, int W, int max_len, int K, int64_t VT, bool fused, bool own_bp, int nparts = -1) {
-    SessBeamBufs p;
-    p.nparts = fused ? (nparts >= 0 ? nparts : beam_nparts(R, K, VT)) : 1;
-    p.logits = a.take<float>(fused ? 0 : (size_t)R * VT);
-    p.pval = a.take<float>((size_t)p.nparts * R * W);
-    p.pidx = a.take<int>((size_t)p.nparts * R * W);
-    p.pm = a.take<float>((size_t)p.nparts * R);
-    p.ps = a.take<float>(fused ? (size_t)p.nparts * R : 0);
-    p.tgt = a.take<int64_t>((size_t)R);
-    p.cum = a.take<float>((size_t)R);
-    p.fin = a.take<int>((size_t)R);
-    p.bp = a.take<int>(own_bp ? (size_t)max_len * R : 0);
-    p.tok = a.take<int>((size_t)max_len * R);
-    return p;
-}
-// (lse, top-W) partials of the generator over x [R, K]: the fused kernel, or the fp32 GEMM into logits + one workgroup per row
-static int sess_beam_gen(const SessBeamBufs& p, bool fused, const float* x, int64_t R, int K, const float* gen_w, const float* gen_b, const void* gen_frag,
-                         int64_t VT, int W, hipStream_t st) {
-    if (fused) return launch_beam_gen_topk(x, gen_frag, gen_b, VT, R, K, W, p.pval, p.pidx, p.pm, p.ps, st);
-    NIR_PROPAGATE(launch_linear(x, K, nullptr, nullptr, 0, 0, 0, gen_w, K, gen_b, nullptr, p.logits, VT, R, (int)VT, K, NIR_ACT_NONE, st));
-    return launch_beam_row_topk(p.logits, VT, R, W, p.pval, p.pidx, p.pm, st);
-}
-// select + (all steps but the last) the state shuffle from slot 1 into slot 0
-static int sess_beam_tail(const SessBeamBufs& p, bool fused, int step, int max_len, int64_t Bd, int W, int H, int64_t VT, const int64_t* tgt2src, int64_t V,
-                          int* bp, float* const* h, float* const* c, float* const* h16, bool step16, hipStream_t st) {
-    const int64_t R = Bd * W;
-    NIR_PROPAGATE(launch_beam_select(p.pval, p.pidx, p.pm, fused ? p.ps : nullptr, p.nparts, Bd, W, VT, tgt2src, V, p.cum, p.fin, bp + (int64_t)step * R,
-                                     p.tok + (int64_t)step * R, p.tgt, st));
-    if (step + 1 < max_len)
-        NIR_PROPAGATE(launch_beam_reorder(bp + (int64_t)step * R, Bd, W, H, h[1], h[0], c[1], c[0], step16 ? h16[1] : nullptr, step16 ? h16[0] : nullptr, st));
-    return 0;
-}
-static int sess_beam_begin(const SessBeamBufs& p, const float* dec_h, const float* dec_c, int64_t Bd, int W, int H, float* h0, float* c0, float* h16first,
-                           bool step16, const int64_t* map_in, int64_t* map_out, int64_t bos, hipStream_t st) {
-    const int64_t R = Bd * W;
+// the first state of every beam row (and the repeated row map) into slot 0; h16first given: and its fp16 term pairs, for the fp16-term step
+static int launch_beam_repeat(const float* dec_h, const float* dec_c, int64_t Bd, int64_t R, int H, float* h0, float* c0, float* h16first,
+                              const int64_t* map_in, int64_t* map_out, hipStream_t st) {
     hipLaunchKernelGGL(beam_repeat_kernel, dim3((unsigned)R), dim3(256), 0, st, (const float4*)dec_h, (const float4*)dec_c, Bd, H / 4, (float4*)h0, (float4*)c0,
                        map_in, map_out);
     NIR_CHECK_LAUNCH("beam_repeat_kernel");
-    if (step16) NIR_PROPAGATE(launch_h16_pack(h0, R * H, reinterpret_cast<_Float16*>(h16first), st));
-    NIR_PROPAGATE(launch_fill_i64(p.tgt, bos, R, st));
-    hipLaunchKernelGGL(beam_init_kernel, g1(R), dim3(256), 0, st, p.cum, p.fin, R, W);
-    NIR_CHECK_LAUNCH("beam_init_kernel");
+    if (h16first) NIR_PROPAGATE(launch_h16_pack(h0, R * H, reinterpret_cast<_Float16*>(h16first), st));
     return 0;
 }
-static int sess_beam_end(const SessBeamBufs& p, const int* bp, int64_t Bd, int W, int max_len, int64_t* predictions, float* scores, int64_t* lengths,
-                         hipStream_t st) {
-    {
-        ProfScope ps_("beam_backtrack_tokens_kernel", st);
-        hipLaunchKernelGGL(beam_backtrack_tokens_kernel, g1(Bd * W), dim3(256), 0, st, p.tok, bp, p.cum, Bd, W, max_len, predictions, scores, lengths);
+// the token-fed LSTM step of these decoders over the R beam rows, every step from state slot 0 (the reordered one) into slot 1; step16: the
+// fp16-term step on gate_fold and whh_frag, with the states' term pairs h16
+static LstmStepArgs beam_lstm_step_args(const float* table, const int64_t* tgt, int E, const float* w_ih, const float* w_hh, const float* b_ih,
+                                        const float* b_hh, bool step16, const float* gate_fold, const void* whh_frag, int64_t R, int H, float* const* h,
+                                        float* const* c, float* const* h16) {
+    LstmStepArgs a = LstmStepArgs::token_fed(table, tgt, E, w_ih, w_hh, b_ih, b_hh, R, H);
+    a.hprev[0] = h[0]; a.cprev[0] = c[0]; a.hnext[0] = h[1]; a.cnext[0] = c[1];
+    if (step16) {
+        a.fold_token_fed(gate_fold, whh_frag);
+        a.h16prev[0] = reinterpret_cast<const _Float16*>(h16[0]);
+        a.h16next[0] = reinterpret_cast<_Float16*>(h16[1]);
     }
-    NIR_CHECK_LAUNCH("beam_backtrack_tokens_kernel");
-    return 0;
+    return a;
 }
 
 // ---- CARS ----------------------------------------------------------------------------------------------------------------------------------
@@ -1188,14 +1035,14 @@ static int sess_beam_end(const SessBeamBufs& p, const int* bp, int64_t Bd, int W
 // entry stays as it is): prepare once -- the banks mem / memq over the source rows, the session projection over the R rows through the
 // repeated rowmap -- then per step lstm step, (linear_in,) dec_attend, linear_out + tanh, pred1 + session term.
 struct CarsBeamPlan {
-    float *mem, *memq, *sess, *h[2], *c[2], *h16[2], *qv, *cat, *ah, *p1;
+    float *mem, *memq, *sess, *h[2], *c[2], *h16[2], *qv, *cat, *ah, *p1, *logits;        // (logits: the plain generator's)
     int64_t* rowmap;
-    SessBeamBufs b;
+    BeamTail t;
     size_t bytes;
 };
 static bool cars_beam_step16(const nir_cars_decoder_weights* w) { return w->rnn_gate_fold && w->rnn_whh_frag && w->HD % 32 == 0 && !tun(g_tun.exact_f32); }
 static CarsBeamPlan cars_beam_plan(void* ws, size_t cap, int64_t rows_src, int64_t Bd, int QL, int W, int max_len, const nir_cars_decoder_weights* w,
-                                   bool fused, bool own_bp) {
+                                   bool fused, int32_t* backptr) {
     Workspace a(ws, cap);
     CarsBeamPlan p;
     const int64_t R = Bd * W;
@@ -1211,7 +1058,8 @@ static CarsBeamPlan cars_beam_plan(void* ws, size_t cap, int64_t rows_src, int64
     p.ah = a.take<float>((size_t)R * HD);
     p.p1 = a.take<float>((size_t)R * P);
     p.rowmap = a.take<int64_t>((size_t)R);
-    p.b = sess_beam_bufs(a, R, W, max_len, P, w->VT, fused, own_bp);
+    p.logits = a.take<float>(fused ? 0 : (size_t)R * w->VT);
+    p.t.carve(a, Bd, W, max_len, fused ? beam_nparts(R, P, w->VT) : 1, fused, backptr);
     p.bytes = align_up(a.off, 256);
     return p;
 }
@@ -1225,7 +1073,7 @@ static bool cars_beam_weights_ok(const nir_cars_decoder_weights* w) {
 extern "C" size_t nir_beam_cars_decode_workspace_bytes(int64_t rows_src, int64_t Bd, int QL, int W, int max_len, const nir_cars_decoder_weights* w, int fused) {
     using namespace nir;
     if (!cars_beam_weights_ok(w) || rows_src < 0 || Bd < 0 || QL <= 0 || max_len <= 0 || !beam_dims_ok(W, w->VT)) return 0;
-    return cars_beam_plan(nullptr, 0, rows_src, Bd, QL, W, max_len, w, fused && s2s_fusable(w->P, w->VT) && !tun(g_tun.exact_f32), true).bytes;
+    return cars_beam_plan(nullptr, 0, rows_src, Bd, QL, W, max_len, w, fused && s2s_fusable(w->P, w->VT) && !tun(g_tun.exact_f32), nullptr).bytes;
 }
 
 extern "C" int nir_beam_cars_decode(const float* dec_h, const float* dec_c, const float* encoded_source, const int64_t* source_len, int64_t rows_src, int QL,
@@ -1245,7 +1093,8 @@ extern "C" int nir_beam_cars_decode(const float* dec_h, const float* dec_c, cons
     const int HD = w->HD, P = w->P;
     const int64_t R = Bd * W, VT = w->VT;
     const bool fused = s2s_gen_fused(gen_frag, P, VT), foldq = w->attn_q_w != nullptr, step16 = cars_beam_step16(w);
-    CarsBeamPlan p = cars_beam_plan(workspace, workspace_bytes, rows_src, Bd, QL, W, max_len, w, fused, backptr == nullptr);
+    const CarsBeamPlan p = cars_beam_plan(workspace, workspace_bytes, rows_src, Bd, QL, W, max_len, w, fused, backptr);
+    const BeamTail& t = p.t;
     if (!workspace || p.bytes > workspace_bytes) {
         set_error("beam_cars_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
         return NIR_ERR_WORKSPACE;
@@ -1257,56 +1106,97 @@ extern "C" int nir_beam_cars_decode(const float* dec_h, const float* dec_c, cons
     if (foldq)
         NIR_PROPAGATE(launch_linear(encoded_source, w->DQ, nullptr, nullptr, 0, 0, 0, w->attn_q_w, w->DQ, nullptr, nullptr, p.memq, HD, rows_src * QL, HD, w->DQ,
                                     NIR_ACT_NONE, st));
-    NIR_PROPAGATE(sess_beam_begin(p.b, dec_h, dec_c, Bd, W, HD, p.h[0], p.c[0], p.h16[0], step16, rowmap, p.rowmap, bos, st));
+    NIR_PROPAGATE(launch_beam_repeat(dec_h, dec_c, Bd, R, HD, p.h[0], p.c[0], step16 ? p.h16[0] : nullptr, rowmap, p.rowmap, st));
+    NIR_PROPAGATE(launch_fill_i64(t.tgt, bos, R, st));
+    NIR_PROPAGATE(t.begin(st));
     if (w->KS > 0)
         NIR_PROPAGATE(launch_linear(nullptr, 0, p.rowmap, session_cat, w->KS, 1, 1, w->sess_w, w->KS, nullptr, nullptr, p.sess, P, R, P, w->KS, NIR_ACT_NONE, st));
-    LstmStepArgs a = LstmStepArgs::token_fed(table, p.b.tgt, E, w->rnn_wih, w->rnn_whh, w->rnn_bih, w->rnn_bhh, R, HD);
-    if (step16) a.fold_token_fed(w->rnn_gate_fold, w->rnn_whh_frag);
-    int* bp = backptr ? backptr : p.b.bp;
+    const LstmStepArgs a = beam_lstm_step_args(table, t.tgt, E, w->rnn_wih, w->rnn_whh, w->rnn_bih, w->rnn_bhh, step16, w->rnn_gate_fold, w->rnn_whh_frag, R, HD,
+                                               p.h, p.c, p.h16);
+    float* hn = p.h[1];
     for (int step = 0; step < max_len; ++step) {
-        // a step reads state slot 0 (the reordered one) and writes slot 1
-        float* hn = p.h[1];
-        a.hprev[0] = p.h[0]; a.cprev[0] = p.c[0]; a.hnext[0] = hn; a.cnext[0] = p.c[1];
-        if (step16) {
-            a.h16prev[0] = reinterpret_cast<const _Float16*>(p.h16[0]);
-            a.h16next[0] = reinterpret_cast<_Float16*>(p.h16[1]);
-        }
         NIR_PROPAGATE(launch_lstm_step(a, 1, st));
         if (!foldq) NIR_PROPAGATE(launch_linear(hn, HD, nullptr, nullptr, 0, 0, 0, w->attn_in_w, HD, nullptr, nullptr, p.qv, HD, R, HD, HD, NIR_ACT_NONE, st));
         NIR_PROPAGATE(launch_dec_attend(foldq ? hn : p.qv, hn, p.mem, foldq ? p.memq : p.mem, p.rowmap, source_len, R, QL, HD, p.cat, st));
         NIR_PROPAGATE(launch_linear(p.cat, 2 * HD, nullptr, nullptr, 0, 0, 0, w->attn_out_w, 2 * HD, nullptr, nullptr, p.ah, HD, R, HD, 2 * HD, NIR_ACT_TANH, st));
         NIR_PROPAGATE(launch_linear_ex(p.ah, HD, nullptr, nullptr, 0, 0, 0, w->pred1_w, HD, nullptr, nullptr, p.p1, P, R, P, HD, NIR_ACT_NONE,
                                        w->KS > 0 ? p.sess : nullptr, P, st));
-        NIR_PROPAGATE(sess_beam_gen(p.b, fused, p.p1, R, P, w->pred2_w, nullptr, gen_frag, VT, W, st));
-        NIR_PROPAGATE(sess_beam_tail(p.b, fused, step, max_len, Bd, W, HD, VT, tgt2src, V, bp, p.h, p.c, p.h16, step16, st));
+        NIR_PROPAGATE(t.gen(fused, p.p1, P, w->pred2_w, nullptr, gen_frag, VT, p.logits, st));
+        NIR_PROPAGATE(t.select(step, VT, tgt2src, V, st));
+        NIR_PROPAGATE(t.reorder(step, HD, p.h, p.c, step16 ? p.h16 : nullptr, st));
     }
-    return sess_beam_end(p.b, bp, Bd, W, max_len, predictions, scores, lengths, st);
+    return t.end(predictions, scores, lengths, st);
 }
 
 // ---- the decoders without attention (M_MATCH_TENSOR, MNSRF): nir_decode_greedy_plain_folded's step over R rows ------------------------------------
 namespace nir {
 struct PlainBeamPlan {
-    float *h[2], *c[2], *h16[2];
-    SessBeamBufs b;
+    float *h[2], *c[2], *h16[2], *logits;             // (logits: the plain generator's)
+    BeamTail t;
     size_t bytes;
 };
-static PlainBeamPlan plain_beam_plan(void* ws, size_t cap, int64_t Bd, int H, int64_t VT, int W, int max_len, bool step16, bool fused, bool own_bp,
-                                     int nparts = -1) {
+// nparts: the partials a row of the producer -- fused: beam_nparts or hq_beam_nparts, else 1
+static PlainBeamPlan plain_beam_plan(void* ws, size_t cap, int64_t Bd, int H, int64_t VT, int W, int max_len, bool step16, bool fused, int nparts,
+                                     int32_t* backptr) {
     Workspace a(ws, cap);
     PlainBeamPlan p;
     const int64_t R = Bd * W;
     for (int k = 0; k < 2; ++k) { p.h[k] = a.take<float>((size_t)R * H); p.c[k] = a.take<float>((size_t)R * H); }
     for (int k = 0; k < 2; ++k) p.h16[k] = a.take<float>(step16 ? (size_t)R * H : 0);
-    p.b = sess_beam_bufs(a, R, W, max_len, H, VT, fused, own_bp, nparts);
+    p.logits = a.take<float>(fused ? 0 : (size_t)R * VT);
+    p.t.carve(a, Bd, W, max_len, nparts, fused, backptr);
     p.bytes = align_up(a.off, 256);
     return p;
+}
+// The search of both entries below, in the entry's `name`.  begin(p): the first state of every beam row into slot 0 (step16: and its term pairs
+// into h16[0]).  Per step: the token-fed LSTM step from slot 0 into slot 1, the partials of the new state -- fused: gen_fused(p), the entry's
+// producer; else the GEMM and the row kernel --, select, reorder.
+template <class Begin, class GenFused>
+static int plain_beam_decode(const char* name, int64_t Bd, int H, const float* table, int E, const float* w_ih, const float* w_hh, const float* b_ih,
+                             const float* b_hh, const float* gate_fold, const void* whh_frag, bool step16, const float* gen_w, const float* gen_b, int64_t VT,
+                             bool fused, int nparts, const int64_t* tgt2src, int64_t V, int64_t bos, int W, int max_len, void* workspace,
+                             size_t workspace_bytes, int64_t* predictions, float* scores, int64_t* lengths, int32_t* backptr, hipStream_t st, Begin begin,
+                             GenFused gen_fused) {
+    const int64_t R = Bd * W;
+    const PlainBeamPlan p = plain_beam_plan(workspace, workspace_bytes, Bd, H, VT, W, max_len, step16, fused, nparts, backptr);
+    if (!workspace || p.bytes > workspace_bytes) {
+        set_error("%s: workspace too small (%zu < %zu)", name, workspace_bytes, p.bytes);
+        return NIR_ERR_WORKSPACE;
+    }
+    if (Bd == 0) return 0;
+    const BeamTail& t = p.t;
+    NIR_PROPAGATE(begin(p));
+    NIR_PROPAGATE(launch_fill_i64(t.tgt, bos, R, st));
+    NIR_PROPAGATE(t.begin(st));
+    const LstmStepArgs s = beam_lstm_step_args(table, t.tgt, E, w_ih, w_hh, b_ih, b_hh, step16, gate_fold, whh_frag, R, H, p.h, p.c, p.h16);
+    for (int step = 0; step < max_len; ++step) {
+        NIR_PROPAGATE(launch_lstm_step(s, 1, st));
+        NIR_PROPAGATE(fused ? gen_fused(p) : t.gen(false, p.h[1], H, gen_w, gen_b, nullptr, VT, p.logits, st));
+        NIR_PROPAGATE(t.select(step, VT, tgt2src, V, st));
+        NIR_PROPAGATE(t.reorder(step, H, p.h, p.c, step16 ? p.h16 : nullptr, st));
+    }
+    return t.end(predictions, scores, lengths, st);
+}
+// The stand-alone top-k of a fused producer: gen(p) writes its partials, nparts a row, into the workspace; one wave per row merges them.
+template <class Gen>
+static int beam_gen_topk_finish(void* workspace, size_t workspace_bytes, int nparts, int64_t rows, int W, float* top_val, int32_t* top_idx, float* lse,
+                                hipStream_t st, Gen gen) {
+    Workspace a(workspace, workspace_bytes);
+    BeamPartials p;
+    p.take(a, (size_t)nparts, rows, W, true);
+    NIR_PROPAGATE(gen(p));
+    hipLaunchKernelGGL(beam_topk_finish_kernel, dim3((unsigned)rows), dim3(64), 0, st, p.pval, p.pidx, p.pm, p.ps, nparts, rows, W, top_val, top_idx, lse);
+    NIR_CHECK_LAUNCH("beam_topk_finish_kernel");
+    return 0;
 }
 }  // namespace nir
 
 extern "C" size_t nir_beam_plain_decode_workspace_bytes(int64_t Bd, int H, int64_t VT, int W, int max_len, int folded, int fused) {
     using namespace nir;
     if (Bd < 0 || H <= 0 || H % 4 || VT <= 0 || max_len <= 0 || !beam_dims_ok(W, VT)) return 0;
-    return plain_beam_plan(nullptr, 0, Bd, H, VT, W, max_len, folded && H % 32 == 0 && !tun(g_tun.exact_f32), fused && s2s_fusable(H, VT) && !tun(g_tun.exact_f32), true).bytes;
+    const bool fuse = fused && s2s_fusable(H, VT) && !tun(g_tun.exact_f32);
+    return plain_beam_plan(nullptr, 0, Bd, H, VT, W, max_len, folded && H % 32 == 0 && !tun(g_tun.exact_f32), fuse, fuse ? beam_nparts(Bd * W, H, VT) : 1, nullptr)
+        .bytes;
 }
 
 extern "C" int nir_beam_plain_decode(const float* dec_h, const float* dec_c, int64_t Bd, int H, const float* table, int64_t V, int E, const float* w_ih,
@@ -1323,27 +1213,11 @@ extern "C" int nir_beam_plain_decode(const float* dec_h, const float* dec_c, int
     NIR_REQUIRE(Bd * NIR_BEAM_MAX_W < 0x7FFFFFFFLL && VT < 0x7FFFFFF0LL, "beam_plain_decode: too many decode rows or target tokens");
     const int64_t R = Bd * W;
     const bool step16 = gate_fold && whh_frag && H % 32 == 0 && !tun(g_tun.exact_f32), fused = s2s_gen_fused(gen_frag, H, VT);
-    PlainBeamPlan p = plain_beam_plan(workspace, workspace_bytes, Bd, H, VT, W, max_len, step16, fused, backptr == nullptr);
-    if (!workspace || p.bytes > workspace_bytes) {
-        set_error("beam_plain_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
-        return NIR_ERR_WORKSPACE;
-    }
-    if (Bd == 0) return 0;
-    NIR_PROPAGATE(sess_beam_begin(p.b, dec_h, dec_c, Bd, W, H, p.h[0], p.c[0], p.h16[0], step16, nullptr, nullptr, bos, st));
-    LstmStepArgs s = LstmStepArgs::token_fed(table, p.b.tgt, E, w_ih, w_hh, b_ih, b_hh, R, H);
-    if (step16) s.fold_token_fed(gate_fold, whh_frag);
-    int* bp = backptr ? backptr : p.b.bp;
-    for (int step = 0; step < max_len; ++step) {
-        s.hprev[0] = p.h[0]; s.cprev[0] = p.c[0]; s.hnext[0] = p.h[1]; s.cnext[0] = p.c[1];
-        if (step16) {
-            s.h16prev[0] = reinterpret_cast<const _Float16*>(p.h16[0]);
-            s.h16next[0] = reinterpret_cast<_Float16*>(p.h16[1]);
-        }
-        NIR_PROPAGATE(launch_lstm_step(s, 1, st));
-        NIR_PROPAGATE(sess_beam_gen(p.b, fused, p.h[1], R, H, gen_w, gen_b, gen_frag, VT, W, st));
-        NIR_PROPAGATE(sess_beam_tail(p.b, fused, step, max_len, Bd, W, H, VT, tgt2src, V, bp, p.h, p.c, p.h16, step16, st));
-    }
-    return sess_beam_end(p.b, bp, Bd, W, max_len, predictions, scores, lengths, st);
+    return plain_beam_decode(
+        "beam_plain_decode", Bd, H, table, E, w_ih, w_hh, b_ih, b_hh, gate_fold, whh_frag, step16, gen_w, gen_b, VT, fused, fused ? beam_nparts(R, H, VT) : 1,
+        tgt2src, V, bos, W, max_len, workspace, workspace_bytes, predictions, scores, lengths, backptr, st,
+        [&](const PlainBeamPlan& p) { return launch_beam_repeat(dec_h, dec_c, Bd, R, H, p.h[0], p.c[0], step16 ? p.h16[0] : nullptr, nullptr, nullptr, st); },
+        [&](const PlainBeamPlan& p) { return p.t.gen(true, p.h[1], H, gen_w, gen_b, gen_frag, VT, nullptr, st); });
 }
 
 // ---- HredQS (include/neuroir_hredqs_beam.h): the plain decoder's beam over Bd = B S source rows in the reference's pairing,
@@ -1351,7 +1225,7 @@ extern "C" int nir_beam_plain_decode(const float* dec_h, const float* dec_c, int
 extern "C" size_t nir_beam_hredqs_gen_topk_workspace_bytes(int64_t rows, int K, int64_t VT, int W) {
     using namespace nir;
     if (rows <= 0 || !hq_fusable(K, VT) || !beam_dims_ok(W, VT)) return 0;
-    return (size_t)hq_beam_nparts(rows, K, VT) * rows * ((size_t)W * 8 + 8) + 4 * 256;
+    return beam_partials_bytes((size_t)hq_beam_nparts(rows, K, VT), rows, W, 4);
 }
 
 extern "C" int nir_beam_hredqs_gen_topk(const void* h16, int64_t rows, int K, const float* gen_b, const void* gen_frag, int64_t VT, int W, void* workspace,
@@ -1367,23 +1241,16 @@ extern "C" int nir_beam_hredqs_gen_topk(const void* h16, int64_t rows, int K, co
         set_error("beam_hredqs_gen_topk: workspace too small");
         return NIR_ERR_WORKSPACE;
     }
-    Workspace a(workspace, workspace_bytes);
-    const int nparts = hq_beam_nparts(rows, K, VT);
-    float* pval = a.take<float>((size_t)nparts * rows * W);
-    int* pidx = a.take<int>((size_t)nparts * rows * W);
-    float* pm = a.take<float>((size_t)nparts * rows);
-    float* ps = a.take<float>((size_t)nparts * rows);
-    NIR_PROPAGATE(launch_hq_beam_gen_topk((const _Float16*)h16, gen_frag, gen_b, VT, rows, K, W, pval, pidx, pm, ps, st));
-    hipLaunchKernelGGL(beam_topk_finish_kernel, dim3((unsigned)rows), dim3(64), 0, st, pval, pidx, pm, ps, nparts, rows, W, top_val, top_idx, lse);
-    NIR_CHECK_LAUNCH("beam_topk_finish_kernel");
-    return 0;
+    return beam_gen_topk_finish(workspace, workspace_bytes, hq_beam_nparts(rows, K, VT), rows, W, top_val, top_idx, lse, st, [&](const BeamPartials& p) {
+        return launch_hq_beam_gen_topk((const _Float16*)h16, gen_frag, gen_b, VT, rows, K, W, p, st);
+    });
 }
 
 extern "C" size_t nir_beam_hredqs_decode_workspace_bytes(int64_t B, int64_t S, int W, int max_len, const nir_hredqs_decoder_weights* w) {
     using namespace nir;
     if (!hq_weights_ok(w) || B < 0 || S < 0 || max_len <= 0 || !beam_dims_ok(W, w->VT)) return 0;
     const bool fast = hq_fast(w);
-    return plain_beam_plan(nullptr, 0, B * S, w->H, w->VT, W, max_len, fast, fast, true, hq_beam_nparts(B * S * W, w->H, w->VT)).bytes;
+    return plain_beam_plan(nullptr, 0, B * S, w->H, w->VT, W, max_len, fast, fast, fast ? hq_beam_nparts(B * S * W, w->H, w->VT) : 1, nullptr).bytes;
 }
 
 extern "C" int nir_beam_hredqs_decode(const float* h_steps, const float* c_steps, int64_t B, int64_t S, const float* table, int64_t V, int E,
@@ -1402,37 +1269,19 @@ extern "C" int nir_beam_hredqs_decode(const float* h_steps, const float* c_steps
     const int H = w->H;
     const int64_t Bd = B * S, R = Bd * W, VT = w->VT;
     const bool fast = hq_fast(w);
-    PlainBeamPlan p = plain_beam_plan(workspace, workspace_bytes, Bd, H, VT, W, max_len, fast, fast, backptr == nullptr, hq_beam_nparts(R, H, VT));
-    if (!workspace || p.bytes > workspace_bytes) {
-        set_error("beam_hredqs_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
-        return NIR_ERR_WORKSPACE;
-    }
-    if (Bd == 0) return 0;
-    // pairing, repeat and split in one launch: every beam of source row i starts from step i / B of session i % B, in state slot 0
-    hipLaunchKernelGGL(hq_beam_begin_kernel, g1(R * H), dim3(256), 0, st, h_steps, c_steps, B, S, H, R * H, p.h[0], p.c[0],
-                       fast ? reinterpret_cast<_Float16*>(p.h16[0]) : nullptr);
-    NIR_CHECK_LAUNCH("hq_beam_begin_kernel");
-    NIR_PROPAGATE(launch_fill_i64(p.b.tgt, bos, R, st));
-    hipLaunchKernelGGL(beam_init_kernel, g1(R), dim3(256), 0, st, p.b.cum, p.b.fin, R, W);
-    NIR_CHECK_LAUNCH("beam_init_kernel");
-    LstmStepArgs s = LstmStepArgs::token_fed(table, p.b.tgt, E, w->rnn_wih, w->rnn_whh, w->rnn_bih, w->rnn_bhh, R, H);
-    if (fast) s.fold_token_fed(w->rnn_gate_fold, w->rnn_whh_frag);
-    int* bp = backptr ? backptr : p.b.bp;
-    for (int step = 0; step < max_len; ++step) {
-        // a step reads state slot 0 (the reordered one) and writes slot 1
-        s.hprev[0] = p.h[0]; s.cprev[0] = p.c[0]; s.hnext[0] = p.h[1]; s.cnext[0] = p.c[1];
-        if (fast) {
-            s.h16prev[0] = reinterpret_cast<const _Float16*>(p.h16[0]);
-            s.h16next[0] = reinterpret_cast<_Float16*>(p.h16[1]);
-        }
-        NIR_PROPAGATE(launch_lstm_step(s, 1, st));
-        if (fast)
-            NIR_PROPAGATE(launch_hq_beam_gen_topk(s.h16next[0], w->gen_frag, w->gen_b, VT, R, H, W, p.b.pval, p.b.pidx, p.b.pm, p.b.ps, st));
-        else
-            NIR_PROPAGATE(sess_beam_gen(p.b, false, p.h[1], R, H, w->gen_w, w->gen_b, nullptr, VT, W, st));
-        NIR_PROPAGATE(sess_beam_tail(p.b, fast, step, max_len, Bd, W, H, VT, tgt2src, V, bp, p.h, p.c, p.h16, fast, st));
-    }
-    return sess_beam_end(p.b, bp, Bd, W, max_len, predictions, scores, lengths, st);
+    return plain_beam_decode(
+        "beam_hredqs_decode", Bd, H, table, E, w->rnn_wih, w->rnn_whh, w->rnn_bih, w->rnn_bhh, w->rnn_gate_fold, w->rnn_whh_frag, fast, w->gen_w, w->gen_b, VT, fast,
+        fast ? hq_beam_nparts(R, H, VT) : 1, tgt2src, V, bos, W, max_len, workspace, workspace_bytes, predictions, scores, lengths, backptr, st,
+        [&](const PlainBeamPlan& p) {
+            // pairing, repeat and split in one launch: every beam of source row i starts from step i / B of session i % B
+            hipLaunchKernelGGL(hq_beam_begin_kernel, g1(R * H), dim3(256), 0, st, h_steps, c_steps, B, S, H, R * H, p.h[0], p.c[0],
+                               fast ? reinterpret_cast<_Float16*>(p.h16[0]) : nullptr);
+            NIR_CHECK_LAUNCH("hq_beam_begin_kernel");
+            return 0;
+        },
+        [&](const PlainBeamPlan& p) {
+            return launch_hq_beam_gen_topk(reinterpret_cast<const _Float16*>(p.h16[1]), w->gen_frag, w->gen_b, VT, R, H, W, p.t.part, st);
+        });
 }
 
 extern "C" size_t nir_beam_gen_topk_workspace_bytes(int64_t rows, int K, int64_t VT, int W, int fused) {
@@ -1440,7 +1289,7 @@ extern "C" size_t nir_beam_gen_topk_workspace_bytes(int64_t rows, int K, int64_t
     if (rows <= 0 || K <= 0 || !beam_dims_ok(W, VT)) return 0;
     if (!fused) return (size_t)rows * VT * sizeof(float) + 256;
     if (!s2s_fusable(K, VT)) return 0;
-    return (size_t)beam_nparts(rows, K, VT) * rows * ((size_t)W * 8 + 8) + 4 * 256;
+    return beam_partials_bytes((size_t)beam_nparts(rows, K, VT), rows, W, 4);
 }
 
 extern "C" int nir_beam_gen_topk(const float* x, int64_t rows, int K, const float* gen_w, const float* gen_b, const void* gen_frag, int64_t VT, int W,
@@ -1457,18 +1306,11 @@ extern "C" int nir_beam_gen_topk(const float* x, int64_t rows, int K, const floa
         set_error("beam_gen_topk: workspace too small");
         return NIR_ERR_WORKSPACE;
     }
+    if (fused)
+        return beam_gen_topk_finish(workspace, workspace_bytes, beam_nparts(rows, K, VT), rows, W, top_val, top_idx, lse, st, [&](const BeamPartials& p) {
+            return launch_beam_gen_topk(x, gen_frag, gen_b, VT, rows, K, W, p, st);
+        });
     Workspace a(workspace, workspace_bytes);
-    if (fused) {
-        const int nparts = beam_nparts(rows, K, VT);
-        float* pval = a.take<float>((size_t)nparts * rows * W);
-        int* pidx = a.take<int>((size_t)nparts * rows * W);
-        float* pm = a.take<float>((size_t)nparts * rows);
-        float* ps = a.take<float>((size_t)nparts * rows);
-        NIR_PROPAGATE(launch_beam_gen_topk(x, gen_frag, gen_b, VT, rows, K, W, pval, pidx, pm, ps, st));
-        hipLaunchKernelGGL(beam_topk_finish_kernel, dim3((unsigned)rows), dim3(64), 0, st, pval, pidx, pm, ps, nparts, rows, W, top_val, top_idx, lse);
-        NIR_CHECK_LAUNCH("beam_topk_finish_kernel");
-        return 0;
-    }
     float* logits = a.take<float>((size_t)rows * VT);
     NIR_PROPAGATE(launch_linear(x, K, nullptr, nullptr, 0, 0, 0, gen_w, K, gen_b, nullptr, logits, VT, rows, (int)VT, K, NIR_ACT_NONE, st));
     return launch_beam_row_topk(logits, VT, rows, W, top_val, top_idx, lse, st);
@@ -1523,7 +1365,7 @@ extern "C" size_t nir_acg_beam_gen_select_workspace_bytes(int64_t rows, int K, i
     if (rows <= 0 || K <= 0 || !beam_dims_ok(W, VT)) return 0;
     if (fused && !s2s_fusable(K, VT)) return 0;
     const size_t parts = fused ? (size_t)beam_nparts(rows, K, VT) : 1;
-    return (fused ? 0 : align_up((size_t)rows * VT * sizeof(float), 256)) + parts * rows * ((size_t)W * 8 + 8) + 5 * 256;
+    return (fused ? 0 : align_up((size_t)rows * VT * sizeof(float), 256)) + beam_partials_bytes(parts, rows, W, 5);
 }
 
 extern "C" int nir_acg_beam_gen_select(const float* o, int64_t rows, int64_t nsrc, int K, const float* gen_w, const float* gen_b, const void* gen_frag,
@@ -1547,12 +1389,10 @@ extern "C" int nir_acg_beam_gen_select(const float* o, int64_t rows, int64_t nsr
     Workspace a(workspace, workspace_bytes);
     const size_t parts = fused ? (size_t)beam_nparts(rows, K, VT) : 1;
     float* logits = a.take<float>(fused ? 0 : (size_t)rows * VT);
-    float* pval = a.take<float>(parts * rows * W);
-    int* pidx = a.take<int>(parts * rows * W);
-    float* pm = a.take<float>(parts * rows);
-    float* ps = a.take<float>(parts * rows);
-    return launch_acg_beam_gen_select(o, rows, nsrc, K, gen_w, gen_b, fused ? gen_frag : nullptr, VT, W, logits, pval, pidx, pm, ps, copy_w, copy_b, copy_attn,
-                                      attn_stride, source_len, QL, src_map_idx, ext2tgt, CV, nullptr, top_val, top_idx, (hipStream_t)stream);
+    BeamPartials p;
+    p.take(a, parts, rows, W, true);
+    return launch_acg_beam_gen_select(o, rows, nsrc, K, gen_w, gen_b, fused ? gen_frag : nullptr, VT, W, logits, p, copy_w, copy_b, copy_attn, attn_stride,
+                                      source_len, QL, src_map_idx, ext2tgt, CV, nullptr, top_val, top_idx, (hipStream_t)stream);
 }
 
 extern "C" int nir_acg_beam_select(const float* top_val, const int32_t* top_idx, const float* lse, int64_t B, int W, int64_t VT, int CV,

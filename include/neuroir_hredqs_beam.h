@@ -20,7 +20,7 @@ extern "C" {
  * workspace size covers a call without it).  There are no attentions.
  * Two forms, as the greedy entry has.  Fast: all three packs of nir_hredqs_decoder_weights given, H a multiple of 32 up to 1024, tunable
  * exact_f32 off -- per step the folded LSTM step, the generator + bias + log-sum-exp + top-W on the split state the step leaves
- * (hq_beam_gen_topk_kernel: no fp32 row is read and no [R, VT] logits are written), select, reorder.  Plain otherwise: the fp32 step, the fp32
+ * (beam_gen_topk_kernel on BeamRowsSplit: no fp32 row is read and no [R, VT] logits are written), select, reorder.  Plain otherwise: the fp32 step, the fp32
  * GEMM into workspace logits, beam_row_topk_kernel, select, reorder.
  * House rules as in neuroir_beam.h: enqueued on `stream`, no synchronisation, no allocation, the same inputs give the same bits; bad arguments
  * (W outside 1..NIR_BEAM_MAX_W, VT < W, null pointers, bad dims) return NIR_ERR_BAD_ARG and a short workspace NIR_ERR_WORKSPACE, with nothing

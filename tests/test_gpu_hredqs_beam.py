@@ -3,7 +3,7 @@ against the float64 restatement of tests/hredqs_beam_ref.py on the beam fixtures
 bitwise repeatability; W = 1 against the greedy decode on the unmodified goldens; the C entry fed the recorded session states; B = 1 and S = 1;
 eager against graph replay; and the n-best strings of a collated batch.
 
-Which test reaches which kernel form: the fast form runs hq_beam_gen_topk_kernel<4, 4> on h64 / h96 / h256 at W <= 4, <4, 8> nowhere on the
+Which test reaches which kernel form: the fast form runs beam_gen_topk_kernel<BeamRowsSplit, 4, 4> on h64 / h96 / h256 at W <= 4, <4, 8> nowhere on the
 fixtures (h64 has no W = 8 seed; the envelope module covers it), <2, 4> on h1024 at W <= 4 and <2, 8> on h1024 at W = 8 (48 beam rows: two
 32-row blocks)."""
 import pytest

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the generator + bias + (lse, top-W) kernel on the split state (csrc/beam.hip: hq_beam_gen_topk_kernel through
+"""GPU (-m gpu): the generator + bias + (lse, top-W) kernel on the split state (csrc/beam.hip: beam_gen_topk_kernel on BeamRowsSplit through
 nir_beam_hredqs_gen_topk) and the decode entry nir_beam_hredqs_decode at the C ABI, across their envelope.
 
 Shapes of the kernel tests: K in {32, 96, 512, 544, 1024} (one k-step, a chunk that is not full, both row-tile widths on either side of

@@ -46,7 +46,7 @@ def test_the_fixture_widths_are_the_ones_the_kernel_forms_need():
     want = {(t, W) for t in R.CASES for W in R.widths(t)}
     missing = want - set(CASE_W)
     assert missing <= {("h64", 8)}, missing                                     # the one pair the seed search may come back from empty-handed
-    assert ("h1024", 8) in CASE_W                                               # 48 beam rows: two 32-row blocks of hq_beam_gen_topk_kernel<2, 8>
+    assert ("h1024", 8) in CASE_W                                               # 48 beam rows: two 32-row blocks of beam_gen_topk_kernel<BeamRowsSplit, 2, 8>
     cs = R.load_case("h1024")
     assert cs["B"] * cs["S"] * 8 == 48 and cs["cfg"]["nhid_session"] == 1024
     assert R.seeds()["h1024"]["8"][2] == cs["max_len"]
