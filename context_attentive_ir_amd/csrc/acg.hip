@@ -13,7 +13,6 @@
 //       (l[t] from one fp32 dot of o with generator row t).
 // The rows of the teacher-forced loss (CopyGeneratorCriterion) are at the bottom.  fp32 throughout, vector stores only, no float atomics.
 #include <algorithm>
-#include <mutex>
 #include "s2s_gen.hpp"
 
 namespace nir {
@@ -167,31 +166,6 @@ __global__ __launch_bounds__(256) void acg_select_kernel(const float* __restrict
     }
 }
 
-static int launch_gen_stats(const float* x, const void* frag, const float* bias, int64_t VT, int64_t Bd, int K, float* pval, int* pidx, float* psum,
-                            int* nparts, hipStream_t st) {
-    const int64_t ntiles = (VT + 15) / 16;
-    const int nbt = s2s_nbt(K), nvr = s2s_nvr(Bd, K, ntiles);
-    const int64_t rb = (Bd + 16 * nbt - 1) / (16 * nbt);
-    const size_t lds = s2s_lds(K);
-    static std::once_flag once;
-    std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void*)s2s_gen_argmax_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(512));
-        (void)hipFuncSetAttribute((const void*)s2s_gen_argmax_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(1024));
-    });
-    {
-        ProfScope ps(prof_shape_name("s2s_gen_stats_kernel", (long long)Bd, (long long)VT, K), st);
-        if (nbt == 4)
-            hipLaunchKernelGGL((s2s_gen_argmax_kernel<4, true>), dim3((unsigned)(nvr * rb)), dim3(256), lds, st, x, (const _Float16*)frag, bias, VT, ntiles, Bd,
-                               K, nvr, pval, pidx, psum);
-        else
-            hipLaunchKernelGGL((s2s_gen_argmax_kernel<2, true>), dim3((unsigned)(nvr * rb)), dim3(256), lds, st, x, (const _Float16*)frag, bias, VT, ntiles, Bd,
-                               K, nvr, pval, pidx, psum);
-    }
-    NIR_CHECK_LAUNCH("s2s_gen_stats_kernel");
-    *nparts = nvr * 4;
-    return 0;
-}
-
 static int launch_acg_gen_select_stats(const float* o, int64_t B, int K, const float* gen_w, const float* gen_b, const void* gen_frag, int64_t VT,
                                        float* logits, float* pval, int* pidx, float* psum, const float* copy_w, const float* copy_b, const float* attn,
                                        int64_t attn_stride, const int64_t* lens, int QL, const int64_t* src_map_idx, const int64_t* ext2tgt,
@@ -199,7 +173,7 @@ static int launch_acg_gen_select_stats(const float* o, int64_t B, int K, const f
                                        float* stat_max, float* stat_lse, int64_t* stat_idx, hipStream_t st) {
     int nparts = 1;
     if (gen_frag) {
-        NIR_PROPAGATE(launch_gen_stats(o, gen_frag, gen_b, VT, B, K, pval, pidx, psum, &nparts, st));
+        NIR_PROPAGATE(launch_gen_argmax_partials<true>("s2s_gen_stats_kernel", o, gen_frag, gen_b, VT, B, K, pval, pidx, psum, &nparts, st));
     } else {
         NIR_PROPAGATE(launch_linear(o, K, nullptr, nullptr, 0, 0, 0, gen_w, K, gen_b, nullptr, logits, VT, B, (int)VT, K, NIR_ACT_NONE, st));
         {

@@ -19,7 +19,8 @@
 // hq_beam_begin_kernel in front (pairing, repeat, split) and, in its fast form, the generator top-k on the split state the folded step leaves.
 // The generator top-k kernel restates the staging, the chunk clamp and the fragment walk of the two greedy kernels, s2s_gen_argmax_kernel
 // (s2s_gen.hpp) and hq_gen_argmax_kernel (csrc/hredqs.hip), whose code and register allocation stay as they are: a change to one of those has
-// to be made in the greedy kernels too.
+// to be made in the greedy kernels too.  (One shared body with a tail policy was built and measured: the top-k and the keyed form ran slower
+// than these bodies, outside their spread -- DESIGN.md section 21.)
 #include <type_traits>
 #include "s2s_gen.hpp"
 
@@ -190,24 +191,24 @@ __global__ __launch_bounds__(256, 1) void beam_gen_topk_kernel(const typename RO
 #pragma unroll
         for (int j = 0; j < WM; ++j) { tv[bt][j] = -INFINITY; ti[bt][j] = BEAM_NONE; }
     }
-    const int NCH = (KS + S2S_KC - 1) / S2S_KC;
+    const int NCH = (KS + GEN_KC - 1) / GEN_KC;
     const int64_t first = t_lo + wave;
     const int64_t nt = first < t_hi ? (t_hi - first + 3) / 4 : 0;             // this wave's tiles: first, first + 4, ...
     const int64_t items = nt * NCH;                                           // (tile, chunk) pairs, in order
     f32x4 acc[NBT], acx[NBT];
-    auto load_w = [&](int64_t it, f16x8 (&wf)[S2S_KC][2]) {
+    auto load_w = [&](int64_t it, f16x8 (&wf)[GEN_KC][2]) {
         const int64_t t = first + 4 * (it / NCH);
         const int c = (int)(it % NCH);
 #pragma unroll
-        for (int u = 0; u < S2S_KC; ++u) {
-            const int ks = min(c * S2S_KC + u, KS - 1);                       // clamped: a duplicate k-step is not multiplied below
+        for (int u = 0; u < GEN_KC; ++u) {
+            const int ks = min(c * GEN_KC + u, KS - 1);                       // clamped: a duplicate k-step is not multiplied below
             const _Float16* wp = wfrag + ((t * KS + ks) * 2 * 64 + lane) * 8;
             wf[u][0] = *reinterpret_cast<const f16x8*>(wp);
             wf[u][1] = *reinterpret_cast<const f16x8*>(wp + 512);
         }
     };
     const _Float16* bp0 = beam_sm + c16 * LD + 8 * g4;
-    auto compute = [&](int64_t it, const f16x8 (&wf)[S2S_KC][2]) {
+    auto compute = [&](int64_t it, const f16x8 (&wf)[GEN_KC][2]) {
         const int64_t t = first + 4 * (it / NCH);
         const int c = (int)(it % NCH);
         if (c == 0) {
@@ -215,8 +216,8 @@ __global__ __launch_bounds__(256, 1) void beam_gen_topk_kernel(const typename RO
             for (int bt = 0; bt < NBT; ++bt) { acc[bt] = (f32x4){0.f, 0.f, 0.f, 0.f}; acx[bt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
         }
 #pragma unroll
-        for (int u = 0; u < S2S_KC; ++u) {
-            const int ks = c * S2S_KC + u;
+        for (int u = 0; u < GEN_KC; ++u) {
+            const int ks = c * GEN_KC + u;
             if (ks < KS) {                                                    // wave-uniform
                 f16x8 b[NBT][2];
 #pragma unroll
@@ -261,7 +262,7 @@ __global__ __launch_bounds__(256, 1) void beam_gen_topk_kernel(const typename RO
         }
     };
     {
-        f16x8 wfA[S2S_KC][2], wfB[S2S_KC][2];
+        f16x8 wfA[GEN_KC][2], wfB[GEN_KC][2];
         if (items > 0) load_w(0, wfA);
         for (int64_t it = 0; it < items; it += 2) {
             if (it + 1 < items) load_w(it + 1, wfB);
@@ -712,7 +713,7 @@ struct BeamPartials {
 };
 static size_t beam_partials_bytes(size_t parts, int64_t rows, int W, int takes) { return parts * rows * ((size_t)W * 8 + 8) + (size_t)takes * 256; }
 
-// The dispatch over (NBT, WM) of one form of the fused generator: nbt row tiles a workgroup (s2s_nbt), lists of 4 or NIR_BEAM_MAX_W entries.
+// The dispatch over (NBT, WM) of one form of the fused generator: nbt row tiles a workgroup (gen_nbt), lists of 4 or NIR_BEAM_MAX_W entries.
 // An instantiation's LDS limit is raised once, in front of its first launch.  name: the label of the profile and of the launch check.
 template <class ROWSRC, bool PAD>
 static int beam_gen_launch(const char* name, int nvr, int nbt, int64_t grid, const typename ROWSRC::elem* x, const void* frag, const float* bias, int64_t VT,
@@ -720,9 +721,9 @@ static int beam_gen_launch(const char* name, int nvr, int nbt, int64_t grid, con
     auto go = [&](auto nbt_c, auto wm_c) {
         constexpr int NBT = decltype(nbt_c)::value, WM = decltype(wm_c)::value;
         static const hipError_t raised = hipFuncSetAttribute((const void*)beam_gen_topk_kernel<ROWSRC, NBT, WM, PAD>,
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(NBT == 4 ? 512 : 1024));
+                                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(NBT == 4 ? 512 : 1024));
         (void)raised;
-        hipLaunchKernelGGL((beam_gen_topk_kernel<ROWSRC, NBT, WM, PAD>), dim3((unsigned)grid), dim3(256), s2s_lds(K), st, x, (const _Float16*)frag, bias, VT,
+        hipLaunchKernelGGL((beam_gen_topk_kernel<ROWSRC, NBT, WM, PAD>), dim3((unsigned)grid), dim3(256), gen_lds(K), st, x, (const _Float16*)frag, bias, VT,
                            (VT + 15) / 16, rows, K, nvr, W, p.pval, p.pidx, p.pm, p.ps);
     };
     {
@@ -743,19 +744,19 @@ static int beam_nparts(int64_t rows, int K, int64_t VT) { return rows > 0 ? 4 * 
 // the fused generator on fp32 rows: beam_nparts partials a row (pad: the PAD-substituting instantiations of the copy generator's beam)
 static int launch_beam_gen_topk(const float* x, const void* frag, const float* bias, int64_t VT, int64_t rows, int K, int W, const BeamPartials& p,
                                 hipStream_t st, bool pad = false) {
-    const int nbt = s2s_nbt(K), nvr = s2s_nvr(rows, K, (VT + 15) / 16);
+    const int nbt = gen_nbt(K), nvr = s2s_nvr(rows, K, (VT + 15) / 16);
     const int64_t rb = (rows + 16 * nbt - 1) / (16 * nbt);
     if (pad) return beam_gen_launch<BeamRowsF32, true>("beam_gen_topk_kernel", nvr, nbt, nvr * rb, x, frag, bias, VT, rows, K, W, p, st);
     return beam_gen_launch<BeamRowsF32, false>("beam_gen_topk_kernel", nvr, nbt, nvr * rb, x, frag, bias, VT, rows, K, W, p, st);
 }
 // partials per beam row of the split-state generator: one per wave of every vocabulary range of hq_nvr's grid
 static int hq_beam_nparts(int64_t rows, int K, int64_t VT) {
-    return rows > 0 ? 4 * hq_nvr((rows + 16 * hq_nbt(K) - 1) / (16 * hq_nbt(K)), (VT + 15) / 16) : 0;
+    return rows > 0 ? 4 * hq_nvr((rows + 16 * gen_nbt(K) - 1) / (16 * gen_nbt(K)), (VT + 15) / 16) : 0;
 }
 // the fused generator on the split state: hq_beam_nparts partials a row
 static int launch_hq_beam_gen_topk(const _Float16* h16, const void* frag, const float* bias, int64_t VT, int64_t rows, int K, int W, const BeamPartials& p,
                                    hipStream_t st) {
-    const int nbt = hq_nbt(K);
+    const int nbt = gen_nbt(K);
     const int64_t nrb = (rows + 16 * nbt - 1) / (16 * nbt);
     const int nvr = hq_nvr(nrb, (VT + 15) / 16);
     return beam_gen_launch<BeamRowsSplit, false>("hq_beam_gen_topk_kernel", nvr, nbt, nvr * nrb, h16, frag, bias, VT, rows, K, W, p, st);
@@ -1073,7 +1074,7 @@ static bool cars_beam_weights_ok(const nir_cars_decoder_weights* w) {
 extern "C" size_t nir_beam_cars_decode_workspace_bytes(int64_t rows_src, int64_t Bd, int QL, int W, int max_len, const nir_cars_decoder_weights* w, int fused) {
     using namespace nir;
     if (!cars_beam_weights_ok(w) || rows_src < 0 || Bd < 0 || QL <= 0 || max_len <= 0 || !beam_dims_ok(W, w->VT)) return 0;
-    return cars_beam_plan(nullptr, 0, rows_src, Bd, QL, W, max_len, w, fused && s2s_fusable(w->P, w->VT) && !tun(g_tun.exact_f32), nullptr).bytes;
+    return cars_beam_plan(nullptr, 0, rows_src, Bd, QL, W, max_len, w, fused && gen_fusable(w->P, w->VT) && !tun(g_tun.exact_f32), nullptr).bytes;
 }
 
 extern "C" int nir_beam_cars_decode(const float* dec_h, const float* dec_c, const float* encoded_source, const int64_t* source_len, int64_t rows_src, int QL,
@@ -1194,7 +1195,7 @@ static int beam_gen_topk_finish(void* workspace, size_t workspace_bytes, int npa
 extern "C" size_t nir_beam_plain_decode_workspace_bytes(int64_t Bd, int H, int64_t VT, int W, int max_len, int folded, int fused) {
     using namespace nir;
     if (Bd < 0 || H <= 0 || H % 4 || VT <= 0 || max_len <= 0 || !beam_dims_ok(W, VT)) return 0;
-    const bool fuse = fused && s2s_fusable(H, VT) && !tun(g_tun.exact_f32);
+    const bool fuse = fused && gen_fusable(H, VT) && !tun(g_tun.exact_f32);
     return plain_beam_plan(nullptr, 0, Bd, H, VT, W, max_len, folded && H % 32 == 0 && !tun(g_tun.exact_f32), fuse, fuse ? beam_nparts(Bd * W, H, VT) : 1, nullptr)
         .bytes;
 }
@@ -1224,7 +1225,7 @@ extern "C" int nir_beam_plain_decode(const float* dec_h, const float* dec_c, int
 // the fast form's top-W on the split state the folded step leaves ---------------------------------------------------------------------------
 extern "C" size_t nir_beam_hredqs_gen_topk_workspace_bytes(int64_t rows, int K, int64_t VT, int W) {
     using namespace nir;
-    if (rows <= 0 || !hq_fusable(K, VT) || !beam_dims_ok(W, VT)) return 0;
+    if (rows <= 0 || !gen_fusable(K, VT) || !beam_dims_ok(W, VT)) return 0;
     return beam_partials_bytes((size_t)hq_beam_nparts(rows, K, VT), rows, W, 4);
 }
 
@@ -1234,7 +1235,7 @@ extern "C" int nir_beam_hredqs_gen_topk(const void* h16, int64_t rows, int K, co
     hipStream_t st = (hipStream_t)stream;
     NIR_REQUIRE(h16 && gen_frag && workspace && top_val && top_idx && lse, "beam_hredqs_gen_topk: null pointer");
     NIR_REQUIRE(rows >= 0 && rows < 0x7FFFFFFFLL, "beam_hredqs_gen_topk: bad dims");
-    NIR_REQUIRE(hq_fusable(K, VT), "beam_hredqs_gen_topk: K must be a multiple of 32 in [32, 1024] and 0 < VT < 2^31 - 16");
+    NIR_REQUIRE(gen_fusable(K, VT), "beam_hredqs_gen_topk: K must be a multiple of 32 in [32, 1024] and 0 < VT < 2^31 - 16");
     NIR_REQUIRE(beam_dims_ok(W, VT), "beam_hredqs_gen_topk: beam width outside [1, %d] or above VT", NIR_BEAM_MAX_W);
     if (rows == 0) return 0;
     if (workspace_bytes < nir_beam_hredqs_gen_topk_workspace_bytes(rows, K, VT, W)) {
@@ -1288,7 +1289,7 @@ extern "C" size_t nir_beam_gen_topk_workspace_bytes(int64_t rows, int K, int64_t
     using namespace nir;
     if (rows <= 0 || K <= 0 || !beam_dims_ok(W, VT)) return 0;
     if (!fused) return (size_t)rows * VT * sizeof(float) + 256;
-    if (!s2s_fusable(K, VT)) return 0;
+    if (!gen_fusable(K, VT)) return 0;
     return beam_partials_bytes((size_t)beam_nparts(rows, K, VT), rows, W, 4);
 }
 
@@ -1363,7 +1364,7 @@ extern "C" int nir_beam_seq2seq_gru_decode(const float* dec_h, const float* memo
 extern "C" size_t nir_acg_beam_gen_select_workspace_bytes(int64_t rows, int K, int64_t VT, int W, int fused) {
     using namespace nir;
     if (rows <= 0 || K <= 0 || !beam_dims_ok(W, VT)) return 0;
-    if (fused && !s2s_fusable(K, VT)) return 0;
+    if (fused && !gen_fusable(K, VT)) return 0;
     const size_t parts = fused ? (size_t)beam_nparts(rows, K, VT) : 1;
     return (fused ? 0 : align_up((size_t)rows * VT * sizeof(float), 256)) + beam_partials_bytes(parts, rows, W, 5);
 }

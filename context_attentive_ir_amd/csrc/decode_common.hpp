@@ -30,16 +30,23 @@ int launch_argmax_finish(const float* pval, const int* pidx, int nparts, int64_t
 // multiProcessorCount of the current device (256 if unknown)
 int device_cu_count();
 
-// ---- the launch geometry of the HredQS generator kernels on the split state (csrc/hredqs.hip: hq_gen_argmax_kernel; csrc/beam.hip:
-// hq_beam_gen_topk_kernel) and the form test of the HredQS decode entries -----------------------------------------------------------------------
-constexpr int HQ_KC = 8;
+// ---- the launch geometry of the fused generator kernels (s2s_gen.hpp: s2s_gen_argmax_kernel; csrc/hredqs.hip: hq_gen_argmax_kernel;
+// csrc/beam.hip: beam_gen_topk_kernel) and the form test of the HredQS decode entries ---------------------------------------------------------
+constexpr int GEN_KC = 8;                             // k-steps a chunk
+constexpr int S2S_MAX_WGS = 256;
 
-static inline int hq_nbt(int K) { return K <= 512 ? 4 : 2; }
-static inline size_t hq_lds(int K) { return (size_t)2 * 16 * hq_nbt(K) * (K + 8) * sizeof(_Float16); }
-static inline bool hq_fusable(int K, int64_t VT) { return K >= 32 && K <= 1024 && K % 32 == 0 && VT > 0 && VT < 0x7FFFFFF0LL; }
+static inline int gen_nbt(int K) { return K <= 512 ? 4 : 2; }
+static inline size_t gen_lds(int K) { return (size_t)2 * 16 * gen_nbt(K) * (K + 8) * sizeof(_Float16); }
+static inline bool gen_fusable(int K, int64_t VT) { return K >= 32 && K <= 1024 && K % 32 == 0 && VT > 0 && VT < 0x7FFFFFF0LL; }
 
-// vocabulary ranges: one workgroup per CU (the staged rows fill its LDS) in a single round, at least ~2 tiles per wave; a multiple of 8 from
-// 8 on, so that the row blocks of a range can share an XCD (see hq_gen_argmax_kernel)
+// vocabulary ranges of the kernels on fp32 rows (s2s_gen_argmax_kernel, beam_gen_topk_kernel on BeamRowsF32): workgroups per row block, enough for the chip, at least ~2 tiles per wave
+static inline int s2s_nvr(int64_t Bd, int K, int64_t ntiles) {
+    const int64_t rb = (Bd + 16 * gen_nbt(K) - 1) / (16 * gen_nbt(K));
+    return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(S2S_MAX_WGS, (device_cu_count() + rb - 1) / rb), (ntiles + 7) / 8));
+}
+// vocabulary ranges of the kernels on the split state (hq_gen_argmax_kernel, beam_gen_topk_kernel on BeamRowsSplit): one workgroup per CU
+// (the staged rows fill its LDS) in a single round, at least ~2 tiles per wave; a multiple of 8 from 8 on, so that the row blocks of a
+// range can share an XCD
 static inline int hq_nvr(int64_t nrb, int64_t ntiles) {
     int64_t n = std::max<int64_t>(1, std::min<int64_t>(device_cu_count() / nrb, (ntiles + 7) / 8));
     if (n >= 8) n -= n % 8;
@@ -51,7 +58,7 @@ static inline bool hq_weights_ok(const nir_hredqs_decoder_weights* w) {
            w->gen_b;
 }
 static inline bool hq_fast(const nir_hredqs_decoder_weights* w) {
-    return w->rnn_gate_fold && w->rnn_whh_frag && w->gen_frag && hq_fusable(w->H, w->VT) && !tun(g_tun.exact_f32);
+    return w->rnn_gate_fold && w->rnn_whh_frag && w->gen_frag && gen_fusable(w->H, w->VT) && !tun(g_tun.exact_f32);
 }
 
 // One GRU decoder step (csrc/gru_step.hip).  Fast form (gru_step_fast): whh_frag, h16prev and h16next given, H % 32 == 0, tunable exact_f32 off --

@@ -52,7 +52,7 @@ __global__ void hq_pair_kernel(const float* __restrict__ hs, const float* __rest
 // ascending order there, so with j = blockIdx / 8 the row block is j % nrb and the range (j / nrb) * 8 + blockIdx % 8 (nvr a multiple of 8).
 // A range's fragments then come from HBM once and from that XCD's L2 for the other row blocks.  With nvr no multiple of 8 the row block is
 // blockIdx % nrb: still adjacent in dispatch order, sharing through the Infinity Cache only.  The mapping is a speed choice: any placement
-// gives the same keys.  (HQ_KC and the grid helpers hq_nbt / hq_lds / hq_nvr live in decode_common.hpp: the beam's top-W kernel shares them.)
+// gives the same keys.  (GEN_KC and the grid helpers gen_nbt / gen_lds / hq_nvr live in decode_common.hpp, shared with the other generator kernels.)
 template <int NBT>
 __global__ __launch_bounds__(256, 1) void hq_gen_argmax_kernel(const _Float16* __restrict__ h16, const _Float16* __restrict__ wfrag,
                                                                const float* __restrict__ bias, int64_t VT, int64_t ntiles, int64_t R, int K, int nvr,
@@ -105,24 +105,24 @@ __global__ __launch_bounds__(256, 1) void hq_gen_argmax_kernel(const _Float16* _
     int bidx[NBT];
 #pragma unroll
     for (int bt = 0; bt < NBT; ++bt) { best[bt] = -INFINITY; bidx[bt] = 0x7FFFFFFF; }
-    const int NCH = (KS + HQ_KC - 1) / HQ_KC;
+    const int NCH = (KS + GEN_KC - 1) / GEN_KC;
     const int64_t first = t_lo + wave;
     const int64_t nt = first < t_hi ? (t_hi - first + 3) / 4 : 0;              // this wave's tiles: first, first + 4, ...
     const int64_t items = nt * NCH;                                            // (tile, chunk) pairs, in order
     f32x4 acc[NBT], acx[NBT];
-    auto load_w = [&](int64_t it, f16x8 (&wf)[HQ_KC][2]) {
+    auto load_w = [&](int64_t it, f16x8 (&wf)[GEN_KC][2]) {
         const int64_t t = first + 4 * (it / NCH);
         const int c = (int)(it % NCH);
 #pragma unroll
-        for (int u = 0; u < HQ_KC; ++u) {
-            const int ks = min(c * HQ_KC + u, KS - 1);                         // clamped: a duplicate k-step is not multiplied below
+        for (int u = 0; u < GEN_KC; ++u) {
+            const int ks = min(c * GEN_KC + u, KS - 1);                         // clamped: a duplicate k-step is not multiplied below
             const _Float16* wp = wfrag + ((t * KS + ks) * 2 * 64 + lane) * 8;
             wf[u][0] = *reinterpret_cast<const f16x8*>(wp);
             wf[u][1] = *reinterpret_cast<const f16x8*>(wp + 512);
         }
     };
     const _Float16* bp0 = hq_sm + c16 * LD + 8 * g4;
-    auto compute = [&](int64_t it, const f16x8 (&wf)[HQ_KC][2]) {
+    auto compute = [&](int64_t it, const f16x8 (&wf)[GEN_KC][2]) {
         const int64_t t = first + 4 * (it / NCH);
         const int c = (int)(it % NCH);
         if (c == 0) {
@@ -130,8 +130,8 @@ __global__ __launch_bounds__(256, 1) void hq_gen_argmax_kernel(const _Float16* _
             for (int bt = 0; bt < NBT; ++bt) { acc[bt] = (f32x4){0.f, 0.f, 0.f, 0.f}; acx[bt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
         }
 #pragma unroll
-        for (int u = 0; u < HQ_KC; ++u) {
-            const int ks = c * HQ_KC + u;
+        for (int u = 0; u < GEN_KC; ++u) {
+            const int ks = c * GEN_KC + u;
             if (ks < KS) {                                                     // wave-uniform
                 f16x8 b[NBT][2];
 #pragma unroll
@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256, 1) void hq_gen_argmax_kernel(const _Float16* _
         }
     };
     {
-        f16x8 wfA[HQ_KC][2], wfB[HQ_KC][2];
+        f16x8 wfA[GEN_KC][2], wfB[GEN_KC][2];
         if (items > 0) load_w(0, wfA);
         for (int64_t it = 0; it < items; it += 2) {
             if (it + 1 < items) load_w(it + 1, wfB);
@@ -222,14 +222,14 @@ __global__ void hq_keys_decode_kernel(const unsigned long long* __restrict__ key
 static int launch_hq_gen_argmax(const _Float16* h16, const void* frag, const float* bias, int64_t VT, int64_t R, int K, unsigned long long* keys,
                                 hipStream_t st) {
     const int64_t ntiles = (VT + 15) / 16;
-    const int nbt = hq_nbt(K);
+    const int nbt = gen_nbt(K);
     const int64_t nrb = (R + 16 * nbt - 1) / (16 * nbt);
     const int nvr = hq_nvr(nrb, ntiles);
-    const size_t lds = hq_lds(K);
+    const size_t lds = gen_lds(K);
     static std::once_flag once;
     std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void*)hq_gen_argmax_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hq_lds(512));
-        (void)hipFuncSetAttribute((const void*)hq_gen_argmax_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hq_lds(1024));
+        (void)hipFuncSetAttribute((const void*)hq_gen_argmax_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(512));
+        (void)hipFuncSetAttribute((const void*)hq_gen_argmax_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(1024));
     });
     {
         ProfScope ps(prof_shape_name("hq_gen_argmax_kernel", (long long)R, (long long)VT, K), st);
@@ -281,7 +281,7 @@ extern "C" int nir_hredqs_gen_argmax(const void* h16, int64_t rows, int K, const
     hipStream_t st = (hipStream_t)stream;
     NIR_REQUIRE(h16 && gen_frag && predictions && next_tokens && workspace, "hredqs_gen_argmax: null pointer");
     NIR_REQUIRE(rows >= 0 && V > 0 && pred_stride >= 1, "hredqs_gen_argmax: bad dims");
-    NIR_REQUIRE(hq_fusable(K, VT), "hredqs_gen_argmax: K must be a multiple of 32 in [32, 1024] and 0 < VT < 2^31 - 16");
+    NIR_REQUIRE(gen_fusable(K, VT), "hredqs_gen_argmax: K must be a multiple of 32 in [32, 1024] and 0 < VT < 2^31 - 16");
     if (workspace_bytes < nir_hredqs_gen_argmax_workspace_bytes(rows)) {
         set_error("hredqs_gen_argmax: workspace too small");
         return NIR_ERR_WORKSPACE;

@@ -1,6 +1,7 @@
 // The generator kernel of the greedy attention decoders (csrc/seq2seq.hip: arg-max; csrc/acg.hip: arg-max + softmax statistics) and its
 // launch geometry.  One template: STATS = false is the Seq2seq kernel, STATS = true additionally keeps the online-softmax sum of every row.
 #pragma once
+#include <mutex>
 #include "decode_common.hpp"
 
 namespace nir {
@@ -10,12 +11,10 @@ namespace nir {
 //   frag[vt][ks][term][lane][8],  element (lane, j) = W[16 vt + (lane & 15)][32 ks + 8 (lane >> 4) + j],  rows past VT are zero.
 // A workgroup stages 16 NBT decode rows as two fp16 planes in LDS ([2][16 NBT][K + 8] halves: NBT = 4 up to K = 512 -- 133 KB -- and 2
 // beyond -- 132 KB at K = 1024; gfx950 has 160 KB) and walks its range of vocabulary tiles, a wave one tile at a time.  A tile's k-steps
-// go in chunks of S2S_KC: the fragments of the next chunk (or of the next tile's first chunk) are requested before the MFMAs of the
+// go in chunks of GEN_KC: the fragments of the next chunk (or of the next tile's first chunk) are requested before the MFMAs of the
 // current one are issued.  Three v_mfma_f32_16x16x32_f16 per product block (hi hi -> acc; lo hi, hi lo -> acx; result acc + 2^-11 acx),
 // the bias is added in fp32 before the comparison, `>` in ascending index order keeps the first index on ties.  Every wave writes one
 // (value, index) partial per decode row; argmax_finish_kernel reduces them.
-constexpr int S2S_KC = 8;
-
 //
 // STATS (csrc/acg.hip, the copy generator: modules/copy_generator.py:78-80): the logit of v == PAD (0) is replaced by -1e-20f before the comparison,
 // and every lane keeps the online-softmax sum of its rows next to the running maximum -- sum_v exp(y_v - best), rescaled when best moves (one
@@ -73,24 +72,24 @@ __global__ __launch_bounds__(256, 1) void s2s_gen_argmax_kernel(const float* __r
     float rsum[NBT];
 #pragma unroll
     for (int bt = 0; bt < NBT; ++bt) rsum[bt] = 0.f;
-    const int NCH = (KS + S2S_KC - 1) / S2S_KC;
+    const int NCH = (KS + GEN_KC - 1) / GEN_KC;
     const int64_t first = t_lo + wave;
     const int64_t nt = first < t_hi ? (t_hi - first + 3) / 4 : 0;             // this wave's tiles: first, first + 4, ...
     const int64_t items = nt * NCH;                                           // (tile, chunk) pairs, in order
     f32x4 acc[NBT], acx[NBT];
-    auto load_w = [&](int64_t it, f16x8 (&wf)[S2S_KC][2]) {
+    auto load_w = [&](int64_t it, f16x8 (&wf)[GEN_KC][2]) {
         const int64_t t = first + 4 * (it / NCH);
         const int c = (int)(it % NCH);
 #pragma unroll
-        for (int u = 0; u < S2S_KC; ++u) {
-            const int ks = min(c * S2S_KC + u, KS - 1);                       // clamped: a duplicate k-step is not multiplied below
+        for (int u = 0; u < GEN_KC; ++u) {
+            const int ks = min(c * GEN_KC + u, KS - 1);                       // clamped: a duplicate k-step is not multiplied below
             const _Float16* wp = wfrag + ((t * KS + ks) * 2 * 64 + lane) * 8;
             wf[u][0] = *reinterpret_cast<const f16x8*>(wp);
             wf[u][1] = *reinterpret_cast<const f16x8*>(wp + 512);
         }
     };
     const _Float16* bp0 = s2s_sm + c16 * LD + 8 * g4;
-    auto compute = [&](int64_t it, const f16x8 (&wf)[S2S_KC][2]) {
+    auto compute = [&](int64_t it, const f16x8 (&wf)[GEN_KC][2]) {
         const int64_t t = first + 4 * (it / NCH);
         const int c = (int)(it % NCH);
         if (c == 0) {
@@ -98,8 +97,8 @@ __global__ __launch_bounds__(256, 1) void s2s_gen_argmax_kernel(const float* __r
             for (int bt = 0; bt < NBT; ++bt) { acc[bt] = (f32x4){0.f, 0.f, 0.f, 0.f}; acx[bt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
         }
 #pragma unroll
-        for (int u = 0; u < S2S_KC; ++u) {
-            const int ks = c * S2S_KC + u;
+        for (int u = 0; u < GEN_KC; ++u) {
+            const int ks = c * GEN_KC + u;
             if (ks < KS) {                                                    // wave-uniform
                 f16x8 b[NBT][2];
 #pragma unroll
@@ -155,7 +154,7 @@ __global__ __launch_bounds__(256, 1) void s2s_gen_argmax_kernel(const float* __r
         }
     };
     {
-        f16x8 wfA[S2S_KC][2], wfB[S2S_KC][2];
+        f16x8 wfA[GEN_KC][2], wfB[GEN_KC][2];
         if (items > 0) load_w(0, wfA);
         for (int64_t it = 0; it < items; it += 2) {
             if (it + 1 < items) load_w(it + 1, wfB);
@@ -189,18 +188,36 @@ __global__ __launch_bounds__(256, 1) void s2s_gen_argmax_kernel(const float* __r
     }
 }
 
-constexpr int S2S_MAX_WGS = 256;
-static inline int s2s_nbt(int K) { return K <= 512 ? 4 : 2; }
-static inline size_t s2s_lds(int K) { return (size_t)2 * 16 * s2s_nbt(K) * (K + 8) * sizeof(_Float16); }
-static inline bool s2s_fusable(int K, int64_t VT) { return K >= 32 && K <= 1024 && K % 32 == 0 && VT > 0 && VT < 0x7FFFFFF0LL; }
-// the fused generator runs (arg-max, statistics or top-k alike): the fragments are given, the shape has a fused form, tunable exact_f32 is off
-static inline bool s2s_gen_fused(const void* gen_frag, int K, int64_t VT) { return gen_frag != nullptr && s2s_fusable(K, VT) && !tun(g_tun.exact_f32); }
-
-// workgroups per row block: enough for the chip, at least ~2 tiles per wave
-static inline int s2s_nvr(int64_t Bd, int K, int64_t ntiles) {
-    const int64_t rb = (Bd + 16 * s2s_nbt(K) - 1) / (16 * s2s_nbt(K));
-    return (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(S2S_MAX_WGS, (device_cu_count() + rb - 1) / rb), (ntiles + 7) / 8));
+// The launch of either form: nvr vocabulary ranges (s2s_nvr) x the row blocks of Bd, *nparts = 4 nvr partials a row.  name: the label of the
+// profile and of the launch check (s2s_gen_argmax_kernel, s2s_gen_stats_kernel).  GEN_KC and the geometry (gen_nbt, gen_lds, gen_fusable,
+// s2s_nvr) live in decode_common.hpp, shared with the generator kernels of csrc/hredqs.hip and csrc/beam.hip.
+template <bool STATS>
+static int launch_gen_argmax_partials(const char* name, const float* x, const void* frag, const float* bias, int64_t VT, int64_t Bd, int K, float* pval,
+                                      int* pidx, float* psum, int* nparts, hipStream_t st) {
+    const int64_t ntiles = (VT + 15) / 16;
+    const int nbt = gen_nbt(K), nvr = s2s_nvr(Bd, K, ntiles);
+    const int64_t rb = (Bd + 16 * nbt - 1) / (16 * nbt);
+    const size_t lds = gen_lds(K);
+    static std::once_flag once;
+    std::call_once(once, [] {
+        (void)hipFuncSetAttribute((const void*)s2s_gen_argmax_kernel<4, STATS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(512));
+        (void)hipFuncSetAttribute((const void*)s2s_gen_argmax_kernel<2, STATS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(1024));
+    });
+    {
+        ProfScope ps(prof_shape_name(name, (long long)Bd, (long long)VT, K), st);
+        if (nbt == 4)
+            hipLaunchKernelGGL((s2s_gen_argmax_kernel<4, STATS>), dim3((unsigned)(nvr * rb)), dim3(256), lds, st, x, (const _Float16*)frag, bias, VT, ntiles, Bd,
+                               K, nvr, pval, pidx, psum);
+        else
+            hipLaunchKernelGGL((s2s_gen_argmax_kernel<2, STATS>), dim3((unsigned)(nvr * rb)), dim3(256), lds, st, x, (const _Float16*)frag, bias, VT, ntiles, Bd,
+                               K, nvr, pval, pidx, psum);
+    }
+    NIR_CHECK_LAUNCH(name);
+    *nparts = nvr * 4;
+    return 0;
 }
+// the fused generator runs (arg-max, statistics or top-k alike): the fragments are given, the shape has a fused form, tunable exact_f32 is off
+static inline bool s2s_gen_fused(const void* gen_frag, int K, int64_t VT) { return gen_frag != nullptr && gen_fusable(K, VT) && !tun(g_tun.exact_f32); }
 
 // ---- ACG: the copy generator behind the Seq2seq step (csrc/acg.hip) ----------------------------------------------------------------------
 constexpr float ACG_PAD_LOGIT = -1e-20f;              // copy_generator.py:79: logits[:, :, PAD] = -eps

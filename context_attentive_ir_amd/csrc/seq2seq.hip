@@ -21,7 +21,6 @@
 //                                                                                                    (or GEMM + argmax_map_kernel)
 // Everything is enqueued on the caller's stream; no host synchronisation, no allocation, no float atomics.
 #include <algorithm>
-#include <mutex>
 #include "s2s_gen.hpp"
 
 namespace nir {
@@ -104,26 +103,9 @@ __global__ void s2s_gen_frag_kernel(const float* __restrict__ w, int64_t VT, int
 
 static int launch_gen_argmax(const float* x, const void* frag, const float* bias, int64_t VT, int64_t Bd, int K, float* pval, int* pidx,
                              const int64_t* lut, int64_t* pred, int64_t pstride, int64_t* tgt, int64_t Vsrc, hipStream_t st) {
-    const int64_t ntiles = (VT + 15) / 16;
-    const int nbt = s2s_nbt(K), nvr = s2s_nvr(Bd, K, ntiles);
-    const int64_t rb = (Bd + 16 * nbt - 1) / (16 * nbt);
-    const size_t lds = s2s_lds(K);
-    static std::once_flag once;
-    std::call_once(once, [] {
-        (void)hipFuncSetAttribute((const void*)s2s_gen_argmax_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(512));
-        (void)hipFuncSetAttribute((const void*)s2s_gen_argmax_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s2s_lds(1024));
-    });
-    {
-        ProfScope ps(prof_shape_name("s2s_gen_argmax_kernel", (long long)Bd, (long long)VT, K), st);
-        if (nbt == 4)
-            hipLaunchKernelGGL((s2s_gen_argmax_kernel<4, false>), dim3((unsigned)(nvr * rb)), dim3(256), lds, st, x, (const _Float16*)frag, bias, VT, ntiles, Bd, K,
-                               nvr, pval, pidx, (float*)nullptr);
-        else
-            hipLaunchKernelGGL((s2s_gen_argmax_kernel<2, false>), dim3((unsigned)(nvr * rb)), dim3(256), lds, st, x, (const _Float16*)frag, bias, VT, ntiles, Bd, K,
-                               nvr, pval, pidx, (float*)nullptr);
-    }
-    NIR_CHECK_LAUNCH("s2s_gen_argmax_kernel");
-    return launch_argmax_finish(pval, pidx, nvr * 4, Bd, lut, pred, pstride, tgt, Vsrc, st);
+    int nparts;
+    NIR_PROPAGATE(launch_gen_argmax_partials<false>("s2s_gen_argmax_kernel", x, frag, bias, VT, Bd, K, pval, pidx, nullptr, &nparts, st));
+    return launch_argmax_finish(pval, pidx, nparts, Bd, lut, pred, pstride, tgt, Vsrc, st);
 }
 
 int launch_attend(const float* q, const float* h, const float* mem, const float* sb, const float* v, const int64_t* lens, int64_t B, int QL, int H,
@@ -263,14 +245,14 @@ size_t s2s_decode_workspace_bytes(int64_t B, int QL, const nir_seq2seq_decoder_w
 }  // namespace nir
 
 extern "C" size_t nir_seq2seq_gen_frag_bytes(int64_t VT, int K) {
-    if (!nir::s2s_fusable(K, VT)) return 0;
+    if (!nir::gen_fusable(K, VT)) return 0;
     return (size_t)((VT + 15) / 16) * (K / 32) * 2 * 64 * 8 * sizeof(_Float16);
 }
 
 extern "C" int nir_seq2seq_pack_gen_frag(const float* gen_w, int64_t VT, int K, void* frag, int* err_flag, nir_stream_t stream) {
     using namespace nir;
     NIR_REQUIRE(gen_w && frag, "seq2seq_pack_gen_frag: null pointer");
-    NIR_REQUIRE(s2s_fusable(K, VT), "seq2seq_pack_gen_frag: K must be a multiple of 32 in [32, 1024] and 0 < VT < 2^31 - 16");
+    NIR_REQUIRE(gen_fusable(K, VT), "seq2seq_pack_gen_frag: K must be a multiple of 32 in [32, 1024] and 0 < VT < 2^31 - 16");
     const int64_t n = (VT + 15) / 16 * (K / 32) * 512;
     hipLaunchKernelGGL(s2s_gen_frag_kernel, g1(n), dim3(256), 0, (hipStream_t)stream, gen_w, VT, K, n, (_Float16*)frag, err_flag);
     NIR_CHECK_LAUNCH("s2s_gen_frag_kernel");

@@ -2,7 +2,8 @@
 
 Statistics (the STATS form of s2s_gen_argmax_kernel, and the plain GEMM + acg_row_stats_kernel), read through nir_acg_gen_select's optional
 outputs: K in {32, 96, 512, 1024} x VT in {17, 200, 4099} x rows in {1, 5, 97} (both row-tile widths, a padded last tile, more than one
-vocabulary range, more than one row block).  The arg-max is planted with a float64 gap of at least 1e-3 of the row's largest |logit|; from 5
+vocabulary range, more than one row block), and K = 544 at VT = 200 (two row tiles a workgroup with a last chunk of k-steps that is not
+full).  The arg-max is planted with a float64 gap of at least 1e-3 of the row's largest |logit|; from 5
 rows on a batch holds a row whose logits ascend along v (every tile moves the running maximum), one that descends, one with a spread above 60,
 and one whose other logits are all negative so that PAD (-1e-20) wins; the RAW PAD logit is the largest of every row through its bias and must
 neither win nor count.  lse = max + log(sum): with e = |lse - lse64| relative to the row's largest |logit| and e_chain the same chain in
@@ -101,8 +102,8 @@ def _stat_ref(x, W, b, dt):
 
 
 @pytest.mark.parametrize("fused", [True, False], ids=["fused", "plain"])
-@pytest.mark.parametrize("VT", [17, 200, 4099])
-@pytest.mark.parametrize("K", [32, 96, 512, 1024])
+# (544, 200): the fp32 staging at two row tiles a workgroup with a last chunk of k-steps that is not full
+@pytest.mark.parametrize("K,VT", [(K, VT) for VT in (17, 200, 4099) for K in (32, 96, 512, 1024)] + [(544, 200)])
 def test_statistics_against_fp64(K, VT, fused):
     assert MARGIN <= gemm_ref.MARGIN_CAP
     g = torch.Generator().manual_seed(11 * K + VT)

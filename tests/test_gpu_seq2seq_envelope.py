@@ -6,7 +6,8 @@ above QL in every batch (clamped).  Bound: the house form on both outputs, e <= 
 float32 on the CPU (no split product on this path); masked positions exactly 0.
 
 Generator + arg-max (nir_seq2seq_gen_argmax): K in {32, 96, 512, 1024} x VT in {17, 200, 4099} x rows in {1, 5, 97} (both row-tile
-widths, a zero-padded last vocabulary tile, more than one vocabulary range and more than one row block), every winner PLANTED with a float64
+widths, a zero-padded last vocabulary tile, more than one vocabulary range and more than one row block), and K = 544 at VT = 200 (two row
+tiles a workgroup with a last chunk of k-steps that is not full), every winner PLANTED with a float64
 gap of at least 1e-3 of the row's largest |logit| -- no row is excluded: winners at index 0, at VT - 1 and inside the padded tile, a winner
 decided by the bias alone, an exact tie (first index wins); and every condition that sends the call to the fp32 GEMM + arg-max path, once.
 Bad arguments return NIR_ERR_BAD_ARG and leave a sentinel output untouched."""
@@ -158,8 +159,8 @@ def _check_planted(logits, winners, pred, allow_equal=None):
     assert torch.equal(pred, winners), (pred, winners)
 
 
-@pytest.mark.parametrize("VT", [17, 200, 4099])
-@pytest.mark.parametrize("K", [32, 96, 512, 1024])
+# (544, 200): the fp32 staging at two row tiles a workgroup with a last chunk of k-steps that is not full
+@pytest.mark.parametrize("K,VT", [(K, VT) for VT in (17, 200, 4099) for K in (32, 96, 512, 1024)] + [(544, 200)])
 def test_generator_argmax_planted_winners(K, VT):
     g = torch.Generator().manual_seed(7 * K + VT)
     lut = torch.randperm(VT, generator=g)
