@@ -370,6 +370,14 @@ HREDQS_BEAM_SIGNATURES = {
     "nir_beam_hredqs_decode": (_i, [c_fp, c_fp, _l, _l, c_fp, _l, _i, c_ip, _l, _i, _HW, _i, C.c_void_p, _z, c_ip, c_fp, c_ip, C.c_void_p, c_st]),
 }
 
+# Teacher-forced scoring of candidate queries, declared in include/neuroir_score.h (csrc/score.hip): every symbol starts with nir_score_.  A
+# table of its own, like the ones above.
+SCORE_SIGNATURES = {
+    "nir_score_gen_target_workspace_bytes": (_z, [_l, _i, _l, _i]),
+    "nir_score_gen_target": (_i, [c_fp, _l, _i, c_fp, c_fp, C.c_void_p, _l, c_ip, _l, C.c_void_p, _z, c_fp, c_fp, C.c_void_p, c_st]),
+    "nir_score_sequences": (_i, [c_fp, c_ip, _l, _i, _l, _l, c_fp, c_ip, c_st]),
+}
+
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_SPLIT2 = 0, 1, 2
 DTYPES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "bf16": DTYPE_BF16, "f32_split2": DTYPE_F32_SPLIT2}
 
@@ -386,7 +394,7 @@ def load():
                 "(hipcc, gfx950). The HIP path has no CPU fallback." % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(GRU_DECODE_SIGNATURES.items()) + list(BEAM_SIGNATURES.items()) + list(SESSION_BEAM_SIGNATURES.items())
-                                  + list(ACG_BEAM_SIGNATURES.items()) + list(HREDQS_BEAM_SIGNATURES.items())):
+                                  + list(ACG_BEAM_SIGNATURES.items()) + list(HREDQS_BEAM_SIGNATURES.items()) + list(SCORE_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

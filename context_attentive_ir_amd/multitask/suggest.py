@@ -10,7 +10,7 @@ import torch
 
 from .. import autograd as A
 from .. import lib
-from ..constants import BOS, PAD
+from ..constants import BOS, EOS, PAD, UNK
 
 
 def session_states(x, lstm):
@@ -47,6 +47,43 @@ def tgt2src_lut(owner, src_dict, tgt_dict, n, dev):
         lut = [int(src_dict[tgt_dict[i]]) if i < len(tgt_dict) else 0 for i in range(n)]
         owner._lut, owner._lut_key = torch.tensor(lut, dtype=torch.int64, device=dev), key
     return owner._lut
+
+
+def candidate_inputs(owner, candidate_seq, candidate_rep, src_dict, tgt_dict, tgt2src, VT, V):
+    """the embedder ids a teacher-forced scorer feeds for candidate_seq [..., TL] (target-vocabulary ids, BOS first): candidate_rep through the
+    model's id check where given, else what the decodes feed -- the first token as it is (they start from BOS itself, an id both vocabularies
+    share), tgt2src[token] behind it (the token itself without a table), <unk> outside the source vocabulary"""
+    if candidate_rep is not None:
+        return owner._clean_ids(candidate_rep.reshape(candidate_seq.shape), None, V)[0]
+    if tgt2src is None:
+        tgt2src = tgt2src_lut(owner, src_dict, tgt_dict, VT, candidate_seq.device)
+    rep = candidate_seq if tgt2src is None else torch.cat((candidate_seq[..., :1], tgt2src[candidate_seq[..., 1:].clamp(0, VT - 1)]), -1)
+    return torch.where((rep >= 0) & (rep < V), rep, torch.full_like(rep, UNK))
+
+
+def score_rows(owner, dec_out, candidate_seq, gen_w, gen_b, gen_frag):
+    """The tail of every score_candidates (include/neuroir_score.h).  dec_out [..., TL - 1, K]: the decoder outputs of the
+    teacher-forced steps, rows in candidate_seq's order; candidate_seq [..., TL].  ONE nir_score_gen_target over all rows -- step t against token
+    t + 1; gen_frag (a uint8 tensor, or None: the plain form) -- and one nir_score_sequences -> {'token_logprobs': [..., TL - 1], 'scores':
+    [...], 'lengths': LongTensor [...]}.  An id outside the target vocabulary sets the device's id flag (owner.check_ids())."""
+    L = lib.load()
+    lead, TL = tuple(candidate_seq.shape[:-1]), int(candidate_seq.shape[-1])
+    T, K, VT = TL - 1, int(dec_out.shape[-1]), int(gen_w.shape[0])
+    x = dec_out.reshape(-1, K).float().contiguous()
+    dev = x.device
+    R = x.shape[0]
+    nseq = R // T
+    target = candidate_seq[..., 1:].reshape(-1).contiguous()
+    logp = torch.empty(R, dtype=torch.float32, device=dev)
+    scores = torch.empty(nseq, dtype=torch.float32, device=dev)
+    lengths = torch.empty(nseq, dtype=torch.int64, device=dev)
+    if R > 0:
+        ws = lib.workspace(L.nir_score_gen_target_workspace_bytes(R, K, VT, 1 if gen_frag is not None else 0), dev)
+        lib.check(L.nir_score_gen_target(lib.ptr(x), R, K, lib.ptr(gen_w), lib.ptr(gen_b), lib.ptr(gen_frag), VT, lib.ptr(target), PAD, lib.ptr(ws),
+                                         ws.numel(), lib.ptr(logp), None, lib.ptr(owner._flag_word(dev)), lib.stream()), "nir_score_gen_target")
+        lib.check(L.nir_score_sequences(lib.ptr(logp), lib.ptr(target), nseq, T, PAD, EOS, lib.ptr(scores), lib.ptr(lengths), lib.stream()),
+                  "nir_score_sequences")
+    return {"token_logprobs": logp.view(lead + (T,)), "scores": scores.view(lead), "lengths": lengths.view(lead)}
 
 
 def plain_fold(owner, table, dec_rnn, t, p, H, dev):

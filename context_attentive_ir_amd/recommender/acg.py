@@ -166,6 +166,13 @@ class ACG(Seq2seq):
         return self._greedy(source_rep, source_len, max_len, src_dict, tgt_dict, tgt2src,
                             extra=(cw.ref(), lib.ptr(idx), lib.ptr(e2t), lib.ptr(e2s), CV), ws_bytes=ws_bytes)
 
+    # ---- eval: scoring -------------------------------------------------------------------------------------------------------------
+    def score_candidates(self, *args, **kwargs):
+        """not Seq2seq's: a token's likelihood under ACG is generator mass plus copy mass of the collapsed extended distribution, not the
+        generator's softmax alone (DESIGN.md section 26 names it as the follow-up)"""
+        raise NotImplementedError("HIP %s.score_candidates: scoring under the copy generator's collapsed extended distribution is not built yet "
+                                  "(the generator's log-likelihood alone would be another model's)" % type(self).__name__)
+
     # ---- eval: beam search ---------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def decode_beam(self, source_rep, source_len, max_len, beam_size, src_dict=None, tgt_dict=None, src_map=None, blank=None, fill=None,

@@ -7,6 +7,8 @@ decode():  ONE C-ABI call for the whole greedy decode of all B S session prefixe
            step and the generator + bias + arg-max kernel, two launches per step; the winner travels as an arg-max key.
 decode_beam(): ONE C-ABI call for the beam search over the same prefixes (nir_beam_hredqs_decode, csrc/beam.hip): n-best suggestions with scores.
 forward(): the teacher-forced loss on the differentiable HIP operators of autograd.py.
+score_candidates(): log P(candidate | session prefix) of given next queries: the session states and pairing of decode(), the teacher-forced
+           decoder pass, ONE generator call over the rows of all time steps that keeps the logits on chip (nir_score_gen_target, csrc/score.hip).
 
 Kept quirks of the reference:
   * the pairing: the decoder's rows are in (b, s) order (source_rep.view(B S, -1)), the session states in (s, b) order (torch.cat over the
@@ -198,6 +200,40 @@ class HredQS(nn.Module, lib.IdCheck):
         out["predictions"] = out["predictions"].view(B, S, W, max_len)
         out["scores"], out["lengths"] = out["scores"].view(B, S, W), out["lengths"].view(B, S, W)
         return out
+
+    # ---- eval: teacher-forced scoring of given candidates ---------------------------------------------------------------------------------
+    @torch.no_grad()
+    def score_candidates(self, source_rep, source_len, candidate_seq, candidate_rep=None, src_dict=None, tgt_dict=None, tgt2src=None):
+        """log P(candidate | session prefix) for N candidate next queries per prefix (include/neuroir_score.h).
+        source_rep [B, S, QL], source_len [B, S]; candidate_seq [B, S, N, TL]: target-vocabulary ids, BOS first, PAD behind the end; candidate_rep
+        [B, S, N, TL]: the embedder ids fed to the decoder (default: what decode() feeds -- the first token as it is, tgt2src[token] behind it, <unk> outside the source
+        vocabulary) -> {'token_logprobs': [B, S, N, TL - 1], 'scores': [B, S, N], 'lengths': LongTensor [B, S, N]}.  The session states and
+        their pairing are decode()'s (row b S + s starts from step (b S + s) // B of session (b S + s) % B); the teacher-forced decoder pass
+        is forward()'s without dropout; ONE generator call over all rows that keeps the logits on chip (`fast_decode = False`: its plain form)."""
+        dec_out, cand, w = self._candidate_rows(source_rep, source_len, candidate_seq, candidate_rep, src_dict, tgt_dict, tgt2src)
+        return suggest.score_rows(self, dec_out, cand, w.keep["gen_w"], w.keep["gen_b"], w.keep.get("gen_frag"))
+
+    def _candidate_rows(self, source_rep, source_len, candidate_seq, candidate_rep, src_dict, tgt_dict, tgt2src):
+        """score_candidates in front of the generator -> (the decoder outputs of the teacher-forced steps [B, S, N, TL - 1, nhid_session],
+        candidate_seq as int64, the packed decoder weights)"""
+        if self.training:
+            raise NotImplementedError("HIP HredQS.score_candidates runs in eval mode")
+        self._check_config()
+        B, S, QL = source_rep.shape
+        table = self.embedder.word_embeddings.table
+        cand = lib.ids64(candidate_seq)
+        if cand.dim() != 4 or tuple(cand.shape[:2]) != (B, S) or cand.shape[3] < 2:
+            raise ValueError("score_candidates: candidate_seq must be [B, S, N, TL] with TL >= 2 (got %s)" % (tuple(cand.shape),))
+        lib.require_device(source_rep, source_len, table, cand, candidate_rep)
+        R, N, T = B * S, int(cand.shape[2]), int(cand.shape[3]) - 1
+        src, _ = self._clean_ids(source_rep.reshape(R, QL), None, table.shape[0])
+        hs, cs = self._session_steps(src, lib.ids64(source_len.reshape(-1)), B, S)
+        w = self._decoder_weights()
+        rep = suggest.candidate_inputs(self, cand, candidate_rep, src_dict, tgt_dict, tgt2src, int(w.struct.VT), table.shape[0])
+        # the reference's pairing (see the module docstring), then every row's state once per candidate: rows (b, s, n)
+        dec_h, dec_c = (s.transpose(0, 1).reshape(R, -1).repeat_interleave(N, 0).contiguous() for s in (hs, cs))
+        h_all, _ = A.lstm_seq(A.embed(rep[..., :-1].reshape(R * N, T), table), self.decoder.decoder.rnn, dec_h, dec_c)
+        return h_all.view(B, S, N, T, -1), cand, w
 
     # ---- train: teacher-forced loss ---------------------------------------------------------------------------------------------------
     def forward(self, source_rep, source_len, target_rep, target_len, target_seq, source_map=None, alignment=None):

@@ -5,6 +5,8 @@ decode():  RNNEncoder over the source query -> the decoder's initial state (the 
            -> ONE C-ABI call for the whole greedy decode (nir_seq2seq_decode_greedy, csrc/seq2seq.hip): LSTM step, Luong attention
            ('general' / 'dot' / 'mlp'), linear_out, generator + arg-max, the token fed back through a device lookup table.
 forward(): the teacher-forced loss on the differentiable HIP operators of autograd.py.
+score_candidates(): log P(candidate | source) of given next queries -- decode()'s encoder and initial state, the teacher-forced decoder pass,
+           then ONE generator call over the rows of all time steps that keeps the logits on chip (nir_score_gen_target, csrc/score.hip).
 
 Kept quirks of the reference:
   * RNNEncoder returns its final state in LENGTH-SORTED order (encoders/rnn_encoder.py:72-74,104-121; only the memory bank is un-sorted), so
@@ -252,6 +254,43 @@ class Seq2seq(nn.Module, lib.IdCheck):
                 args = front + mid + list(tail) + [W, lib.ptr(ws), ws.numel()] + outs
             lib.check(getattr(L, entry)(*args), entry)
         return out
+
+    # ---- eval: teacher-forced scoring of given candidates ---------------------------------------------------------------------------------
+    @torch.no_grad()
+    def score_candidates(self, source_rep, source_len, candidate_seq, candidate_rep=None, src_dict=None, tgt_dict=None, tgt2src=None):
+        """log P(candidate | source) for N candidate next queries per source (include/neuroir_score.h; the reference has no
+        counterpart beyond its training loss).  candidate_seq [B, N, TL]: target-vocabulary ids, BOS first, PAD behind the end; candidate_rep
+        [B, N, TL]: the embedder ids fed to the decoder (default: what decode() and decode_beam() feed -- the first token as it is, tgt2src[token]
+        behind it, <unk> outside the source vocabulary) -> {'token_logprobs': [B, N, TL - 1] (step t against token t + 1; 0 at PAD, behind the first EOS and for an
+        id outside the vocabulary), 'scores': [B, N] (their sum), 'lengths': LongTensor [B, N] (their number)}.
+        The encoder and the initial state are decode()'s; the teacher-forced decoder pass is forward()'s without dropout, the N (TL - 1) rows of
+        a source taken as its steps so that the memory bank is not repeated; then ONE generator call over all B N (TL - 1) rows that keeps the
+        logits on chip (`fuse_generator_argmax = False`: its plain form) and one pass over the sequences."""
+        dec_out, cand, w = self._candidate_rows(source_rep, source_len, candidate_seq, candidate_rep, src_dict, tgt_dict, tgt2src)
+        return suggest.score_rows(self, dec_out, cand, w.keep["gen_w"], w.keep["gen_b"], w.keep.get("gen_frag"))
+
+    def _candidate_rows(self, source_rep, source_len, candidate_seq, candidate_rep, src_dict, tgt_dict, tgt2src):
+        """score_candidates in front of the generator -> (the decoder outputs of the teacher-forced steps [B, N, TL - 1, nhid], candidate_seq as
+        int64, the packed decoder weights)"""
+        cand = lib.ids64(candidate_seq)
+        if cand.dim() != 3 or cand.shape[0] != source_rep.shape[0] or cand.shape[2] < 2:
+            raise ValueError("score_candidates: candidate_seq must be [B, N, TL] with TL >= 2 (got %s)" % (tuple(cand.shape),))
+        B, QL, table = self._decode_ready("score_candidates", source_rep, source_len)
+        lib.require_device(cand, candidate_rep)
+        N, T = int(cand.shape[1]), int(cand.shape[2]) - 1
+        src, _ = self._clean_ids(source_rep, None, table.shape[0])
+        lens = lib.ids64(source_len)
+        state, bank = self._encode_state(src, lens)
+        w = self._decoder_weights()
+        rep = suggest.candidate_inputs(self, cand, candidate_rep, src_dict, tgt_dict, tgt2src, int(w.struct.VT), table.shape[0])
+        temb = A.embed(rep[:, :, :-1].reshape(B * N, T), table)
+        h_all = self._cell_train(temb, [s.repeat_interleave(N, 0).contiguous() for s in state]).reshape(B, N * T, -1)      # rows (b, n, t)
+        att = self.decoder.decoder.attn
+        mask = torch.arange(QL, device=bank.device).unsqueeze(0) < lens.unsqueeze(1)
+        ctx = A.softmax_pool(self._align(h_all, bank), mask, bank, mask_div=N * T).view(B, N * T, -1)
+        mlp = self.attn_type == "mlp"
+        dec_out = A.linear(torch.cat((ctx, h_all), 2), att.linear_out.weight, att.linear_out.bias if mlp else None, act=None if mlp else "tanh")
+        return dec_out.view(B, N, T, -1), cand, w
 
     # ---- train: teacher-forced loss ---------------------------------------------------------------------------------------------------
     def _align(self, h_all, mem, att=None):

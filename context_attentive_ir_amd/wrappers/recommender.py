@@ -1,6 +1,6 @@
 """Recommender -- wrapper with the call shapes of neuroir.models.recommender.Recommender
 (/root/reference/neuroir/models/recommender.py:21-420) for Seq2seq: update(ex) is the training step, predict(ex) the greedy decode
-(+ the reference's host-side tail for a batch in its collate layout).  SessionRecommender is the same wrapper for HredQS, whose batches keep
+(+ the reference's host-side tail for a batch in its collate layout), score(ex, candidates) the log-likelihood of given next queries.  SessionRecommender is the same wrapper for HredQS, whose batches keep
 their session axis; CopyRecommender is the same wrapper for ACG, whose batches carry the copy generator's maps."""
 import torch
 
@@ -146,6 +146,38 @@ class Recommender(WrapperBase):
         """n-best suggestions, the one name every wrapper has: predict_beam here; CopyRecommender's is ACG's search over the copy generator's
         distribution; SessionRecommender (HredQS) keeps the session axis: predict_session_nbest."""
         return self.predict_beam(ex, beam_size)
+
+    # ---- scoring --------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def score(self, ex, candidates=None, length_normalize=False):
+        """Teacher-forced log-likelihood of given next queries (the network's score_candidates) -> {'token_logprobs',
+        'scores', 'lengths'} as it returns them.
+        candidates=None: the batch's own `target_seq` is the one candidate of every row (fed `target_words`); additionally 'nll' = -mean over
+        rows of `scores`, the reference forward's loss in eval mode, and 'perplexity' = exp(-sum scores / sum lengths).
+        With candidates -- a LongTensor [B, N, TL] (HredQS: [B, S, N, TL]) of target-vocabulary ids, BOS first, or ex['candidate_seq'], with
+        ex['candidate_rep'] as the ids fed to the decoder where given -- additionally 'ranking' [B, N] (HredQS: [B, S, N]): the candidates
+        best first by `scores`, or by scores / lengths with `length_normalize`, ties to the smaller n; usable as it is with eval.MRR /
+        eval.MAP.  Eager: candidate shapes vary per call, nothing is captured."""
+        self._poll_ids()
+        self.network.eval()
+        src, sl = self._dev(self._rows3(ex["source_words"])), self._dev(self._rows2(ex["source_lens"]))
+        own = candidates is None and "candidate_seq" not in ex
+        if own:
+            cand = self._rows3(ex["target_seq"]).unsqueeze(-2)
+            rep = self._rows3(ex["target_words"]).unsqueeze(-2)
+        else:
+            cand = ex["candidate_seq"] if candidates is None else candidates
+            rep = ex.get("candidate_rep") if isinstance(ex, dict) else None
+        out = self.network.score_candidates(source_rep=src, source_len=sl, candidate_seq=self._dev(cand),
+                                            candidate_rep=self._dev(rep) if rep is not None else None, src_dict=self.src_dict, tgt_dict=self.tgt_dict)
+        self._maybe_check_ids()
+        if own:
+            out["nll"] = -out["scores"].mean()
+            out["perplexity"] = torch.exp(-out["scores"].sum() / out["lengths"].sum().clamp(min=1))
+        else:
+            key = out["scores"] / out["lengths"].clamp(min=1) if length_normalize else out["scores"]
+            out["ranking"] = torch.sort(key, dim=-1, descending=True, stable=True)[1]
+        return out
 
     def _text(self, ex, pred_ids, attns):
         """the host-side tail of the reference's predict (models/recommender.py:294-309): tens2sen (utils/misc.py:36-62) + replace_unknown
@@ -376,6 +408,11 @@ class CopyRecommender(Recommender):
     def predict_beam(self, ex, beam_size):
         raise NotImplementedError("CopyRecommender.predict_beam: ACG's beam search is predict_nbest(ex, beam_size) -- its ids are EXTENDED ids and its "
                                   "batches carry the copy maps (DESIGN.md section 24)")
+
+    def score(self, ex, candidates=None, length_normalize=False):
+        raise NotImplementedError("CopyRecommender.score: the likelihood of a candidate under ACG is a sum over its collapsed extended distribution "
+                                  "(generator mass + copy mass per token), not the generator's alone -- scoring it is the follow-up to DESIGN.md "
+                                  "section 26")
 
     def _predict_nbest_body(self, ex, beam_size):
         self.network.eval()

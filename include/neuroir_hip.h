@@ -1151,6 +1151,7 @@ int nir_acg_copy_loss_bwd(const float* logits, int64_t ld, const float* switch_l
 #include "neuroir_acg_beam.h"
 /* ... and for HredQS, top-W on the split state of its folded step, in a fifth (ctypes: lib.HREDQS_BEAM_SIGNATURES). */
 #include "neuroir_hredqs_beam.h"
+#include "neuroir_score.h"
 
 #ifdef __cplusplus
 }
