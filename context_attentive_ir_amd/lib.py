@@ -378,6 +378,14 @@ SCORE_SIGNATURES = {
     "nir_score_sequences": (_i, [c_fp, c_ip, _l, _i, _l, _l, c_fp, c_ip, c_st]),
 }
 
+# The teacher-forced decoder pass of the session models, declared in include/neuroir_teacher.h (csrc/tf_attend.hip): grouped attention for many
+# decoder rows that share one memory bank.  A table of its own, like the ones above.
+TEACHER_SIGNATURES = {
+    "nir_tf_attend_fusable": (_i, [_i, _i, _i]),
+    "nir_tf_attend_workspace_bytes": (_z, [_l, _l, _i, _i]),
+    "nir_tf_attend": (_i, [c_fp, c_fp, c_fp, c_ip, c_ip, _l, _l, _l, _i, _i, c_fp, c_fp, _l, C.c_void_p, _z, c_st]),
+}
+
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_SPLIT2 = 0, 1, 2
 DTYPES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "bf16": DTYPE_BF16, "f32_split2": DTYPE_F32_SPLIT2}
 
@@ -394,7 +402,8 @@ def load():
                 "(hipcc, gfx950). The HIP path has no CPU fallback." % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(GRU_DECODE_SIGNATURES.items()) + list(BEAM_SIGNATURES.items()) + list(SESSION_BEAM_SIGNATURES.items())
-                                  + list(ACG_BEAM_SIGNATURES.items()) + list(HREDQS_BEAM_SIGNATURES.items()) + list(SCORE_SIGNATURES.items())):
+                                  + list(ACG_BEAM_SIGNATURES.items()) + list(HREDQS_BEAM_SIGNATURES.items()) + list(SCORE_SIGNATURES.items())
+                                  + list(TEACHER_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

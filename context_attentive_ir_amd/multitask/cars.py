@@ -747,6 +747,100 @@ class CARS(nn.Module, lib.IdCheck):
                                                              out["lengths"].view(B, SD, W))
         return out
 
+    # score_candidates: nir_tf_attend's fused form where the shape has one.  False: its plain form through the debug tunable exact_f32, set around
+    # that one call -- for tests and tools, which run with NIR_DEBUG_TUNABLES=1; a product process keeps the switches frozen and refuses it
+    fuse_teacher_attention = True
+
+    @torch.no_grad()
+    def score_candidates(self, states, candidate_seq, src_dict, tgt_dict, batch_size, session_len, encoded_source, source_len, session_attns,
+                         candidate_rep=None, tgt2src=None):
+        """log P(candidate | session prefix) for N candidate next queries per decode row, with the inputs of decode() (include/neuroir_teacher.h,
+        DESIGN.md section 27): candidate_seq [B, S-1, N, TL] target-vocabulary ids, BOS first, PAD behind the end; candidate_rep: the embedder
+        ids fed to the decoder (default: what decode() feeds back) -> {'token_logprobs': [B, S-1, N, TL-1], 'scores': [B, S-1, N], 'lengths':
+        LongTensor [B, S-1, N]} by section 26's rules.
+        Candidate row i = b (S-1) + j is paired with row i of `states`, with source row rowmap[i] and with the session term of row i, exactly
+        as decode() and decode_beam() pair their output rows.  The teacher-forced pass: the decoder LSTM over all Bd N sequences, ONE
+        nir_tf_attend over all Bd N (TL-1) rows -- the N (TL-1) rows of a decode row share its two banks, which are built once per call and never
+        repeated --, tanh(linear_out), token_prob_predictor1, the session term, and the generator's log-likelihood without the logits."""
+        c = self._score_front(states, candidate_seq, src_dict, tgt_dict, batch_size, session_len, encoded_source, source_len, session_attns,
+                              candidate_rep, tgt2src)
+        return self._score_tail(c, self._score_attend(c))
+
+    def _score_linear(self, x, wt, M, No, K, act=0):
+        out = torch.empty(M, No, device=x.device, dtype=torch.float32)
+        if M > 0:
+            lib.check(lib.load().nir_linear_f32(lib.ptr(x), K, None, None, 0, 0, 0, lib.ptr(wt), K, None, None, lib.ptr(out), No, M, No, K, act,
+                                                lib.stream()), "nir_linear_f32")
+        return out
+
+    def _score_front(self, states, candidate_seq, src_dict, tgt_dict, batch_size, session_len, encoded_source, source_len, session_attns,
+                     candidate_rep, tgt2src):
+        """score_candidates in front of the attention: the checks, the decoder LSTM over all candidates (suggest.candidate_front) and decode()'s
+        row bookkeeping -> a dict of what the two later parts read"""
+        if self.training:
+            raise NotImplementedError("HIP CARS.score_candidates runs in eval mode")
+        if self.no_recommender:
+            raise RuntimeError("decode needs the recommender (turn_recommender_off=False)")
+        assert all(s is not None for s in states)
+        table = self.embedder.word_embeddings.table
+        B, SD = int(batch_size), int(session_len)
+        VT = self.token_prob_predictor2.weight.shape[0]
+        rnn = self.decoder.decoder.rnn
+        h_all, cand = suggest.candidate_front(self, states, candidate_seq, candidate_rep, src_dict, tgt_dict, tgt2src, B, SD, table, rnn, VT)
+        lib.require_device(encoded_source, source_len)
+        dev = h_all.device
+        Bd, N, T = B * SD, int(cand.shape[2]), int(cand.shape[3]) - 1
+        enc = encoded_source.float().contiguous()
+        rows_src, QL, DQ = enc.shape
+        lens = lib.ids64(source_len.reshape(-1))
+        if rows_src != B * (SD + 1) or lens.numel() != rows_src:
+            raise RuntimeError("score_candidates: encoded_source must hold batch_size*(session_len+1) query rows")
+        i = torch.arange(Bd, device=dev)
+        rowmap = ((i // SD) * (SD + 1) + i % SD).contiguous()                       # the reference's [:, :-1] selection
+        cat = [a for a in session_attns if a is not None]
+        session_cat = torch.cat(cat, 2).reshape(rows_src, -1).float().contiguous() if cat else None
+        return dict(h_all=h_all, cand=cand, enc=enc, lens=lens, rowmap=rowmap, session_cat=session_cat, w=self._decoder_weights(), B=B, SD=SD, Bd=Bd,
+                    N=N, T=T, G=N * T, R=Bd * N * T, rows_src=rows_src, QL=QL, DQ=DQ, HD=int(rnn.hidden_size))
+
+    def _score_banks(self, c):
+        """the two banks over every source row, once per call (nir_cars_decode_greedy builds the same two): memory bank encoded_source
+        dec_attn_w^T, score bank encoded_source attn_q_w^T"""
+        w, n = c["w"], c["rows_src"] * c["QL"]
+        mem = self._score_linear(c["enc"], w.keep["dec_attn_w"], n, c["HD"], c["DQ"])
+        if "attn_q_w" in w.keep:
+            return mem, self._score_linear(c["enc"], w.keep["attn_q_w"], n, c["HD"], c["DQ"])
+        # score_j = (W_in h) . m_j = h . (W_in^T m_j)
+        return mem, self._score_linear(mem, w.keep["attn_in_w"].t().contiguous(), n, c["HD"], c["HD"])
+
+    def _score_attend(self, c, banks=None):
+        """-> cat [R, 2 HD] = [ctx ; h]: ONE nir_tf_attend over all rows, G = N (TL-1) rows per decode row"""
+        L = lib.load()
+        mem, sbank = self._score_banks(c) if banks is None else banks
+        catb = torch.empty(c["R"], 2 * c["HD"], device=mem.device, dtype=torch.float32)
+        if c["R"] > 0:
+            ws = lib.workspace(L.nir_tf_attend_workspace_bytes(c["Bd"], c["G"], c["QL"], c["HD"]), mem.device)
+            args = (lib.ptr(c["h_all"]), lib.ptr(mem), lib.ptr(sbank), lib.ptr(c["lens"]), lib.ptr(c["rowmap"]), c["Bd"], c["G"], c["rows_src"], c["QL"],
+                    c["HD"], lib.ptr(catb), None, 0, lib.ptr(ws), ws.numel(), lib.stream())
+            if self.fuse_teacher_attention:
+                lib.check(L.nir_tf_attend(*args), "nir_tf_attend")
+            else:                                                                    # the entry's plain form: what exact_f32 selects
+                with lib.tunable("exact_f32", 1, 0):
+                    lib.check(L.nir_tf_attend(*args), "nir_tf_attend")
+        return catb
+
+    def _score_tail(self, c, catb):
+        """tanh(linear_out [ctx ; h]) -> token_prob_predictor1 -> + the session term of the decode row -> the generator's log-likelihood"""
+        w, R, HD, Bd, G = c["w"], c["R"], c["HD"], c["Bd"], c["G"]
+        P = self.token_prob_predictor1.weight.shape[0]
+        dec_out = self._score_linear(catb, w.keep["attn_out_w"], R, HD, 2 * HD, act=1)
+        p1 = self._score_linear(dec_out, w.keep["pred1_w"], R, P, HD)
+        if c["session_cat"] is not None and R > 0:
+            sc = c["session_cat"]
+            sess = self._score_linear(sc.index_select(0, c["rowmap"]).contiguous(), w.keep["sess_w"], Bd, P, sc.shape[1])      # (shared + private2), row i
+            p1.view(Bd, G, P).add_(sess.unsqueeze(1))
+        frag = suggest.gen_frag_pack(self, self.token_prob_predictor2.weight, 0, attr="_pgen_score")
+        return suggest.score_rows(self, p1.view(c["B"], c["SD"], c["N"], c["T"], P), c["cand"], w.keep["pred2_w"], None, frag)
+
     def _tgt2src(self, src_dict, tgt_dict, dev):
         if src_dict is None or tgt_dict is None:
             return None

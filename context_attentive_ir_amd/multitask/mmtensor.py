@@ -210,3 +210,12 @@ class M_MATCH_TENSOR(nn.Module, lib.IdCheck):
         self._check_eval()
         return suggest.beam_decode(self, states, max_len, beam_size, src_dict, tgt_dict, batch_size, session_len, self.embedder.word_embeddings.table,
                                    self.decoder.decoder.rnn, self.generator, tgt2src, return_backptr)
+
+    @torch.no_grad()
+    def score_candidates(self, states, candidate_seq, src_dict, tgt_dict, batch_size, session_len, candidate_rep=None, tgt2src=None):
+        """log P(candidate | session prefix) for N candidate next queries per decode row, with the states of decode():
+        candidate_seq [B, S-1, N, TL] target-vocabulary ids, BOS first, PAD behind the end; candidate_rep: the embedder ids fed to the decoder
+        (default: what decode() feeds back) -> {'token_logprobs': [B, S-1, N, TL-1], 'scores': [B, S-1, N], 'lengths': LongTensor [B, S-1, N]}
+        by section 26's rules.  Candidate row b (S-1) + j starts from row b (S-1) + j of `states`, like decode()'s output rows."""
+        return suggest.plain_candidate_rows(self, states, candidate_seq, candidate_rep, src_dict, tgt_dict, batch_size, session_len,
+                                            self.embedder.word_embeddings.table, self.decoder.decoder.rnn, self.generator, tgt2src)

@@ -86,6 +86,60 @@ def score_rows(owner, dec_out, candidate_seq, gen_w, gen_b, gen_frag):
     return {"token_logprobs": logp.view(lead + (T,)), "scores": scores.view(lead), "lengths": lengths.view(lead)}
 
 
+def candidate_front(owner, states, candidate_seq, candidate_rep, src_dict, tgt_dict, tgt2src, batch_size, session_len, table, dec_rnn, VT):
+    """The front every session model's score_candidates shares: the shape checks, candidate_inputs, the embedding, ONE
+    GEMM for the input gates of all teacher-forced steps and ONE nir_birnn_steps_fwd over the Bd N sequences of TL - 1 steps, each started from
+    the state of its decode row -> (h_all [Bd N, TL - 1, H], candidate_seq as int64 [B, S-1, N, TL]).  Candidate row (i, n), i = b (S-1) + j,
+    starts from row i of `states` -- the pairing of decode() and decode_beam()."""
+    name = type(owner).__name__
+    if owner.training:
+        raise NotImplementedError("HIP %s.score_candidates runs in eval mode" % name)
+    B, SD = int(batch_size), int(session_len)
+    cand = lib.ids64(candidate_seq)
+    if cand.dim() != 4 or tuple(cand.shape[:2]) != (B, SD) or cand.shape[3] < 2:
+        raise ValueError("score_candidates: candidate_seq must be [B, S-1, N, TL] = [%d, %d, N, TL] with TL >= 2 (got %s)" % (B, SD, tuple(cand.shape)))
+    if candidate_rep is not None and candidate_rep.numel() != cand.numel():
+        raise ValueError("score_candidates: candidate_rep %s does not match candidate_seq %s" % (tuple(candidate_rep.shape), tuple(cand.shape)))
+    lib.require_device(*states, cand, candidate_rep, table)
+    L, st = lib.load(), lib.stream()
+    dec_h, dec_c = (s.reshape(-1, s.shape[-1]).float().contiguous() for s in states)
+    Bd, H = dec_h.shape
+    if Bd != B * SD:
+        raise RuntimeError("score_candidates: %d initial states for %d x %d decode rows" % (Bd, B, SD))
+    dev = dec_h.device
+    N, T = int(cand.shape[2]), int(cand.shape[3]) - 1
+    rep = candidate_inputs(owner, cand, candidate_rep, src_dict, tgt_dict, tgt2src, int(VT), table.shape[0])
+    M = Bd * N
+    h_all = torch.empty(M, T, H, device=dev, dtype=torch.float32)
+    if M == 0:
+        return h_all, cand
+    t = table.detach().float().contiguous()
+    emb = A.embed(rep[..., :-1].reshape(M, T), t).reshape(M * T, -1).contiguous()
+    wih, whh, bih, bhh = (getattr(dec_rnn, n).detach().float().contiguous() for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"))
+    E = emb.shape[1]
+    gates = torch.empty(M * T, 4 * H, device=dev, dtype=torch.float32)
+    lib.check(L.nir_linear_f32(lib.ptr(emb), E, None, None, 0, 0, 0, lib.ptr(wih), E, lib.ptr(bih), lib.ptr(bhh), lib.ptr(gates), 4 * H, M * T, 4 * H, E,
+                               0, st), "nir_linear_f32")
+    h0, c0 = dec_h.repeat_interleave(N, 0).contiguous(), dec_c.repeat_interleave(N, 0).contiguous()          # rows (i, n)
+    ws = lib.workspace(L.nir_bilstm_steps_workspace_bytes(M, H), dev)
+    lib.check(L.nir_birnn_steps_fwd(0, lib.ptr(gates), None, lib.ptr(whh), None, lib.ptr(h0), lib.ptr(c0), lib.ptr(h_all), None, None, None, M, T, H, 1,
+                                    lib.ptr(ws), ws.numel(), st), "nir_birnn_steps_fwd")
+    return h_all, cand
+
+
+def plain_candidate_rows(owner, states, candidate_seq, candidate_rep, src_dict, tgt_dict, batch_size, session_len, table, dec_rnn, generator,
+                         tgt2src=None):
+    """score_candidates of the two decoders without attention (M_MATCH_TENSOR, MNSRF): candidate_front, then score_rows on
+    the LSTM outputs with the generator's weight and bias.  The generator fragments are a pack of their own (`_pgen_score`): the beam's row cap
+    does not apply -- the score kernel stages a row block once per vocabulary range, not once per step -- and `fuse_generator_topk = False`
+    selects the plain generator form here as it does in the beam."""
+    VT = generator.weight.shape[0]
+    h_all, cand = candidate_front(owner, states, candidate_seq, candidate_rep, src_dict, tgt_dict, tgt2src, batch_size, session_len, table, dec_rnn, VT)
+    frag = gen_frag_pack(owner, generator.weight, 0, attr="_pgen_score")
+    gw, gb = generator.weight.detach().float().contiguous(), generator.bias.detach().float().contiguous()
+    return score_rows(owner, h_all.view(tuple(cand.shape[:3]) + h_all.shape[1:]), cand, gw, gb, frag)
+
+
 def plain_fold(owner, table, dec_rnn, t, p, H, dev):
     """(folded gate table, W_hh fragments) of a decoder without attention, or None -- shared by greedy_decode and beam_decode, cached on `owner`.
     The decoder LSTM's input is the previous token's embedding alone: gate rows folded per token + W_hh as fp16 term fragments, once per weight

@@ -348,6 +348,55 @@ class Multitask(WrapperBase):
             out.update(text)
         return out
 
+    # ---- teacher-forced scoring ---------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def score_suggestions(self, ex, candidates=None, length_normalize=False):
+        """Teacher-forced log-likelihood of given next queries under the session model (the network's score_candidates; DESIGN.md section 27;
+        `scores(ex)` are the raw click scores) -> {'click_scores': exactly predict()'s, 'token_logprobs', 'scores', 'lengths'}.
+        candidates=None: the batch's own `target_seq` [B, S-1, TL] is the one candidate of every decode row, fed `target_words`; additionally
+        'nll' = -mean(scores) and 'perplexity' = exp(-sum scores / sum lengths).
+        With candidates -- a LongTensor [B, S-1, N, TL] of target-vocabulary ids, BOS first, or ex['candidate_seq'], with ex['candidate_rep'] as
+        the ids fed to the decoder where given -- additionally 'ranking' [B, S-1, N]: the candidates best first by `scores`, or by scores /
+        lengths with `length_normalize`, ties to the smaller n; usable as it is with eval.MRR.  Eager: candidate shapes vary per call, nothing
+        is captured.  CARS with the recommender off returns the scoring keys as None, like predict_beam."""
+        own = candidates is None and "candidate_seq" not in ex
+        if self.type == "CARS" and self.network.no_recommender:
+            out = self.predict(ex, suggest=False)
+            out.pop("predictions", None)
+            out.update(token_logprobs=None, scores=None, lengths=None)
+            out.update(dict(nll=None, perplexity=None) if own else dict(ranking=None))
+            return out
+        self._poll_ids()
+        s, states, attns, enc = self._rank(ex, True)
+        out = {"click_scores": None}
+        if torch.is_tensor(s):
+            s = s.contiguous()
+            probs = torch.empty_like(s)
+            lib.check(lib.load().nir_softmax_rows(lib.ptr(s), lib.ptr(probs), s.shape[0] * s.shape[1], s.shape[2], lib.stream()), "nir_softmax_rows")
+            out["click_scores"] = probs
+        B, S = ex["source_words"].shape[0], ex["source_words"].shape[1]
+        if own:
+            cand = ex["target_seq"].reshape(B, S - 1, 1, -1)
+            rep = ex["target_words"].reshape(B, S - 1, 1, -1)
+        else:
+            cand = ex["candidate_seq"] if candidates is None else candidates
+            rep = ex.get("candidate_rep")
+        kw = dict(states=states, candidate_seq=self._dev(cand), src_dict=self.src_dict, tgt_dict=self.tgt_dict, batch_size=B, session_len=S - 1,
+                  candidate_rep=self._dev(rep) if rep is not None else None)
+        if self.type == "CARS":
+            kw.update(encoded_source=enc[0], source_len=enc[1], session_attns=attns)
+        out.update(self.network.score_candidates(**kw))
+        self._maybe_check_ids()
+        if out["click_scores"] is not None:
+            out["click_scores"] = self._checked(out["click_scores"])
+        if own:
+            out["nll"] = -out["scores"].mean()
+            out["perplexity"] = torch.exp(-out["scores"].sum() / out["lengths"].sum().clamp(min=1))
+        else:
+            key = out["scores"] / out["lengths"].clamp(min=1) if length_normalize else out["scores"]
+            out["ranking"] = torch.sort(key, dim=-1, descending=True, stable=True)[1]
+        return out
+
     def _finish_scores(self, s):
         probs, published = self._softmax_rows(s)
         self._maybe_check_ids(published)

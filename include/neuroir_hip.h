@@ -1152,6 +1152,8 @@ int nir_acg_copy_loss_bwd(const float* logits, int64_t ld, const float* switch_l
 /* ... and for HredQS, top-W on the split state of its folded step, in a fifth (ctypes: lib.HREDQS_BEAM_SIGNATURES). */
 #include "neuroir_hredqs_beam.h"
 #include "neuroir_score.h"
+/* The teacher-forced decoder pass of the session models: grouped attention (ctypes: lib.TEACHER_SIGNATURES). */
+#include "neuroir_teacher.h"
 
 #ifdef __cplusplus
 }
