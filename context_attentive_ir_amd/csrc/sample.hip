@@ -1,0 +1,665 @@
+// Sampling decode for the Seq2seq recommenders (include/neuroir_sample.h).  The reference has no sampler; the semantics
+// are this project's and stand at the head of the header.  A draw is the arg-max of the perturbed logits (Gumbel-max): the decode is the
+// S2sStepper of csrc/seq2seq.hip (s2s_gen.hpp) over R = B N decode rows and B source rows -- the beam's row layout r = n B + b -- with a fourth
+// tail behind the attentional output.  Per step, for all R rows at once:
+//   (h,c) = cell(emb(tok), (h,c)); attention over source row `row % B`; o = linear_out([ctx ; h])                                 S2sStepper::step
+//   per row: argmax_v fmaf(y_v, 1/tau, g_v) with its logit, and (max, sum) of exp(y), y = W_g o + b_g never written     sample_gen_kernel
+//   per row: the partials merge; logp = y - lse; freeze, cum, lengths, the prediction column, the next input id         sample_finish_kernel
+// or, plain form: the fp32 GEMM into workspace logits + sample_row_kernel (one workgroup per row); or, top_k > 0: nir_beam_gen_topk as it is
+// (either of its forms) + sample_topk_select_kernel.  All three read the noise from ONE device function, sample_noise4: Philox4x32-10 keyed by
+// the seed on the counter (v >> 2, source row, step, sample), four Gumbel values a call.  nir_sample_noise returns it to the tests.
+// sample_gen_kernel is the fifth consumer of the generator tile walk, next to arg-max (s2s_gen.hpp), its STATS form, top-W (csrc/beam.hip) and
+// the target logit (csrc/score.hip), and restates their staging, chunk clamp and fragment walk as they do: a change to one of those has to be
+// made here too (the shared body was measured slower).
+// Everything is enqueued on the caller's stream: no host synchronisation, no allocation, no atomics, every reduction in a fixed order.
+#include <cmath>
+#include "s2s_gen.hpp"
+#include "gen_rows.hpp"
+
+namespace nir {
+
+constexpr int SAMPLE_NONE = 0x7FFFFFFF;               // the index of "no candidate yet"
+
+// ---- the noise: one function for every form ------------------------------------------------------------------------------------------------
+struct SampleKey {
+    uint32_t k0, k1, step;                            // the seed's halves; the step t
+    uint32_t nsrc;                                    // decode row r draws as (source row r % nsrc, sample r / nsrc)
+};
+static inline SampleKey sample_key(uint64_t seed, int64_t step, int64_t nsrc) {
+    return SampleKey{(uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), (uint32_t)step, (uint32_t)nsrc};
+}
+
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants)
+// PRECONDITION: k0 and k1 are wave-uniform (every caller passes the seed's halves from a kernel argument): the empty asm below pins them to
+// scalar registers, which holds one value per wave.  The counter words may differ per lane.
+__device__ __forceinline__ void sample_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
+    asm volatile("" : "+s"(k0), "+s"(k1));            // the round keys are re-derived per call on the scalar unit: hoisted, the twenty of them spill SGPRs
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0;
+        c1 = l1;
+        c2 = h0 ^ c3 ^ k1;
+        c3 = l0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// g = -log(-log u), u = ((word >> 9) + 0.5) 2^-23.  w = -log u must keep its RELATIVE accuracy -- the outer log turns it into an absolute error of
+// g -- and the winners come from u -> 1, where w is tiny and a log of u itself has lost it.  So:
+//   u >  1/2   w = -log1p(-q) on the exact q = 1 - u, as 2 atanh(s), s = q / (2 - q) <= 1/3: s (2 + 2 s^2 / 3 + ... + 2 s^14 / 15), the next term
+//              below 2^-29 of the sum
+//   u <= 1/2   w = -ln 2 log2(u): |log2 u| >= 1, where one ulp of the hardware's log2 is a relative 2^-23
+// and g = -ln 2 log2(w) with the product carried in two terms (ocml's logf without its denormal and infinity branches: w lies in [2^-24, 16.7]).
+// |g - g64| is measured by tests/test_gpu_sample_envelope.py against sample_ref.E_G.
+__device__ __forceinline__ float sample_gumbel(uint32_t word) {
+    const uint32_t m = word >> 9;
+    const float u = ((float)m + 0.5f) * 0x1p-23f;
+    const float q = ((float)(0x7FFFFFu - m) + 0.5f) * 0x1p-23f;                  // 1 - u, exactly
+    const float s = q * __builtin_amdgcn_rcpf(2.0f - q), z = s * s;
+    float a = 2.0f / 15.0f;
+    a = fmaf(a, z, 2.0f / 13.0f);
+    a = fmaf(a, z, 2.0f / 11.0f);
+    a = fmaf(a, z, 2.0f / 9.0f);
+    a = fmaf(a, z, 2.0f / 7.0f);
+    a = fmaf(a, z, 2.0f / 5.0f);
+    a = fmaf(a, z, 2.0f / 3.0f);
+    a = fmaf(a, z, 2.0f);
+    const float w = u > 0.5f ? s * a : -0x1.62e430p-1f * __log2f(u);
+    const float l2 = __log2f(w), hi = l2 * 0x1.62e42ep-1f;
+    return -(hi + fmaf(l2, 0x1.efa39ep-25f, fmaf(l2, 0x1.62e42ep-1f, -hi)));
+}
+// the Philox words and the Gumbel values of vocabulary ids 4 vq .. 4 vq + 3 for (source row b, sample n)
+__device__ __forceinline__ void sample_noise4(const SampleKey& k, uint32_t vq, uint32_t b, uint32_t n, uint32_t (&word)[4], float (&g)[4]) {
+    sample_philox(vq, b, k.step, n, k.k0, k.k1, word);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) g[r] = sample_gumbel(word[r]);
+}
+
+// g [rows, VT] (and the words): one thread per (row, four ids)
+__global__ __launch_bounds__(256) void sample_noise_kernel(SampleKey k, int64_t rows, int64_t VT, float* __restrict__ g, uint32_t* __restrict__ words) {
+    const int64_t nq = (VT + 3) / 4;
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= rows * nq) return;
+    const int64_t row = e / nq, vq = e - row * nq;
+    uint32_t wd[4];
+    float gv[4];
+    sample_noise4(k, (uint32_t)vq, (uint32_t)(row % k.nsrc), (uint32_t)(row / k.nsrc), wd, gv);
+    for (int r = 0; r < 4; ++r) {
+        const int64_t v = 4 * vq + r;
+        if (v < VT) {
+            g[row * VT + v] = gv[r];
+            if (words) words[row * VT + v] = wd[r];
+        }
+    }
+}
+
+// ---- where a row's choice goes ------------------------------------------------------------------------------------------------------------------
+// Kernel-level entries (fin == NULL): token / logp / lse [rows], no freeze, no feedback.  Decode (fin given): the freeze rule on the row's state
+// fin / cum / len [rows] (row order r = n nsrc + b), column `step` of predictions and token_logprobs [nsrc, N, max_len], and the id the next
+// step reads, through lut (tgt2src), <unk> (1) outside [0, Vsrc).
+struct SampleOut {
+    int32_t* token;
+    float *logp, *lse;
+    int* fin;
+    float* cum;
+    int64_t* len;
+    int64_t* pred;
+    float* tlp;
+    int64_t* next_ids;
+    const int64_t* lut;
+    int64_t Vsrc, VT, nsrc;
+    int N, step, max_len;
+};
+__device__ __forceinline__ void sample_emit(const SampleOut& o, int64_t row, int idx, float y, float lse) {
+    const int tok = (idx >= 0 && (int64_t)idx < o.VT) ? idx : 0;                 // (only a row of NaN logits has no winner)
+    float lp = y - lse;
+    if (!o.fin) {
+        o.token[row] = tok;
+        o.logp[row] = lp;
+        if (o.lse) o.lse[row] = lse;
+        return;
+    }
+    int64_t t = tok;
+    if (o.fin[row]) {
+        t = NIR_BEAM_EOS;
+        lp = 0.f;
+    } else {
+        o.cum[row] += lp;
+        if (t == NIR_BEAM_EOS) { o.fin[row] = 1; o.len[row] = o.step + 1; }
+    }
+    const int64_t out = ((row % o.nsrc) * o.N + row / o.nsrc) * o.max_len + o.step;
+    o.pred[out] = t;
+    o.tlp[out] = lp;
+    const int64_t nxt = (o.lut && t < o.VT) ? o.lut[t] : t;
+    o.next_ids[row] = (nxt >= 0 && nxt < o.Vsrc) ? nxt : 1;
+}
+
+// (a, ai) in front of (b, bi): the larger perturbed value, the smaller index among equals
+__device__ __forceinline__ bool sample_before(float a, int ai, float b, int bi) { return a > b || (a == b && ai < bi); }
+// the best (perturbed value, index, its logit) of the wave, in every lane
+__device__ __forceinline__ void sample_wave_best(float& p, int& i, float& y) {
+#pragma unroll
+    for (int sh = 1; sh < 64; sh <<= 1) {
+        const float op = __shfl_xor(p, sh), oy = __shfl_xor(y, sh);
+        const int oi = __shfl_xor(i, sh);
+        if (sample_before(op, oi, p, i)) { p = op; i = oi; y = oy; }
+    }
+}
+
+// ---- generator + bias + (perturbed arg-max, its logit, max, sum): logits[b, v] = x[b, :] . W[v, :] + bias[v] never leave the chip -------------------
+// The staging, tiling, fragment format, chunked prefetch and logit expression of score_gen_target_kernel on BeamRowsF32 (the greedy kernel's
+// expression: top_k = 1 and the noise-free limit pick its token).  Epilogue per lane and row tile: the online-softmax pair of the UNPERTURBED y
+// (no PAD substitution: that is ACG's), one Philox call, four Gumbel values, the perturbed compare in ascending index order ('>' keeps the
+// first index on ties) carrying (perturbed best, index, that index's y).  Every wave writes one partial per decode row -- pv / pi / py / pm / ps
+// [part][Bd]; a wave without tiles writes (-inf, SAMPLE_NONE, 0, -inf, 0), which the merge passes over.
+template <int NBT>
+__global__ __launch_bounds__(256, 1) void sample_gen_kernel(const float* __restrict__ x, const _Float16* __restrict__ wfrag, const float* __restrict__ bias,
+                                                            int64_t VT, int64_t ntiles, int64_t Bd, int K, int nvr, SampleKey key, float inv_tau,
+                                                            float* __restrict__ pv, int* __restrict__ pi, float* __restrict__ py,
+                                                            float* __restrict__ pm, float* __restrict__ ps) {
+    extern __shared__ __attribute__((aligned(16))) _Float16 sample_sm[];       // [2 terms][ROWS][LD]
+    constexpr int ROWS = 16 * NBT;
+    const int LD = K + 8, KS = K / 32;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c16 = lane & 15, g4 = lane >> 4;
+    int vr;
+    int64_t b0;
+    BeamRowsF32::map<ROWS>(nvr, Bd, vr, b0);
+    const int64_t per_wg = (ntiles + nvr - 1) / nvr;
+    const int64_t t_lo = (int64_t)vr * per_wg, t_hi = min(ntiles, t_lo + per_wg);
+    {
+        constexpr int SB = 8;                                                     // loads in flight before the first is written
+        const int K4 = K / 4, total = ROWS * K4;                                  // a multiple of 256
+        for (int e0 = tid; e0 < total; e0 += 256 * SB) {
+            float4 sv[SB];
+#pragma unroll
+            for (int q = 0; q < SB; ++q) {
+                const int e = min(e0 + 256 * q, total - 1);
+                const int r = e / K4, c = e - r * K4;
+                const int64_t b = b0 + r;
+                sv[q] = BeamRowsF32::load(x, b < Bd ? b : Bd - 1, c, K);
+            }
+#pragma unroll
+            for (int q = 0; q < SB; ++q) {
+                const int e = e0 + 256 * q;
+                if (e < total) {
+                    const int r = e / K4, c = e - r * K4;
+                    float4 v = sv[q];
+                    if (b0 + r >= Bd) v = {};
+                    BeamRowsF32::store<ROWS>(sample_sm, r, c, LD, v);
+                }
+            }
+        }
+    }
+    uint32_t rb[NBT], rn[NBT];                                                    // (source row, sample) of this lane's decode rows
+    float best[NBT], by[NBT], rm[NBT], rs[NBT];
+    int bidx[NBT];
+#pragma unroll
+    for (int bt = 0; bt < NBT; ++bt) {
+        const uint32_t b = (uint32_t)(b0 + bt * 16 + c16);                        // Bd < 2^31
+        rn[bt] = b / key.nsrc;
+        rb[bt] = b - rn[bt] * key.nsrc;
+        best[bt] = -INFINITY; bidx[bt] = SAMPLE_NONE; by[bt] = 0.f;
+        rm[bt] = -INFINITY; rs[bt] = 0.f;
+    }
+    __syncthreads();
+    const int NCH = (KS + GEN_KC - 1) / GEN_KC;
+    const int64_t first = t_lo + wave;
+    const int64_t nt = first < t_hi ? (t_hi - first + 3) / 4 : 0;             // this wave's tiles: first, first + 4, ...
+    const int64_t items = nt * NCH;                                           // (tile, chunk) pairs, in order
+    f32x4 acc[NBT], acx[NBT];
+    auto load_w = [&](int64_t it, f16x8 (&wf)[GEN_KC][2]) {
+        const int64_t t = first + 4 * (it / NCH);
+        const int c = (int)(it % NCH);
+#pragma unroll
+        for (int u = 0; u < GEN_KC; ++u) {
+            const int ks = min(c * GEN_KC + u, KS - 1);                       // clamped: a duplicate k-step is not multiplied below
+            const _Float16* wp = wfrag + ((t * KS + ks) * 2 * 64 + lane) * 8;
+            wf[u][0] = *reinterpret_cast<const f16x8*>(wp);
+            wf[u][1] = *reinterpret_cast<const f16x8*>(wp + 512);
+        }
+    };
+    const _Float16* bp0 = sample_sm + c16 * LD + 8 * g4;
+    auto compute = [&](int64_t it, const f16x8 (&wf)[GEN_KC][2]) {
+        const int64_t t = first + 4 * (it / NCH);
+        const int c = (int)(it % NCH);
+        if (c == 0) {
+#pragma unroll
+            for (int bt = 0; bt < NBT; ++bt) { acc[bt] = (f32x4){0.f, 0.f, 0.f, 0.f}; acx[bt] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+        }
+#pragma unroll
+        for (int u = 0; u < GEN_KC; ++u) {
+            const int ks = c * GEN_KC + u;
+            if (ks < KS) {                                                    // wave-uniform
+                f16x8 b[NBT][2];
+#pragma unroll
+                for (int bt = 0; bt < NBT; ++bt) {
+                    b[bt][0] = *reinterpret_cast<const f16x8*>(bp0 + 32 * ks + bt * 16 * LD);
+                    b[bt][1] = *reinterpret_cast<const f16x8*>(bp0 + 32 * ks + bt * 16 * LD + ROWS * LD);
+                }
+#pragma unroll
+                for (int bt = 0; bt < NBT; ++bt) acx[bt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][1], b[bt][0], acx[bt], 0, 0, 0);
+#pragma unroll
+                for (int bt = 0; bt < NBT; ++bt) acc[bt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][0], b[bt][0], acc[bt], 0, 0, 0);
+#pragma unroll
+                for (int bt = 0; bt < NBT; ++bt) acx[bt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u][0], b[bt][1], acx[bt], 0, 0, 0);
+            }
+        }
+        if (c == NCH - 1) {
+            const int64_t v0 = t * 16 + 4 * g4;
+            float bv[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) bv[r] = (bias && v0 + r < VT) ? bias[v0 + r] : 0.f;
+#pragma unroll
+            for (int bt = 0; bt < NBT; ++bt) {
+                float y[4];
+                float m = rm[bt];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    y[r] = fmaf(acx[bt][r], SPLIT2_INV, acc[bt][r]) + bv[r];  // the greedy, top-k and scoring kernels' expression
+                    if (v0 + r >= VT) y[r] = -INFINITY;                       // padded tile rows: never win, add exp(-inf) = 0
+                    m = fmaxf(m, y[r]);
+                }
+                if (m > -INFINITY) {
+                    rs[bt] = rs[bt] * __expf(rm[bt] - m) + ((__expf(y[0] - m) + __expf(y[1] - m)) + (__expf(y[2] - m) + __expf(y[3] - m)));
+                    rm[bt] = m;
+                }
+                uint32_t wd[4];
+                float g[4];
+                sample_noise4(key, (uint32_t)(v0 >> 2), rb[bt], rn[bt], wd, g);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {                                 // ascending in r: '>' keeps the first index on ties
+                    const float p = fmaf(y[r], inv_tau, g[r]);                // (-inf for a padded row: inv_tau > 0)
+                    if (p > best[bt]) { best[bt] = p; bidx[bt] = (int)(v0 + r); by[bt] = y[r]; }
+                }
+            }
+        }
+    };
+    {
+        f16x8 wfA[GEN_KC][2], wfB[GEN_KC][2];
+        if (items > 0) load_w(0, wfA);
+        for (int64_t it = 0; it < items; it += 2) {
+            if (it + 1 < items) load_w(it + 1, wfB);
+            compute(it, wfA);
+            if (it + 1 >= items) break;
+            if (it + 2 < items) load_w(it + 2, wfA);
+            compute(it + 1, wfB);
+        }
+    }
+    // lanes l, l + 16, l + 32, l + 48 hold the same decode row: the pairs combine, the smaller index wins ties; only the g4 == 0 lane's value is
+    // written
+#pragma unroll
+    for (int bt = 0; bt < NBT; ++bt) {
+#pragma unroll
+        for (int sh = 16; sh <= 32; sh <<= 1) {
+            const float om = __shfl_xor(rm[bt], sh), os = __shfl_xor(rs[bt], sh);
+            const float m = fmaxf(om, rm[bt]);
+            rs[bt] = m > -INFINITY ? rs[bt] * __expf(rm[bt] - m) + os * __expf(om - m) : 0.f;
+            rm[bt] = m;
+            const float op = __shfl_xor(best[bt], sh), oy = __shfl_xor(by[bt], sh);
+            const int oi = __shfl_xor(bidx[bt], sh);
+            if (sample_before(op, oi, best[bt], bidx[bt])) { best[bt] = op; bidx[bt] = oi; by[bt] = oy; }
+        }
+        const int64_t b = b0 + bt * 16 + c16;
+        if (g4 == 0 && b < Bd) {
+            const int64_t slot = ((int64_t)vr * 4 + wave) * Bd + b;
+            pv[slot] = best[bt];
+            pi[slot] = bidx[bt];
+            py[slot] = by[bt];
+            pm[slot] = rm[bt];
+            ps[slot] = rs[bt];
+        }
+    }
+}
+
+// ---- the partials of one row -> (token, logp) and the tail: one wave per row, four rows a workgroup ------------------------------------------------------
+// Lane l takes parts l, l + 64, ... in order; the pairs combine through wave_max / wave_sum (a fixed tree), the candidates by comparisons alone
+// (ties in the perturbed value go to the smaller index, so the order of the parts does not enter).
+__global__ __launch_bounds__(256) void sample_finish_kernel(const float* __restrict__ pv, const int* __restrict__ pi, const float* __restrict__ py,
+                                                            const float* __restrict__ pm, const float* __restrict__ ps, int nparts, int64_t rows,
+                                                            SampleOut o) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                                                  // wave-uniform
+    float m = -INFINITY, s = 0.f, bp = -INFINITY, byv = 0.f;
+    int bi = SAMPLE_NONE;
+    for (int p = lane; p < nparts; p += 64) {
+        const int64_t slot = (int64_t)p * rows + row;
+        const float om = pm[slot], os = ps[slot];
+        const float nm = fmaxf(m, om);
+        if (nm > -INFINITY) s = s * expf(m - nm) + os * expf(om - nm);
+        m = nm;
+        const float cp = pv[slot];
+        const int ci = pi[slot];
+        if (sample_before(cp, ci, bp, bi)) { bp = cp; bi = ci; byv = py[slot]; }
+    }
+    const float M = wave_max(m);
+    const float S = wave_sum(m > -INFINITY ? s * expf(m - M) : 0.f);
+    sample_wave_best(bp, bi, byv);
+    if (lane == 0) sample_emit(o, row, bi, byv, M + logf(S));
+}
+
+// ---- plain form: one workgroup per row of [rows, VT] logits -> the same choice from the same noise -----------------------------------------------------------
+// A thread takes the ids 4 (tid + 256 i) .. + 3: one Philox call for four logits, as in the fused kernel.
+__global__ __launch_bounds__(256) void sample_row_kernel(const float* __restrict__ logits, int64_t VT, SampleKey key, float inv_tau, SampleOut o) {
+    __shared__ float lm[4], ls[4], lp[4], ly[4];
+    __shared__ int li[4];
+    const int64_t row = blockIdx.x;
+    const int tid = threadIdx.x;
+    const float* y = logits + row * VT;
+    const uint32_t rn = (uint32_t)row / key.nsrc, rb = (uint32_t)row - rn * key.nsrc;
+    float m = -INFINITY, s = 0.f, bp = -INFINITY, byv = 0.f;
+    int bi = SAMPLE_NONE;
+    for (int64_t v0 = 4 * (int64_t)tid; v0 < VT; v0 += 1024) {
+        uint32_t wd[4];
+        float g[4];
+        sample_noise4(key, (uint32_t)(v0 >> 2), rb, rn, wd, g);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {                                         // ascending: '>' keeps the first index on ties
+            if (v0 + r < VT) {
+                const float a = y[v0 + r];
+                const float nm = fmaxf(m, a);
+                if (nm > -INFINITY) s = s * expf(m - nm) + expf(a - nm);
+                m = nm;
+                const float p = fmaf(a, inv_tau, g[r]);
+                if (p > bp) { bp = p; bi = (int)(v0 + r); byv = a; }
+            }
+        }
+    }
+    const float wm = wave_max(m);
+    const float wsum = wave_sum(m > -INFINITY ? s * expf(m - wm) : 0.f);
+    sample_wave_best(bp, bi, byv);
+    if ((tid & 63) == 0) { lm[tid >> 6] = wm; ls[tid >> 6] = wsum; lp[tid >> 6] = bp; li[tid >> 6] = bi; ly[tid >> 6] = byv; }
+    __syncthreads();
+    if (tid == 0) {
+        const float M = fmaxf(fmaxf(lm[0], lm[1]), fmaxf(lm[2], lm[3]));
+        float S = 0.f;
+        for (int w = 0; w < 4; ++w) S += lm[w] > -INFINITY ? ls[w] * expf(lm[w] - M) : 0.f;
+        for (int w = 1; w < 4; ++w)
+            if (sample_before(lp[w], li[w], bp, bi)) { bp = lp[w]; bi = li[w]; byv = ly[w]; }
+        sample_emit(o, row, bi, byv, M + logf(S));
+    }
+}
+
+// ---- top-k form: the choice among a row's W largest logits, perturbed by the noise of their ids: one thread per row -------------------------------------------
+__global__ __launch_bounds__(256) void sample_topk_select_kernel(const float* __restrict__ top_val, const int* __restrict__ top_idx,
+                                                                 const float* __restrict__ lse, int64_t rows, int W, SampleKey key, float inv_tau,
+                                                                 SampleOut o) {
+    const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= rows) return;
+    const uint32_t rn = (uint32_t)row / key.nsrc, rb = (uint32_t)row - rn * key.nsrc;
+    float bp = -INFINITY, byv = 0.f;
+    int bi = SAMPLE_NONE;
+    for (int j = 0; j < W; ++j) {
+        const int v = top_idx[row * W + j];
+        if (v < 0 || (int64_t)v >= o.VT) continue;                            // an empty list slot
+        const float a = top_val[row * W + j];
+        uint32_t wd[4];
+        float g[4];
+        sample_noise4(key, (uint32_t)v >> 2, rb, rn, wd, g);
+        const int r = v & 3;
+        const float p = fmaf(a, inv_tau, r == 0 ? g[0] : r == 1 ? g[1] : r == 2 ? g[2] : g[3]);
+        if (sample_before(p, v, bp, bi)) { bp = p; bi = v; byv = a; }
+    }
+    sample_emit(o, row, bi, byv, lse[row]);
+}
+
+// ---- the decode's first and last launch --------------------------------------------------------------------------------------------------------------
+__global__ void sample_init_kernel(float* __restrict__ cum, int* __restrict__ fin, int64_t* __restrict__ len, int64_t n, int max_len) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    cum[e] = 0.f;
+    fin[e] = 0;
+    len[e] = max_len;
+}
+// one wave per decode row r = n B + b -> output (b, n): the score, the length and the attention rows of every step, attn_ws [max_len][R][QL]
+__global__ __launch_bounds__(64) void sample_end_kernel(const float* __restrict__ cum, const int64_t* __restrict__ len, const float* __restrict__ attn_ws,
+                                                        int64_t B, int N, int max_len, int QL, float* __restrict__ scores,
+                                                        int64_t* __restrict__ lengths, float* __restrict__ attn) {
+    const int64_t r = blockIdx.x, R = B * N;
+    const int64_t out = (r % B) * N + r / B;
+    const int lane = threadIdx.x;
+    if (lane == 0) { scores[out] = cum[r]; lengths[out] = len[r]; }
+    for (int t = 0; t < max_len; ++t) {
+        const float* ar = attn_ws + ((int64_t)t * R + r) * QL;
+        float* ao = attn + (out * max_len + t) * QL;
+        for (int q = lane; q < QL; q += 64) ao[q] = ar[q];
+    }
+}
+
+// ---- launchers ------------------------------------------------------------------------------------------------------------------------------------------
+static int sample_nparts(int64_t rows, int K, int64_t VT) { return rows > 0 ? 4 * s2s_nvr(rows, K, (VT + 15) / 16) : 0; }
+static size_t sample_gen_bytes(int64_t rows, int K, int64_t VT, bool fused) {
+    if (!fused) return (size_t)rows * VT * sizeof(float) + 256;
+    return (size_t)sample_nparts(rows, K, VT) * rows * 5 * sizeof(float) + 5 * 256;
+}
+static bool sample_tau_ok(float inv_tau) { return std::isfinite(inv_tau) && inv_tau > 0.f; }
+static bool sample_key_ok(int64_t step, int64_t nsrc, int64_t rows) { return step >= 0 && step <= 0xFFFFFFFFLL && nsrc >= 1 && nsrc < 0x7FFFFFFFLL && rows >= 0 && rows < 0x7FFFFFFFLL; }
+
+// one sampling step over the whole vocabulary on x [rows, K]: the fused kernel + finish, or the fp32 GEMM + one workgroup per row
+static int launch_sample_gen(bool fused, const float* x, int64_t rows, int K, const float* gen_w, const float* gen_b, const void* gen_frag, int64_t VT,
+                             const SampleKey& key, float inv_tau, void* ws, size_t ws_bytes, const SampleOut& o, hipStream_t st) {
+    Workspace a(ws, ws_bytes);
+    if (!fused) {
+        float* logits = a.take<float>((size_t)rows * VT);
+        NIR_PROPAGATE(launch_linear(x, K, nullptr, nullptr, 0, 0, 0, gen_w, K, gen_b, nullptr, logits, VT, rows, (int)VT, K, NIR_ACT_NONE, st));
+        {
+            ProfScope ps_("sample_row_kernel", st);
+            hipLaunchKernelGGL(sample_row_kernel, dim3((unsigned)rows), dim3(256), 0, st, logits, VT, key, inv_tau, o);
+        }
+        NIR_CHECK_LAUNCH("sample_row_kernel");
+        return 0;
+    }
+    const int64_t ntiles = (VT + 15) / 16;
+    const int nbt = gen_nbt(K), nvr = s2s_nvr(rows, K, ntiles), nparts = 4 * nvr;
+    const int64_t rb = (rows + 16 * nbt - 1) / (16 * nbt);
+    const size_t n = (size_t)nparts * rows;
+    float* pv = a.take<float>(n);
+    int* pi = a.take<int>(n);
+    float* py = a.take<float>(n);
+    float* pm = a.take<float>(n);
+    float* ps = a.take<float>(n);
+    {
+        ProfScope ps_(prof_shape_name("sample_gen_kernel", (long long)rows, (long long)VT, K), st);
+        const dim3 grid((unsigned)(nvr * rb));
+        if (nbt == 4) {
+            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(512));
+            (void)raised;
+            hipLaunchKernelGGL(sample_gen_kernel<4>, grid, dim3(256), gen_lds(K), st, x, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key, inv_tau,
+                               pv, pi, py, pm, ps);
+        } else {
+            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(1024));
+            (void)raised;
+            hipLaunchKernelGGL(sample_gen_kernel<2>, grid, dim3(256), gen_lds(K), st, x, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key, inv_tau,
+                               pv, pi, py, pm, ps);
+        }
+    }
+    NIR_CHECK_LAUNCH("sample_gen_kernel");
+    {
+        ProfScope ps_("sample_finish_kernel", st);
+        hipLaunchKernelGGL(sample_finish_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, pv, pi, py, pm, ps, nparts, rows, o);
+    }
+    NIR_CHECK_LAUNCH("sample_finish_kernel");
+    return 0;
+}
+static int launch_sample_topk_select(const float* top_val, const int* top_idx, const float* lse, int64_t rows, int W, const SampleKey& key, float inv_tau,
+                                     const SampleOut& o, hipStream_t st) {
+    {
+        ProfScope ps_("sample_topk_select_kernel", st);
+        hipLaunchKernelGGL(sample_topk_select_kernel, g1(rows), dim3(256), 0, st, top_val, top_idx, lse, rows, W, key, inv_tau, o);
+    }
+    NIR_CHECK_LAUNCH("sample_topk_select_kernel");
+    return 0;
+}
+
+// ---- the decode --------------------------------------------------------------------------------------------------------------------------------------
+static bool sample_dims_ok(int N, int top_k, int64_t VT) { return N >= 1 && top_k >= 0 && top_k <= NIR_BEAM_MAX_W && (int64_t)top_k <= VT; }
+struct SamplePlan {
+    S2sStepBufs s;                                    // the stepper's buffers, over R = B N decode rows
+    void* gen;                                        // the generator's workspace: sample_gen_bytes, or nir_beam_gen_topk's
+    size_t gen_bytes;
+    float *tval, *lse;                                // top_k > 0: the rows' lists [R, top_k] and lse [R]
+    int* tidx;
+    float* cum;                                       // [R] the state of the freeze rule
+    int* fin;
+    int64_t* len;
+    float* attn;                                      // [max_len][R][QL] the attention rows of every step
+    size_t bytes;
+};
+static SamplePlan sample_plan(void* ws, size_t cap, int64_t B, int QL, int N, int top_k, int max_len, int H, int64_t VT, int attn_type, bool fused, int cell,
+                              bool step16) {
+    Workspace a(ws, cap);
+    SamplePlan p;
+    const int64_t R = B * N;
+    p.s = s2s_step_bufs(a, R, B, QL, H, VT, attn_type, true, cell, step16);                 // (no logits of the stepper's: the generator's workspace below)
+    p.s.tgt = a.take<int64_t>((size_t)R);
+    if (cell == S2S_CELL_GRU) p.s.gru = a.take<float>(gru_step_scratch_floats(R, H));
+    p.gen_bytes = R == 0 ? 0 : top_k > 0 ? nir_beam_gen_topk_workspace_bytes(R, H, VT, top_k, fused) : sample_gen_bytes(R, H, VT, fused);
+    p.gen = a.take<char>(p.gen_bytes);
+    p.tval = a.take<float>((size_t)R * top_k);
+    p.tidx = a.take<int>((size_t)R * top_k);
+    p.lse = a.take<float>(top_k > 0 ? (size_t)R : 0);
+    p.cum = a.take<float>((size_t)R);
+    p.fin = a.take<int>((size_t)R);
+    p.len = a.take<int64_t>((size_t)R);
+    p.attn = a.take<float>((size_t)max_len * R * QL);
+    p.bytes = align_up(a.off, 256);
+    return p;
+}
+static size_t sample_decode_workspace_bytes(int64_t B, int QL, int N, int top_k, int max_len, const nir_seq2seq_decoder_weights* w, int cell) {
+    if (!s2s_weights_ok(w) || B < 0 || QL <= 0 || max_len <= 0 || !sample_dims_ok(N, top_k, w->VT) || B * N >= 0x7FFFFFFFLL) return 0;
+    return sample_plan(nullptr, 0, B, QL, N, top_k, max_len, w->H, w->VT, w->attn_type, s2s_fused(w), cell, s2s_step16(w)).bytes;
+}
+
+// The stepper of s2s_gen.hpp over N decode rows per source row, with the sampling tail behind the attentional output.  The state ping-pongs as
+// in the greedy decode: step s writes slot s & 1 and reads the other.
+static int s2s_sample_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, int N, int top_k,
+                             float inv_tau, uint64_t seed, const float* table, int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len,
+                             const nir_seq2seq_decoder_weights* w, void* workspace, size_t workspace_bytes, int64_t* predictions, float* token_logprobs,
+                             float* scores, int64_t* lengths, float* attentions, int cell, hipStream_t st) {
+    NIR_REQUIRE(N >= 1 && B >= 0 && B * (int64_t)N < 0x7FFFFFFFLL, "sample_seq2seq_decode: N < 1 or too many decode rows");
+    const int64_t R = B * N;
+    S2sStepper s{"sample_seq2seq_decode", w, cell, table, memory_bank, source_len, V, R, B, E, QL, st};
+    NIR_PROPAGATE(s.check(dec_h, dec_c, predictions && token_logprobs && scores && lengths && attentions, bos, max_len));
+    NIR_REQUIRE(sample_dims_ok(N, top_k, w->VT), "sample_seq2seq_decode: top_k outside 0 .. %d or above the target vocabulary", NIR_BEAM_MAX_W);
+    NIR_REQUIRE(sample_tau_ok(inv_tau), "sample_seq2seq_decode: inv_temperature must be finite and > 0");
+    const int H = w->H;
+    const bool fused = s.fused;
+    const SamplePlan p = sample_plan(workspace, workspace_bytes, B, QL, N, top_k, max_len, H, w->VT, w->attn_type, fused, cell, s.step16);
+    if (B == 0) return 0;                                 // nothing to enqueue: no workspace is needed either
+    if (!workspace || p.bytes > workspace_bytes) {
+        set_error("sample_seq2seq_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
+        return NIR_ERR_WORKSPACE;
+    }
+    s.b = p.s;
+    NIR_PROPAGATE(s.prepare(dec_h, bos, p.s.h16[1]));
+    hipLaunchKernelGGL(sample_init_kernel, g1(R), dim3(256), 0, st, p.cum, p.fin, p.len, R, max_len);
+    NIR_CHECK_LAUNCH("sample_init_kernel");
+    SampleOut o{nullptr, nullptr, nullptr, p.fin, p.cum, p.len, predictions, token_logprobs, p.s.tgt, tgt2src, V, w->VT, B, N, 0, max_len};
+    const float* hp = dec_h;
+    const float* cp = dec_c;
+    for (int step = 0; step < max_len; ++step) {
+        float* hn = p.s.h[step & 1];
+        float* cn = p.s.c[step & 1];
+        NIR_PROPAGATE(s.step(hp, cp, hn, cn, p.s.h16[(step + 1) & 1], p.s.h16[step & 1], p.attn + (int64_t)step * R * QL, QL));
+        const SampleKey key = sample_key(seed, step, B);
+        o.step = step;
+        if (top_k > 0) {
+            const int rc = nir_beam_gen_topk(p.s.ah, R, H, w->gen_w, w->gen_b, fused ? w->gen_frag : nullptr, w->VT, top_k, p.gen, p.gen_bytes, p.tval, p.tidx,
+                                             p.lse, (nir_stream_t)st);
+            if (rc != 0) return rc;
+            NIR_PROPAGATE(launch_sample_topk_select(p.tval, p.tidx, p.lse, R, top_k, key, inv_tau, o, st));
+        } else {
+            NIR_PROPAGATE(launch_sample_gen(fused, p.s.ah, R, H, w->gen_w, w->gen_b, w->gen_frag, w->VT, key, inv_tau, p.gen, p.gen_bytes, o, st));
+        }
+        hp = hn;
+        cp = cn;
+    }
+    {
+        ProfScope ps_("sample_end_kernel", st);
+        hipLaunchKernelGGL(sample_end_kernel, dim3((unsigned)R), dim3(64), 0, st, p.cum, p.len, p.attn, B, N, max_len, QL, scores, lengths, attentions);
+    }
+    NIR_CHECK_LAUNCH("sample_end_kernel");
+    return 0;
+}
+
+}  // namespace nir
+
+extern "C" int nir_sample_noise(uint64_t seed, int64_t step, int64_t nsrc, int64_t rows, int64_t VT, float* g, uint32_t* words, nir_stream_t stream) {
+    using namespace nir;
+    NIR_REQUIRE(g, "sample_noise: null pointer");
+    NIR_REQUIRE(sample_key_ok(step, nsrc, rows), "sample_noise: step outside [0, 2^32), nsrc < 1 or rows outside [0, 2^31)");
+    NIR_REQUIRE(VT > 0 && VT < 0x7FFFFFF0LL, "sample_noise: VT outside [1, 2^31 - 16)");
+    if (rows == 0) return 0;
+    const int64_t n = rows * ((VT + 3) / 4);
+    NIR_REQUIRE((n + 255) / 256 < 0x7FFFFFFFLL, "sample_noise: rows * VT too large for one launch");
+    hipLaunchKernelGGL(sample_noise_kernel, g1(n), dim3(256), 0, (hipStream_t)stream, sample_key(seed, step, nsrc), rows, VT, g, words);
+    NIR_CHECK_LAUNCH("sample_noise_kernel");
+    return 0;
+}
+
+extern "C" size_t nir_sample_gen_workspace_bytes(int64_t rows, int K, int64_t VT, int fused) {
+    using namespace nir;
+    if (rows <= 0 || rows >= 0x7FFFFFFFLL || K < 4 || K > 8192 || K % 4 || VT <= 0 || VT >= 0x7FFFFFF0LL) return 0;
+    return sample_gen_bytes(rows, K, VT, fused && gen_fusable(K, VT) && !tun(g_tun.exact_f32));
+}
+
+extern "C" int nir_sample_gen(const float* x, int64_t rows, int64_t nsrc, int K, const float* gen_w, const float* gen_b, const void* gen_frag, int64_t VT,
+                              float inv_temperature, uint64_t seed, int64_t step, void* workspace, size_t workspace_bytes, int32_t* token, float* logp,
+                              float* lse, nir_stream_t stream) {
+    using namespace nir;
+    NIR_REQUIRE(x && gen_w && token && logp, "sample_gen: null pointer");
+    NIR_REQUIRE(sample_key_ok(step, nsrc, rows), "sample_gen: step outside [0, 2^32), nsrc < 1 or rows outside [0, 2^31)");
+    NIR_REQUIRE(K >= 4 && K <= 8192 && K % 4 == 0, "sample_gen: K outside [4, 8192] or no multiple of 4");
+    NIR_REQUIRE(VT > 0 && VT < 0x7FFFFFF0LL, "sample_gen: VT outside [1, 2^31 - 16)");
+    NIR_REQUIRE(sample_tau_ok(inv_temperature), "sample_gen: inv_temperature must be finite and > 0");
+    if (rows == 0) return 0;
+    const bool fused = s2s_gen_fused(gen_frag, K, VT);
+    if (!workspace || workspace_bytes < sample_gen_bytes(rows, K, VT, fused)) {
+        set_error("sample_gen: workspace null or too small");
+        return NIR_ERR_WORKSPACE;
+    }
+    const SampleOut o{token, logp, lse, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, VT, nsrc, 1, 0, 1};
+    return launch_sample_gen(fused, x, rows, K, gen_w, gen_b, gen_frag, VT, sample_key(seed, step, nsrc), inv_temperature, workspace, workspace_bytes, o,
+                             (hipStream_t)stream);
+}
+
+extern "C" int nir_sample_topk_select(const float* top_val, const int32_t* top_idx, const float* lse, int64_t rows, int64_t nsrc, int W,
+                                      float inv_temperature, uint64_t seed, int64_t step, int32_t* token, float* logp, nir_stream_t stream) {
+    using namespace nir;
+    NIR_REQUIRE(top_val && top_idx && lse && token && logp, "sample_topk_select: null pointer");
+    NIR_REQUIRE(sample_key_ok(step, nsrc, rows), "sample_topk_select: step outside [0, 2^32), nsrc < 1 or rows outside [0, 2^31)");
+    NIR_REQUIRE(W >= 1 && W <= NIR_BEAM_MAX_W, "sample_topk_select: W outside [1, %d]", NIR_BEAM_MAX_W);
+    NIR_REQUIRE(sample_tau_ok(inv_temperature), "sample_topk_select: inv_temperature must be finite and > 0");
+    if (rows == 0) return 0;
+    const SampleOut o{token, logp, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0x7FFFFFF0LL, nsrc, 1, 0, 1};
+    return launch_sample_topk_select(top_val, top_idx, lse, rows, W, sample_key(seed, step, nsrc), inv_temperature, o, (hipStream_t)stream);
+}
+
+extern "C" size_t nir_sample_seq2seq_decode_workspace_bytes(int64_t B, int QL, int N, int top_k, int max_len, const nir_seq2seq_decoder_weights* w) {
+    return nir::sample_decode_workspace_bytes(B, QL, N, top_k, max_len, w, nir::S2S_CELL_LSTM);
+}
+extern "C" int nir_sample_seq2seq_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL,
+                                         int N, int top_k, float inv_temperature, uint64_t seed, const float* table, int64_t V, int E,
+                                         const int64_t* tgt2src, int64_t bos, int max_len, const nir_seq2seq_decoder_weights* w, void* workspace,
+                                         size_t workspace_bytes, int64_t* predictions, float* token_logprobs, float* scores, int64_t* lengths,
+                                         float* attentions, nir_stream_t stream) {
+    return nir::s2s_sample_decode(dec_h, dec_c, memory_bank, source_len, B, QL, N, top_k, inv_temperature, seed, table, V, E, tgt2src, bos, max_len, w,
+                                  workspace, workspace_bytes, predictions, token_logprobs, scores, lengths, attentions, nir::S2S_CELL_LSTM,
+                                  (hipStream_t)stream);
+}
+extern "C" size_t nir_sample_seq2seq_gru_decode_workspace_bytes(int64_t B, int QL, int N, int top_k, int max_len, const nir_seq2seq_decoder_weights* w) {
+    return nir::sample_decode_workspace_bytes(B, QL, N, top_k, max_len, w, nir::S2S_CELL_GRU);
+}
+extern "C" int nir_sample_seq2seq_gru_decode(const float* dec_h, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, int N, int top_k,
+                                             float inv_temperature, uint64_t seed, const float* table, int64_t V, int E, const int64_t* tgt2src,
+                                             int64_t bos, int max_len, const nir_seq2seq_decoder_weights* w, void* workspace, size_t workspace_bytes,
+                                             int64_t* predictions, float* token_logprobs, float* scores, int64_t* lengths, float* attentions,
+                                             nir_stream_t stream) {
+    return nir::s2s_sample_decode(dec_h, nullptr, memory_bank, source_len, B, QL, N, top_k, inv_temperature, seed, table, V, E, tgt2src, bos, max_len, w,
+                                  workspace, workspace_bytes, predictions, token_logprobs, scores, lengths, attentions, nir::S2S_CELL_GRU,
+                                  (hipStream_t)stream);
+}

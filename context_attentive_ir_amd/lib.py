@@ -386,6 +386,22 @@ TEACHER_SIGNATURES = {
     "nir_tf_attend": (_i, [c_fp, c_fp, c_fp, c_ip, c_ip, _l, _l, _l, _i, _i, c_fp, c_fp, _l, C.c_void_p, _z, c_st]),
 }
 
+# Sampling decode for Seq2seq, declared in include/neuroir_sample.h (csrc/sample.hip): every symbol starts with nir_sample_.  A table of its
+# own, like the ones above.  (the seed is a uint64, the inverse temperature a float)
+_u64, _f = C.c_uint64, C.c_float
+SAMPLE_SIGNATURES = {
+    "nir_sample_noise": (_i, [_u64, _l, _l, _l, _l, c_fp, C.c_void_p, c_st]),
+    "nir_sample_gen_workspace_bytes": (_z, [_l, _i, _l, _i]),
+    "nir_sample_gen": (_i, [c_fp, _l, _l, _i, c_fp, c_fp, C.c_void_p, _l, _f, _u64, _l, C.c_void_p, _z, C.c_void_p, c_fp, c_fp, c_st]),
+    "nir_sample_topk_select": (_i, [c_fp, C.c_void_p, c_fp, _l, _l, _i, _f, _u64, _l, C.c_void_p, c_fp, c_st]),
+    "nir_sample_seq2seq_decode_workspace_bytes": (_z, [_l, _i, _i, _i, _i, _W]),
+    "nir_sample_seq2seq_decode": (_i, [c_fp, c_fp, c_fp, c_ip, _l, _i, _i, _i, _f, _u64, c_fp, _l, _i, c_ip, _l, _i, _W, C.c_void_p, _z, c_ip, c_fp,
+                                       c_fp, c_ip, c_fp, c_st]),
+    "nir_sample_seq2seq_gru_decode_workspace_bytes": (_z, [_l, _i, _i, _i, _i, _W]),
+    "nir_sample_seq2seq_gru_decode": (_i, [c_fp, c_fp, c_ip, _l, _i, _i, _i, _f, _u64, c_fp, _l, _i, c_ip, _l, _i, _W, C.c_void_p, _z, c_ip, c_fp, c_fp,
+                                           c_ip, c_fp, c_st]),
+}
+
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_SPLIT2 = 0, 1, 2
 DTYPES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "bf16": DTYPE_BF16, "f32_split2": DTYPE_F32_SPLIT2}
 
@@ -403,7 +419,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(GRU_DECODE_SIGNATURES.items()) + list(BEAM_SIGNATURES.items()) + list(SESSION_BEAM_SIGNATURES.items())
                                   + list(ACG_BEAM_SIGNATURES.items()) + list(HREDQS_BEAM_SIGNATURES.items()) + list(SCORE_SIGNATURES.items())
-                                  + list(TEACHER_SIGNATURES.items())):
+                                  + list(TEACHER_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

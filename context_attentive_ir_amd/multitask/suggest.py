@@ -188,6 +188,7 @@ def greedy_decode(owner, states, max_len, src_dict, tgt_dict, batch_size, sessio
 
 
 FUSE_TOPK_MAX_ROWS = 384     # beam rows up to which the fused generator + top-k is the default (it wins at 384, loses at 768)
+FUSE_SAMPLE_MAX_ROWS = 512   # decode rows up to which the fused generator + Gumbel arg-max is the default (it wins at 512, not at 768)
 
 
 def gen_frag_pack(owner, weight, rows, attr="_pgen_beam"):

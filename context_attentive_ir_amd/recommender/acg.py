@@ -173,6 +173,13 @@ class ACG(Seq2seq):
         raise NotImplementedError("HIP %s.score_candidates: scoring under the copy generator's collapsed extended distribution is not built yet "
                                   "(the generator's log-likelihood alone would be another model's)" % type(self).__name__)
 
+    # ---- eval: sampling ------------------------------------------------------------------------------------------------------------
+    def decode_sample(self, *args, **kwargs):
+        """not Seq2seq's: ACG's next-token distribution is the collapsed extended one (generator mass plus copy mass), which the generator's
+        Gumbel arg-max does not draw from (DESIGN.md section 28 names it as a follow-up)"""
+        raise NotImplementedError("HIP %s.decode_sample: sampling from the copy generator's collapsed extended distribution is not built yet "
+                                  "(a draw from the generator's softmax alone would be another model's)" % type(self).__name__)
+
     # ---- eval: beam search ---------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def decode_beam(self, source_rep, source_len, max_len, beam_size, src_dict=None, tgt_dict=None, src_map=None, blank=None, fill=None,

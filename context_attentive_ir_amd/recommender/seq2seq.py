@@ -7,6 +7,9 @@ decode():  RNNEncoder over the source query -> the decoder's initial state (the 
 forward(): the teacher-forced loss on the differentiable HIP operators of autograd.py.
 score_candidates(): log P(candidate | source) of given next queries -- decode()'s encoder and initial state, the teacher-forced decoder pass,
            then ONE generator call over the rows of all time steps that keeps the logits on chip (nir_score_gen_target, csrc/score.hip).
+decode_sample(): N i.i.d. draws per source row at a temperature, over the vocabulary or each step's top-k -- decode_beam()'s stages with the
+           sampling tail behind the step: generator + Gumbel arg-max on counter-based noise in one kernel (nir_sample_seq2seq_decode,
+           csrc/sample.hip).
 
 Kept quirks of the reference:
   * RNNEncoder returns its final state in LENGTH-SORTED order (encoders/rnn_encoder.py:72-74,104-121; only the memory bank is un-sorted), so
@@ -18,6 +21,8 @@ Kept quirks of the reference:
   * nlayers != 1 (hyparam.SEQ2SEQ has 2) constructs, and fails in forward / decode like the reference: the encoder (use_last) hands over one
     layer's state, the decoder LSTM expects nlayers of them.
 """
+import math
+
 import torch
 import torch.nn as nn
 
@@ -63,6 +68,7 @@ class Seq2seq(nn.Module, lib.IdCheck):
     _ENTRY_CELL = ""                                     # the cell's part of a C entry's name
     _GREEDY_ENTRY = "nir_seq2seq%s_decode"               # + "_greedy" / "_workspace_bytes": nir_seq2seq_decode_greedy, nir_seq2seq_gru_decode_greedy
     _BEAM_ENTRY = "nir_beam_seq2seq%s_decode"            # (+ "_workspace_bytes"): nir_beam_seq2seq_decode, nir_beam_seq2seq_gru_decode
+    _SAMPLE_ENTRY = "nir_sample_seq2seq%s_decode"        # (+ "_workspace_bytes"): nir_sample_seq2seq_decode, nir_sample_seq2seq_gru_decode
 
     @staticmethod
     def _fold_table(table, wih, bih, bhh, H):
@@ -252,6 +258,70 @@ class Seq2seq(nn.Module, lib.IdCheck):
                     raise ValueError("%s.decode_beam: the shapes are outside the entry's range (%s)" % (type(self).__name__, entry))
                 ws = lib.workspace(nb, dev)
                 args = front + mid + list(tail) + [W, lib.ptr(ws), ws.numel()] + outs
+            lib.check(getattr(L, entry)(*args), entry)
+        return out
+
+    # ---- eval: sampling ------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def decode_sample(self, source_rep, source_len, max_len, num_samples, temperature=1.0, top_k=0, seed=0, src_dict=None, tgt_dict=None,
+                      tgt2src=None):
+        """`num_samples` i.i.d. draws per source row from the model's next-token distributions at `temperature`, over the whole target
+        vocabulary (top_k = 0) or restricted to each step's top_k most likely tokens (1 .. lib.BEAM_MAX_W; top_k = 1 is the greedy decode),
+        over max_len steps with no early stop (include/neuroir_sample.h; the reference has no counterpart)
+        -> {'predictions': LongTensor [B, N, max_len] (in sample order, EOS repeated behind the first EOS), 'token_logprobs': [B, N, max_len]
+        (the model's own log-probability of every token at temperature 1 over the full vocabulary, 0 behind EOS), 'scores': [B, N] (their
+        sum: what score_candidates([BOS] + sample) returns for a sample without PAD in front of its first EOS -- a whole-vocabulary draw can
+        emit PAD like any id, and score_candidates does not count that position), 'lengths': LongTensor [B, N], 'attentions': [B, N, max_len, QL]}.
+        The noise is a counter-based function of (seed, step, source row, sample, token): the same seed gives the same bits, and a source
+        row's samples do not depend on the rows decoded next to it.  The stages of decode_beam(): encoder, the sorted-order pairing, the state
+        repeated N times (row n B + b), ONE C call; the logits never leave the chip (`fuse_generator_argmax = False`, and for top_k > 0
+        `fuse_generator_topk = False`: the plain generator form; over the whole vocabulary it is also the default beyond
+        `fuse_sample_max_rows` = suggest.FUSE_SAMPLE_MAX_ROWS decode rows, where it was measured no slower)."""
+        if self.training:
+            raise NotImplementedError("HIP %s.decode_sample runs in eval mode" % type(self).__name__)
+        N, K, tau, seed = int(num_samples), int(top_k), float(temperature), int(seed)
+        if N < 1:
+            raise ValueError("decode_sample: num_samples %d < 1" % N)
+        if not (math.isfinite(tau) and tau > 0.0 and 1e-38 < 1.0 / tau < 3e38):      # (1 / tau travels as an fp32)
+            raise ValueError("decode_sample: temperature %r is not finite and > 0" % (temperature,))
+        if not 0 <= seed < (1 << 64):
+            raise ValueError("decode_sample: seed %d outside [0, 2^64)" % seed)
+        VT = int(self.generator.weight.shape[0])
+        if not 0 <= K <= min(lib.BEAM_MAX_W, VT):
+            raise ValueError("decode_sample: top_k %d outside {0} and [1, %d] (at most %d, and the target vocabulary's %d)"
+                             % (K, min(lib.BEAM_MAX_W, VT), lib.BEAM_MAX_W, VT))
+        B, QL, table = self._decode_ready("decode_sample", source_rep, source_len)
+        L = lib.load()
+        w = self._decoder_weights()
+        src, _ = self._clean_ids(source_rep, None, table.shape[0])
+        lens = lib.ids64(source_len)
+        state, bank = self._encode_state(src, lens)
+        state = [s.repeat(N, 1).contiguous() for s in state]                  # row n B + b
+        dev = bank.device
+        ws_ref = w.ref()
+        fuse = self.fuse_generator_topk if K > 0 else (self.fuse_generator_argmax
+                                                       and B * N <= getattr(self, "fuse_sample_max_rows", suggest.FUSE_SAMPLE_MAX_ROWS))
+        if w.struct.gen_frag and not fuse:
+            plain = lib.Seq2seqDecoderWeights.from_buffer_copy(w.struct)      # the same pack without the fragment: the plain generator form
+            plain.gen_frag = None
+            ws_ref = lib.C.byref(plain)
+        if tgt2src is None:
+            tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, VT, dev)
+        t = table.detach().float().contiguous()
+        max_len = int(max_len)
+        out = {"predictions": torch.empty(B, N, max_len, dtype=torch.int64, device=dev),
+               "token_logprobs": torch.empty(B, N, max_len, dtype=torch.float32, device=dev),
+               "scores": torch.empty(B, N, dtype=torch.float32, device=dev), "lengths": torch.empty(B, N, dtype=torch.int64, device=dev),
+               "attentions": torch.empty(B, N, max_len, QL, dtype=torch.float32, device=dev)}
+        if B > 0 and max_len > 0:
+            entry = self._SAMPLE_ENTRY % self._ENTRY_CELL
+            nb = getattr(L, entry + "_workspace_bytes")(B, QL, N, K, max_len, ws_ref)
+            if nb == 0:
+                raise ValueError("%s.decode_sample: the shapes are outside the entry's range (%s)" % (type(self).__name__, entry))
+            ws = lib.workspace(nb, dev)
+            args = [lib.ptr(s) for s in state] + [lib.ptr(bank), lib.ptr(lens), B, QL, N, K, 1.0 / tau, seed, lib.ptr(t), t.shape[0], t.shape[1],
+                                                  lib.ptr(tgt2src), BOS, max_len, ws_ref, lib.ptr(ws), ws.numel()]
+            args += [lib.ptr(out[k]) for k in ("predictions", "token_logprobs", "scores", "lengths", "attentions")] + [lib.stream()]
             lib.check(getattr(L, entry)(*args), entry)
         return out
 

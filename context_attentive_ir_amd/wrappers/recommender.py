@@ -147,6 +147,33 @@ class Recommender(WrapperBase):
         distribution; SessionRecommender (HredQS) keeps the session axis: predict_session_nbest."""
         return self.predict_beam(ex, beam_size)
 
+    # ---- sampling -------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def predict_samples(self, ex, num_samples, temperature=1.0, top_k=0, seed=None):
+        """`num_samples` i.i.d. suggestions per row drawn from the model (Seq2seq.decode_sample; the reference has no counterpart):
+        {'prediction_ids': LongTensor [B, N, max_query_len], 'token_logprobs': [B, N, max_query_len], 'scores': [B, N], 'lengths': LongTensor
+        [B, N], 'attentions': [B, N, max_query_len, QL], 'seed': the seed used}, in sample order (not sorted, duplicates possible); for a batch
+        in the reference's collate layout also `ex_ids`, `targets`, `src_sequences` and `predictions`: per row the list of its N strings, each
+        formed like predict()'s.  seed=None draws a 63-bit seed from torch's default CPU generator (no device synchronisation); calling again
+        with the returned 'seed' replays the draw bit for bit.  Always eager: the seed is a host argument of the C entry, so a captured graph
+        would replay one and the same draw."""
+        N = int(num_samples)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        self._poll_ids()
+        self.network.eval()
+        dec = self.network.decode_sample(source_rep=self._dev(self._rows3(ex["source_words"])), source_len=self._dev(self._rows2(ex["source_lens"])),
+                                         max_len=self.args.max_query_len, num_samples=N, temperature=temperature, top_k=top_k, seed=seed,
+                                         src_dict=self.src_dict, tgt_dict=self.tgt_dict)
+        self._maybe_check_ids()
+        out = {"prediction_ids": dec["predictions"], "token_logprobs": dec["token_logprobs"], "scores": dec["scores"], "lengths": dec["lengths"],
+               "attentions": dec["attentions"], "seed": int(seed)}
+        if all(k in ex for k in ("ids", "source_tokens", "target_tokens", "src_vocab")):
+            per = [Recommender._text(self, ex, out["prediction_ids"][:, n], out["attentions"][:, n]) for n in range(N)]
+            out.update(per[0])
+            out["predictions"] = [[per[n]["predictions"][b] for n in range(N)] for b in range(len(per[0]["predictions"]))]
+        return out
+
     # ---- scoring --------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def score(self, ex, candidates=None, length_normalize=False):
@@ -249,6 +276,11 @@ class SessionRecommender(Recommender):
     def predict_nbest(self, ex, beam_size):
         raise NotImplementedError("SessionRecommender.predict_nbest: the n-best suggestions of HredQS are predict_session_nbest(ex, beam_size) -- one "
                                   "list per session prefix, [B, S, W, max_query_len] (DESIGN.md section 25)")
+
+    def predict_samples(self, ex, num_samples, temperature=1.0, top_k=0, seed=None):
+        raise NotImplementedError("SessionRecommender.predict_samples: sampling for HredQS is not built yet -- the sampling tail "
+                                  "(include/neuroir_sample.h) stands behind the Seq2seq step only; its follow-up puts it behind the decoder "
+                                  "without attention (DESIGN.md section 28)")
 
     def _predict_session_nbest_body(self, ex, beam_size):
         self.network.eval()
@@ -413,6 +445,11 @@ class CopyRecommender(Recommender):
         raise NotImplementedError("CopyRecommender.score: the likelihood of a candidate under ACG is a sum over its collapsed extended distribution "
                                   "(generator mass + copy mass per token), not the generator's alone -- scoring it is the follow-up to DESIGN.md "
                                   "section 26")
+
+    def predict_samples(self, ex, num_samples, temperature=1.0, top_k=0, seed=None):
+        raise NotImplementedError("CopyRecommender.predict_samples: a draw under ACG comes from its collapsed extended distribution (generator mass "
+                                  "+ copy mass per token), not from the generator's softmax alone -- sampling it is the follow-up to DESIGN.md "
+                                  "section 28")
 
     def _predict_nbest_body(self, ex, beam_size):
         self.network.eval()

@@ -1154,6 +1154,8 @@ int nir_acg_copy_loss_bwd(const float* logits, int64_t ld, const float* switch_l
 #include "neuroir_score.h"
 /* The teacher-forced decoder pass of the session models: grouped attention (ctypes: lib.TEACHER_SIGNATURES). */
 #include "neuroir_teacher.h"
+/* Sampling decode for Seq2seq (both decoders' cells): fused generator + Gumbel arg-max (ctypes: lib.SAMPLE_SIGNATURES). */
+#include "neuroir_sample.h"
 
 #ifdef __cplusplus
 }
