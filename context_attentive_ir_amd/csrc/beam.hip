@@ -24,6 +24,7 @@
 #include <type_traits>
 #include "s2s_gen.hpp"
 #include "gen_rows.hpp"
+#include "beam_steps.hpp"
 
 namespace nir {
 
@@ -960,7 +961,7 @@ static int s2s_beam_decode(const float* dec_h, const float* dec_c, const float* 
 // =================================================================================================================================================
 
 // the first state of every beam row (and the repeated row map) into slot 0; h16first given: and its fp16 term pairs, for the fp16-term step
-static int launch_beam_repeat(const float* dec_h, const float* dec_c, int64_t Bd, int64_t R, int H, float* h0, float* c0, float* h16first,
+int launch_beam_repeat(const float* dec_h, const float* dec_c, int64_t Bd, int64_t R, int H, float* h0, float* c0, float* h16first,
                               const int64_t* map_in, int64_t* map_out, hipStream_t st) {
     hipLaunchKernelGGL(beam_repeat_kernel, dim3((unsigned)R), dim3(256), 0, st, (const float4*)dec_h, (const float4*)dec_c, Bd, H / 4, (float4*)h0, (float4*)c0,
                        map_in, map_out);
@@ -968,21 +969,12 @@ static int launch_beam_repeat(const float* dec_h, const float* dec_c, int64_t Bd
     if (h16first) NIR_PROPAGATE(launch_h16_pack(h0, R * H, reinterpret_cast<_Float16*>(h16first), st));
     return 0;
 }
-// the token-fed LSTM step of these decoders over the R beam rows, every step from state slot 0 (the reordered one) into slot 1; step16: the
-// fp16-term step on gate_fold and whh_frag, with the states' term pairs h16
-static LstmStepArgs beam_lstm_step_args(const float* table, const int64_t* tgt, int E, const float* w_ih, const float* w_hh, const float* b_ih,
-                                        const float* b_hh, bool step16, const float* gate_fold, const void* whh_frag, int64_t R, int H, float* const* h,
-                                        float* const* c, float* const* h16) {
-    LstmStepArgs a = LstmStepArgs::token_fed(table, tgt, E, w_ih, w_hh, b_ih, b_hh, R, H);
-    a.hprev[0] = h[0]; a.cprev[0] = c[0]; a.hnext[0] = h[1]; a.cnext[0] = c[1];
-    if (step16) {
-        a.fold_token_fed(gate_fold, whh_frag);
-        a.h16prev[0] = reinterpret_cast<const _Float16*>(h16[0]);
-        a.h16next[0] = reinterpret_cast<_Float16*>(h16[1]);
-    }
-    return a;
+// HredQS: pairing, repeat and split in one launch (hq_beam_begin_kernel) -- h0 / c0 [R, H] and, h16 given, the term pairs of h0
+int launch_hq_beam_begin(const float* hs, const float* cs, int64_t B, int64_t S, int H, int64_t R, float* h0, float* c0, _Float16* h16, hipStream_t st) {
+    hipLaunchKernelGGL(hq_beam_begin_kernel, g1(R * H), dim3(256), 0, st, hs, cs, B, S, H, R * H, h0, c0, h16);
+    NIR_CHECK_LAUNCH("hq_beam_begin_kernel");
+    return 0;
 }
-
 // ---- CARS ----------------------------------------------------------------------------------------------------------------------------------
 // The step of nir_cars_decode_greedy restated over R rows (its keyed arg-max path ties the greedy loop's launches to its own tail; the greedy
 // entry stays as it is): prepare once -- the banks mem / memq over the source rows, the session projection over the R rows through the
@@ -993,7 +985,6 @@ struct CarsBeamPlan {
     BeamTail t;
     size_t bytes;
 };
-static bool cars_beam_step16(const nir_cars_decoder_weights* w) { return w->rnn_gate_fold && w->rnn_whh_frag && w->HD % 32 == 0 && !tun(g_tun.exact_f32); }
 static CarsBeamPlan cars_beam_plan(void* ws, size_t cap, int64_t rows_src, int64_t Bd, int QL, int W, int max_len, const nir_cars_decoder_weights* w,
                                    bool fused, int32_t* backptr) {
     Workspace a(ws, cap);
@@ -1015,10 +1006,6 @@ static CarsBeamPlan cars_beam_plan(void* ws, size_t cap, int64_t rows_src, int64
     p.t.carve(a, Bd, W, max_len, fused ? beam_nparts(R, P, w->VT) : 1, fused, backptr);
     p.bytes = align_up(a.off, 256);
     return p;
-}
-static bool cars_beam_weights_ok(const nir_cars_decoder_weights* w) {
-    return w && w->rnn_wih && w->rnn_whh && w->rnn_bih && w->rnn_bhh && w->attn_out_w && w->dec_attn_w && w->pred1_w && w->pred2_w &&
-           (w->attn_in_w || w->attn_q_w) && w->HD > 0 && w->DQ > 0 && w->P > 0 && w->KS >= 0 && w->VT > 0 && w->HD % 4 == 0 && w->DQ % 4 == 0 && w->P % 4 == 0;
 }
 
 }  // namespace nir
@@ -1227,10 +1214,7 @@ extern "C" int nir_beam_hredqs_decode(const float* h_steps, const float* c_steps
         fast ? hq_beam_nparts(R, H, VT) : 1, tgt2src, V, bos, W, max_len, workspace, workspace_bytes, predictions, scores, lengths, backptr, st,
         [&](const PlainBeamPlan& p) {
             // pairing, repeat and split in one launch: every beam of source row i starts from step i / B of session i % B
-            hipLaunchKernelGGL(hq_beam_begin_kernel, g1(R * H), dim3(256), 0, st, h_steps, c_steps, B, S, H, R * H, p.h[0], p.c[0],
-                               fast ? reinterpret_cast<_Float16*>(p.h16[0]) : nullptr);
-            NIR_CHECK_LAUNCH("hq_beam_begin_kernel");
-            return 0;
+            return launch_hq_beam_begin(h_steps, c_steps, B, S, H, R, p.h[0], p.c[0], fast ? reinterpret_cast<_Float16*>(p.h16[0]) : nullptr, st);
         },
         [&](const PlainBeamPlan& p) {
             return launch_hq_beam_gen_topk(reinterpret_cast<const _Float16*>(p.h16[1]), w->gen_frag, w->gen_b, VT, R, H, W, p.t.part, st);

@@ -11,24 +11,17 @@
 // sample_gen_kernel is the fifth consumer of the generator tile walk, next to arg-max (s2s_gen.hpp), its STATS form, top-W (csrc/beam.hip) and
 // the target logit (csrc/score.hip), and restates their staging, chunk clamp and fragment walk as they do: a change to one of those has to be
 // made here too (the shared body was measured slower).
+// The types, argument checks and launchers other units need stand in sample_tail.hpp (csrc/session_sample.hip: the same tail behind the steps
+// of HredQS and the session models); the kernels live here.
 // Everything is enqueued on the caller's stream: no host synchronisation, no allocation, no atomics, every reduction in a fixed order.
 #include <cmath>
 #include "s2s_gen.hpp"
 #include "gen_rows.hpp"
+#include "sample_tail.hpp"
 
 namespace nir {
 
-constexpr int SAMPLE_NONE = 0x7FFFFFFF;               // the index of "no candidate yet"
-
 // ---- the noise: one function for every form ------------------------------------------------------------------------------------------------
-struct SampleKey {
-    uint32_t k0, k1, step;                            // the seed's halves; the step t
-    uint32_t nsrc;                                    // decode row r draws as (source row r % nsrc, sample r / nsrc)
-};
-static inline SampleKey sample_key(uint64_t seed, int64_t step, int64_t nsrc) {
-    return SampleKey{(uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), (uint32_t)step, (uint32_t)nsrc};
-}
-
 // Philox4x32-10 (Salmon et al., SC'11; the Random123 constants)
 // PRECONDITION: k0 and k1 are wave-uniform (every caller passes the seed's halves from a kernel argument): the empty asm below pins them to
 // scalar registers, which holds one value per wave.  The counter words may differ per lane.
@@ -100,19 +93,6 @@ __global__ __launch_bounds__(256) void sample_noise_kernel(SampleKey k, int64_t 
 // Kernel-level entries (fin == NULL): token / logp / lse [rows], no freeze, no feedback.  Decode (fin given): the freeze rule on the row's state
 // fin / cum / len [rows] (row order r = n nsrc + b), column `step` of predictions and token_logprobs [nsrc, N, max_len], and the id the next
 // step reads, through lut (tgt2src), <unk> (1) outside [0, Vsrc).
-struct SampleOut {
-    int32_t* token;
-    float *logp, *lse;
-    int* fin;
-    float* cum;
-    int64_t* len;
-    int64_t* pred;
-    float* tlp;
-    int64_t* next_ids;
-    const int64_t* lut;
-    int64_t Vsrc, VT, nsrc;
-    int N, step, max_len;
-};
 __device__ __forceinline__ void sample_emit(const SampleOut& o, int64_t row, int idx, float y, float lse) {
     const int tok = (idx >= 0 && (int64_t)idx < o.VT) ? idx : 0;                 // (only a row of NaN logits has no winner)
     float lp = y - lse;
@@ -155,8 +135,11 @@ __device__ __forceinline__ void sample_wave_best(float& p, int& i, float& y) {
 // (no PAD substitution: that is ACG's), one Philox call, four Gumbel values, the perturbed compare in ascending index order ('>' keeps the
 // first index on ties) carrying (perturbed best, index, that index's y).  Every wave writes one partial per decode row -- pv / pi / py / pm / ps
 // [part][Bd]; a wave without tiles writes (-inf, SAMPLE_NONE, 0, -inf, 0), which the merge passes over.
-template <int NBT>
-__global__ __launch_bounds__(256, 1) void sample_gen_kernel(const float* __restrict__ x, const _Float16* __restrict__ wfrag, const float* __restrict__ bias,
+// ROWSRC (gen_rows.hpp), as in beam_gen_topk_kernel: BeamRowsF32 -- fp32 rows split on load, a row block's ranges adjacent (s2s_nvr) -- or
+// BeamRowsSplit -- the fp16 term pairs h16 [row][K/8][2][8] the folded LSTM step leaves (HredQS): 16-byte copies into the
+// planes, hq_nvr ranges on the XCD-aware grid.  The instantiations on BeamRowsF32 compile to the registers they had before the parameter.
+template <class ROWSRC, int NBT>
+__global__ __launch_bounds__(256, 1) void sample_gen_kernel(const typename ROWSRC::elem* __restrict__ x, const _Float16* __restrict__ wfrag, const float* __restrict__ bias,
                                                             int64_t VT, int64_t ntiles, int64_t Bd, int K, int nvr, SampleKey key, float inv_tau,
                                                             float* __restrict__ pv, int* __restrict__ pi, float* __restrict__ py,
                                                             float* __restrict__ pm, float* __restrict__ ps) {
@@ -167,29 +150,29 @@ __global__ __launch_bounds__(256, 1) void sample_gen_kernel(const float* __restr
     const int c16 = lane & 15, g4 = lane >> 4;
     int vr;
     int64_t b0;
-    BeamRowsF32::map<ROWS>(nvr, Bd, vr, b0);
+    ROWSRC::template map<ROWS>(nvr, Bd, vr, b0);
     const int64_t per_wg = (ntiles + nvr - 1) / nvr;
     const int64_t t_lo = (int64_t)vr * per_wg, t_hi = min(ntiles, t_lo + per_wg);
     {
         constexpr int SB = 8;                                                     // loads in flight before the first is written
         const int K4 = K / 4, total = ROWS * K4;                                  // a multiple of 256
         for (int e0 = tid; e0 < total; e0 += 256 * SB) {
-            float4 sv[SB];
+            typename ROWSRC::chunk sv[SB];
 #pragma unroll
             for (int q = 0; q < SB; ++q) {
                 const int e = min(e0 + 256 * q, total - 1);
                 const int r = e / K4, c = e - r * K4;
                 const int64_t b = b0 + r;
-                sv[q] = BeamRowsF32::load(x, b < Bd ? b : Bd - 1, c, K);
+                sv[q] = ROWSRC::load(x, b < Bd ? b : Bd - 1, c, K);
             }
 #pragma unroll
             for (int q = 0; q < SB; ++q) {
                 const int e = e0 + 256 * q;
                 if (e < total) {
                     const int r = e / K4, c = e - r * K4;
-                    float4 v = sv[q];
+                    typename ROWSRC::chunk v = sv[q];
                     if (b0 + r >= Bd) v = {};
-                    BeamRowsF32::store<ROWS>(sample_sm, r, c, LD, v);
+                    ROWSRC::template store<ROWS>(sample_sm, r, c, LD, v);
                 }
             }
         }
@@ -423,6 +406,7 @@ __global__ __launch_bounds__(64) void sample_end_kernel(const float* __restrict_
     const int64_t out = (r % B) * N + r / B;
     const int lane = threadIdx.x;
     if (lane == 0) { scores[out] = cum[r]; lengths[out] = len[r]; }
+    if (QL <= 0 || !attn) return;                                             // the decoders without attention output (section 29)
     for (int t = 0; t < max_len; ++t) {
         const float* ar = attn_ws + ((int64_t)t * R + r) * QL;
         float* ao = attn + (out * max_len + t) * QL;
@@ -432,15 +416,13 @@ __global__ __launch_bounds__(64) void sample_end_kernel(const float* __restrict_
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------------------------------------
 static int sample_nparts(int64_t rows, int K, int64_t VT) { return rows > 0 ? 4 * s2s_nvr(rows, K, (VT + 15) / 16) : 0; }
-static size_t sample_gen_bytes(int64_t rows, int K, int64_t VT, bool fused) {
+size_t sample_gen_bytes(int64_t rows, int K, int64_t VT, bool fused) {
     if (!fused) return (size_t)rows * VT * sizeof(float) + 256;
     return (size_t)sample_nparts(rows, K, VT) * rows * 5 * sizeof(float) + 5 * 256;
 }
-static bool sample_tau_ok(float inv_tau) { return std::isfinite(inv_tau) && inv_tau > 0.f; }
-static bool sample_key_ok(int64_t step, int64_t nsrc, int64_t rows) { return step >= 0 && step <= 0xFFFFFFFFLL && nsrc >= 1 && nsrc < 0x7FFFFFFFLL && rows >= 0 && rows < 0x7FFFFFFFLL; }
 
 // one sampling step over the whole vocabulary on x [rows, K]: the fused kernel + finish, or the fp32 GEMM + one workgroup per row
-static int launch_sample_gen(bool fused, const float* x, int64_t rows, int K, const float* gen_w, const float* gen_b, const void* gen_frag, int64_t VT,
+int launch_sample_gen(bool fused, const float* x, int64_t rows, int K, const float* gen_w, const float* gen_b, const void* gen_frag, int64_t VT,
                              const SampleKey& key, float inv_tau, void* ws, size_t ws_bytes, const SampleOut& o, hipStream_t st) {
     Workspace a(ws, ws_bytes);
     if (!fused) {
@@ -466,14 +448,14 @@ static int launch_sample_gen(bool fused, const float* x, int64_t rows, int K, co
         ProfScope ps_(prof_shape_name("sample_gen_kernel", (long long)rows, (long long)VT, K), st);
         const dim3 grid((unsigned)(nvr * rb));
         if (nbt == 4) {
-            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(512));
+            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<BeamRowsF32, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(512));
             (void)raised;
-            hipLaunchKernelGGL(sample_gen_kernel<4>, grid, dim3(256), gen_lds(K), st, x, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key, inv_tau,
+            hipLaunchKernelGGL((sample_gen_kernel<BeamRowsF32, 4>), grid, dim3(256), gen_lds(K), st, x, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key, inv_tau,
                                pv, pi, py, pm, ps);
         } else {
-            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(1024));
+            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<BeamRowsF32, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(1024));
             (void)raised;
-            hipLaunchKernelGGL(sample_gen_kernel<2>, grid, dim3(256), gen_lds(K), st, x, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key, inv_tau,
+            hipLaunchKernelGGL((sample_gen_kernel<BeamRowsF32, 2>), grid, dim3(256), gen_lds(K), st, x, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key, inv_tau,
                                pv, pi, py, pm, ps);
         }
     }
@@ -485,7 +467,49 @@ static int launch_sample_gen(bool fused, const float* x, int64_t rows, int K, co
     NIR_CHECK_LAUNCH("sample_finish_kernel");
     return 0;
 }
-static int launch_sample_topk_select(const float* top_val, const int* top_idx, const float* lse, int64_t rows, int W, const SampleKey& key, float inv_tau,
+// partials per row of the split-state form: one per wave of every vocabulary range of hq_nvr's grid (one workgroup per CU, XCD-aware)
+static int sample_split_nparts(int64_t rows, int K, int64_t VT) {
+    return rows > 0 ? 4 * hq_nvr((rows + 16 * gen_nbt(K) - 1) / (16 * gen_nbt(K)), (VT + 15) / 16) : 0;
+}
+size_t sample_gen_split_bytes(int64_t rows, int K, int64_t VT) { return (size_t)sample_split_nparts(rows, K, VT) * rows * 5 * sizeof(float) + 5 * 256; }
+// one sampling step over the whole vocabulary on the split state h16 [rows][K/8][2][8]: sample_gen_kernel on BeamRowsSplit + the same finish
+int launch_sample_gen_split(const _Float16* h16, int64_t rows, int K, const float* gen_b, const void* gen_frag, int64_t VT, const SampleKey& key,
+                            float inv_tau, void* ws, size_t ws_bytes, const SampleOut& o, hipStream_t st) {
+    Workspace a(ws, ws_bytes);
+    const int64_t ntiles = (VT + 15) / 16;
+    const int nbt = gen_nbt(K);
+    const int64_t nrb = (rows + 16 * nbt - 1) / (16 * nbt);
+    const int nvr = hq_nvr(nrb, ntiles), nparts = 4 * nvr;
+    const size_t n = (size_t)nparts * rows;
+    float* pv = a.take<float>(n);
+    int* pi = a.take<int>(n);
+    float* py = a.take<float>(n);
+    float* pm = a.take<float>(n);
+    float* ps = a.take<float>(n);
+    {
+        ProfScope ps_(prof_shape_name("hq_sample_gen_kernel", (long long)rows, (long long)VT, K), st);
+        const dim3 grid((unsigned)(nvr * nrb));
+        if (nbt == 4) {
+            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<BeamRowsSplit, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(512));
+            (void)raised;
+            hipLaunchKernelGGL((sample_gen_kernel<BeamRowsSplit, 4>), grid, dim3(256), gen_lds(K), st, h16, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key,
+                               inv_tau, pv, pi, py, pm, ps);
+        } else {
+            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<BeamRowsSplit, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(1024));
+            (void)raised;
+            hipLaunchKernelGGL((sample_gen_kernel<BeamRowsSplit, 2>), grid, dim3(256), gen_lds(K), st, h16, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key,
+                               inv_tau, pv, pi, py, pm, ps);
+        }
+    }
+    NIR_CHECK_LAUNCH("hq_sample_gen_kernel");
+    {
+        ProfScope ps_("sample_finish_kernel", st);
+        hipLaunchKernelGGL(sample_finish_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, pv, pi, py, pm, ps, nparts, rows, o);
+    }
+    NIR_CHECK_LAUNCH("sample_finish_kernel");
+    return 0;
+}
+int launch_sample_topk_select(const float* top_val, const int* top_idx, const float* lse, int64_t rows, int W, const SampleKey& key, float inv_tau,
                                      const SampleOut& o, hipStream_t st) {
     {
         ProfScope ps_("sample_topk_select_kernel", st);
@@ -495,8 +519,22 @@ static int launch_sample_topk_select(const float* top_val, const int* top_idx, c
     return 0;
 }
 
+int launch_sample_init(float* cum, int* fin, int64_t* len, int64_t R, int max_len, hipStream_t st) {
+    hipLaunchKernelGGL(sample_init_kernel, g1(R), dim3(256), 0, st, cum, fin, len, R, max_len);
+    NIR_CHECK_LAUNCH("sample_init_kernel");
+    return 0;
+}
+int launch_sample_end(const float* cum, const int64_t* len, const float* attn_ws, int64_t B, int N, int max_len, int QL, float* scores, int64_t* lengths,
+                      float* attn, hipStream_t st) {
+    {
+        ProfScope ps_("sample_end_kernel", st);
+        hipLaunchKernelGGL(sample_end_kernel, dim3((unsigned)(B * N)), dim3(64), 0, st, cum, len, attn_ws, B, N, max_len, QL, scores, lengths, attn);
+    }
+    NIR_CHECK_LAUNCH("sample_end_kernel");
+    return 0;
+}
+
 // ---- the decode --------------------------------------------------------------------------------------------------------------------------------------
-static bool sample_dims_ok(int N, int top_k, int64_t VT) { return N >= 1 && top_k >= 0 && top_k <= NIR_BEAM_MAX_W && (int64_t)top_k <= VT; }
 struct SamplePlan {
     S2sStepBufs s;                                    // the stepper's buffers, over R = B N decode rows
     void* gen;                                        // the generator's workspace: sample_gen_bytes, or nir_beam_gen_topk's
@@ -556,8 +594,7 @@ static int s2s_sample_decode(const float* dec_h, const float* dec_c, const float
     }
     s.b = p.s;
     NIR_PROPAGATE(s.prepare(dec_h, bos, p.s.h16[1]));
-    hipLaunchKernelGGL(sample_init_kernel, g1(R), dim3(256), 0, st, p.cum, p.fin, p.len, R, max_len);
-    NIR_CHECK_LAUNCH("sample_init_kernel");
+    NIR_PROPAGATE(launch_sample_init(p.cum, p.fin, p.len, R, max_len, st));
     SampleOut o{nullptr, nullptr, nullptr, p.fin, p.cum, p.len, predictions, token_logprobs, p.s.tgt, tgt2src, V, w->VT, B, N, 0, max_len};
     const float* hp = dec_h;
     const float* cp = dec_c;
@@ -578,12 +615,7 @@ static int s2s_sample_decode(const float* dec_h, const float* dec_c, const float
         hp = hn;
         cp = cn;
     }
-    {
-        ProfScope ps_("sample_end_kernel", st);
-        hipLaunchKernelGGL(sample_end_kernel, dim3((unsigned)R), dim3(64), 0, st, p.cum, p.len, p.attn, B, N, max_len, QL, scores, lengths, attentions);
-    }
-    NIR_CHECK_LAUNCH("sample_end_kernel");
-    return 0;
+    return launch_sample_end(p.cum, p.len, p.attn, B, N, max_len, QL, scores, lengths, attentions, st);
 }
 
 }  // namespace nir

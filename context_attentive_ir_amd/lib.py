@@ -402,6 +402,21 @@ SAMPLE_SIGNATURES = {
                                            c_ip, c_fp, c_st]),
 }
 
+# Sampling decode for HredQS and the session models, declared in include/neuroir_session_sample.h (csrc/session_sample.hip).  SAMPLE_SIGNATURES
+# mirrors neuroir_sample.h exactly (pinned by a test), so these have a table of their own.
+SESSION_SAMPLE_SIGNATURES = {
+    "nir_sample_hredqs_gen_workspace_bytes": (_z, [_l, _i, _l]),
+    "nir_sample_hredqs_gen": (_i, [C.c_void_p, _l, _l, _i, c_fp, C.c_void_p, _l, _f, _u64, _l, C.c_void_p, _z, C.c_void_p, c_fp, c_fp, c_st]),
+    "nir_sample_hredqs_decode_workspace_bytes": (_z, [_l, _l, _i, _i, _i, _HW]),
+    "nir_sample_hredqs_decode": (_i, [c_fp, c_fp, _l, _l, c_fp, _l, _i, c_ip, _l, _i, _HW, _i, _i, _f, _u64, C.c_void_p, _z, c_ip, c_fp, c_fp, c_ip, c_st]),
+    "nir_sample_plain_decode_workspace_bytes": (_z, [_l, _i, _l, _i, _i, _i, _i, _i]),
+    "nir_sample_plain_decode": (_i, [c_fp, c_fp, _l, _i, c_fp, _l, _i, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, _l, c_ip, _l, _i, c_fp, C.c_void_p, C.c_void_p, _i,
+                                     _i, _f, _u64, C.c_void_p, _z, c_ip, c_fp, c_fp, c_ip, c_st]),
+    "nir_sample_cars_decode_workspace_bytes": (_z, [_l, _l, _i, _i, _i, _i, _CW, _i]),
+    "nir_sample_cars_decode": (_i, [c_fp, c_fp, c_fp, c_ip, _l, _i, c_ip, _l, c_fp, c_fp, _l, _i, c_ip, _l, _i, _CW, C.c_void_p, _i, _i, _f, _u64, C.c_void_p,
+                                    _z, c_ip, c_fp, c_fp, c_ip, c_st]),
+}
+
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_SPLIT2 = 0, 1, 2
 DTYPES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "bf16": DTYPE_BF16, "f32_split2": DTYPE_F32_SPLIT2}
 
@@ -419,7 +434,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(GRU_DECODE_SIGNATURES.items()) + list(BEAM_SIGNATURES.items()) + list(SESSION_BEAM_SIGNATURES.items())
                                   + list(ACG_BEAM_SIGNATURES.items()) + list(HREDQS_BEAM_SIGNATURES.items()) + list(SCORE_SIGNATURES.items())
-                                  + list(TEACHER_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items())):
+                                  + list(TEACHER_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SESSION_SAMPLE_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -747,6 +747,58 @@ class CARS(nn.Module, lib.IdCheck):
                                                              out["lengths"].view(B, SD, W))
         return out
 
+    # decode_sample: the fused generator at every row count -- it wins outside the rounds' spreads at 384, 768 and 1152 sample rows, with and
+    # without top_k (P = 256: a row block's fragments are a quarter of a K = 1024 decoder's)
+    fuse_sample_max_rows = None
+
+    @torch.no_grad()
+    def decode_sample(self, states, max_len, num_samples, src_dict, tgt_dict, batch_size, session_len, encoded_source, source_len, session_attns,
+                      temperature=1.0, top_k=0, seed=0, tgt2src=None):
+        """`num_samples` i.i.d. draws per decode row with the inputs of decode() (include/neuroir_session_sample.h; the
+        rules are Seq2seq.decode_sample's, section 28) -> {'predictions': LongTensor [batch_size, session_len, N, max_len] (in sample order, EOS
+        repeated behind the first EOS), 'token_logprobs': [batch_size, session_len, N, max_len], 'scores': [batch_size, session_len, N],
+        'lengths': LongTensor [batch_size, session_len, N]}.  Nothing is repeated here: ONE C call; sample row n Bd + i reads the memory bank,
+        length and session term of decode row i.  The switches are suggest.sample_fused's; there is no row cap (`fuse_sample_max_rows = None`)."""
+        VT = self.token_prob_predictor2.weight.shape[0]
+        N, K, tau, seed = suggest.check_sample_args(self, num_samples, temperature, top_k, seed, VT)
+        if self.no_recommender:
+            raise RuntimeError("decode needs the recommender (turn_recommender_off=False)")
+        assert all(s is not None for s in states)
+        lib.require_device(*states)
+        L = lib.load()
+        dec_h, dec_c = (s.reshape(-1, s.shape[-1]).float().contiguous() for s in states)
+        B, SD, max_len = int(batch_size), int(session_len), int(max_len)
+        Bd = B * SD
+        if dec_h.shape[0] != Bd:
+            raise RuntimeError("decode: %d initial states for %d x %d decode rows" % (dec_h.shape[0], B, SD))
+        dev = dec_h.device
+        enc = encoded_source.float().contiguous()
+        rows_src, QL = enc.shape[0], enc.shape[1]
+        lens = lib.ids64(source_len.reshape(-1))
+        if rows_src != B * (SD + 1) or lens.numel() != rows_src:
+            raise RuntimeError("decode: encoded_source must hold batch_size*(session_len+1) query rows")
+        i = torch.arange(Bd, device=dev)
+        rowmap = ((i // SD) * (SD + 1) + i % SD).contiguous()                       # the reference's [:, :-1] selection
+        cat = [a for a in session_attns if a is not None]
+        session_cat = torch.cat(cat, 2).reshape(rows_src, -1).float().contiguous() if cat else None
+        if tgt2src is None:
+            tgt2src = self._tgt2src(src_dict, tgt_dict, dev)
+        w = self._decoder_weights()
+        frag = suggest.gen_frag_pack(self, self.token_prob_predictor2.weight, Bd * N, attr="_pgen_sample", wanted=suggest.sample_fused(self, Bd * N, K))
+        table = self.embedder.word_embeddings.table
+        out = suggest.sample_outputs(Bd, N, max_len, dev)
+        if Bd > 0 and max_len > 0:
+            nb = L.nir_sample_cars_decode_workspace_bytes(rows_src, Bd, QL, N, K, max_len, w.ref(), int(frag is not None))
+            if nb == 0:
+                raise ValueError("CARS.decode_sample: the shapes are outside the entry's range (nir_sample_cars_decode)")
+            ws = lib.workspace(nb, dev)
+            lib.check(L.nir_sample_cars_decode(lib.ptr(dec_h), lib.ptr(dec_c), lib.ptr(enc), lib.ptr(lens), rows_src, QL, lib.ptr(rowmap), Bd,
+                                               lib.ptr(session_cat), lib.ptr(table), table.shape[0], table.shape[1], lib.ptr(tgt2src), BOS, max_len,
+                                               w.ref(), lib.ptr(frag), N, K, 1.0 / tau, seed, lib.ptr(ws), ws.numel(), lib.ptr(out["predictions"]),
+                                               lib.ptr(out["token_logprobs"]), lib.ptr(out["scores"]), lib.ptr(out["lengths"]), lib.stream()),
+                      "nir_sample_cars_decode")
+        return suggest.sample_view(out, B, SD)
+
     # score_candidates: nir_tf_attend's fused form where the shape has one.  False: its plain form through the debug tunable exact_f32, set around
     # that one call -- for tests and tools, which run with NIR_DEBUG_TUNABLES=1; a product process keeps the switches frozen and refuses it
     fuse_teacher_attention = True

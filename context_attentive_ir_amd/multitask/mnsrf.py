@@ -240,6 +240,15 @@ class MNSRF(nn.Module, lib.IdCheck):
                                    self.decoder.decoder.rnn, self.generator, tgt2src, return_backptr)
 
     @torch.no_grad()
+    def decode_sample(self, states, max_len, num_samples, src_dict, tgt_dict, batch_size, session_len, temperature=1.0, top_k=0, seed=0, use_cuda=True,
+                      tgt2src=None, **kwargs):
+        """`num_samples` i.i.d. draws per decode row with the arguments of decode() (include/neuroir_session_sample.h; the
+        rules are Seq2seq.decode_sample's) -> {'predictions': LongTensor [batch_size, session_len, N, max_len], 'token_logprobs': [batch_size,
+        session_len, N, max_len], 'scores': [batch_size, session_len, N], 'lengths': LongTensor [batch_size, session_len, N]}, in sample order."""
+        return suggest.sample_decode(self, states, max_len, num_samples, temperature, top_k, seed, src_dict, tgt_dict, batch_size, session_len,
+                                     self.embedder.word_embeddings.table, self.decoder.decoder.rnn, self.generator, tgt2src)
+
+    @torch.no_grad()
     def score_candidates(self, states, candidate_seq, src_dict, tgt_dict, batch_size, session_len, candidate_rep=None, tgt2src=None):
         """log P(candidate | session prefix) for N candidate next queries per decode row, with the states of decode():
         candidate_seq [B, S-1, N, TL] target-vocabulary ids, BOS first, PAD behind the end; candidate_rep: the embedder ids fed to the decoder

@@ -6,6 +6,8 @@
 * greedy_decode: embedding -> Decoder(attn_type='none') LSTM step -> generator -> arg-max -> target id mapped to its source id and
   fed back (mmtensor.py:281-325, mnsrf.py:251-296) -- nir_decode_greedy_plain, no host synchronisation.
 """
+import math
+
 import torch
 
 from .. import autograd as A
@@ -191,12 +193,13 @@ FUSE_TOPK_MAX_ROWS = 384     # beam rows up to which the fused generator + top-k
 FUSE_SAMPLE_MAX_ROWS = 512   # decode rows up to which the fused generator + Gumbel arg-max is the default (it wins at 512, not at 768)
 
 
-def gen_frag_pack(owner, weight, rows, attr="_pgen_beam"):
+def gen_frag_pack(owner, weight, rows, attr="_pgen_beam", wanted=None):
     """nir_seq2seq_pack_gen_frag of a generator weight [VT, K] (the fused generator + top-W kernel of the beam reads it), once per weight version,
     cached on `owner`; None when K has no fragment form, the weight lies outside the split's range, the model says `fuse_generator_topk = False`
     or the decode has more than `fuse_topk_max_rows` (default FUSE_TOPK_MAX_ROWS) beam rows: the fused kernel re-reads the fragments once per
-    64-row block, and from there on the fp32 GEMM + row top-k was measured faster."""
-    if not getattr(owner, "fuse_generator_topk", True) or rows > getattr(owner, "fuse_topk_max_rows", FUSE_TOPK_MAX_ROWS):
+    64-row block, and from there on the fp32 GEMM + row top-k was measured faster.  wanted (a bool): the caller's own switch and cap in the
+    place of those two (sample_fused below)."""
+    if (not getattr(owner, "fuse_generator_topk", True) or rows > getattr(owner, "fuse_topk_max_rows", FUSE_TOPK_MAX_ROWS)) if wanted is None else not wanted:
         return None
     L = lib.load()
 
@@ -265,6 +268,84 @@ def beam_decode(owner, states, max_len, beam_size, src_dict, tgt_dict, batch_siz
     B, SD = int(batch_size), int(session_len)
     out["predictions"], out["scores"], out["lengths"] = out["predictions"].view(B, SD, W, max_len), out["scores"].view(B, SD, W), out["lengths"].view(B, SD, W)
     return out
+
+
+def check_sample_args(owner, num_samples, temperature, top_k, seed, VT):
+    """the argument checks of every decode_sample (Seq2seq.decode_sample's) -> (N, top_k, temperature, seed)"""
+    if owner.training:
+        raise NotImplementedError("HIP %s.decode_sample runs in eval mode" % type(owner).__name__)
+    N, K, tau, seed = int(num_samples), int(top_k), float(temperature), int(seed)
+    if N < 1:
+        raise ValueError("decode_sample: num_samples %d < 1" % N)
+    if not (math.isfinite(tau) and tau > 0.0 and 1e-38 < 1.0 / tau < 3e38):      # (1 / tau travels as an fp32)
+        raise ValueError("decode_sample: temperature %r is not finite and > 0" % (temperature,))
+    if not 0 <= seed < (1 << 64):
+        raise ValueError("decode_sample: seed %d outside [0, 2^64)" % seed)
+    VT = int(VT)
+    if not 0 <= K <= min(lib.BEAM_MAX_W, VT):
+        raise ValueError("decode_sample: top_k %d outside {0} and [1, %d] (at most %d, and the target vocabulary's %d)"
+                         % (K, min(lib.BEAM_MAX_W, VT), lib.BEAM_MAX_W, VT))
+    return N, K, tau, seed
+
+
+def sample_fused(owner, rows, top_k):
+    """whether a decode_sample of the session models over `rows` sample rows runs its fused generator form: `fuse_generator_argmax` (top_k = 0)
+    or `fuse_generator_topk` (top_k > 0) on the model, up to `fuse_sample_max_rows` sample rows in either case (None: no cap).  Measured at 384,
+    768 and 1152 rows (profiles/session_sample_bench_mi355x.json): CARS' fused form wins at all three in both settings --
+    the model sets no cap --; MNSRF's wins at 384 and loses at 768 in both settings, which the cap inherited from section 28
+    (FUSE_SAMPLE_MAX_ROWS = 512, between the last measured win and the first loss) already separates, so it stays."""
+    cap = getattr(owner, "fuse_sample_max_rows", FUSE_SAMPLE_MAX_ROWS)
+    on = getattr(owner, "fuse_generator_topk", True) if top_k > 0 else getattr(owner, "fuse_generator_argmax", True)
+    return bool(on) and (cap is None or rows <= cap)
+
+
+def sample_outputs(Bd, N, max_len, dev):
+    return {"predictions": torch.empty(Bd, N, max_len, dtype=torch.int64, device=dev),
+            "token_logprobs": torch.empty(Bd, N, max_len, dtype=torch.float32, device=dev),
+            "scores": torch.empty(Bd, N, dtype=torch.float32, device=dev), "lengths": torch.empty(Bd, N, dtype=torch.int64, device=dev)}
+
+
+def sample_view(out, B, SD):
+    """the four outputs of a sampling entry, [Bd, N, ...], viewed [B, SD, N, ...]"""
+    return {k: v.view((B, SD) + tuple(v.shape[1:])) for k, v in out.items()}
+
+
+def sample_decode(owner, states, max_len, num_samples, temperature, top_k, seed, src_dict, tgt_dict, batch_size, session_len, table, dec_rnn, generator,
+                  tgt2src=None):
+    """Sampling next to greedy_decode and beam_decode (include/neuroir_session_sample.h) -> {'predictions': LongTensor
+    [batch_size, session_len, N, max_len] (in sample order, EOS repeated behind the first EOS), 'token_logprobs': [batch_size, session_len, N,
+    max_len], 'scores': [batch_size, session_len, N], 'lengths': LongTensor [batch_size, session_len, N]}.  The same fold cache as greedy_decode,
+    a cached generator fragment pack of its own (`_pgen_sample`) under sample_fused's switches; the initial states are not repeated here --
+    nir_sample_plain_decode does that."""
+    VT = generator.weight.shape[0]
+    N, K, tau, seed = check_sample_args(owner, num_samples, temperature, top_k, seed, VT)
+    lib.require_device(*states)
+    L = lib.load()
+    dec_h, dec_c = (s.reshape(-1, s.shape[-1]).float().contiguous() for s in states)
+    Bd, H = dec_h.shape
+    if Bd != int(batch_size) * int(session_len):
+        raise RuntimeError("decode: %d initial states for %d x %d decode rows" % (Bd, batch_size, session_len))
+    dev = dec_h.device
+    max_len = int(max_len)
+    gw, gb = generator.weight.detach().float().contiguous(), generator.bias.detach().float().contiguous()
+    if tgt2src is None:
+        tgt2src = tgt2src_lut(owner, src_dict, tgt_dict, VT, dev)
+    t = table.detach().float().contiguous()
+    p = [getattr(dec_rnn, n).detach().float().contiguous() for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")]
+    fold = plain_fold(owner, table, dec_rnn, t, p, H, dev)
+    frag = gen_frag_pack(owner, generator.weight, Bd * N, attr="_pgen_sample", wanted=sample_fused(owner, Bd * N, K))
+    out = sample_outputs(Bd, N, max_len, dev)
+    if Bd > 0 and max_len > 0:
+        nb = L.nir_sample_plain_decode_workspace_bytes(Bd, H, VT, N, K, max_len, int(fold is not None), int(frag is not None))
+        if nb == 0:
+            raise ValueError("%s.decode_sample: the shapes are outside the entry's range (nir_sample_plain_decode)" % type(owner).__name__)
+        ws = lib.workspace(nb, dev)
+        lib.check(L.nir_sample_plain_decode(lib.ptr(dec_h), lib.ptr(dec_c), Bd, H, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(p[0]), lib.ptr(p[1]),
+                                            lib.ptr(p[2]), lib.ptr(p[3]), lib.ptr(gw), lib.ptr(gb), VT, lib.ptr(tgt2src), BOS, max_len,
+                                            lib.ptr(fold[0]) if fold else None, lib.ptr(fold[1]) if fold else None, lib.ptr(frag), N, K, 1.0 / tau, seed,
+                                            lib.ptr(ws), ws.numel(), lib.ptr(out["predictions"]), lib.ptr(out["token_logprobs"]), lib.ptr(out["scores"]),
+                                            lib.ptr(out["lengths"]), lib.stream()), "nir_sample_plain_decode")
+    return sample_view(out, int(batch_size), int(session_len))
 
 
 def bilstm_train(x, lens, lstm):

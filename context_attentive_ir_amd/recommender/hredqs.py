@@ -201,6 +201,51 @@ class HredQS(nn.Module, lib.IdCheck):
         out["scores"], out["lengths"] = out["scores"].view(B, S, W), out["lengths"].view(B, S, W)
         return out
 
+    # ---- eval: sampling ------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def decode_sample(self, source_rep, source_len, max_len, num_samples, temperature=1.0, top_k=0, seed=0, src_dict=None, tgt_dict=None,
+                      tgt2src=None):
+        """`num_samples` i.i.d. draws per session prefix next to decode() and decode_beam() (include/neuroir_session_sample.h, DESIGN.md section
+        29; the rules are Seq2seq.decode_sample's, section 28) -> {'predictions': LongTensor [B, S, N, max_len] (in sample order, EOS repeated
+        behind the first EOS), 'token_logprobs': [B, S, N, max_len], 'scores': [B, S, N], 'lengths': LongTensor [B, S, N]}; there are no
+        attentions.  One C-ABI call (nir_sample_hredqs_decode) over the same session states, pack cache and target -> source table as decode();
+        the entry pairs and repeats the states itself, and in its fast form draws on the split state the folded step leaves: no [R, VT] logits.
+        `fast_decode = False` forces its plain form, as does a `fuse_sample_max_rows` set on the model for more sample rows than that (none by
+        default: DESIGN.md section 29)."""
+        N, K, tau, seed = suggest.check_sample_args(self, num_samples, temperature, top_k, seed, self.generator.weight.shape[0])
+        self._check_config()
+        max_len = int(max_len)
+        if max_len < 1:
+            raise ValueError("decode_sample: max_len must be positive")
+        B, S, QL = source_rep.shape
+        table = self.embedder.word_embeddings.table
+        lib.require_device(source_rep, source_len, table)
+        L = lib.load()
+        dev = table.device
+        out = suggest.sample_outputs(B * S, N, max_len, dev)
+        if B * S > 0:
+            src, _ = self._clean_ids(source_rep.reshape(B * S, QL), None, table.shape[0])
+            hs, cs = self._session_steps(src, lib.ids64(source_len.reshape(-1)), B, S)
+            w = self._decoder_weights()
+            ref = w.ref()
+            cap = getattr(self, "fuse_sample_max_rows", None)
+            if cap is not None and K == 0 and B * S * N > cap and w.struct.gen_frag:
+                plain = lib.HredqsDecoderWeights.from_buffer_copy(w.struct)      # the same pack without the three packs: the entry's plain form
+                plain.rnn_gate_fold = plain.rnn_whh_frag = plain.gen_frag = None
+                ref = lib.C.byref(plain)
+            if tgt2src is None:
+                tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, int(w.struct.VT), dev)
+            t = table.detach().float().contiguous()
+            nb = L.nir_sample_hredqs_decode_workspace_bytes(B, S, N, K, max_len, ref)
+            if nb == 0:
+                raise ValueError("HredQS.decode_sample: the shapes are outside the entry's range (nir_sample_hredqs_decode)")
+            ws = lib.workspace(nb, dev)
+            lib.check(L.nir_sample_hredqs_decode(lib.ptr(hs), lib.ptr(cs), B, S, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(tgt2src), BOS, max_len,
+                                                 ref, N, K, 1.0 / tau, seed, lib.ptr(ws), ws.numel(), lib.ptr(out["predictions"]),
+                                                 lib.ptr(out["token_logprobs"]), lib.ptr(out["scores"]), lib.ptr(out["lengths"]), lib.stream()),
+                      "nir_sample_hredqs_decode")
+        return suggest.sample_view(out, B, S)
+
     # ---- eval: teacher-forced scoring of given candidates ---------------------------------------------------------------------------------
     @torch.no_grad()
     def score_candidates(self, source_rep, source_len, candidate_seq, candidate_rep=None, src_dict=None, tgt_dict=None, tgt2src=None):

@@ -348,6 +348,49 @@ class Multitask(WrapperBase):
             out.update(text)
         return out
 
+    # ---- sampling -------------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def predict_samples(self, ex, num_samples, temperature=1.0, top_k=0, seed=None):
+        """`num_samples` i.i.d. query suggestions per decoded query drawn from the model (decode_sample of the three session models, DESIGN.md
+        section 29; the reference has no counterpart): {'click_scores': exactly predict()'s, 'prediction_ids': LongTensor [B, S-1, N,
+        max_query_len], 'token_logprobs': [B, S-1, N, max_query_len], 'scores': [B, S-1, N], 'lengths': LongTensor [B, S-1, N], 'seed': the seed
+        used}, in sample order.  For a batch in the reference's collate layout also the text fields as predict_beam() forms them, `predictions` =
+        one list of N strings per decoded query.  seed=None draws a 63-bit seed from torch's default CPU generator; the returned 'seed' replays
+        the draw.  Always eager: the seed is a host argument of the C entry, so a captured graph would replay one draw.  CARS with the
+        recommender off returns the sampling keys as None, like predict_beam()."""
+        N = int(num_samples)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        if self.type == "CARS" and self.network.no_recommender:
+            out = self.predict(ex, suggest=False)
+            out.pop("predictions", None)
+            out.update(prediction_ids=None, token_logprobs=None, scores=None, lengths=None, seed=None)
+            return out
+        self._poll_ids()
+        # _predict_beam_body with the sampling decode in the place of the beam: the same kernels in the same order in front of it
+        s, states, attns, enc = self._rank(ex, True)
+        out = {"click_scores": None}
+        if torch.is_tensor(s):
+            s = s.contiguous()
+            probs = torch.empty_like(s)
+            lib.check(lib.load().nir_softmax_rows(lib.ptr(s), lib.ptr(probs), s.shape[0] * s.shape[1], s.shape[2], lib.stream()), "nir_softmax_rows")
+            out["click_scores"] = probs
+        B, S = ex["source_words"].shape[0], ex["source_words"].shape[1]
+        dec = self.network.decode_sample(states=states, max_len=self.args.max_query_len, num_samples=N, temperature=temperature, top_k=top_k, seed=seed,
+                                         src_dict=self.src_dict, tgt_dict=self.tgt_dict, batch_size=B, session_len=S - 1, encoded_source=enc[0],
+                                         source_len=enc[1], session_attns=attns)
+        out.update(prediction_ids=dec["predictions"], token_logprobs=dec["token_logprobs"], scores=dec["scores"], lengths=dec["lengths"], seed=int(seed))
+        self._maybe_check_ids(False)
+        if out["click_scores"] is not None:
+            out["click_scores"] = self._checked(out["click_scores"])
+        if "ids" in ex and ex.get("source_tokens") is not None:
+            per = [self._suggestion_text(ex, out["prediction_ids"][:, :, n]) for n in range(N)]
+            text = dict(per[0])
+            text["prediction_ids"] = out["prediction_ids"]
+            text["predictions"] = [[per[n]["predictions"][j] for n in range(N)] for j in range(len(per[0]["predictions"]))]
+            out.update(text)
+        return out
+
     # ---- teacher-forced scoring ---------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def score_suggestions(self, ex, candidates=None, length_normalize=False):

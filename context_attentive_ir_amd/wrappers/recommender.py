@@ -278,9 +278,33 @@ class SessionRecommender(Recommender):
                                   "list per session prefix, [B, S, W, max_query_len] (DESIGN.md section 25)")
 
     def predict_samples(self, ex, num_samples, temperature=1.0, top_k=0, seed=None):
-        raise NotImplementedError("SessionRecommender.predict_samples: sampling for HredQS is not built yet -- the sampling tail "
-                                  "(include/neuroir_sample.h) stands behind the Seq2seq step only; its follow-up puts it behind the decoder "
-                                  "without attention (DESIGN.md section 28)")
+        raise NotImplementedError("SessionRecommender.predict_samples: sampling for HredQS is predict_session_samples(ex, num_samples, ...) -- its "
+                                  "outputs keep the session axis, [B, S, N, max_query_len], and there are no attentions (the rules of DESIGN.md "
+                                  "section 28, built behind the decoder without attention in section 29)")
+
+    @torch.no_grad()
+    def predict_session_samples(self, ex, num_samples, temperature=1.0, top_k=0, seed=None):
+        """`num_samples` i.i.d. suggestions per session prefix drawn from the model (HredQS.decode_sample; the reference has no counterpart):
+        {'prediction_ids': LongTensor [B, S, N, max_query_len], 'token_logprobs': [B, S, N, max_query_len], 'scores': [B, S, N], 'lengths':
+        LongTensor [B, S, N], 'seed': the seed used}, in sample order (not sorted, duplicates possible); for a batch in the reference's collate
+        layout also predict()'s step-major `ex_ids`, `targets`, `src_sequences` and `predictions`: per prefix the list of its N strings.
+        seed=None draws a 63-bit seed from torch's default CPU generator (no device synchronisation); calling again with the returned 'seed'
+        replays the draw bit for bit.  Always eager: the seed is a host argument of the C entry, so a captured graph would replay one draw."""
+        N = int(num_samples)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        self._poll_ids()
+        self.network.eval()
+        dec = self.network.decode_sample(source_rep=self._dev(ex["source_words"]), source_len=self._dev(ex["source_lens"]), max_len=self.args.max_query_len,
+                                         num_samples=N, temperature=temperature, top_k=top_k, seed=seed, src_dict=self.src_dict, tgt_dict=self.tgt_dict)
+        self._maybe_check_ids()
+        out = {"prediction_ids": dec["predictions"], "token_logprobs": dec["token_logprobs"], "scores": dec["scores"], "lengths": dec["lengths"],
+               "seed": int(seed)}
+        if all(k in ex for k in ("ids", "source_tokens", "target_tokens")):
+            per = [self._text(ex, out["prediction_ids"][:, :, n]) for n in range(N)]
+            out.update(per[0])
+            out["predictions"] = [[per[n]["predictions"][i] for n in range(N)] for i in range(len(per[0]["predictions"]))]
+        return out
 
     def _predict_session_nbest_body(self, ex, beam_size):
         self.network.eval()

@@ -1156,6 +1156,8 @@ int nir_acg_copy_loss_bwd(const float* logits, int64_t ld, const float* switch_l
 #include "neuroir_teacher.h"
 /* Sampling decode for Seq2seq (both decoders' cells): fused generator + Gumbel arg-max (ctypes: lib.SAMPLE_SIGNATURES). */
 #include "neuroir_sample.h"
+/* ... and for HredQS and the session models, the draw on the split state included (ctypes: lib.SESSION_SAMPLE_SIGNATURES). */
+#include "neuroir_session_sample.h"
 
 #ifdef __cplusplus
 }
