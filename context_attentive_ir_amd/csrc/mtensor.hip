@@ -133,6 +133,25 @@ __global__ __launch_bounds__(256) void mt_fold_kernel(const float* __restrict__ 
     }
 }
 
+// wave_sum's butterflies (common.hpp) on the two words of a double: every 16-lane row ends fully reduced
+template <int CTRL>
+__device__ __forceinline__ double dpp_mov_f64(double v) {
+    const uint2 w = __builtin_bit_cast(uint2, v);
+    return __builtin_bit_cast(double, make_uint2((unsigned)__builtin_amdgcn_update_dpp(0, (int)w.x, CTRL, 0xF, 0xF, true),
+                                                 (unsigned)__builtin_amdgcn_update_dpp(0, (int)w.y, CTRL, 0xF, 0xF, true)));
+}
+__device__ __forceinline__ double row_sum_f64(double v) {
+    v += dpp_mov_f64<0xB1>(v);
+    v += dpp_mov_f64<0x4E>(v);
+    v += dpp_mov_f64<0x141>(v);
+    v += dpp_mov_f64<0x140>(v);
+    return v;
+}
+__device__ __forceinline__ double readlane_f64(double v, int lane) {
+    const uint2 w = __builtin_bit_cast(uint2, v);
+    return __builtin_bit_cast(double, make_uint2((unsigned)__builtin_amdgcn_readlane((int)w.x, lane), (unsigned)__builtin_amdgcn_readlane((int)w.y, lane)));
+}
+
 // One workgroup (4 waves) per (query, candidate) pair.  Per 64-position chunk of the document:
 //   phase 1 (MFMA): for each conv k and 32-column tile, D[32 rows x 32 cols] += U[rows][kk] * Pd[j+dj-pw][c]
 //            with B read straight out of the transposed, zero-haloed LDS image PdT[c][j] (an im2col view: the K
@@ -442,6 +461,9 @@ __global__ __launch_bounds__(256, 3) void mt_head_kernel(const float* __restrict
             const int kw = 3 + 2 * k, pw = k + 1, Kp = kw * CP;
             const float* arow = ub + (int64_t)mt * 32 * KTOT + (int64_t)mt_koff(k) * 32 + (int64_t)col * Kp + 4 * g2;
             const float* bcol = pdt + (4 * g2) * DLP + (j0 + nt * 32 + col) - pw + 3;
+            // One accumulator per tap, added to the running sum once the tap is done: a chain of 28 MFMAs and kw additions instead of one chain
+            // of 28 kw MFMAs.  With a single accumulator the rounding of up to 196 dependent additions left this form, the one selected for
+            // exactness, with a larger error than the fp16 two-term form (tests/test_gpu_mt_head_envelope.py, planted DL = 321).
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -463,6 +485,9 @@ __global__ __launch_bounds__(256, 3) void mt_head_kernel(const float* __restrict
                 // ds_read right before its MFMA behind an lgkmcnt(0), i.e. one exposed LDS round trip per 64-cycle MFMA
                 const float* bp0 = bcol + dj;
                 float bn0 = bp0[0], bn1 = bp0[DLP], bn2 = bp0[2 * DLP], bn3 = bp0[3 * DLP];
+                f32x16 at;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) at[r] = 0.f;
 #pragma unroll
                 for (int u = 0; u < NG; ++u) {
                     const float b0 = bn0, b1 = bn1, b2 = bn2, b3 = bn3;
@@ -471,11 +496,12 @@ __global__ __launch_bounds__(256, 3) void mt_head_kernel(const float* __restrict
                         bn0 = bp[0]; bn1 = bp[DLP]; bn2 = bp[2 * DLP]; bn3 = bp[3 * DLP];
                     }
                     __builtin_amdgcn_sched_barrier(0);   // keep the reads above the MFMAs (the scheduler sinks them)
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[u].x, b0, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[u].y, b1, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[u].z, b2, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[u].w, b3, acc, 0, 0, 0);
+                    at = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[u].x, b0, at, 0, 0, 0);
+                    at = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[u].y, b1, at, 0, 0, 0);
+                    at = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[u].z, b2, at, 0, 0, 0);
+                    at = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[u].w, b3, at, 0, 0, 0);
                 }
+                acc += at;
             }
             float* yk = Y + ((int64_t)k * rows + mtl * 32) * YLD + nt * 32 + col;
 #pragma unroll
@@ -550,10 +576,13 @@ __global__ __launch_bounds__(256, 3) void mt_head_kernel(const float* __restrict
     }
     __syncthreads();
     if (wave == 0) {   // global max over the 4 waves, then the output Linear as one wave reduction
-        float t = 0.f;
-        if (lane < MFC) t = ow_s[lane] * fmaxf(fmaxf(wmax[0][lane], wmax[1][lane]), fmaxf(wmax[2][lane], wmax[3][lane]));
-        t = wave_sum(t);
-        if (lane == 0) scores[pair] = t + ow_s[MFC];
+        // in double: the 20 terms cancel (sum |ow z| is several times |score|), and in fp32 the reduction alone cost up to 5 ulp of the score
+        // (tests/test_gpu_mt_head_envelope.py, the `dead` family); products of two floats are exact in double
+        double t = 0.0;
+        if (lane < MFC) t = (double)ow_s[lane] * (double)fmaxf(fmaxf(wmax[0][lane], wmax[1][lane]), fmaxf(wmax[2][lane], wmax[3][lane]));
+        t = row_sum_f64(t);
+        const double lo = readlane_f64(t, 0), hi = readlane_f64(t, 16);    // lanes 0..19 hold the terms: rows 0 and 1
+        if (lane == 0) scores[pair] = (float)((lo + hi) + (double)ow_s[MFC]);
     }
     MT_STAMP(5);
     if (w.dbg && tid == 0) w.dbg[64 + 4 * blockIdx.x + 1] = wall_clock64();
