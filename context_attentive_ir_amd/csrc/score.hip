@@ -9,9 +9,12 @@
 // (csrc/beam.hip), and restates their staging, chunk clamp and fragment walk as they do: a change to one of those has to be made here too.
 // The rows and the grid mapping are BeamRowsF32's (gen_rows.hpp); what differs from the per-step kernels is the number of vocabulary ranges
 // (score_nvr): with hundreds of row blocks the chip is full whatever the split, and a range is made long so that a row block is staged seldom.
+// The copy generator's scorer (include/neuroir_acg_score.h) lives here too, so that the tile walk is not restated a fifth
+// time: the PADSUB form of score_gen_target_kernel, a resolve kernel in front (extended id -> word / slot) and acg_score_finish_kernel behind.
 // Everything is enqueued on the caller's stream: no host synchronisation, no allocation, no float atomics, every reduction in a fixed order.
 #include "decode_common.hpp"
 #include "gen_rows.hpp"
+#include "s2s_gen.hpp"
 
 namespace nir {
 
@@ -40,10 +43,14 @@ static inline int score_nvr(int64_t nrb, int64_t ntiles) {
 // vocabulary index equals); the one lane of the grid that computes element (row, target[row]) stores the biased logit into tlogit[row] -- a
 // plain store, one owner per row, none for a target out of range.  Every wave writes one (max, sum) partial per decode row, pm / ps
 // [part][Bd]; a wave without tiles writes (-inf, 0), which the merge passes over.
-template <int NBT>
+// PADSUB (the copy generator's scorer, include/neuroir_acg_score.h): the biased logit of v == 0 is replaced by ACG_PAD_LOGIT
+// before it enters (max, sum) and before the target compare, as PAD does in beam_gen_topk_kernel; a row whose word is PAD stores the substituted
+// value.  TG: the type of the per-row word ids (that scorer resolves its extended ids into int32 words once per call).  PADSUB = false compiles
+// to the kernel without the test.
+template <int NBT, bool PADSUB = false, typename TG = int64_t>
 __global__ __launch_bounds__(256, 1) void score_gen_target_kernel(const float* __restrict__ x, const _Float16* __restrict__ wfrag,
                                                                   const float* __restrict__ bias, int64_t VT, int64_t ntiles, int64_t Bd, int K, int nvr,
-                                                                  const int64_t* __restrict__ target, float* __restrict__ tlogit,
+                                                                  const TG* __restrict__ target, float* __restrict__ tlogit,
                                                                   float* __restrict__ pm, float* __restrict__ ps) {
     extern __shared__ __attribute__((aligned(16))) _Float16 score_sm[];        // [2 terms][ROWS][LD]
     constexpr int ROWS = 16 * NBT;
@@ -144,6 +151,9 @@ __global__ __launch_bounds__(256, 1) void score_gen_target_kernel(const float* _
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     y[r] = fmaf(acx[bt][r], SPLIT2_INV, acc[bt][r]) + bv[r];  // the greedy and top-k kernels' expression
+                    if constexpr (PADSUB) {
+                        if (v0 + r == 0) y[r] = ACG_PAD_LOGIT;                // the reference assigns this constant behind the linear
+                    }
                     if (v0 + r >= VT) y[r] = -INFINITY;                       // padded tile rows: add exp(-inf) = 0
                     m = fmaxf(m, y[r]);
                 }
@@ -284,31 +294,36 @@ static size_t score_fused_bytes(int64_t rows, int K, int64_t VT) {
 static int64_t score_plain_rows(int64_t VT) { return std::max<int64_t>(1, (int64_t)(SCORE_PLAIN_LOGITS_BYTES / ((size_t)VT * sizeof(float)))); }
 static size_t score_plain_bytes(int64_t rows, int64_t VT) { return (size_t)std::min(rows, score_plain_rows(VT)) * VT * sizeof(float) + 256; }
 
+// the launch of score_gen_target_kernel<NBT, PADSUB, TG> over `rows` rows (one chunk): the row blocks, the vocabulary ranges, the LDS size and its
+// raised limit are stated here once, for the generator's scorer and for the copy generator's.  pm / ps hold 4 nvr parts of `rows` floats each.
+template <bool PADSUB, typename TG>
+static void launch_score_gen_walk(const char* name, const float* x, const void* frag, const float* bias, int64_t VT, int64_t rows, int K, int nvr,
+                                  const TG* target, float* tlogit, float* pm, float* ps, hipStream_t st) {
+    const int64_t nrb = score_nrb(rows, K), ntiles = (VT + 15) / 16;
+    ProfScope ps_(prof_shape_name(name, (long long)rows, (long long)VT, K), st);
+    const dim3 grid((unsigned)(nrb * nvr));                                   // nrb <= 2^18 / 32, nvr <= S2S_MAX_WGS
+    if (gen_nbt(K) == 4) {
+        static const hipError_t raised =
+            hipFuncSetAttribute((const void*)score_gen_target_kernel<4, PADSUB, TG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(512));
+        (void)raised;
+        hipLaunchKernelGGL((score_gen_target_kernel<4, PADSUB, TG>), grid, dim3(256), gen_lds(K), st, x, (const _Float16*)frag, bias, VT, ntiles, rows, K,
+                           nvr, target, tlogit, pm, ps);
+    } else {
+        static const hipError_t raised =
+            hipFuncSetAttribute((const void*)score_gen_target_kernel<2, PADSUB, TG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(1024));
+        (void)raised;
+        hipLaunchKernelGGL((score_gen_target_kernel<2, PADSUB, TG>), grid, dim3(256), gen_lds(K), st, x, (const _Float16*)frag, bias, VT, ntiles, rows, K,
+                           nvr, target, tlogit, pm, ps);
+    }
+}
+
 static int launch_score_gen_target(const float* x, const void* frag, const float* bias, int64_t VT, int64_t rows, int K, const int64_t* target, int64_t pad,
                                    void* ws, size_t ws_bytes, float* token_logp, float* lse, int* id_flag, hipStream_t st) {
-    const int nbt = gen_nbt(K);
-    const int64_t nrb = score_nrb(rows, K), ntiles = (VT + 15) / 16;
-    const int nvr = score_nvr(nrb, ntiles), nparts = 4 * nvr;
+    const int nvr = score_nvr(score_nrb(rows, K), (VT + 15) / 16), nparts = 4 * nvr;
     Workspace a(ws, ws_bytes);
     float* pm = a.take<float>((size_t)nparts * rows);
     float* ps = a.take<float>((size_t)nparts * rows);
-    {
-        ProfScope ps_(prof_shape_name("score_gen_target_kernel", (long long)rows, (long long)VT, K), st);
-        const dim3 grid((unsigned)(nrb * nvr));                               // nrb <= 2^18 / 32, nvr <= S2S_MAX_WGS
-        if (nbt == 4) {
-            static const hipError_t raised =
-                hipFuncSetAttribute((const void*)score_gen_target_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(512));
-            (void)raised;
-            hipLaunchKernelGGL(score_gen_target_kernel<4>, grid, dim3(256), gen_lds(K), st, x, (const _Float16*)frag, bias, VT, ntiles, rows, K, nvr, target,
-                               token_logp, pm, ps);
-        } else {
-            static const hipError_t raised =
-                hipFuncSetAttribute((const void*)score_gen_target_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(1024));
-            (void)raised;
-            hipLaunchKernelGGL(score_gen_target_kernel<2>, grid, dim3(256), gen_lds(K), st, x, (const _Float16*)frag, bias, VT, ntiles, rows, K, nvr, target,
-                               token_logp, pm, ps);
-        }
-    }
+    launch_score_gen_walk<false, int64_t>("score_gen_target_kernel", x, frag, bias, VT, rows, K, nvr, target, token_logp, pm, ps, st);
     NIR_CHECK_LAUNCH("score_gen_target_kernel");
     {
         ProfScope ps_("score_finish_kernel", st);
@@ -317,6 +332,174 @@ static int launch_score_gen_target(const float* x, const void* frag, const float
     }
     NIR_CHECK_LAUNCH("score_finish_kernel");
     return 0;
+}
+
+// ---- the copy generator's scorer (include/neuroir_acg_score.h) -----------------------------------------------------------------
+// log P of a given EXTENDED id under the collapsed extended distribution of nir_acg_beam_gen_select, per teacher-forced row, with neither the
+// [rows, VT] logits nor a [rows, CV] copy distribution written.
+//   once per call: extended id -> (generator word or -1, slot or -1 / masked), int32                              acg_score_resolve_kernel
+//   per row: (max, sum) per wave and the word's logit, PAD substituted: score_gen_target_kernel<.., PADSUB>  |  acg_score_row_kernel (plain form)
+//   per row: merge, the copy switch, the copy mass of the row's word or slot, log P, mask                         acg_score_finish_kernel
+constexpr int ACG_SCORE_MASKED = -2;                            // slot[r]: the row reads 0 (PAD, or an id outside [0, VT + CV))
+
+// Row r of the call reads source row r / rows_per_src.  word[r]: the generator column that enters P (the id itself below VT, the collapse target
+// of a slot c >= 2 with ext2tgt in [0, VT)), -1 for a slot that is not collapsed and for a masked row -- which score_gen_target_kernel takes as
+// "no target".  slot[r]: c for such a slot, -1 for a word, ACG_SCORE_MASKED for a masked row.  An id at or past VT + CV ORs bit 0 into id_flag;
+// a negative one does not.
+__global__ __launch_bounds__(256) void acg_score_resolve_kernel(const int64_t* __restrict__ target, int64_t rows, int64_t rows_per_src, int64_t VT, int CV,
+                                                                const int64_t* __restrict__ e2t, int64_t pad, int* __restrict__ word,
+                                                                int* __restrict__ slot, int* __restrict__ id_flag) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= rows) return;
+    const int64_t e = target[r];
+    int w = -1, s = ACG_SCORE_MASKED;
+    if (e >= VT + CV) {
+        if (id_flag) atomicOr(id_flag, 1);
+    } else if (e >= 0 && e != pad) {
+        if (e < VT) {
+            w = (int)e;
+            s = -1;
+        } else {
+            const int c = (int)(e - VT);
+            const int64_t t = e2t[(r / rows_per_src) * CV + c];
+            if (c >= 2 && t >= 0 && t < VT) {                  // one word has one probability, however it is spelled
+                w = (int)t;
+                s = -1;
+            } else {
+                s = c;
+            }
+        }
+    }
+    word[r] = w;
+    slot[r] = s;
+}
+
+// plain form: one workgroup per row of [rows, VT] logits -> the row's (max, sum) as ONE partial and the word's logit, logits[row, 0] read as
+// ACG_PAD_LOGIT (score_row_kernel's reduction with beam_row_topk_kernel<PAD>'s override)
+__global__ __launch_bounds__(256) void acg_score_row_kernel(const float* __restrict__ logits, int64_t VT, const int* __restrict__ word,
+                                                            float* __restrict__ tlogit, float* __restrict__ pm, float* __restrict__ ps) {
+    __shared__ float lm[4], ls[4];
+    const int64_t row = blockIdx.x;
+    const int tid = threadIdx.x;
+    const float* y = logits + row * VT;
+    float m = -INFINITY, s = 0.f;
+    for (int64_t v = tid; v < VT; v += 256) {
+        const float a = v == 0 ? ACG_PAD_LOGIT : y[v];
+        const float nm = fmaxf(m, a);
+        if (nm > -INFINITY) s = s * expf(m - nm) + expf(a - nm);
+        m = nm;
+    }
+    const float wm = wave_max(m);
+    const float wsum = wave_sum(m > -INFINITY ? s * expf(m - wm) : 0.f);
+    if ((tid & 63) == 0) { lm[tid >> 6] = wm; ls[tid >> 6] = wsum; }
+    __syncthreads();
+    if (tid == 0) {
+        const float M = fmaxf(fmaxf(lm[0], lm[1]), fmaxf(lm[2], lm[3]));
+        float S = 0.f;
+        for (int w = 0; w < 4; ++w) S += lm[w] > -INFINITY ? ls[w] * expf(lm[w] - M) : 0.f;
+        pm[row] = M;
+        ps[row] = S;
+        const int t = word[row];
+        if (t >= 0) tlogit[row] = t == 0 ? ACG_PAD_LOGIT : y[t];
+    }
+}
+
+// One wave per row, four rows a workgroup.  pm / ps [nparts][rows] as in score_finish_kernel; token_logp[row] holds the word's logit on entry
+// where word[row] >= 0 and the result on exit.  The switch and the copy mass are acg_beam_row_kernel's fp32 expressions: x by the same wave dot,
+// z = 1 / (1 + exp(-x)) and 1 - z = 1 / (1 + exp(x)), and the mass a sum of z a[j] in ascending j over the positions j < len whose slot is the
+// row's own (a slot) or collapses onto the row's word (a word) -- a gather: 64 positions a round, the hits taken in order from the ballot.
+// `row0`: the call's row of this launch's row 0 (the host chunks the rows; the source row is (row0 + row) / rows_per_src).
+__global__ __launch_bounds__(256) void acg_score_finish_kernel(const float* __restrict__ pm, const float* __restrict__ ps, int nparts, int64_t rows,
+                                                               int64_t row0, int64_t rows_per_src, const int* __restrict__ word,
+                                                               const int* __restrict__ slot, const float* __restrict__ o, int K,
+                                                               const float* __restrict__ copy_w, const float* __restrict__ copy_b,
+                                                               const float* __restrict__ attn, int64_t attn_stride, const int64_t* __restrict__ lens,
+                                                               int QL, const int64_t* __restrict__ map, const int64_t* __restrict__ e2t, int CV,
+                                                               float* __restrict__ token_logp) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;                                                  // wave-uniform
+    const int w = word[row], sl = slot[row];
+    if (sl == ACG_SCORE_MASKED) {
+        if (lane == 0) token_logp[row] = 0.f;
+        return;
+    }
+    // 1. the generator's statistics
+    float gen = 0.f;                                                          // (1 - z) exp(l[w] - m) / Z, formed below
+    float M = 0.f, S = 1.f;
+    if (w >= 0) {
+        float m = -INFINITY, s = 0.f;
+        for (int p = lane; p < nparts; p += 64) {
+            const int64_t at = (int64_t)p * rows + row;
+            const float om = pm[at], os = ps[at];
+            const float nm = fmaxf(m, om);
+            if (nm > -INFINITY) s = s * expf(m - nm) + os * expf(om - nm);
+            m = nm;
+        }
+        M = wave_max(m);
+        S = wave_sum(m > -INFINITY ? s * expf(m - M) : 0.f);
+    }
+    // 2. the copy switch
+    const float* ob = o + row * K;
+    float x = 0.f;
+    for (int k = 4 * lane; k < K; k += 256) {
+        const float4 a = *reinterpret_cast<const float4*>(ob + k), cw = *reinterpret_cast<const float4*>(copy_w + k);
+        x += (a.x * cw.x + a.y * cw.y) + (a.z * cw.z + a.w * cw.w);
+    }
+    x = wave_sum(x) + copy_b[0];
+    const float z = 1.0f / (1.0f + expf(-x)), omz = 1.0f / (1.0f + expf(x));
+    if (w >= 0) gen = omz * expf(token_logp[row] - M) / S;
+    // 3. the copy mass of the row's word or slot
+    const int64_t b = (row0 + row) / rows_per_src;
+    const int64_t len64 = lens[b];                                            // clamped as int64: a length past 2^32 is QL, not its low word
+    const int len = (int)(len64 < 0 ? 0 : (len64 > QL ? QL : len64));
+    const int64_t* mb = map + b * QL;
+    const int64_t* tb = e2t + b * CV;
+    const float* ab = attn + row * attn_stride;
+    float mass = 0.f;
+    for (int j0 = 0; j0 < len; j0 += 64) {                                    // wave-uniform
+        const int j = j0 + lane;
+        float a = 0.f;
+        bool hit = false;
+        if (j < len) {
+            const int64_t c = mb[j];
+            if (c >= 0 && c < CV) {
+                hit = w >= 0 ? (c >= 2 && tb[c] == (int64_t)w) : c == (int64_t)sl;
+                if (hit) a = ab[j];
+            }
+        }
+        unsigned long long hits = __ballot(hit);
+        while (hits) {                                                        // ascending j, every lane the same sum
+            const int src = __ffsll((long long)hits) - 1;
+            mass += z * __shfl(a, src);
+            hits &= hits - 1;
+        }
+    }
+    // 4. log P
+    if (lane == 0) token_logp[row] = logf(w >= 0 ? gen + mass : mass);
+}
+
+static size_t acg_score_ids_bytes(int64_t rows) { return 2 * align_up((size_t)rows * sizeof(int), 256); }
+
+// one chunk of at most SCORE_ROW_CHUNK rows of the fused form; the pointers are the chunk's own, row0 its first row in the call
+static int launch_acg_score_chunk(const float* o, const void* frag, const float* bias, int64_t VT, int64_t rows, int64_t row0, int64_t rows_per_src, int K,
+                                  const int* word, const int* slot, const float* copy_w, const float* copy_b, const float* attn, int64_t attn_stride,
+                                  const int64_t* lens, int QL, const int64_t* map, const int64_t* e2t, int CV, float* pm, float* ps, float* token_logp,
+                                  hipStream_t st) {
+    const int nvr = score_nvr(score_nrb(rows, K), (VT + 15) / 16), nparts = 4 * nvr;
+    launch_score_gen_walk<true, int>("score_gen_target_kernel<pad>", o, frag, bias, VT, rows, K, nvr, word, token_logp, pm, ps, st);
+    NIR_CHECK_LAUNCH("score_gen_target_kernel<pad>");
+    {
+        ProfScope ps_("acg_score_finish_kernel", st);
+        hipLaunchKernelGGL(acg_score_finish_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, pm, ps, nparts, rows, row0, rows_per_src, word, slot, o,
+                           K, copy_w, copy_b, attn, attn_stride, lens, QL, map, e2t, CV, token_logp);
+    }
+    NIR_CHECK_LAUNCH("acg_score_finish_kernel");
+    return 0;
+}
+
+static bool acg_score_dims_ok(int64_t rows, int K, int64_t VT) {
+    return rows >= 0 && rows < 0x7FFFFFFFLL && K >= 4 && K <= 8192 && K % 4 == 0 && VT > 0 && VT < 0x7FFFFFF0LL - ACG_MAX_CV;
 }
 
 }  // namespace nir
@@ -378,5 +561,80 @@ extern "C" int nir_score_sequences(float* token_logp, const int64_t* target, int
         hipLaunchKernelGGL(score_sequences_kernel, g1(nseq), dim3(256), 0, (hipStream_t)stream, token_logp, target, nseq, T, pad, eos, scores, lengths);
     }
     NIR_CHECK_LAUNCH("score_sequences_kernel");
+    return 0;
+}
+
+// ---- the copy generator's scorer (include/neuroir_acg_score.h) ---------------------------------------------------------------------------------------
+extern "C" size_t nir_acg_score_gen_target_workspace_bytes(int64_t rows, int K, int64_t VT, int fused) {
+    using namespace nir;
+    if (rows <= 0 || !acg_score_dims_ok(rows, K, VT)) return 0;
+    // the two int32 id arrays of the whole call, then the form's buffers: the partials of the largest chunk | the logits and one partial per row
+    if (fused && gen_fusable(K, VT) && !tun(g_tun.exact_f32)) return acg_score_ids_bytes(rows) + score_fused_bytes(rows, K, VT);
+    return acg_score_ids_bytes(rows) + score_plain_bytes(rows, VT) + 2 * align_up((size_t)std::min(rows, score_plain_rows(VT)) * sizeof(float), 256);
+}
+
+extern "C" int nir_acg_score_gen_target(const float* o, int64_t rows, int64_t rows_per_src, int K, const float* gen_w, const float* gen_b,
+                                        const void* gen_frag, int64_t VT, const float* copy_w, const float* copy_b, const float* copy_attn,
+                                        int64_t attn_stride, const int64_t* source_len, int QL, const int64_t* src_map_idx, const int64_t* ext2tgt, int CV,
+                                        const int64_t* target, int64_t pad, void* workspace, size_t workspace_bytes, float* token_logp, int32_t* id_flag,
+                                        nir_stream_t stream) {
+    using namespace nir;
+    hipStream_t st = (hipStream_t)stream;
+    NIR_REQUIRE(o && gen_w && copy_w && copy_b && copy_attn && source_len && src_map_idx && ext2tgt && target && token_logp,
+                "acg_score_gen_target: null pointer");
+    NIR_REQUIRE(rows >= 0 && rows < 0x7FFFFFFFLL, "acg_score_gen_target: rows outside [0, 2^31)");
+    NIR_REQUIRE(K >= 4 && K <= 8192 && K % 4 == 0, "acg_score_gen_target: K outside [4, 8192] or no multiple of 4");
+    NIR_REQUIRE(VT > 0 && VT < 0x7FFFFFF0LL - ACG_MAX_CV, "acg_score_gen_target: VT outside [1, 2^31 - 16 - %d)", ACG_MAX_CV);
+    NIR_REQUIRE(acg_dims_ok(QL, CV), "acg_score_gen_target: QL outside [1, 4096] or CV outside [2, %d]", ACG_MAX_CV);
+    NIR_REQUIRE(attn_stride >= QL, "acg_score_gen_target: attn_stride below QL");
+    NIR_REQUIRE(rows_per_src >= 1 && rows % rows_per_src == 0, "acg_score_gen_target: rows_per_src must be at least 1 and divide rows");
+    if (rows == 0) return 0;
+    const bool fused = gen_frag != nullptr && gen_fusable(K, VT) && !tun(g_tun.exact_f32);
+    if (!workspace || workspace_bytes < nir_acg_score_gen_target_workspace_bytes(rows, K, VT, fused)) {
+        set_error("acg_score_gen_target: workspace null or too small");
+        return NIR_ERR_WORKSPACE;
+    }
+    Workspace a(workspace, workspace_bytes);
+    int* word = a.take<int>((size_t)rows);
+    int* slot = a.take<int>((size_t)rows);
+    {
+        ProfScope ps_("acg_score_resolve_kernel", st);
+        hipLaunchKernelGGL(acg_score_resolve_kernel, g1(rows), dim3(256), 0, st, target, rows, rows_per_src, VT, CV, ext2tgt, pad, word, slot, id_flag);
+    }
+    NIR_CHECK_LAUNCH("acg_score_resolve_kernel");
+    if (fused) {
+        const size_t ids = acg_score_ids_bytes(rows);
+        for (int64_t r0 = 0; r0 < rows; r0 += SCORE_ROW_CHUNK) {
+            const int64_t n = std::min(SCORE_ROW_CHUNK, rows - r0);
+            Workspace c((char*)workspace + ids, workspace_bytes - ids);          // every chunk reuses the partials' room (one stream: in order)
+            const size_t np = (size_t)score_nparts(n, K, VT) * n;
+            float* pm = c.take<float>(np);
+            float* ps = c.take<float>(np);
+            NIR_PROPAGATE(launch_acg_score_chunk(o + r0 * K, gen_frag, gen_b, VT, n, r0, rows_per_src, K, word + r0, slot + r0, copy_w, copy_b,
+                                                 copy_attn + r0 * attn_stride, attn_stride, source_len, QL, src_map_idx, ext2tgt, CV, pm, ps, token_logp + r0,
+                                                 st));
+        }
+        return 0;
+    }
+    const int64_t ch = std::min(rows, score_plain_rows(VT));
+    float* logits = a.take<float>((size_t)ch * VT);
+    float* pm = a.take<float>((size_t)ch);
+    float* ps = a.take<float>((size_t)ch);
+    for (int64_t r0 = 0; r0 < rows; r0 += ch) {
+        const int64_t n = std::min(ch, rows - r0);
+        NIR_PROPAGATE(launch_linear(o + r0 * K, K, nullptr, nullptr, 0, 0, 0, gen_w, K, gen_b, nullptr, logits, VT, n, (int)VT, K, NIR_ACT_NONE, st));
+        {
+            ProfScope ps_("acg_score_row_kernel", st);
+            hipLaunchKernelGGL(acg_score_row_kernel, dim3((unsigned)n), dim3(256), 0, st, logits, VT, word + r0, token_logp + r0, pm, ps);
+        }
+        NIR_CHECK_LAUNCH("acg_score_row_kernel");
+        {
+            ProfScope ps_("acg_score_finish_kernel", st);
+            hipLaunchKernelGGL(acg_score_finish_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, pm, ps, 1, n, r0, rows_per_src, word + r0, slot + r0,
+                               o + r0 * K, K, copy_w, copy_b, copy_attn + r0 * attn_stride, attn_stride, source_len, QL, src_map_idx, ext2tgt, CV,
+                               token_logp + r0);
+        }
+        NIR_CHECK_LAUNCH("acg_score_finish_kernel");
+    }
     return 0;
 }

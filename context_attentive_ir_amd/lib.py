@@ -417,6 +417,14 @@ SESSION_SAMPLE_SIGNATURES = {
                                     _z, c_ip, c_fp, c_fp, c_ip, c_st]),
 }
 
+# Teacher-forced scoring under ACG's collapsed extended distribution, declared in include/neuroir_acg_score.h (csrc/score.hip).  A table of its
+# own, like the ones above.
+ACG_SCORE_SIGNATURES = {
+    "nir_acg_score_gen_target_workspace_bytes": (_z, [_l, _i, _l, _i]),
+    "nir_acg_score_gen_target": (_i, [c_fp, _l, _l, _i, c_fp, c_fp, C.c_void_p, _l, c_fp, c_fp, c_fp, _l, c_ip, _i, c_ip, c_ip, _i, c_ip, _l, C.c_void_p, _z,
+                                      c_fp, C.c_void_p, c_st]),
+}
+
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_SPLIT2 = 0, 1, 2
 DTYPES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "bf16": DTYPE_BF16, "f32_split2": DTYPE_F32_SPLIT2}
 
@@ -434,7 +442,8 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(GRU_DECODE_SIGNATURES.items()) + list(BEAM_SIGNATURES.items()) + list(SESSION_BEAM_SIGNATURES.items())
                                   + list(ACG_BEAM_SIGNATURES.items()) + list(HREDQS_BEAM_SIGNATURES.items()) + list(SCORE_SIGNATURES.items())
-                                  + list(TEACHER_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SESSION_SAMPLE_SIGNATURES.items())):
+                                  + list(TEACHER_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SESSION_SAMPLE_SIGNATURES.items())
+                                  + list(ACG_SCORE_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

@@ -14,6 +14,9 @@ decode():  the extended distribution over the VT target words and the CV words o
 decode_beam(): beam search over the COLLAPSED extended distribution (include/neuroir_acg_beam.h): per beam row the W
            best entries come out of the generator's top-W, its softmax pair and at most CV further candidates (csrc/beam.hip); a slot that
            collapses onto a target word is no candidate of its own.  The same index tensors, not repeated over the beams.
+score_extended(): the teacher-forced log-probability of given EXTENDED ids under that same collapsed distribution (include/neuroir_acg_score.h,
+           DESIGN.md section 31): ONE grouped attention over all rows, ONE generator call that keeps the logits on chip and gathers each row's
+           copy mass; extended_targets() gives the id under which the loss finds a gold token.
 forward(): the teacher-forced loss of CopyGeneratorCriterion on the differentiable HIP operators of autograd.py (the [B, TL, QL] gather of
            the copy mass and the [B, TL] switch logit are tensor glue).
 
@@ -29,7 +32,8 @@ import torch.nn as nn
 
 from .. import autograd as A
 from .. import lib
-from ..constants import PAD, UNK
+from ..constants import EOS, PAD, UNK
+from ..multitask import suggest
 from .layers import CopyGeneratorParams
 from .seq2seq import Seq2seq, build_network, check_supported
 
@@ -86,6 +90,18 @@ def vocab_index(source_vocabs, src_dict, tgt_dict, CV=None):
                 if t != UNK:
                     e2t[b, c] = t
     return e2t, e2s
+
+
+def extended_targets(target_seq, alignment, VT):
+    """the EXTENDED id under which CopyGeneratorCriterion (modules/copy_generator.py:91-135) finds a gold token's probability: VT + alignment
+    where the target is <unk> and its alignment is not (a source word outside the target vocabulary: copy mass alone), the target itself
+    elsewhere (a target word: generator mass plus the mass of its slot, which collapses onto it).  alignment is padded with 0 to the
+    target's width, as forward() pads it."""
+    t, al = lib.ids64(target_seq), lib.ids64(alignment).to(target_seq.device)
+    if al.shape[-1] < t.shape[-1]:
+        al = torch.nn.functional.pad(al, (0, t.shape[-1] - al.shape[-1]))
+    al = al[..., :t.shape[-1]]
+    return torch.where((t == UNK) & (al != UNK), al + int(VT), t)
 
 
 class ACG(Seq2seq):
@@ -169,9 +185,131 @@ class ACG(Seq2seq):
     # ---- eval: scoring -------------------------------------------------------------------------------------------------------------
     def score_candidates(self, *args, **kwargs):
         """not Seq2seq's: a token's likelihood under ACG is generator mass plus copy mass of the collapsed extended distribution, not the
-        generator's softmax alone (DESIGN.md section 26 names it as the follow-up)"""
+        generator's softmax alone; candidates of EXTENDED ids are scored by score_extended"""
         raise NotImplementedError("HIP %s.score_candidates: scoring under the copy generator's collapsed extended distribution is not built yet "
-                                  "(the generator's log-likelihood alone would be another model's)" % type(self).__name__)
+                                  "for target-vocabulary ids (the generator's log-likelihood alone would be another model's); candidates of "
+                                  "EXTENDED ids, with the copy maps of decode(), are scored by score_extended" % type(self).__name__)
+
+    # score_extended: ONE nir_tf_attend over all teacher-forced rows for attn_type dot / general.  False: the tensor-glue front forward() composes
+    # (what attn_type mlp always takes) -- for tests and tools
+    fuse_teacher_front = True
+
+    def _extended_inputs(self, cand, tgt2src, e2s, VT, V):
+        """the embedder ids the ACG decodes feed back for candidates of EXTENDED ids [B, N, TL]: the first token as it is, tgt2src[e] below VT (e
+        itself without a table), ext2src[b, e - VT] from VT on, <unk> outside [0, V)"""
+        B, N, _ = cand.shape
+        CV = e2s.shape[1]
+        low = cand.clamp(0, VT - 1)
+        word_src = low if tgt2src is None else tgt2src[low]
+        ext = e2s.unsqueeze(1).expand(B, N, CV).gather(2, (cand - VT).clamp(0, CV - 1))
+        rep = torch.cat((cand[..., :1], torch.where(cand < VT, word_src, ext)[..., 1:]), -1)
+        return torch.where((rep >= 0) & (rep < V), rep, torch.full_like(rep, UNK))
+
+    def _teacher_front(self, h_all, bank, lens, B, G, w):
+        """h_all [B G, H]: the decoder states of the teacher-forced steps, rows (b, n, t), G = N (TL-1) per source row -> (the attentional
+        outputs [B G, H], the copy attention [B G, QL], exact 0 past the length).  dot / general: ONE nir_tf_attend with the attention output
+        requested -- no [B, G, QL, H] intermediate; mlp, and fuse_teacher_front off: _align and a masked softmax, as forward() composes them.  A
+        copy attention of its own: _align with the attentional output as the query."""
+        att = self.decoder.decoder.attn
+        QL, H = int(bank.shape[1]), int(bank.shape[2])
+        R, dev, mlp = B * G, bank.device, self.attn_type == "mlp"
+        mask = torch.arange(QL, device=dev).unsqueeze(0) < lens.unsqueeze(1)
+
+        def attention(align):
+            return torch.softmax(align.masked_fill(~mask.unsqueeze(1), float("-inf")), -1).reshape(R, QL)
+        if mlp or not self.fuse_teacher_front:
+            align = self._align(h_all.view(B, G, H), bank)
+            ctx = A.softmax_pool(align, mask, bank, mask_div=G).view(B, G, -1)
+            cat, a_std = torch.cat((ctx, h_all.view(B, G, H)), 2).reshape(R, 2 * H), attention(align)
+        else:
+            L = lib.load()
+            sbank = bank if self.attn_type == "dot" else A.linear(bank, w.keep["attn_in_wt"]).contiguous()     # score_j = (W_in h) . m_j = h . (W_in^T m_j)
+            cat = torch.empty(R, 2 * H, device=dev, dtype=torch.float32)
+            a_std = torch.empty(R, QL, device=dev, dtype=torch.float32)
+            if R > 0:
+                ws = lib.workspace(L.nir_tf_attend_workspace_bytes(B, G, QL, H), dev)
+                lib.check(L.nir_tf_attend(lib.ptr(h_all), lib.ptr(bank), lib.ptr(sbank), lib.ptr(lens), None, B, G, B, QL, H, lib.ptr(cat), lib.ptr(a_std),
+                                          QL, lib.ptr(ws), ws.numel(), lib.stream()), "nir_tf_attend")
+        dec_out = A.linear(cat, att.linear_out.weight, att.linear_out.bias if mlp else None, act=None if mlp else "tanh")
+        if self.reuse_copy_attn:
+            return dec_out, a_std
+        return dec_out, attention(self._align(dec_out.view(B, G, H), bank, self.decoder.decoder.copy_attn))
+
+    @torch.no_grad()
+    def score_extended(self, source_rep, source_len, candidate_seq, candidate_rep=None, src_dict=None, tgt_dict=None, tgt2src=None, src_map=None,
+                       blank=None, fill=None, source_vocabs=None, src_map_idx=None, ext2tgt=None, ext2src=None):
+        """log P(candidate | source) under the COLLAPSED extended distribution decode() and decode_beam() choose from (include/neuroir_acg_score.h,
+        DESIGN.md section 31; the reference has no scorer).  candidate_seq [B, N, TL]: EXTENDED ids in [0, VT + CV) -- what the decodes emit --,
+        BOS first, PAD behind the end; candidate_rep [B, N, TL]: the embedder ids fed to the decoder (default: what the decodes feed back, so that
+        [BOS] + decode_beam(..)['predictions'] reproduces the beam's scores and lengths).  The copy inputs are decode()'s.
+        -> {'token_logprobs': [B, N, TL - 1] (step t against token t + 1; 0 at PAD, behind the first EOS and for an id outside [0, VT + CV);
+        -inf for an id without mass), 'scores': [B, N], 'lengths': LongTensor [B, N]}.  A slot that collapses onto a target word is scored as
+        that word.  `force_copy` is a loss option and takes no part, as in the decodes."""
+        return self._score_extended_rows(*self._extended_front(source_rep, source_len, candidate_seq, candidate_rep, src_dict, tgt_dict, tgt2src, src_map,
+                                                               blank, fill, source_vocabs, src_map_idx, ext2tgt, ext2src))
+
+    def _extended_front(self, source_rep, source_len, candidate_seq, candidate_rep, src_dict, tgt_dict, tgt2src, src_map, blank, fill, source_vocabs,
+                        src_map_idx, ext2tgt, ext2src):
+        """score_extended in front of the generator: the checks, the copy maps, the encoder, the default decoder inputs, the decoder's cell over all
+        B N sequences and _teacher_front -> the arguments of _score_extended_rows"""
+        name = type(self).__name__
+        cand = lib.ids64(candidate_seq)
+        if cand.dim() != 3 or cand.shape[0] != source_rep.shape[0] or cand.shape[2] < 2:
+            raise ValueError("score_extended: candidate_seq must be [B, N, TL] with TL >= 2 (got %s)" % (tuple(cand.shape),))
+        if candidate_rep is not None and candidate_rep.numel() != cand.numel():
+            raise ValueError("score_extended: candidate_rep %s does not match candidate_seq %s" % (tuple(candidate_rep.shape), tuple(cand.shape)))
+        B, QL, table = self._decode_ready("score_extended", source_rep, source_len)
+        lib.require_device(cand, candidate_rep)
+        maps = (src_map_idx, ext2tgt, ext2src)
+        if any(t is None for t in maps):
+            maps = self.copy_index(QL, src_map, blank, fill, source_vocabs, src_dict, tgt_dict)
+        dev = table.device
+        idx, e2t, e2s = (lib.ids64(t).to(dev).contiguous() for t in maps)
+        CV = int(e2t.shape[1])
+        if tuple(idx.shape) != (B, QL) or tuple(e2t.shape) != (B, CV) or tuple(e2s.shape) != (B, CV):
+            raise ValueError("%s.score_extended: src_map_idx %s, ext2tgt %s, ext2src %s do not fit %d rows of width %d"
+                             % (name, tuple(idx.shape), tuple(e2t.shape), tuple(e2s.shape), B, QL))
+        if not (1 <= QL <= 4096 and 2 <= CV <= 1024):
+            raise ValueError("%s.score_extended: QL = %d / CV = %d outside the copy generator's range (QL <= 4096, 2 <= CV <= 1024)" % (name, QL, CV))
+        N, T = int(cand.shape[1]), int(cand.shape[2]) - 1
+        src, _ = self._clean_ids(source_rep, None, table.shape[0])
+        lens = lib.ids64(source_len)
+        state, bank = self._encode_state(src, lens)
+        w = self._decoder_weights()
+        VT, H = int(w.struct.VT), int(bank.shape[2])
+        if candidate_rep is not None:
+            rep = self._clean_ids(candidate_rep.reshape(cand.shape), None, table.shape[0])[0]
+        else:
+            if tgt2src is None:
+                tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, VT, dev)
+            rep = self._extended_inputs(cand, tgt2src, e2s, VT, table.shape[0])
+        R = B * N * T
+        temb = A.embed(rep[:, :, :-1].reshape(B * N, T), table)
+        h_all = self._cell_train(temb, [s.repeat_interleave(N, 0).contiguous() for s in state]).reshape(R, H).float().contiguous()   # rows (b, n, t)
+        dec_out, a_copy = self._teacher_front(h_all, bank, lens, B, N * T, w)
+        return dec_out.reshape(R, H).float().contiguous(), a_copy.float().contiguous(), cand, lens, idx, e2t, w
+
+    def _score_extended_rows(self, dec_out, a_copy, cand, lens, idx, e2t, w):
+        """the tail of score_extended: dec_out [B N (TL-1), H] and the copy attention [B N (TL-1), QL] of the teacher-forced rows, rows (b, n, t)
+        -> ONE nir_acg_score_gen_target over all rows (the fused form where the packed weights hold the generator fragment) and one
+        nir_score_sequences"""
+        L = lib.load()
+        B, N, T = int(cand.shape[0]), int(cand.shape[1]), int(cand.shape[2]) - 1
+        R, H, QL, CV, VT, dev = dec_out.shape[0], dec_out.shape[1], int(idx.shape[1]), int(e2t.shape[1]), int(w.struct.VT), dec_out.device
+        target = cand[..., 1:].reshape(-1).contiguous()
+        logp = torch.empty(R, dtype=torch.float32, device=dev)
+        scores = torch.empty(B * N, dtype=torch.float32, device=dev)
+        lengths = torch.empty(B * N, dtype=torch.int64, device=dev)
+        if R > 0:
+            cw, frag = self._copy_weights(), w.keep.get("gen_frag")
+            ws = lib.workspace(L.nir_acg_score_gen_target_workspace_bytes(R, H, VT, 1 if frag is not None else 0), dev)
+            lib.check(L.nir_acg_score_gen_target(lib.ptr(dec_out), R, N * T, H, lib.ptr(w.keep["gen_w"]), lib.ptr(w.keep["gen_b"]), lib.ptr(frag), VT,
+                                                 lib.ptr(cw.keep["copy_w"]), lib.ptr(cw.keep["copy_b"]), lib.ptr(a_copy), QL, lib.ptr(lens), QL,
+                                                 lib.ptr(idx), lib.ptr(e2t), CV, lib.ptr(target), PAD, lib.ptr(ws), ws.numel(), lib.ptr(logp),
+                                                 lib.ptr(self._flag_word(dev)), lib.stream()), "nir_acg_score_gen_target")
+            lib.check(L.nir_score_sequences(lib.ptr(logp), lib.ptr(target), B * N, T, PAD, EOS, lib.ptr(scores), lib.ptr(lengths), lib.stream()),
+                      "nir_score_sequences")
+        return {"token_logprobs": logp.view(B, N, T), "scores": scores.view(B, N), "lengths": lengths.view(B, N)}
 
     # ---- eval: sampling ------------------------------------------------------------------------------------------------------------
     def decode_sample(self, *args, **kwargs):

@@ -467,8 +467,46 @@ class CopyRecommender(Recommender):
 
     def score(self, ex, candidates=None, length_normalize=False):
         raise NotImplementedError("CopyRecommender.score: the likelihood of a candidate under ACG is a sum over its collapsed extended distribution "
-                                  "(generator mass + copy mass per token), not the generator's alone -- scoring it is the follow-up to DESIGN.md "
-                                  "section 26")
+                                  "(generator mass + copy mass per token), not the generator's alone -- scoring it is score_extended(ex, "
+                                  "candidates) over EXTENDED ids (DESIGN.md section 31)")
+
+    @torch.no_grad()
+    def score_extended(self, ex, candidates=None, length_normalize=False):
+        """Teacher-forced log-likelihood under ACG's collapsed extended distribution (ACG.score_extended), by
+        Recommender.score's contract -> {'token_logprobs', 'scores', 'lengths'}.
+        candidates=None: the batch's own target, as the EXTENDED ids under which the loss finds every gold token (extended_targets of
+        `target_seq` and `alignment`), fed `target_words`; additionally 'nll' = -mean over rows of `scores` -- the reference forward's loss in
+        eval mode without force_copy, up to the criterion's 1e-20 -- and 'perplexity' = exp(-sum scores / sum lengths).
+        With candidates -- a LongTensor [B, N, TL] of EXTENDED ids, BOS first, or ex['candidate_seq'] (then with ex['candidate_rep'] as the ids
+        fed to the decoder where given; candidates passed explicitly are fed the default inputs) -- additionally 'ranking' [B, N] as in score().  The copy maps are predict()'s (_copy_fields).  Eager."""
+        from ..recommender.acg import extended_targets
+        ex = self._copy_fields(ex)
+        self._poll_ids()
+        self.network.eval()
+        src, sl = self._dev(self._rows3(ex["source_words"])), self._dev(self._rows2(ex["source_lens"]))
+        own = candidates is None and "candidate_seq" not in ex
+        if own:
+            if "alignment" not in ex:
+                raise AssertionError("CopyRecommender.score_extended needs ex['alignment'] to score the batch's own target")
+            seq = self._rows3(ex["target_seq"])
+            al = ex["alignment"] if torch.is_tensor(ex["alignment"]) else self._rows_of(ex["alignment"], seq.shape[1])
+            cand = extended_targets(seq, al, self.network.generator.weight.shape[0]).unsqueeze(-2)
+            rep = self._rows3(ex["target_words"]).unsqueeze(-2)
+        else:
+            cand = ex["candidate_seq"] if candidates is None else candidates
+            rep = ex.get("candidate_rep") if candidates is None else None      # the batch's inputs belong to the batch's candidates only
+        out = self.network.score_extended(source_rep=src, source_len=sl, candidate_seq=self._dev(cand),
+                                          candidate_rep=self._dev(rep) if rep is not None else None, src_dict=self.src_dict, tgt_dict=self.tgt_dict,
+                                          src_map_idx=self._dev(ex["copy_src_map_idx"]), ext2tgt=self._dev(ex["copy_ext2tgt"]),
+                                          ext2src=self._dev(ex["copy_ext2src"]))
+        self._maybe_check_ids()
+        if own:
+            out["nll"] = -out["scores"].mean()
+            out["perplexity"] = torch.exp(-out["scores"].sum() / out["lengths"].sum().clamp(min=1))
+        else:
+            key = out["scores"] / out["lengths"].clamp(min=1) if length_normalize else out["scores"]
+            out["ranking"] = torch.sort(key, dim=-1, descending=True, stable=True)[1]
+        return out
 
     def predict_samples(self, ex, num_samples, temperature=1.0, top_k=0, seed=None):
         raise NotImplementedError("CopyRecommender.predict_samples: a draw under ACG comes from its collapsed extended distribution (generator mass "

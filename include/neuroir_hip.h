@@ -1158,6 +1158,8 @@ int nir_acg_copy_loss_bwd(const float* logits, int64_t ld, const float* switch_l
 #include "neuroir_sample.h"
 /* ... and for HredQS and the session models, the draw on the split state included (ctypes: lib.SESSION_SAMPLE_SIGNATURES). */
 #include "neuroir_session_sample.h"
+/* Teacher-forced scoring under ACG's collapsed extended distribution (ctypes: lib.ACG_SCORE_SIGNATURES). */
+#include "neuroir_acg_score.h"
 
 #ifdef __cplusplus
 }
