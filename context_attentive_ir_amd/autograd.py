@@ -229,6 +229,16 @@ def _colsum(dy2, ld, M, N):
     return out
 
 
+def _colsum_det(x2, ld, M, N):
+    """column sum in a fixed order (nir_colsum_det_f32): the same bits on every run, which nir_colsum_set_f32 does not give above 64 rows"""
+    L = lib.load()
+    out = torch.empty(N, device=x2.device, dtype=torch.float32)
+    n = L.nir_colsum_det_floats(M, N)
+    ws = torch.empty(n, device=x2.device, dtype=torch.float32) if n else None
+    lib.check(L.nir_colsum_det_f32(lib.ptr(x2) if M else lib.ptr(out), ld, M, N, lib.ptr(out), lib.ptr(ws), lib.stream()), "nir_colsum_det_f32")
+    return out
+
+
 class _Linear(Function):
     @staticmethod
     def forward(ctx, x, w, b, act):
@@ -347,8 +357,8 @@ class _MTConv3(Function):
                                      lib.stream()), "nir_mt_conv3_bwd")
         grads = [None] * 6
         if need_w:
-            dw = _colsum(part, NW, part.shape[0], NW)
-            db = _colsum(dpre, 3 * NF, dpre.shape[0], 3 * NF)
+            dw = _colsum_det(part, NW, part.shape[0], NW)
+            db = _colsum_det(dpre, 3 * NF, dpre.shape[0], 3 * NF)
             o = 0
             for g, w in enumerate((w1, w2, w3)):
                 n = w.numel()

@@ -153,7 +153,8 @@ __global__ __launch_bounds__(256) void mt_conv3_bwd_data_kernel(MtConvArgs p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// weight gradient, per-sample partial sums (reduced over m by the column-sum kernel: no atomics, fixed summation order inside a sample):
+// weight gradient, per-sample partial sums (fixed summation order inside a sample; reduced over m by nir_colsum_det_f32, which adds the rows in
+// a fixed order as well: no atomics anywhere -- nir_colsum_set_f32 would combine its slices of more than 64 rows with atomicAdd):
 //   part[m][w_g[o, c, dy, dx]] = sum_(y, x) dpre[(m, y, x), g NF + o] T[m, c, y + dy - 1, x + dx - pw_g]
 // One workgroup per sample, wave = filter row dy, lane = channel c (C1 <= 64).  The sample's T tile sits in LDS [c][y][x]; a lane walks its
 // channel's row y + dy - 1 and meets every (g, o, dx) whose window holds that element: the gradient value of that pairing is the same for

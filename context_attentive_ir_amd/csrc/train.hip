@@ -3,6 +3,7 @@
 //
 //   nir_linear_wgrad_f32   dW[n,k] += sum_m dY[m,n] X[m,k]   (X dense or gathered embedding rows)  -- fp32 MFMA, "TN" GEMM
 //   nir_colsum_f32         db[n]   += sum_m dY[m,n]
+//   nir_colsum_det_f32     db[n]    = sum_m dY[m,n] in a fixed order: no atomics, the same bits on every run
 //   nir_transpose_f32      W^T for the data-gradient GEMM dX = dY W (nir_linear_f32 computes A B^T)
 //   nir_lstm_train_fwd     LSTM recurrence that also stores the gate activations and cell states of every step
 //   nir_lstm_train_bwd     BPTT: pre-activation gate gradients of every step (dW_ih, dW_hh, db, dx follow as GEMMs)
@@ -391,16 +392,39 @@ __global__ __launch_bounds__(256) void seq_rows_fill_kernel(const int64_t* __res
     if (t >= t0 && t < lens[m]) rows[offs[m] + (t - t0)] = (int32_t)i;
 }
 
-// out[n] += sum_m x[m*ld + n]
+// out[n] += sum_m x[m*ld + n]   (store: slice blockIdx.y writes its sum to out[blockIdx.y * ostride + n] instead)
 __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ x, int64_t ld, int64_t M, int N, float* __restrict__ out,
-                                                     int64_t mslice, int store) {
+                                                     int64_t mslice, int store, int64_t ostride) {
     const int n = blockIdx.x * 256 + threadIdx.x;
     const int64_t ms = (int64_t)blockIdx.y * mslice, me = min(M, ms + mslice);
     if (n >= N) return;
     float s = 0.f;
     for (int64_t m = ms; m < me; ++m) s += x[m * ld + n];
-    if (store) out[n] = s;
+    if (store) out[blockIdx.y * ostride + n] = s;
     else atomicAdd(out + n, s);
+}
+
+// The column sum with 16 row lanes: a block is 16 columns x 16 lanes; lane ty adds rows ms + ty, ms + ty + 16, .. of slice blockIdx.y in row order,
+// then ONE thread per column adds the 16 lane sums in lane order and stores to out[blockIdx.y * ostride + n].  Every output float is a fixed
+// sequence of additions.  Serves narrow matrices (N <= 64: the wide form above would run a few threads over hundreds of rows each) and, with one
+// slice over the slice buffer, the second pass of nir_colsum_det_f32.
+__global__ __launch_bounds__(256) void colsum_lanes_kernel(const float* __restrict__ x, int64_t ld, int64_t M, int N, float* __restrict__ out,
+                                                           int64_t mslice, int64_t ostride) {
+    __shared__ float part[16][17];
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int n = blockIdx.x * 16 + tx;
+    const int64_t ms = (int64_t)blockIdx.y * mslice, me = min(M, ms + mslice);
+    float s = 0.f;
+    if (n < N)
+        for (int64_t m = ms + ty; m < me; m += 16) s += x[m * ld + n];
+    part[ty][tx] = s;
+    __syncthreads();
+    if (ty == 0 && n < N) {
+        float t = 0.f;
+#pragma unroll
+        for (int l = 0; l < 16; ++l) t += part[l][tx];
+        out[blockIdx.y * ostride + n] = t;
+    }
 }
 
 __global__ void transpose_kernel(const float* __restrict__ in, int R, int Cc, float* __restrict__ out) {
@@ -1483,15 +1507,18 @@ extern "C" int nir_linear_wgrad_rows_set_f32(const float* dy, int64_t lddy, int6
     return wgrad_impl(dy, lddy, x, ldx, nullptr, nullptr, 0, dw, lddw, max_rows, N, K, true, (hipStream_t)stream, db, rl);
 }
 
+// rows per slice and slices of a column sum over M rows: at most 256 slices of at least 64 rows
+static int64_t colsum_mslice(int64_t M) { return std::max<int64_t>(64, (M + 255) / 256); }
+static int64_t colsum_slices(int64_t M) { return (M + colsum_mslice(M) - 1) / colsum_mslice(M); }
+
 static int colsum_impl(const float* x, int64_t ld, int64_t M, int N, float* out, bool set, hipStream_t st) {
     using namespace nir;
     NIR_REQUIRE(x && out && M >= 0 && N > 0, "colsum: bad args");
     if (M == 0) return set ? (int)hipMemsetAsync(out, 0, (size_t)N * 4, st) : 0;
-    const int64_t mslice = std::max<int64_t>(64, (M + 255) / 256);
-    const int64_t slices = (M + mslice - 1) / mslice;
+    const int64_t mslice = colsum_mslice(M), slices = colsum_slices(M);
     const int store = set && slices == 1;
     if (set && !store) NIR_PROPAGATE((int)hipMemsetAsync(out, 0, (size_t)N * 4, st));
-    hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)slices), dim3(256), 0, st, x, ld, M, N, out, mslice, store);
+    hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)slices), dim3(256), 0, st, x, ld, M, N, out, mslice, store, (int64_t)0);
     NIR_CHECK_LAUNCH("colsum_kernel");
     return 0;
 }
@@ -1500,6 +1527,32 @@ extern "C" int nir_colsum_f32(const float* x, int64_t ld, int64_t M, int N, floa
 }
 extern "C" int nir_colsum_set_f32(const float* x, int64_t ld, int64_t M, int N, float* out, nir_stream_t stream) {
     return colsum_impl(x, ld, M, N, out, true, (hipStream_t)stream);
+}
+
+// The fixed-order column sum.  Pass 1: every slice of rows is summed and STORED to its row of slice_ws -- N > 64: one thread per column in row
+// order (colsum_kernel); N <= 64: 16 row lanes per column, lane sums added in lane order (colsum_lanes_kernel).  Pass 2: colsum_lanes_kernel over
+// the slice rows.  No atomics, no memset: the bits of out depend on x, M and N alone.
+extern "C" size_t nir_colsum_det_floats(int64_t M, int N) { return (M > 0 && N > 0 && colsum_slices(M) > 1) ? (size_t)colsum_slices(M) * (size_t)N : 0; }
+extern "C" int nir_colsum_det_f32(const float* x, int64_t ld, int64_t M, int N, float* out, float* slice_ws, nir_stream_t stream) {
+    using namespace nir;
+    hipStream_t st = (hipStream_t)stream;
+    NIR_REQUIRE(x && out && M >= 0 && N > 0 && ld >= N, "colsum_det: bad args");
+    if (M == 0) return (int)hipMemsetAsync(out, 0, (size_t)N * 4, st);
+    const int64_t mslice = colsum_mslice(M), slices = colsum_slices(M);
+    NIR_REQUIRE(slices == 1 || slice_ws != nullptr, "colsum_det: %lld rows need the nir_colsum_det_floats() slice buffer", (long long)M);
+    float* const dst = slices == 1 ? out : slice_ws;
+    if (N <= 64) {
+        hipLaunchKernelGGL(colsum_lanes_kernel, dim3((unsigned)((N + 15) / 16), (unsigned)slices), dim3(256), 0, st, x, ld, M, N, dst, mslice, (int64_t)N);
+        NIR_CHECK_LAUNCH("colsum_lanes_kernel");
+    } else {
+        hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)slices), dim3(256), 0, st, x, ld, M, N, dst, mslice, 1, (int64_t)N);
+        NIR_CHECK_LAUNCH("colsum_kernel");
+    }
+    if (slices > 1) {
+        hipLaunchKernelGGL(colsum_lanes_kernel, dim3((unsigned)((N + 15) / 16), 1), dim3(256), 0, st, slice_ws, (int64_t)N, slices, N, out, slices, (int64_t)0);
+        NIR_CHECK_LAUNCH("colsum_lanes_kernel");
+    }
+    return 0;
 }
 
 extern "C" int nir_transpose_f32(const float* in, int R, int Cc, float* out, nir_stream_t stream) {

@@ -866,6 +866,13 @@ int nir_linear_wgrad_rows_set_f32(const float* dy, int64_t lddy, int64_t dy_row_
                                   const int32_t* rows, const int32_t* count, int64_t max_rows, int period, int skip, float* dw, int64_t lddw,
                                   float* db, int N, int K, nir_stream_t stream);
 int nir_colsum_set_f32(const float* x, int64_t ld, int64_t M, int N, float* out, nir_stream_t stream);
+/* out[n] = sum_m x[m*ld + n] in a FIXED order: no atomics, the bits depend on x, M and N alone.  Rows are cut into the slices of nir_colsum_set_f32
+ * (at most 256, of at least 64 rows).  Pass 1 stores every slice's sum to its row of slice_ws: N > 64, one thread per column adds the slice in row
+ * order; N <= 64, 16 lanes per column add rows r, r + 16, .. in order and one thread adds the lane sums in lane order.  Pass 2 adds the slice rows the
+ * same lane-wise way.  slice_ws: nir_colsum_det_floats(M, N) floats supplied by the caller (0, and slice_ws may be NULL, while one slice holds all
+ * rows: M <= 64); nothing is allocated or zero-filled by the library. */
+size_t nir_colsum_det_floats(int64_t M, int N);
+int nir_colsum_det_f32(const float* x, int64_t ld, int64_t M, int N, float* out, float* slice_ws, nir_stream_t stream);
 /* out [C,R] = in [R,C]^T  (data gradient: dX = dY W is nir_linear_f32(dY, W^T)) */
 int nir_transpose_f32(const float* in, int R, int C, float* out, nir_stream_t stream);
 /* n transposes (HOST arrays of device pointers and dims) in as few launches as possible (up to 48 per launch, descriptors as kernel arguments) */
@@ -964,8 +971,11 @@ int nir_im2col_rows_f32(const float* in, int64_t M, int C, int H, int W, int kh,
  * back to nir_im2col_rows_f32 + the GEMMs otherwise.
  * nir_mt_conv3_bwd: dpre [M H W, 3 NF] = gradient of the PRE-activation (dout * (out > 0));  dT [M, C1, H, W] (optional; needs a workspace of
  * nir_mt_conv3_wt_floats() floats);  partial (optional, nir_mt_conv3_partial_floats() floats = rows of NF C1 45) = per-sample, per-column-range
- * weight-gradient sums with the three filters' gradients back to back in their own layouts -- the column sum over the rows (nir_colsum_set_f32)
- * is the gradient, without atomics. */
+ * weight-gradient sums with the three filters' gradients back to back in their own layouts -- the column sum over the rows is the gradient.  Inside
+ * a row the summation order is fixed (y, then x); nir_colsum_det_f32 adds the rows in a fixed order too, so the filter gradients (and the bias
+ * gradients, its column sum of dpre) are the same bits on every run.  nir_colsum_set_f32 is NOT: above 64 rows it combines slices with atomics.
+ * Either pointer NULL skips that gradient; both NULL or M = 0 launch nothing.  Refused (non-zero, nothing launched): a shape that
+ * nir_mt_conv3_supported refuses, a NULL dpre / T / filter, dT without wt_workspace. */
 int nir_mt_conv3_supported(int NF, int C1, int H, int W);
 int nir_mt_conv3_fwd(const float* T, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
                      int64_t M, int C1, int H, int W, int NF, float* out, nir_stream_t stream);
