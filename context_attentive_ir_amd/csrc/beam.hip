@@ -457,13 +457,17 @@ __global__ __launch_bounds__(64) void beam_select_kernel(const float* __restrict
 // offers (any arrival order: beam_insert<TOTAL>); W rounds of (largest head, smallest id among equals) merge them.  log 0 = -inf is a
 // candidate like any other: it loses to every finite one and is ordered by id among its kind.  `finished` [nsrc, W] (optional): the rows of
 // finished beams are skipped, their outputs left as they are -- the selection does not read them.
+// LT (the sampler's plain top-k form, csrc/sample.hip): a target's logit is read from the GEMM's workspace `logits` [R, VT] -- what m and Z were
+// formed from -- instead of the wave's row dot.  LT = false is the beam's kernel, to the instruction; `logits` is not read there.
+template <bool LT = false>
 __global__ __launch_bounds__(64) void acg_beam_row_kernel(const float* __restrict__ o, int K, const float* __restrict__ gen_w, const float* __restrict__ gen_b,
                                                           int64_t VT, const float* __restrict__ pval, const int* __restrict__ pidx,
                                                           const float* __restrict__ pm, const float* __restrict__ ps, int nparts, int64_t R, int64_t nsrc,
                                                           int W, const float* __restrict__ copy_w, const float* __restrict__ copy_b,
                                                           const float* __restrict__ attn, int64_t attn_stride, const int64_t* __restrict__ lens, int QL,
                                                           const int64_t* __restrict__ map, const int64_t* __restrict__ e2t, int CV,
-                                                          const int* __restrict__ finished, float* __restrict__ top_val, int* __restrict__ top_idx) {
+                                                          const int* __restrict__ finished, float* __restrict__ top_val, int* __restrict__ top_idx,
+                                                          const float* __restrict__ logits) {
     constexpr int WM = NIR_BEAM_MAX_W;
     extern __shared__ float acgb_sm[];                         // mass [CV] floats, tl [CV] ints
     __shared__ float rv[WM];
@@ -531,7 +535,9 @@ __global__ __launch_bounds__(64) void acg_beam_row_kernel(const float* __restric
         if (__any(dup)) continue;
         cp = wave_sum(cp);
         float lt = ACG_PAD_LOGIT;
-        if (t != 0) {
+        if constexpr (LT) {
+            if (t != 0) lt = logits[r * VT + t];
+        } else if (t != 0) {
             const float* wr = gen_w + (int64_t)t * K;
             float d = 0.f;
             for (int k = 4 * lane; k < K; k += 256) {
@@ -753,7 +759,7 @@ static bool beam_dims_ok(int W, int64_t VT) { return W >= 1 && W <= NIR_BEAM_MAX
 static int launch_acg_beam_gen_select(const float* o, int64_t R, int64_t nsrc, int K, const float* gen_w, const float* gen_b, const void* gen_frag,
                                       int64_t VT, int W, float* logits, const BeamPartials& p, const float* copy_w, const float* copy_b,
                                       const float* attn, int64_t attn_stride, const int64_t* lens, int QL, const int64_t* map, const int64_t* e2t, int CV,
-                                      const int* finished, float* top_val, int* top_idx, hipStream_t st) {
+                                      const int* finished, float* top_val, int* top_idx, hipStream_t st, bool logit_targets = false) {
     int nparts = 1;
     if (gen_frag) {
         nparts = beam_nparts(R, K, VT);
@@ -764,8 +770,13 @@ static int launch_acg_beam_gen_select(const float* o, int64_t R, int64_t nsrc, i
     }
     {
         ProfScope ps_("acg_beam_row_kernel", st);
-        hipLaunchKernelGGL(acg_beam_row_kernel, dim3((unsigned)R), dim3(64), (size_t)2 * CV * sizeof(float), st, o, K, gen_w, gen_b, VT, p.pval, p.pidx, p.pm,
-                           p.ps, nparts, R, nsrc, W, copy_w, copy_b, attn, attn_stride, lens, QL, map, e2t, CV, finished, top_val, top_idx);
+        if (logit_targets && !gen_frag)
+            hipLaunchKernelGGL(acg_beam_row_kernel<true>, dim3((unsigned)R), dim3(64), (size_t)2 * CV * sizeof(float), st, o, K, gen_w, gen_b, VT, p.pval, p.pidx,
+                               p.pm, p.ps, nparts, R, nsrc, W, copy_w, copy_b, attn, attn_stride, lens, QL, map, e2t, CV, finished, top_val, top_idx, logits);
+        else
+            hipLaunchKernelGGL(acg_beam_row_kernel<false>, dim3((unsigned)R), dim3(64), (size_t)2 * CV * sizeof(float), st, o, K, gen_w, gen_b, VT, p.pval, p.pidx,
+                               p.pm, p.ps, nparts, R, nsrc, W, copy_w, copy_b, attn, attn_stride, lens, QL, map, e2t, CV, finished, top_val, top_idx,
+                               (const float*)nullptr);
     }
     NIR_CHECK_LAUNCH("acg_beam_row_kernel");
     return 0;
@@ -1305,11 +1316,13 @@ extern "C" size_t nir_acg_beam_gen_select_workspace_bytes(int64_t rows, int K, i
     return (fused ? 0 : align_up((size_t)rows * VT * sizeof(float), 256)) + beam_partials_bytes(parts, rows, W, 5);
 }
 
-extern "C" int nir_acg_beam_gen_select(const float* o, int64_t rows, int64_t nsrc, int K, const float* gen_w, const float* gen_b, const void* gen_frag,
-                                       int64_t VT, int W, const float* copy_w, const float* copy_b, const float* copy_attn, int64_t attn_stride,
-                                       const int64_t* source_len, int QL, const int64_t* src_map_idx, const int64_t* ext2tgt, const int64_t* ext2src, int CV,
-                                       void* workspace, size_t workspace_bytes, float* top_val, int32_t* top_idx, nir_stream_t stream) {
-    using namespace nir;
+namespace nir {
+// nir_acg_beam_gen_select; logit_targets (the sampler's top-k form, csrc/sample.hip): in the plain form a collapse target's logit is read from the
+// GEMM's workspace logits instead of the wave's row dot.  The beam's entry passes false.
+int acg_beam_gen_select_rows(const float* o, int64_t rows, int64_t nsrc, int K, const float* gen_w, const float* gen_b, const void* gen_frag,
+                             int64_t VT, int W, const float* copy_w, const float* copy_b, const float* copy_attn, int64_t attn_stride,
+                             const int64_t* source_len, int QL, const int64_t* src_map_idx, const int64_t* ext2tgt, const int64_t* ext2src, int CV,
+                             void* workspace, size_t workspace_bytes, float* top_val, int32_t* top_idx, nir_stream_t stream, bool logit_targets) {
     NIR_REQUIRE(o && gen_w && copy_w && copy_b && copy_attn && source_len && src_map_idx && ext2tgt && ext2src && workspace && top_val && top_idx,
                 "acg_beam_gen_select: null pointer");
     NIR_REQUIRE(rows >= 0 && rows < 0x7FFFFFFFLL && nsrc >= 0 && (rows == 0 || (nsrc > 0 && nsrc <= rows)) && K > 0 && K % 4 == 0 && VT > 0 &&
@@ -1329,7 +1342,16 @@ extern "C" int nir_acg_beam_gen_select(const float* o, int64_t rows, int64_t nsr
     BeamPartials p;
     p.take(a, parts, rows, W, true);
     return launch_acg_beam_gen_select(o, rows, nsrc, K, gen_w, gen_b, fused ? gen_frag : nullptr, VT, W, logits, p, copy_w, copy_b, copy_attn, attn_stride,
-                                      source_len, QL, src_map_idx, ext2tgt, CV, nullptr, top_val, top_idx, (hipStream_t)stream);
+                                      source_len, QL, src_map_idx, ext2tgt, CV, nullptr, top_val, top_idx, (hipStream_t)stream, logit_targets);
+}
+}  // namespace nir
+
+extern "C" int nir_acg_beam_gen_select(const float* o, int64_t rows, int64_t nsrc, int K, const float* gen_w, const float* gen_b, const void* gen_frag,
+                                       int64_t VT, int W, const float* copy_w, const float* copy_b, const float* copy_attn, int64_t attn_stride,
+                                       const int64_t* source_len, int QL, const int64_t* src_map_idx, const int64_t* ext2tgt, const int64_t* ext2src, int CV,
+                                       void* workspace, size_t workspace_bytes, float* top_val, int32_t* top_idx, nir_stream_t stream) {
+    return nir::acg_beam_gen_select_rows(o, rows, nsrc, K, gen_w, gen_b, gen_frag, VT, W, copy_w, copy_b, copy_attn, attn_stride, source_len, QL, src_map_idx,
+                                         ext2tgt, ext2src, CV, workspace, workspace_bytes, top_val, top_idx, stream, false);
 }
 
 extern "C" int nir_acg_beam_select(const float* top_val, const int32_t* top_idx, const float* lse, int64_t B, int W, int64_t VT, int CV,

@@ -26,6 +26,13 @@ static inline LstmStepArgs beam_lstm_step_args(const float* table, const int64_t
     return a;
 }
 
+// nir_acg_beam_gen_select for the sampler's top-k form (csrc/sample.hip).  logit_targets: in the plain form a collapse target's logit is read from
+// the GEMM's workspace logits (what m and Z were formed from) instead of the wave's row dot; the beam's own entry passes false
+int acg_beam_gen_select_rows(const float* o, int64_t rows, int64_t nsrc, int K, const float* gen_w, const float* gen_b, const void* gen_frag, int64_t VT,
+                             int W, const float* copy_w, const float* copy_b, const float* copy_attn, int64_t attn_stride, const int64_t* source_len, int QL,
+                             const int64_t* src_map_idx, const int64_t* ext2tgt, const int64_t* ext2src, int CV, void* workspace, size_t workspace_bytes,
+                             float* top_val, int32_t* top_idx, nir_stream_t stream, bool logit_targets);
+
 static inline bool cars_beam_step16(const nir_cars_decoder_weights* w) { return w->rnn_gate_fold && w->rnn_whh_frag && w->HD % 32 == 0 && !tun(g_tun.exact_f32); }
 static inline bool cars_beam_weights_ok(const nir_cars_decoder_weights* w) {
     return w && w->rnn_wih && w->rnn_whh && w->rnn_bih && w->rnn_bhh && w->attn_out_w && w->dec_attn_w && w->pred1_w && w->pred2_w &&

@@ -18,6 +18,7 @@
 #include "s2s_gen.hpp"
 #include "gen_rows.hpp"
 #include "sample_tail.hpp"
+#include "beam_steps.hpp"
 
 namespace nir {
 
@@ -93,8 +94,9 @@ __global__ __launch_bounds__(256) void sample_noise_kernel(SampleKey k, int64_t 
 // Kernel-level entries (fin == NULL): token / logp / lse [rows], no freeze, no feedback.  Decode (fin given): the freeze rule on the row's state
 // fin / cum / len [rows] (row order r = n nsrc + b), column `step` of predictions and token_logprobs [nsrc, N, max_len], and the id the next
 // step reads, through lut (tgt2src), <unk> (1) outside [0, Vsrc).
+// o.CV > 0 (the copy generator): ids in [VT, VT + CV) are slots of the source row's dictionary, fed back through e2s [nsrc, CV].
 __device__ __forceinline__ void sample_emit(const SampleOut& o, int64_t row, int idx, float y, float lse) {
-    const int tok = (idx >= 0 && (int64_t)idx < o.VT) ? idx : 0;                 // (only a row of NaN logits has no winner)
+    const int tok = (idx >= 0 && (int64_t)idx < o.VT + o.CV) ? idx : 0;          // (only a row of NaN logits has no winner)
     float lp = y - lse;
     if (!o.fin) {
         o.token[row] = tok;
@@ -113,7 +115,7 @@ __device__ __forceinline__ void sample_emit(const SampleOut& o, int64_t row, int
     const int64_t out = ((row % o.nsrc) * o.N + row / o.nsrc) * o.max_len + o.step;
     o.pred[out] = t;
     o.tlp[out] = lp;
-    const int64_t nxt = (o.lut && t < o.VT) ? o.lut[t] : t;
+    const int64_t nxt = (o.CV > 0 && t >= o.VT) ? o.e2s[(row % o.nsrc) * o.CV + (t - o.VT)] : (o.lut && t < o.VT) ? o.lut[t] : t;
     o.next_ids[row] = (nxt >= 0 && nxt < o.Vsrc) ? nxt : 1;
 }
 
@@ -132,13 +134,16 @@ __device__ __forceinline__ void sample_wave_best(float& p, int& i, float& y) {
 // ---- generator + bias + (perturbed arg-max, its logit, max, sum): logits[b, v] = x[b, :] . W[v, :] + bias[v] never leave the chip -------------------
 // The staging, tiling, fragment format, chunked prefetch and logit expression of score_gen_target_kernel on BeamRowsF32 (the greedy kernel's
 // expression: top_k = 1 and the noise-free limit pick its token).  Epilogue per lane and row tile: the online-softmax pair of the UNPERTURBED y
-// (no PAD substitution: that is ACG's), one Philox call, four Gumbel values, the perturbed compare in ascending index order ('>' keeps the
+// (PAD substituted in the copy generator's instantiations only: the flag below), one Philox call, four Gumbel values, the perturbed compare in ascending index order ('>' keeps the
 // first index on ties) carrying (perturbed best, index, that index's y).  Every wave writes one partial per decode row -- pv / pi / py / pm / ps
 // [part][Bd]; a wave without tiles writes (-inf, SAMPLE_NONE, 0, -inf, 0), which the merge passes over.
 // ROWSRC (gen_rows.hpp), as in beam_gen_topk_kernel: BeamRowsF32 -- fp32 rows split on load, a row block's ranges adjacent (s2s_nvr) -- or
 // BeamRowsSplit -- the fp16 term pairs h16 [row][K/8][2][8] the folded LSTM step leaves (HredQS): 16-byte copies into the
 // planes, hq_nvr ranges on the XCD-aware grid.  The instantiations on BeamRowsF32 compile to the registers they had before the parameter.
-template <class ROWSRC, int NBT>
+// PAD (the copy generator's sampler), as in beam_gen_topk_kernel<.., PAD>: the logit of v == 0 is replaced by ACG_PAD_LOGIT
+// before both the online-softmax pair and the perturbed compare; the partial layout is unchanged, and acg_sample_row_kernel merges it.  PAD =
+// false compiles the substitution away.
+template <class ROWSRC, int NBT, bool PAD = false>
 __global__ __launch_bounds__(256, 1) void sample_gen_kernel(const typename ROWSRC::elem* __restrict__ x, const _Float16* __restrict__ wfrag, const float* __restrict__ bias,
                                                             int64_t VT, int64_t ntiles, int64_t Bd, int K, int nvr, SampleKey key, float inv_tau,
                                                             float* __restrict__ pv, int* __restrict__ pi, float* __restrict__ py,
@@ -243,6 +248,9 @@ __global__ __launch_bounds__(256, 1) void sample_gen_kernel(const typename ROWSR
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     y[r] = fmaf(acx[bt][r], SPLIT2_INV, acc[bt][r]) + bv[r];  // the greedy, top-k and scoring kernels' expression
+                    if constexpr (PAD) {
+                        if (v0 + r == 0) y[r] = ACG_PAD_LOGIT;                // the reference assigns this constant behind the linear
+                    }
                     if (v0 + r >= VT) y[r] = -INFINITY;                       // padded tile rows: never win, add exp(-inf) = 0
                     m = fmaxf(m, y[r]);
                 }
@@ -327,7 +335,18 @@ __global__ __launch_bounds__(256) void sample_finish_kernel(const float* __restr
 
 // ---- plain form: one workgroup per row of [rows, VT] logits -> the same choice from the same noise -----------------------------------------------------------
 // A thread takes the ids 4 (tid + 256 i) .. + 3: one Philox call for four logits, as in the fused kernel.
-__global__ __launch_bounds__(256) void sample_row_kernel(const float* __restrict__ logits, int64_t VT, SampleKey key, float inv_tau, SampleOut o) {
+// PAD (the copy generator's sampler): logits[row, 0] is read as ACG_PAD_LOGIT and the row's choice is not emitted -- it comes out as ONE partial
+// (perturbed best, its index, its logit, max, sum) in the fused kernel's layout, SamplePartials [rows], which acg_sample_row_kernel merges.
+struct SamplePartials {                               // one partial per row, the fused kernel's layout
+    float* pv;
+    int* pi;
+    float *py, *pm, *ps;
+};
+template <bool PAD> struct SampleRowDest { using type = SampleOut; };
+template <> struct SampleRowDest<true> { using type = SamplePartials; };
+template <bool PAD = false>
+__global__ __launch_bounds__(256) void sample_row_kernel(const float* __restrict__ logits, int64_t VT, SampleKey key, float inv_tau,
+                                                         typename SampleRowDest<PAD>::type o) {
     __shared__ float lm[4], ls[4], lp[4], ly[4];
     __shared__ int li[4];
     const int64_t row = blockIdx.x;
@@ -343,7 +362,10 @@ __global__ __launch_bounds__(256) void sample_row_kernel(const float* __restrict
 #pragma unroll
         for (int r = 0; r < 4; ++r) {                                         // ascending: '>' keeps the first index on ties
             if (v0 + r < VT) {
-                const float a = y[v0 + r];
+                float a = y[v0 + r];
+                if constexpr (PAD) {
+                    if (v0 + r == 0) a = ACG_PAD_LOGIT;
+                }
                 const float nm = fmaxf(m, a);
                 if (nm > -INFINITY) s = s * expf(m - nm) + expf(a - nm);
                 m = nm;
@@ -363,7 +385,11 @@ __global__ __launch_bounds__(256) void sample_row_kernel(const float* __restrict
         for (int w = 0; w < 4; ++w) S += lm[w] > -INFINITY ? ls[w] * expf(lm[w] - M) : 0.f;
         for (int w = 1; w < 4; ++w)
             if (sample_before(lp[w], li[w], bp, bi)) { bp = lp[w]; bi = li[w]; byv = ly[w]; }
-        sample_emit(o, row, bi, byv, M + logf(S));
+        if constexpr (PAD) {
+            o.pv[row] = bp; o.pi[row] = bi; o.py[row] = byv; o.pm[row] = M; o.ps[row] = S;
+        } else {
+            sample_emit(o, row, bi, byv, M + logf(S));
+        }
     }
 }
 
@@ -378,7 +404,7 @@ __global__ __launch_bounds__(256) void sample_topk_select_kernel(const float* __
     int bi = SAMPLE_NONE;
     for (int j = 0; j < W; ++j) {
         const int v = top_idx[row * W + j];
-        if (v < 0 || (int64_t)v >= o.VT) continue;                            // an empty list slot
+        if (v < 0 || (int64_t)v >= o.VT + o.CV) continue;                     // an empty list slot
         const float a = top_val[row * W + j];
         uint32_t wd[4];
         float g[4];
@@ -387,7 +413,130 @@ __global__ __launch_bounds__(256) void sample_topk_select_kernel(const float* __
         const float p = fmaf(a, inv_tau, r == 0 ? g[0] : r == 1 ? g[1] : r == 2 ? g[2] : g[3]);
         if (sample_before(p, v, bp, bi)) { bp = p; bi = v; byv = a; }
     }
-    sample_emit(o, row, bi, byv, lse[row]);
+    sample_emit(o, row, bi, byv, lse ? lse[row] : 0.f);                       // lse NULL: the lists hold log-probabilities (the copy generator's)
+}
+
+// ---- the copy generator's sampler (include/neuroir_acg_sample.h): one wave per decode row r = n nsrc + b --------------------------
+// A draw from the row's COLLAPSED extended distribution, which is never written.  Steps 1-3 are those of acg_select_kernel / acg_beam_row_kernel in
+// their fp32 expressions: the partials of the PAD-substituting walk merge to (m, Z) and the raw perturbed winner (its perturbed value, id and
+// logit); z = sigmoid(x), 1 - z = sigmoid(-x); the copy mass of every slot (j ascending; map entries at j >= len are never read) and the slots'
+// targets in LDS.  The maps, ext2tgt and the length are those of source row b; o and the copy attention are the decode row's own.  Candidates, each
+// perturbed by the noise of its EXTENDED id e (counter (e >> 2, b, t, n), word e & 3):
+//   the raw perturbed winner v, unless a slot collapses onto it   fmaf(l[v], 1/tau, g[v]) + c_row,  c_row = (log(1 - z) - m - log Z) / tau
+//   a slot that is not collapsed                                  fmaf(logf(mass[c]), 1/tau, g[VT + c])
+//   a target t of one or more slots, once                         fmaf(logf((1 - z) exp(l[t] - m) / Z + the slots' mass), 1/tau, g[t])
+//                                                                 (l[t]: the fp32 row dot behind the fused walk, the GEMM's logit in the plain form)
+// Among the words no slot collapses onto the perturbed values differ from the walk's by the row constant c_row alone, so their best is the walk's
+// winner; if that winner is a target its exact value is at least the raw one and still dominates them.  -inf (P = 0) is never chosen; a row
+// without a candidate of positive probability emits id 0.  The wave's arg-max takes the smaller id among equals; lane 0 runs the tail with
+// logp = logf(P(token)), the probability at tau = 1.  No atomics; every reduction in a fixed order.
+__device__ __forceinline__ float sample_noise1(const SampleKey& k, uint32_t e, uint32_t b, uint32_t n) {
+    uint32_t wd[4];
+    float g[4];
+    sample_noise4(k, e >> 2, b, n, wd, g);
+    const uint32_t r = e & 3;
+    return r == 0 ? g[0] : r == 1 ? g[1] : r == 2 ? g[2] : g[3];
+}
+__global__ __launch_bounds__(64) void acg_sample_row_kernel(const float* __restrict__ o, int K, const float* __restrict__ gen_w, const float* __restrict__ gen_b,
+                                                            int64_t VT, const float* __restrict__ pv, const int* __restrict__ pi,
+                                                            const float* __restrict__ py, const float* __restrict__ pm, const float* __restrict__ ps,
+                                                            int nparts, int64_t R, SampleKey key, float inv_tau, const float* __restrict__ copy_w,
+                                                            const float* __restrict__ copy_b, const float* __restrict__ attn, int64_t attn_stride,
+                                                            const int64_t* __restrict__ lens, int QL, const int64_t* __restrict__ map,
+                                                            const int64_t* __restrict__ e2t, int CV, float* __restrict__ stat_max,
+                                                            float* __restrict__ stat_lse, const float* __restrict__ logits, SampleOut out) {
+    extern __shared__ float acgs_sm[];                         // mass [CV] floats, tl [CV] ints
+    const int lane = threadIdx.x;
+    const int64_t r = blockIdx.x;
+    const uint32_t rn = (uint32_t)r / key.nsrc, rb = (uint32_t)r - rn * key.nsrc;
+    const int64_t b = rb;
+    float* mass = acgs_sm;
+    int* tl = reinterpret_cast<int*>(acgs_sm + CV);
+    // 1. the generator's statistics and the raw perturbed winner (sample_finish_kernel's merge)
+    float m = -INFINITY, s = 0.f, wp = -INFINITY, wy = 0.f;
+    int wi = SAMPLE_NONE;
+    for (int p = lane; p < nparts; p += 64) {
+        const int64_t slot = (int64_t)p * R + r;
+        const float om = pm[slot], os = ps[slot];
+        const float nm = fmaxf(m, om);
+        if (nm > -INFINITY) s = s * expf(m - nm) + os * expf(om - nm);
+        m = nm;
+        const float cp = pv[slot];
+        const int ci = pi[slot];
+        if (sample_before(cp, ci, wp, wi)) { wp = cp; wi = ci; wy = py[slot]; }
+    }
+    const float M = wave_max(m);
+    const float Z = wave_sum(m > -INFINITY ? s * expf(m - M) : 0.f);
+    sample_wave_best(wp, wi, wy);
+    if (lane == 0) {
+        if (stat_max) stat_max[r] = M;
+        if (stat_lse) stat_lse[r] = M + logf(Z);
+    }
+    // 2. the copy switch
+    const float* ob = o + r * K;
+    float x = 0.f;
+    for (int k = 4 * lane; k < K; k += 256) {
+        const float4 a = *reinterpret_cast<const float4*>(ob + k), w = *reinterpret_cast<const float4*>(copy_w + k);
+        x += (a.x * w.x + a.y * w.y) + (a.z * w.z + a.w * w.w);
+    }
+    x = wave_sum(x) + copy_b[0];
+    const float z = 1.0f / (1.0f + expf(-x)), omz = 1.0f / (1.0f + expf(x));
+    // 3. the copy mass and the target of every slot of source row b
+    int len = (int)lens[b];
+    len = len < 0 ? 0 : (len > QL ? QL : len);
+    const int64_t* mb = map + b * QL;
+    const float* ab = attn + r * attn_stride;
+    for (int c = lane; c < CV; c += 64) {
+        float acc = 0.f;
+        for (int j = 0; j < len; ++j)
+            if (mb[j] == c) acc += z * ab[j];
+        mass[c] = acc;
+        const int64_t t = e2t[b * CV + c];
+        tl[c] = (c >= 2 && t >= 0 && t < VT) ? (int)t : -1;
+    }
+    __syncthreads();                                           // (one wave: the LDS writes above are visible below)
+    // 4. the candidates: (perturbed value, extended id, P)
+    float bp = -INFINITY, bP = 0.f;
+    int be = SAMPLE_NONE;
+    auto take = [&](float p, int e, float P) {
+        if (p > -INFINITY && sample_before(p, e, bp, be)) { bp = p; be = e; bP = P; }
+    };
+    auto offer = [&](float P, int e) { take(fmaf(logf(P), inv_tau, sample_noise1(key, (uint32_t)e, rb, rn)), e, P); };
+    for (int c = lane; c < CV; c += 64)
+        if (tl[c] < 0) offer(mass[c], (int)(VT + c));
+    if (wi >= 0 && wi < VT) {                                  // wave-uniform: the raw winner, dropped when it is a target
+        int hit = 0;
+        for (int c = lane; c < CV; c += 64) hit |= tl[c] == wi;
+        if (!__any(hit) && lane == 0) take(wp + (logf(omz) - M - logf(Z)) * inv_tau, wi, omz * expf(wy - M) / Z);
+    }
+    for (int c = 2; c < CV; ++c) {                             // wave-uniform: every slot that is the FIRST of its target id
+        const int t = tl[c];
+        if (t < 0) continue;
+        int dup = 0;
+        float cp = 0.f;
+        for (int c2 = lane; c2 < CV; c2 += 64)
+            if (tl[c2] == t) {
+                if (c2 < c) dup = 1;
+                else cp += mass[c2];
+            }
+        if (__any(dup)) continue;
+        cp = wave_sum(cp);
+        float lt = ACG_PAD_LOGIT;
+        if (t != 0 && logits) {                                // plain form: the GEMM's own logit, the sum m and Z were formed from
+            lt = logits[r * VT + t];
+        } else if (t != 0) {
+            const float* wr = gen_w + (int64_t)t * K;
+            float d = 0.f;
+            for (int k = 4 * lane; k < K; k += 256) {
+                const float4 a = *reinterpret_cast<const float4*>(ob + k), w = *reinterpret_cast<const float4*>(wr + k);
+                d += (a.x * w.x + a.y * w.y) + (a.z * w.z + a.w * w.w);
+            }
+            lt = wave_sum(d) + (gen_b ? gen_b[t] : 0.f);
+        }
+        if (lane == 0) offer(omz * expf(lt - M) / Z + cp, t);
+    }
+    sample_wave_best(bp, be, bP);
+    if (lane == 0) sample_emit(out, r, be, logf(bP), 0.f);
 }
 
 // ---- the decode's first and last launch --------------------------------------------------------------------------------------------------------------
@@ -421,6 +570,32 @@ size_t sample_gen_bytes(int64_t rows, int K, int64_t VT, bool fused) {
     return (size_t)sample_nparts(rows, K, VT) * rows * 5 * sizeof(float) + 5 * 256;
 }
 
+// the fused walk on fp32 rows: sample_nparts partials a row into pv .. ps.  PAD: the copy generator's instantiations, under a name of their own
+template <bool PAD>
+static int launch_sample_gen_partials(const char* name, const float* x, int64_t rows, int K, const float* gen_b, const void* gen_frag, int64_t VT,
+                                      const SampleKey& key, float inv_tau, float* pv, int* pi, float* py, float* pm, float* ps, hipStream_t st) {
+    const int64_t ntiles = (VT + 15) / 16;
+    const int nbt = gen_nbt(K), nvr = s2s_nvr(rows, K, ntiles);
+    const int64_t rb = (rows + 16 * nbt - 1) / (16 * nbt);
+    {
+        ProfScope ps_(prof_shape_name(name, (long long)rows, (long long)VT, K), st);
+        const dim3 grid((unsigned)(nvr * rb));
+        if (nbt == 4) {
+            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<BeamRowsF32, 4, PAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(512));
+            (void)raised;
+            hipLaunchKernelGGL((sample_gen_kernel<BeamRowsF32, 4, PAD>), grid, dim3(256), gen_lds(K), st, x, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key,
+                               inv_tau, pv, pi, py, pm, ps);
+        } else {
+            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<BeamRowsF32, 2, PAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(1024));
+            (void)raised;
+            hipLaunchKernelGGL((sample_gen_kernel<BeamRowsF32, 2, PAD>), grid, dim3(256), gen_lds(K), st, x, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key,
+                               inv_tau, pv, pi, py, pm, ps);
+        }
+    }
+    NIR_CHECK_LAUNCH(name);
+    return 0;
+}
+
 // one sampling step over the whole vocabulary on x [rows, K]: the fused kernel + finish, or the fp32 GEMM + one workgroup per row
 int launch_sample_gen(bool fused, const float* x, int64_t rows, int K, const float* gen_w, const float* gen_b, const void* gen_frag, int64_t VT,
                              const SampleKey& key, float inv_tau, void* ws, size_t ws_bytes, const SampleOut& o, hipStream_t st) {
@@ -430,36 +605,19 @@ int launch_sample_gen(bool fused, const float* x, int64_t rows, int K, const flo
         NIR_PROPAGATE(launch_linear(x, K, nullptr, nullptr, 0, 0, 0, gen_w, K, gen_b, nullptr, logits, VT, rows, (int)VT, K, NIR_ACT_NONE, st));
         {
             ProfScope ps_("sample_row_kernel", st);
-            hipLaunchKernelGGL(sample_row_kernel, dim3((unsigned)rows), dim3(256), 0, st, logits, VT, key, inv_tau, o);
+            hipLaunchKernelGGL(sample_row_kernel<false>, dim3((unsigned)rows), dim3(256), 0, st, logits, VT, key, inv_tau, o);
         }
         NIR_CHECK_LAUNCH("sample_row_kernel");
         return 0;
     }
-    const int64_t ntiles = (VT + 15) / 16;
-    const int nbt = gen_nbt(K), nvr = s2s_nvr(rows, K, ntiles), nparts = 4 * nvr;
-    const int64_t rb = (rows + 16 * nbt - 1) / (16 * nbt);
+    const int nparts = sample_nparts(rows, K, VT);
     const size_t n = (size_t)nparts * rows;
     float* pv = a.take<float>(n);
     int* pi = a.take<int>(n);
     float* py = a.take<float>(n);
     float* pm = a.take<float>(n);
     float* ps = a.take<float>(n);
-    {
-        ProfScope ps_(prof_shape_name("sample_gen_kernel", (long long)rows, (long long)VT, K), st);
-        const dim3 grid((unsigned)(nvr * rb));
-        if (nbt == 4) {
-            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<BeamRowsF32, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(512));
-            (void)raised;
-            hipLaunchKernelGGL((sample_gen_kernel<BeamRowsF32, 4>), grid, dim3(256), gen_lds(K), st, x, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key, inv_tau,
-                               pv, pi, py, pm, ps);
-        } else {
-            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<BeamRowsF32, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(1024));
-            (void)raised;
-            hipLaunchKernelGGL((sample_gen_kernel<BeamRowsF32, 2>), grid, dim3(256), gen_lds(K), st, x, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key, inv_tau,
-                               pv, pi, py, pm, ps);
-        }
-    }
-    NIR_CHECK_LAUNCH("sample_gen_kernel");
+    NIR_PROPAGATE(launch_sample_gen_partials<false>("sample_gen_kernel", x, rows, K, gen_b, gen_frag, VT, key, inv_tau, pv, pi, py, pm, ps, st));
     {
         ProfScope ps_("sample_finish_kernel", st);
         hipLaunchKernelGGL(sample_finish_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, pv, pi, py, pm, ps, nparts, rows, o);
@@ -618,6 +776,183 @@ static int s2s_sample_decode(const float* dec_h, const float* dec_c, const float
     return launch_sample_end(p.cum, p.len, p.attn, B, N, max_len, QL, scores, lengths, attentions, st);
 }
 
+// ---- the copy generator's sampler: the per-row launches and the decode (include/neuroir_acg_sample.h) -----------------------------------------------------
+static bool acg_sample_dims_ok(int QL, int CV, int64_t VT) { return acg_dims_ok(QL, CV) && VT > 0 && VT + CV < 0x7FFFFFF0LL; }
+// whole-distribution form: the partials (fused: sample_nparts a row; plain: the GEMM's logits in front of one a row)
+static size_t acg_sample_gen_bytes(int64_t rows, int K, int64_t VT, bool fused) {
+    if (fused) return sample_gen_bytes(rows, K, VT, true);
+    return align_up((size_t)rows * VT * sizeof(float), 256) + 5 * align_up((size_t)rows * sizeof(float), 256) + 256;
+}
+// top-k form: nir_acg_beam_gen_select's workspace in front of its lists [rows, top_k]
+static size_t acg_sample_topk_bytes(int64_t rows, int K, int64_t VT, int top_k, bool fused) {
+    return align_up(nir_acg_beam_gen_select_workspace_bytes(rows, K, VT, top_k, fused), 256) + 2 * align_up((size_t)rows * top_k * sizeof(float), 256) + 256;
+}
+struct AcgSampleIn {                                   // what a row reads besides o: the switch, the copy attention and the maps of source row r % nsrc
+    const float *copy_w, *copy_b, *attn;
+    int64_t attn_stride;
+    const int64_t* lens;
+    int QL;
+    const int64_t *map, *e2t, *e2s;
+    int CV;
+};
+// one draw per row over the whole collapsed distribution: the PAD-substituting walk (fused) or the fp32 GEMM + sample_row_kernel<true> (plain), then
+// acg_sample_row_kernel
+static int launch_acg_sample_gen_select(bool fused, const float* o, int64_t R, int K, const float* gen_w, const float* gen_b, const void* gen_frag, int64_t VT,
+                                        const SampleKey& key, float inv_tau, const AcgSampleIn& in, void* ws, size_t ws_bytes, float* stat_max,
+                                        float* stat_lse, const SampleOut& out, hipStream_t st) {
+    Workspace a(ws, ws_bytes);
+    int nparts = 1;
+    float* logits = a.take<float>(fused ? 0 : (size_t)R * VT);
+    if (fused) nparts = sample_nparts(R, K, VT);
+    const size_t n = (size_t)nparts * R;
+    float* pv = a.take<float>(n);
+    int* pi = a.take<int>(n);
+    float* py = a.take<float>(n);
+    float* pm = a.take<float>(n);
+    float* ps = a.take<float>(n);
+    if (fused) {
+        NIR_PROPAGATE(launch_sample_gen_partials<true>("acg_sample_gen_kernel", o, R, K, gen_b, gen_frag, VT, key, inv_tau, pv, pi, py, pm, ps, st));
+    } else {
+        NIR_PROPAGATE(launch_linear(o, K, nullptr, nullptr, 0, 0, 0, gen_w, K, gen_b, nullptr, logits, VT, R, (int)VT, K, NIR_ACT_NONE, st));
+        {
+            ProfScope ps_("acg_sample_plain_row_kernel", st);
+            hipLaunchKernelGGL(sample_row_kernel<true>, dim3((unsigned)R), dim3(256), 0, st, logits, VT, key, inv_tau, SamplePartials{pv, pi, py, pm, ps});
+        }
+        NIR_CHECK_LAUNCH("acg_sample_plain_row_kernel");
+    }
+    {
+        ProfScope ps_("acg_sample_row_kernel", st);
+        hipLaunchKernelGGL(acg_sample_row_kernel, dim3((unsigned)R), dim3(64), (size_t)2 * in.CV * sizeof(float), st, o, K, gen_w, gen_b, VT, pv, pi, py, pm, ps,
+                           nparts, R, key, inv_tau, in.copy_w, in.copy_b, in.attn, in.attn_stride, in.lens, in.QL, in.map, in.e2t, in.CV, stat_max, stat_lse, fused ? nullptr : logits, out);
+    }
+    NIR_CHECK_LAUNCH("acg_sample_row_kernel");
+    return 0;
+}
+// one draw per row among the top_k most probable entries: acg_beam_row_kernel's lists with every row live (nir_acg_beam_gen_select's body; in the
+// plain form a target's logit is read from the GEMM's logits), then
+// sample_topk_select_kernel on (log P, e) with lse read as 0
+static int launch_acg_sample_topk(const float* o, int64_t R, int64_t nsrc, int K, const float* gen_w, const float* gen_b, const void* gen_frag, int64_t VT,
+                                  int top_k, const SampleKey& key, float inv_tau, const AcgSampleIn& in, void* ws, size_t ws_bytes, const SampleOut& out,
+                                  hipStream_t st) {
+    Workspace a(ws, ws_bytes);
+    const size_t nb = nir_acg_beam_gen_select_workspace_bytes(R, K, VT, top_k, gen_frag != nullptr);
+    char* bw = a.take<char>(nb);
+    float* tval = a.take<float>((size_t)R * top_k);
+    int* tidx = a.take<int>((size_t)R * top_k);
+    const int rc = acg_beam_gen_select_rows(o, R, nsrc, K, gen_w, gen_b, gen_frag, VT, top_k, in.copy_w, in.copy_b, in.attn, in.attn_stride, in.lens, in.QL,
+                                            in.map, in.e2t, in.e2s, in.CV, bw, nb, tval, tidx, (nir_stream_t)st, true);
+    if (rc != 0) return rc;
+    return launch_sample_topk_select(tval, tidx, nullptr, R, top_k, key, inv_tau, out, st);
+}
+
+struct AcgSamplePlan {
+    S2sStepBufs s;                                    // the stepper's buffers, over R = B N decode rows
+    void* gen;                                        // acg_sample_gen_bytes or acg_sample_topk_bytes
+    size_t gen_bytes;
+    float* cum;                                       // [R] the state of the freeze rule
+    int* fin;
+    int64_t* len;
+    float* attn;                                      // [max_len][R][QL] the decoder's attention rows of every step
+    float *csb, *cq, *ccat, *cattn;                   // a copy attention of its own (reuse_copy_attn off), as in the beam's plan
+    size_t bytes;
+};
+static AcgSamplePlan acg_sample_plan(void* ws, size_t cap, int64_t B, int QL, int N, int top_k, int max_len, int H, int64_t VT, int attn_type, bool fused,
+                                     int cell, bool step16, bool own_copy_attn) {
+    Workspace a(ws, cap);
+    AcgSamplePlan p;
+    const int64_t R = B * N;
+    p.s = s2s_step_bufs(a, R, B, QL, H, VT, attn_type, true, cell, step16);                 // (no logits of the stepper's: the generator's workspace below)
+    p.s.tgt = a.take<int64_t>((size_t)R);
+    if (cell == S2S_CELL_GRU) p.s.gru = a.take<float>(gru_step_scratch_floats(R, H));
+    p.gen_bytes = R == 0 ? 0 : top_k > 0 ? acg_sample_topk_bytes(R, H, VT, top_k, fused) : acg_sample_gen_bytes(R, H, VT, fused);
+    p.gen = a.take<char>(p.gen_bytes);
+    p.cum = a.take<float>((size_t)R);
+    p.fin = a.take<int>((size_t)R);
+    p.len = a.take<int64_t>((size_t)R);
+    p.attn = a.take<float>((size_t)max_len * R * QL);
+    p.csb = p.cq = p.ccat = p.cattn = nullptr;
+    if (own_copy_attn) {
+        p.csb = a.take<float>(attn_type == NIR_S2S_ATTN_DOT ? 0 : (size_t)B * QL * H);
+        p.cq = a.take<float>(attn_type == NIR_S2S_ATTN_MLP ? (size_t)R * H : 0);
+        p.ccat = a.take<float>((size_t)R * 2 * H);
+        p.cattn = a.take<float>((size_t)R * QL);
+    }
+    p.bytes = align_up(a.off, 256);
+    return p;
+}
+static size_t acg_sample_decode_workspace_bytes(int64_t B, int QL, int CV, int N, int top_k, int max_len, const nir_seq2seq_decoder_weights* w,
+                                                const nir_acg_copy_weights* cw, int cell) {
+    if (!cw || !s2s_weights_ok(w) || B < 0 || QL <= 0 || max_len <= 0 || !sample_dims_ok(N, top_k, w->VT) || B * N >= 0x7FFFFFFFLL) return 0;
+    const AcgDecode g{cw, nullptr, nullptr, nullptr, CV};
+    if (!acg_weights_ok(w, &g) || !acg_sample_dims_ok(QL, CV, w->VT)) return 0;
+    return acg_sample_plan(nullptr, 0, B, QL, N, top_k, max_len, w->H, w->VT, w->attn_type, s2s_fused(w), cell, s2s_step16(w), !cw->reuse_copy_attn).bytes;
+}
+
+// s2s_sample_decode with the copy generator's tail (s2s_beam_decode's): (a second attention over the R rows with nsrc = B whose
+// query is the attentional output,) then one draw per row from the collapsed extended distribution, or from its top_k entries.
+static int acg_sample_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, const float* table,
+                             int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len, const nir_seq2seq_decoder_weights* w,
+                             const nir_acg_copy_weights* cw, const int64_t* src_map_idx, const int64_t* ext2tgt, const int64_t* ext2src, int CV, int N,
+                             int top_k, float inv_tau, uint64_t seed, void* workspace, size_t workspace_bytes, int64_t* predictions, float* token_logprobs,
+                             float* scores, int64_t* lengths, float* attentions, int cell, hipStream_t st) {
+    NIR_REQUIRE(cw, "acg_sample_decode: null copy weights");
+    NIR_REQUIRE(N >= 1 && B >= 0 && B * (int64_t)N < 0x7FFFFFFFLL, "acg_sample_decode: N < 1 or too many decode rows");
+    const int64_t R = B * N;
+    S2sStepper s{"acg_sample_decode", w, cell, table, memory_bank, source_len, V, R, B, E, QL, st};
+    NIR_PROPAGATE(s.check(dec_h, dec_c, predictions && token_logprobs && scores && lengths && attentions, bos, max_len));
+    NIR_REQUIRE(sample_dims_ok(N, top_k, w->VT), "acg_sample_decode: top_k outside 0 .. %d or above the target vocabulary", NIR_BEAM_MAX_W);
+    NIR_REQUIRE(sample_tau_ok(inv_tau), "acg_sample_decode: inv_temperature must be finite and > 0");
+    const AcgDecode g{cw, src_map_idx, ext2tgt, ext2src, CV};
+    NIR_REQUIRE(acg_weights_ok(w, &g), "acg_sample_decode: copy weights incomplete for the attention type");
+    NIR_REQUIRE(src_map_idx && ext2tgt && ext2src, "acg_sample_decode: null index tensor");
+    NIR_REQUIRE(acg_sample_dims_ok(QL, CV, w->VT), "acg_sample_decode: QL outside [1, 4096], CV outside [2, %d], or VT + CV too large", ACG_MAX_CV);
+    const int H = w->H;
+    const bool fused = s.fused, own_copy_attn = !cw->reuse_copy_attn, mlp = w->attn_type == NIR_S2S_ATTN_MLP;
+    const AcgSamplePlan p = acg_sample_plan(workspace, workspace_bytes, B, QL, N, top_k, max_len, H, w->VT, w->attn_type, fused, cell, s.step16, own_copy_attn);
+    if (B == 0) return 0;                                 // nothing to enqueue: no workspace is needed either
+    if (!workspace || p.bytes > workspace_bytes) {
+        set_error("acg_sample_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
+        return NIR_ERR_WORKSPACE;
+    }
+    s.b = p.s;
+    NIR_PROPAGATE(s.prepare(dec_h, bos, p.s.h16[1]));
+    NIR_PROPAGATE(launch_sample_init(p.cum, p.fin, p.len, R, max_len, st));
+    const float* csb = memory_bank;                       // the score bank of the copy attention, over the B source rows (s2s_beam_decode)
+    if (own_copy_attn && w->attn_type != NIR_S2S_ATTN_DOT) {
+        NIR_PROPAGATE(launch_linear(memory_bank, H, nullptr, nullptr, 0, 0, 0, mlp ? cw->attn_ctx_w : cw->attn_in_wt, H, nullptr, nullptr, p.csb, H, B * QL, H, H,
+                                    NIR_ACT_NONE, st));
+        csb = p.csb;
+    }
+    SampleOut o{nullptr, nullptr, nullptr, p.fin, p.cum, p.len, predictions, token_logprobs, p.s.tgt, tgt2src, V, w->VT, B, N, 0, max_len, ext2src, CV};
+    const float* hp = dec_h;
+    const float* cp = dec_c;
+    for (int step = 0; step < max_len; ++step) {
+        float* hn = p.s.h[step & 1];
+        float* cn = p.s.c[step & 1];
+        float* arow = p.attn + (int64_t)step * R * QL;
+        NIR_PROPAGATE(s.step(hp, cp, hn, cn, p.s.h16[(step + 1) & 1], p.s.h16[step & 1], arow, QL));
+        const float* ca = arow;
+        if (own_copy_attn) {
+            if (mlp)
+                NIR_PROPAGATE(launch_linear(p.s.ah, H, nullptr, nullptr, 0, 0, 0, cw->attn_query_w, H, cw->attn_query_b, nullptr, p.cq, H, R, H, H, NIR_ACT_NONE, st));
+            NIR_PROPAGATE(launch_attend(mlp ? p.cq : p.s.ah, p.s.ah, memory_bank, csb, cw->attn_v, source_len, R, QL, H, mlp, p.ccat, p.cattn, QL, st, B));
+            ca = p.cattn;
+        }
+        const SampleKey key = sample_key(seed, step, B);
+        const AcgSampleIn in{cw->copy_w, cw->copy_b, ca, QL, source_len, QL, src_map_idx, ext2tgt, ext2src, CV};
+        o.step = step;
+        if (top_k > 0)
+            NIR_PROPAGATE(launch_acg_sample_topk(p.s.ah, R, B, H, w->gen_w, w->gen_b, fused ? w->gen_frag : nullptr, w->VT, top_k, key, inv_tau, in, p.gen, p.gen_bytes,
+                                                 o, st));
+        else
+            NIR_PROPAGATE(launch_acg_sample_gen_select(fused, p.s.ah, R, H, w->gen_w, w->gen_b, w->gen_frag, w->VT, key, inv_tau, in, p.gen, p.gen_bytes, nullptr,
+                                                       nullptr, o, st));
+        hp = hn;
+        cp = cn;
+    }
+    return launch_sample_end(p.cum, p.len, p.attn, B, N, max_len, QL, scores, lengths, attentions, st);
+}
+
 }  // namespace nir
 
 extern "C" int nir_sample_noise(uint64_t seed, int64_t step, int64_t nsrc, int64_t rows, int64_t VT, float* g, uint32_t* words, nir_stream_t stream) {
@@ -694,4 +1029,73 @@ extern "C" int nir_sample_seq2seq_gru_decode(const float* dec_h, const float* me
     return nir::s2s_sample_decode(dec_h, nullptr, memory_bank, source_len, B, QL, N, top_k, inv_temperature, seed, table, V, E, tgt2src, bos, max_len, w,
                                   workspace, workspace_bytes, predictions, token_logprobs, scores, lengths, attentions, nir::S2S_CELL_GRU,
                                   (hipStream_t)stream);
+}
+
+// ---- the copy generator's sampler (include/neuroir_acg_sample.h) ---------------------------------------------------------------------------------------
+extern "C" size_t nir_acg_sample_gen_select_workspace_bytes(int64_t rows, int K, int64_t VT, int top_k, int fused) {
+    using namespace nir;
+    if (rows <= 0 || rows >= 0x7FFFFFFFLL || K < 4 || K > 8192 || K % 4 || VT <= 0 || VT >= 0x7FFFFFF0LL || !sample_dims_ok(1, top_k, VT)) return 0;
+    const bool f = fused && gen_fusable(K, VT) && !tun(g_tun.exact_f32);
+    return top_k > 0 ? acg_sample_topk_bytes(rows, K, VT, top_k, f) : acg_sample_gen_bytes(rows, K, VT, f);
+}
+
+extern "C" int nir_acg_sample_gen_select(const float* o, int64_t rows, int64_t nsrc, int K, const float* gen_w, const float* gen_b, const void* gen_frag,
+                                         int64_t VT, int top_k, float inv_temperature, uint64_t seed, int64_t step, const float* copy_w,
+                                         const float* copy_b, const float* copy_attn, int64_t attn_stride, const int64_t* source_len, int QL,
+                                         const int64_t* src_map_idx, const int64_t* ext2tgt, const int64_t* ext2src, int CV, void* workspace,
+                                         size_t workspace_bytes, int32_t* token, float* logp, float* gen_max, float* gen_lse, nir_stream_t stream) {
+    using namespace nir;
+    NIR_REQUIRE(o && gen_w && copy_w && copy_b && copy_attn && source_len && src_map_idx && ext2tgt && ext2src && token && logp,
+                "acg_sample_gen_select: null pointer");
+    NIR_REQUIRE(sample_key_ok(step, nsrc, rows) && (rows == 0 || nsrc <= rows),
+                "acg_sample_gen_select: step outside [0, 2^32), nsrc outside [1, rows] or rows outside [0, 2^31)");
+    NIR_REQUIRE(K >= 4 && K <= 8192 && K % 4 == 0 && attn_stride >= QL, "acg_sample_gen_select: K outside [4, 8192], no multiple of 4, or attn_stride < QL");
+    NIR_REQUIRE(acg_sample_dims_ok(QL, CV, VT), "acg_sample_gen_select: QL outside [1, 4096], CV outside [2, %d], or VT + CV outside [3, 2^31 - 16)", ACG_MAX_CV);
+    NIR_REQUIRE(sample_dims_ok(1, top_k, VT), "acg_sample_gen_select: top_k outside 0 .. %d or above VT", NIR_BEAM_MAX_W);
+    NIR_REQUIRE(sample_tau_ok(inv_temperature), "acg_sample_gen_select: inv_temperature must be finite and > 0");
+    NIR_REQUIRE(top_k == 0 || (!gen_max && !gen_lse), "acg_sample_gen_select: gen_max / gen_lse are outputs of the whole-distribution form (top_k = 0)");
+    if (rows == 0) return 0;
+    const bool fused = s2s_gen_fused(gen_frag, K, VT);
+    const size_t need = top_k > 0 ? acg_sample_topk_bytes(rows, K, VT, top_k, fused) : acg_sample_gen_bytes(rows, K, VT, fused);
+    if (!workspace || workspace_bytes < need) {
+        set_error("acg_sample_gen_select: workspace null or too small");
+        return NIR_ERR_WORKSPACE;
+    }
+    const SampleOut out{token, logp, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, VT, nsrc, 1, 0, 1, ext2src, CV};
+    const AcgSampleIn in{copy_w, copy_b, copy_attn, attn_stride, source_len, QL, src_map_idx, ext2tgt, ext2src, CV};
+    const SampleKey key = sample_key(seed, step, nsrc);
+    if (top_k > 0)
+        return launch_acg_sample_topk(o, rows, nsrc, K, gen_w, gen_b, fused ? gen_frag : nullptr, VT, top_k, key, inv_temperature, in, workspace, workspace_bytes,
+                                      out, (hipStream_t)stream);
+    return launch_acg_sample_gen_select(fused, o, rows, K, gen_w, gen_b, gen_frag, VT, key, inv_temperature, in, workspace, workspace_bytes, gen_max, gen_lse, out,
+                                        (hipStream_t)stream);
+}
+
+extern "C" size_t nir_acg_sample_decode_workspace_bytes(int64_t B, int QL, int CV, int N, int top_k, int max_len, const nir_seq2seq_decoder_weights* w,
+                                                        const nir_acg_copy_weights* cw) {
+    return nir::acg_sample_decode_workspace_bytes(B, QL, CV, N, top_k, max_len, w, cw, nir::S2S_CELL_LSTM);
+}
+extern "C" int nir_acg_sample_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL,
+                                     const float* table, int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len,
+                                     const nir_seq2seq_decoder_weights* w, const nir_acg_copy_weights* cw, const int64_t* src_map_idx,
+                                     const int64_t* ext2tgt, const int64_t* ext2src, int CV, int N, int top_k, float inv_temperature, uint64_t seed,
+                                     void* workspace, size_t workspace_bytes, int64_t* predictions, float* token_logprobs, float* scores, int64_t* lengths,
+                                     float* attentions, nir_stream_t stream) {
+    return nir::acg_sample_decode(dec_h, dec_c, memory_bank, source_len, B, QL, table, V, E, tgt2src, bos, max_len, w, cw, src_map_idx, ext2tgt, ext2src, CV, N,
+                                  top_k, inv_temperature, seed, workspace, workspace_bytes, predictions, token_logprobs, scores, lengths, attentions,
+                                  nir::S2S_CELL_LSTM, (hipStream_t)stream);
+}
+extern "C" size_t nir_acg_sample_gru_decode_workspace_bytes(int64_t B, int QL, int CV, int N, int top_k, int max_len, const nir_seq2seq_decoder_weights* w,
+                                                            const nir_acg_copy_weights* cw) {
+    return nir::acg_sample_decode_workspace_bytes(B, QL, CV, N, top_k, max_len, w, cw, nir::S2S_CELL_GRU);
+}
+extern "C" int nir_acg_sample_gru_decode(const float* dec_h, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, const float* table,
+                                         int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len, const nir_seq2seq_decoder_weights* w,
+                                         const nir_acg_copy_weights* cw, const int64_t* src_map_idx, const int64_t* ext2tgt, const int64_t* ext2src, int CV,
+                                         int N, int top_k, float inv_temperature, uint64_t seed, void* workspace, size_t workspace_bytes,
+                                         int64_t* predictions, float* token_logprobs, float* scores, int64_t* lengths, float* attentions,
+                                         nir_stream_t stream) {
+    return nir::acg_sample_decode(dec_h, nullptr, memory_bank, source_len, B, QL, table, V, E, tgt2src, bos, max_len, w, cw, src_map_idx, ext2tgt, ext2src, CV, N,
+                                  top_k, inv_temperature, seed, workspace, workspace_bytes, predictions, token_logprobs, scores, lengths, attentions,
+                                  nir::S2S_CELL_GRU, (hipStream_t)stream);
 }

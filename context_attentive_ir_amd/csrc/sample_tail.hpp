@@ -33,6 +33,10 @@ struct SampleOut {
     const int64_t* lut;
     int64_t Vsrc, VT, nsrc;
     int N, step, max_len;
+    // the copy generator's sampler: ids in [VT, VT + CV) are dictionary slots of source row `row % nsrc`, fed back through
+    // e2s [nsrc, CV]; CV = 0 everywhere else
+    const int64_t* e2s = nullptr;
+    int CV = 0;
 };
 
 static inline bool sample_tau_ok(float inv_tau) { return std::isfinite(inv_tau) && inv_tau > 0.f; }
@@ -49,6 +53,7 @@ int launch_sample_gen(bool fused, const float* x, int64_t rows, int K, const flo
 size_t sample_gen_split_bytes(int64_t rows, int K, int64_t VT);
 int launch_sample_gen_split(const _Float16* h16, int64_t rows, int K, const float* gen_b, const void* gen_frag, int64_t VT, const SampleKey& key,
                             float inv_tau, void* ws, size_t ws_bytes, const SampleOut& o, hipStream_t st);
+// lse NULL: read as 0 (top_val already a log-probability), ids in [0, o.VT + o.CV) -- the copy generator's lists
 int launch_sample_topk_select(const float* top_val, const int* top_idx, const float* lse, int64_t rows, int W, const SampleKey& key, float inv_tau,
                               const SampleOut& o, hipStream_t st);
 // the decode's first and last launch: the freeze rule's state over R rows; scores / lengths (and the attention rows, QL > 0) in sample order

@@ -427,6 +427,20 @@ ACG_SCORE_SIGNATURES = {
                                       c_fp, C.c_void_p, c_st]),
 }
 
+# Sampling decode for ACG (draws from the collapsed extended distribution), declared in include/neuroir_acg_sample.h (csrc/sample.hip): every
+# symbol starts with nir_acg_sample_.  A table of its own, like the ones above.
+ACG_SAMPLE_SIGNATURES = {
+    "nir_acg_sample_gen_select_workspace_bytes": (_z, [_l, _i, _l, _i, _i]),
+    "nir_acg_sample_gen_select": (_i, [c_fp, _l, _l, _i, c_fp, c_fp, C.c_void_p, _l, _i, _f, _u64, _l, c_fp, c_fp, c_fp, _l, c_ip, _i, c_ip, c_ip, c_ip, _i,
+                                       C.c_void_p, _z, C.c_void_p, c_fp, c_fp, c_fp, c_st]),
+    "nir_acg_sample_decode_workspace_bytes": (_z, [_l, _i, _i, _i, _i, _i, _W, _AW]),
+    "nir_acg_sample_decode": (_i, [c_fp, c_fp, c_fp, c_ip, _l, _i, c_fp, _l, _i, c_ip, _l, _i, _W, _AW, c_ip, c_ip, c_ip, _i, _i, _i, _f, _u64, C.c_void_p, _z,
+                                   c_ip, c_fp, c_fp, c_ip, c_fp, c_st]),
+    "nir_acg_sample_gru_decode_workspace_bytes": (_z, [_l, _i, _i, _i, _i, _i, _W, _AW]),
+    "nir_acg_sample_gru_decode": (_i, [c_fp, c_fp, c_ip, _l, _i, c_fp, _l, _i, c_ip, _l, _i, _W, _AW, c_ip, c_ip, c_ip, _i, _i, _i, _f, _u64, C.c_void_p, _z,
+                                       c_ip, c_fp, c_fp, c_ip, c_fp, c_st]),
+}
+
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_SPLIT2 = 0, 1, 2
 DTYPES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "bf16": DTYPE_BF16, "f32_split2": DTYPE_F32_SPLIT2}
 
@@ -445,7 +459,7 @@ def load():
         for name, (res, args) in (list(SIGNATURES.items()) + list(GRU_DECODE_SIGNATURES.items()) + list(BEAM_SIGNATURES.items()) + list(SESSION_BEAM_SIGNATURES.items())
                                   + list(ACG_BEAM_SIGNATURES.items()) + list(HREDQS_BEAM_SIGNATURES.items()) + list(SCORE_SIGNATURES.items())
                                   + list(TEACHER_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SESSION_SAMPLE_SIGNATURES.items())
-                                  + list(ACG_SCORE_SIGNATURES.items())):
+                                  + list(ACG_SCORE_SIGNATURES.items()) + list(ACG_SAMPLE_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

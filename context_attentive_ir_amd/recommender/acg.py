@@ -32,7 +32,7 @@ import torch.nn as nn
 
 from .. import autograd as A
 from .. import lib
-from ..constants import EOS, PAD, UNK
+from ..constants import BOS, EOS, PAD, UNK
 from ..multitask import suggest
 from .layers import CopyGeneratorParams
 from .seq2seq import Seq2seq, build_network, check_supported
@@ -314,9 +314,75 @@ class ACG(Seq2seq):
     # ---- eval: sampling ------------------------------------------------------------------------------------------------------------
     def decode_sample(self, *args, **kwargs):
         """not Seq2seq's: ACG's next-token distribution is the collapsed extended one (generator mass plus copy mass), which the generator's
-        Gumbel arg-max does not draw from (DESIGN.md section 28 names it as a follow-up)"""
-        raise NotImplementedError("HIP %s.decode_sample: sampling from the copy generator's collapsed extended distribution is not built yet "
-                                  "(a draw from the generator's softmax alone would be another model's)" % type(self).__name__)
+        Gumbel arg-max does not draw from; the draw over EXTENDED ids, with the copy maps of decode(), is sample_extended"""
+        raise NotImplementedError("HIP %s.decode_sample: a draw from the generator's softmax alone would be another model's; sampling from the copy "
+                                  "generator's collapsed extended distribution, over EXTENDED ids and with the copy maps of decode(), is "
+                                  "sample_extended" % type(self).__name__)
+
+    _ACG_SAMPLE_ENTRY = "nir_acg_sample%s_decode"        # (+ "_workspace_bytes"): nir_acg_sample_decode, nir_acg_sample_gru_decode
+
+    @torch.no_grad()
+    def sample_extended(self, source_rep, source_len, max_len, num_samples, temperature=1.0, top_k=0, seed=0, src_dict=None, tgt_dict=None,
+                        src_map=None, blank=None, fill=None, source_vocabs=None, tgt2src=None, src_map_idx=None, ext2tgt=None, ext2src=None):
+        """`num_samples` i.i.d. draws per source row from the COLLAPSED extended distribution decode() and decode_beam() choose from, at
+        `temperature`, over all of it (top_k = 0) or restricted to each step's top_k most probable entries (1 .. lib.BEAM_MAX_W, at most VT;
+        top_k = 1 is decode()), over max_len steps with no early stop (include/neuroir_acg_sample.h; the reference has no
+        sampler) -> Seq2seq.decode_sample's dict with EXTENDED ids in 'predictions' [B, N, max_len]: below VT a target word, from VT on slot
+        id - VT of the row's dynamic dictionary; a slot that collapses onto a target word is never drawn, its mass is part of the word's.
+        'token_logprobs' is log P(token) at temperature 1 over the full collapsed distribution whatever temperature and top_k are, so
+        score_extended([BOS] + predictions) reproduces 'scores' and 'lengths' (for samples without PAD in front of their first EOS; PAD has
+        real mass under ACG).  The noise is Seq2seq.decode_sample's, keyed by the extended id.  The copy inputs are decode()'s; neither they nor
+        the memory bank are repeated.  ONE C call; neither logits nor a dense copy distribution is written (`fuse_generator_argmax = False`, and
+        for top_k > 0 `fuse_generator_topk = False`: the plain generator forms; over the whole distribution the plain form is also the default
+        beyond `fuse_sample_max_rows` decode rows)."""
+        name = type(self).__name__
+        VT = int(self.generator.weight.shape[0])
+        N, K, tau, seed = suggest.check_sample_args(self, num_samples, temperature, top_k, seed, VT)      # (its messages say decode_sample: the shared rules)
+        B, QL, table = self._decode_ready("sample_extended", source_rep, source_len)
+        maps = (src_map_idx, ext2tgt, ext2src)
+        if any(t is None for t in maps):
+            maps = self.copy_index(QL, src_map, blank, fill, source_vocabs, src_dict, tgt_dict)
+        dev = table.device
+        idx, e2t, e2s = (lib.ids64(t).to(dev).contiguous() for t in maps)
+        CV = int(e2t.shape[1])
+        if tuple(idx.shape) != (B, QL) or tuple(e2t.shape) != (B, CV) or tuple(e2s.shape) != (B, CV):
+            raise ValueError("%s.sample_extended: src_map_idx %s, ext2tgt %s, ext2src %s do not fit %d rows of width %d"
+                             % (name, tuple(idx.shape), tuple(e2t.shape), tuple(e2s.shape), B, QL))
+        if not (1 <= QL <= 4096 and 2 <= CV <= 1024):
+            raise ValueError("%s.sample_extended: QL = %d / CV = %d outside the copy generator's range (QL <= 4096, 2 <= CV <= 1024)" % (name, QL, CV))
+        L = lib.load()
+        w, cw = self._decoder_weights(), self._copy_weights()
+        src, _ = self._clean_ids(source_rep, None, table.shape[0])
+        lens = lib.ids64(source_len)
+        state, bank = self._encode_state(src, lens)
+        state = [s.repeat(N, 1).contiguous() for s in state]                  # row n B + b
+        ws_ref = w.ref()
+        fuse = self.fuse_generator_topk if K > 0 else (self.fuse_generator_argmax
+                                                       and B * N <= getattr(self, "fuse_sample_max_rows", suggest.FUSE_SAMPLE_MAX_ROWS))
+        if w.struct.gen_frag and not fuse:
+            plain = lib.Seq2seqDecoderWeights.from_buffer_copy(w.struct)      # the same pack without the fragment: the plain generator form
+            plain.gen_frag = None
+            ws_ref = lib.C.byref(plain)
+        if tgt2src is None:
+            tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, VT, dev)
+        t = table.detach().float().contiguous()
+        max_len = int(max_len)
+        out = {"predictions": torch.empty(B, N, max_len, dtype=torch.int64, device=dev),
+               "token_logprobs": torch.empty(B, N, max_len, dtype=torch.float32, device=dev),
+               "scores": torch.empty(B, N, dtype=torch.float32, device=dev), "lengths": torch.empty(B, N, dtype=torch.int64, device=dev),
+               "attentions": torch.empty(B, N, max_len, QL, dtype=torch.float32, device=dev)}
+        if B > 0 and max_len > 0:
+            entry = self._ACG_SAMPLE_ENTRY % self._ENTRY_CELL
+            nb = getattr(L, entry + "_workspace_bytes")(B, QL, CV, N, K, max_len, ws_ref, cw.ref())
+            if nb == 0:
+                raise ValueError("%s.sample_extended: the shapes are outside the entry's range (%s)" % (name, entry))
+            ws = lib.workspace(nb, dev)
+            args = [lib.ptr(s) for s in state] + [lib.ptr(bank), lib.ptr(lens), B, QL, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(tgt2src), BOS, max_len,
+                                                  ws_ref, cw.ref(), lib.ptr(idx), lib.ptr(e2t), lib.ptr(e2s), CV, N, K, 1.0 / tau, seed, lib.ptr(ws),
+                                                  ws.numel()]
+            args += [lib.ptr(out[k]) for k in ("predictions", "token_logprobs", "scores", "lengths", "attentions")] + [lib.stream()]
+            lib.check(getattr(L, entry)(*args), entry)
+        return out
 
     # ---- eval: beam search ---------------------------------------------------------------------------------------------------------
     @torch.no_grad()

@@ -510,8 +510,35 @@ class CopyRecommender(Recommender):
 
     def predict_samples(self, ex, num_samples, temperature=1.0, top_k=0, seed=None):
         raise NotImplementedError("CopyRecommender.predict_samples: a draw under ACG comes from its collapsed extended distribution (generator mass "
-                                  "+ copy mass per token), not from the generator's softmax alone -- sampling it is the follow-up to DESIGN.md "
-                                  "section 28")
+                                  "+ copy mass per token), not from the generator's softmax alone as in DESIGN.md section 28 -- sampling it is "
+                                  "sample_extended(ex, num_samples, ...) over EXTENDED ids (DESIGN.md section 33)")
+
+    @torch.no_grad()
+    def sample_extended(self, ex, num_samples, temperature=1.0, top_k=0, seed=None):
+        """`num_samples` i.i.d. suggestions per row drawn from ACG's collapsed extended distribution (ACG.sample_extended),
+        by Recommender.predict_samples' contract: {'prediction_ids': LongTensor [B, N, max_query_len] (EXTENDED ids), 'token_logprobs',
+        'scores', 'lengths', 'attentions', 'seed': the seed used}, in sample order; for a full collate batch also `ex_ids`, `targets`,
+        `src_sequences` and `predictions`: per row the list of its N strings, each formed like predict()'s (copied words come from the row's
+        dictionary).  seed=None draws 63 bits from torch's default CPU generator; calling again with the returned 'seed' replays the draw bit
+        for bit.  The copy maps are predict()'s (_copy_fields).  Always eager: the seed is a host argument of the C entry."""
+        N = int(num_samples)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        ex = self._copy_fields(ex)
+        self._poll_ids()
+        self.network.eval()
+        dec = self.network.sample_extended(source_rep=self._dev(self._rows3(ex["source_words"])), source_len=self._dev(self._rows2(ex["source_lens"])),
+                                           max_len=self.args.max_query_len, num_samples=N, temperature=temperature, top_k=top_k, seed=seed,
+                                           src_dict=self.src_dict, tgt_dict=self.tgt_dict, src_map_idx=self._dev(ex["copy_src_map_idx"]),
+                                           ext2tgt=self._dev(ex["copy_ext2tgt"]), ext2src=self._dev(ex["copy_ext2src"]))
+        self._maybe_check_ids()
+        out = {"prediction_ids": dec["predictions"], "token_logprobs": dec["token_logprobs"], "scores": dec["scores"], "lengths": dec["lengths"],
+               "attentions": dec["attentions"], "seed": int(seed)}
+        if all(k in ex for k in ("ids", "source_tokens", "target_tokens", "src_vocab")):
+            per = [self._text(ex, out["prediction_ids"][:, n], out["attentions"][:, n]) for n in range(N)]
+            out.update(per[0])
+            out["predictions"] = [[per[n]["predictions"][b] for n in range(N)] for b in range(len(per[0]["predictions"]))]
+        return out
 
     def _predict_nbest_body(self, ex, beam_size):
         self.network.eval()

@@ -1170,6 +1170,8 @@ int nir_acg_copy_loss_bwd(const float* logits, int64_t ld, const float* switch_l
 #include "neuroir_session_sample.h"
 /* Teacher-forced scoring under ACG's collapsed extended distribution (ctypes: lib.ACG_SCORE_SIGNATURES). */
 #include "neuroir_acg_score.h"
+/* Sampling decode for ACG: draws from that collapsed extended distribution (ctypes: lib.ACG_SAMPLE_SIGNATURES). */
+#include "neuroir_acg_sample.h"
 
 #ifdef __cplusplus
 }
