@@ -857,8 +857,9 @@ struct BeamPlan {
     S2sStepBufs s;                                    // the stepper's buffers, over R = B W decode rows
     BeamTail t;
     float* attn;                                      // [max_len][R][QL] the attention rows of every step
-    float *tval, *csb, *cq, *ccat, *cattn;            // ACG only: the rows' lists; a copy attention of its own
+    float* tval;                                      // ACG only: the rows' lists; a copy attention of its own
     int* tidx;
+    AcgCopyAttn ca;
     size_t bytes;
 };
 // acg: 0 = Seq2seq, 1 = ACG with reuse_copy_attn, 2 = ACG with a copy attention of its own (its buffers lie behind everything Seq2seq's plan holds)
@@ -872,19 +873,14 @@ static BeamPlan beam_plan(void* ws, size_t cap, int64_t B, int QL, int W, int ma
     p.s.tgt = p.t.tgt;
     p.attn = a.take<float>((size_t)max_len * R * QL);
     if (cell == S2S_CELL_GRU) p.s.gru = a.take<float>(gru_step_scratch_floats(R, H));
-    p.tval = p.csb = p.cq = p.ccat = p.cattn = nullptr;
+    p.tval = nullptr;
     p.tidx = nullptr;
     if (acg) {
         if (!fused) p.t.part.ps = a.take<float>((size_t)R);                                // the plain row kernel's sums
         p.tval = a.take<float>((size_t)R * W);
         p.tidx = a.take<int>((size_t)R * W);
     }
-    if (acg == 2) {
-        p.csb = a.take<float>(attn_type == NIR_S2S_ATTN_DOT ? 0 : (size_t)B * QL * H);
-        p.cq = a.take<float>(attn_type == NIR_S2S_ATTN_MLP ? (size_t)R * H : 0);
-        p.ccat = a.take<float>((size_t)R * 2 * H);
-        p.cattn = a.take<float>((size_t)R * QL);
-    }
+    if (acg == 2) p.ca.carve(a, R, B, QL, H, attn_type);
     p.bytes = align_up(a.off, 256);
     return p;
 }
@@ -907,7 +903,6 @@ static int s2s_beam_decode(const float* dec_h, const float* dec_c, const float* 
     NIR_PROPAGATE(s.check(dec_h, dec_c, predictions && scores && lengths && attentions, bos, max_len));
     NIR_REQUIRE(beam_dims_ok(W, w->VT), "beam_seq2seq_decode: beam width outside [1, %d] or above the target vocabulary", NIR_BEAM_MAX_W);
     NIR_REQUIRE(R < 0x7FFFFFFFLL, "beam_seq2seq_decode: too many decode rows");
-    const bool own_copy_attn = acg && acg->cw && !acg->cw->reuse_copy_attn;
     if (acg) {
         NIR_REQUIRE(acg_weights_ok(w, acg), "acg_beam_decode: copy weights incomplete for the attention type");
         NIR_REQUIRE(acg->src_map_idx && acg->ext2tgt && acg->ext2src, "acg_beam_decode: null index tensor");
@@ -916,7 +911,7 @@ static int s2s_beam_decode(const float* dec_h, const float* dec_c, const float* 
     const int H = w->H;
     const bool fused = s.fused, step16 = s.step16, gru = cell == S2S_CELL_GRU;
     const BeamPlan p = beam_plan(workspace, workspace_bytes, B, QL, W, max_len, H, w->VT, w->attn_type, fused, cell, step16, backptr,
-                                 acg ? (own_copy_attn ? 2 : 1) : 0);
+                                 acg ? (acg->cw->reuse_copy_attn ? 1 : 2) : 0);
     if (!workspace || p.bytes > workspace_bytes) {
         set_error("beam_seq2seq_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
         return NIR_ERR_WORKSPACE;
@@ -928,28 +923,17 @@ static int s2s_beam_decode(const float* dec_h, const float* dec_c, const float* 
     NIR_PROPAGATE(t.begin(st));
     const float* hp = dec_h;
     const float* cp = dec_c;
-    const bool mlp = w->attn_type == NIR_S2S_ATTN_MLP;
-    const float* csb = memory_bank;                       // the score bank of ACG's own copy attention, over the B source rows (s2s_decode)
-    if (own_copy_attn && w->attn_type != NIR_S2S_ATTN_DOT) {
-        NIR_PROPAGATE(launch_linear(memory_bank, H, nullptr, nullptr, 0, 0, 0, mlp ? acg->cw->attn_ctx_w : acg->cw->attn_in_wt, H, nullptr, nullptr, p.csb, H,
-                                    B * QL, H, H, NIR_ACT_NONE, st));
-        csb = p.csb;
-    }
+    if (acg) NIR_PROPAGATE(p.ca.prepare(acg->cw, memory_bank, B, QL, H, w->attn_type, st));
     for (int step = 0; step < max_len; ++step) {
         NIR_PROPAGATE(s.step(hp, cp, p.s.h[1], p.s.c[1], p.s.h16[0], p.s.h16[1], p.attn + (int64_t)step * R * QL, QL));
         if (acg) {
             // ACG's tail: (a second attention whose query is the attentional output,) the W best of every row's collapsed extended distribution,
             // the selection over the source row's W W candidates
             const float* ca = p.attn + (int64_t)step * R * QL;
-            if (own_copy_attn) {
-                if (mlp)
-                    NIR_PROPAGATE(launch_linear(p.s.ah, H, nullptr, nullptr, 0, 0, 0, acg->cw->attn_query_w, H, acg->cw->attn_query_b, nullptr, p.cq, H, R, H, H,
-                                                NIR_ACT_NONE, st));
-                NIR_PROPAGATE(launch_attend(mlp ? p.cq : p.s.ah, p.s.ah, memory_bank, csb, acg->cw->attn_v, source_len, R, QL, H, mlp, p.ccat, p.cattn, QL, st, B));
-                ca = p.cattn;
-            }
+            int64_t ca_stride = QL;
+            NIR_PROPAGATE(p.ca.step(acg->cw, p.s.ah, R, B, memory_bank, source_len, QL, H, w->attn_type, &ca, &ca_stride, st));
             NIR_PROPAGATE(launch_acg_beam_gen_select(p.s.ah, R, B, H, w->gen_w, w->gen_b, fused ? w->gen_frag : nullptr, w->VT, W, p.s.logits, t.part,
-                                                     acg->cw->copy_w, acg->cw->copy_b, ca, QL, source_len, QL, acg->src_map_idx, acg->ext2tgt, acg->CV, t.fin,
+                                                     acg->cw->copy_w, acg->cw->copy_b, ca, ca_stride, source_len, QL, acg->src_map_idx, acg->ext2tgt, acg->CV, t.fin,
                                                      p.tval, p.tidx, st));
             NIR_PROPAGATE(launch_acg_beam_select(p.tval, p.tidx, nullptr, B, W, w->VT, acg->CV, tgt2src, acg->ext2src, V, t.cum, t.fin, t.bp + (int64_t)step * R,
                                                  t.tok + (int64_t)step * R, t.tgt, st));
@@ -987,12 +971,10 @@ int launch_hq_beam_begin(const float* hs, const float* cs, int64_t B, int64_t S,
     return 0;
 }
 // ---- CARS ----------------------------------------------------------------------------------------------------------------------------------
-// The step of nir_cars_decode_greedy restated over R rows (its keyed arg-max path ties the greedy loop's launches to its own tail; the greedy
-// entry stays as it is): prepare once -- the banks mem / memq over the source rows, the session projection over the R rows through the
-// repeated rowmap -- then per step lstm step, (linear_in,) dec_attend, linear_out + tanh, pred1 + session term.
+// CarsRowsStep (beam_steps.hpp) over R = Bd W rows, every step from state slot 0 (the reordered one) into slot 1, with the tail above on p1.
 struct CarsBeamPlan {
-    float *mem, *memq, *sess, *h[2], *c[2], *h16[2], *qv, *cat, *ah, *p1, *logits;        // (logits: the plain generator's)
-    int64_t* rowmap;
+    CarsRowsStep s;
+    float* logits;                                    // the plain generator's
     BeamTail t;
     size_t bytes;
 };
@@ -1001,20 +983,9 @@ static CarsBeamPlan cars_beam_plan(void* ws, size_t cap, int64_t rows_src, int64
     Workspace a(ws, cap);
     CarsBeamPlan p;
     const int64_t R = Bd * W;
-    const int HD = w->HD, P = w->P;
-    const bool foldq = w->attn_q_w != nullptr, step16 = cars_beam_step16(w);
-    p.mem = a.take<float>((size_t)rows_src * QL * HD);
-    p.memq = a.take<float>(foldq ? (size_t)rows_src * QL * HD : 0);
-    p.sess = a.take<float>(w->KS > 0 ? (size_t)R * P : 0);
-    for (int k = 0; k < 2; ++k) { p.h[k] = a.take<float>((size_t)R * HD); p.c[k] = a.take<float>((size_t)R * HD); }
-    for (int k = 0; k < 2; ++k) p.h16[k] = a.take<float>(step16 ? (size_t)R * HD : 0);
-    p.qv = a.take<float>(foldq ? 0 : (size_t)R * HD);
-    p.cat = a.take<float>((size_t)R * 2 * HD);
-    p.ah = a.take<float>((size_t)R * HD);
-    p.p1 = a.take<float>((size_t)R * P);
-    p.rowmap = a.take<int64_t>((size_t)R);
+    p.s.carve(a, rows_src, R, QL, w);
     p.logits = a.take<float>(fused ? 0 : (size_t)R * w->VT);
-    p.t.carve(a, Bd, W, max_len, fused ? beam_nparts(R, P, w->VT) : 1, fused, backptr);
+    p.t.carve(a, Bd, W, max_len, fused ? beam_nparts(R, w->P, w->VT) : 1, fused, backptr);
     p.bytes = align_up(a.off, 256);
     return p;
 }
@@ -1043,38 +1014,23 @@ extern "C" int nir_beam_cars_decode(const float* dec_h, const float* dec_c, cons
     NIR_REQUIRE(Bd * NIR_BEAM_MAX_W < 0x7FFFFFFFLL && w->VT < 0x7FFFFFF0LL, "beam_cars_decode: too many decode rows or target tokens");
     const int HD = w->HD, P = w->P;
     const int64_t R = Bd * W, VT = w->VT;
-    const bool fused = s2s_gen_fused(gen_frag, P, VT), foldq = w->attn_q_w != nullptr, step16 = cars_beam_step16(w);
-    const CarsBeamPlan p = cars_beam_plan(workspace, workspace_bytes, rows_src, Bd, QL, W, max_len, w, fused, backptr);
+    const bool fused = s2s_gen_fused(gen_frag, P, VT);
+    CarsBeamPlan p = cars_beam_plan(workspace, workspace_bytes, rows_src, Bd, QL, W, max_len, w, fused, backptr);
     const BeamTail& t = p.t;
     if (!workspace || p.bytes > workspace_bytes) {
         set_error("beam_cars_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
         return NIR_ERR_WORKSPACE;
     }
     if (Bd == 0) return 0;
-    // once per decode, as the greedy entry: the banks over every source row, the session projection (gathered through the repeated rowmap)
-    NIR_PROPAGATE(launch_linear(encoded_source, w->DQ, nullptr, nullptr, 0, 0, 0, w->dec_attn_w, w->DQ, nullptr, nullptr, p.mem, HD, rows_src * QL, HD, w->DQ,
-                                NIR_ACT_NONE, st));
-    if (foldq)
-        NIR_PROPAGATE(launch_linear(encoded_source, w->DQ, nullptr, nullptr, 0, 0, 0, w->attn_q_w, w->DQ, nullptr, nullptr, p.memq, HD, rows_src * QL, HD, w->DQ,
-                                    NIR_ACT_NONE, st));
-    NIR_PROPAGATE(launch_beam_repeat(dec_h, dec_c, Bd, R, HD, p.h[0], p.c[0], step16 ? p.h16[0] : nullptr, rowmap, p.rowmap, st));
-    NIR_PROPAGATE(launch_fill_i64(t.tgt, bos, R, st));
-    NIR_PROPAGATE(t.begin(st));
-    if (w->KS > 0)
-        NIR_PROPAGATE(launch_linear(nullptr, 0, p.rowmap, session_cat, w->KS, 1, 1, w->sess_w, w->KS, nullptr, nullptr, p.sess, P, R, P, w->KS, NIR_ACT_NONE, st));
-    const LstmStepArgs a = beam_lstm_step_args(table, t.tgt, E, w->rnn_wih, w->rnn_whh, w->rnn_bih, w->rnn_bhh, step16, w->rnn_gate_fold, w->rnn_whh_frag, R, HD,
-                                               p.h, p.c, p.h16);
-    float* hn = p.h[1];
+    NIR_PROPAGATE(p.s.prepare(dec_h, dec_c, encoded_source, source_len, rows_src, rowmap, Bd, session_cat, table, t.tgt, E, 0, st, [&] {
+        const int rc = launch_fill_i64(t.tgt, bos, R, st);
+        return rc != 0 ? rc : t.begin(st);
+    }));
     for (int step = 0; step < max_len; ++step) {
-        NIR_PROPAGATE(launch_lstm_step(a, 1, st));
-        if (!foldq) NIR_PROPAGATE(launch_linear(hn, HD, nullptr, nullptr, 0, 0, 0, w->attn_in_w, HD, nullptr, nullptr, p.qv, HD, R, HD, HD, NIR_ACT_NONE, st));
-        NIR_PROPAGATE(launch_dec_attend(foldq ? hn : p.qv, hn, p.mem, foldq ? p.memq : p.mem, p.rowmap, source_len, R, QL, HD, p.cat, st));
-        NIR_PROPAGATE(launch_linear(p.cat, 2 * HD, nullptr, nullptr, 0, 0, 0, w->attn_out_w, 2 * HD, nullptr, nullptr, p.ah, HD, R, HD, 2 * HD, NIR_ACT_TANH, st));
-        NIR_PROPAGATE(launch_linear_ex(p.ah, HD, nullptr, nullptr, 0, 0, 0, w->pred1_w, HD, nullptr, nullptr, p.p1, P, R, P, HD, NIR_ACT_NONE,
-                                       w->KS > 0 ? p.sess : nullptr, P, st));
-        NIR_PROPAGATE(t.gen(fused, p.p1, P, w->pred2_w, nullptr, gen_frag, VT, p.logits, st));
+        NIR_PROPAGATE(p.s.step(0, 1));
+        NIR_PROPAGATE(t.gen(fused, p.s.p1, P, w->pred2_w, nullptr, gen_frag, VT, p.logits, st));
         NIR_PROPAGATE(t.select(step, VT, tgt2src, V, st));
-        NIR_PROPAGATE(t.reorder(step, HD, p.h, p.c, step16 ? p.h16 : nullptr, st));
+        NIR_PROPAGATE(t.reorder(step, HD, p.s.h, p.s.c, p.s.step16 ? p.s.h16 : nullptr, st));
     }
     return t.end(predictions, scores, lengths, st);
 }

@@ -243,6 +243,40 @@ bool s2s_step16(const nir_seq2seq_decoder_weights* w);
 int launch_attend(const float* q, const float* h, const float* mem, const float* sb, const float* v, const int64_t* lens, int64_t B, int QL, int H,
                   int mlp, float* cat, float* attn, int64_t attn_stride, hipStream_t st, int64_t nsrc = 0);
 
+// ACG's copy attention, once for the greedy, beam and sampling decodes.  With reuse_copy_attn it is the stepper's attention row as it stands (own
+// stays false: nothing is carved or launched).  Otherwise a second attention in the forms of the stepper's, whose query is the attentional output
+// ah [rows, H] (its own cat and linear_out take no part in the value): the score bank over the nsrc source rows once per decode, per step the
+// (mlp) query GEMM and launch_attend into cattn [rows, QL].
+struct AcgCopyAttn {
+    float *csb = nullptr, *cq = nullptr, *ccat = nullptr, *cattn = nullptr;
+    bool own = false;
+    // own_copy_attn: the four buffers, in this order
+    void carve(Workspace& a, int64_t rows, int64_t nsrc, int QL, int H, int attn_type) {
+        own = true;
+        csb = a.take<float>(attn_type == NIR_S2S_ATTN_DOT ? 0 : (size_t)nsrc * QL * H);
+        cq = a.take<float>(attn_type == NIR_S2S_ATTN_MLP ? (size_t)rows * H : 0);
+        ccat = a.take<float>((size_t)rows * 2 * H);
+        cattn = a.take<float>((size_t)rows * QL);
+    }
+    int prepare(const nir_acg_copy_weights* cw, const float* memory_bank, int64_t nsrc, int QL, int H, int attn_type, hipStream_t st) const {
+        if (!own || attn_type == NIR_S2S_ATTN_DOT) return 0;
+        return launch_linear(memory_bank, H, nullptr, nullptr, 0, 0, 0, attn_type == NIR_S2S_ATTN_MLP ? cw->attn_ctx_w : cw->attn_in_wt, H, nullptr, nullptr, csb, H,
+                             nsrc * QL, H, H, NIR_ACT_NONE, st);
+    }
+    // *ca / *ca_stride: in, the stepper's attention rows of this step; out, the copy attention's
+    int step(const nir_acg_copy_weights* cw, const float* ah, int64_t rows, int64_t nsrc, const float* memory_bank, const int64_t* source_len, int QL, int H,
+             int attn_type, const float** ca, int64_t* ca_stride, hipStream_t st) const {
+        if (!own) return 0;
+        const bool mlp = attn_type == NIR_S2S_ATTN_MLP;
+        if (mlp) NIR_PROPAGATE(launch_linear(ah, H, nullptr, nullptr, 0, 0, 0, cw->attn_query_w, H, cw->attn_query_b, nullptr, cq, H, rows, H, H, NIR_ACT_NONE, st));
+        NIR_PROPAGATE(launch_attend(mlp ? cq : ah, ah, memory_bank, attn_type == NIR_S2S_ATTN_DOT ? memory_bank : csb, cw->attn_v, source_len, rows, QL, H, mlp,
+                                    ccat, cattn, QL, st, nsrc));
+        *ca = cattn;
+        *ca_stride = QL;
+        return 0;
+    }
+};
+
 // ---- the attention-decoder step, once: cell -> (mlp: query GEMM) -> attention -> linear_out -----------------------------------------------------
 // The greedy decodes of Seq2seq and ACG (s2s_decode) and the beam search (csrc/beam.hip) are this stepper with a tail each behind linear_out:
 // arg-max, the copy generator's select, or top-k + select + reorder.  `rows` decode rows over `nsrc` source rows (greedy: B and B; beam: B W and B,

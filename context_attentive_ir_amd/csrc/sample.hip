@@ -11,8 +11,12 @@
 // sample_gen_kernel is the fifth consumer of the generator tile walk, next to arg-max (s2s_gen.hpp), its STATS form, top-W (csrc/beam.hip) and
 // the target logit (csrc/score.hip), and restates their staging, chunk clamp and fragment walk as they do: a change to one of those has to be
 // made here too (the shared body was measured slower).
-// The types, argument checks and launchers other units need stand in sample_tail.hpp (csrc/session_sample.hip: the same tail behind the steps
-// of HredQS and the session models); the kernels live here.
+// The types, argument checks, launchers and the host-side tail other units need stand in sample_tail.hpp (SampleTail: carve, begin, draw, end --
+// csrc/session_sample.hip runs the same tail behind the steps of HredQS and the session models); the kernels live here.  One decode loop,
+// s2s_sample_decode, serves Seq2seq (acg == NULL: the tail's own draw) and ACG (the copy generator's draw), as s2s_decode and
+// s2s_beam_decode do; SamplePlan is the only plan of this unit.  The fused walks share one launcher (launch_sample_walk) and one "take the
+// partials, walk, finish" helper (sample_walk_finish); the merge loop at the head of acg_sample_row_kernel stays a copy of sample_finish_kernel's:
+// factored into one device function it cost sample_finish_kernel two SGPRs.
 // Everything is enqueued on the caller's stream: no host synchronisation, no allocation, no atomics, every reduction in a fixed order.
 #include <cmath>
 #include "s2s_gen.hpp"
@@ -564,35 +568,66 @@ __global__ __launch_bounds__(64) void sample_end_kernel(const float* __restrict_
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------------------------------------
+// partials per row of the fused walk, the two policies: fp32 rows -- one per wave of every vocabulary range of s2s_nvr, a row block's ranges
+// adjacent; the split state -- of hq_nvr's grid (one workgroup per CU, XCD-aware)
 static int sample_nparts(int64_t rows, int K, int64_t VT) { return rows > 0 ? 4 * s2s_nvr(rows, K, (VT + 15) / 16) : 0; }
+static int sample_split_nparts(int64_t rows, int K, int64_t VT) {
+    return rows > 0 ? 4 * hq_nvr((rows + 16 * gen_nbt(K) - 1) / (16 * gen_nbt(K)), (VT + 15) / 16) : 0;
+}
 size_t sample_gen_bytes(int64_t rows, int K, int64_t VT, bool fused) {
     if (!fused) return (size_t)rows * VT * sizeof(float) + 256;
     return (size_t)sample_nparts(rows, K, VT) * rows * 5 * sizeof(float) + 5 * 256;
 }
+size_t sample_gen_split_bytes(int64_t rows, int K, int64_t VT) { return (size_t)sample_split_nparts(rows, K, VT) * rows * 5 * sizeof(float) + 5 * 256; }
 
-// the fused walk on fp32 rows: sample_nparts partials a row into pv .. ps.  PAD: the copy generator's instantiations, under a name of their own
-template <bool PAD>
-static int launch_sample_gen_partials(const char* name, const float* x, int64_t rows, int K, const float* gen_b, const void* gen_frag, int64_t VT,
-                                      const SampleKey& key, float inv_tau, float* pv, int* pi, float* py, float* pm, float* ps, hipStream_t st) {
+static SamplePartials sample_take_partials(Workspace& a, size_t n) {
+    SamplePartials p;
+    p.pv = a.take<float>(n);
+    p.pi = a.take<int>(n);
+    p.py = a.take<float>(n);
+    p.pm = a.take<float>(n);
+    p.ps = a.take<float>(n);
+    return p;
+}
+// the fused walk over nvr vocabulary ranges x the row blocks: 4 nvr partials a row into p, under `name` (PAD: the copy generator's instantiations)
+template <class ROWSRC, bool PAD>
+static int launch_sample_walk(const char* name, const typename ROWSRC::elem* x, int64_t rows, int K, int nvr, const float* gen_b, const void* gen_frag,
+                              int64_t VT, const SampleKey& key, float inv_tau, const SamplePartials& p, hipStream_t st) {
     const int64_t ntiles = (VT + 15) / 16;
-    const int nbt = gen_nbt(K), nvr = s2s_nvr(rows, K, ntiles);
+    const int nbt = gen_nbt(K);
     const int64_t rb = (rows + 16 * nbt - 1) / (16 * nbt);
     {
         ProfScope ps_(prof_shape_name(name, (long long)rows, (long long)VT, K), st);
         const dim3 grid((unsigned)(nvr * rb));
         if (nbt == 4) {
-            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<BeamRowsF32, 4, PAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(512));
+            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<ROWSRC, 4, PAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(512));
             (void)raised;
-            hipLaunchKernelGGL((sample_gen_kernel<BeamRowsF32, 4, PAD>), grid, dim3(256), gen_lds(K), st, x, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key,
-                               inv_tau, pv, pi, py, pm, ps);
+            hipLaunchKernelGGL((sample_gen_kernel<ROWSRC, 4, PAD>), grid, dim3(256), gen_lds(K), st, x, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key,
+                               inv_tau, p.pv, p.pi, p.py, p.pm, p.ps);
         } else {
-            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<BeamRowsF32, 2, PAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(1024));
+            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<ROWSRC, 2, PAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(1024));
             (void)raised;
-            hipLaunchKernelGGL((sample_gen_kernel<BeamRowsF32, 2, PAD>), grid, dim3(256), gen_lds(K), st, x, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key,
-                               inv_tau, pv, pi, py, pm, ps);
+            hipLaunchKernelGGL((sample_gen_kernel<ROWSRC, 2, PAD>), grid, dim3(256), gen_lds(K), st, x, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key,
+                               inv_tau, p.pv, p.pi, p.py, p.pm, p.ps);
         }
     }
     NIR_CHECK_LAUNCH(name);
+    return 0;
+}
+// take the five partial arrays (nparts a row), walk, finish(p): sample_finish_kernel, or the copy generator's row kernel
+template <class ROWSRC, bool PAD, class Finish>
+static int sample_walk_finish(const char* name, Workspace& a, const typename ROWSRC::elem* x, int64_t rows, int K, int nparts, const float* gen_b,
+                              const void* gen_frag, int64_t VT, const SampleKey& key, float inv_tau, hipStream_t st, Finish finish) {
+    const SamplePartials p = sample_take_partials(a, (size_t)nparts * rows);
+    NIR_PROPAGATE((launch_sample_walk<ROWSRC, PAD>(name, x, rows, K, nparts / 4, gen_b, gen_frag, VT, key, inv_tau, p, st)));
+    return finish(p);
+}
+static int launch_sample_finish(const SamplePartials& p, int nparts, int64_t rows, const SampleOut& o, hipStream_t st) {
+    {
+        ProfScope ps_("sample_finish_kernel", st);
+        hipLaunchKernelGGL(sample_finish_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, p.pv, p.pi, p.py, p.pm, p.ps, nparts, rows, o);
+    }
+    NIR_CHECK_LAUNCH("sample_finish_kernel");
     return 0;
 }
 
@@ -611,61 +646,16 @@ int launch_sample_gen(bool fused, const float* x, int64_t rows, int K, const flo
         return 0;
     }
     const int nparts = sample_nparts(rows, K, VT);
-    const size_t n = (size_t)nparts * rows;
-    float* pv = a.take<float>(n);
-    int* pi = a.take<int>(n);
-    float* py = a.take<float>(n);
-    float* pm = a.take<float>(n);
-    float* ps = a.take<float>(n);
-    NIR_PROPAGATE(launch_sample_gen_partials<false>("sample_gen_kernel", x, rows, K, gen_b, gen_frag, VT, key, inv_tau, pv, pi, py, pm, ps, st));
-    {
-        ProfScope ps_("sample_finish_kernel", st);
-        hipLaunchKernelGGL(sample_finish_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, pv, pi, py, pm, ps, nparts, rows, o);
-    }
-    NIR_CHECK_LAUNCH("sample_finish_kernel");
-    return 0;
+    return sample_walk_finish<BeamRowsF32, false>("sample_gen_kernel", a, x, rows, K, nparts, gen_b, gen_frag, VT, key, inv_tau, st,
+                                                  [&](const SamplePartials& p) { return launch_sample_finish(p, nparts, rows, o, st); });
 }
-// partials per row of the split-state form: one per wave of every vocabulary range of hq_nvr's grid (one workgroup per CU, XCD-aware)
-static int sample_split_nparts(int64_t rows, int K, int64_t VT) {
-    return rows > 0 ? 4 * hq_nvr((rows + 16 * gen_nbt(K) - 1) / (16 * gen_nbt(K)), (VT + 15) / 16) : 0;
-}
-size_t sample_gen_split_bytes(int64_t rows, int K, int64_t VT) { return (size_t)sample_split_nparts(rows, K, VT) * rows * 5 * sizeof(float) + 5 * 256; }
 // one sampling step over the whole vocabulary on the split state h16 [rows][K/8][2][8]: sample_gen_kernel on BeamRowsSplit + the same finish
 int launch_sample_gen_split(const _Float16* h16, int64_t rows, int K, const float* gen_b, const void* gen_frag, int64_t VT, const SampleKey& key,
                             float inv_tau, void* ws, size_t ws_bytes, const SampleOut& o, hipStream_t st) {
     Workspace a(ws, ws_bytes);
-    const int64_t ntiles = (VT + 15) / 16;
-    const int nbt = gen_nbt(K);
-    const int64_t nrb = (rows + 16 * nbt - 1) / (16 * nbt);
-    const int nvr = hq_nvr(nrb, ntiles), nparts = 4 * nvr;
-    const size_t n = (size_t)nparts * rows;
-    float* pv = a.take<float>(n);
-    int* pi = a.take<int>(n);
-    float* py = a.take<float>(n);
-    float* pm = a.take<float>(n);
-    float* ps = a.take<float>(n);
-    {
-        ProfScope ps_(prof_shape_name("hq_sample_gen_kernel", (long long)rows, (long long)VT, K), st);
-        const dim3 grid((unsigned)(nvr * nrb));
-        if (nbt == 4) {
-            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<BeamRowsSplit, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(512));
-            (void)raised;
-            hipLaunchKernelGGL((sample_gen_kernel<BeamRowsSplit, 4>), grid, dim3(256), gen_lds(K), st, h16, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key,
-                               inv_tau, pv, pi, py, pm, ps);
-        } else {
-            static const hipError_t raised = hipFuncSetAttribute((const void*)sample_gen_kernel<BeamRowsSplit, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gen_lds(1024));
-            (void)raised;
-            hipLaunchKernelGGL((sample_gen_kernel<BeamRowsSplit, 2>), grid, dim3(256), gen_lds(K), st, h16, (const _Float16*)gen_frag, gen_b, VT, ntiles, rows, K, nvr, key,
-                               inv_tau, pv, pi, py, pm, ps);
-        }
-    }
-    NIR_CHECK_LAUNCH("hq_sample_gen_kernel");
-    {
-        ProfScope ps_("sample_finish_kernel", st);
-        hipLaunchKernelGGL(sample_finish_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, pv, pi, py, pm, ps, nparts, rows, o);
-    }
-    NIR_CHECK_LAUNCH("sample_finish_kernel");
-    return 0;
+    const int nparts = sample_split_nparts(rows, K, VT);
+    return sample_walk_finish<BeamRowsSplit, false>("hq_sample_gen_kernel", a, h16, rows, K, nparts, gen_b, gen_frag, VT, key, inv_tau, st,
+                                                    [&](const SamplePartials& p) { return launch_sample_finish(p, nparts, rows, o, st); });
 }
 int launch_sample_topk_select(const float* top_val, const int* top_idx, const float* lse, int64_t rows, int W, const SampleKey& key, float inv_tau,
                                      const SampleOut& o, hipStream_t st) {
@@ -692,91 +682,7 @@ int launch_sample_end(const float* cum, const int64_t* len, const float* attn_ws
     return 0;
 }
 
-// ---- the decode --------------------------------------------------------------------------------------------------------------------------------------
-struct SamplePlan {
-    S2sStepBufs s;                                    // the stepper's buffers, over R = B N decode rows
-    void* gen;                                        // the generator's workspace: sample_gen_bytes, or nir_beam_gen_topk's
-    size_t gen_bytes;
-    float *tval, *lse;                                // top_k > 0: the rows' lists [R, top_k] and lse [R]
-    int* tidx;
-    float* cum;                                       // [R] the state of the freeze rule
-    int* fin;
-    int64_t* len;
-    float* attn;                                      // [max_len][R][QL] the attention rows of every step
-    size_t bytes;
-};
-static SamplePlan sample_plan(void* ws, size_t cap, int64_t B, int QL, int N, int top_k, int max_len, int H, int64_t VT, int attn_type, bool fused, int cell,
-                              bool step16) {
-    Workspace a(ws, cap);
-    SamplePlan p;
-    const int64_t R = B * N;
-    p.s = s2s_step_bufs(a, R, B, QL, H, VT, attn_type, true, cell, step16);                 // (no logits of the stepper's: the generator's workspace below)
-    p.s.tgt = a.take<int64_t>((size_t)R);
-    if (cell == S2S_CELL_GRU) p.s.gru = a.take<float>(gru_step_scratch_floats(R, H));
-    p.gen_bytes = R == 0 ? 0 : top_k > 0 ? nir_beam_gen_topk_workspace_bytes(R, H, VT, top_k, fused) : sample_gen_bytes(R, H, VT, fused);
-    p.gen = a.take<char>(p.gen_bytes);
-    p.tval = a.take<float>((size_t)R * top_k);
-    p.tidx = a.take<int>((size_t)R * top_k);
-    p.lse = a.take<float>(top_k > 0 ? (size_t)R : 0);
-    p.cum = a.take<float>((size_t)R);
-    p.fin = a.take<int>((size_t)R);
-    p.len = a.take<int64_t>((size_t)R);
-    p.attn = a.take<float>((size_t)max_len * R * QL);
-    p.bytes = align_up(a.off, 256);
-    return p;
-}
-static size_t sample_decode_workspace_bytes(int64_t B, int QL, int N, int top_k, int max_len, const nir_seq2seq_decoder_weights* w, int cell) {
-    if (!s2s_weights_ok(w) || B < 0 || QL <= 0 || max_len <= 0 || !sample_dims_ok(N, top_k, w->VT) || B * N >= 0x7FFFFFFFLL) return 0;
-    return sample_plan(nullptr, 0, B, QL, N, top_k, max_len, w->H, w->VT, w->attn_type, s2s_fused(w), cell, s2s_step16(w)).bytes;
-}
-
-// The stepper of s2s_gen.hpp over N decode rows per source row, with the sampling tail behind the attentional output.  The state ping-pongs as
-// in the greedy decode: step s writes slot s & 1 and reads the other.
-static int s2s_sample_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, int N, int top_k,
-                             float inv_tau, uint64_t seed, const float* table, int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len,
-                             const nir_seq2seq_decoder_weights* w, void* workspace, size_t workspace_bytes, int64_t* predictions, float* token_logprobs,
-                             float* scores, int64_t* lengths, float* attentions, int cell, hipStream_t st) {
-    NIR_REQUIRE(N >= 1 && B >= 0 && B * (int64_t)N < 0x7FFFFFFFLL, "sample_seq2seq_decode: N < 1 or too many decode rows");
-    const int64_t R = B * N;
-    S2sStepper s{"sample_seq2seq_decode", w, cell, table, memory_bank, source_len, V, R, B, E, QL, st};
-    NIR_PROPAGATE(s.check(dec_h, dec_c, predictions && token_logprobs && scores && lengths && attentions, bos, max_len));
-    NIR_REQUIRE(sample_dims_ok(N, top_k, w->VT), "sample_seq2seq_decode: top_k outside 0 .. %d or above the target vocabulary", NIR_BEAM_MAX_W);
-    NIR_REQUIRE(sample_tau_ok(inv_tau), "sample_seq2seq_decode: inv_temperature must be finite and > 0");
-    const int H = w->H;
-    const bool fused = s.fused;
-    const SamplePlan p = sample_plan(workspace, workspace_bytes, B, QL, N, top_k, max_len, H, w->VT, w->attn_type, fused, cell, s.step16);
-    if (B == 0) return 0;                                 // nothing to enqueue: no workspace is needed either
-    if (!workspace || p.bytes > workspace_bytes) {
-        set_error("sample_seq2seq_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
-        return NIR_ERR_WORKSPACE;
-    }
-    s.b = p.s;
-    NIR_PROPAGATE(s.prepare(dec_h, bos, p.s.h16[1]));
-    NIR_PROPAGATE(launch_sample_init(p.cum, p.fin, p.len, R, max_len, st));
-    SampleOut o{nullptr, nullptr, nullptr, p.fin, p.cum, p.len, predictions, token_logprobs, p.s.tgt, tgt2src, V, w->VT, B, N, 0, max_len};
-    const float* hp = dec_h;
-    const float* cp = dec_c;
-    for (int step = 0; step < max_len; ++step) {
-        float* hn = p.s.h[step & 1];
-        float* cn = p.s.c[step & 1];
-        NIR_PROPAGATE(s.step(hp, cp, hn, cn, p.s.h16[(step + 1) & 1], p.s.h16[step & 1], p.attn + (int64_t)step * R * QL, QL));
-        const SampleKey key = sample_key(seed, step, B);
-        o.step = step;
-        if (top_k > 0) {
-            const int rc = nir_beam_gen_topk(p.s.ah, R, H, w->gen_w, w->gen_b, fused ? w->gen_frag : nullptr, w->VT, top_k, p.gen, p.gen_bytes, p.tval, p.tidx,
-                                             p.lse, (nir_stream_t)st);
-            if (rc != 0) return rc;
-            NIR_PROPAGATE(launch_sample_topk_select(p.tval, p.tidx, p.lse, R, top_k, key, inv_tau, o, st));
-        } else {
-            NIR_PROPAGATE(launch_sample_gen(fused, p.s.ah, R, H, w->gen_w, w->gen_b, w->gen_frag, w->VT, key, inv_tau, p.gen, p.gen_bytes, o, st));
-        }
-        hp = hn;
-        cp = cn;
-    }
-    return launch_sample_end(p.cum, p.len, p.attn, B, N, max_len, QL, scores, lengths, attentions, st);
-}
-
-// ---- the copy generator's sampler: the per-row launches and the decode (include/neuroir_acg_sample.h) -----------------------------------------------------
+// ---- the copy generator's sampler: the per-row launches (include/neuroir_acg_sample.h) ------------------------------------------------------------------
 static bool acg_sample_dims_ok(int QL, int CV, int64_t VT) { return acg_dims_ok(QL, CV) && VT > 0 && VT + CV < 0x7FFFFFF0LL; }
 // whole-distribution form: the partials (fused: sample_nparts a row; plain: the GEMM's logits in front of one a row)
 static size_t acg_sample_gen_bytes(int64_t rows, int K, int64_t VT, bool fused) {
@@ -801,32 +707,27 @@ static int launch_acg_sample_gen_select(bool fused, const float* o, int64_t R, i
                                         const SampleKey& key, float inv_tau, const AcgSampleIn& in, void* ws, size_t ws_bytes, float* stat_max,
                                         float* stat_lse, const SampleOut& out, hipStream_t st) {
     Workspace a(ws, ws_bytes);
-    int nparts = 1;
     float* logits = a.take<float>(fused ? 0 : (size_t)R * VT);
-    if (fused) nparts = sample_nparts(R, K, VT);
-    const size_t n = (size_t)nparts * R;
-    float* pv = a.take<float>(n);
-    int* pi = a.take<int>(n);
-    float* py = a.take<float>(n);
-    float* pm = a.take<float>(n);
-    float* ps = a.take<float>(n);
-    if (fused) {
-        NIR_PROPAGATE(launch_sample_gen_partials<true>("acg_sample_gen_kernel", o, R, K, gen_b, gen_frag, VT, key, inv_tau, pv, pi, py, pm, ps, st));
-    } else {
-        NIR_PROPAGATE(launch_linear(o, K, nullptr, nullptr, 0, 0, 0, gen_w, K, gen_b, nullptr, logits, VT, R, (int)VT, K, NIR_ACT_NONE, st));
+    const int nparts = fused ? sample_nparts(R, K, VT) : 1;
+    auto row_kernel = [&](const SamplePartials& p) {
         {
-            ProfScope ps_("acg_sample_plain_row_kernel", st);
-            hipLaunchKernelGGL(sample_row_kernel<true>, dim3((unsigned)R), dim3(256), 0, st, logits, VT, key, inv_tau, SamplePartials{pv, pi, py, pm, ps});
+            ProfScope ps_("acg_sample_row_kernel", st);
+            hipLaunchKernelGGL(acg_sample_row_kernel, dim3((unsigned)R), dim3(64), (size_t)2 * in.CV * sizeof(float), st, o, K, gen_w, gen_b, VT, p.pv, p.pi, p.py, p.pm,
+                               p.ps, nparts, R, key, inv_tau, in.copy_w, in.copy_b, in.attn, in.attn_stride, in.lens, in.QL, in.map, in.e2t, in.CV, stat_max, stat_lse,
+                               fused ? nullptr : logits, out);
         }
-        NIR_CHECK_LAUNCH("acg_sample_plain_row_kernel");
-    }
+        NIR_CHECK_LAUNCH("acg_sample_row_kernel");
+        return 0;
+    };
+    if (fused) return sample_walk_finish<BeamRowsF32, true>("acg_sample_gen_kernel", a, o, R, K, nparts, gen_b, gen_frag, VT, key, inv_tau, st, row_kernel);
+    const SamplePartials p = sample_take_partials(a, (size_t)R);
+    NIR_PROPAGATE(launch_linear(o, K, nullptr, nullptr, 0, 0, 0, gen_w, K, gen_b, nullptr, logits, VT, R, (int)VT, K, NIR_ACT_NONE, st));
     {
-        ProfScope ps_("acg_sample_row_kernel", st);
-        hipLaunchKernelGGL(acg_sample_row_kernel, dim3((unsigned)R), dim3(64), (size_t)2 * in.CV * sizeof(float), st, o, K, gen_w, gen_b, VT, pv, pi, py, pm, ps,
-                           nparts, R, key, inv_tau, in.copy_w, in.copy_b, in.attn, in.attn_stride, in.lens, in.QL, in.map, in.e2t, in.CV, stat_max, stat_lse, fused ? nullptr : logits, out);
+        ProfScope ps_("acg_sample_plain_row_kernel", st);
+        hipLaunchKernelGGL(sample_row_kernel<true>, dim3((unsigned)R), dim3(256), 0, st, logits, VT, key, inv_tau, p);
     }
-    NIR_CHECK_LAUNCH("acg_sample_row_kernel");
-    return 0;
+    NIR_CHECK_LAUNCH("acg_sample_plain_row_kernel");
+    return row_kernel(p);
 }
 // one draw per row among the top_k most probable entries: acg_beam_row_kernel's lists with every row live (nir_acg_beam_gen_select's body; in the
 // plain form a target's logit is read from the GEMM's logits), then
@@ -845,85 +746,76 @@ static int launch_acg_sample_topk(const float* o, int64_t R, int64_t nsrc, int K
     return launch_sample_topk_select(tval, tidx, nullptr, R, top_k, key, inv_tau, out, st);
 }
 
-struct AcgSamplePlan {
+// ---- the decode of Seq2seq (acg == NULL) and of ACG ---------------------------------------------------------------------------------------------------
+struct SamplePlan {
     S2sStepBufs s;                                    // the stepper's buffers, over R = B N decode rows
-    void* gen;                                        // acg_sample_gen_bytes or acg_sample_topk_bytes
-    size_t gen_bytes;
-    float* cum;                                       // [R] the state of the freeze rule
-    int* fin;
-    int64_t* len;
-    float* attn;                                      // [max_len][R][QL] the decoder's attention rows of every step
-    float *csb, *cq, *ccat, *cattn;                   // a copy attention of its own (reuse_copy_attn off), as in the beam's plan
+    SampleTail t;                                     // (ACG: its generator's workspace holds the top-k lists)
+    float* attn;                                      // [max_len][R][QL] the attention rows of every step
+    AcgCopyAttn ca;                                   // ACG only: a copy attention of its own
     size_t bytes;
 };
-static AcgSamplePlan acg_sample_plan(void* ws, size_t cap, int64_t B, int QL, int N, int top_k, int max_len, int H, int64_t VT, int attn_type, bool fused,
-                                     int cell, bool step16, bool own_copy_attn) {
+// acg: 0 = Seq2seq, 1 = ACG with reuse_copy_attn, 2 = ACG with a copy attention of its own
+static SamplePlan sample_plan(void* ws, size_t cap, int64_t B, int QL, int N, int top_k, int max_len, int H, int64_t VT, int attn_type, bool fused, int cell,
+                              bool step16, int acg) {
     Workspace a(ws, cap);
-    AcgSamplePlan p;
+    SamplePlan p;
     const int64_t R = B * N;
     p.s = s2s_step_bufs(a, R, B, QL, H, VT, attn_type, true, cell, step16);                 // (no logits of the stepper's: the generator's workspace below)
-    p.s.tgt = a.take<int64_t>((size_t)R);
+    if (acg)
+        p.t.carve(a, R, top_k, R == 0 ? 0 : top_k > 0 ? acg_sample_topk_bytes(R, H, VT, top_k, fused) : acg_sample_gen_bytes(R, H, VT, fused), false);
+    else
+        p.t.carve(a, R, H, VT, top_k, fused ? SAMPLE_GEN_FUSED : SAMPLE_GEN_PLAIN);
+    p.s.tgt = p.t.tgt;
     if (cell == S2S_CELL_GRU) p.s.gru = a.take<float>(gru_step_scratch_floats(R, H));
-    p.gen_bytes = R == 0 ? 0 : top_k > 0 ? acg_sample_topk_bytes(R, H, VT, top_k, fused) : acg_sample_gen_bytes(R, H, VT, fused);
-    p.gen = a.take<char>(p.gen_bytes);
-    p.cum = a.take<float>((size_t)R);
-    p.fin = a.take<int>((size_t)R);
-    p.len = a.take<int64_t>((size_t)R);
     p.attn = a.take<float>((size_t)max_len * R * QL);
-    p.csb = p.cq = p.ccat = p.cattn = nullptr;
-    if (own_copy_attn) {
-        p.csb = a.take<float>(attn_type == NIR_S2S_ATTN_DOT ? 0 : (size_t)B * QL * H);
-        p.cq = a.take<float>(attn_type == NIR_S2S_ATTN_MLP ? (size_t)R * H : 0);
-        p.ccat = a.take<float>((size_t)R * 2 * H);
-        p.cattn = a.take<float>((size_t)R * QL);
-    }
+    if (acg == 2) p.ca.carve(a, R, B, QL, H, attn_type);
     p.bytes = align_up(a.off, 256);
     return p;
 }
-static size_t acg_sample_decode_workspace_bytes(int64_t B, int QL, int CV, int N, int top_k, int max_len, const nir_seq2seq_decoder_weights* w,
-                                                const nir_acg_copy_weights* cw, int cell) {
-    if (!cw || !s2s_weights_ok(w) || B < 0 || QL <= 0 || max_len <= 0 || !sample_dims_ok(N, top_k, w->VT) || B * N >= 0x7FFFFFFFLL) return 0;
-    const AcgDecode g{cw, nullptr, nullptr, nullptr, CV};
-    if (!acg_weights_ok(w, &g) || !acg_sample_dims_ok(QL, CV, w->VT)) return 0;
-    return acg_sample_plan(nullptr, 0, B, QL, N, top_k, max_len, w->H, w->VT, w->attn_type, s2s_fused(w), cell, s2s_step16(w), !cw->reuse_copy_attn).bytes;
+static size_t sample_decode_workspace_bytes(int64_t B, int QL, int N, int top_k, int max_len, const nir_seq2seq_decoder_weights* w, int cell,
+                                            const AcgDecode* acg = nullptr) {
+    if (!s2s_weights_ok(w) || B < 0 || QL <= 0 || max_len <= 0 || !sample_dims_ok(N, top_k, w->VT) || B * N >= 0x7FFFFFFFLL) return 0;
+    if (acg && (!acg_weights_ok(w, acg) || !acg_sample_dims_ok(QL, acg->CV, w->VT))) return 0;
+    return sample_plan(nullptr, 0, B, QL, N, top_k, max_len, w->H, w->VT, w->attn_type, s2s_fused(w), cell, s2s_step16(w),
+                       acg ? (acg->cw->reuse_copy_attn ? 1 : 2) : 0).bytes;
 }
 
-// s2s_sample_decode with the copy generator's tail (s2s_beam_decode's): (a second attention over the R rows with nsrc = B whose
-// query is the attentional output,) then one draw per row from the collapsed extended distribution, or from its top_k entries.
-static int acg_sample_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, const float* table,
-                             int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len, const nir_seq2seq_decoder_weights* w,
-                             const nir_acg_copy_weights* cw, const int64_t* src_map_idx, const int64_t* ext2tgt, const int64_t* ext2src, int CV, int N,
-                             int top_k, float inv_tau, uint64_t seed, void* workspace, size_t workspace_bytes, int64_t* predictions, float* token_logprobs,
-                             float* scores, int64_t* lengths, float* attentions, int cell, hipStream_t st) {
-    NIR_REQUIRE(cw, "acg_sample_decode: null copy weights");
-    NIR_REQUIRE(N >= 1 && B >= 0 && B * (int64_t)N < 0x7FFFFFFFLL, "acg_sample_decode: N < 1 or too many decode rows");
+// The stepper of s2s_gen.hpp over N decode rows per source row, with the sampling tail behind the attentional output: Seq2seq's draw is the tail's
+// own; ACG's (s2s_beam_decode's tail, DESIGN.md sections 24 and 33) is (a second attention over the R rows with nsrc = B whose query is the
+// attentional output,) then one draw per row from the collapsed extended distribution, or from its top_k entries.  The state ping-pongs as in the
+// greedy decode: step s writes slot s & 1 and reads the other.
+static int s2s_sample_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, int N, int top_k,
+                             float inv_tau, uint64_t seed, const float* table, int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len,
+                             const nir_seq2seq_decoder_weights* w, void* workspace, size_t workspace_bytes, int64_t* predictions, float* token_logprobs,
+                             float* scores, int64_t* lengths, float* attentions, int cell, hipStream_t st, const AcgDecode* acg = nullptr) {
+    const char* name = acg ? "acg_sample_decode" : "sample_seq2seq_decode";
+    NIR_REQUIRE(!acg || acg->cw, "acg_sample_decode: null copy weights");
+    NIR_REQUIRE(N >= 1 && B >= 0 && B * (int64_t)N < 0x7FFFFFFFLL, "%s: N < 1 or too many decode rows", name);
     const int64_t R = B * N;
-    S2sStepper s{"acg_sample_decode", w, cell, table, memory_bank, source_len, V, R, B, E, QL, st};
+    S2sStepper s{name, w, cell, table, memory_bank, source_len, V, R, B, E, QL, st};
     NIR_PROPAGATE(s.check(dec_h, dec_c, predictions && token_logprobs && scores && lengths && attentions, bos, max_len));
-    NIR_REQUIRE(sample_dims_ok(N, top_k, w->VT), "acg_sample_decode: top_k outside 0 .. %d or above the target vocabulary", NIR_BEAM_MAX_W);
-    NIR_REQUIRE(sample_tau_ok(inv_tau), "acg_sample_decode: inv_temperature must be finite and > 0");
-    const AcgDecode g{cw, src_map_idx, ext2tgt, ext2src, CV};
-    NIR_REQUIRE(acg_weights_ok(w, &g), "acg_sample_decode: copy weights incomplete for the attention type");
-    NIR_REQUIRE(src_map_idx && ext2tgt && ext2src, "acg_sample_decode: null index tensor");
-    NIR_REQUIRE(acg_sample_dims_ok(QL, CV, w->VT), "acg_sample_decode: QL outside [1, 4096], CV outside [2, %d], or VT + CV too large", ACG_MAX_CV);
+    NIR_REQUIRE(sample_dims_ok(N, top_k, w->VT), "%s: top_k outside 0 .. %d or above the target vocabulary", name, NIR_BEAM_MAX_W);
+    NIR_REQUIRE(sample_tau_ok(inv_tau), "%s: inv_temperature must be finite and > 0", name);
+    if (acg) {
+        NIR_REQUIRE(acg_weights_ok(w, acg), "acg_sample_decode: copy weights incomplete for the attention type");
+        NIR_REQUIRE(acg->src_map_idx && acg->ext2tgt && acg->ext2src, "acg_sample_decode: null index tensor");
+        NIR_REQUIRE(acg_sample_dims_ok(QL, acg->CV, w->VT), "acg_sample_decode: QL outside [1, 4096], CV outside [2, %d], or VT + CV too large", ACG_MAX_CV);
+    }
     const int H = w->H;
-    const bool fused = s.fused, own_copy_attn = !cw->reuse_copy_attn, mlp = w->attn_type == NIR_S2S_ATTN_MLP;
-    const AcgSamplePlan p = acg_sample_plan(workspace, workspace_bytes, B, QL, N, top_k, max_len, H, w->VT, w->attn_type, fused, cell, s.step16, own_copy_attn);
+    const bool fused = s.fused;
+    const SamplePlan p = sample_plan(workspace, workspace_bytes, B, QL, N, top_k, max_len, H, w->VT, w->attn_type, fused, cell, s.step16,
+                                     acg ? (acg->cw->reuse_copy_attn ? 1 : 2) : 0);
     if (B == 0) return 0;                                 // nothing to enqueue: no workspace is needed either
     if (!workspace || p.bytes > workspace_bytes) {
-        set_error("acg_sample_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
+        set_error("%s: workspace too small (%zu < %zu)", name, workspace_bytes, p.bytes);
         return NIR_ERR_WORKSPACE;
     }
+    const SampleTail& t = p.t;
     s.b = p.s;
     NIR_PROPAGATE(s.prepare(dec_h, bos, p.s.h16[1]));
-    NIR_PROPAGATE(launch_sample_init(p.cum, p.fin, p.len, R, max_len, st));
-    const float* csb = memory_bank;                       // the score bank of the copy attention, over the B source rows (s2s_beam_decode)
-    if (own_copy_attn && w->attn_type != NIR_S2S_ATTN_DOT) {
-        NIR_PROPAGATE(launch_linear(memory_bank, H, nullptr, nullptr, 0, 0, 0, mlp ? cw->attn_ctx_w : cw->attn_in_wt, H, nullptr, nullptr, p.csb, H, B * QL, H, H,
-                                    NIR_ACT_NONE, st));
-        csb = p.csb;
-    }
-    SampleOut o{nullptr, nullptr, nullptr, p.fin, p.cum, p.len, predictions, token_logprobs, p.s.tgt, tgt2src, V, w->VT, B, N, 0, max_len, ext2src, CV};
+    NIR_PROPAGATE(t.init(R, max_len, st));
+    if (acg) NIR_PROPAGATE(p.ca.prepare(acg->cw, memory_bank, B, QL, H, w->attn_type, st));
+    SampleOut o = t.out(predictions, token_logprobs, tgt2src, V, w->VT, B, N, max_len, acg ? acg->ext2src : nullptr, acg ? acg->CV : 0);
     const float* hp = dec_h;
     const float* cp = dec_c;
     for (int step = 0; step < max_len; ++step) {
@@ -931,26 +823,26 @@ static int acg_sample_decode(const float* dec_h, const float* dec_c, const float
         float* cn = p.s.c[step & 1];
         float* arow = p.attn + (int64_t)step * R * QL;
         NIR_PROPAGATE(s.step(hp, cp, hn, cn, p.s.h16[(step + 1) & 1], p.s.h16[step & 1], arow, QL));
-        const float* ca = arow;
-        if (own_copy_attn) {
-            if (mlp)
-                NIR_PROPAGATE(launch_linear(p.s.ah, H, nullptr, nullptr, 0, 0, 0, cw->attn_query_w, H, cw->attn_query_b, nullptr, p.cq, H, R, H, H, NIR_ACT_NONE, st));
-            NIR_PROPAGATE(launch_attend(mlp ? p.cq : p.s.ah, p.s.ah, memory_bank, csb, cw->attn_v, source_len, R, QL, H, mlp, p.ccat, p.cattn, QL, st, B));
-            ca = p.cattn;
-        }
         const SampleKey key = sample_key(seed, step, B);
-        const AcgSampleIn in{cw->copy_w, cw->copy_b, ca, QL, source_len, QL, src_map_idx, ext2tgt, ext2src, CV};
         o.step = step;
-        if (top_k > 0)
-            NIR_PROPAGATE(launch_acg_sample_topk(p.s.ah, R, B, H, w->gen_w, w->gen_b, fused ? w->gen_frag : nullptr, w->VT, top_k, key, inv_tau, in, p.gen, p.gen_bytes,
-                                                 o, st));
-        else
-            NIR_PROPAGATE(launch_acg_sample_gen_select(fused, p.s.ah, R, H, w->gen_w, w->gen_b, w->gen_frag, w->VT, key, inv_tau, in, p.gen, p.gen_bytes, nullptr,
-                                                       nullptr, o, st));
+        if (!acg) {
+            NIR_PROPAGATE(t.draw(fused ? SAMPLE_GEN_FUSED : SAMPLE_GEN_PLAIN, p.s.ah, nullptr, R, H, w->gen_w, w->gen_b, w->gen_frag, w->VT, top_k, key, inv_tau, o, st));
+        } else {
+            const float* ca = arow;
+            int64_t ca_stride = QL;
+            NIR_PROPAGATE(p.ca.step(acg->cw, p.s.ah, R, B, memory_bank, source_len, QL, H, w->attn_type, &ca, &ca_stride, st));
+            const AcgSampleIn in{acg->cw->copy_w, acg->cw->copy_b, ca, ca_stride, source_len, QL, acg->src_map_idx, acg->ext2tgt, acg->ext2src, acg->CV};
+            if (top_k > 0)
+                NIR_PROPAGATE(launch_acg_sample_topk(p.s.ah, R, B, H, w->gen_w, w->gen_b, fused ? w->gen_frag : nullptr, w->VT, top_k, key, inv_tau, in, t.gen, t.gen_bytes,
+                                                     o, st));
+            else
+                NIR_PROPAGATE(launch_acg_sample_gen_select(fused, p.s.ah, R, H, w->gen_w, w->gen_b, w->gen_frag, w->VT, key, inv_tau, in, t.gen, t.gen_bytes, nullptr,
+                                                           nullptr, o, st));
+        }
         hp = hn;
         cp = cn;
     }
-    return launch_sample_end(p.cum, p.len, p.attn, B, N, max_len, QL, scores, lengths, attentions, st);
+    return t.end(B, N, max_len, scores, lengths, st, p.attn, QL, attentions);
 }
 
 }  // namespace nir
@@ -1073,7 +965,8 @@ extern "C" int nir_acg_sample_gen_select(const float* o, int64_t rows, int64_t n
 
 extern "C" size_t nir_acg_sample_decode_workspace_bytes(int64_t B, int QL, int CV, int N, int top_k, int max_len, const nir_seq2seq_decoder_weights* w,
                                                         const nir_acg_copy_weights* cw) {
-    return nir::acg_sample_decode_workspace_bytes(B, QL, CV, N, top_k, max_len, w, cw, nir::S2S_CELL_LSTM);
+    const nir::AcgDecode g{cw, nullptr, nullptr, nullptr, CV};
+    return nir::sample_decode_workspace_bytes(B, QL, N, top_k, max_len, w, nir::S2S_CELL_LSTM, &g);
 }
 extern "C" int nir_acg_sample_decode(const float* dec_h, const float* dec_c, const float* memory_bank, const int64_t* source_len, int64_t B, int QL,
                                      const float* table, int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len,
@@ -1081,13 +974,15 @@ extern "C" int nir_acg_sample_decode(const float* dec_h, const float* dec_c, con
                                      const int64_t* ext2tgt, const int64_t* ext2src, int CV, int N, int top_k, float inv_temperature, uint64_t seed,
                                      void* workspace, size_t workspace_bytes, int64_t* predictions, float* token_logprobs, float* scores, int64_t* lengths,
                                      float* attentions, nir_stream_t stream) {
-    return nir::acg_sample_decode(dec_h, dec_c, memory_bank, source_len, B, QL, table, V, E, tgt2src, bos, max_len, w, cw, src_map_idx, ext2tgt, ext2src, CV, N,
-                                  top_k, inv_temperature, seed, workspace, workspace_bytes, predictions, token_logprobs, scores, lengths, attentions,
-                                  nir::S2S_CELL_LSTM, (hipStream_t)stream);
+    const nir::AcgDecode g{cw, src_map_idx, ext2tgt, ext2src, CV};
+    return nir::s2s_sample_decode(dec_h, dec_c, memory_bank, source_len, B, QL, N, top_k, inv_temperature, seed, table, V, E, tgt2src, bos, max_len, w,
+                                  workspace, workspace_bytes, predictions, token_logprobs, scores, lengths, attentions, nir::S2S_CELL_LSTM,
+                                  (hipStream_t)stream, &g);
 }
 extern "C" size_t nir_acg_sample_gru_decode_workspace_bytes(int64_t B, int QL, int CV, int N, int top_k, int max_len, const nir_seq2seq_decoder_weights* w,
                                                             const nir_acg_copy_weights* cw) {
-    return nir::acg_sample_decode_workspace_bytes(B, QL, CV, N, top_k, max_len, w, cw, nir::S2S_CELL_GRU);
+    const nir::AcgDecode g{cw, nullptr, nullptr, nullptr, CV};
+    return nir::sample_decode_workspace_bytes(B, QL, N, top_k, max_len, w, nir::S2S_CELL_GRU, &g);
 }
 extern "C" int nir_acg_sample_gru_decode(const float* dec_h, const float* memory_bank, const int64_t* source_len, int64_t B, int QL, const float* table,
                                          int64_t V, int E, const int64_t* tgt2src, int64_t bos, int max_len, const nir_seq2seq_decoder_weights* w,
@@ -1095,7 +990,8 @@ extern "C" int nir_acg_sample_gru_decode(const float* dec_h, const float* memory
                                          int N, int top_k, float inv_temperature, uint64_t seed, void* workspace, size_t workspace_bytes,
                                          int64_t* predictions, float* token_logprobs, float* scores, int64_t* lengths, float* attentions,
                                          nir_stream_t stream) {
-    return nir::acg_sample_decode(dec_h, nullptr, memory_bank, source_len, B, QL, table, V, E, tgt2src, bos, max_len, w, cw, src_map_idx, ext2tgt, ext2src, CV, N,
-                                  top_k, inv_temperature, seed, workspace, workspace_bytes, predictions, token_logprobs, scores, lengths, attentions,
-                                  nir::S2S_CELL_GRU, (hipStream_t)stream);
+    const nir::AcgDecode g{cw, src_map_idx, ext2tgt, ext2src, CV};
+    return nir::s2s_sample_decode(dec_h, nullptr, memory_bank, source_len, B, QL, N, top_k, inv_temperature, seed, table, V, E, tgt2src, bos, max_len, w,
+                                  workspace, workspace_bytes, predictions, token_logprobs, scores, lengths, attentions, nir::S2S_CELL_GRU,
+                                  (hipStream_t)stream, &g);
 }

@@ -137,7 +137,8 @@ struct S2sPlan {
     S2sStepBufs s;
     float* pval;
     int* pidx;
-    float *psum, *csb, *cq, *ccat, *cattn;             // ACG only: the sums of the partials; a copy attention of its own
+    float* psum;                                      // ACG only: the sums of the partials
+    AcgCopyAttn ca;                                   // ACG only: a copy attention of its own
     size_t bytes;
 };
 // acg: 0 = Seq2seq, 1 = ACG with reuse_copy_attn, 2 = ACG with a copy attention of its own
@@ -148,17 +149,12 @@ static S2sPlan s2s_plan(void* ws, size_t cap, int64_t B, int QL, int H, int64_t 
     p.pval = a.take<float>(fused ? (size_t)S2S_MAX_WGS * 4 * B : 0);
     p.pidx = a.take<int>(fused ? (size_t)S2S_MAX_WGS * 4 * B : 0);
     p.s.tgt = a.take<int64_t>((size_t)B);
-    p.psum = p.csb = p.cq = p.ccat = p.cattn = nullptr;
+    p.psum = nullptr;
     if (acg) {
         if (!fused) { p.pval = a.take<float>((size_t)B); p.pidx = a.take<int>((size_t)B); }      // one partial per row behind the GEMM
         p.psum = a.take<float>(fused ? (size_t)S2S_MAX_WGS * 4 * B : (size_t)B);
     }
-    if (acg == 2) {
-        p.csb = a.take<float>(attn_type == NIR_S2S_ATTN_DOT ? 0 : (size_t)B * QL * H);
-        p.cq = a.take<float>(attn_type == NIR_S2S_ATTN_MLP ? (size_t)B * H : 0);
-        p.ccat = a.take<float>((size_t)B * 2 * H);
-        p.cattn = a.take<float>((size_t)B * QL);
-    }
+    if (acg == 2) p.ca.carve(a, B, B, QL, H, attn_type);
     if (cell == S2S_CELL_GRU) p.s.gru = a.take<float>(gru_step_scratch_floats(B, H));
     p.bytes = align_up(a.off, 256);
     return p;
@@ -338,13 +334,12 @@ int nir::s2s_decode(const float* dec_h, const float* dec_c, const float* memory_
     NIR_PROPAGATE(s.check(dec_h, dec_c, predictions && attentions, bos, max_len));
     const int H = w->H;
     const bool fused = s.fused;
-    const bool own_copy_attn = acg && acg->cw && !acg->cw->reuse_copy_attn;
     if (acg) {
         NIR_REQUIRE(acg_weights_ok(w, acg), "acg_decode: copy weights incomplete for the attention type");
         NIR_REQUIRE(acg->src_map_idx && acg->ext2tgt && acg->ext2src, "acg_decode: null index tensor");
         NIR_REQUIRE(acg_dims_ok(QL, acg->CV), "acg_decode: CV outside [2, %d]", ACG_MAX_CV);
     }
-    S2sPlan p = s2s_plan(workspace, workspace_bytes, B, QL, H, w->VT, w->attn_type, fused, acg ? (own_copy_attn ? 2 : 1) : 0, cell);
+    S2sPlan p = s2s_plan(workspace, workspace_bytes, B, QL, H, w->VT, w->attn_type, fused, acg ? (acg->cw->reuse_copy_attn ? 1 : 2) : 0, cell);
     if (!workspace || p.bytes > workspace_bytes) {
         set_error("seq2seq_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
         return NIR_ERR_WORKSPACE;
@@ -352,13 +347,7 @@ int nir::s2s_decode(const float* dec_h, const float* dec_c, const float* memory_
     if (B == 0) return 0;
     s.b = p.s;
     NIR_PROPAGATE(s.prepare(dec_h, bos, p.s.h16[1]));
-    const bool mlp = w->attn_type == NIR_S2S_ATTN_MLP;
-    const float* csb = memory_bank;                       // the score bank of ACG's own copy attention, the forms of the stepper's
-    if (own_copy_attn && w->attn_type != NIR_S2S_ATTN_DOT) {
-        NIR_PROPAGATE(launch_linear(memory_bank, H, nullptr, nullptr, 0, 0, 0, mlp ? acg->cw->attn_ctx_w : acg->cw->attn_in_wt, H, nullptr, nullptr, p.csb, H,
-                                    B * QL, H, H, NIR_ACT_NONE, st));
-        csb = p.csb;
-    }
+    if (acg) NIR_PROPAGATE(p.ca.prepare(acg->cw, memory_bank, B, QL, H, w->attn_type, st));
     const float* hp = dec_h;
     const float* cp = dec_c;
     for (int step = 0; step < max_len; ++step) {
@@ -367,16 +356,9 @@ int nir::s2s_decode(const float* dec_h, const float* dec_c, const float* memory_
         NIR_PROPAGATE(s.step(hp, cp, hn, cn, p.s.h16[(step + 1) & 1], p.s.h16[step & 1], attentions + (int64_t)step * QL, (int64_t)max_len * QL));
         const float* ah = p.s.ah;
         if (acg) {
-            const float* ca = attentions + (int64_t)step * QL;                 // the copy attention: the std one, or the alignment of a second
-            int64_t ca_stride = (int64_t)max_len * QL;                           // attention whose query is the attentional output (its own cat
-            if (own_copy_attn) {                                                 // and linear_out take no part in the value)
-                if (mlp)
-                    NIR_PROPAGATE(launch_linear(ah, H, nullptr, nullptr, 0, 0, 0, acg->cw->attn_query_w, H, acg->cw->attn_query_b, nullptr, p.cq, H, B, H, H,
-                                                NIR_ACT_NONE, st));
-                NIR_PROPAGATE(launch_attend(mlp ? p.cq : ah, ah, memory_bank, csb, acg->cw->attn_v, source_len, B, QL, H, mlp, p.ccat, p.cattn, QL, st));
-                ca = p.cattn;
-                ca_stride = QL;
-            }
+            const float* ca = attentions + (int64_t)step * QL;                 // the copy attention: the std one, or ACG's own
+            int64_t ca_stride = (int64_t)max_len * QL;
+            NIR_PROPAGATE(p.ca.step(acg->cw, ah, B, B, memory_bank, source_len, QL, H, w->attn_type, &ca, &ca_stride, st));
             NIR_PROPAGATE(launch_acg_gen_select(ah, B, H, w->gen_w, w->gen_b, fused ? w->gen_frag : nullptr, w->VT, p.s.logits, p.pval, p.pidx, p.psum,
                                                 acg->cw->copy_w, acg->cw->copy_b, ca, ca_stride, source_len, QL, acg->src_map_idx, acg->ext2tgt,
                                                 acg->ext2src, acg->CV, tgt2src, V, predictions + step, (int64_t)max_len, p.s.tgt, st));

@@ -1,8 +1,9 @@
 // Sampling decode for HredQS and the session models (include/neuroir_session_sample.h).  Nothing new is drawn: the noise,
 // the choice, the freeze rule and the outputs are those of csrc/sample.hip (section 28) with "source row" read as "decode row of the greedy
 // decode", and the steps in front of the tail are those of the beams in csrc/beam.hip over R = Bd N un-repeated rows, row r = n Bd + i.  This
-// unit holds host code only: the step helpers come from beam_steps.hpp, the tail's launchers from sample_tail.hpp, the top-k lists from the
-// public entries nir_beam_gen_topk / nir_beam_hredqs_gen_topk.  No sampling loop has a reorder: the state ping-pongs as in s2s_sample_decode,
+// unit holds host code only: the step helpers (CARS: the whole step, CarsRowsStep) come from beam_steps.hpp, the tail (SampleTail: carve, begin,
+// draw, end -- the one s2s_sample_decode runs too) and its launchers from sample_tail.hpp, the top-k lists from the public entries
+// nir_beam_gen_topk / nir_beam_hredqs_gen_topk.  No sampling loop has a reorder: the state ping-pongs as in s2s_sample_decode,
 // step s writes slot s & 1 and reads the other (the first state goes into slot 1).
 // Everything is enqueued on the caller's stream: no host synchronisation, no allocation, no atomics.
 #include "beam_steps.hpp"
@@ -10,67 +11,13 @@
 
 namespace nir {
 
-// where the tail reads a step's rows from, and which generator it runs on them
-enum SessGen { SESS_GEN_PLAIN = 0, SESS_GEN_FUSED = 1, SESS_GEN_SPLIT = 2 };     // fp32 rows + GEMM; fp32 rows, fused; the split state, fused
-
-// the tail's part of a workspace plan over R sample rows
-struct SessTail {
-    int64_t* tgt;                                     // [R] the ids the next step reads
-    void* gen;                                        // the generator's workspace
-    size_t gen_bytes;
-    float *tval, *lse;                                // top_k > 0: the rows' lists [R, top_k] and lse [R]
-    int* tidx;
-    float* cum;                                       // [R] the state of the freeze rule
-    int* fin;
-    int64_t* len;
-    void carve(Workspace& a, int64_t R, int K, int64_t VT, int top_k, SessGen g) {
-        tgt = a.take<int64_t>((size_t)R);
-        gen_bytes = R == 0      ? 0
-                    : top_k > 0 ? (g == SESS_GEN_SPLIT ? nir_beam_hredqs_gen_topk_workspace_bytes(R, K, VT, top_k)
-                                                       : nir_beam_gen_topk_workspace_bytes(R, K, VT, top_k, g == SESS_GEN_FUSED))
-                    : g == SESS_GEN_SPLIT ? sample_gen_split_bytes(R, K, VT)
-                                          : sample_gen_bytes(R, K, VT, g == SESS_GEN_FUSED);
-        gen = a.take<char>(gen_bytes);
-        tval = a.take<float>((size_t)R * top_k);
-        tidx = a.take<int>((size_t)R * top_k);
-        lse = a.take<float>(top_k > 0 ? (size_t)R : 0);
-        cum = a.take<float>((size_t)R);
-        fin = a.take<int>((size_t)R);
-        len = a.take<int64_t>((size_t)R);
-    }
-    int begin(int64_t R, int64_t bos, int max_len, hipStream_t st) const {
-        NIR_PROPAGATE(launch_fill_i64(tgt, bos, R, st));
-        return launch_sample_init(cum, fin, len, R, max_len, st);
-    }
-    SampleOut out(int64_t* predictions, float* token_logprobs, const int64_t* tgt2src, int64_t V, int64_t VT, int64_t Bd, int N, int max_len) const {
-        return SampleOut{nullptr, nullptr, nullptr, fin, cum, len, predictions, token_logprobs, tgt, tgt2src, V, VT, Bd, N, 0, max_len};
-    }
-    // one step's draw for all R rows: x [R, K] fp32 (PLAIN, FUSED) or h16 [R][K/8][2][8] (SPLIT)
-    int draw(SessGen g, const float* x, const _Float16* h16, int64_t R, int K, const float* gen_w, const float* gen_b, const void* gen_frag, int64_t VT,
-             int top_k, const SampleKey& key, float inv_tau, const SampleOut& o, hipStream_t st) const {
-        if (top_k > 0) {
-            const int rc = g == SESS_GEN_SPLIT
-                               ? nir_beam_hredqs_gen_topk(h16, R, K, gen_b, gen_frag, VT, top_k, gen, gen_bytes, tval, tidx, lse, (nir_stream_t)st)
-                               : nir_beam_gen_topk(x, R, K, gen_w, gen_b, g == SESS_GEN_FUSED ? gen_frag : nullptr, VT, top_k, gen, gen_bytes, tval, tidx, lse,
-                                                   (nir_stream_t)st);
-            if (rc != 0) return rc;
-            return launch_sample_topk_select(tval, tidx, lse, R, top_k, key, inv_tau, o, st);
-        }
-        if (g == SESS_GEN_SPLIT) return launch_sample_gen_split(h16, R, K, gen_b, gen_frag, VT, key, inv_tau, gen, gen_bytes, o, st);
-        return launch_sample_gen(g == SESS_GEN_FUSED, x, R, K, gen_w, gen_b, gen_frag, VT, key, inv_tau, gen, gen_bytes, o, st);
-    }
-    int end(int64_t Bd, int N, int max_len, float* scores, int64_t* lengths, hipStream_t st) const {
-        return launch_sample_end(cum, len, nullptr, Bd, N, max_len, 0, scores, lengths, nullptr, st);
-    }
-};
-
 // ---- the decoders without attention (M_MATCH_TENSOR, MNSRF) and HredQS: state buffers + tail -----------------------------------------------------
 struct PlainSamplePlan {
     float *h[2], *c[2], *h16[2];
-    SessTail t;
+    SampleTail t;
     size_t bytes;
 };
-static PlainSamplePlan plain_sample_plan(void* ws, size_t cap, int64_t Bd, int H, int64_t VT, int N, int top_k, bool step16, SessGen g) {
+static PlainSamplePlan plain_sample_plan(void* ws, size_t cap, int64_t Bd, int H, int64_t VT, int N, int top_k, bool step16, SampleGenForm g) {
     Workspace a(ws, cap);
     PlainSamplePlan p;
     const int64_t R = Bd * N;
@@ -85,7 +32,7 @@ static PlainSamplePlan plain_sample_plan(void* ws, size_t cap, int64_t Bd, int H
 template <class Begin>
 static int plain_sample_decode(const char* name, int64_t Bd, int H, const float* table, int E, const float* w_ih, const float* w_hh, const float* b_ih,
                                const float* b_hh, const float* gate_fold, const void* whh_frag, bool step16, const float* gen_w, const float* gen_b,
-                               const void* gen_frag, int64_t VT, SessGen g, const int64_t* tgt2src, int64_t V, int64_t bos, int N, int top_k, float inv_tau,
+                               const void* gen_frag, int64_t VT, SampleGenForm g, const int64_t* tgt2src, int64_t V, int64_t bos, int N, int top_k, float inv_tau,
                                uint64_t seed, int max_len, void* workspace, size_t workspace_bytes, int64_t* predictions, float* token_logprobs,
                                float* scores, int64_t* lengths, hipStream_t st, Begin begin) {
     const int64_t R = Bd * N;
@@ -95,7 +42,7 @@ static int plain_sample_decode(const char* name, int64_t Bd, int H, const float*
         set_error("%s: workspace too small (%zu < %zu)", name, workspace_bytes, p.bytes);
         return NIR_ERR_WORKSPACE;
     }
-    const SessTail& t = p.t;
+    const SampleTail& t = p.t;
     NIR_PROPAGATE(begin(p));
     NIR_PROPAGATE(t.begin(R, bos, max_len, st));
     LstmStepArgs a = beam_lstm_step_args(table, t.tgt, E, w_ih, w_hh, b_ih, b_hh, step16, gate_fold, whh_frag, R, H, p.h, p.c, p.h16);
@@ -117,29 +64,16 @@ static int plain_sample_decode(const char* name, int64_t Bd, int H, const float*
 
 // ---- CARS: the step of nir_beam_cars_decode over R rows, the tail on p1 ----------------------------------------------------------------------------------
 struct CarsSamplePlan {
-    float *mem, *memq, *sess, *h[2], *c[2], *h16[2], *qv, *cat, *ah, *p1;
-    int64_t* rowmap;
-    SessTail t;
+    CarsRowsStep s;
+    SampleTail t;
     size_t bytes;
 };
 static CarsSamplePlan cars_sample_plan(void* ws, size_t cap, int64_t rows_src, int64_t Bd, int QL, int N, int top_k, const nir_cars_decoder_weights* w,
                                        bool fused) {
     Workspace a(ws, cap);
     CarsSamplePlan p;
-    const int64_t R = Bd * N;
-    const int HD = w->HD, P = w->P;
-    const bool foldq = w->attn_q_w != nullptr, step16 = cars_beam_step16(w);
-    p.mem = a.take<float>((size_t)rows_src * QL * HD);
-    p.memq = a.take<float>(foldq ? (size_t)rows_src * QL * HD : 0);
-    p.sess = a.take<float>(w->KS > 0 ? (size_t)R * P : 0);
-    for (int k = 0; k < 2; ++k) { p.h[k] = a.take<float>((size_t)R * HD); p.c[k] = a.take<float>((size_t)R * HD); }
-    for (int k = 0; k < 2; ++k) p.h16[k] = a.take<float>(step16 ? (size_t)R * HD : 0);
-    p.qv = a.take<float>(foldq ? 0 : (size_t)R * HD);
-    p.cat = a.take<float>((size_t)R * 2 * HD);
-    p.ah = a.take<float>((size_t)R * HD);
-    p.p1 = a.take<float>((size_t)R * P);
-    p.rowmap = a.take<int64_t>((size_t)R);
-    p.t.carve(a, R, P, w->VT, top_k, fused ? SESS_GEN_FUSED : SESS_GEN_PLAIN);
+    p.s.carve(a, rows_src, Bd * N, QL, w);
+    p.t.carve(a, Bd * N, w->P, w->VT, top_k, fused ? SAMPLE_GEN_FUSED : SAMPLE_GEN_PLAIN);
     p.bytes = align_up(a.off, 256);
     return p;
 }
@@ -178,7 +112,7 @@ extern "C" size_t nir_sample_hredqs_decode_workspace_bytes(int64_t B, int64_t S,
         !sess_rows_ok(B * S, N))
         return 0;
     const bool fast = hq_fast(w);
-    return plain_sample_plan(nullptr, 0, B * S, w->H, w->VT, N, top_k, fast, fast ? SESS_GEN_SPLIT : SESS_GEN_PLAIN).bytes;
+    return plain_sample_plan(nullptr, 0, B * S, w->H, w->VT, N, top_k, fast, fast ? SAMPLE_GEN_SPLIT : SAMPLE_GEN_PLAIN).bytes;
 }
 
 extern "C" int nir_sample_hredqs_decode(const float* h_steps, const float* c_steps, int64_t B, int64_t S, const float* table, int64_t V, int E,
@@ -199,7 +133,7 @@ extern "C" int nir_sample_hredqs_decode(const float* h_steps, const float* c_ste
     const int64_t Bd = B * S, R = Bd * N;
     const bool fast = hq_fast(w);
     return plain_sample_decode("sample_hredqs_decode", Bd, H, table, E, w->rnn_wih, w->rnn_whh, w->rnn_bih, w->rnn_bhh, w->rnn_gate_fold, w->rnn_whh_frag, fast,
-                               w->gen_w, w->gen_b, w->gen_frag, w->VT, fast ? SESS_GEN_SPLIT : SESS_GEN_PLAIN, tgt2src, V, bos, N, top_k, inv_temperature, seed,
+                               w->gen_w, w->gen_b, w->gen_frag, w->VT, fast ? SAMPLE_GEN_SPLIT : SAMPLE_GEN_PLAIN, tgt2src, V, bos, N, top_k, inv_temperature, seed,
                                max_len, workspace, workspace_bytes, predictions, token_logprobs, scores, lengths, st, [&](const PlainSamplePlan& p) {
                                    // pairing, repeat and split in one launch: every sample of decode row i starts from step i / B of session i % B
                                    return launch_hq_beam_begin(h_steps, c_steps, B, S, H, R, p.h[1], p.c[1],
@@ -211,7 +145,7 @@ extern "C" size_t nir_sample_plain_decode_workspace_bytes(int64_t Bd, int H, int
     using namespace nir;
     if (H <= 0 || H % 4 || VT <= 0 || VT >= 0x7FFFFFF0LL || max_len <= 0 || !sample_dims_ok(N, top_k, VT) || !sess_rows_ok(Bd, N)) return 0;
     const bool fuse = fused && gen_fusable(H, VT) && !tun(g_tun.exact_f32);
-    return plain_sample_plan(nullptr, 0, Bd, H, VT, N, top_k, folded && H % 32 == 0 && !tun(g_tun.exact_f32), fuse ? SESS_GEN_FUSED : SESS_GEN_PLAIN).bytes;
+    return plain_sample_plan(nullptr, 0, Bd, H, VT, N, top_k, folded && H % 32 == 0 && !tun(g_tun.exact_f32), fuse ? SAMPLE_GEN_FUSED : SAMPLE_GEN_PLAIN).bytes;
 }
 
 extern "C" int nir_sample_plain_decode(const float* dec_h, const float* dec_c, int64_t Bd, int H, const float* table, int64_t V, int E, const float* w_ih,
@@ -232,7 +166,7 @@ extern "C" int nir_sample_plain_decode(const float* dec_h, const float* dec_c, i
     const int64_t R = Bd * N;
     const bool step16 = gate_fold && whh_frag && H % 32 == 0 && !tun(g_tun.exact_f32), fused = s2s_gen_fused(gen_frag, H, VT);
     return plain_sample_decode("sample_plain_decode", Bd, H, table, E, w_ih, w_hh, b_ih, b_hh, gate_fold, whh_frag, step16, gen_w, gen_b, gen_frag, VT,
-                               fused ? SESS_GEN_FUSED : SESS_GEN_PLAIN, tgt2src, V, bos, N, top_k, inv_temperature, seed, max_len, workspace, workspace_bytes,
+                               fused ? SAMPLE_GEN_FUSED : SAMPLE_GEN_PLAIN, tgt2src, V, bos, N, top_k, inv_temperature, seed, max_len, workspace, workspace_bytes,
                                predictions, token_logprobs, scores, lengths, st, [&](const PlainSamplePlan& p) {
                                    return launch_beam_repeat(dec_h, dec_c, Bd, R, H, p.h[1], p.c[1], step16 ? p.h16[1] : nullptr, nullptr, nullptr, st);
                                });
@@ -262,47 +196,25 @@ extern "C" int nir_sample_cars_decode(const float* dec_h, const float* dec_c, co
     NIR_REQUIRE(sample_dims_ok(N, top_k, w->VT), "sample_cars_decode: N < 1, or top_k outside 0 .. %d or above the target vocabulary", NIR_BEAM_MAX_W);
     NIR_REQUIRE(sample_tau_ok(inv_temperature), "sample_cars_decode: inv_temperature must be finite and > 0");
     NIR_REQUIRE(sess_rows_ok(Bd, N) && w->VT < 0x7FFFFFF0LL, "sample_cars_decode: too many decode rows or target tokens");
-    const int HD = w->HD, P = w->P;
+    const int P = w->P;
     const int64_t R = Bd * N, VT = w->VT;
-    const bool fused = s2s_gen_fused(gen_frag, P, VT), foldq = w->attn_q_w != nullptr, step16 = cars_beam_step16(w);
+    const bool fused = s2s_gen_fused(gen_frag, P, VT);
     if (Bd == 0) return 0;                                // nothing to enqueue: no workspace is needed either
-    const CarsSamplePlan p = cars_sample_plan(workspace, workspace_bytes, rows_src, Bd, QL, N, top_k, w, fused);
-    const SessTail& t = p.t;
+    CarsSamplePlan p = cars_sample_plan(workspace, workspace_bytes, rows_src, Bd, QL, N, top_k, w, fused);
+    const SampleTail& t = p.t;
     if (!workspace || p.bytes > workspace_bytes) {
         set_error("sample_cars_decode: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
         return NIR_ERR_WORKSPACE;
     }
-    // once per decode, as the greedy and the beam entries: the banks over every source row, the session projection (gathered through the
-    // repeated rowmap)
-    NIR_PROPAGATE(launch_linear(encoded_source, w->DQ, nullptr, nullptr, 0, 0, 0, w->dec_attn_w, w->DQ, nullptr, nullptr, p.mem, HD, rows_src * QL, HD, w->DQ,
-                                NIR_ACT_NONE, st));
-    if (foldq)
-        NIR_PROPAGATE(launch_linear(encoded_source, w->DQ, nullptr, nullptr, 0, 0, 0, w->attn_q_w, w->DQ, nullptr, nullptr, p.memq, HD, rows_src * QL, HD, w->DQ,
-                                    NIR_ACT_NONE, st));
-    NIR_PROPAGATE(launch_beam_repeat(dec_h, dec_c, Bd, R, HD, p.h[1], p.c[1], step16 ? p.h16[1] : nullptr, rowmap, p.rowmap, st));
-    NIR_PROPAGATE(t.begin(R, bos, max_len, st));
-    if (w->KS > 0)
-        NIR_PROPAGATE(launch_linear(nullptr, 0, p.rowmap, session_cat, w->KS, 1, 1, w->sess_w, w->KS, nullptr, nullptr, p.sess, P, R, P, w->KS, NIR_ACT_NONE, st));
-    LstmStepArgs a = beam_lstm_step_args(table, t.tgt, E, w->rnn_wih, w->rnn_whh, w->rnn_bih, w->rnn_bhh, step16, w->rnn_gate_fold, w->rnn_whh_frag, R, HD, p.h,
-                                         p.c, p.h16);
+    NIR_PROPAGATE(p.s.prepare(dec_h, dec_c, encoded_source, source_len, rows_src, rowmap, Bd, session_cat, table, t.tgt, E, 1, st,
+                              [&] { return t.begin(R, bos, max_len, st); }));
     SampleOut o = t.out(predictions, token_logprobs, tgt2src, V, VT, Bd, N, max_len);
-    const SessGen g = fused ? SESS_GEN_FUSED : SESS_GEN_PLAIN;
+    const SampleGenForm g = fused ? SAMPLE_GEN_FUSED : SAMPLE_GEN_PLAIN;
     for (int step = 0; step < max_len; ++step) {
-        const int wr = step & 1, rd = wr ^ 1;
-        float* hn = p.h[wr];
-        a.hprev[0] = p.h[rd]; a.cprev[0] = p.c[rd]; a.hnext[0] = hn; a.cnext[0] = p.c[wr];
-        if (step16) {
-            a.h16prev[0] = reinterpret_cast<const _Float16*>(p.h16[rd]);
-            a.h16next[0] = reinterpret_cast<_Float16*>(p.h16[wr]);
-        }
-        NIR_PROPAGATE(launch_lstm_step(a, 1, st));
-        if (!foldq) NIR_PROPAGATE(launch_linear(hn, HD, nullptr, nullptr, 0, 0, 0, w->attn_in_w, HD, nullptr, nullptr, p.qv, HD, R, HD, HD, NIR_ACT_NONE, st));
-        NIR_PROPAGATE(launch_dec_attend(foldq ? hn : p.qv, hn, p.mem, foldq ? p.memq : p.mem, p.rowmap, source_len, R, QL, HD, p.cat, st));
-        NIR_PROPAGATE(launch_linear(p.cat, 2 * HD, nullptr, nullptr, 0, 0, 0, w->attn_out_w, 2 * HD, nullptr, nullptr, p.ah, HD, R, HD, 2 * HD, NIR_ACT_TANH, st));
-        NIR_PROPAGATE(launch_linear_ex(p.ah, HD, nullptr, nullptr, 0, 0, 0, w->pred1_w, HD, nullptr, nullptr, p.p1, P, R, P, HD, NIR_ACT_NONE,
-                                       w->KS > 0 ? p.sess : nullptr, P, st));
+        const int wr = step & 1;
+        NIR_PROPAGATE(p.s.step(wr ^ 1, wr));
         o.step = step;
-        NIR_PROPAGATE(t.draw(g, p.p1, nullptr, R, P, w->pred2_w, nullptr, gen_frag, VT, top_k, sample_key(seed, step, Bd), inv_temperature, o, st));
+        NIR_PROPAGATE(t.draw(g, p.s.p1, nullptr, R, P, w->pred2_w, nullptr, gen_frag, VT, top_k, sample_key(seed, step, Bd), inv_temperature, o, st));
     }
     return t.end(Bd, N, max_len, scores, lengths, st);
 }
