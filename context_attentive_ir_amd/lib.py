@@ -441,6 +441,21 @@ ACG_SAMPLE_SIGNATURES = {
                                        c_ip, c_fp, c_fp, c_ip, c_fp, c_st]),
 }
 
+# Corpus retrieval for DSSM / CDSSM (the document index and the fused cosine top-k), declared in include/neuroir_retrieve.h (csrc/retrieve.hip):
+# every symbol starts with nir_retrieve_.  A table of its own, like the ones above; neuroir_hip.h does not include that header.
+RETRIEVE_MAX_K, RETRIEVE_MAX_D = 128, 256
+RETRIEVE_AUTO, RETRIEVE_FUSED, RETRIEVE_PLAIN = 0, 1, 2
+RETRIEVE_SIGNATURES = {
+    "nir_retrieve_index_bytes": (_z, [_l, _i]),
+    "nir_retrieve_add": (_i, [c_fp, _l, _i, C.c_void_p, _l, _l, C.c_void_p, c_st]),
+    "nir_retrieve_export": (_i, [C.c_void_p, _l, _i, _l, _l, c_fp, c_st]),
+    "nir_retrieve_import": (_i, [c_fp, _l, _i, C.c_void_p, _l, _l, c_st]),
+    "nir_retrieve_topk_workspace_bytes": (_z, [_l, _l, _i, _i, _i]),
+    "nir_retrieve_topk": (_i, [c_fp, _l, C.c_void_p, _l, _i, _i, _i, C.c_void_p, _z, C.c_void_p, c_fp, C.c_void_p, c_st]),
+    "nir_retrieve_merge": (_i, [c_fp, C.c_void_p, _i, _l, _i, c_fp, C.c_void_p, c_st]),
+    "nir_retrieve_chunk_docs": (_i, []),
+}
+
 DTYPE_F32, DTYPE_BF16, DTYPE_F32_SPLIT2 = 0, 1, 2
 DTYPES = {"f32": DTYPE_F32, "fp32": DTYPE_F32, "bf16": DTYPE_BF16, "f32_split2": DTYPE_F32_SPLIT2}
 
@@ -459,7 +474,8 @@ def load():
         for name, (res, args) in (list(SIGNATURES.items()) + list(GRU_DECODE_SIGNATURES.items()) + list(BEAM_SIGNATURES.items()) + list(SESSION_BEAM_SIGNATURES.items())
                                   + list(ACG_BEAM_SIGNATURES.items()) + list(HREDQS_BEAM_SIGNATURES.items()) + list(SCORE_SIGNATURES.items())
                                   + list(TEACHER_SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SESSION_SAMPLE_SIGNATURES.items())
-                                  + list(ACG_SCORE_SIGNATURES.items()) + list(ACG_SAMPLE_SIGNATURES.items())):
+                                  + list(ACG_SCORE_SIGNATURES.items()) + list(ACG_SAMPLE_SIGNATURES.items())
+                                  + list(RETRIEVE_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         _lib = lib

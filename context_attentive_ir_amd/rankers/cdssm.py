@@ -112,3 +112,30 @@ class CDSSM(nn.Module, lib.IdCheck):
             lib.check(L.nir_cdssm_score(lib.ptr(q), lib.ptr(d), B, N, QL, DL, lib.ptr(table), table.shape[0], table.shape[1], PAD, w.ref(),
                                         lib.ptr(ws), ws.numel(), lib.ptr(scores), lib.ptr(rq), lib.ptr(rd), lib.stream()), "nir_cdssm_score")
         return (scores, rq, rd) if return_reps else scores
+
+    # -- corpus retrieval (retrieval.DocumentIndex): each tower on its own ----------------------------------------------
+    def _encode(self, ids, side):
+        """one tower over the rows ids [R, L] -> [R, nout], through the scoring entry itself (nir_cdssm_score, return_reps): a tower row
+        depends on nothing but its own ids, so these are the bits of rep_q / rep_d of any forward that holds the row.  The other tower gets
+        one all-PAD row of the smallest width per call (documents) or per query (queries); its output is dropped."""
+        if self.training:
+            raise NotImplementedError("CDSSM.encode_queries / encode_documents run in eval mode only (call .eval())")
+        if ids.dim() != 2:
+            raise ValueError("CDSSM.encode_%s: expected ids [rows, width], got %s" % (side, tuple(ids.shape)))
+        R = ids.shape[0]
+        lib.require_device(ids, self.word_embeddings.table)
+        if R == 0:
+            return torch.empty(0, self._weights().struct.NO, device=ids.device, dtype=torch.float32)
+        if side == "queries":
+            other = torch.full((R, 1, TAPS), PAD, dtype=torch.int64, device=ids.device)
+            return self.forward(ids, None, other, None, return_reps=True)[1]
+        other = torch.full((1, TAPS), PAD, dtype=torch.int64, device=ids.device)
+        return self.forward(other, None, ids.unsqueeze(0), None, return_reps=True)[2][0]
+
+    def encode_queries(self, ids):
+        """query tower: ids [B, QL] -> [B, nout], bit-identical to rep_q of forward(..., return_reps=True) on the same rows (eval only)"""
+        return self._encode(ids, "queries")
+
+    def encode_documents(self, ids):
+        """document tower: ids [M, DL] -> [M, nout], bit-identical to rep_d of forward(..., return_reps=True) on the same rows (eval only)"""
+        return self._encode(ids, "documents")

@@ -148,6 +148,69 @@ class Ranker(WrapperBase):
         self.optimizer.step()
         return loss
 
+    # -- corpus retrieval (retrieval.DocumentIndex) ------------------------------
+    RETRIEVAL_MODELS = ("DSSM", "CDSSM")          # score = cos(rep_q, rep_d): the document tower can run once over a corpus
+    index_chunk_docs = 8192                        # documents per tower launch of build_index
+
+    def _require_two_towers(self, what):
+        if self.kind not in self.RETRIEVAL_MODELS:
+            raise RuntimeError("%s: corpus retrieval needs a two-tower model whose score is an inner product of the towers' outputs -- DSSM or "
+                               "CDSSM, not %s" % (what, self.kind))
+
+    @torch.no_grad()
+    def build_index(self, batches, index=None):
+        """batches: an iterable of {"doc_rep": [m, DL]} -> a retrieval.DocumentIndex over all their documents, in order (document ids count from
+        0, or from len(index) of a given index).  The document tower runs over at most `index_chunk_docs` documents per launch."""
+        from ..retrieval import DocumentIndex
+        self._require_two_towers("Ranker.build_index")
+        self.network.eval()
+        for ex in batches:
+            d = ex["doc_rep"]
+            d = d.cuda(non_blocking=True) if self.use_cuda else d
+            for lo in range(0, d.shape[0], self.index_chunk_docs):
+                reps = self.network.encode_documents(d[lo:lo + self.index_chunk_docs])
+                if index is None:
+                    index = DocumentIndex(reps.shape[1], reps.device)
+                index.add(reps)
+        if index is None:
+            index = DocumentIndex(self.args.nout, next(self.network.parameters()).device if self.use_cuda else None)
+        return index
+
+    def _search_body(self, ex, index, k):
+        self.network.eval()
+        q = ex["que_rep"].cuda(non_blocking=True) if self.use_cuda else ex["que_rep"]
+        val, ids = index.search(self.network.encode_queries(q), k)
+        return {"scores": val, "ids": ids}
+
+    def _drop_stale_search_graphs(self, index):
+        """A captured search holds the raw addresses of the index's buffer, so its key is the index's process-wide serial and version -- never
+        id(), which a later object can get again.  Graphs over an earlier version of this index or over an index that no longer exists can
+        never be replayed: they are dropped here, so that they neither pin dead buffers' graphs nor push live predict() graphs out of the
+        shared cache."""
+        import weakref
+        live = self.__dict__.setdefault("_search_indices", weakref.WeakValueDictionary())
+        live[index.serial] = index
+        g = self._graphs
+        if g is None:
+            return
+        for store in (g.entries, g.seen):
+            for key in [key for key in store if isinstance(key[1], tuple) and key[1][:1] == ("search",)
+                        and (key[1][1] not in live or (key[1][1] == index.serial and key[1][2] != index.version))]:
+                del store[key]
+
+    @torch.no_grad()
+    def search(self, ex, index, k):
+        """the k best documents of `index` for every query of ex["que_rep"] [B, QL] -> (scores [B, k] fp32 -- the model's cosine --, ids [B, k]
+        int64), descending.  No synchronisation; from the `predict_graph_min_calls`-th call of a (batch shape, index state, k) on, the call
+        replays a captured hipGraph like predict(); the index state is (index.serial, index.version)."""
+        self._require_two_towers("Ranker.search")
+        flavour = ("search", index.serial, index.version, int(k))
+        self._drop_stale_search_graphs(index)
+        out = self._graphed(ex, ("que_rep",), flavour, lambda e: self._search_body(e, index, k))
+        if out is None:
+            out = self._search_body(ex, index, k)
+        return out["scores"], out["ids"]
+
     # -- persistence (save / checkpoint in WrapperBase) ---------------------------------------------
     @staticmethod
     def load(filename, new_args=None):
