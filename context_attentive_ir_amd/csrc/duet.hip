@@ -253,6 +253,80 @@ static DuetPlan duet_plan(void* ws, size_t cap, int B, int N, int QL, int DL, in
     return p;
 }
 
+// The document side of the distributed model (duet.py:174,180,185,187-201): conv_d1 -> pool -> conv_d2 -> Hadamard with qv [B, NF] -> fc2 over
+// positions -> m1 [M, NF].  fused: one kernel per document tile (cd holds the per-tile fc2 partials; pooled / dd unused); else the
+// GEMM-per-layer chain (on pre-split planes when the pack carries them) and the Hadamard kernel.  Shared by nir_duet_score and
+// nir_duet_document_branch.
+static int duet_document_side(const int64_t* d_ids, const float* table, int E, int DL, int64_t M, int N, const nir_duet_weights* w, bool fused,
+                              bool tplanes, const float* qv, float* cd, float* pooled, float* dd, float* m1, hipStream_t st) {
+    const int NF = w->NF, P = w->pool, Tc = DL - 2, Tp = Tc - P + 1;
+    const int bnd = w->bounded ? 0x100 : 0;          // ACT_BOUNDED (gemm.hip): operands < 2^15 -> fp16 two-term split allowed
+    const bool planes = w->bounded && w->EP > 0 && w->table_h1 && w->table_h2 && w->convd1_h1 && w->convd1_h2 && w->convd2_h1 && w->convd2_h2 &&
+                        w->EP % 8 == 0 && w->EP >= NF && w->EP <= NF + 8 && w->EP >= E;
+    if (fused) {
+        NIR_PROPAGATE(launch_duet_doc(d_ids, table, E, DL, M, N, w->fw1, w->K1P, w->fw2, tplanes ? w->ftable : nullptr, w->fw1c, w->EPT, w->convd1_b,
+                                      w->convd2_b, w->fc2_w, w->fc2_b, qv, NF, P, cd, m1, st));
+    } else if (planes) {
+        // pre-split fp16 term planes end to end: table planes gathered by id (3 taps) -> conv_d1 + tanh (fp32) -> pooling writes
+        // planes -> conv_d2 + tanh; no operand is split inside a GEMM
+        const int EP = w->EP;
+        NIR_PROPAGATE(launch_linear_planes(w->table_h1, w->table_h2, EP, d_ids, Tc, DL, EP, 3, w->convd1_h1, w->convd1_h2, 3 * EP, w->convd1_b, cd, NF,
+                                           M * Tc, NF, 3 * EP, NIR_ACT_TANH, nullptr, 0, st));
+        _Float16* pp1 = reinterpret_cast<_Float16*>(pooled);
+        _Float16* pp2 = pp1 + (size_t)M * Tp * EP;
+        {
+            const int64_t total = (int64_t)M * ((Tp + MP_TR - 1) / MP_TR) * (EP / 4);
+            ProfScope ps("maxpool_t_planes_kernel", st);
+            hipLaunchKernelGGL(maxpool_t_planes_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 1 << 20)), dim3(256), 0, st, cd, pp1,
+                               pp2, Tc, P, NF / 4, EP / 4, (int64_t)M);
+        }
+        NIR_CHECK_LAUNCH("maxpool_t_planes_kernel");
+        NIR_PROPAGATE(launch_linear_planes(pp1, pp2, EP, nullptr, 0, 0, 0, 0, w->convd2_h1, w->convd2_h2, EP, w->convd2_b, dd, NF, M * Tp, NF, EP,
+                                           NIR_ACT_TANH, nullptr, 0, st));
+    } else {
+        NIR_PROPAGATE(launch_linear(nullptr, 0, d_ids, table, E, Tc, DL, w->convd1_w, 3 * E, w->convd1_b, nullptr, cd, NF, M * Tc, NF, 3 * E, NIR_ACT_TANH | bnd, st));
+        {
+            const int64_t total = (int64_t)M * ((Tp + MP_TR - 1) / MP_TR) * (NF / 4);
+            ProfScope ps("maxpool_t_kernel", st);
+            hipLaunchKernelGGL(maxpool_t_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 1 << 20)), dim3(256), 0, st, cd,
+                               pooled, Tc, P, NF / 4, (int64_t)M);
+        }
+        NIR_CHECK_LAUNCH("maxpool_t_kernel");
+        NIR_PROPAGATE(launch_linear(pooled, NF, nullptr, nullptr, 0, 0, 0, w->convd2_w, NF, w->convd2_b, nullptr, dd, NF, M * Tp, NF, NF, NIR_ACT_TANH | bnd, st));
+    }
+    // ---- Hadamard + fc2 over positions (duet.py:187-201)
+    if (!fused) {
+        ProfScope ps("duet_hadamard_kernel", st);
+        hipLaunchKernelGGL(duet_hadamard_kernel, dim3((unsigned)M), dim3(256), (size_t)(256 / (NF / 4)) * (NF / 4) * 16, st, dd, qv, w->fc2_w,
+                           w->fc2_b, N, Tp, NF, m1);
+        NIR_CHECK_LAUNCH("duet_hadamard_kernel");
+    }
+    return 0;
+}
+
+// workspace of the document side alone (nir_duet_document_branch): the caller owns qv and m1
+struct DuetDocPlan {
+    float *cd, *pooled, *dd;
+    size_t bytes;
+};
+
+static DuetDocPlan duet_doc_plan(void* ws, size_t cap, int B, int N, int DL, int NF, int P, bool fused, bool tplanes, int EPT) {
+    Workspace a(ws, cap);
+    const size_t M = (size_t)B * N;
+    const int Tc = DL - 2, Tp = Tc - P + 1;
+    DuetDocPlan p;
+    if (fused) {
+        p.cd = a.take<float>(duet_doc_partial_floats((int64_t)M, DL, P, tplanes, EPT));
+        p.pooled = p.dd = nullptr;
+    } else {
+        p.cd = a.take<float>(M * Tc * NF);
+        p.pooled = a.take<float>(M * Tp * (NF + 8));
+        p.dd = a.take<float>(M * Tp * NF);
+    }
+    p.bytes = align_up(a.off, 256);
+    return p;
+}
+
 }  // namespace nir
 
 extern "C" size_t nir_duet_workspace_bytes(int B, int N, int QL, int DL, int E, const nir_duet_weights* w) {
@@ -275,7 +349,7 @@ extern "C" int nir_duet_score(const int64_t* q_ids, const int64_t* d_ids, int B,
     NIR_REQUIRE((size_t)(DL + QL) * 8 + (size_t)(QL + (size_t)QL * DL) * 4 <= 64 * 1024,
                 "duet: QL=%d x DL=%d exact-match lists exceed 64 KB of LDS", QL, DL);
     if (B == 0) return 0;
-    const int NF = w->NF, P = w->pool, Tc = DL - 2, Tp = Tc - P + 1;
+    const int NF = w->NF, P = w->pool;
     const bool fused = duet_fused(w, E, DL);
     const bool tplanes = duet_table_planes(w, E);
     DuetPlan p = duet_plan(workspace, workspace_bytes, B, N, QL, DL, NF, P, fused, tplanes, w->EPT);
@@ -284,7 +358,6 @@ extern "C" int nir_duet_score(const int64_t* q_ids, const int64_t* d_ids, int B,
         return NIR_ERR_WORKSPACE;
     }
     const int64_t M = (int64_t)B * N;
-    const int bnd = w->bounded ? 0x100 : 0;          // ACT_BOUNDED (gemm.hip): operands < 2^15 -> fp16 two-term split allowed
     float* sloc = local_out ? local_out : p.sloc;
     float* sdist = dist_out ? dist_out : p.sdist;
     // ---- local model (duet.py:77-121)
@@ -304,50 +377,39 @@ extern "C" int nir_duet_score(const int64_t* q_ids, const int64_t* d_ids, int B,
     }
     NIR_CHECK_LAUNCH("colmax_kernel");
     NIR_PROPAGATE(launch_linear(p.qmax, NF, nullptr, nullptr, 0, 0, 0, w->fc1_w, NF, w->fc1_b, nullptr, p.qv, NF, B, NF, NF, NIR_ACT_TANH, st));
-    // ---- distributed model, document side (duet.py:174,180,185)
-    const bool planes = w->bounded && w->EP > 0 && w->table_h1 && w->table_h2 && w->convd1_h1 && w->convd1_h2 && w->convd2_h1 && w->convd2_h2 &&
-                        w->EP % 8 == 0 && w->EP >= NF && w->EP <= NF + 8 && w->EP >= E;
-    if (fused) {
-        NIR_PROPAGATE(launch_duet_doc(d_ids, table, E, DL, M, N, w->fw1, w->K1P, w->fw2, tplanes ? w->ftable : nullptr, w->fw1c, w->EPT, w->convd1_b,
-                                      w->convd2_b, w->fc2_w, w->fc2_b, p.qv, NF, P, p.cd, p.m1, st));
-    } else if (planes) {
-        // pre-split fp16 term planes end to end: table planes gathered by id (3 taps) -> conv_d1 + tanh (fp32) -> pooling writes
-        // planes -> conv_d2 + tanh; no operand is split inside a GEMM
-        const int EP = w->EP;
-        NIR_PROPAGATE(launch_linear_planes(w->table_h1, w->table_h2, EP, d_ids, Tc, DL, EP, 3, w->convd1_h1, w->convd1_h2, 3 * EP, w->convd1_b, p.cd, NF,
-                                           M * Tc, NF, 3 * EP, NIR_ACT_TANH, nullptr, 0, st));
-        _Float16* pp1 = reinterpret_cast<_Float16*>(p.pooled);
-        _Float16* pp2 = pp1 + (size_t)M * Tp * EP;
-        {
-            const int64_t total = (int64_t)M * ((Tp + MP_TR - 1) / MP_TR) * (EP / 4);
-            ProfScope ps("maxpool_t_planes_kernel", st);
-            hipLaunchKernelGGL(maxpool_t_planes_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 1 << 20)), dim3(256), 0, st, p.cd, pp1,
-                               pp2, Tc, P, NF / 4, EP / 4, (int64_t)M);
-        }
-        NIR_CHECK_LAUNCH("maxpool_t_planes_kernel");
-        NIR_PROPAGATE(launch_linear_planes(pp1, pp2, EP, nullptr, 0, 0, 0, 0, w->convd2_h1, w->convd2_h2, EP, w->convd2_b, p.dd, NF, M * Tp, NF, EP,
-                                           NIR_ACT_TANH, nullptr, 0, st));
-    } else {
-        NIR_PROPAGATE(launch_linear(nullptr, 0, d_ids, table, E, Tc, DL, w->convd1_w, 3 * E, w->convd1_b, nullptr, p.cd, NF, M * Tc, NF, 3 * E, NIR_ACT_TANH | bnd, st));
-        {
-            const int64_t total = (int64_t)M * ((Tp + MP_TR - 1) / MP_TR) * (NF / 4);
-            ProfScope ps("maxpool_t_kernel", st);
-            hipLaunchKernelGGL(maxpool_t_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 1 << 20)), dim3(256), 0, st, p.cd,
-                               p.pooled, Tc, P, NF / 4, (int64_t)M);
-        }
-        NIR_CHECK_LAUNCH("maxpool_t_kernel");
-        NIR_PROPAGATE(launch_linear(p.pooled, NF, nullptr, nullptr, 0, 0, 0, w->convd2_w, NF, w->convd2_b, nullptr, p.dd, NF, M * Tp, NF, NF, NIR_ACT_TANH | bnd, st));
-    }
-    // ---- Hadamard + fc2 over positions, fc3, fc4 (duet.py:187-207)
-    if (!fused) {
-        ProfScope ps("duet_hadamard_kernel", st);
-        hipLaunchKernelGGL(duet_hadamard_kernel, dim3((unsigned)M), dim3(256), (size_t)(256 / (NF / 4)) * (NF / 4) * 16, st, p.dd, p.qv, w->fc2_w,
-                           w->fc2_b, N, Tp, NF, p.m1);
-        NIR_CHECK_LAUNCH("duet_hadamard_kernel");
-    }
+    // ---- distributed model, document side + Hadamard + fc2 over positions (duet.py:174,180,185,187-201)
+    NIR_PROPAGATE(duet_document_side(d_ids, table, E, DL, M, N, w, fused, tplanes, p.qv, p.cd, p.pooled, p.dd, p.m1, st));
+    // ---- fc3, fc4 (duet.py:203-207)
     NIR_PROPAGATE(launch_linear(p.m1, NF, nullptr, nullptr, 0, 0, 0, w->fc3_w, NF, w->fc3_b, nullptr, p.m2, NF, M, NF, NF, NIR_ACT_TANH, st));
     NIR_PROPAGATE(launch_rowdot(p.m2, NF, w->fc4_w, w->fc4_b, sdist, M, NF, NIR_ACT_TANH, st));
     hipLaunchKernelGGL(add2_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, sloc, sdist, scores, M);
     NIR_CHECK_LAUNCH("add2_kernel");
     return 0;
+}
+
+extern "C" size_t nir_duet_document_workspace_bytes(int B, int N, int DL, int E, const nir_duet_weights* w) {
+    if (!w || B < 0 || N <= 0 || DL < w->pool + 2) return 0;
+    return nir::duet_doc_plan(nullptr, 0, B, N, DL, w->NF, w->pool, nir::duet_fused(w, E, DL), nir::duet_table_planes(w, E), w->EPT).bytes;
+}
+
+// The document side of nir_duet_score on its own: the caller supplies the query vector qv [B, NF] (fc1's output) and receives m1 [B N, NF].
+// Same checks, dispatch predicates and launches as the document side of nir_duet_score.
+extern "C" int nir_duet_document_branch(const int64_t* d_ids, int B, int N, int DL, const float* table, int64_t V, int E, const nir_duet_weights* w,
+                                        const float* qv, void* workspace, size_t workspace_bytes, float* m1, nir_stream_t stream) {
+    using namespace nir;
+    hipStream_t st = (hipStream_t)stream;
+    NIR_REQUIRE(d_ids && table && w && qv && m1, "duet: null pointer");
+    NIR_REQUIRE(B >= 0 && N > 0 && V > 0 && E > 0, "duet: bad dims");
+    NIR_REQUIRE(DL >= w->pool + 2, "duet: doc length %d too short for conv(3) + max_pool(%d)", DL, w->pool);
+    NIR_REQUIRE(w->pool >= 1 && w->pool <= 8, "duet: pool_size %d unsupported (1..8)", w->pool);
+    NIR_REQUIRE(w->NF % 4 == 0 && w->NF <= 1024, "duet: nfilters %d must be a multiple of 4 and <= 1024", w->NF);
+    if (B == 0) return 0;
+    const bool fused = duet_fused(w, E, DL);
+    const bool tplanes = duet_table_planes(w, E);
+    DuetDocPlan p = duet_doc_plan(workspace, workspace_bytes, B, N, DL, w->NF, w->pool, fused, tplanes, w->EPT);
+    if (!workspace || p.bytes > workspace_bytes) {
+        set_error("duet: workspace too small (%zu < %zu)", workspace_bytes, p.bytes);
+        return NIR_ERR_WORKSPACE;
+    }
+    return duet_document_side(d_ids, table, E, DL, (int64_t)B * N, N, w, fused, tplanes, qv, p.cd, p.pooled, p.dd, m1, st);
 }

@@ -184,6 +184,8 @@ SIGNATURES = {
     "nir_duet_workspace_bytes": (_z, [_i, _i, _i, _i, _i, C.POINTER(DuetWeights)]),
     "nir_duet_score": (_i, [c_ip, c_ip, _i, _i, _i, _i, c_fp, _l, _i, C.POINTER(DuetWeights), C.c_void_p, _z,
                             c_fp, c_fp, c_fp, c_st]),
+    "nir_duet_document_workspace_bytes": (_z, [_i, _i, _i, _i, C.POINTER(DuetWeights)]),
+    "nir_duet_document_branch": (_i, [c_ip, _i, _i, _i, c_fp, _l, _i, C.POINTER(DuetWeights), c_fp, C.c_void_p, _z, c_fp, c_st]),
     "nir_dssm_workspace_bytes": (_z, [_i, _i, _i]),
     "nir_dssm_score": (_i, [c_ip, c_ip, _i, _i, _i, _i, c_fp, _l, _i, _l, C.POINTER(DssmWeights), C.c_void_p, _z, c_fp, c_fp, c_fp, c_st]),
     "nir_cdssm_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),

@@ -20,6 +20,53 @@ from ..constants import PAD
 from ..modules import Embeddings
 
 
+def split_bounded(*operands):
+    """`bounded` of the DuetWeights pack: every operand (table, conv weights) below 2^15 in magnitude, so the fp16 two-term split holds them"""
+    return max(float(t.detach().abs().max()) for t in operands) < 32768.0
+
+
+def attach_document_fragments(pk, table, fuse=True, table_planes=True, presplit=False):
+    """The optional operands of the document branch on a DuetWeights pack `pk` (csrc/duet_fused.hip, csrc/duet.hip), built once per weight
+    version from pk.keep["convd1_w"] [NF, 3, E], pk.keep["convd2_w"] [NF, NF] and the embedding table [V, E] (on the device):
+      fuse          fw1 / fw2 / K1P: conv_d1 / conv_d2 zero-padded to 320 filter rows and a multiple of 32 in k, split into two fp16 terms and
+                    re-ordered into MFMA fragments;
+      table_planes  on top of them ftable / fw1c / EPT: the table as fp16 term planes [V, 2, EPT] and conv_d1 in chunk-major k order;
+      presplit      table_h1 .. convd2_h2 / EP: the term planes of the pre-split GEMM chain.
+    Nothing is attached unless the pack is `bounded` (table and conv weights below 2^15) and the shape has the form in question."""
+    E, NF, pool = table.shape[1], pk.struct.NF, pk.struct.pool
+    bounded = bool(pk.struct.bounded)
+    if bounded and fuse and NF <= 320 and NF % 4 == 0 and E % 4 == 0 and pool <= 5:
+        def fragments(w2d, kp=None):
+            rows, k = w2d.shape
+            kp = (k + 31) // 32 * 32 if kp is None else kp
+            pad = torch.zeros(320, kp, device=w2d.device, dtype=torch.float32)
+            pad[:rows, :k] = w2d
+            planes = torch.stack(lib.split_f16x2(pad, kp))                      # [2 terms, 320, kp] int16
+            return planes.view(2, 20, 16, kp // 32, 4, 8).permute(3, 1, 0, 4, 2, 5).contiguous(), kp
+        pk.keep["fw1"], k1p = fragments(pk.keep["convd1_w"].reshape(NF, 3 * E))
+        pk.keep["fw2"], _ = fragments(pk.keep["convd2_w"].reshape(NF, NF), 320)   # GEMM 2 always runs its 10 k-steps
+        pk.struct.fw1, pk.struct.fw2, pk.struct.K1P = pk.keep["fw1"].data_ptr(), pk.keep["fw2"].data_ptr(), k1p
+        if table_planes:
+            EPT = (E + 63) // 64 * 64            # an even number of 32-element column chunks
+            wc = torch.zeros(NF, 3, EPT, device=pk.keep["convd1_w"].device, dtype=torch.float32)
+            wc[:, :, :E] = pk.keep["convd1_w"].reshape(NF, 3, E)
+            wc = wc.view(NF, 3, EPT // 32, 32).permute(0, 2, 1, 3).reshape(NF, 3 * EPT)       # k = (chunk, tap, element)
+            pk.keep["fw1c"], _ = fragments(wc, 3 * EPT)
+            pk.keep["ftable"] = torch.stack(lib.split_f16x2(table, EPT), 1).contiguous()   # [V, 2, EPT]
+            pk.struct.fw1c, pk.struct.ftable, pk.struct.EPT = pk.keep["fw1c"].data_ptr(), pk.keep["ftable"].data_ptr(), EPT
+    EP = (max(E, NF) + 7) // 8 * 8
+    if bounded and presplit and EP <= NF + 8 and EP - E < 8:
+        # fp16 term planes of the table and of the two big conv weights, split once per weight version (122 MB at V = 100 000)
+        planes = dict(zip(("table_h1", "table_h2"), lib.split_f16x2(table, EP)))
+        planes.update(zip(("convd1_h1", "convd1_h2"), lib.split_f16x2(pk.keep["convd1_w"].reshape(NF * 3, E), EP)))
+        planes.update(zip(("convd2_h1", "convd2_h2"), lib.split_f16x2(pk.keep["convd2_w"], EP)))
+        for k, v in planes.items():
+            pk.keep[k] = v
+            setattr(pk.struct, k, v.data_ptr())
+        pk.struct.EP = EP
+    return pk
+
+
 class LocalModel(nn.Module):
     """Parameters of duet.py:62-121."""
 
@@ -86,41 +133,10 @@ class DUET(nn.Module, lib.IdCheck):
                      fc3_w=dm.fc3.weight, fc3_b=dm.fc3.bias, fc4_w=dm.fc4.weight, fc4_b=dm.fc4.bias)
             # host-side bound check, once per weight version: table and conv weights below 2^15 in magnitude -> the two big
             # convolution GEMMs may use the fp16 two-term split (their other operand is a tanh output)
-            mx = max(float(self.word_embeddings.table.detach().abs().max()), float(dm.conv_d1.weight.detach().abs().max()),
-                     float(dm.conv_d2.weight.detach().abs().max()), float(dm.conv_q.weight.detach().abs().max()))
-            pk = lib.Packed(lib.DuetWeights, t, dict(self._dims, bounded=int(mx < 32768.0)))
-            E, NF = self.word_embeddings.table.shape[1], self._dims["NF"]
-            if mx < 32768.0 and self.fuse_document_branch and NF <= 320 and NF % 4 == 0 and E % 4 == 0 and self._dims["pool"] <= 5:
-                # operands of the fused document-branch kernel (csrc/duet_fused.hip): conv_d1 / conv_d2 zero-padded to 320 filter rows and
-                # a multiple of 32 in k, split into two fp16 terms and re-ordered into MFMA fragments, once per weight version
-                def fragments(w2d, kp=None):
-                    rows, k = w2d.shape
-                    kp = (k + 31) // 32 * 32 if kp is None else kp
-                    pad = torch.zeros(320, kp, device=w2d.device, dtype=torch.float32)
-                    pad[:rows, :k] = w2d
-                    planes = torch.stack(lib.split_f16x2(pad, kp))                      # [2 terms, 320, kp] int16
-                    return planes.view(2, 20, 16, kp // 32, 4, 8).permute(3, 1, 0, 4, 2, 5).contiguous(), kp
-                pk.keep["fw1"], k1p = fragments(pk.keep["convd1_w"].reshape(NF, 3 * E))
-                pk.keep["fw2"], _ = fragments(pk.keep["convd2_w"].reshape(NF, NF), 320)   # GEMM 2 always runs its 10 k-steps
-                pk.struct.fw1, pk.struct.fw2, pk.struct.K1P = pk.keep["fw1"].data_ptr(), pk.keep["fw2"].data_ptr(), k1p
-                if self.table_planes:
-                    EPT = (E + 63) // 64 * 64            # an even number of 32-element column chunks
-                    wc = torch.zeros(NF, 3, EPT, device=pk.keep["convd1_w"].device, dtype=torch.float32)
-                    wc[:, :, :E] = pk.keep["convd1_w"].reshape(NF, 3, E)
-                    wc = wc.view(NF, 3, EPT // 32, 32).permute(0, 2, 1, 3).reshape(NF, 3 * EPT)       # k = (chunk, tap, element)
-                    pk.keep["fw1c"], _ = fragments(wc, 3 * EPT)
-                    pk.keep["ftable"] = torch.stack(lib.split_f16x2(self.word_embeddings.table, EPT), 1).contiguous()   # [V, 2, EPT]
-                    pk.struct.fw1c, pk.struct.ftable, pk.struct.EPT = pk.keep["fw1c"].data_ptr(), pk.keep["ftable"].data_ptr(), EPT
-            EP = (max(E, NF) + 7) // 8 * 8
-            if mx < 32768.0 and self.presplit_operands and EP <= NF + 8 and EP - E < 8:
-                # fp16 term planes of the table and of the two big conv weights, split once per weight version (122 MB at V = 100 000)
-                planes = dict(zip(("table_h1", "table_h2"), lib.split_f16x2(self.word_embeddings.table, EP)))
-                planes.update(zip(("convd1_h1", "convd1_h2"), lib.split_f16x2(pk.keep["convd1_w"].reshape(NF * 3, E), EP)))
-                planes.update(zip(("convd2_h1", "convd2_h2"), lib.split_f16x2(pk.keep["convd2_w"], EP)))
-                for k, v in planes.items():
-                    pk.keep[k] = v
-                    setattr(pk.struct, k, v.data_ptr())
-                pk.struct.EP = EP
+            bounded = split_bounded(self.word_embeddings.table, dm.conv_d1.weight, dm.conv_d2.weight, dm.conv_q.weight)
+            pk = lib.Packed(lib.DuetWeights, t, dict(self._dims, bounded=int(bounded)))
+            attach_document_fragments(pk, self.word_embeddings.table, fuse=self.fuse_document_branch, table_planes=self.table_planes,
+                                      presplit=self.presplit_operands)
             return pk
         params = [p for n, p in self.named_parameters() if not n.startswith("word_embeddings")] + [self.word_embeddings.table]
         return self._pack.get(params, build)

@@ -339,6 +339,13 @@ size_t nir_duet_workspace_bytes(int B, int N, int QL, int DL, int E, const nir_d
 int nir_duet_score(const int64_t* q_ids, const int64_t* d_ids, int B, int N, int QL, int DL,
                    const float* table, int64_t V, int E, const nir_duet_weights* w /*host*/, void* workspace,
                    size_t workspace_bytes, float* scores, float* local_out, float* dist_out, nir_stream_t stream);
+/* The document side of nir_duet_score on its own (conv_d1 -> tanh -> max-pool -> conv_d2 -> tanh -> Hadamard with qv -> fc2 over positions ->
+ * tanh): the caller supplies the query vector qv [B, NF] (what fc1 gives in nir_duet_score) and receives m1 [B*N, NF].  Same argument checks,
+ * dispatch and launches as that part of nir_duet_score; the workspace holds only the branch's intermediates. */
+size_t nir_duet_document_workspace_bytes(int B, int N, int DL, int E, const nir_duet_weights* w /*host*/);
+int nir_duet_document_branch(const int64_t* d_ids, int B, int N, int DL, const float* table, int64_t V, int E,
+                             const nir_duet_weights* w /*host*/, const float* qv /*[B, NF]*/, void* workspace, size_t workspace_bytes,
+                             float* m1 /*[B*N, NF]*/, nir_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * DSSM  (neuroir/rankers/dssm.py:33-63) and CDSSM (neuroir/rankers/cdssm.py:42-77):  score[b,n] = cos(rep(q_b), rep(d_bn))
