@@ -550,6 +550,14 @@ class Packed(object):
     def ref(self):
         return C.byref(self.struct)
 
+    def without(self, *fields):
+        """a copy of the struct with those pointer fields null -- the same pack in an entry's plain form; the entry takes C.byref() of it, and
+        the caller holds the copy until the call is enqueued (the tensors behind the other pointers stay with this pack)"""
+        plain = type(self.struct).from_buffer_copy(self.struct)
+        for f in fields:
+            setattr(plain, f, None)
+        return plain
+
 
 # bumped whenever any PackCache rebuilds (= the only moment a superseded pack can be FREED): a hipGraph captured at epoch e references live packs
 # for as long as the epoch is still e, whatever happened to the parameters meanwhile (graph_runner.PredictGraphCache's optimistic replay)

@@ -662,6 +662,44 @@ class CARS(nn.Module, lib.IdCheck):
             out["ranking_loss"] = loss[0]
         return out
 
+    def _need_recommender(self, states):
+        if self.no_recommender:
+            raise RuntimeError("decode needs the recommender (turn_recommender_off=False)")
+        assert all(s is not None for s in states)
+
+    def _decode_inputs(self, what, states, batch_size, session_len, encoded_source, source_len, session_attns, src_dict, tgt_dict, tgt2src):
+        """What decode, decode_beam, decode_sample and score_candidates prepare alike (`what`: the name in the messages): the initial states as
+        [Bd, HD] rows, Bd = batch_size x session_len; the memory bank rows and lengths of all batch_size x (session_len + 1) queries; `rowmap`,
+        decode row -> its source row; the session attentions side by side; the target -> source table (given, or suggest.tgt2src_lut); the packed
+        decoder weights and the embedding table -> a dict of them."""
+        lib.require_device(*states, encoded_source, source_len)
+        dec_h, dec_c = (s.reshape(-1, s.shape[-1]).float().contiguous() for s in states)
+        B, SD = int(batch_size), int(session_len)
+        Bd = B * SD
+        if dec_h.shape[0] != Bd:
+            raise RuntimeError("%s: %d initial states for %d x %d decode rows" % (what, dec_h.shape[0], B, SD))
+        dev = dec_h.device
+        enc = encoded_source.float().contiguous()
+        rows_src, QL = enc.shape[0], enc.shape[1]
+        lens = lib.ids64(source_len.reshape(-1))
+        if rows_src != B * (SD + 1) or lens.numel() != rows_src:
+            raise RuntimeError("%s: encoded_source must hold batch_size*(session_len+1) query rows" % what)
+        i = torch.arange(Bd, device=dev)
+        rowmap = ((i // SD) * (SD + 1) + i % SD).contiguous()                       # the reference's [:, :-1] selection
+        cat = [a for a in session_attns if a is not None]
+        session_cat = torch.cat(cat, 2).reshape(rows_src, -1).float().contiguous() if cat else None
+        if tgt2src is None:
+            tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, self.token_prob_predictor2.weight.shape[0], dev)
+        return dict(dec_h=dec_h, dec_c=dec_c, B=B, SD=SD, Bd=Bd, dev=dev, enc=enc, rows_src=rows_src, QL=QL, lens=lens, rowmap=rowmap,
+                    session_cat=session_cat, tgt2src=tgt2src, w=self._decoder_weights(), table=self.embedder.word_embeddings.table)
+
+    @staticmethod
+    def _decode_c_args(c, max_len):
+        """the arguments the three decode entries share, states to decoder weights"""
+        t = c["table"]
+        return [lib.ptr(c["dec_h"]), lib.ptr(c["dec_c"]), lib.ptr(c["enc"]), lib.ptr(c["lens"]), c["rows_src"], c["QL"], lib.ptr(c["rowmap"]), c["Bd"],
+                lib.ptr(c["session_cat"]), lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(c["tgt2src"]), BOS, max_len, c["w"].ref()]
+
     def decode(self, states, max_len, src_dict, tgt_dict, batch_size, session_len, use_cuda, encoded_source, source_len,
                session_attns, tgt2src=None):
         """cars.py:706-791 (greedy): -> {'predictions': LongTensor [batch_size, session_len, max_len]} in target-vocabulary ids.
@@ -670,36 +708,15 @@ class CARS(nn.Module, lib.IdCheck):
         src_dict[word]); here that mapping is ONE device lookup table `tgt2src` [V_tgt] (built from the two dictionaries on
         first use and cached; identity when no dictionaries are given)."""
         self._check_eval()
-        if self.no_recommender:
-            raise RuntimeError("decode needs the recommender (turn_recommender_off=False)")
-        assert all(s is not None for s in states)
+        self._need_recommender(states)
         L = lib.load()
-        dec_h, dec_c = (s.reshape(-1, s.shape[-1]).float().contiguous() for s in states)
-        B, SD = int(batch_size), int(session_len)
-        Bd = B * SD
-        if dec_h.shape[0] != Bd:
-            raise RuntimeError("decode: %d initial states for %d x %d decode rows" % (dec_h.shape[0], B, SD))
-        dev = dec_h.device
-        enc = encoded_source.float().contiguous()
-        rows_src, QL = enc.shape[0], enc.shape[1]
-        lens = lib.ids64(source_len.reshape(-1))
-        if rows_src != B * (SD + 1) or lens.numel() != rows_src:
-            raise RuntimeError("decode: encoded_source must hold batch_size*(session_len+1) query rows")
-        i = torch.arange(Bd, device=dev)
-        rowmap = ((i // SD) * (SD + 1) + i % SD).contiguous()                       # the reference's [:, :-1] selection
-        cat = [a for a in session_attns if a is not None]
-        session_cat = torch.cat(cat, 2).reshape(rows_src, -1).float().contiguous() if cat else None
-        if tgt2src is None:
-            tgt2src = self._tgt2src(src_dict, tgt_dict, dev)
-        w = self._decoder_weights()
-        table = self.embedder.word_embeddings.table
-        ws = lib.workspace(L.nir_cars_decode_workspace_bytes(rows_src, Bd, QL, w.ref()), dev)
-        preds = torch.empty(Bd, int(max_len), dtype=torch.int64, device=dev)
-        lib.check(L.nir_cars_decode_greedy(lib.ptr(dec_h), lib.ptr(dec_c), lib.ptr(enc), lib.ptr(lens), rows_src, QL, lib.ptr(rowmap), Bd,
-                                           lib.ptr(session_cat), lib.ptr(table), table.shape[0], table.shape[1], lib.ptr(tgt2src), BOS,
-                                           int(max_len), w.ref(), lib.ptr(ws), ws.numel(), lib.ptr(preds), lib.stream()),
+        c = self._decode_inputs("decode", states, batch_size, session_len, encoded_source, source_len, session_attns, src_dict, tgt_dict, tgt2src)
+        Bd, dev, max_len = c["Bd"], c["dev"], int(max_len)
+        ws = lib.workspace(L.nir_cars_decode_workspace_bytes(c["rows_src"], Bd, c["QL"], c["w"].ref()), dev)
+        preds = torch.empty(Bd, max_len, dtype=torch.int64, device=dev)
+        lib.check(L.nir_cars_decode_greedy(*self._decode_c_args(c, max_len), lib.ptr(ws), ws.numel(), lib.ptr(preds), lib.stream()),
                   "nir_cars_decode_greedy")
-        return {"predictions": preds.view(B, SD, int(max_len))}
+        return {"predictions": preds.view(c["B"], c["SD"], max_len)}
 
     def decode_beam(self, states, max_len, beam_size, src_dict, tgt_dict, batch_size, session_len, encoded_source, source_len, session_attns,
                     tgt2src=None, return_backptr=False):
@@ -708,44 +725,21 @@ class CARS(nn.Module, lib.IdCheck):
         'scores': [batch_size, session_len, W] (sum of the tokens' log-probabilities, frozen at EOS), 'lengths': LongTensor [batch_size,
         session_len, W]} (+ 'backptr': IntTensor [max_len, Bd, W] on request).  The inputs of decode(); nothing is repeated here: ONE C call."""
         self._check_eval()
-        if self.no_recommender:
-            raise RuntimeError("decode needs the recommender (turn_recommender_off=False)")
-        assert all(s is not None for s in states)
-        lib.require_device(*states)
+        self._need_recommender(states)
         L = lib.load()
-        dec_h, dec_c = (s.reshape(-1, s.shape[-1]).float().contiguous() for s in states)
-        B, SD, W, max_len = int(batch_size), int(session_len), int(beam_size), int(max_len)
-        Bd = B * SD
-        if dec_h.shape[0] != Bd:
-            raise RuntimeError("decode: %d initial states for %d x %d decode rows" % (dec_h.shape[0], B, SD))
-        dev = dec_h.device
-        enc = encoded_source.float().contiguous()
-        rows_src, QL = enc.shape[0], enc.shape[1]
-        lens = lib.ids64(source_len.reshape(-1))
-        if rows_src != B * (SD + 1) or lens.numel() != rows_src:
-            raise RuntimeError("decode: encoded_source must hold batch_size*(session_len+1) query rows")
+        c = self._decode_inputs("decode", states, batch_size, session_len, encoded_source, source_len, session_attns, src_dict, tgt_dict, tgt2src)
+        Bd, dev, W, max_len = c["Bd"], c["dev"], int(beam_size), int(max_len)
         suggest.check_beam_size(W, self.token_prob_predictor2.weight.shape[0])
-        i = torch.arange(Bd, device=dev)
-        rowmap = ((i // SD) * (SD + 1) + i % SD).contiguous()                       # the reference's [:, :-1] selection
-        cat = [a for a in session_attns if a is not None]
-        session_cat = torch.cat(cat, 2).reshape(rows_src, -1).float().contiguous() if cat else None
-        if tgt2src is None:
-            tgt2src = self._tgt2src(src_dict, tgt_dict, dev)
-        w = self._decoder_weights()
         # the beam's generator reads nir_seq2seq_pack_gen_frag's fragments of token_prob_predictor2 (any P % 32 == 0), a pack of its own next to
         # the greedy arg-max's pred2_frag
         frag = suggest.gen_frag_pack(self, self.token_prob_predictor2.weight, Bd * W)
-        table = self.embedder.word_embeddings.table
         out = suggest.beam_outputs(Bd, W, max_len, dev, return_backptr)
         if Bd > 0 and max_len > 0:
-            ws = lib.workspace(L.nir_beam_cars_decode_workspace_bytes(rows_src, Bd, QL, W, max_len, w.ref(), int(frag is not None)), dev)
-            lib.check(L.nir_beam_cars_decode(lib.ptr(dec_h), lib.ptr(dec_c), lib.ptr(enc), lib.ptr(lens), rows_src, QL, lib.ptr(rowmap), Bd,
-                                             lib.ptr(session_cat), lib.ptr(table), table.shape[0], table.shape[1], lib.ptr(tgt2src), BOS, max_len,
-                                             w.ref(), lib.ptr(frag), W, lib.ptr(ws), ws.numel(), lib.ptr(out["predictions"]), lib.ptr(out["scores"]),
-                                             lib.ptr(out["lengths"]), lib.ptr(out.get("backptr")), lib.stream()), "nir_beam_cars_decode")
-        out["predictions"], out["scores"], out["lengths"] = (out["predictions"].view(B, SD, W, max_len), out["scores"].view(B, SD, W),
-                                                             out["lengths"].view(B, SD, W))
-        return out
+            ws = lib.workspace(L.nir_beam_cars_decode_workspace_bytes(c["rows_src"], Bd, c["QL"], W, max_len, c["w"].ref(), int(frag is not None)), dev)
+            lib.check(L.nir_beam_cars_decode(*self._decode_c_args(c, max_len), lib.ptr(frag), W, lib.ptr(ws), ws.numel(), lib.ptr(out["predictions"]),
+                                             lib.ptr(out["scores"]), lib.ptr(out["lengths"]), lib.ptr(out.get("backptr")), lib.stream()),
+                      "nir_beam_cars_decode")
+        return suggest.beam_view(out, c["B"], c["SD"])
 
     # decode_sample: the fused generator at every row count -- it wins outside the rounds' spreads at 384, 768 and 1152 sample rows, with and
     # without top_k (P = 256: a row block's fragments are a quarter of a K = 1024 decoder's; DESIGN.md section 29)
@@ -759,45 +753,22 @@ class CARS(nn.Module, lib.IdCheck):
         repeated behind the first EOS), 'token_logprobs': [batch_size, session_len, N, max_len], 'scores': [batch_size, session_len, N],
         'lengths': LongTensor [batch_size, session_len, N]}.  Nothing is repeated here: ONE C call; sample row n Bd + i reads the memory bank,
         length and session term of decode row i.  The switches are suggest.sample_fused's; there is no row cap (`fuse_sample_max_rows = None`)."""
-        VT = self.token_prob_predictor2.weight.shape[0]
-        N, K, tau, seed = suggest.check_sample_args(self, num_samples, temperature, top_k, seed, VT)
-        if self.no_recommender:
-            raise RuntimeError("decode needs the recommender (turn_recommender_off=False)")
-        assert all(s is not None for s in states)
-        lib.require_device(*states)
+        N, K, tau, seed = suggest.check_sample_args(self, num_samples, temperature, top_k, seed, self.token_prob_predictor2.weight.shape[0])
+        self._need_recommender(states)
         L = lib.load()
-        dec_h, dec_c = (s.reshape(-1, s.shape[-1]).float().contiguous() for s in states)
-        B, SD, max_len = int(batch_size), int(session_len), int(max_len)
-        Bd = B * SD
-        if dec_h.shape[0] != Bd:
-            raise RuntimeError("decode: %d initial states for %d x %d decode rows" % (dec_h.shape[0], B, SD))
-        dev = dec_h.device
-        enc = encoded_source.float().contiguous()
-        rows_src, QL = enc.shape[0], enc.shape[1]
-        lens = lib.ids64(source_len.reshape(-1))
-        if rows_src != B * (SD + 1) or lens.numel() != rows_src:
-            raise RuntimeError("decode: encoded_source must hold batch_size*(session_len+1) query rows")
-        i = torch.arange(Bd, device=dev)
-        rowmap = ((i // SD) * (SD + 1) + i % SD).contiguous()                       # the reference's [:, :-1] selection
-        cat = [a for a in session_attns if a is not None]
-        session_cat = torch.cat(cat, 2).reshape(rows_src, -1).float().contiguous() if cat else None
-        if tgt2src is None:
-            tgt2src = self._tgt2src(src_dict, tgt_dict, dev)
-        w = self._decoder_weights()
+        c = self._decode_inputs("decode", states, batch_size, session_len, encoded_source, source_len, session_attns, src_dict, tgt_dict, tgt2src)
+        Bd, dev, max_len = c["Bd"], c["dev"], int(max_len)
         frag = suggest.gen_frag_pack(self, self.token_prob_predictor2.weight, Bd * N, attr="_pgen_sample", wanted=suggest.sample_fused(self, Bd * N, K))
-        table = self.embedder.word_embeddings.table
         out = suggest.sample_outputs(Bd, N, max_len, dev)
         if Bd > 0 and max_len > 0:
-            nb = L.nir_sample_cars_decode_workspace_bytes(rows_src, Bd, QL, N, K, max_len, w.ref(), int(frag is not None))
+            nb = L.nir_sample_cars_decode_workspace_bytes(c["rows_src"], Bd, c["QL"], N, K, max_len, c["w"].ref(), int(frag is not None))
             if nb == 0:
                 raise ValueError("CARS.decode_sample: the shapes are outside the entry's range (nir_sample_cars_decode)")
             ws = lib.workspace(nb, dev)
-            lib.check(L.nir_sample_cars_decode(lib.ptr(dec_h), lib.ptr(dec_c), lib.ptr(enc), lib.ptr(lens), rows_src, QL, lib.ptr(rowmap), Bd,
-                                               lib.ptr(session_cat), lib.ptr(table), table.shape[0], table.shape[1], lib.ptr(tgt2src), BOS, max_len,
-                                               w.ref(), lib.ptr(frag), N, K, 1.0 / tau, seed, lib.ptr(ws), ws.numel(), lib.ptr(out["predictions"]),
-                                               lib.ptr(out["token_logprobs"]), lib.ptr(out["scores"]), lib.ptr(out["lengths"]), lib.stream()),
-                      "nir_sample_cars_decode")
-        return suggest.sample_view(out, B, SD)
+            lib.check(L.nir_sample_cars_decode(*self._decode_c_args(c, max_len), lib.ptr(frag), N, K, 1.0 / tau, seed, lib.ptr(ws), ws.numel(),
+                                               lib.ptr(out["predictions"]), lib.ptr(out["token_logprobs"]), lib.ptr(out["scores"]),
+                                               lib.ptr(out["lengths"]), lib.stream()), "nir_sample_cars_decode")
+        return suggest.sample_view(out, c["B"], c["SD"])
 
     # score_candidates: nir_tf_attend's fused form where the shape has one.  False: its plain form through the debug tunable exact_f32, set around
     # that one call -- for tests and tools, which run with NIR_DEBUG_TUNABLES=1; a product process keeps the switches frozen and refuses it
@@ -831,28 +802,16 @@ class CARS(nn.Module, lib.IdCheck):
         row bookkeeping -> a dict of what the two later parts read"""
         if self.training:
             raise NotImplementedError("HIP CARS.score_candidates runs in eval mode")
-        if self.no_recommender:
-            raise RuntimeError("decode needs the recommender (turn_recommender_off=False)")
-        assert all(s is not None for s in states)
-        table = self.embedder.word_embeddings.table
-        B, SD = int(batch_size), int(session_len)
+        self._need_recommender(states)
         VT = self.token_prob_predictor2.weight.shape[0]
         rnn = self.decoder.decoder.rnn
-        h_all, cand = suggest.candidate_front(self, states, candidate_seq, candidate_rep, src_dict, tgt_dict, tgt2src, B, SD, table, rnn, VT)
-        lib.require_device(encoded_source, source_len)
-        dev = h_all.device
-        Bd, N, T = B * SD, int(cand.shape[2]), int(cand.shape[3]) - 1
-        enc = encoded_source.float().contiguous()
-        rows_src, QL, DQ = enc.shape
-        lens = lib.ids64(source_len.reshape(-1))
-        if rows_src != B * (SD + 1) or lens.numel() != rows_src:
-            raise RuntimeError("score_candidates: encoded_source must hold batch_size*(session_len+1) query rows")
-        i = torch.arange(Bd, device=dev)
-        rowmap = ((i // SD) * (SD + 1) + i % SD).contiguous()                       # the reference's [:, :-1] selection
-        cat = [a for a in session_attns if a is not None]
-        session_cat = torch.cat(cat, 2).reshape(rows_src, -1).float().contiguous() if cat else None
-        return dict(h_all=h_all, cand=cand, enc=enc, lens=lens, rowmap=rowmap, session_cat=session_cat, w=self._decoder_weights(), B=B, SD=SD, Bd=Bd,
-                    N=N, T=T, G=N * T, R=Bd * N * T, rows_src=rows_src, QL=QL, DQ=DQ, HD=int(rnn.hidden_size))
+        h_all, cand = suggest.candidate_front(self, states, candidate_seq, candidate_rep, src_dict, tgt_dict, tgt2src, batch_size, session_len,
+                                              self.embedder.word_embeddings.table, rnn, VT)
+        c = self._decode_inputs("score_candidates", states, batch_size, session_len, encoded_source, source_len, session_attns, src_dict, tgt_dict,
+                                tgt2src)
+        N, T = int(cand.shape[2]), int(cand.shape[3]) - 1
+        c.update(h_all=h_all, cand=cand, N=N, T=T, G=N * T, R=c["Bd"] * N * T, DQ=c["enc"].shape[2], HD=int(rnn.hidden_size))
+        return c
 
     def _score_banks(self, c):
         """the two banks over every source row, once per call (nir_cars_decode_greedy builds the same two): memory bank encoded_source
@@ -892,13 +851,3 @@ class CARS(nn.Module, lib.IdCheck):
             p1.view(Bd, G, P).add_(sess.unsqueeze(1))
         frag = suggest.gen_frag_pack(self, self.token_prob_predictor2.weight, 0, attr="_pgen_score")
         return suggest.score_rows(self, p1.view(c["B"], c["SD"], c["N"], c["T"], P), c["cand"], w.keep["pred2_w"], None, frag)
-
-    def _tgt2src(self, src_dict, tgt_dict, dev):
-        if src_dict is None or tgt_dict is None:
-            return None
-        key = (id(src_dict), id(tgt_dict), len(src_dict), len(tgt_dict), str(dev))
-        if getattr(self, "_lut_key", None) != key:
-            n = self.token_prob_predictor2.weight.shape[0]
-            lut = [int(src_dict[tgt_dict[i]]) if i < len(tgt_dict) else 0 for i in range(n)]
-            self._lut, self._lut_key = torch.tensor(lut, dtype=torch.int64, device=dev), key
-        return self._lut

@@ -27,7 +27,7 @@ class _PlainDecoderParams(nn.Module):
         self.rnn = nn.LSTM(emsize, nhid, 1, batch_first=True)
 
 
-class M_MATCH_TENSOR(nn.Module, lib.IdCheck):
+class M_MATCH_TENSOR(nn.Module, lib.IdCheck, suggest.PlainSuggestions):
     def __init__(self, args):
         super().__init__()
         if args.rnn_type != "LSTM" or not args.bidirection or args.nlayers != 1:
@@ -193,38 +193,3 @@ class M_MATCH_TENSOR(nn.Module, lib.IdCheck):
         scores = train_head(self, q, d, pq, pd).view(B, S, N)
         return {"ranking_loss": A.bce_with_logits(scores, document_label.float()),
                 "suggestion_loss": suggest.suggestion_loss(self, h_steps, c_steps, target_rep, target_seq)}
-
-    def decode(self, states, max_len, src_dict, tgt_dict, batch_size, session_len, use_cuda=True, tgt2src=None, **kwargs):
-        """mmtensor.py:281-325 (greedy, decoder without attention) -> {'predictions': LongTensor [batch_size, session_len, max_len]}."""
-        self._check_eval()
-        return suggest.greedy_decode(self, states, max_len, src_dict, tgt_dict, batch_size, session_len, self.embedder.word_embeddings.table,
-                                     self.decoder.decoder.rnn, self.generator, tgt2src)
-
-    fuse_generator_topk = True               # decode_beam: generator + bias + (lse, top-W) in one kernel (no [Bd W, VT] logits)
-
-    def decode_beam(self, states, max_len, beam_size, src_dict, tgt_dict, batch_size, session_len, use_cuda=True, tgt2src=None, return_backptr=False,
-                    **kwargs):
-        """Beam search of width `beam_size` with the arguments of decode() (include/neuroir_session_beam.h) ->
-        {'predictions': LongTensor [batch_size, session_len, W, max_len], 'scores': [batch_size, session_len, W], 'lengths': LongTensor
-        [batch_size, session_len, W]}, best beam first."""
-        self._check_eval()
-        return suggest.beam_decode(self, states, max_len, beam_size, src_dict, tgt_dict, batch_size, session_len, self.embedder.word_embeddings.table,
-                                   self.decoder.decoder.rnn, self.generator, tgt2src, return_backptr)
-
-    @torch.no_grad()
-    def decode_sample(self, states, max_len, num_samples, src_dict, tgt_dict, batch_size, session_len, temperature=1.0, top_k=0, seed=0, use_cuda=True,
-                      tgt2src=None, **kwargs):
-        """`num_samples` i.i.d. draws per decode row with the arguments of decode() (include/neuroir_session_sample.h; the
-        rules are Seq2seq.decode_sample's) -> {'predictions': LongTensor [batch_size, session_len, N, max_len], 'token_logprobs': [batch_size,
-        session_len, N, max_len], 'scores': [batch_size, session_len, N], 'lengths': LongTensor [batch_size, session_len, N]}, in sample order."""
-        return suggest.sample_decode(self, states, max_len, num_samples, temperature, top_k, seed, src_dict, tgt_dict, batch_size, session_len,
-                                     self.embedder.word_embeddings.table, self.decoder.decoder.rnn, self.generator, tgt2src)
-
-    @torch.no_grad()
-    def score_candidates(self, states, candidate_seq, src_dict, tgt_dict, batch_size, session_len, candidate_rep=None, tgt2src=None):
-        """log P(candidate | session prefix) for N candidate next queries per decode row, with the states of decode():
-        candidate_seq [B, S-1, N, TL] target-vocabulary ids, BOS first, PAD behind the end; candidate_rep: the embedder ids fed to the decoder
-        (default: what decode() feeds back) -> {'token_logprobs': [B, S-1, N, TL-1], 'scores': [B, S-1, N], 'lengths': LongTensor [B, S-1, N]}
-        by section 26's rules.  Candidate row b (S-1) + j starts from row b (S-1) + j of `states`, like decode()'s output rows."""
-        return suggest.plain_candidate_rows(self, states, candidate_seq, candidate_rep, src_dict, tgt_dict, batch_size, session_len,
-                                            self.embedder.word_embeddings.table, self.decoder.decoder.rnn, self.generator, tgt2src)

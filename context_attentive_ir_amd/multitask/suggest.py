@@ -164,29 +164,44 @@ def plain_fold(owner, table, dec_rnn, t, p, H, dev):
                      + [getattr(owner, "fold_decoder_step", True)], build)
 
 
+class PlainInputs(object):
+    """What greedy_decode, beam_decode and sample_decode prepare alike for a decoder without attention: the initial states as [Bd, H] rows (Bd =
+    batch_size x session_len, else the row-count error), the generator's weight and bias, the target -> source table (given, or tgt2src_lut),
+    the embedding table as fp32, the four LSTM tensors and plain_fold's pair (or None).  The tensors stay alive with the record."""
+
+    def __init__(self, owner, states, src_dict, tgt_dict, batch_size, session_len, table, dec_rnn, generator, tgt2src):
+        self.dec_h, self.dec_c = (s.reshape(-1, s.shape[-1]).float().contiguous() for s in states)
+        self.B, self.SD = int(batch_size), int(session_len)
+        self.Bd, self.H = self.dec_h.shape
+        if self.Bd != self.B * self.SD:
+            raise RuntimeError("decode: %d initial states for %d x %d decode rows" % (self.Bd, batch_size, session_len))
+        self.dev = self.dec_h.device
+        self.gw, self.gb = generator.weight.detach().float().contiguous(), generator.bias.detach().float().contiguous()
+        self.VT = self.gw.shape[0]
+        self.tgt2src = tgt2src_lut(owner, src_dict, tgt_dict, self.VT, self.dev) if tgt2src is None else tgt2src
+        self.t = table.detach().float().contiguous()
+        self.p = [getattr(dec_rnn, n).detach().float().contiguous() for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")]
+        self.fold = plain_fold(owner, table, dec_rnn, self.t, self.p, self.H, self.dev)
+
+    def c_args(self, max_len):
+        """the arguments the three plain entries share, states to fold pointers"""
+        t, fold = self.t, self.fold
+        return [lib.ptr(self.dec_h), lib.ptr(self.dec_c), self.Bd, self.H, lib.ptr(t), t.shape[0], t.shape[1]] + [lib.ptr(x) for x in self.p] + [
+            lib.ptr(self.gw), lib.ptr(self.gb), self.VT, lib.ptr(self.tgt2src), BOS, max_len, lib.ptr(fold[0]) if fold else None,
+            lib.ptr(fold[1]) if fold else None]
+
+
 def greedy_decode(owner, states, max_len, src_dict, tgt_dict, batch_size, session_len, table, dec_rnn, generator, tgt2src=None):
     """-> {'predictions': LongTensor [batch_size, session_len, max_len]} in target-vocabulary ids; `session_len` = decoded queries per
     session (the caller passes S-1, models/multitask.py:286)."""
     L = lib.load()
-    dec_h, dec_c = (s.reshape(-1, s.shape[-1]).float().contiguous() for s in states)
-    Bd, H = dec_h.shape
-    if Bd != int(batch_size) * int(session_len):
-        raise RuntimeError("decode: %d initial states for %d x %d decode rows" % (Bd, batch_size, session_len))
-    dev = dec_h.device
-    gw, gb = generator.weight.detach().float().contiguous(), generator.bias.detach().float().contiguous()
-    VT = gw.shape[0]
-    if tgt2src is None:
-        tgt2src = tgt2src_lut(owner, src_dict, tgt_dict, VT, dev)
-    t = table.detach().float().contiguous()
-    p = [getattr(dec_rnn, n).detach().float().contiguous() for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")]
-    fold = plain_fold(owner, table, dec_rnn, t, p, H, dev)
-    ws = lib.workspace(L.nir_decode_greedy_plain_workspace_bytes(Bd, H, VT), dev)
-    preds = torch.empty(Bd, int(max_len), dtype=torch.int64, device=dev)
-    lib.check(L.nir_decode_greedy_plain_folded(lib.ptr(dec_h), lib.ptr(dec_c), Bd, H, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(p[0]), lib.ptr(p[1]),
-                                               lib.ptr(p[2]), lib.ptr(p[3]), lib.ptr(gw), lib.ptr(gb), VT, lib.ptr(tgt2src), BOS, int(max_len),
-                                               lib.ptr(fold[0]) if fold else None, lib.ptr(fold[1]) if fold else None, lib.ptr(ws),
-                                               ws.numel(), lib.ptr(preds), lib.stream()), "nir_decode_greedy_plain_folded")
-    return {"predictions": preds.view(int(batch_size), int(session_len), int(max_len))}
+    c = PlainInputs(owner, states, src_dict, tgt_dict, batch_size, session_len, table, dec_rnn, generator, tgt2src)
+    max_len = int(max_len)
+    ws = lib.workspace(L.nir_decode_greedy_plain_workspace_bytes(c.Bd, c.H, c.VT), c.dev)
+    preds = torch.empty(c.Bd, max_len, dtype=torch.int64, device=c.dev)
+    lib.check(L.nir_decode_greedy_plain_folded(*c.c_args(max_len), lib.ptr(ws), ws.numel(), lib.ptr(preds), lib.stream()),
+              "nir_decode_greedy_plain_folded")
+    return {"predictions": preds.view(c.B, c.SD, max_len)}
 
 
 FUSE_TOPK_MAX_ROWS = 384     # beam rows up to which the fused generator + top-k is the default (DESIGN.md section 23: it wins at 384, loses at 768)
@@ -219,11 +234,21 @@ def gen_frag_pack(owner, weight, rows, attr="_pgen_beam", wanted=None):
     return cache.get([weight], build)
 
 
-def beam_outputs(Bd, W, max_len, dev, return_backptr):
+def beam_outputs(Bd, W, max_len, dev, return_backptr, QL=None):
+    """the output tensors of a beam entry over Bd decode rows; QL: the attention decoders' 'attentions' [Bd, W, max_len, QL] with them"""
     out = {"predictions": torch.empty(Bd, W, max_len, dtype=torch.int64, device=dev), "scores": torch.empty(Bd, W, dtype=torch.float32, device=dev),
            "lengths": torch.empty(Bd, W, dtype=torch.int64, device=dev)}
+    if QL is not None:
+        out["attentions"] = torch.empty(Bd, W, max_len, QL, dtype=torch.float32, device=dev)
     if return_backptr:
         out["backptr"] = torch.empty(max_len, Bd, W, dtype=torch.int32, device=dev)
+    return out
+
+
+def beam_view(out, B, SD):
+    """predictions, scores and lengths of a beam entry, [Bd, W, ...], viewed [B, SD, W, ...] in place ('backptr' stays [max_len, Bd, W])"""
+    for k in ("predictions", "scores", "lengths"):
+        out[k] = out[k].view((B, SD) + tuple(out[k].shape[1:]))
     return out
 
 
@@ -242,32 +267,17 @@ def beam_decode(owner, states, max_len, beam_size, src_dict, tgt_dict, batch_siz
         raise NotImplementedError("HIP %s.decode_beam runs in eval mode" % type(owner).__name__)
     lib.require_device(*states)
     L = lib.load()
-    dec_h, dec_c = (s.reshape(-1, s.shape[-1]).float().contiguous() for s in states)
-    Bd, H = dec_h.shape
-    if Bd != int(batch_size) * int(session_len):
-        raise RuntimeError("decode: %d initial states for %d x %d decode rows" % (Bd, batch_size, session_len))
-    dev = dec_h.device
+    c = PlainInputs(owner, states, src_dict, tgt_dict, batch_size, session_len, table, dec_rnn, generator, tgt2src)
     W, max_len = int(beam_size), int(max_len)
-    gw, gb = generator.weight.detach().float().contiguous(), generator.bias.detach().float().contiguous()
-    VT = gw.shape[0]
-    check_beam_size(W, VT)
-    if tgt2src is None:
-        tgt2src = tgt2src_lut(owner, src_dict, tgt_dict, VT, dev)
-    t = table.detach().float().contiguous()
-    p = [getattr(dec_rnn, n).detach().float().contiguous() for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")]
-    fold = plain_fold(owner, table, dec_rnn, t, p, H, dev)
-    frag = gen_frag_pack(owner, generator.weight, Bd * W)
-    out = beam_outputs(Bd, W, max_len, dev, return_backptr)
-    if Bd > 0 and max_len > 0:
-        ws = lib.workspace(L.nir_beam_plain_decode_workspace_bytes(Bd, H, VT, W, max_len, int(fold is not None), int(frag is not None)), dev)
-        lib.check(L.nir_beam_plain_decode(lib.ptr(dec_h), lib.ptr(dec_c), Bd, H, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(p[0]), lib.ptr(p[1]),
-                                          lib.ptr(p[2]), lib.ptr(p[3]), lib.ptr(gw), lib.ptr(gb), VT, lib.ptr(tgt2src), BOS, max_len,
-                                          lib.ptr(fold[0]) if fold else None, lib.ptr(fold[1]) if fold else None, lib.ptr(frag), W, lib.ptr(ws), ws.numel(),
-                                          lib.ptr(out["predictions"]), lib.ptr(out["scores"]), lib.ptr(out["lengths"]), lib.ptr(out.get("backptr")),
-                                          lib.stream()), "nir_beam_plain_decode")
-    B, SD = int(batch_size), int(session_len)
-    out["predictions"], out["scores"], out["lengths"] = out["predictions"].view(B, SD, W, max_len), out["scores"].view(B, SD, W), out["lengths"].view(B, SD, W)
-    return out
+    check_beam_size(W, c.VT)
+    frag = gen_frag_pack(owner, generator.weight, c.Bd * W)
+    out = beam_outputs(c.Bd, W, max_len, c.dev, return_backptr)
+    if c.Bd > 0 and max_len > 0:
+        ws = lib.workspace(L.nir_beam_plain_decode_workspace_bytes(c.Bd, c.H, c.VT, W, max_len, int(c.fold is not None), int(frag is not None)), c.dev)
+        lib.check(L.nir_beam_plain_decode(*c.c_args(max_len), lib.ptr(frag), W, lib.ptr(ws), ws.numel(), lib.ptr(out["predictions"]),
+                                          lib.ptr(out["scores"]), lib.ptr(out["lengths"]), lib.ptr(out.get("backptr")), lib.stream()),
+                  "nir_beam_plain_decode")
+    return beam_view(out, c.B, c.SD)
 
 
 def check_sample_args(owner, num_samples, temperature, top_k, seed, VT):
@@ -299,10 +309,14 @@ def sample_fused(owner, rows, top_k):
     return bool(on) and (cap is None or rows <= cap)
 
 
-def sample_outputs(Bd, N, max_len, dev):
-    return {"predictions": torch.empty(Bd, N, max_len, dtype=torch.int64, device=dev),
-            "token_logprobs": torch.empty(Bd, N, max_len, dtype=torch.float32, device=dev),
-            "scores": torch.empty(Bd, N, dtype=torch.float32, device=dev), "lengths": torch.empty(Bd, N, dtype=torch.int64, device=dev)}
+def sample_outputs(Bd, N, max_len, dev, QL=None):
+    """the output tensors of a sampling entry over Bd decode rows; QL: the attention decoders' 'attentions' [Bd, N, max_len, QL] with them"""
+    out = {"predictions": torch.empty(Bd, N, max_len, dtype=torch.int64, device=dev),
+           "token_logprobs": torch.empty(Bd, N, max_len, dtype=torch.float32, device=dev),
+           "scores": torch.empty(Bd, N, dtype=torch.float32, device=dev), "lengths": torch.empty(Bd, N, dtype=torch.int64, device=dev)}
+    if QL is not None:
+        out["attentions"] = torch.empty(Bd, N, max_len, QL, dtype=torch.float32, device=dev)
+    return out
 
 
 def sample_view(out, B, SD):
@@ -317,35 +331,64 @@ def sample_decode(owner, states, max_len, num_samples, temperature, top_k, seed,
     max_len], 'scores': [batch_size, session_len, N], 'lengths': LongTensor [batch_size, session_len, N]}.  The same fold cache as greedy_decode,
     a cached generator fragment pack of its own (`_pgen_sample`) under sample_fused's switches; the initial states are not repeated here --
     nir_sample_plain_decode does that."""
-    VT = generator.weight.shape[0]
-    N, K, tau, seed = check_sample_args(owner, num_samples, temperature, top_k, seed, VT)
+    N, K, tau, seed = check_sample_args(owner, num_samples, temperature, top_k, seed, generator.weight.shape[0])
     lib.require_device(*states)
     L = lib.load()
-    dec_h, dec_c = (s.reshape(-1, s.shape[-1]).float().contiguous() for s in states)
-    Bd, H = dec_h.shape
-    if Bd != int(batch_size) * int(session_len):
-        raise RuntimeError("decode: %d initial states for %d x %d decode rows" % (Bd, batch_size, session_len))
-    dev = dec_h.device
+    c = PlainInputs(owner, states, src_dict, tgt_dict, batch_size, session_len, table, dec_rnn, generator, tgt2src)
     max_len = int(max_len)
-    gw, gb = generator.weight.detach().float().contiguous(), generator.bias.detach().float().contiguous()
-    if tgt2src is None:
-        tgt2src = tgt2src_lut(owner, src_dict, tgt_dict, VT, dev)
-    t = table.detach().float().contiguous()
-    p = [getattr(dec_rnn, n).detach().float().contiguous() for n in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")]
-    fold = plain_fold(owner, table, dec_rnn, t, p, H, dev)
-    frag = gen_frag_pack(owner, generator.weight, Bd * N, attr="_pgen_sample", wanted=sample_fused(owner, Bd * N, K))
-    out = sample_outputs(Bd, N, max_len, dev)
-    if Bd > 0 and max_len > 0:
-        nb = L.nir_sample_plain_decode_workspace_bytes(Bd, H, VT, N, K, max_len, int(fold is not None), int(frag is not None))
+    frag = gen_frag_pack(owner, generator.weight, c.Bd * N, attr="_pgen_sample", wanted=sample_fused(owner, c.Bd * N, K))
+    out = sample_outputs(c.Bd, N, max_len, c.dev)
+    if c.Bd > 0 and max_len > 0:
+        nb = L.nir_sample_plain_decode_workspace_bytes(c.Bd, c.H, c.VT, N, K, max_len, int(c.fold is not None), int(frag is not None))
         if nb == 0:
             raise ValueError("%s.decode_sample: the shapes are outside the entry's range (nir_sample_plain_decode)" % type(owner).__name__)
-        ws = lib.workspace(nb, dev)
-        lib.check(L.nir_sample_plain_decode(lib.ptr(dec_h), lib.ptr(dec_c), Bd, H, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(p[0]), lib.ptr(p[1]),
-                                            lib.ptr(p[2]), lib.ptr(p[3]), lib.ptr(gw), lib.ptr(gb), VT, lib.ptr(tgt2src), BOS, max_len,
-                                            lib.ptr(fold[0]) if fold else None, lib.ptr(fold[1]) if fold else None, lib.ptr(frag), N, K, 1.0 / tau, seed,
-                                            lib.ptr(ws), ws.numel(), lib.ptr(out["predictions"]), lib.ptr(out["token_logprobs"]), lib.ptr(out["scores"]),
+        ws = lib.workspace(nb, c.dev)
+        lib.check(L.nir_sample_plain_decode(*c.c_args(max_len), lib.ptr(frag), N, K, 1.0 / tau, seed, lib.ptr(ws), ws.numel(),
+                                            lib.ptr(out["predictions"]), lib.ptr(out["token_logprobs"]), lib.ptr(out["scores"]),
                                             lib.ptr(out["lengths"]), lib.stream()), "nir_sample_plain_decode")
-    return sample_view(out, int(batch_size), int(session_len))
+    return sample_view(out, c.B, c.SD)
+
+
+class PlainSuggestions(object):
+    """decode / decode_beam / decode_sample / score_candidates of the two session models whose decoder has no attention (M_MATCH_TENSOR:
+    mmtensor.py:281-325; MNSRF: mnsrf.py:251-296): the class supplies `embedder`, `decoder.decoder.rnn`, `generator` and its own _check_eval."""
+
+    fuse_generator_topk = True               # decode_beam: generator + bias + (lse, top-W) in one kernel (no [Bd W, VT] logits)
+
+    def _plain_modules(self):
+        return self.embedder.word_embeddings.table, self.decoder.decoder.rnn, self.generator
+
+    def decode(self, states, max_len, src_dict, tgt_dict, batch_size, session_len, use_cuda=True, tgt2src=None, **kwargs):
+        """greedy, decoder without attention -> {'predictions': LongTensor [batch_size, session_len, max_len]}."""
+        self._check_eval()
+        return greedy_decode(self, states, max_len, src_dict, tgt_dict, batch_size, session_len, *self._plain_modules(), tgt2src)
+
+    def decode_beam(self, states, max_len, beam_size, src_dict, tgt_dict, batch_size, session_len, use_cuda=True, tgt2src=None, return_backptr=False,
+                    **kwargs):
+        """Beam search of width `beam_size` with the arguments of decode() (include/neuroir_session_beam.h) ->
+        {'predictions': LongTensor [batch_size, session_len, W, max_len], 'scores': [batch_size, session_len, W], 'lengths': LongTensor
+        [batch_size, session_len, W]}, best beam first."""
+        self._check_eval()
+        return beam_decode(self, states, max_len, beam_size, src_dict, tgt_dict, batch_size, session_len, *self._plain_modules(), tgt2src,
+                           return_backptr)
+
+    @torch.no_grad()
+    def decode_sample(self, states, max_len, num_samples, src_dict, tgt_dict, batch_size, session_len, temperature=1.0, top_k=0, seed=0, use_cuda=True,
+                      tgt2src=None, **kwargs):
+        """`num_samples` i.i.d. draws per decode row with the arguments of decode() (include/neuroir_session_sample.h; the
+        rules are Seq2seq.decode_sample's) -> {'predictions': LongTensor [batch_size, session_len, N, max_len], 'token_logprobs': [batch_size,
+        session_len, N, max_len], 'scores': [batch_size, session_len, N], 'lengths': LongTensor [batch_size, session_len, N]}, in sample order."""
+        return sample_decode(self, states, max_len, num_samples, temperature, top_k, seed, src_dict, tgt_dict, batch_size, session_len,
+                             *self._plain_modules(), tgt2src)
+
+    @torch.no_grad()
+    def score_candidates(self, states, candidate_seq, src_dict, tgt_dict, batch_size, session_len, candidate_rep=None, tgt2src=None):
+        """log P(candidate | session prefix) for N candidate next queries per decode row, with the states of decode():
+        candidate_seq [B, S-1, N, TL] target-vocabulary ids, BOS first, PAD behind the end; candidate_rep: the embedder ids fed to the decoder
+        (default: what decode() feeds back) -> {'token_logprobs': [B, S-1, N, TL-1], 'scores': [B, S-1, N], 'lengths': LongTensor [B, S-1, N]}
+        by section 26's rules.  Candidate row b (S-1) + j starts from row b (S-1) + j of `states`, like decode()'s output rows."""
+        return plain_candidate_rows(self, states, candidate_seq, candidate_rep, src_dict, tgt_dict, batch_size, session_len,
+                                    *self._plain_modules(), tgt2src)
 
 
 def bilstm_train(x, lens, lstm):

@@ -163,24 +163,38 @@ class ACG(Seq2seq):
         pred - VT of the row's dynamic dictionary), 'attentions': [B, max_len, QL] (the decoder's own attention)}.  The copy inputs are the
         reference's (`src_map` as a list of index tensors or the dense one-hot, `blank` / `fill`, `source_vocabs`) or the three index
         tensors (module docstring); `alignment` is unused, as in the reference's decode."""
-        name = type(self).__name__
-        B, QL, table = self._decode_ready("decode", source_rep, source_len)
-        if src_map_idx is None or ext2tgt is None or ext2src is None:
-            src_map_idx, ext2tgt, ext2src = self.copy_index(QL, src_map, blank, fill, source_vocabs, src_dict, tgt_dict)
-        idx, e2t, e2s = (lib.ids64(t).to(table.device).contiguous() for t in (src_map_idx, ext2tgt, ext2src))
-        CV = int(e2t.shape[1])
-        if tuple(idx.shape) != (B, QL) or tuple(e2t.shape) != (B, CV) or tuple(e2s.shape) != (B, CV):
-            raise ValueError("%s.decode: src_map_idx %s, ext2tgt %s, ext2src %s do not fit %d rows of width %d"
-                             % (name, tuple(idx.shape), tuple(e2t.shape), tuple(e2s.shape), B, QL))
-        cw = self._copy_weights()
-
-        def ws_bytes(size, B, QL, w):
-            nb = size(B, QL, CV, w.ref(), cw.ref())
-            if nb == 0:
-                raise ValueError("%s.decode: QL = %d / CV = %d outside the copy generator's range (QL <= 4096, 2 <= CV <= 1024)" % (name, QL, CV))
-            return nb
         return self._greedy(source_rep, source_len, max_len, src_dict, tgt_dict, tgt2src,
-                            extra=(cw.ref(), lib.ptr(idx), lib.ptr(e2t), lib.ptr(e2s), CV), ws_bytes=ws_bytes)
+                            extra=self._copy_extra("decode", src_dict, tgt_dict, src_map, blank, fill, source_vocabs, src_map_idx, ext2tgt, ext2src))
+
+    def _copy_maps(self, what, B, QL, src_dict, tgt_dict, src_map, blank, fill, source_vocabs, src_map_idx, ext2tgt, ext2src):
+        """the copy inputs of `what` (a method's name, for the messages) -> (src_map_idx [B, QL], ext2tgt [B, CV], ext2src [B, CV], CV) as int64 on
+        the model's device: the three index tensors where all are given, else copy_index of the reference's arguments; their shapes and the copy
+        generator's range are checked here"""
+        maps = (src_map_idx, ext2tgt, ext2src)
+        if any(t is None for t in maps):
+            maps = self.copy_index(QL, src_map, blank, fill, source_vocabs, src_dict, tgt_dict)
+        dev = self.embedder.word_embeddings.table.device
+        idx, e2t, e2s = (lib.ids64(t).to(dev).contiguous() for t in maps)
+        CV = int(e2t.shape[1])
+        name = type(self).__name__
+        if tuple(idx.shape) != (B, QL) or tuple(e2t.shape) != (B, CV) or tuple(e2s.shape) != (B, CV):
+            raise ValueError("%s.%s: src_map_idx %s, ext2tgt %s, ext2src %s do not fit %d rows of width %d"
+                             % (name, what, tuple(idx.shape), tuple(e2t.shape), tuple(e2s.shape), B, QL))
+        if not (1 <= QL <= 4096 and 2 <= CV <= 1024):
+            raise ValueError("%s.%s: QL = %d / CV = %d outside the copy generator's range (QL <= 4096, 2 <= CV <= 1024)" % (name, what, QL, CV))
+        return idx, e2t, e2s, CV
+
+    def _copy_extra(self, what, *copy_inputs):
+        """_copy_maps' arguments behind B and QL -> the `extra` of Seq2seq._greedy / _beam / _sample: (B, QL) -> ((CV,), the copy arguments of the
+        C entries); what the pointers refer to stays alive with the function"""
+        keep = []
+
+        def extra(B, QL):
+            idx, e2t, e2s, CV = self._copy_maps(what, B, QL, *copy_inputs)
+            cw = self._copy_weights()
+            keep.extend((idx, e2t, e2s, cw))                               # alive until the call is enqueued
+            return (CV,), (cw.ref(), lib.ptr(idx), lib.ptr(e2t), lib.ptr(e2s), CV)
+        return extra
 
     # ---- eval: scoring -------------------------------------------------------------------------------------------------------------
     def score_candidates(self, *args, **kwargs):
@@ -252,7 +266,6 @@ class ACG(Seq2seq):
                         src_map_idx, ext2tgt, ext2src):
         """score_extended in front of the generator: the checks, the copy maps, the encoder, the default decoder inputs, the decoder's cell over all
         B N sequences and _teacher_front -> the arguments of _score_extended_rows"""
-        name = type(self).__name__
         cand = lib.ids64(candidate_seq)
         if cand.dim() != 3 or cand.shape[0] != source_rep.shape[0] or cand.shape[2] < 2:
             raise ValueError("score_extended: candidate_seq must be [B, N, TL] with TL >= 2 (got %s)" % (tuple(cand.shape),))
@@ -260,21 +273,10 @@ class ACG(Seq2seq):
             raise ValueError("score_extended: candidate_rep %s does not match candidate_seq %s" % (tuple(candidate_rep.shape), tuple(cand.shape)))
         B, QL, table = self._decode_ready("score_extended", source_rep, source_len)
         lib.require_device(cand, candidate_rep)
-        maps = (src_map_idx, ext2tgt, ext2src)
-        if any(t is None for t in maps):
-            maps = self.copy_index(QL, src_map, blank, fill, source_vocabs, src_dict, tgt_dict)
+        idx, e2t, e2s, _ = self._copy_maps("score_extended", B, QL, src_dict, tgt_dict, src_map, blank, fill, source_vocabs, src_map_idx, ext2tgt, ext2src)
         dev = table.device
-        idx, e2t, e2s = (lib.ids64(t).to(dev).contiguous() for t in maps)
-        CV = int(e2t.shape[1])
-        if tuple(idx.shape) != (B, QL) or tuple(e2t.shape) != (B, CV) or tuple(e2s.shape) != (B, CV):
-            raise ValueError("%s.score_extended: src_map_idx %s, ext2tgt %s, ext2src %s do not fit %d rows of width %d"
-                             % (name, tuple(idx.shape), tuple(e2t.shape), tuple(e2s.shape), B, QL))
-        if not (1 <= QL <= 4096 and 2 <= CV <= 1024):
-            raise ValueError("%s.score_extended: QL = %d / CV = %d outside the copy generator's range (QL <= 4096, 2 <= CV <= 1024)" % (name, QL, CV))
         N, T = int(cand.shape[1]), int(cand.shape[2]) - 1
-        src, _ = self._clean_ids(source_rep, None, table.shape[0])
-        lens = lib.ids64(source_len)
-        state, bank = self._encode_state(src, lens)
+        lens, state, bank = self._encoded(source_rep, source_len, table)
         w = self._decoder_weights()
         VT, H = int(w.struct.VT), int(bank.shape[2])
         if candidate_rep is not None:
@@ -335,54 +337,10 @@ class ACG(Seq2seq):
         the memory bank are repeated.  ONE C call; neither logits nor a dense copy distribution is written (`fuse_generator_argmax = False`, and
         for top_k > 0 `fuse_generator_topk = False`: the plain generator forms; over the whole distribution the plain form is also the default
         beyond `fuse_sample_max_rows` decode rows)."""
-        name = type(self).__name__
-        VT = int(self.generator.weight.shape[0])
-        N, K, tau, seed = suggest.check_sample_args(self, num_samples, temperature, top_k, seed, VT)      # (its messages say decode_sample: the shared rules)
-        B, QL, table = self._decode_ready("sample_extended", source_rep, source_len)
-        maps = (src_map_idx, ext2tgt, ext2src)
-        if any(t is None for t in maps):
-            maps = self.copy_index(QL, src_map, blank, fill, source_vocabs, src_dict, tgt_dict)
-        dev = table.device
-        idx, e2t, e2s = (lib.ids64(t).to(dev).contiguous() for t in maps)
-        CV = int(e2t.shape[1])
-        if tuple(idx.shape) != (B, QL) or tuple(e2t.shape) != (B, CV) or tuple(e2s.shape) != (B, CV):
-            raise ValueError("%s.sample_extended: src_map_idx %s, ext2tgt %s, ext2src %s do not fit %d rows of width %d"
-                             % (name, tuple(idx.shape), tuple(e2t.shape), tuple(e2s.shape), B, QL))
-        if not (1 <= QL <= 4096 and 2 <= CV <= 1024):
-            raise ValueError("%s.sample_extended: QL = %d / CV = %d outside the copy generator's range (QL <= 4096, 2 <= CV <= 1024)" % (name, QL, CV))
-        L = lib.load()
-        w, cw = self._decoder_weights(), self._copy_weights()
-        src, _ = self._clean_ids(source_rep, None, table.shape[0])
-        lens = lib.ids64(source_len)
-        state, bank = self._encode_state(src, lens)
-        state = [s.repeat(N, 1).contiguous() for s in state]                  # row n B + b
-        ws_ref = w.ref()
-        fuse = self.fuse_generator_topk if K > 0 else (self.fuse_generator_argmax
-                                                       and B * N <= getattr(self, "fuse_sample_max_rows", suggest.FUSE_SAMPLE_MAX_ROWS))
-        if w.struct.gen_frag and not fuse:
-            plain = lib.Seq2seqDecoderWeights.from_buffer_copy(w.struct)      # the same pack without the fragment: the plain generator form
-            plain.gen_frag = None
-            ws_ref = lib.C.byref(plain)
-        if tgt2src is None:
-            tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, VT, dev)
-        t = table.detach().float().contiguous()
-        max_len = int(max_len)
-        out = {"predictions": torch.empty(B, N, max_len, dtype=torch.int64, device=dev),
-               "token_logprobs": torch.empty(B, N, max_len, dtype=torch.float32, device=dev),
-               "scores": torch.empty(B, N, dtype=torch.float32, device=dev), "lengths": torch.empty(B, N, dtype=torch.int64, device=dev),
-               "attentions": torch.empty(B, N, max_len, QL, dtype=torch.float32, device=dev)}
-        if B > 0 and max_len > 0:
-            entry = self._ACG_SAMPLE_ENTRY % self._ENTRY_CELL
-            nb = getattr(L, entry + "_workspace_bytes")(B, QL, CV, N, K, max_len, ws_ref, cw.ref())
-            if nb == 0:
-                raise ValueError("%s.sample_extended: the shapes are outside the entry's range (%s)" % (name, entry))
-            ws = lib.workspace(nb, dev)
-            args = [lib.ptr(s) for s in state] + [lib.ptr(bank), lib.ptr(lens), B, QL, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(tgt2src), BOS, max_len,
-                                                  ws_ref, cw.ref(), lib.ptr(idx), lib.ptr(e2t), lib.ptr(e2s), CV, N, K, 1.0 / tau, seed, lib.ptr(ws),
-                                                  ws.numel()]
-            args += [lib.ptr(out[k]) for k in ("predictions", "token_logprobs", "scores", "lengths", "attentions")] + [lib.stream()]
-            lib.check(getattr(L, entry)(*args), entry)
-        return out
+        return self._sample("sample_extended", source_rep, source_len, max_len, num_samples, temperature, top_k, seed, src_dict, tgt_dict, tgt2src,
+                            entry=self._ACG_SAMPLE_ENTRY,
+                            extra=self._copy_extra("sample_extended", src_dict, tgt_dict, src_map, blank, fill, source_vocabs, src_map_idx, ext2tgt,
+                                                   ext2src))
 
     # ---- eval: beam search ---------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -392,29 +350,11 @@ class ACG(Seq2seq):
         section 24) -> Seq2seq.decode_beam's dict with EXTENDED ids in 'predictions' [B, W, max_len]: below VT a target word, from VT on slot
         id - VT of the row's dynamic dictionary.  A word is offered once per beam: a slot that collapses onto a target word is no candidate of
         its own, its mass is part of the word's.  The copy inputs are decode()'s; neither they nor the memory bank are repeated."""
-        name = type(self).__name__
         if self.training:
-            raise NotImplementedError("HIP %s.decode_beam runs in eval mode" % name)
+            raise NotImplementedError("HIP %s.decode_beam runs in eval mode" % type(self).__name__)
         lib.require_device(source_rep, source_len, self.embedder.word_embeddings.table)
-        keep = []
-
-        def extra(B, QL):
-            maps = (src_map_idx, ext2tgt, ext2src)
-            if any(t is None for t in maps):
-                maps = self.copy_index(QL, src_map, blank, fill, source_vocabs, src_dict, tgt_dict)
-            dev = self.embedder.word_embeddings.table.device
-            idx, e2t, e2s = (lib.ids64(t).to(dev).contiguous() for t in maps)
-            CV = int(e2t.shape[1])
-            if tuple(idx.shape) != (B, QL) or tuple(e2t.shape) != (B, CV) or tuple(e2s.shape) != (B, CV):
-                raise ValueError("%s.decode_beam: src_map_idx %s, ext2tgt %s, ext2src %s do not fit %d rows of width %d"
-                                 % (name, tuple(idx.shape), tuple(e2t.shape), tuple(e2s.shape), B, QL))
-            if not (1 <= QL <= 4096 and 2 <= CV <= 1024):
-                raise ValueError("%s.decode_beam: QL = %d / CV = %d outside the copy generator's range (QL <= 4096, 2 <= CV <= 1024)" % (name, QL, CV))
-            cw = self._copy_weights()
-            keep.extend((idx, e2t, e2s, cw))                               # alive until the call is enqueued
-            return (CV,), (cw.ref(), lib.ptr(idx), lib.ptr(e2t), lib.ptr(e2s), CV)
         return self._beam(source_rep, source_len, max_len, beam_size, src_dict, tgt_dict, tgt2src, return_backptr, entry=self._ACG_BEAM_ENTRY,
-                          extra=extra)
+                          extra=self._copy_extra("decode_beam", src_dict, tgt_dict, src_map, blank, fill, source_vocabs, src_map_idx, ext2tgt, ext2src))
 
     # ---- train: teacher-forced loss ---------------------------------------------------------------------------------------------------
     def forward(self, source_rep, source_len, target_rep, target_len, target_seq, source_map=None, alignment=None):

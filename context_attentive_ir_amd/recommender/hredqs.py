@@ -137,6 +137,23 @@ class HredQS(nn.Module, lib.IdCheck):
         hs, cs = (self._session_steps_train if self.training else self._session_steps)(src, lens, B, S)
         return tuple(s.transpose(0, 1).reshape(1, S * B, -1) for s in (hs, cs))
 
+    def _source_rows(self, source_rep, source_len, *more):
+        """source_rep [B, S, QL] -> (B, S, QL, the embedding table), all tensors of the call on the device"""
+        B, S, QL = source_rep.shape
+        table = self.embedder.word_embeddings.table
+        lib.require_device(source_rep, source_len, table, *more)
+        return B, S, QL, table
+
+    def _decode_inputs(self, source_rep, source_len, B, S, table, src_dict, tgt_dict, tgt2src):
+        """what every decode and score_candidates feed their entry: the checked ids through _session_steps -> ((h, c) of every session step, the
+        packed decoder weights, the target -> source table (given, or suggest.tgt2src_lut), the embedding table as fp32)"""
+        src, _ = self._clean_ids(source_rep.reshape(B * S, source_rep.shape[2]), None, table.shape[0])
+        hs, cs = self._session_steps(src, lib.ids64(source_len.reshape(-1)), B, S)
+        w = self._decoder_weights()
+        if tgt2src is None:
+            tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, int(w.struct.VT), table.device)
+        return hs, cs, w, tgt2src, table.detach().float().contiguous()
+
     @torch.no_grad()
     def decode(self, source_rep, source_len, max_len, src_dict, tgt_dict, src_map=None, alignment=None, blank=None, fill=None,
                source_vocabs=None, tgt2src=None):
@@ -146,21 +163,14 @@ class HredQS(nn.Module, lib.IdCheck):
         if self.training:
             raise NotImplementedError("HIP HredQS.decode runs in eval mode")
         self._check_config()
-        B, S, QL = source_rep.shape
-        table = self.embedder.word_embeddings.table
-        lib.require_device(source_rep, source_len, table)
+        B, S, _, table = self._source_rows(source_rep, source_len)
         L = lib.load()
         max_len = int(max_len)
         dev = table.device
         preds = torch.empty(B, S, max_len, dtype=torch.int64, device=dev)
         if B * S == 0 or max_len == 0:
             return {"predictions": preds}
-        src, _ = self._clean_ids(source_rep.reshape(B * S, QL), None, table.shape[0])
-        hs, cs = self._session_steps(src, lib.ids64(source_len.reshape(-1)), B, S)
-        w = self._decoder_weights()
-        if tgt2src is None:
-            tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, int(w.struct.VT), dev)
-        t = table.detach().float().contiguous()
+        hs, cs, w, tgt2src, t = self._decode_inputs(source_rep, source_len, B, S, table, src_dict, tgt_dict, tgt2src)
         ws = lib.workspace(L.nir_hredqs_decode_workspace_bytes(B, S, max_len, w.ref()), dev)
         lib.check(L.nir_hredqs_decode_greedy(lib.ptr(hs), lib.ptr(cs), B, S, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(tgt2src), BOS, max_len,
                                              w.ref(), lib.ptr(ws), ws.numel(), lib.ptr(preds), lib.stream()), "nir_hredqs_decode_greedy")
@@ -180,26 +190,17 @@ class HredQS(nn.Module, lib.IdCheck):
         suggest.check_beam_size(W, int(self.generator.weight.shape[0]))
         if max_len < 1:
             raise ValueError("decode_beam: max_len must be positive")
-        B, S, QL = source_rep.shape
-        table = self.embedder.word_embeddings.table
-        lib.require_device(source_rep, source_len, table)
+        B, S, _, table = self._source_rows(source_rep, source_len)
         L = lib.load()
         dev = table.device
         out = suggest.beam_outputs(B * S, W, max_len, dev, return_backptr)
         if B * S > 0:
-            src, _ = self._clean_ids(source_rep.reshape(B * S, QL), None, table.shape[0])
-            hs, cs = self._session_steps(src, lib.ids64(source_len.reshape(-1)), B, S)
-            w = self._decoder_weights()
-            if tgt2src is None:
-                tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, int(w.struct.VT), dev)
-            t = table.detach().float().contiguous()
+            hs, cs, w, tgt2src, t = self._decode_inputs(source_rep, source_len, B, S, table, src_dict, tgt_dict, tgt2src)
             ws = lib.workspace(L.nir_beam_hredqs_decode_workspace_bytes(B, S, W, max_len, w.ref()), dev)
             lib.check(L.nir_beam_hredqs_decode(lib.ptr(hs), lib.ptr(cs), B, S, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(tgt2src), BOS, max_len,
                                                w.ref(), W, lib.ptr(ws), ws.numel(), lib.ptr(out["predictions"]), lib.ptr(out["scores"]),
                                                lib.ptr(out["lengths"]), lib.ptr(out.get("backptr")), lib.stream()), "nir_beam_hredqs_decode")
-        out["predictions"] = out["predictions"].view(B, S, W, max_len)
-        out["scores"], out["lengths"] = out["scores"].view(B, S, W), out["lengths"].view(B, S, W)
-        return out
+        return suggest.beam_view(out, B, S)
 
     # ---- eval: sampling ------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -217,25 +218,16 @@ class HredQS(nn.Module, lib.IdCheck):
         max_len = int(max_len)
         if max_len < 1:
             raise ValueError("decode_sample: max_len must be positive")
-        B, S, QL = source_rep.shape
-        table = self.embedder.word_embeddings.table
-        lib.require_device(source_rep, source_len, table)
+        B, S, _, table = self._source_rows(source_rep, source_len)
         L = lib.load()
         dev = table.device
         out = suggest.sample_outputs(B * S, N, max_len, dev)
         if B * S > 0:
-            src, _ = self._clean_ids(source_rep.reshape(B * S, QL), None, table.shape[0])
-            hs, cs = self._session_steps(src, lib.ids64(source_len.reshape(-1)), B, S)
-            w = self._decoder_weights()
+            hs, cs, w, tgt2src, t = self._decode_inputs(source_rep, source_len, B, S, table, src_dict, tgt_dict, tgt2src)
             ref = w.ref()
             cap = getattr(self, "fuse_sample_max_rows", None)
             if cap is not None and K == 0 and B * S * N > cap and w.struct.gen_frag:
-                plain = lib.HredqsDecoderWeights.from_buffer_copy(w.struct)      # the same pack without the three packs: the entry's plain form
-                plain.rnn_gate_fold = plain.rnn_whh_frag = plain.gen_frag = None
-                ref = lib.C.byref(plain)
-            if tgt2src is None:
-                tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, int(w.struct.VT), dev)
-            t = table.detach().float().contiguous()
+                ref = lib.C.byref(w.without("rnn_gate_fold", "rnn_whh_frag", "gen_frag"))      # without the three packs: the entry's plain form
             nb = L.nir_sample_hredqs_decode_workspace_bytes(B, S, N, K, max_len, ref)
             if nb == 0:
                 raise ValueError("HredQS.decode_sample: the shapes are outside the entry's range (nir_sample_hredqs_decode)")
@@ -264,16 +256,13 @@ class HredQS(nn.Module, lib.IdCheck):
         if self.training:
             raise NotImplementedError("HIP HredQS.score_candidates runs in eval mode")
         self._check_config()
-        B, S, QL = source_rep.shape
-        table = self.embedder.word_embeddings.table
+        B, S, _ = source_rep.shape
         cand = lib.ids64(candidate_seq)
         if cand.dim() != 4 or tuple(cand.shape[:2]) != (B, S) or cand.shape[3] < 2:
             raise ValueError("score_candidates: candidate_seq must be [B, S, N, TL] with TL >= 2 (got %s)" % (tuple(cand.shape),))
-        lib.require_device(source_rep, source_len, table, cand, candidate_rep)
+        table = self._source_rows(source_rep, source_len, cand, candidate_rep)[3]
         R, N, T = B * S, int(cand.shape[2]), int(cand.shape[3]) - 1
-        src, _ = self._clean_ids(source_rep.reshape(R, QL), None, table.shape[0])
-        hs, cs = self._session_steps(src, lib.ids64(source_len.reshape(-1)), B, S)
-        w = self._decoder_weights()
+        hs, cs, w, tgt2src, _ = self._decode_inputs(source_rep, source_len, B, S, table, src_dict, tgt_dict, tgt2src)
         rep = suggest.candidate_inputs(self, cand, candidate_rep, src_dict, tgt_dict, tgt2src, int(w.struct.VT), table.shape[0])
         # the reference's pairing (see the module docstring), then every row's state once per candidate: rows (b, s, n)
         dec_h, dec_c = (s.transpose(0, 1).reshape(R, -1).repeat_interleave(N, 0).contiguous() for s in (hs, cs))

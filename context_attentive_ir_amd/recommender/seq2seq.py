@@ -21,8 +21,6 @@ Kept quirks of the reference:
   * nlayers != 1 (hyparam.SEQ2SEQ has 2) constructs, and fails in forward / decode like the reference: the encoder (use_last) hands over one
     layer's state, the decoder LSTM expects nlayers of them.
 """
-import math
-
 import torch
 import torch.nn as nn
 
@@ -167,14 +165,29 @@ class Seq2seq(nn.Module, lib.IdCheck):
         state = self.initial_state(final, lens)
         return (state if isinstance(state, tuple) else (state,)), bank.float().contiguous()
 
-    def _greedy(self, source_rep, source_len, max_len, src_dict, tgt_dict, tgt2src, extra=(), ws_bytes=None):
-        """the greedy decode of Seq2seq and ACG, either cell: encoder, the sorted-order pairing, ONE C call.  extra: the C arguments an entry takes
-        behind the decoder weights (ACG's copy inputs); ws_bytes(size entry, B, QL, weights): the workspace size where the entry's takes more."""
-        B, QL, table = self._decode_ready("decode", source_rep, source_len)
-        L = lib.load()
+    def _encoded(self, source_rep, source_len, table, repeat=None):
+        """the checked source ids through _encode_state -> (lengths as int64, the initial state tensors, the bank); repeat = n: every state tensor
+        n times along the rows, row k B + b -- the reference's beam layout (decoders/state.py:65-69), which the sampling entries share"""
         src, _ = self._clean_ids(source_rep, None, table.shape[0])
         lens = lib.ids64(source_len)
         state, bank = self._encode_state(src, lens)
+        if repeat is not None:
+            state = [s.repeat(repeat, 1).contiguous() for s in state]
+        return lens, state, bank
+
+    @staticmethod
+    def _generator_form(w, fuse):
+        """what an entry takes as the decoder weights: the pack, or -- `fuse` off -- the same pack without the generator fragment, which selects the
+        plain generator form (the reference returned keeps the copy alive)"""
+        return w.ref() if fuse or not w.struct.gen_frag else lib.C.byref(w.without("gen_frag"))
+
+    def _greedy(self, source_rep, source_len, max_len, src_dict, tgt_dict, tgt2src, extra=None):
+        """the greedy decode of Seq2seq and ACG, either cell: encoder, the sorted-order pairing, ONE C call.  extra(B, QL) -> (what the size entry
+        takes behind QL, the C arguments the entry takes behind the decoder weights): ACG's copy inputs, checked once the shapes are known."""
+        B, QL, table = self._decode_ready("decode", source_rep, source_len)
+        ws_extra, tail = ((), ()) if extra is None else extra(B, QL)
+        L = lib.load()
+        lens, state, bank = self._encoded(source_rep, source_len, table)
         dev = bank.device
         w = self._decoder_weights()
         if tgt2src is None:
@@ -185,10 +198,12 @@ class Seq2seq(nn.Module, lib.IdCheck):
         attns = torch.empty(B, max_len, QL, dtype=torch.float32, device=dev)
         if B > 0 and max_len > 0:
             entry = self._GREEDY_ENTRY % self._ENTRY_CELL
-            size = getattr(L, entry + "_workspace_bytes")
-            ws = lib.workspace(size(B, QL, w.ref()) if ws_bytes is None else ws_bytes(size, B, QL, w), dev)
+            nb = getattr(L, entry + "_workspace_bytes")(B, QL, *ws_extra, w.ref(), *tail[:1])
+            if nb == 0 and tail:
+                raise ValueError("%s.decode: the shapes are outside the entry's range (%s_greedy)" % (type(self).__name__, entry))
+            ws = lib.workspace(nb, dev)
             args = [lib.ptr(s) for s in state] + [lib.ptr(bank), lib.ptr(lens), B, QL, lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(tgt2src), BOS, max_len,
-                                                  w.ref(), *extra, lib.ptr(ws), ws.numel(), lib.ptr(preds), lib.ptr(attns), lib.stream()]
+                                                  w.ref(), *tail, lib.ptr(ws), ws.numel(), lib.ptr(preds), lib.ptr(attns), lib.stream()]
             lib.check(getattr(L, entry + "_greedy")(*args), entry + "_greedy")
         return {"predictions": preds, "attentions": attns}
 
@@ -222,27 +237,16 @@ class Seq2seq(nn.Module, lib.IdCheck):
         L = lib.load()
         w = self._decoder_weights()
         VT = int(w.struct.VT)
-        if not 1 <= W <= lib.BEAM_MAX_W or W > VT:
-            raise ValueError("decode_beam: beam_size %d outside [1, %d] or above the target vocabulary (%d)" % (W, lib.BEAM_MAX_W, VT))
+        suggest.check_beam_size(W, VT)
         ws_extra, tail = (None, None) if extra is None else extra(B, QL)
-        src, _ = self._clean_ids(source_rep, None, table.shape[0])
-        lens = lib.ids64(source_len)
-        state, bank = self._encode_state(src, lens)
-        state = [s.repeat(W, 1).contiguous() for s in state]                  # row k B + b
+        lens, state, bank = self._encoded(source_rep, source_len, table, repeat=W)
         dev = bank.device
-        ws_ref = w.ref()
-        if not self.fuse_generator_topk and w.struct.gen_frag:
-            plain = lib.Seq2seqDecoderWeights.from_buffer_copy(w.struct)      # the same pack without the fragment: the plain generator form
-            plain.gen_frag = None
-            ws_ref = lib.C.byref(plain)
+        ws_ref = self._generator_form(w, self.fuse_generator_topk)
         if tgt2src is None:
             tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, VT, dev)
         t = table.detach().float().contiguous()
         max_len = int(max_len)
-        out = {"predictions": torch.empty(B, W, max_len, dtype=torch.int64, device=dev), "scores": torch.empty(B, W, dtype=torch.float32, device=dev),
-               "lengths": torch.empty(B, W, dtype=torch.int64, device=dev), "attentions": torch.empty(B, W, max_len, QL, dtype=torch.float32, device=dev)}
-        if return_backptr:
-            out["backptr"] = torch.empty(max_len, B, W, dtype=torch.int32, device=dev)
+        out = suggest.beam_outputs(B, W, max_len, dev, return_backptr, QL)
         if B > 0 and max_len > 0:
             entry = (self._BEAM_ENTRY if entry is None else entry) % self._ENTRY_CELL
             outs = [lib.ptr(out["predictions"]), lib.ptr(out["scores"]), lib.ptr(out["lengths"]), lib.ptr(out["attentions"]), lib.ptr(out.get("backptr")),
@@ -277,52 +281,43 @@ class Seq2seq(nn.Module, lib.IdCheck):
         repeated N times (row n B + b), ONE C call; the logits never leave the chip (`fuse_generator_argmax = False`, and for top_k > 0
         `fuse_generator_topk = False`: the plain generator form; over the whole vocabulary it is also the default beyond
         `fuse_sample_max_rows` = suggest.FUSE_SAMPLE_MAX_ROWS decode rows, where it was measured no slower)."""
-        if self.training:
-            raise NotImplementedError("HIP %s.decode_sample runs in eval mode" % type(self).__name__)
-        N, K, tau, seed = int(num_samples), int(top_k), float(temperature), int(seed)
-        if N < 1:
-            raise ValueError("decode_sample: num_samples %d < 1" % N)
-        if not (math.isfinite(tau) and tau > 0.0 and 1e-38 < 1.0 / tau < 3e38):      # (1 / tau travels as an fp32)
-            raise ValueError("decode_sample: temperature %r is not finite and > 0" % (temperature,))
-        if not 0 <= seed < (1 << 64):
-            raise ValueError("decode_sample: seed %d outside [0, 2^64)" % seed)
+        return self._sample("decode_sample", source_rep, source_len, max_len, num_samples, temperature, top_k, seed, src_dict, tgt_dict, tgt2src)
+
+    def _sample(self, what, source_rep, source_len, max_len, num_samples, temperature, top_k, seed, src_dict, tgt_dict, tgt2src, entry=None, extra=None):
+        """the sampling decode of Seq2seq and ACG, either cell, `what` the method's name in the messages.  entry: the C entry (default:
+        _SAMPLE_ENTRY, which takes the draw's arguments behind QL); extra(B, QL) as in _beam, the draw's arguments following the copy inputs."""
         VT = int(self.generator.weight.shape[0])
-        if not 0 <= K <= min(lib.BEAM_MAX_W, VT):
-            raise ValueError("decode_sample: top_k %d outside {0} and [1, %d] (at most %d, and the target vocabulary's %d)"
-                             % (K, min(lib.BEAM_MAX_W, VT), lib.BEAM_MAX_W, VT))
-        B, QL, table = self._decode_ready("decode_sample", source_rep, source_len)
+        N, K, tau, seed = suggest.check_sample_args(self, num_samples, temperature, top_k, seed, VT)      # (its messages say decode_sample: the shared rules)
+        B, QL, table = self._decode_ready(what, source_rep, source_len)
+        ws_extra, tail = (None, None) if extra is None else extra(B, QL)
         L = lib.load()
         w = self._decoder_weights()
-        src, _ = self._clean_ids(source_rep, None, table.shape[0])
-        lens = lib.ids64(source_len)
-        state, bank = self._encode_state(src, lens)
-        state = [s.repeat(N, 1).contiguous() for s in state]                  # row n B + b
+        lens, state, bank = self._encoded(source_rep, source_len, table, repeat=N)
         dev = bank.device
-        ws_ref = w.ref()
         fuse = self.fuse_generator_topk if K > 0 else (self.fuse_generator_argmax
                                                        and B * N <= getattr(self, "fuse_sample_max_rows", suggest.FUSE_SAMPLE_MAX_ROWS))
-        if w.struct.gen_frag and not fuse:
-            plain = lib.Seq2seqDecoderWeights.from_buffer_copy(w.struct)      # the same pack without the fragment: the plain generator form
-            plain.gen_frag = None
-            ws_ref = lib.C.byref(plain)
+        ws_ref = self._generator_form(w, fuse)
         if tgt2src is None:
             tgt2src = suggest.tgt2src_lut(self, src_dict, tgt_dict, VT, dev)
         t = table.detach().float().contiguous()
         max_len = int(max_len)
-        out = {"predictions": torch.empty(B, N, max_len, dtype=torch.int64, device=dev),
-               "token_logprobs": torch.empty(B, N, max_len, dtype=torch.float32, device=dev),
-               "scores": torch.empty(B, N, dtype=torch.float32, device=dev), "lengths": torch.empty(B, N, dtype=torch.int64, device=dev),
-               "attentions": torch.empty(B, N, max_len, QL, dtype=torch.float32, device=dev)}
+        out = suggest.sample_outputs(B, N, max_len, dev, QL)
         if B > 0 and max_len > 0:
-            entry = self._SAMPLE_ENTRY % self._ENTRY_CELL
-            nb = getattr(L, entry + "_workspace_bytes")(B, QL, N, K, max_len, ws_ref)
+            entry = (self._SAMPLE_ENTRY if entry is None else entry) % self._ENTRY_CELL
+            front = [lib.ptr(s) for s in state] + [lib.ptr(bank), lib.ptr(lens), B, QL]
+            mid = [lib.ptr(t), t.shape[0], t.shape[1], lib.ptr(tgt2src), BOS, max_len, ws_ref]
+            draw = [N, K, 1.0 / tau, seed]
+            if tail is None:
+                nb = getattr(L, entry + "_workspace_bytes")(B, QL, N, K, max_len, ws_ref)
+                args = front + draw + mid
+            else:
+                nb = getattr(L, entry + "_workspace_bytes")(B, QL, *ws_extra, N, K, max_len, ws_ref, tail[0])
+                args = front + mid + list(tail) + draw
             if nb == 0:
-                raise ValueError("%s.decode_sample: the shapes are outside the entry's range (%s)" % (type(self).__name__, entry))
+                raise ValueError("%s.%s: the shapes are outside the entry's range (%s)" % (type(self).__name__, what, entry))
             ws = lib.workspace(nb, dev)
-            args = [lib.ptr(s) for s in state] + [lib.ptr(bank), lib.ptr(lens), B, QL, N, K, 1.0 / tau, seed, lib.ptr(t), t.shape[0], t.shape[1],
-                                                  lib.ptr(tgt2src), BOS, max_len, ws_ref, lib.ptr(ws), ws.numel()]
-            args += [lib.ptr(out[k]) for k in ("predictions", "token_logprobs", "scores", "lengths", "attentions")] + [lib.stream()]
-            lib.check(getattr(L, entry)(*args), entry)
+            args += [lib.ptr(ws), ws.numel()] + [lib.ptr(out[k]) for k in ("predictions", "token_logprobs", "scores", "lengths", "attentions")]
+            lib.check(getattr(L, entry)(*args, lib.stream()), entry)
         return out
 
     # ---- eval: teacher-forced scoring of given candidates ---------------------------------------------------------------------------------
@@ -348,9 +343,7 @@ class Seq2seq(nn.Module, lib.IdCheck):
         B, QL, table = self._decode_ready("score_candidates", source_rep, source_len)
         lib.require_device(cand, candidate_rep)
         N, T = int(cand.shape[1]), int(cand.shape[2]) - 1
-        src, _ = self._clean_ids(source_rep, None, table.shape[0])
-        lens = lib.ids64(source_len)
-        state, bank = self._encode_state(src, lens)
+        lens, state, bank = self._encoded(source_rep, source_len, table)
         w = self._decoder_weights()
         rep = suggest.candidate_inputs(self, cand, candidate_rep, src_dict, tgt_dict, tgt2src, int(w.struct.VT), table.shape[0])
         temb = A.embed(rep[:, :, :-1].reshape(B * N, T), table)

@@ -123,6 +123,23 @@ class WrapperBase(object):
         out = self._graphs.call(ex, fields, flavour, body, finish)
         return None if out is self._graphs.EAGER else out
 
+    @staticmethod
+    def _score_summary(out, own, length_normalize):
+        """the tail of every scoring call, added to `out` (a network's 'scores' and 'lengths'): for the batch's own target 'nll' and 'perplexity',
+        for given candidates 'ranking' -- best first by `scores`, or by scores / lengths with `length_normalize`, ties to the smaller n"""
+        if own:
+            out["nll"] = -out["scores"].mean()
+            out["perplexity"] = torch.exp(-out["scores"].sum() / out["lengths"].sum().clamp(min=1))
+        else:
+            key = out["scores"] / out["lengths"].clamp(min=1) if length_normalize else out["scores"]
+            out["ranking"] = torch.sort(key, dim=-1, descending=True, stable=True)[1]
+        return out
+
+    @staticmethod
+    def _draw_seed(seed):
+        """the seed of a sampling call: the caller's, or 63 bits from torch's default CPU generator (no device synchronisation)"""
+        return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if seed is None else seed
+
     def clear_predict_graphs(self):
         if self._graphs is not None:
             self._graphs.clear()

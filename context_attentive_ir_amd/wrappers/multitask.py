@@ -296,22 +296,43 @@ class Multitask(WrapperBase):
         return {"prediction_ids": pred_ids, "predictions": preds, "targets": targets, "src_sequences": srcs,
                 "ex_ids": [_id + str(i) for i in range(S) for _id in ex["ids"]]}
 
-    # ---- beam search ------------------------------------------------------------------------------------------------------------------
-    def _predict_beam_body(self, ex, beam_size):
-        """_predict_body with the beam decode in the place of the greedy one: the same kernels in the same order in front of it"""
+    # ---- what the beam, sampling and scoring calls share ------------------------------------------------------------------------------------
+    def _rank_softmax(self, ex):
+        """_predict_body's front with the decoder's inputs kept: _rank, then the click scores through nir_softmax_rows -> (click probabilities
+        [B,S,N], or None without a ranker; states, attns, enc as _rank returns them)"""
         s, states, attns, enc = self._rank(ex, True)
-        out = {"click_scores": None, "prediction_ids": None, "scores": None, "lengths": None}
+        probs = None
         if torch.is_tensor(s):
             s = s.contiguous()
             probs = torch.empty_like(s)
             lib.check(lib.load().nir_softmax_rows(lib.ptr(s), lib.ptr(probs), s.shape[0] * s.shape[1], s.shape[2], lib.stream()), "nir_softmax_rows")
-            out["click_scores"] = probs
+        return probs, states, attns, enc
+
+    def _ranking_only(self, ex, *keys):
+        """CARS with the recommender off: predict()'s ranking path, with `keys` -- what the decoder would have returned -- set to None"""
+        out = self.predict(ex, suggest=False)
+        out.pop("predictions", None)
+        out.update(dict.fromkeys(keys))
+        return out
+
+    def _nbest_text(self, ex, pred_ids):
+        """_suggestion_text for pred_ids [B, S-1, n, max_query_len]: `predictions` = one list of n strings per decoded query (step-major, each
+        string formed like predict()'s), the other text fields as predict() forms them"""
+        per = [self._suggestion_text(ex, pred_ids[:, :, k]) for k in range(pred_ids.shape[2])]
+        text = dict(per[0])
+        text["prediction_ids"] = pred_ids
+        text["predictions"] = [[p["predictions"][j] for p in per] for j in range(len(per[0]["predictions"]))]
+        return text
+
+    # ---- beam search ------------------------------------------------------------------------------------------------------------------
+    def _predict_beam_body(self, ex, beam_size):
+        """_predict_body with the beam decode in the place of the greedy one: the same kernels in the same order in front of it"""
+        probs, states, attns, enc = self._rank_softmax(ex)
         B, S = ex["source_words"].shape[0], ex["source_words"].shape[1]
         dec = self.network.decode_beam(states=states, max_len=self.args.max_query_len, beam_size=beam_size, src_dict=self.src_dict, tgt_dict=self.tgt_dict,
                                        batch_size=B, session_len=S - 1, encoded_source=enc[0], source_len=enc[1], session_attns=attns)
-        out.update(prediction_ids=dec["predictions"], scores=dec["scores"], lengths=dec["lengths"])
         self._maybe_check_ids(False)
-        return out
+        return {"click_scores": probs, "prediction_ids": dec["predictions"], "scores": dec["scores"], "lengths": dec["lengths"]}
 
     @torch.no_grad()
     def predict_beam(self, ex, beam_size):
@@ -325,10 +346,7 @@ class Multitask(WrapperBase):
         if not 1 <= W <= lib.BEAM_MAX_W:
             raise ValueError("predict_beam: beam_size %d outside [1, %d]" % (W, lib.BEAM_MAX_W))
         if self.type == "CARS" and self.network.no_recommender:
-            out = self.predict(ex, suggest=False)
-            out.pop("predictions", None)
-            out.update(prediction_ids=None, scores=None, lengths=None)
-            return out
+            return self._ranking_only(ex, "prediction_ids", "scores", "lengths")
         self._poll_ids()
         fields = self._FIELDS if self.type == "CARS" else self._FIELDS[:4]
         body = lambda e: self._predict_beam_body(e, W)                        # noqa: E731
@@ -341,11 +359,7 @@ class Multitask(WrapperBase):
         if out["click_scores"] is not None:
             out["click_scores"] = self._checked(out["click_scores"])
         if "ids" in ex and ex.get("source_tokens") is not None:
-            per_beam = [self._suggestion_text(ex, out["prediction_ids"][:, :, k]) for k in range(W)]
-            text = dict(per_beam[0])
-            text["prediction_ids"] = out["prediction_ids"]
-            text["predictions"] = [[per_beam[k]["predictions"][j] for k in range(W)] for j in range(len(per_beam[0]["predictions"]))]
-            out.update(text)
+            out.update(self._nbest_text(ex, out["prediction_ids"]))
         return out
 
     # ---- sampling -------------------------------------------------------------------------------------------------------------------
@@ -359,36 +373,23 @@ class Multitask(WrapperBase):
         the draw.  Always eager: the seed is a host argument of the C entry, so a captured graph would replay one draw.  CARS with the
         recommender off returns the sampling keys as None, like predict_beam()."""
         N = int(num_samples)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        seed = self._draw_seed(seed)
         if self.type == "CARS" and self.network.no_recommender:
-            out = self.predict(ex, suggest=False)
-            out.pop("predictions", None)
-            out.update(prediction_ids=None, token_logprobs=None, scores=None, lengths=None, seed=None)
-            return out
+            return self._ranking_only(ex, "prediction_ids", "token_logprobs", "scores", "lengths", "seed")
         self._poll_ids()
         # _predict_beam_body with the sampling decode in the place of the beam: the same kernels in the same order in front of it
-        s, states, attns, enc = self._rank(ex, True)
-        out = {"click_scores": None}
-        if torch.is_tensor(s):
-            s = s.contiguous()
-            probs = torch.empty_like(s)
-            lib.check(lib.load().nir_softmax_rows(lib.ptr(s), lib.ptr(probs), s.shape[0] * s.shape[1], s.shape[2], lib.stream()), "nir_softmax_rows")
-            out["click_scores"] = probs
+        probs, states, attns, enc = self._rank_softmax(ex)
         B, S = ex["source_words"].shape[0], ex["source_words"].shape[1]
         dec = self.network.decode_sample(states=states, max_len=self.args.max_query_len, num_samples=N, temperature=temperature, top_k=top_k, seed=seed,
                                          src_dict=self.src_dict, tgt_dict=self.tgt_dict, batch_size=B, session_len=S - 1, encoded_source=enc[0],
                                          source_len=enc[1], session_attns=attns)
-        out.update(prediction_ids=dec["predictions"], token_logprobs=dec["token_logprobs"], scores=dec["scores"], lengths=dec["lengths"], seed=int(seed))
+        out = {"click_scores": probs, "prediction_ids": dec["predictions"], "token_logprobs": dec["token_logprobs"], "scores": dec["scores"],
+               "lengths": dec["lengths"], "seed": int(seed)}
         self._maybe_check_ids(False)
-        if out["click_scores"] is not None:
-            out["click_scores"] = self._checked(out["click_scores"])
+        if probs is not None:
+            out["click_scores"] = self._checked(probs)
         if "ids" in ex and ex.get("source_tokens") is not None:
-            per = [self._suggestion_text(ex, out["prediction_ids"][:, :, n]) for n in range(N)]
-            text = dict(per[0])
-            text["prediction_ids"] = out["prediction_ids"]
-            text["predictions"] = [[per[n]["predictions"][j] for n in range(N)] for j in range(len(per[0]["predictions"]))]
-            out.update(text)
+            out.update(self._nbest_text(ex, out["prediction_ids"]))
         return out
 
     # ---- teacher-forced scoring ---------------------------------------------------------------------------------------------------------
@@ -404,19 +405,10 @@ class Multitask(WrapperBase):
         is captured.  CARS with the recommender off returns the scoring keys as None, like predict_beam."""
         own = candidates is None and "candidate_seq" not in ex
         if self.type == "CARS" and self.network.no_recommender:
-            out = self.predict(ex, suggest=False)
-            out.pop("predictions", None)
-            out.update(token_logprobs=None, scores=None, lengths=None)
-            out.update(dict(nll=None, perplexity=None) if own else dict(ranking=None))
-            return out
+            return self._ranking_only(ex, "token_logprobs", "scores", "lengths", *(("nll", "perplexity") if own else ("ranking",)))
         self._poll_ids()
-        s, states, attns, enc = self._rank(ex, True)
-        out = {"click_scores": None}
-        if torch.is_tensor(s):
-            s = s.contiguous()
-            probs = torch.empty_like(s)
-            lib.check(lib.load().nir_softmax_rows(lib.ptr(s), lib.ptr(probs), s.shape[0] * s.shape[1], s.shape[2], lib.stream()), "nir_softmax_rows")
-            out["click_scores"] = probs
+        probs, states, attns, enc = self._rank_softmax(ex)
+        out = {"click_scores": probs}
         B, S = ex["source_words"].shape[0], ex["source_words"].shape[1]
         if own:
             cand = ex["target_seq"].reshape(B, S - 1, 1, -1)
@@ -430,15 +422,9 @@ class Multitask(WrapperBase):
             kw.update(encoded_source=enc[0], source_len=enc[1], session_attns=attns)
         out.update(self.network.score_candidates(**kw))
         self._maybe_check_ids()
-        if out["click_scores"] is not None:
-            out["click_scores"] = self._checked(out["click_scores"])
-        if own:
-            out["nll"] = -out["scores"].mean()
-            out["perplexity"] = torch.exp(-out["scores"].sum() / out["lengths"].sum().clamp(min=1))
-        else:
-            key = out["scores"] / out["lengths"].clamp(min=1) if length_normalize else out["scores"]
-            out["ranking"] = torch.sort(key, dim=-1, descending=True, stable=True)[1]
-        return out
+        if probs is not None:
+            out["click_scores"] = self._checked(probs)
+        return self._score_summary(out, own, length_normalize)
 
     def _finish_scores(self, s):
         probs, published = self._softmax_rows(s)

@@ -98,6 +98,38 @@ class Recommender(WrapperBase):
         self._maybe_check_ids()
         return {"prediction_ids": dec["predictions"], "attentions": dec["attentions"]}
 
+    _TEXT_FIELDS = ("ids", "source_tokens", "target_tokens", "src_vocab")      # a batch in the reference's collate layout has all of them
+    _NBEST_AXIS = 1                                                            # the beam / sample axis of prediction_ids and attentions
+
+    def _graphed_or_eager(self, ex, flavour, body):
+        """body(ex) through the hipGraph cache (WrapperBase._graphed, `flavour` in the key), or eagerly where that declines"""
+        out = self._graphed(ex, self._FIELDS, flavour, body)
+        if out is None:
+            out = body(ex)
+        elif self.id_check == "blocking":
+            self._maybe_check_ids()
+        return out
+
+    def _decode_kw(self, ex):
+        """what every decode of the network takes from a batch"""
+        return dict(source_rep=self._dev(self._rows3(ex["source_words"])), source_len=self._dev(self._rows2(ex["source_lens"])),
+                    max_len=self.args.max_query_len, src_dict=self.src_dict, tgt_dict=self.tgt_dict)
+
+    @staticmethod
+    def _ids_first(dec):
+        """a decode's dict under the wrappers' key: 'predictions' -> 'prediction_ids' ('predictions' are the strings here)"""
+        return {("prediction_ids" if k == "predictions" else k): v for k, v in dec.items()}
+
+    def _nbest_text(self, ex, out):
+        """out, for a batch in the reference's collate layout with predict()'s text fields: `predictions` = per row the list of its n strings,
+        one _text per beam / sample"""
+        if all(k in ex for k in self._TEXT_FIELDS):
+            ids, att, ax = out["prediction_ids"], out.get("attentions"), self._NBEST_AXIS
+            per = [self._text(ex, ids.select(ax, k), None if att is None else att.select(ax, k)) for k in range(ids.shape[ax])]
+            out.update(per[0])
+            out["predictions"] = [[p["predictions"][i] for p in per] for i in range(len(per[0]["predictions"]))]
+        return out
+
     @torch.no_grad()
     def predict(self, ex):
         """models/recommender.py:233-329: {'prediction_ids': LongTensor [B, max_query_len] (target-vocabulary ids), 'attentions':
@@ -105,22 +137,22 @@ class Recommender(WrapperBase):
         reference's `ex_ids`, `predictions` (strings, <unk> replaced by the most attended source token), `targets`, `src_sequences`.
         From the `predict_graph_min_calls`-th call of a batch shape on, the call replays a captured hipGraph (WrapperBase._graphed)."""
         self._poll_ids()
-        out = self._graphed(ex, self._FIELDS, "decode", self._predict_body)
-        if out is None:
-            out = self._predict_body(ex)
-        elif self.id_check == "blocking":
-            self._maybe_check_ids()
-        if all(k in ex for k in ("ids", "source_tokens", "target_tokens", "src_vocab")):
-            out.update(self._text(ex, out["prediction_ids"], out["attentions"]))
+        out = self._graphed_or_eager(ex, "decode", self._predict_body)
+        if all(k in ex for k in self._TEXT_FIELDS):
+            out.update(self._text(ex, out["prediction_ids"], out.get("attentions")))
         return out
 
     # ---- beam search ------------------------------------------------------------------------------------------------------------------
     def _predict_beam_body(self, ex, beam_size):
         self.network.eval()
-        dec = self.network.decode_beam(source_rep=self._dev(self._rows3(ex["source_words"])), source_len=self._dev(self._rows2(ex["source_lens"])),
-                                       max_len=self.args.max_query_len, beam_size=beam_size, src_dict=self.src_dict, tgt_dict=self.tgt_dict)
+        dec = self.network.decode_beam(beam_size=beam_size, **self._decode_kw(ex))
         self._maybe_check_ids()
-        return {"prediction_ids": dec["predictions"], "scores": dec["scores"], "lengths": dec["lengths"], "attentions": dec["attentions"]}
+        return self._ids_first(dec)
+
+    def _nbest(self, ex, W, flavour):
+        """the n-best call of every wrapper here: _predict_beam_body under the graph key flavour % W, then the strings"""
+        self._poll_ids()
+        return self._nbest_text(ex, self._graphed_or_eager(ex, flavour % W, lambda e: self._predict_beam_body(e, W)))
 
     @torch.no_grad()
     def predict_beam(self, ex, beam_size):
@@ -128,19 +160,7 @@ class Recommender(WrapperBase):
         [B, W, max_query_len], 'scores': [B, W], 'lengths': LongTensor [B, W], 'attentions': [B, W, max_query_len, QL]}, best beam first; for
         a batch in the reference's collate layout also `ex_ids`, `targets`, `src_sequences` and `predictions`: per row the list of its W
         strings, each formed like predict()'s.  `beam_size` is an argument of the call, not a field of args.  Graph replay as in predict()."""
-        W = int(beam_size)
-        self._poll_ids()
-        body = lambda e: self._predict_beam_body(e, W)                        # noqa: E731
-        out = self._graphed(ex, Recommender._FIELDS, "decode_beam%d" % W, body)
-        if out is None:
-            out = body(ex)
-        elif self.id_check == "blocking":
-            self._maybe_check_ids()
-        if all(k in ex for k in ("ids", "source_tokens", "target_tokens", "src_vocab")):
-            per_beam = [Recommender._text(self, ex, out["prediction_ids"][:, k], out["attentions"][:, k]) for k in range(W)]
-            out.update(per_beam[0])
-            out["predictions"] = [[per_beam[k]["predictions"][b] for k in range(W)] for b in range(len(per_beam[0]["predictions"]))]
-        return out
+        return self._nbest(ex, int(beam_size), "decode_beam%d")
 
     def predict_nbest(self, ex, beam_size):
         """n-best suggestions, the one name every wrapper has: predict_beam here; CopyRecommender's is ACG's search over the copy generator's
@@ -148,6 +168,15 @@ class Recommender(WrapperBase):
         return self.predict_beam(ex, beam_size)
 
     # ---- sampling -------------------------------------------------------------------------------------------------------------------
+    def _samples(self, ex, draw, num_samples, temperature, top_k, seed):
+        """the sampling call of every wrapper here; draw: the network's sampling method"""
+        seed = self._draw_seed(seed)
+        self._poll_ids()
+        self.network.eval()
+        dec = draw(num_samples=int(num_samples), temperature=temperature, top_k=top_k, seed=seed, **self._decode_kw(ex))
+        self._maybe_check_ids()
+        return self._nbest_text(ex, dict(self._ids_first(dec), seed=int(seed)))
+
     @torch.no_grad()
     def predict_samples(self, ex, num_samples, temperature=1.0, top_k=0, seed=None):
         """`num_samples` i.i.d. suggestions per row drawn from the model (Seq2seq.decode_sample; the reference has no counterpart):
@@ -157,22 +186,7 @@ class Recommender(WrapperBase):
         formed like predict()'s.  seed=None draws a 63-bit seed from torch's default CPU generator (no device synchronisation); calling again
         with the returned 'seed' replays the draw bit for bit.  Always eager: the seed is a host argument of the C entry, so a captured graph
         would replay one and the same draw."""
-        N = int(num_samples)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
-        self._poll_ids()
-        self.network.eval()
-        dec = self.network.decode_sample(source_rep=self._dev(self._rows3(ex["source_words"])), source_len=self._dev(self._rows2(ex["source_lens"])),
-                                         max_len=self.args.max_query_len, num_samples=N, temperature=temperature, top_k=top_k, seed=seed,
-                                         src_dict=self.src_dict, tgt_dict=self.tgt_dict)
-        self._maybe_check_ids()
-        out = {"prediction_ids": dec["predictions"], "token_logprobs": dec["token_logprobs"], "scores": dec["scores"], "lengths": dec["lengths"],
-               "attentions": dec["attentions"], "seed": int(seed)}
-        if all(k in ex for k in ("ids", "source_tokens", "target_tokens", "src_vocab")):
-            per = [Recommender._text(self, ex, out["prediction_ids"][:, n], out["attentions"][:, n]) for n in range(N)]
-            out.update(per[0])
-            out["predictions"] = [[per[n]["predictions"][b] for n in range(N)] for b in range(len(per[0]["predictions"]))]
-        return out
+        return self._samples(ex, self.network.decode_sample, num_samples, temperature, top_k, seed)
 
     # ---- scoring --------------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -198,13 +212,7 @@ class Recommender(WrapperBase):
         out = self.network.score_candidates(source_rep=src, source_len=sl, candidate_seq=self._dev(cand),
                                             candidate_rep=self._dev(rep) if rep is not None else None, src_dict=self.src_dict, tgt_dict=self.tgt_dict)
         self._maybe_check_ids()
-        if own:
-            out["nll"] = -out["scores"].mean()
-            out["perplexity"] = torch.exp(-out["scores"].sum() / out["lengths"].sum().clamp(min=1))
-        else:
-            key = out["scores"] / out["lengths"].clamp(min=1) if length_normalize else out["scores"]
-            out["ranking"] = torch.sort(key, dim=-1, descending=True, stable=True)[1]
-        return out
+        return self._score_summary(out, own, length_normalize)
 
     def _text(self, ex, pred_ids, attns):
         """the host-side tail of the reference's predict (models/recommender.py:294-309): tens2sen (utils/misc.py:36-62) + replace_unknown
@@ -282,6 +290,9 @@ class SessionRecommender(Recommender):
                                   "outputs keep the session axis, [B, S, N, max_query_len], and there are no attentions (the rules of DESIGN.md "
                                   "section 28, built behind the decoder without attention in section 29)")
 
+    _TEXT_FIELDS = ("ids", "source_tokens", "target_tokens")
+    _NBEST_AXIS = 2
+
     @torch.no_grad()
     def predict_session_samples(self, ex, num_samples, temperature=1.0, top_k=0, seed=None):
         """`num_samples` i.i.d. suggestions per session prefix drawn from the model (HredQS.decode_sample; the reference has no counterpart):
@@ -290,28 +301,7 @@ class SessionRecommender(Recommender):
         layout also predict()'s step-major `ex_ids`, `targets`, `src_sequences` and `predictions`: per prefix the list of its N strings.
         seed=None draws a 63-bit seed from torch's default CPU generator (no device synchronisation); calling again with the returned 'seed'
         replays the draw bit for bit.  Always eager: the seed is a host argument of the C entry, so a captured graph would replay one draw."""
-        N = int(num_samples)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
-        self._poll_ids()
-        self.network.eval()
-        dec = self.network.decode_sample(source_rep=self._dev(ex["source_words"]), source_len=self._dev(ex["source_lens"]), max_len=self.args.max_query_len,
-                                         num_samples=N, temperature=temperature, top_k=top_k, seed=seed, src_dict=self.src_dict, tgt_dict=self.tgt_dict)
-        self._maybe_check_ids()
-        out = {"prediction_ids": dec["predictions"], "token_logprobs": dec["token_logprobs"], "scores": dec["scores"], "lengths": dec["lengths"],
-               "seed": int(seed)}
-        if all(k in ex for k in ("ids", "source_tokens", "target_tokens")):
-            per = [self._text(ex, out["prediction_ids"][:, :, n]) for n in range(N)]
-            out.update(per[0])
-            out["predictions"] = [[per[n]["predictions"][i] for n in range(N)] for i in range(len(per[0]["predictions"]))]
-        return out
-
-    def _predict_session_nbest_body(self, ex, beam_size):
-        self.network.eval()
-        dec = self.network.decode_beam(source_rep=self._dev(ex["source_words"]), source_len=self._dev(ex["source_lens"]), max_len=self.args.max_query_len,
-                                       beam_size=beam_size, src_dict=self.src_dict, tgt_dict=self.tgt_dict)
-        self._maybe_check_ids()
-        return {"prediction_ids": dec["predictions"], "scores": dec["scores"], "lengths": dec["lengths"]}
+        return self._samples(ex, self.network.decode_sample, num_samples, temperature, top_k, seed)
 
     @torch.no_grad()
     def predict_session_nbest(self, ex, beam_size):
@@ -323,18 +313,7 @@ class SessionRecommender(Recommender):
         W = int(beam_size)
         if not 1 <= W <= lib.BEAM_MAX_W:
             raise ValueError("predict_session_nbest: beam_size %d outside [1, %d]" % (W, lib.BEAM_MAX_W))
-        self._poll_ids()
-        body = lambda e: self._predict_session_nbest_body(e, W)               # noqa: E731
-        out = self._graphed(ex, self._FIELDS, "decode_session_nbest%d" % W, body)
-        if out is None:
-            out = body(ex)
-        elif self.id_check == "blocking":
-            self._maybe_check_ids()
-        if all(k in ex for k in ("ids", "source_tokens", "target_tokens")):
-            per_beam = [self._text(ex, out["prediction_ids"][:, :, k]) for k in range(W)]
-            out.update(per_beam[0])
-            out["predictions"] = [[per_beam[k]["predictions"][i] for k in range(W)] for i in range(len(per_beam[0]["predictions"]))]
-        return out
+        return self._nbest(ex, W, "decode_session_nbest%d")
 
     def _predict_body(self, ex):
         self.network.eval()
@@ -350,15 +329,7 @@ class SessionRecommender(Recommender):
         reference's collate layout (`ids`, `source_tokens`, `target_tokens`) also the reference's `ex_ids`, `predictions`, `targets` and
         `src_sequences`, step-major (index s B + b).  There are no attentions, so no <unk> is replaced.  From the
         `predict_graph_min_calls`-th call of a batch shape on, the call replays a captured hipGraph (WrapperBase._graphed)."""
-        self._poll_ids()
-        out = self._graphed(ex, self._FIELDS, "decode", self._predict_body)
-        if out is None:
-            out = self._predict_body(ex)
-        elif self.id_check == "blocking":
-            self._maybe_check_ids()
-        if all(k in ex for k in ("ids", "source_tokens", "target_tokens")):
-            out.update(self._text(ex, out["prediction_ids"]))
-        return out
+        return super().predict(ex)
 
     def _text(self, ex, pred_ids, attns=None):
         """the host-side tail of the reference's predict for HREDQS (models/recommender.py:310-327; tens2sen: utils/misc.py:36-62).  The one
@@ -444,14 +415,18 @@ class CopyRecommender(Recommender):
         out.update(copy_src_map_idx=idx, copy_ext2tgt=e2t, copy_ext2src=e2s)
         return out
 
+    def _decode_kw(self, ex):
+        """Recommender's + the three copy maps of _copy_fields"""
+        return dict(super()._decode_kw(ex), src_map_idx=self._dev(ex["copy_src_map_idx"]), ext2tgt=self._dev(ex["copy_ext2tgt"]),
+                    ext2src=self._dev(ex["copy_ext2src"]))
+
     def _predict_body(self, ex):
         self.network.eval()
-        dec = self.network.decode(source_rep=self._dev(self._rows3(ex["source_words"])), source_len=self._dev(self._rows2(ex["source_lens"])),
-                                  max_len=self.args.max_query_len, src_dict=self.src_dict, tgt_dict=self.tgt_dict,
-                                  src_map_idx=self._dev(ex["copy_src_map_idx"]), ext2tgt=self._dev(ex["copy_ext2tgt"]),
-                                  ext2src=self._dev(ex["copy_ext2src"]))
+        dec = self.network.decode(**self._decode_kw(ex))
         self._maybe_check_ids()
         return {"prediction_ids": dec["predictions"], "attentions": dec["attentions"]}
+
+    _predict_nbest_body = Recommender._predict_beam_body                      # (ACG's n-best body under the name of its call)
 
     @torch.no_grad()
     def predict(self, ex):
@@ -500,13 +475,7 @@ class CopyRecommender(Recommender):
                                           src_map_idx=self._dev(ex["copy_src_map_idx"]), ext2tgt=self._dev(ex["copy_ext2tgt"]),
                                           ext2src=self._dev(ex["copy_ext2src"]))
         self._maybe_check_ids()
-        if own:
-            out["nll"] = -out["scores"].mean()
-            out["perplexity"] = torch.exp(-out["scores"].sum() / out["lengths"].sum().clamp(min=1))
-        else:
-            key = out["scores"] / out["lengths"].clamp(min=1) if length_normalize else out["scores"]
-            out["ranking"] = torch.sort(key, dim=-1, descending=True, stable=True)[1]
-        return out
+        return self._score_summary(out, own, length_normalize)
 
     def predict_samples(self, ex, num_samples, temperature=1.0, top_k=0, seed=None):
         raise NotImplementedError("CopyRecommender.predict_samples: a draw under ACG comes from its collapsed extended distribution (generator mass "
@@ -521,33 +490,7 @@ class CopyRecommender(Recommender):
         `src_sequences` and `predictions`: per row the list of its N strings, each formed like predict()'s (copied words come from the row's
         dictionary).  seed=None draws 63 bits from torch's default CPU generator; calling again with the returned 'seed' replays the draw bit
         for bit.  The copy maps are predict()'s (_copy_fields).  Always eager: the seed is a host argument of the C entry."""
-        N = int(num_samples)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
-        ex = self._copy_fields(ex)
-        self._poll_ids()
-        self.network.eval()
-        dec = self.network.sample_extended(source_rep=self._dev(self._rows3(ex["source_words"])), source_len=self._dev(self._rows2(ex["source_lens"])),
-                                           max_len=self.args.max_query_len, num_samples=N, temperature=temperature, top_k=top_k, seed=seed,
-                                           src_dict=self.src_dict, tgt_dict=self.tgt_dict, src_map_idx=self._dev(ex["copy_src_map_idx"]),
-                                           ext2tgt=self._dev(ex["copy_ext2tgt"]), ext2src=self._dev(ex["copy_ext2src"]))
-        self._maybe_check_ids()
-        out = {"prediction_ids": dec["predictions"], "token_logprobs": dec["token_logprobs"], "scores": dec["scores"], "lengths": dec["lengths"],
-               "attentions": dec["attentions"], "seed": int(seed)}
-        if all(k in ex for k in ("ids", "source_tokens", "target_tokens", "src_vocab")):
-            per = [self._text(ex, out["prediction_ids"][:, n], out["attentions"][:, n]) for n in range(N)]
-            out.update(per[0])
-            out["predictions"] = [[per[n]["predictions"][b] for n in range(N)] for b in range(len(per[0]["predictions"]))]
-        return out
-
-    def _predict_nbest_body(self, ex, beam_size):
-        self.network.eval()
-        dec = self.network.decode_beam(source_rep=self._dev(self._rows3(ex["source_words"])), source_len=self._dev(self._rows2(ex["source_lens"])),
-                                       max_len=self.args.max_query_len, beam_size=beam_size, src_dict=self.src_dict, tgt_dict=self.tgt_dict,
-                                       src_map_idx=self._dev(ex["copy_src_map_idx"]), ext2tgt=self._dev(ex["copy_ext2tgt"]),
-                                       ext2src=self._dev(ex["copy_ext2src"]))
-        self._maybe_check_ids()
-        return {"prediction_ids": dec["predictions"], "scores": dec["scores"], "lengths": dec["lengths"], "attentions": dec["attentions"]}
+        return self._samples(self._copy_fields(ex), self.network.sample_extended, num_samples, temperature, top_k, seed)
 
     @torch.no_grad()
     def predict_nbest(self, ex, beam_size):
@@ -556,20 +499,7 @@ class CopyRecommender(Recommender):
         [B, W, max_query_len, QL]}, best beam first; for a full collate batch also `ex_ids`, `targets`, `src_sequences` and `predictions`: per
         row the list of its W strings, each formed like predict()'s (copied words come from the row's dictionary).  Graph replay as in
         predict(): the width is part of the graph's key, the three copy maps are inputs of the graph."""
-        W = int(beam_size)
-        ex = self._copy_fields(ex)
-        self._poll_ids()
-        body = lambda e: self._predict_nbest_body(e, W)                       # noqa: E731
-        out = self._graphed(ex, self._FIELDS, "decode_nbest%d" % W, body)
-        if out is None:
-            out = body(ex)
-        elif self.id_check == "blocking":
-            self._maybe_check_ids()
-        if all(k in ex for k in ("ids", "source_tokens", "target_tokens", "src_vocab")):
-            per_beam = [self._text(ex, out["prediction_ids"][:, k], out["attentions"][:, k]) for k in range(W)]
-            out.update(per_beam[0])
-            out["predictions"] = [[per_beam[k]["predictions"][b] for k in range(W)] for b in range(len(per_beam[0]["predictions"]))]
-        return out
+        return self._nbest(self._copy_fields(ex), int(beam_size), "decode_nbest%d")
 
     def _text(self, ex, pred_ids, attns):
         """tens2sen with the rows' dictionaries (utils/misc.py:36-62) + replace_unknown"""
