@@ -12,7 +12,8 @@
 //       one lane ends up with i,f,g,o of its (unit, session)), x W_ih^T + h W_hh^T on v_mfma_f32_16x16x4_f32 with K split
 //       over the 4 waves, cell update in the same kernel -- no gate tensor, no separate cell kernel, no fill kernels
 //   1 session_attend2 (softmax over the t+1 previous states incl. the zero state, weighted sums, [q; sq; sd] rows)
-//   1 rank projection GEMM (W_q | W_shared + W_priv1 packed once per weight version), 1 feature kernel, 3 maxout GEMMs
+//   1 rank projection GEMM (W_q | W_shared + W_priv1 packed once per weight version), 3 maxout GEMMs (the first forms the pair features
+//   [q', d, |q' - d|, q' * d] while it stages its A operand: no feature tensor)
 #include "split2.hpp"
 #include <algorithm>
 #include <mutex>
@@ -25,6 +26,8 @@ int launch_linear(const float* a, int64_t lda, const int64_t* ids, const float* 
 int launch_linear_ex(const float* a, int64_t lda, const int64_t* ids, const float* table, int E, int64_t rows_per_seq,
                      int64_t seq_stride, const float* w, int64_t ldw, const float* bias, const float* bias2, float* c,
                      int64_t ldc, int64_t M, int N, int K, int act, const float* add, int64_t ldadd, hipStream_t st);
+int launch_linear_feats(const float* qp, const float* docs, int64_t ldd, int ncand, int D, const float* w, int64_t ldw, const float* bias,
+                        float* c, int64_t ldc, int64_t M, int N, int act, hipStream_t st);
 constexpr int ACT_MAXOUT2 = 16;
 constexpr int ACT_BOUNDED = 0x100;      // (gemm.hip) operands bounded by 2^15: the split-precision GEMM may use its fp16 two-term form
 constexpr int ACT_TANH_ROWDOT16 = 17;
@@ -636,21 +639,6 @@ __global__ void session_pack_kernel(const float* wq, const float* wshared, const
     }
 }
 
-// feats[(b,t,n)] = [q', d, |q'-d|, q'*d]   (cars.py:514-518); q' row = (b,t), d row = (b,t,n)
-__global__ void rank_feats_kernel(const float* qp, const float* docs, int N, int D, int64_t rows, float* feats) {
-    const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i < rows * D) {
-        const int64_t r = i / D;
-        const int f = (int)(i % D);
-        const float4 q = *reinterpret_cast<const float4*>(qp + (r / N) * D + f), d = *reinterpret_cast<const float4*>(docs + r * D + f);
-        float* o = feats + r * 4 * D + f;
-        *reinterpret_cast<float4*>(o) = q;
-        *reinterpret_cast<float4*>(o + D) = d;
-        *reinterpret_cast<float4*>(o + 2 * D) = make_float4(fabsf(q.x - d.x), fabsf(q.y - d.y), fabsf(q.z - d.z), fabsf(q.w - d.w));
-        *reinterpret_cast<float4*>(o + 3 * D) = make_float4(q.x * d.x, q.y * d.y, q.z * d.z, q.w * d.w);
-    }
-}
-
 // inner self-attention pools over the states produced so far (cars.py:385-388, 407-410), suggestion side only:
 // inner[b,t] = sum_{k=1..t+1} softmax_k(l_k) s_k,  l_k = sum of the NP epilogue partials of state row (k,b) + b3;
 // `states` and `lpart` both start at state 1
@@ -690,7 +678,7 @@ __global__ void session_cat_states_kernel(const float* a, const float* b2, int r
 }
 
 struct SessPlan {
-    float *epart, *clicks, *Qs, *Ds, *Cq, *Cd, *U, *xcat, *qp, *feats, *y0, *y1, *lin, *cat, *gx, *Qs16, *Ds16;
+    float *epart, *clicks, *Qs, *Ds, *Cq, *Cd, *U, *xcat, *qp, *y0, *y1, *lin, *cat, *gx, *Qs16, *Ds16;
     size_t bytes;
 };
 static SessPlan sess_plan(void* ws, size_t cap, int B, int S, int N, int D, int HS, int nch, bool rank_on, bool want_states) {
@@ -706,7 +694,6 @@ static SessPlan sess_plan(void* ws, size_t cap, int B, int S, int N, int D, int 
     p.U = a.take<float>(BS * (size_t)(nch * HS + nch + 4));
     p.xcat = a.take<float>(BS * (size_t)(D + nch * HS));
     p.qp = a.take<float>(BS * D);
-    p.feats = a.take<float>(rank_on ? R * 4 * D : 0);
     p.y0 = a.take<float>(rank_on ? R * 256 : 0);
     p.y1 = a.take<float>(rank_on ? R * 128 : 0);
     p.lin = a.take<float>(want_states ? (size_t)(S + 1) * B * (HS / 16) : 0);
@@ -937,14 +924,10 @@ extern "C" int nir_cars_rank_session_pre(const float* pooled_q, const float* poo
         const float* rdocs = rank_docs ? rank_docs : pooled_docs;
         const int Nr = rank_docs ? NR : N;
         const int64_t Rr = BS * Nr;
-        {
-            ProfScope ps("rank_feats_kernel", st);
-            hipLaunchKernelGGL(rank_feats_kernel, g1(Rr * D / 4), dim3(256), 0, st, p.qp, rdocs, Nr, D, Rr, p.feats);
-        }
-        NIR_CHECK_LAUNCH("rank_feats_kernel");
-        // maxout 1024 -> 256 -> 128 -> 1 (pool 2): the pairwise max is fused into the GEMM epilogues
-        NIR_PROPAGATE(launch_linear_ex(p.feats, 4 * D, nullptr, nullptr, 0, 0, 0, w->mo0_w, 4 * D, w->mo0_b, nullptr, p.y0, 256, Rr, 512, 4 * D,
-                                       ACT_MAXOUT2 | ((w->rank_bounded & 1) ? ACT_BOUNDED : 0), nullptr, 0, st));
+        // maxout 1024 -> 256 -> 128 -> 1 (pool 2): the pairwise max is fused into the GEMM epilogues; layer 0 reads its A rows
+        // [q', d, |q' - d|, q' * d] (cars.py:514-518; q' row = (b,t), d row = (b,t,n)) straight from p.qp and the documents
+        NIR_PROPAGATE(launch_linear_feats(p.qp, rdocs, D, Nr, D, w->mo0_w, 4 * D, w->mo0_b, p.y0, 256, Rr, 512,
+                                          ACT_MAXOUT2 | ((w->rank_bounded & 1) ? ACT_BOUNDED : 0), st));
         NIR_PROPAGATE(launch_linear_ex(p.y0, 256, nullptr, nullptr, 0, 0, 0, w->mo1_w, 256, w->mo1_b, nullptr, p.y1, 128, Rr, 256, 256,
                                        ACT_MAXOUT2 | ((w->rank_bounded & 2) ? ACT_BOUNDED : 0), nullptr, 0, st));
         NIR_PROPAGATE(launch_linear_ex(p.y1, 128, nullptr, nullptr, 0, 0, 0, w->mo2_w, 128, w->mo2_b, nullptr, click_scores, 1, Rr, 2, 128, ACT_MAXOUT2, nullptr, 0, st));

@@ -74,7 +74,7 @@ int batches_in_flight(hipStream_t st);
 // NIR_LSTM_S, NIR_DEBUG, NIR_EXACT_F32); nir_debug_set_tunable changes one at run time (tests, profilers).  Hot entry points only do
 // relaxed atomic loads.
 struct Tunables {
-    std::atomic<int> no_fork, lstm_mfma16, lstm_s, debug, exact_f32, duet_unfused, attn_unfused, attn_unfused_pipe, duet_rows64, attn_fp32_rows, attn_io_prio, cl_poll_limit;
+    std::atomic<int> no_fork, lstm_mfma16, lstm_s, debug, exact_f32, duet_unfused, attn_unfused, attn_unfused_pipe, duet_rows64, attn_fp32_rows, attn_io_prio, cl_poll_limit, gemm3_wide;
 };
 extern Tunables g_tun;
 inline int tun(const std::atomic<int>& a) { return a.load(std::memory_order_relaxed); }

@@ -164,7 +164,7 @@ extern "C" int nir_debug_set_tunable(const char* name, int value) {
         {"no_fork", &g_tun.no_fork}, {"lstm_mfma16", &g_tun.lstm_mfma16}, {"lstm_s", &g_tun.lstm_s}, {"debug", &g_tun.debug},
         {"exact_f32", &g_tun.exact_f32}, {"duet_unfused", &g_tun.duet_unfused}, {"attn_unfused", &g_tun.attn_unfused},
         {"attn_unfused_pipe", &g_tun.attn_unfused_pipe}, {"duet_rows64", &g_tun.duet_rows64}, {"attn_fp32_rows", &g_tun.attn_fp32_rows},
-        {"attn_io_prio", &g_tun.attn_io_prio}, {"cl_poll_limit", &g_tun.cl_poll_limit}};
+        {"attn_io_prio", &g_tun.attn_io_prio}, {"cl_poll_limit", &g_tun.cl_poll_limit}, {"gemm3_wide", &g_tun.gemm3_wide}};
     for (auto& t : tab)
         if (!strcmp(t.n, name)) { t.a->store(value); return 0; }
     set_error("nir_debug_set_tunable: unknown tunable '%s'", name);

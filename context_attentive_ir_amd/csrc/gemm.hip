@@ -32,7 +32,26 @@ struct GemmArgs {
     int N, K, act;
     const float* add;    // optional addend [M, ldadd] added before the activation (e.g. precomputed x W_ih^T)
     int64_t ldadd;
+    // ranknet feature mode (featq != NULL; K = 4 E): A row m is never stored -- it is [q', d, |q' - d|, q' * d] (cars.py:514-518) formed while
+    // the operand is loaded, q' = featq[m / featN] (E floats), d = a[m] (row stride lda)
+    const float* featq = nullptr;
+    int featN = 0;
 };
+
+// one float4 of a feature-mode A row: quarter qt of the k axis selects q', d, |q' - d| or q' * d (E % 4 == 0: a float4 never straddles a quarter).
+// The product is an explicitly rounded fp32 multiply: the value must be the one a feature matrix in memory would hold, whatever the compiler
+// could contract it with further down (the split's x - h1).
+__device__ __forceinline__ int feat_quarter(int k, int D) { return k < 2 * D ? (k < D ? 0 : 1) : (k < 3 * D ? 2 : 3); }
+__device__ __forceinline__ float4 feat_mix(const float4& q, const float4& d, int qt) {
+    if (qt == 0) return q;
+    if (qt == 1) return d;
+    if (qt == 2) return make_float4(fabsf(q.x - d.x), fabsf(q.y - d.y), fabsf(q.z - d.z), fabsf(q.w - d.w));
+    return make_float4(__fmul_rn(q.x, d.x), __fmul_rn(q.y, d.y), __fmul_rn(q.z, d.z), __fmul_rn(q.w, d.w));
+}
+__device__ __forceinline__ float4 feat_load4(const float* qrow, const float* drow, int k, int D) {
+    const int qt = feat_quarter(k, D), f = k - qt * D;
+    return feat_mix(*reinterpret_cast<const float4*>(qrow + f), *reinterpret_cast<const float4*>(drow + f), qt);
+}
 
 constexpr int ACT_MAXOUT2 = 16;   // internal: out[m, n/2] = max(v[m,n], v[m,n+1])  (maxout pool 2, maxout.py:77-81)
 // internal: the attention MLP's second layer fused into the first one's epilogue (cars.py:671-691, Linear -> Tanh -> Linear(D,1)):
@@ -79,7 +98,7 @@ constexpr int LPT = BM * BK / 4 / 256;                        // float4 loads pe
 
 // Software pipeline: the global loads of tile t+1 (gathered embedding rows for the A operand) are issued before the
 // MFMAs of tile t and land in the other LDS buffer afterwards -- one barrier per tile.
-template <bool VEC>
+template <bool VEC, bool FEAT = false>
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* As = smem;                          // [2][BM][LDS_LD]
@@ -109,12 +128,14 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     const bool taps3 = p.ids && p.K > p.E && p.K <= 3 * p.E;
     const float* arow1[LPT];
     const float* arow2[LPT];
+    const float* qrow[LPT];
 #pragma unroll
     for (int i = 0; i < LPT; ++i) {
         int64_t m = m0 + lr + RPP * i;
         aval[i] = m < p.M;
-        arow[i] = arow1[i] = arow2[i] = nullptr;
+        arow[i] = arow1[i] = arow2[i] = qrow[i] = nullptr;
         aidx[i] = 0;
+        if (FEAT && aval[i]) qrow[i] = p.featq + (m / p.featN) * p.E;
         if (aval[i]) {
             if (p.ids) {
                 aidx[i] = (m / p.rows_per_seq) * p.seq_stride + (m % p.rows_per_seq);
@@ -153,7 +174,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
                         } else {
                             src = arow[i] + k;
                         }
-                        ra[i] = *reinterpret_cast<const float4*>(src);
+                        if (FEAT) ra[i] = feat_load4(qrow[i], arow[i], k, p.E);
+                        else ra[i] = *reinterpret_cast<const float4*>(src);
                     }
                     if (wval[i]) rw[i] = *reinterpret_cast<const float4*>(wrow[i] + k);
                 }
@@ -232,7 +254,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
 // most CUs idle and serialise K.  Here one workgroup owns ONE 16x16 output tile, its 4 waves split K, operands are
 // read straight from L2 as MFMA fragments (v_mfma_f32_16x16x4_f32; lane group g = lane>>4 takes k = 16q+4g..+3 for
 // both operands, one float4 per 4 MFMAs) and the 4 partial tiles are summed through LDS.
-template <bool VEC>
+template <bool VEC, bool FEAT = false>
 __global__ __launch_bounds__(256) void gemm16_kernel(GemmArgs p) {
     __shared__ float red[4][256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -259,19 +281,28 @@ __global__ __launch_bounds__(256) void gemm16_kernel(GemmArgs p) {
         // L2 round trip, 20 in a row at K = 1280.)  Unconditional loads from clamped addresses, masked afterwards.
         constexpr int CH = 4;
         const float* abase = p.a + (mval ? m : 0) * p.lda;
-        auto loadc = [&](int q0, float4 (&a4)[CH], float4 (&b4)[CH]) {
+        const float* qbase = FEAT ? p.featq + ((mval ? m : 0) / p.featN) * p.E : nullptr;
+        float4 q0s[FEAT ? CH : 1], q1s[FEAT ? CH : 1];     // feature mode: the raw q' values travel with the raw d values, mixed right before use
+        auto loadc = [&](int q0, float4 (&a4)[CH], float4 (&b4)[CH], float4* q4) {
 #pragma unroll
             for (int c = 0; c < CH; ++c) {
                 const int k = 16 * (q0 + 4 * c) + 4 * g;
                 const int kc = k < p.K ? k : 0;
-                a4[c] = *reinterpret_cast<const float4*>(abase + kc);
+                if (FEAT) {
+                    const int f = kc - feat_quarter(kc, p.E) * p.E;
+                    a4[c] = *reinterpret_cast<const float4*>(abase + f);
+                    q4[c] = *reinterpret_cast<const float4*>(qbase + f);
+                } else {
+                    a4[c] = *reinterpret_cast<const float4*>(abase + kc);
+                }
                 b4[c] = *reinterpret_cast<const float4*>(wrow + kc);
             }
         };
-        auto mmac = [&](int q0, float4 (&a4)[CH], float4 (&b4)[CH]) {
+        auto mmac = [&](int q0, float4 (&a4)[CH], float4 (&b4)[CH], const float4* q4) {
 #pragma unroll
             for (int c = 0; c < CH; ++c) {
                 const int k = 16 * (q0 + 4 * c) + 4 * g;
+                if (FEAT) a4[c] = feat_mix(q4[c], a4[c], feat_quarter(k < p.K ? k : 0, p.E));
                 const float ma = (mval && k < p.K) ? 1.f : 0.f, mb = (nval && k < p.K) ? 1.f : 0.f;
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[c].x * ma, b4[c].x * mb, acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[c].y * ma, b4[c].y * mb, acc, 0, 0, 0);
@@ -280,15 +311,15 @@ __global__ __launch_bounds__(256) void gemm16_kernel(GemmArgs p) {
             }
         };
         float4 a0[CH], b0[CH], a1[CH], b1[CH];
-        loadc(wave, a0, b0);
+        loadc(wave, a0, b0, q0s);
         for (int q0 = wave; q0 < nq; q0 += 8 * CH) {
-            loadc(q0 + 4 * CH, a1, b1);
+            loadc(q0 + 4 * CH, a1, b1, q1s);
             __builtin_amdgcn_sched_barrier(0);
-            mmac(q0, a0, b0);
+            mmac(q0, a0, b0, q0s);
             __builtin_amdgcn_sched_barrier(0);
-            loadc(q0 + 8 * CH, a0, b0);
+            loadc(q0 + 8 * CH, a0, b0, q0s);
             __builtin_amdgcn_sched_barrier(0);
-            mmac(q0 + 4 * CH, a1, b1);
+            mmac(q0 + 4 * CH, a1, b1, q1s);
             __builtin_amdgcn_sched_barrier(0);
         }
     } else
@@ -306,7 +337,8 @@ __global__ __launch_bounds__(256) void gemm16_kernel(GemmArgs p) {
                     } else {
                         src = arow + k;
                     }
-                    a4 = *reinterpret_cast<const float4*>(src);
+                    if (FEAT) a4 = feat_load4(p.featq + (m / p.featN) * p.E, arow, k, p.E);
+                    else a4 = *reinterpret_cast<const float4*>(src);
                 }
                 if (nval) b4 = *reinterpret_cast<const float4*>(wrow + k);
             }
@@ -358,7 +390,7 @@ __global__ __launch_bounds__(256) void gemm16_kernel(GemmArgs p) {
 // Mid-size path (hundreds to a few thousand rows: CARS' maxout layers over B*S*N candidate rows).  Same exact-fp32 arithmetic and K split
 // as gemm16_kernel, but a workgroup owns a 32x32 output block: a wave's two A and two W fragments of a k-group feed 16 MFMAs instead of
 // 4 (half the L2 bytes per flop, twice the MFMA work behind every load).  1120x512x1024: 43 -> 27 us.
-template <int RA>                                  // RA row tiles x 2 column tiles of 16x16 per workgroup (16 RA rows x 32 columns)
+template <int RA, bool FEAT = false>               // RA row tiles x 2 column tiles of 16x16 per workgroup (16 RA rows x 32 columns)
 __global__ __launch_bounds__(256) void gemm32_kernel(GemmArgs p) {
     __shared__ float red[4][2 * RA][256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -366,6 +398,7 @@ __global__ __launch_bounds__(256) void gemm32_kernel(GemmArgs p) {
     const int64_t mbase = (int64_t)blockIdx.x * (16 * RA);
     const int nbase = blockIdx.y * 32;
     const float* ar[RA];
+    const float* qr[RA];                           // feature mode: the q' row next to the d row
     const float* wr[2];
     float am[RA], wm[2];
 #pragma unroll
@@ -373,6 +406,7 @@ __global__ __launch_bounds__(256) void gemm32_kernel(GemmArgs p) {
         const int64_t m = mbase + 16 * h + i;
         am[h] = m < p.M ? 1.f : 0.f;
         ar[h] = p.a + (m < p.M ? m : p.M - 1) * p.lda + 4 * g;
+        qr[h] = FEAT ? p.featq + ((m < p.M ? m : p.M - 1) / p.featN) * p.E + 4 * g : nullptr;
     }
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -390,15 +424,30 @@ __global__ __launch_bounds__(256) void gemm32_kernel(GemmArgs p) {
     // unrolled by the compiler, and without the sched_barriers every load sinks next to its first use).  With one workgroup per CU
     // (the launcher picks RA for a single round) nothing else hides the L2 round trip of a k-group.  A k-group past the end re-reads
     // group 0 and is masked to zero.
-    auto loadk = [&](int q, float4 (&a4)[RA], float4 (&b4)[2], float& km) {
+    struct QRegs { float4 q[FEAT ? RA : 1]; int qt; };   // feature mode: raw q' values and the k-group's quarter, mixed right before use
+    auto loadk = [&](int q, float4 (&a4)[RA], float4 (&b4)[2], float& km, QRegs& Q) {
         km = q < nq ? 1.f : 0.f;
         const int qc = q < nq ? q : 0;
+        if (FEAT) {                                // a 16-wide k-group lies inside one quarter (E % 16 == 0)
+            Q.qt = feat_quarter(16 * qc, p.E);
+            const int f = 16 * qc - Q.qt * p.E;
 #pragma unroll
-        for (int h = 0; h < RA; ++h) a4[h] = *reinterpret_cast<const float4*>(ar[h] + 16 * qc);
+            for (int h = 0; h < RA; ++h) {
+                a4[h] = *reinterpret_cast<const float4*>(ar[h] + f);
+                Q.q[h] = *reinterpret_cast<const float4*>(qr[h] + f);
+            }
+        } else {
+#pragma unroll
+            for (int h = 0; h < RA; ++h) a4[h] = *reinterpret_cast<const float4*>(ar[h] + 16 * qc);
+        }
 #pragma unroll
         for (int h = 0; h < 2; ++h) b4[h] = *reinterpret_cast<const float4*>(wr[h] + 16 * qc);
     };
-    auto mma = [&](float4 (&a4)[RA], float4 (&b4)[2], float km) {
+    auto mma = [&](float4 (&a4)[RA], float4 (&b4)[2], float km, const QRegs& Q) {
+        if (FEAT) {
+#pragma unroll
+            for (int h = 0; h < RA; ++h) a4[h] = feat_mix(Q.q[h], a4[h], Q.qt);
+        }
 #pragma unroll
         for (int h = 0; h < RA; ++h) {             // rows / columns past the edge contribute zeros (clamped address, 0/1 mask)
             const float m = am[h] * km;
@@ -420,15 +469,16 @@ __global__ __launch_bounds__(256) void gemm32_kernel(GemmArgs p) {
     };
     float4 a0[RA], b0[2], a1[RA], b1[2];
     float k0, k1;
-    loadk(wave, a0, b0, k0);
+    QRegs Q0, Q1;
+    loadk(wave, a0, b0, k0, Q0);
     for (int q = wave; q < nq; q += 8) {
-        loadk(q + 4, a1, b1, k1);
+        loadk(q + 4, a1, b1, k1, Q1);
         __builtin_amdgcn_sched_barrier(0);
-        mma(a0, b0, k0);
+        mma(a0, b0, k0, Q0);
         __builtin_amdgcn_sched_barrier(0);
-        loadk(q + 8, a0, b0, k0);
+        loadk(q + 8, a0, b0, k0, Q0);
         __builtin_amdgcn_sched_barrier(0);
-        mma(a1, b1, k1);
+        mma(a1, b1, k1, Q1);
         __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
@@ -617,15 +667,24 @@ __device__ __forceinline__ void g3_split_store_h2(unsigned short* base, int row,
 // The mode is a template parameter and every load is unconditional (row pointers of out-of-range rows are clamped to a valid
 // row -- their products land in accumulator rows / columns the epilogue never stores), so the k-loop has no branches: a
 // predicated load would become its own basic block with a vmcnt(0) in front of it.  Only the K tail tile masks its operands.
+// MODE 3: ranknet features (GemmArgs::featq): the q' and d values of a k-stage are requested like any operand tile and mixed into
+// [q', d, |q' - d|, q' * d] when the tile is staged (a k-stage never straddles a quarter of K: E % (KS * 16) == 0, launcher).
 // KS: k-tiles of 16 per pipeline stage (one barrier and one prefetch per KS tiles)
-template <int MODE, bool H2, int KS = 1>
-__global__ __launch_bounds__(256, 2) void gemm3_kernel(GemmArgs p) {
+// NW: waves per workgroup.  4: 2 x 2 waves of 64 x 64, one wave per SIMD -- nothing covers a wave's waits unless a second workgroup shares
+// the CU.  8: 2 x 4 waves of 64(M) x 32(N), two waves per SIMD inside ONE workgroup, for launches too small to put two workgroups on a CU;
+// every thread stages one row instead of two.  The tile is split along M and N only: every accumulator element sees the same MFMA
+// sequence in both forms (bit-identical results).  2 x 4 and 4 x 2 read the same LDS bytes (6 fragment reads per 6 MFMAs) and are both
+// conflict-free; 2 x 4 keeps the A-side addressing of the 4-wave form.
+template <int MODE, bool H2, int KS = 1, int NW = 4>
+__global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void gemm3_kernel(GemmArgs p) {
     constexpr int NTERM = H2 ? 2 : 3;
+    constexpr int NR = 8 / NW;                         // rows of each operand tile staged per thread
+    constexpr int BT = 8 / NW;                         // 32-column accumulator tiles per wave (two 32-row tiles in either form)
     extern __shared__ __attribute__((aligned(16))) unsigned short smem3[];
     unsigned short* As = smem3;                        // [2 stages][KS tiles][NTERM terms][G3_PLANE]
     unsigned short* Ws = smem3 + 2 * KS * NTERM * G3_PLANE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
+    const int wm = NW == 4 ? wave >> 1 : wave >> 2, wn = NW == 4 ? wave & 1 : wave & 3;
     const int nb = (p.N + G3_BN - 1) / G3_BN;
     const int64_t mb = (p.M + G3_BM - 1) / G3_BM;
     const int64_t bid = blockIdx.x;
@@ -634,19 +693,22 @@ __global__ __launch_bounds__(256, 2) void gemm3_kernel(GemmArgs p) {
     if (mblk >= mb) return;
     const int64_t m0 = mblk * G3_BM;
     const int n0 = (int)(tq % nb) * G3_BN;
-    const int lr = tid >> 2, kq = tid & 3;             // thread loads rows lr and lr + 64, k = 4*kq .. +3 of the k-tile
+    const int lr = tid >> 2, kq = tid & 3;             // thread loads rows lr (and lr + 64 with 4 waves), k = 4*kq .. +3 of the k-tile
 
-    const float* arow[2];
-    const float* arow1[2];
-    const float* arow2[2];
-    const float* wrow[2];
+    const float* arow[NR];
+    const float* arow1[NR];
+    const float* arow2[NR];
+    const float* wrow[NR];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < NR; ++i) {
         int64_t m = m0 + lr + 64 * i;
         m = m < p.M ? m : p.M - 1;
         arow1[i] = arow2[i] = nullptr;
         if (MODE == 0) {
             arow[i] = p.a + m * p.lda;
+        } else if (MODE == 3) {
+            arow[i] = p.a + m * p.lda;
+            arow1[i] = p.featq + (m / p.featN) * p.E;
         } else {
             const int64_t ai = (m / p.rows_per_seq) * p.seq_stride + (m % p.rows_per_seq);
             arow[i] = p.table + p.ids[ai] * (int64_t)p.E;
@@ -662,22 +724,30 @@ __global__ __launch_bounds__(256, 2) void gemm3_kernel(GemmArgs p) {
     // Two register sets: the tile loaded in iteration kt is staged into LDS at the END of iteration kt + 1 (prefetch distance two k-stages).
     // Round 6: with one set (tile kt + 1 requested above the MFMAs of tile kt and staged right behind them) an iteration took ~4 000 cycles
     // against 768 of MFMA issue per wave -- the HBM / L2 round trip of the operand loads, not the matrix pipe, set the pace of every gemm3 launch
-    struct TileRegs { float4 a[KS][2], w[KS][2]; };
+    struct TileRegs { float4 a[KS][NR], w[KS][NR], q[MODE == 3 ? KS : 1][NR]; int qt; };   // q, qt: feature mode (raw q' values, the stage's quarter)
     TileRegs R0, R1;
     auto load_tile = [&](TileRegs& R, int k00, bool tail) {
+        if (MODE == 3) R.qt = feat_quarter(k00 < p.K ? k00 : p.K - 4, p.E);
 #pragma unroll
         for (int j = 0; j < KS; ++j) {
             int k = k00 + j * G3_BK + 4 * kq;
             const bool kv = k < p.K;
             k = kv ? k : p.K - 4;
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
+            for (int i = 0; i < NR; ++i) {
                 const float* src = arow[i];
                 if (MODE == 2) src = k < p.E ? arow[i] : (k < 2 * p.E ? arow1[i] : arow2[i]);
-                R.a[j][i] = *reinterpret_cast<const float4*>(src + k);
+                if (MODE == 3) {
+                    const int f = k - R.qt * p.E;
+                    R.a[j][i] = *reinterpret_cast<const float4*>(arow[i] + f);
+                    R.q[j][i] = *reinterpret_cast<const float4*>(arow1[i] + f);
+                } else {
+                    R.a[j][i] = *reinterpret_cast<const float4*>(src + k);
+                }
                 R.w[j][i] = *reinterpret_cast<const float4*>(wrow[i] + k);
                 if (tail && !kv) {
                     R.a[j][i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (MODE == 3) R.q[j][i] = make_float4(0.f, 0.f, 0.f, 0.f);
                     R.w[j][i] = make_float4(0.f, 0.f, 0.f, 0.f);
                 }
             }
@@ -687,24 +757,25 @@ __global__ __launch_bounds__(256, 2) void gemm3_kernel(GemmArgs p) {
 #pragma unroll
         for (int j = 0; j < KS; ++j)
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
+            for (int i = 0; i < NR; ++i) {
                 unsigned short* ad = As + (buf * KS + j) * NTERM * G3_PLANE;
                 unsigned short* wd = Ws + (buf * KS + j) * NTERM * G3_PLANE;
+                const float4 av = MODE == 3 ? feat_mix(R.q[j][i], R.a[j][i], R.qt) : R.a[j][i];
                 if (H2) {
-                    g3_split_store_h2(ad, lr + 64 * i, kq, R.a[j][i]);
+                    g3_split_store_h2(ad, lr + 64 * i, kq, av);
                     g3_split_store_h2(wd, lr + 64 * i, kq, R.w[j][i]);
                 } else {
-                    g3_split_store(ad, lr + 64 * i, kq, R.a[j][i]);
+                    g3_split_store(ad, lr + 64 * i, kq, av);
                     g3_split_store(wd, lr + 64 * i, kq, R.w[j][i]);
                 }
             }
     };
 
-    f32x16 acc[2][2], acx[H2 ? 2 : 1][H2 ? 2 : 1];     // acx: the 2^11-scaled cross terms of the fp16 split
+    f32x16 acc[2][BT], acx[H2 ? 2 : 1][H2 ? BT : 1];   // acx: the 2^11-scaled cross terms of the fp16 split
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int b = 0; b < 2; ++b)
+        for (int b = 0; b < BT; ++b)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 acc[a][b][r] = 0.0f;
@@ -720,45 +791,43 @@ __global__ __launch_bounds__(256, 2) void gemm3_kernel(GemmArgs p) {
     __syncthreads();
     // fragment address inside a plane: [k-half = lane >> 5][row][8]
     const int foff_a = (lane >> 5) * G3_HALF + (wm * 64 + (lane & 31)) * 8;
-    const int foff_w = (lane >> 5) * G3_HALF + (wn * 64 + (lane & 31)) * 8;
+    const int foff_w = (lane >> 5) * G3_HALF + (wn * 32 * BT + (lane & 31)) * 8;
     auto mma_tile = [&](int buf) {
 #pragma unroll
       for (int j = 0; j < KS; ++j) {
         const unsigned short* ab = As + (buf * KS + j) * NTERM * G3_PLANE + foff_a;
         const unsigned short* wb = Ws + (buf * KS + j) * NTERM * G3_PLANE + foff_w;
         if constexpr (H2) {
-            f16x8 af[2][2], wf[2][2];
+            f16x8 af[2][2], wf[BT][2];
 #pragma unroll
-            for (int t = 0; t < 2; ++t)
+            for (int t = 0; t < 2; ++t) {
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    af[i][t] = *reinterpret_cast<const f16x8*>(ab + t * G3_PLANE + i * 32 * 8);
-                    wf[i][t] = *reinterpret_cast<const f16x8*>(wb + t * G3_PLANE + i * 32 * 8);
-                }
+                for (int i = 0; i < 2; ++i) af[i][t] = *reinterpret_cast<const f16x8*>(ab + t * G3_PLANE + i * 32 * 8);
+#pragma unroll
+                for (int i = 0; i < BT; ++i) wf[i][t] = *reinterpret_cast<const f16x8*>(wb + t * G3_PLANE + i * 32 * 8);
+            }
+            // the accumulator tiles are interleaved inside each term so that consecutive MFMAs never depend on each other
 #define G3_H2(ACC, TA, TW)                                                                                       \
-            ACC[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][TA], wf[0][TW], ACC[0][0], 0, 0, 0);        \
-            ACC[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[0][TA], wf[1][TW], ACC[0][1], 0, 0, 0);        \
-            ACC[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1][TA], wf[0][TW], ACC[1][0], 0, 0, 0);        \
-            ACC[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[1][TA], wf[1][TW], ACC[1][1], 0, 0, 0);
+            _Pragma("unroll") for (int a = 0; a < 2; ++a)                                                        \
+                _Pragma("unroll") for (int b = 0; b < BT; ++b)                                                   \
+                    ACC[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[a][TA], wf[b][TW], ACC[a][b], 0, 0, 0);
             G3_H2(acx, 1, 0) G3_H2(acx, 0, 1) G3_H2(acc, 0, 0)
 #undef G3_H2
         } else {
-            bf16x8 af[2][3], wf[2][3];
+            bf16x8 af[2][3], wf[BT][3];
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    af[i][t] = *reinterpret_cast<const bf16x8*>(ab + t * G3_PLANE + i * 32 * 8);
-                    wf[i][t] = *reinterpret_cast<const bf16x8*>(wb + t * G3_PLANE + i * 32 * 8);
-                }
+                for (int i = 0; i < 2; ++i) af[i][t] = *reinterpret_cast<const bf16x8*>(ab + t * G3_PLANE + i * 32 * 8);
+#pragma unroll
+                for (int i = 0; i < BT; ++i) wf[i][t] = *reinterpret_cast<const bf16x8*>(wb + t * G3_PLANE + i * 32 * 8);
             }
-            // six cross terms, smallest first; the four accumulator tiles are interleaved inside each term so that consecutive
+            // six cross terms, smallest first; the accumulator tiles are interleaved inside each term so that consecutive
             // MFMAs never depend on each other
 #define G3_TERM(TA, TW)                                                                                          \
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][TA], wf[0][TW], acc[0][0], 0, 0, 0);       \
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[0][TA], wf[1][TW], acc[0][1], 0, 0, 0);       \
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][TA], wf[0][TW], acc[1][0], 0, 0, 0);       \
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[1][TA], wf[1][TW], acc[1][1], 0, 0, 0);
+            _Pragma("unroll") for (int a = 0; a < 2; ++a)                                                        \
+                _Pragma("unroll") for (int b = 0; b < BT; ++b)                                                   \
+                    acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][TA], wf[b][TW], acc[a][b], 0, 0, 0);
             G3_TERM(2, 0) G3_TERM(1, 1) G3_TERM(0, 2) G3_TERM(1, 0) G3_TERM(0, 1) G3_TERM(0, 0)
 #undef G3_TERM
         }
@@ -818,8 +887,8 @@ __global__ __launch_bounds__(256, 2) void gemm3_kernel(GemmArgs p) {
     }
     // epilogue: C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8*(r >> 2) + 4*(lane >> 5)
 #pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        const int n = n0 + wn * 64 + b * 32 + (lane & 31);
+    for (int b = 0; b < BT; ++b) {
+        const int n = n0 + wn * 32 * BT + b * 32 + (lane & 31);
         float bsum = 0.f;
         if (n < p.N) {
             if (p.bias) bsum += p.bias[n];
@@ -1085,18 +1154,34 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const float* x, int64_t ldx
     }
 }
 
-int launch_linear_ex(const float* a, int64_t lda, const int64_t* ids, const float* table, int E, int64_t rows_per_seq,
-                     int64_t seq_stride, const float* w, int64_t ldw, const float* bias, const float* bias2, float* c,
-                     int64_t ldc, int64_t M, int N, int K, int act, const float* add, int64_t ldadd, hipStream_t st) {
-    const bool bounded = (act & ACT_BOUNDED) != 0;
-    act &= ~ACT_BOUNDED;
+// launches of the split-precision kernels so far, [0] with four waves, [1] with eight (nir_debug_gemm3_launches: the profile label is the
+// same for both forms, tests tell them apart by these)
+static std::atomic<long long> g_gemm3_launches[2];
+
+static int device_cus() {
+    static const int ncu = [] {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+                   ? prop.multiProcessorCount : 256;
+    }();
+    return ncu;
+}
+
+// every dense / gathered / feature-mode GEMM: checks, path choice, launch.  p.act carries no ACT_BOUNDED here.
+static int launch_gemm(GemmArgs p, bool bounded, hipStream_t st) {
+    const float* a = p.a;
+    const int64_t lda = p.lda, ldw = p.ldw, M = p.M;
+    const int64_t* ids = p.ids;
+    const float *table = p.table, *w = p.w;
+    const int E = p.E, N = p.N, K = p.K, act = p.act;
+    const bool feat = p.featq != nullptr;
     NIR_REQUIRE(M >= 0 && N > 0 && K > 0, "linear: bad dims M=%lld N=%d K=%d", (long long)M, N, K);
-    NIR_REQUIRE(w && c, "linear: null weight/output");
-    NIR_REQUIRE(ids ? (table != nullptr && E > 0 && rows_per_seq > 0) : (a != nullptr), "linear: null A operand");
+    NIR_REQUIRE(w && p.c, "linear: null weight/output");
+    NIR_REQUIRE(ids ? (table != nullptr && E > 0 && p.rows_per_seq > 0) : (a != nullptr), "linear: null A operand");
     if (M == 0) return 0;
     NIR_REQUIRE(act != ACT_MAXOUT2 || (N % 2 == 0), "linear: maxout epilogue needs an even N");
-    NIR_REQUIRE(act != ACT_TANH_ROWDOT16 || (N % 16 == 0 && add != nullptr), "linear: tanh-rowdot epilogue needs N %% 16 == 0 and the weight row");
-    GemmArgs p{a, lda, ids, table, E, rows_per_seq, seq_stride, w, ldw, bias, bias2, c, ldc, M, N, K, act, add, ldadd};
+    NIR_REQUIRE(act != ACT_TANH_ROWDOT16 || (N % 16 == 0 && p.add != nullptr), "linear: tanh-rowdot epilogue needs N %% 16 == 0 and the weight row");
     bool vec = (K % 4 == 0) && (ldw % 4 == 0) && (((uintptr_t)w & 15) == 0);
     if (ids) vec = vec && (E % 4 == 0) && (((uintptr_t)table & 15) == 0);
     else vec = vec && (lda % 4 == 0) && (((uintptr_t)a & 15) == 0);
@@ -1107,13 +1192,37 @@ int launch_linear_ex(const float* a, int64_t lda, const int64_t* ids, const floa
     const bool exact_f32 = tun(g_tun.exact_f32) != 0;                    // force the f32-MFMA kernels everywhere
     const int64_t mb3 = (M + G3_BM - 1) / G3_BM;
     const int nb3 = (N + G3_BN - 1) / G3_BN;
-    const int mode3 = !ids ? 0 : (K <= E ? 1 : (K <= 3 * E ? 2 : -1));
+    const int mode3 = feat ? 3 : (!ids ? 0 : (K <= E ? 1 : (K <= 3 * E ? 2 : -1)));
+    // feature mode: every kernel below forms the A rows from float4 loads of q' and d inside one quarter of K
+    NIR_REQUIRE(!feat || (!ids && p.featN > 0 && E % 32 == 0 && K == 4 * E && vec && (((uintptr_t)p.featq & 15) == 0)),
+                "linear_feats: needs D %% 32 == 0, K == 4 D, 16-byte aligned operands and row strides that are multiples of 4");
     // (>= 96 workgroups of 128 x 128: below that the 64 x 64-tile fp32 kernel wins -- 4480 x 256 x 256, 70 of them, measured 6.9 us per call on
     // the fp16 two-term form against 5.2 us)
-    if (vec && !exact_f32 && mode3 >= 0 && N >= 96 && K >= 32 && mb3 * nb3 >= 96) {
+    // 8-wave form of the fp16 two-term kernel (dense and feature-mode launches): a launch that cannot put two workgroups on every CU gets its
+    // second wave per SIMD inside the workgroup.  Measured on the 256-CU part: 112 - 140 workgroups 26 - 29 % faster,
+    // 280 workgroups even (52.2 against 52.8 us: inside the noise), 2 240 within 3 % -- so the rule is "at most ONE workgroup per CU", where the
+    // tile is alone on its CU.  The fp16 feature mode has the 8-wave form only (with four waves its two raw operand sets do not fit 256
+    // registers); the bf16 three-term feature form (rank_bounded bit 0 clear) keeps four waves like every bf16 launch.  Debug tunable gemm3_wide: 0 by the rule; 1 / 2 send EVERY dense fp16 two-term problem to the
+    // 8-wave / 4-wave form, whatever its size (tests compare the two forms on shapes of a few tiles).
+    const int wide_sel = (bounded && vec && !exact_f32 && (mode3 == 0 || mode3 == 3)) ? tun(g_tun.gemm3_wide) : 0;
+    if (vec && !exact_f32 && mode3 >= 0 && ((N >= 96 && K >= 32 && mb3 * nb3 >= 96) || wide_sel != 0)) {
         // large GEMMs: fp32 accuracy from three-term bf16 splits on the bf16 matrix cores (2.65 x the f32 MFMA roof)
-        ProfScope ps(prof_shape_name(bounded ? (ids ? "gemm3h_kernel[gather]" : "gemm3h_kernel") : (ids ? "gemm3_kernel[gather]" : "gemm3_kernel"), M, N, K), st);
         dim3 grid((unsigned)(8 * nb3 * ((mb3 + 7) / 8)));
+        const bool wide = bounded && (mode3 == 3 || (mode3 == 0 && (wide_sel == 1 || (wide_sel == 0 && K >= 64 && mb3 * nb3 <= (int64_t)device_cus()))));
+        // (the label does not tell the 4- from the 8-wave form: the kernel's own name in a trace does)
+        const char* label = bounded ? (ids ? "gemm3h_kernel[gather]" : (feat ? "gemm3h_kernel[feats]" : "gemm3h_kernel"))
+                                    : (ids ? "gemm3_kernel[gather]" : (feat ? "gemm3_kernel[feats]" : "gemm3_kernel"));
+        ProfScope ps(prof_shape_name(label, M, N, K), st);
+        g_gemm3_launches[wide ? 1 : 0].fetch_add(1, std::memory_order_relaxed);
+        if (wide) {
+            // one k-tile per stage: the two operand sets in flight then fit the 128 registers at which two of these workgroups share a CU (114 /
+            // 128 VGPRs dense / feature mode, no scratch); with two k-tiles per stage (135 / 166) a 280-workgroup launch runs in two rounds: 69.6 us
+            constexpr size_t lds = (size_t)2 * 2 * 2 * G3_PLANE * 2;
+            if (mode3 == 0) hipLaunchKernelGGL((gemm3_kernel<0, true, 1, 8>), grid, dim3(512), lds, st, p);
+            else hipLaunchKernelGGL((gemm3_kernel<3, true, 1, 8>), grid, dim3(512), lds, st, p);
+            NIR_CHECK_LAUNCH("gemm3h w8");
+            return 0;
+        }
         // fp16 two-term form: two k-tiles per pipeline stage (one barrier and one prefetch per 32 of K; 66 KB of LDS: still two workgroups per CU):
         // 8 960 x 512 x 1 024 65.5 -> 57.4 us, the gather-GEMM 573 440 x 1 024 x 300 2.135 -> 2.096 ms
         if (bounded && K >= 64) {
@@ -1135,12 +1244,13 @@ int launch_linear_ex(const float* a, int64_t lda, const int64_t* ids, const floa
             constexpr size_t lds = (size_t)2 * 2 * 3 * G3_PLANE * 2;
             if (mode3 == 0) hipLaunchKernelGGL((gemm3_kernel<0, false>), grid, dim3(256), lds, st, p);
             else if (mode3 == 1) hipLaunchKernelGGL((gemm3_kernel<1, false>), grid, dim3(256), lds, st, p);
-            else hipLaunchKernelGGL((gemm3_kernel<2, false>), grid, dim3(256), lds, st, p);
+            else if (mode3 == 2) hipLaunchKernelGGL((gemm3_kernel<2, false>), grid, dim3(256), lds, st, p);
+            else hipLaunchKernelGGL((gemm3_kernel<3, false>), grid, dim3(256), lds, st, p);
         }
         NIR_CHECK_LAUNCH("nir_linear_f32[bf16x3]");
         return 0;
     }
-    if (N <= 64 && vec && M >= 4096 && (!ids || K <= E) && sk_lds <= 128 * 1024 && act != ACT_MAXOUT2 && act != ACT_TANH_ROWDOT16) {
+    if (N <= 64 && vec && !feat && M >= 4096 && (!ids || K <= E) && sk_lds <= 128 * 1024 && act != ACT_MAXOUT2 && act != ACT_TANH_ROWDOT16) {
         ProfScope ps(prof_shape_name(ids ? "gemm_skinny_kernel[gather]" : "gemm_skinny_kernel", M, N, K), st);
         if (skNT == 1) launch_skinny<1>(p, skG, sk_lds, st);
         else if (skNT == 2) launch_skinny<2>(p, skG, sk_lds, st);
@@ -1151,12 +1261,7 @@ int launch_linear_ex(const float* a, int64_t lda, const int64_t* ids, const floa
         ProfScope ps(prof_shape_name("gemm32_kernel", M, N, K), st);
         // rows per workgroup (16 RA) chosen for the fewest rounds of workgroups over the CUs times the work per workgroup: 1120 x 512 is
         // 288 workgroups of 64 rows (two rounds on 256 CUs, 28 us) but 224 of 80 rows (one round)
-        static const int ncu = [] {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                       ? prop.multiProcessorCount : 256;
-        }();
+        const int ncu = device_cus();
         const int64_t ncol = (N + 31) / 32;
         int best = 2;
         int64_t best_cost = INT64_MAX;
@@ -1166,18 +1271,23 @@ int launch_linear_ex(const float* a, int64_t lda, const int64_t* ids, const floa
             if (cost < best_cost) { best_cost = cost; best = ra; }
         }
         const dim3 grid((unsigned)((M + 16 * best - 1) / (16 * best)), (unsigned)ncol);
+#define G32(RA)                                                                            \
+        if (feat) hipLaunchKernelGGL((gemm32_kernel<RA, true>), grid, dim3(256), 0, st, p); \
+        else hipLaunchKernelGGL((gemm32_kernel<RA>), grid, dim3(256), 0, st, p);
         switch (best) {
-            case 2: hipLaunchKernelGGL(gemm32_kernel<2>, grid, dim3(256), 0, st, p); break;
-            case 3: hipLaunchKernelGGL(gemm32_kernel<3>, grid, dim3(256), 0, st, p); break;
-            case 4: hipLaunchKernelGGL(gemm32_kernel<4>, grid, dim3(256), 0, st, p); break;
-            case 5: hipLaunchKernelGGL(gemm32_kernel<5>, grid, dim3(256), 0, st, p); break;
-            default: hipLaunchKernelGGL(gemm32_kernel<6>, grid, dim3(256), 0, st, p); break;
+            case 2: G32(2) break;
+            case 3: G32(3) break;
+            case 4: G32(4) break;
+            case 5: G32(5) break;
+            default: G32(6) break;
         }
+#undef G32
     } else if (mb * nb < 160) {
         // too few 64x64 tiles to fill 256 CUs: one 16x16 tile per workgroup, K split over the waves
         ProfScope ps(prof_shape_name(ids ? "gemm16_kernel[gather]" : "gemm16_kernel", M, N, K), st);
         dim3 grid((unsigned)((M + 15) / 16), (unsigned)((N + 15) / 16));
-        if (vec) hipLaunchKernelGGL(gemm16_kernel<true>, grid, dim3(256), 0, st, p);
+        if (feat) hipLaunchKernelGGL((gemm16_kernel<true, true>), grid, dim3(256), 0, st, p);
+        else if (vec) hipLaunchKernelGGL(gemm16_kernel<true>, grid, dim3(256), 0, st, p);
         else hipLaunchKernelGGL(gemm16_kernel<false>, grid, dim3(256), 0, st, p);
     } else {
         ProfScope ps(prof_shape_name(ids ? "gemm_kernel[gather]" : "gemm_kernel", M, N, K), st);
@@ -1188,11 +1298,30 @@ int launch_linear_ex(const float* a, int64_t lda, const int64_t* ids, const floa
             (void)hipFuncSetAttribute((const void*)gemm_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         });
         dim3 grid((unsigned)(8 * nb * ((mb + 7) / 8)));
-        if (vec) hipLaunchKernelGGL(gemm_kernel<true>, grid, dim3(256), lds, st, p);
+        if (feat) hipLaunchKernelGGL((gemm_kernel<true, true>), grid, dim3(256), lds, st, p);
+        else if (vec) hipLaunchKernelGGL(gemm_kernel<true>, grid, dim3(256), lds, st, p);
         else hipLaunchKernelGGL(gemm_kernel<false>, grid, dim3(256), lds, st, p);
     }
     NIR_CHECK_LAUNCH("nir_linear_f32");
     return 0;
+}
+
+int launch_linear_ex(const float* a, int64_t lda, const int64_t* ids, const float* table, int E, int64_t rows_per_seq,
+                     int64_t seq_stride, const float* w, int64_t ldw, const float* bias, const float* bias2, float* c,
+                     int64_t ldc, int64_t M, int N, int K, int act, const float* add, int64_t ldadd, hipStream_t st) {
+    GemmArgs p{a, lda, ids, table, E, rows_per_seq, seq_stride, w, ldw, bias, bias2, c, ldc, M, N, K, act & ~ACT_BOUNDED, add, ldadd};
+    return launch_gemm(p, (act & ACT_BOUNDED) != 0, st);
+}
+
+// C = act([q', d, |q' - d|, q' * d] W^T + bias) without the feature tensor: row m pairs q' = qp[m / ncand] with d = docs[m] (row stride
+// ldd); w is [N, 4 D].  Same path choice, arithmetic and epilogues as launch_linear_ex on a materialised [M, 4 D] feature matrix.
+int launch_linear_feats(const float* qp, const float* docs, int64_t ldd, int ncand, int D, const float* w, int64_t ldw, const float* bias,
+                        float* c, int64_t ldc, int64_t M, int N, int act, hipStream_t st) {
+    NIR_REQUIRE(qp && docs && ncand > 0 && D > 0, "linear_feats: bad args");
+    GemmArgs p{docs, ldd, nullptr, nullptr, D, 0, 0, w, ldw, bias, nullptr, c, ldc, M, N, 4 * D, act & ~ACT_BOUNDED, nullptr, 0};
+    p.featq = qp;
+    p.featN = ncand;
+    return launch_gemm(p, (act & ACT_BOUNDED) != 0, st);
 }
 
 int launch_linear(const float* a, int64_t lda, const int64_t* ids, const float* table, int E, int64_t rows_per_seq,
@@ -1230,6 +1359,17 @@ extern "C" int nir_linear_ex_f32(const float* a, int64_t lda, const int64_t* ids
                                  int act, const float* add, int64_t ldadd, nir_stream_t stream) {
     return nir::launch_linear_ex(a, lda, ids, table, E, rows_per_seq, seq_stride, w, ldw, bias, bias2, c, ldc, M, N, K,
                                  act, add, ldadd, (hipStream_t)stream);
+}
+
+extern "C" int nir_linear_feats_f32(const float* qp, const float* docs, int64_t ldd, int ncand, int D, const float* w, int64_t ldw,
+                                    const float* bias, float* c, int64_t ldc, int64_t M, int N, int act, nir_stream_t stream) {
+    return nir::launch_linear_feats(qp, docs, ldd, ncand, D, w, ldw, bias, c, ldc, M, N, act, (hipStream_t)stream);
+}
+
+extern "C" int nir_debug_gemm3_launches(long long* four_wave, long long* eight_wave) {
+    if (four_wave) *four_wave = nir::g_gemm3_launches[0].load();
+    if (eight_wave) *eight_wave = nir::g_gemm3_launches[1].load();
+    return 0;
 }
 
 extern "C" int nir_rowdot_f32(const float* x, int64_t ldx, const float* w, const float* b, float* out, int64_t M,

@@ -140,6 +140,8 @@ SIGNATURES = {
     "nir_widen_ids_i32": (_i, [C.c_void_p, C.c_void_p, _l, c_st]),
     "nir_linear_f32": (_i, [c_fp, _l, c_ip, c_fp, _i, _l, _l, c_fp, _l, c_fp, c_fp, c_fp, _l, _l, _i, _i, _i, c_st]),
     "nir_linear_ex_f32": (_i, [c_fp, _l, c_ip, c_fp, _i, _l, _l, c_fp, _l, c_fp, c_fp, c_fp, _l, _l, _i, _i, _i, c_fp, _l, c_st]),
+    "nir_linear_feats_f32": (_i, [c_fp, c_fp, _l, _i, _i, c_fp, _l, c_fp, c_fp, _l, _l, _i, _i, c_st]),
+    "nir_debug_gemm3_launches": (_i, [C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
     "nir_rowdot_f32": (_i, [c_fp, _l, c_fp, c_fp, c_fp, _l, _i, _i, c_st]),
     "nir_attn_pool_workspace_bytes": (_z, [_l, _i, _i]),
     "nir_attn_pool_f32": (_i, [C.c_void_p, _i, C.POINTER(CarsEncoderWeights), c_ip, _l, _i, _i, _i, C.c_void_p, _z, c_fp, c_st]),

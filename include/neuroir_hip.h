@@ -174,6 +174,17 @@ int nir_linear_ex_f32(const float* a, int64_t lda, const int64_t* ids, const flo
                       const float* bias2, float* c, int64_t ldc, int64_t M, int N, int K, int act,
                       const float* add, int64_t ldadd, nir_stream_t stream);
 
+/* nir_linear_ex_f32 on the pair features of the CARS ranker without the feature matrix: A row m is [q', d, |q' - d|, q' * d] with
+ * q' = qp[(m / ncand) * D ..] and d = docs[m * ldd ..] (D floats each), formed in fp32 while the operand is loaded; w is [N, 4 D] (row
+ * stride ldw), K = 4 D.  Path choice, arithmetic and epilogues (act as above, no addend) are those of nir_linear_ex_f32 on the
+ * materialised [M, 4 D] matrix: results are bit-identical to it.  D % 32 == 0; qp, docs and w 16-byte aligned; ldd % 4 == 0, ldw % 4 == 0. */
+int nir_linear_feats_f32(const float* qp, const float* docs, int64_t ldd, int ncand, int D, const float* w, int64_t ldw,
+                         const float* bias, float* c, int64_t ldc, int64_t M, int N, int act, nir_stream_t stream);
+
+/* Debug: how many launches of the split-precision GEMM kernel (gemm3_kernel, any mode) this process has issued with four and with eight
+ * waves per workgroup (either pointer may be NULL).  The two forms share a profile label; tests tell them apart by these counters. */
+int nir_debug_gemm3_launches(long long* four_wave, long long* eight_wave);
+
 /* out[m] = act( sum_k x[m*ldx+k] * w[k] + b[0] )  -- Linear(K -> 1). */
 int nir_rowdot_f32(const float* x, int64_t ldx, const float* w, const float* b, float* out, int64_t M, int K,
                    int act, nir_stream_t stream);
